@@ -23,11 +23,22 @@ backward raster -> geometry backward.
 
 The timed region is K Trainer.step() calls between a barrier + torch.cuda.synchronize() on both sides, max over ranks.  Submission
 (`--pipeline-depth`, default 2): a step awaits the PREVIOUS step's completion ticket, so the host submits step k+1 while step k runs; every
-one of the K steps has finished when the clock stops.  The reference awaits inside every step (trainer.ts:639-645); that form is timed right
-after as `ms_per_step_awaiting_every_step` (and is what `--pipeline-depth 1` makes the headline).  After the timed region:
-an eager pass with hipEvents around every launch on the launch stream (per-kernel averages, roofline of the dominant kernel), at
-N = 1 a `sustained` leg (620 steps at the reference's densify defaults, crossing the first two densify events) and the
-`cpu_baseline` (the oracle's train step built -O3 -march=native on this box's host cores).  ONE JSON line on rank 0.
+one of the K steps has finished when the clock stops.  ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, ONE block of exactly K timed steps, the outputs of the last step
+(`--dump-outputs DIR`), the JSON line.  `--full` adds everything else the record carries, after the timed region: the K-step block repeated
+until `--min-seconds` have been timed (median block reported); the reference's await inside every step (trainer.ts:639-645) timed as
+`ms_per_step_awaiting_every_step` (what `--pipeline-depth 1` makes the headline); an eager pass with hipEvents around every launch on the
+launch stream (per-kernel averages, roofline of the dominant kernel); at N > 1 the exchange time and the single-GPU base of the same step; at
+N = 1 the `batched_step` leg, a `sustained` leg (620 steps at the reference's densify defaults, crossing the first two densify events, carried
+on to `full_run`) and the `cpu_baseline` (the oracle's train step built -O3 -march=native on this box's host cores).
+
+`--dump-outputs DIR` writes, right after the timed region, what the last timed step left to the caller of Trainer.step(), as float32:
+`gaussians.npy` (rows x 12: the trained fp16 Gaussian rows), `sh.npy` (rows x 48: their SH rows) and `image.npy` (pixels x 4: the rgba8
+render of the step's view).  Above SAMPLE_ROWS Gaussians or SAMPLE_PIXELS pixels, a fixed seeded sample of them is written.  The reference's
+densify schedule drives some Gaussians out of the fp16 range ("Non-finite Gaussians"): their NaN / +-infinity fields are written as
+0 in `gaussians.npy` / `sh.npy` and named in `gaussians_nonfinite.npy` / `sh_nonfinite.npy` (same shape: 0 finite, 1 NaN, 2 +inf, 3 -inf), so
+every array stays finite and comparable number for number.
 """
 from __future__ import annotations
 
@@ -218,7 +229,7 @@ def run_batched_step(dev, cfg, g, sh, tg, tsh, args, views_per_step: int = 8) ->
     for _ in range(2):
         t.step()
     t.warmupCommandBuffers()
-    el, _dev_ms, blocks = timed_blocks(t, dev, steps, args.min_seconds, 1, barrier=lambda: None)
+    el, _dev_ms, blocks, _ = timed_blocks(t, dev, steps, args.min_seconds, 1, barrier=lambda: None)
     out = dict(views_per_step=views_per_step, lanes=t._lanes, views_per_s=round(views_per_step * steps / el, 3), ms_per_step=round(el / steps * 1e3, 4), steps_per_block=steps,
                blocks=len(blocks), pipeline_depth=args.pipeline_depth, dataset_views=64,
                note="the per-rank step of BASELINE c4 on this one GPU: Adam on all N Gaussians, no exchange; the like-for-like base of an N > 1 line's value / N")
@@ -240,13 +251,20 @@ def parse_args(argv=None):
     ap.add_argument("--sustained-steps", type=int, default=620, help="N = 1: length of the densify-inclusive leg (0 = skip)")
     ap.add_argument("--full-run-steps", type=int, default=10_000, help="N = 1: the sustained leg goes on to this many iterations -- the reference's default training "
                     "length -- and reports the rate per window of 1 000 iterations (`full_run`; 0 = stop at --sustained-steps)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="the K-step block is repeated until this much time has been timed; the MEDIAN block is reported (0 = one block)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement besides the headline (repeated blocks, awaited leg, per-kernel pass and "
+                    "roofline, exchange time, batched / sustained / full-run legs, CPU baseline); a plain run times one block of --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument("--min-seconds", type=float, default=None, help="the K-step block is repeated until this much time has been timed; the MEDIAN block is reported "
+                    "(default: 1.0 with --full, else 0 = one block)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the eager per-kernel pass (roofline becomes null)")
     ap.add_argument("--no-batched-step", action="store_true", help="N = 1: skip the `batched_step` leg (the 8-views-per-step step of config c4 on this one GPU)")
     ap.add_argument("--no-single-gpu-base", action="store_true", help="N > 1: skip the like-for-like leg (the same batched step on rank 0 alone, no exchange)")
     ap.add_argument("--cpu-baseline-points", type=int, default=0, help="0 = full workload")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.min_seconds is None:
+        args.min_seconds = 1.0 if args.full else 0.0
+    return args
 
 
 def free_port() -> int:
@@ -359,7 +377,7 @@ def timed_blocks(trainer, dev, steps: int, min_seconds: float, world: int, barri
     number of blocks: the count is fixed from the first block's max-over-ranks time) and the MEDIAN block is the one reported, so a
     16 ms region on a shared box is not at the mercy of one noisy neighbour.  Every block starts from the same training state
     (TrainingSnapshot, restored outside the bracket): the blocks time the same K steps.  Returns (median block seconds, max over
-    ranks; device ms of that block; all block times)."""
+    ranks; device ms of that block; all block times; the exchange ms of that block when the trainer's `exchange_timing` is on, else 0)."""
     import torch
     from webdgs_amd import parallel
     if barrier is None:
@@ -378,7 +396,9 @@ def timed_blocks(trainer, dev, steps: int, min_seconds: float, world: int, barri
         ev1.record(dev.torch_stream)
         torch.cuda.synchronize()
         barrier()
-        return time.perf_counter() - t0, ev0.elapsed_time(ev1)
+        wall = time.perf_counter() - t0
+        # (read after the bracket: the exchange intervals of THIS block, so the reported block's exchange time lies inside its own time)
+        return wall, ev0.elapsed_time(ev1), trainer.exchangeMilliseconds() if trainer.exchange_timing else 0.0
 
     def max_over_ranks(values):
         if world <= 1 or not values:
@@ -389,19 +409,20 @@ def timed_blocks(trainer, dev, steps: int, min_seconds: float, world: int, barri
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return [float(x) for x in t.tolist()]
 
-    first, first_dev = one_block()
+    first, first_dev, first_ex = one_block()
     first = max_over_ranks([first])[0]
-    blocks, dev_ms = [first], [first_dev]
+    blocks, dev_ms, ex_ms = [first], [first_dev], [first_ex]
     n_more = 0 if min_seconds <= 0 else min(400, max(0, int(np.ceil(min_seconds / max(first, 1e-6))) - 1))
     for _ in range(n_more):
         snap.restore()
-        e, d = one_block()
+        e, d, x = one_block()
         blocks.append(e)
         dev_ms.append(d)
+        ex_ms.append(x)
     blocks = [first] + max_over_ranks(blocks[1:])
     order = sorted(range(len(blocks)), key=lambda i: blocks[i])
     mid = order[(len(order) - 1) // 2]
-    return blocks[mid], dev_ms[mid], blocks
+    return blocks[mid], dev_ms[mid], blocks, ex_ms[mid]
 
 
 def source_sha(kernel: str) -> str:
@@ -507,6 +528,39 @@ def build_roofline(dom: str, dur_ms: float, n: int, v: int, e: int, p_pix: int, 
     return roof
 
 
+SAMPLE_ROWS, SAMPLE_PIXELS = 1 << 15, 1 << 21  # dumped Gaussians / pixels at most: 49 MB of float32 (c3's 1080p image fits whole)
+
+
+def _sample(n: int, cap: int) -> np.ndarray:
+    """All of range(n), or a fixed seeded sorted sample of `cap` of them: the same indices from run to run and build to build."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+
+
+def _finite_split(a: np.ndarray) -> tuple:
+    """(a with its non-finite entries set to 0, a code of the same shape: 0 finite, 1 NaN, 2 +inf, 3 -inf), both float32."""
+    code = np.select([np.isnan(a), np.isposinf(a), np.isneginf(a)], [1, 2, 3], 0).astype(np.float32)
+    return np.where(code == 0, a, 0).astype(np.float32), code
+
+
+def dump_outputs(trainer, cfg, out_dir: str) -> None:
+    """What the last timed step left to the caller of Trainer.step(): the trained point cloud and the step's render (module docstring)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = trainer.getPointCount()
+    pc = trainer.pointCloud
+    rows = _sample(n, SAMPLE_ROWS)
+    g = pc.gaussian_3d_buffer.read(np.uint32).reshape(-1, 6)[:n][rows]
+    sh = pc.sh_buffer.read(np.uint32).reshape(-1, 24)[:n][rows]  # (the read brings deferred SH-DC rows up to date first)
+    img = trainer.rasterizer.getOutputTextureView().read(np.uint8, cfg.width * cfg.height * 4).reshape(-1, 4)
+    img = img[_sample(img.shape[0], SAMPLE_PIXELS)]
+    for name, words in (("gaussians", g), ("sh", sh)):
+        values, code = _finite_split(np.ascontiguousarray(words).view(np.float16).astype(np.float32))
+        np.save(os.path.join(out_dir, f"{name}.npy"), values)
+        np.save(os.path.join(out_dir, f"{name}_nonfinite.npy"), code)
+    np.save(os.path.join(out_dir, "image.npy"), img.astype(np.float32))
+
+
 def main() -> None:
     args = parse_args()
     if os.environ.get("WDGS_BENCH_SELFTEST") and "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -567,14 +621,15 @@ def main() -> None:
 
     # ---- timed region: recorded command buffers (HIP graphs), no per-kernel events.  Device time of the same region from two
     # events on the kernels' own stream (it is torch's current stream: ops.HipDevice).
-    trainer.exchange_timing = world > 1
-    elapsed, device_ms, blocks = timed_blocks(trainer, dev, args.steps, args.min_seconds, world)
-    #  the exchange events are read and switched off HERE, before the awaited leg below takes its own steps
-    exchange_ms = trainer.exchangeMilliseconds() / max(1, len(blocks)) if world > 1 else 0.0
+    trainer.exchange_timing = world > 1 and args.full
+    elapsed, device_ms, blocks, exchange_ms = timed_blocks(trainer, dev, args.steps, args.min_seconds, world)
+    if args.dump_outputs and rank == 0:  # (before any leg below takes steps of its own)
+        dump_outputs(trainer, cfg, args.dump_outputs)
+    #  the exchange events are switched off HERE, before the awaited leg below takes its own steps
     trainer.exchange_timing = False
     # the same K steps with the reference's own await inside every step (depth 1), for comparison; not the headline
     awaited_ms = None
-    if trainer.pipeline_depth > 1:
+    if args.full and trainer.pipeline_depth > 1:
         trainer.pipeline_depth = 1
         torch.cuda.synchronize()
         parallel.barrier()
@@ -585,7 +640,7 @@ def main() -> None:
         parallel.barrier()
         awaited_ms = (time.perf_counter() - t_a) / args.steps * 1e3
         trainer.pipeline_depth = args.pipeline_depth
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
         tt = torch.tensor([exchange_ms], dtype=torch.float64, device=dev.torch_device)
         with parallel.collective_stream(dev.torch_device):
@@ -595,7 +650,7 @@ def main() -> None:
     # ---- per-kernel durations: the same K steps again, launched eagerly with a hipEvent pair around every kernel on the
     # launch stream (events cannot bracket single kernels inside a replayed graph).  Kernels, grids and data are identical.
     ktimes, eager_elapsed = {}, 0.0
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         trainer.use_command_buffers = False
         trainer._invalidate_command_buffers()
         trainer.step()
@@ -618,7 +673,7 @@ def main() -> None:
     k_coef = (cfg.sh_deg + 1) ** 2
     key_bits = 16 + max(1, tiles).bit_length()
     passes = (key_bits + 7) // 8
-    pairs = int(trainer.rasterizer.getNContribTextureView().read(np.uint32).astype(np.uint64).sum())
+    pairs = int(trainer.rasterizer.getNContribTextureView().read(np.uint32).astype(np.uint64).sum()) if args.full else None
     views_per_step = world * vpr
 
     # ---- roofline for the dominant kernel (group sort_* / scan_* launches into their stage); durations are PER VIEW
@@ -651,7 +706,7 @@ def main() -> None:
     # buffers, pipeline depth) on rank 0's GPU alone, without the exchange (the other ranks wait at the barrier).  The N = 1 bench line
     # is the reference's one-view step, which is a different (slower per view) step: dividing by it would flatter the curve.
     same_step = None
-    if world > 1 and not args.no_single_gpu_base:
+    if world > 1 and args.full and not args.no_single_gpu_base:
         trainer.use_command_buffers = True
         parallel.barrier()
         if rank == 0:
@@ -665,14 +720,14 @@ def main() -> None:
             for _ in range(args.warmup):
                 solo.step()
             solo.warmupCommandBuffers()
-            s_el, s_dev, s_blocks = timed_blocks(solo, dev, args.steps, args.min_seconds, 1, barrier=lambda: None)
+            s_el, s_dev, s_blocks, _ = timed_blocks(solo, dev, args.steps, args.min_seconds, 1, barrier=lambda: None)
             same_step = dict(views_per_s=round(vpr * args.steps / s_el, 3), ms_per_step=round(s_el / args.steps * 1e3, 4), views_per_step=vpr, lanes=solo._lanes,
                              blocks=len(s_blocks), note="rank 0's GPU alone: same views per rank, lanes, command buffers and pipeline depth; Adam on all N Gaussians, no exchange")
             solo.destroy()
         parallel.barrier()
 
     sustained = cpu_baseline = batched = full_run = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         trainer.destroy()
         if vpr == 1 and not args.no_batched_step and args.config in ("c3", "c3-small", "c2"):
             batched = run_batched_step(dev, cfg, g, sh, tg, tsh, args)
@@ -684,11 +739,11 @@ def main() -> None:
 
     if rank == 0:
         exch = None
-        if world > 1:
+        if world > 1 and args.full:
             sl = parallel.slice_points(n, world)
             exch = dict(transport=trainer.exchange.name, ms_per_step=round(exchange_ms / args.steps, 4), frac_of_step=round(exchange_ms / args.steps / ms_per_step, 4),
                         bytes_sent_per_rank_per_step=int((world - 1) * sl * (60 + 32)),
-                        note="device time between the events that bracket the two collectives of a step in the timed region (waiting for the slowest rank included)")
+                        note="device time between the events that bracket the two collectives of a step in the reported block (waiting for the slowest rank included)")
         out = {
             "metric": "training iters/sec (fwd+bwd+Adam), 1M Gaussians @1080p SH3" if args.config == "c3" else f"training iters/sec (fwd+bwd+Adam), {cfg.name}",
             "value": round(value, 3), "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -698,7 +753,7 @@ def main() -> None:
             "ms_per_step_awaiting_every_step": round(awaited_ms, 4) if awaited_ms is not None else None,
             "eager_profiled_ms_per_step": round(eager_elapsed / args.steps * 1e3, 4) if ktimes else None,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "head": head_commit(),
-            "n_ranks_seen": n_ranks_seen, "self_launched": os.environ.get("WDGS_BENCH_SELF_LAUNCHED") == "1",
+            "n_ranks_seen": n_ranks_seen, "self_launched": os.environ.get("WDGS_BENCH_SELF_LAUNCHED") == "1", "full": args.full,
             "single_gpu_same_step": same_step,
             "scaling_efficiency": round(value / (world * same_step["views_per_s"]), 4) if same_step else None,
             # BASELINE c3 as written ("full train loop with densify/prune schedule"): the densify-inclusive rate of the `sustained` leg

