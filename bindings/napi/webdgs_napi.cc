@@ -388,6 +388,12 @@ static napi_value imageSSE(napi_env env, napi_callback_info info) {  // (device,
     WDGS_OK_OR_THROW(wdgs_image_sse_rgb8((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_u32(env, argv[3]), get_ptr(env, argv[4])));
     return js_undefined(env);
 }
+static napi_value imageSSIM(napi_env env, napi_callback_info info) {  // (device, aPtr, bPtr, width, height, outF64Ptr, mapF32Ptr | null)
+    ARGS(7);
+    WDGS_OK_OR_THROW(wdgs_image_ssim_rgb8((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_u32(env, argv[3]), get_u32(env, argv[4]),
+                                          get_ptr(env, argv[5]), get_ptr(env, argv[6])));
+    return js_undefined(env);
+}
 
 static bool read_state(napi_env env, napi_value o, wdgs_optimizer_state* s) {
     napi_valuetype t; napi_typeof(env, o, &t);
@@ -852,7 +858,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(optimizerCreate); EXPORT_FN(optimizerStep); EXPORT_FN(optimizerGetIteration); EXPORT_FN(optimizerDestroy);
     EXPORT_FN(tiledForwardSet); EXPORT_FN(tiledForwardCheck); EXPORT_FN(tiledForwardSetLongLists); EXPORT_FN(tiledForwardLongListStats); EXPORT_FN(tiledRasterizerBlit); EXPORT_FN(bufferClear);
     EXPORT_FN(encoderBegin); EXPORT_FN(encoderFinish); EXPORT_FN(queueSubmit); EXPORT_FN(commandBufferDestroy); EXPORT_FN(queueOnSubmittedWorkDone);
-    EXPORT_FN(tiledBackwardMetric); EXPORT_FN(tiledBackwardGet); EXPORT_FN(downsampleRGBA8); EXPORT_FN(imageSSE);
+    EXPORT_FN(tiledBackwardMetric); EXPORT_FN(tiledBackwardGet); EXPORT_FN(downsampleRGBA8); EXPORT_FN(imageSSE); EXPORT_FN(imageSSIM);
     EXPORT_FN(optimizerStateSizes); EXPORT_FN(optimizerCreateWithState); EXPORT_FN(optimizerState); EXPORT_FN(optimizerHyperparameters);
     EXPORT_FN(optimizerAdvanceIteration); EXPORT_FN(optimizerStepF32); EXPORT_FN(accumulateGradients);
     EXPORT_FN(densifyCreate); EXPORT_FN(densifySetConfig); EXPORT_FN(densifyEncodePrepare); EXPORT_FN(densifyReadTotal); EXPORT_FN(densifyEncodeScatter);

@@ -25,4 +25,6 @@ export function loadColmapCamerasBin(data: Bytes): CameraData[];
 export function mergeColmap(images: CameraData[], cameras: CameraData[]): CameraData[];
 export function loadCamera(fileOrFiles: { name?: string; data: Bytes } | { name?: string; data: Bytes }[]): CameraData[];
 export function cameraUniforms(cam: Partial<CameraData>, width?: number, height?: number): Float32Array;
+/** Train / test split, every `every`-th view (index % every === 0) to test: [trainCams, trainImgs, testCams, testImgs]. */
+export function holdoutSplit<C, I>(cameras: C[], images: I[], every?: number): [C[], I[], C[], I[]];
 export function fromQuat(qx: number, qy: number, qz: number, qw: number): Float32Array;

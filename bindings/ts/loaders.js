@@ -301,5 +301,14 @@ function cameraUniforms(cam, width, height) {
   return uniformBlock(rot, pos, fovX, fovY, w, h, focal);
 }
 
-module.exports = { C0, f16Bits, f16ToNumber, decodeHeader, readRawVertex, nShCoeffs, loadPly, loadColmapBin, loadPointCloud, exportPly, loadCameraJson, loadColmapImagesBin,
+/** Train / test split by the Mip-NeRF 360 / 3DGS --eval convention: view i is a test view when i % every === 0.  Returns
+ *  [trainCams, trainImgs, testCams, testImgs], order kept (Trainer.setDataset takes the first pair, Trainer.setEvaluationViews the second). */
+function holdoutSplit(cameras, images, every = 8) {
+  if (cameras.length !== images.length) throw new Error(`holdoutSplit: ${cameras.length} cameras, ${images.length} images`);
+  if (!(every >= 1)) throw new Error(`holdoutSplit: every = ${every}`);
+  const test = (i) => i % every === 0;
+  return [cameras.filter((_, i) => !test(i)), images.filter((_, i) => !test(i)), cameras.filter((_, i) => test(i)), images.filter((_, i) => test(i))];
+}
+
+module.exports = { holdoutSplit, C0, f16Bits, f16ToNumber, decodeHeader, readRawVertex, nShCoeffs, loadPly, loadColmapBin, loadPointCloud, exportPly, loadCameraJson, loadColmapImagesBin,
   loadColmapCamerasBin, mergeColmap, loadCamera, cameraUniforms, fromQuat };

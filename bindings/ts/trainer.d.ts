@@ -62,6 +62,13 @@ export class Trainer {
   requestResizeTo(numPoints: number): void;
   applyPointCloudSwap(request: PointCloudSwapRequest): void;
   setDataset(cameras: (TrainingView | CameraData)[], images: (TrainingImage | LoadedImage)[]): void;
+  /** Views to evaluate on and never to train on (loaders.holdoutSplit); same shapes as setDataset, any image size. */
+  setEvaluationViews(cameras: (TrainingView | CameraData)[], images: (TrainingImage | LoadedImage)[]): void;
+  /** PSNR (exact SSE kernel) and SSIM (imageSSIM) of the current model on the evaluation views ('eval') or training views ('train'); drains the
+   *  pipeline, leaves the training trajectory untouched. */
+  evaluate(viewIds?: number[] | null, split?: 'eval' | 'train'): EvaluationResult;
+  /** Tile-entry lists of evaluate's own passes (0: what the training passes get); an overflowing view grows them and is rendered again. */
+  evalMaxTileEntries: number;
   getTrainingConfig(): TrainingConfig; setTrainingConfig(next: Partial<TrainingConfig>): void;
   getOptimizerHyperparameters(): AdamHyperparameters; setOptimizerHyperparameters(next: Partial<AdamHyperparameters>): void;
   setDensifyPruneConfig(next: Partial<DensifyPruneTrainingConfig>): void;
@@ -71,6 +78,9 @@ export class Trainer {
   getLastDensifyPruneIteration(): number | null; getNextDensifyPruneIteration(): number | null;
   step(): Promise<void>;
   destroy(): void;
+}
+export interface EvaluationResult {
+  iteration: number; views: number[]; psnr: number[]; ssim: number[]; sse: number[]; mean_psnr: number; mean_ssim: number; ms: number;
 }
 export function cameraBlockFor(block: Float32Array, width: number, height: number): Float32Array;
 export function mat4Inverse(m: ArrayLike<number>): Float32Array;

@@ -82,6 +82,13 @@ class Trainer {
     this.lastDensifyPruneIteration = null; this.lastViewportWidth = 1; this.lastViewportHeight = 1; this.pendingPointCloudSwap = null;
     this.trainCameras = []; this.images = []; this.cameraBuffers = [];
     this.commandBuffers = new Map(); this.eagerSteps = 0;
+    // held-out evaluation (setEvaluationViews / evaluate): views never drawn for training, and render passes of evaluate's own, one
+    // [forwardPass, rasterizer] per image size, built on first use and following the cloud
+    this.evalCameras = []; this.evalImages = []; this.evalCameraBuffers = []; this.evalOwnedTextures = [];
+    this.evalSets = new Map();
+    this.evalMaxTileEntries = 0;   // tile-entry lists of evaluate's passes (0: what the training passes get)
+    this.evalTileEntries = 0;      // (what an overflowing evaluation view has made of them)
+    this.evalLongLists = null;
   }
 
   densifyOpConfig() {
@@ -212,8 +219,9 @@ class Trainer {
   }
 
   /** A forward pass of this trainer: the deferred SH-DC source, and the long-list settings if any were given (this.longLists; null = the library's defaults). */
-  newForwardPass(cam, w, h) {
-    const fw = new hip.TiledForwardPass(this.device, this.pointCloud, cam, { viewportWidth: w, viewportHeight: h, renderMode: 'gaussian', maxTileEntries: this.tileEntries() });
+  newForwardPass(cam, w, h, maxTileEntries) {
+    const entries = maxTileEntries === undefined || maxTileEntries === null ? this.tileEntries() : maxTileEntries;
+    const fw = new hip.TiledForwardPass(this.device, this.pointCloud, cam, { viewportWidth: w, viewportHeight: h, renderMode: 'gaussian', maxTileEntries: entries });
     fw.setDcSource(this.dcWords);
     if (this.longLists) fw.setLongLists(this.longLists.threshold === undefined ? 2048 : this.longLists.threshold, this.longLists.maxItems || 0, this.longLists.maxRows || 0);
     return fw;
@@ -697,6 +705,116 @@ class Trainer {
     this.lastDensifyPruneIteration = this.iteration;
   }
 
+  // ---------------------------------------------------------------- held-out evaluation (no reference counterpart)
+  /** Views to evaluate on and never to train on (loaders.holdoutSplit gives the every-8th test views of the 3DGS convention).  Same shapes as
+   *  setDataset; the images may have another size than the training images. */
+  setEvaluationViews(cameras, images) {
+    if (cameras.length !== images.length) throw new Error(`setEvaluationViews: ${cameras.length} cameras, ${images.length} images`);
+    for (const b of this.evalCameraBuffers.concat(this.evalOwnedTextures)) b.destroy();
+    this.evalOwnedTextures = [];
+    const imgs = images.map((im) => {
+      if (im.texture) return im;
+      const tex = this.device.createBuffer({ size: 4 * im.width * im.height, label: 'eval image' });
+      this.device.queue.writeBuffer(tex, 0, im.bitmap);
+      this.evalOwnedTextures.push(tex);
+      return Object.assign({}, im, { texture: tex });
+    });
+    this.evalCameras = cameras.map((c, i) => (c.camera ? c : Object.assign({}, c, { camera: require('./loaders.js').cameraUniforms(c, imgs[i].width, imgs[i].height) })));
+    this.evalImages = imgs;
+    this.evalCameraBuffers = this.evalCameras.map((c) => {
+      const b = this.device.createBuffer({ size: 272, label: 'eval camera uniform' });
+      this.device.queue.writeBuffer(b, 0, c.camera);
+      return b;
+    });
+  }
+  destroyEvalSets() {
+    for (const [fw, rast] of this.evalSets.values()) { rast.destroy(); fw.destroy(); }
+    this.evalSets = new Map();
+  }
+  /** evaluate's [forwardPass, rasterizer] for one image size, built through newForwardPass (live SH-DC words, this trainer's long-list settings).  Never a guard. */
+  evalSet(w, h, cam) {
+    const key = `${w}x${h}`;
+    if (!this.evalSets.has(key)) {
+      const fw = this.newForwardPass(cam, w, h, this.evalTileEntries || this.evalMaxTileEntries || null);
+      this.evalSets.set(key, [fw, new hip.TiledRasterizer({ device: this.device, forwardPass: fw, format: 'rgba8unorm' })]);
+    }
+    return this.evalSets.get(key);
+  }
+  evalFollowCloud() {
+    if (JSON.stringify(this.evalLongLists) !== JSON.stringify(this.longLists)) {
+      this.destroyEvalSets();
+      this.evalLongLists = this.longLists ? Object.assign({}, this.longLists) : null;
+    }
+    for (const [fw] of this.evalSets.values()) {
+      if (fw.pointCloud !== this.pointCloud && !fw.setPointCloud(this.pointCloud)) { this.destroyEvalSets(); break; }
+    }
+    for (const [fw] of this.evalSets.values()) fw.setDcSource(this.dcWords);
+  }
+  /** Waits for the evaluation renders; the entries the largest overflowing one needed, or null (Trainer.py _eval_overflow). */
+  evalOverflow() {
+    const own = [...this.evalSets.values()].map(([fw]) => BigInt(fw.handle));
+    let err = null;
+    try {
+      this.device.synchronize();
+      if (this.device.capacityReports.pending.length) err = this.device.capacityReports.take(own);
+    } catch (e) {
+      if (!(e && e.code === 'WDGS_E_CAPACITY')) throw e;
+      err = e;
+    }
+    if (!err) return null;
+    const named = [], re = /(\d+) entries needed, max_tile_entries = \d+ \(forward pass (0x[0-9a-fA-F]+)\)/g, text = String(err.message);
+    for (let m = re.exec(text); m; m = re.exec(text)) named.push([Number(m[1]), BigInt(m[2])]);
+    const mine = named.filter((n) => own.some((h) => h === n[1])).map((n) => n[0]);
+    const all = hip.CapacityReports.passesNamed(err);
+    if (all.some((h) => !own.some((o) => o === h))) this.device.capacityReports.post(err);
+    if (!mine.length) { if (all.length) return null; throw err; }
+    return Math.max(...mine);
+  }
+  /** PSNR and SSIM of the current model on the evaluation views (split 'eval') or on training views (split 'train'): { iteration, views, psnr, ssim,
+   *  sse, mean_psnr, mean_ssim, ms }.  Drains the pipeline, renders every view through passes of its own, writes view i's SSE and SSIM into slot i
+   *  of two device arrays and reads them back once; a view that overflowed its tile-entry lists is rendered again with larger lists.  Training is
+   *  untouched (no random draw, no training pass, no recording dropped).  Per rank, no collective.  Same results as the Python host's. */
+  evaluate(viewIds, split) {
+    split = split || 'eval';
+    if (split !== 'eval' && split !== 'train') throw new Error(`evaluate: split must be 'eval' or 'train', not ${split}`);
+    if (!this.pointCloud) throw new Error('evaluate: no point cloud');
+    const t0 = Date.now();
+    const [cams, imgs, bufs] = split === 'eval' ? [this.evalCameras, this.evalImages, this.evalCameraBuffers] : [this.trainCameras, this.images, this.cameraBuffers];
+    const ids = viewIds === undefined || viewIds === null ? cams.map((_, i) => i) : viewIds.map((v) => Math.floor(v));
+    for (const v of ids) if (!(v >= 0 && v < cams.length)) throw new RangeError(`evaluate: view ${v} of ${cams.length} (${split})`);
+    try { this.drain(); } catch (e) { if (!this.growTileEntryCapacity(e)) throw e; }
+    const n = ids.length, slots = Math.max(1, n);
+    const out = this.device.createBuffer({ size: 16 * slots, label: 'evaluation sse + ssim' });
+    while (n) {
+      this.evalFollowCloud();
+      ids.forEach((v, i) => {
+        const im = imgs[v], w = im.width, h = im.height;
+        const [fw, rast] = this.evalSet(w, h, bufs[v]);
+        fw.setCameraBuffer(bufs[v]);
+        fw.encode(null);
+        rast.encode(null, w, h);
+        const pred = rast.getOutputTextureView();
+        hip.encodeImageSSE(this.device, pred, im.texture, w * h, this.device.view(out.ptr + BigInt(8 * i), 8));
+        hip.encodeImageSSIM(this.device, pred, im.texture, w, h, this.device.view(out.ptr + BigInt(8 * (slots + i)), 8));
+      });
+      const needed = this.evalOverflow();
+      if (needed === null) break;
+      const now = Math.max(this.evalTileEntries, ...[...this.evalSets.values()].map(([fw]) => Number(fw.getResources().maxTileEntries)));
+      const next = Math.min(Math.max(2 * now, Math.floor(needed * 1.5)), 0xFFFFF000);
+      if (next <= now) throw new Error(`evaluate: a view needs ${needed} tile entries, more than the lists can hold`);
+      console.warn(`evaluation tile-entry lists grown from ${now} to ${next} entries after an overflow; the views are rendered again`);
+      this.evalTileEntries = next;
+      this.destroyEvalSets();
+    }
+    const raw = n ? this.device.readBuffer(out, 16 * slots) : new ArrayBuffer(16);
+    out.destroy();
+    const sse = [...new BigUint64Array(raw, 0, n)].map(Number);
+    const ssim = [...new Float64Array(raw, 8 * slots, n)];
+    const psnr = ids.map((v, i) => hip.psnrFromSSE(sse[i], imgs[v].width * imgs[v].height));
+    const mean = (a) => (a.length ? a.reduce((x, y) => x + y, 0) / a.length : NaN);
+    return { iteration: this.iteration, views: ids, psnr, ssim, sse, mean_psnr: mean(psnr), mean_ssim: mean(ssim), ms: Date.now() - t0 };
+  }
+
   /** Deterministic teardown: command buffers, ops, the buffers this trainer allocated (the device and the exchange belong to the caller). */
   destroy() {
     if (this.device.handle !== null) {
@@ -711,8 +829,9 @@ class Trainer {
     }
     this.destroyMoreOpSets();
     this.destroyMoreMetricSets();
-    for (const b of this.cameraBuffers) b.destroy();
-    this.cameraBuffers = [];
+    this.destroyEvalSets();
+    for (const b of this.cameraBuffers.concat(this.evalCameraBuffers, this.evalOwnedTextures)) b.destroy();
+    this.cameraBuffers = []; this.evalCameraBuffers = []; this.evalOwnedTextures = [];
     for (const t of this.ownedTextures || []) t.destroy();
     this.ownedTextures = [];
     for (const name of ['dpGrad', 'dpVisible', 'dpRows', 'dpFlag', 'metricsTarget', 'agreeWord']) { if (this[name]) this[name].destroy(); this[name] = null; }

@@ -203,6 +203,10 @@ export function geometryViews(backwardPasses: TiledBackwardPass[], cameraBuffers
                               pointCloud: PointCloud, writeGradients?: boolean, continues?: boolean): void;
 export function imageSSE(device: HipDevice, a: HipBuffer, b: HipBuffer, numPixels: number): number;
 export function imagePSNR(device: HipDevice, a: HipBuffer, b: HipBuffer, numPixels: number): number;
+export function psnrFromSSE(sse: number | bigint, numPixels: number): number;
+export function encodeImageSSE(device: HipDevice, a: HipBuffer, b: HipBuffer, numPixels: number, out: HipBuffer): void;
+export function encodeImageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: number, height: number, out: HipBuffer, map?: HipBuffer | null): void;
+export function imageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: number, height: number, map?: HipBuffer | null): number;
 /** The C-ABI communicator (wdgs_comm_*): RCCL on the device's stream, for the data-parallel step of a host without torch.distributed. */
 export class Communicator {
   constructor(device: HipDevice, uniqueId: ArrayBuffer, worldSize: number, rank: number);

@@ -446,6 +446,24 @@ function imagePSNR(device, a, b, numPixels) {
   const sse = imageSSE(device, a, b, numPixels);
   return sse === 0 ? Infinity : 10 * Math.log10(255 * 255 * 3 * numPixels / sse);
 }
+/** PSNR in dB of an rgb8 sum of squared differences over numPixels pixels; Infinity for 0. */
+function psnrFromSSE(sse, numPixels) { return Number(sse) === 0 ? Infinity : 10 * Math.log10(255 * 255 * 3 * numPixels / Number(sse)); }
+/** Stream-ordered SSE: the u64 sum into the first 8 bytes of `out` (no host wait). */
+function encodeImageSSE(device, a, b, numPixels, out) { addon.imageSSE(device.handle, a.ptr, b.ptr, numPixels, out.ptr); }
+/** Stream-ordered SSIM (wdgs_image_ssim_rgb8): the f64 mean into the first 8 bytes of `out`, the per-pixel, per-channel map (W*H*3 f32) into `map`
+ *  when given.  No host wait. */
+function encodeImageSSIM(device, a, b, width, height, out, map) {
+  addon.imageSSIM(device.handle, a.ptr, b.ptr, width, height, out.ptr, map ? map.ptr : null);
+}
+/** SSIM of two rgba8 images over their rgb channels (11x11 Gaussian window, sigma 1.5, zero padding: the 3DGS convention); 1 when identical.
+ *  `map`: optional W*H*3 f32 buffer for the per-pixel, per-channel values.  Synchronises.  No reference counterpart. */
+function imageSSIM(device, a, b, width, height, map) {
+  const out = device.createBuffer({ size: 8 });
+  encodeImageSSIM(device, a, b, width, height, out, map);
+  const v = new Float64Array(device.readBuffer(out, 8))[0];
+  out.destroy();
+  return v;
+}
 
 /** The C-ABI communicator (wdgs_comm_*, include/webdgs.h): RCCL queued on the device's stream by the library itself -- the transport of the
  *  data-parallel step for a host without torch.distributed.  `uniqueId` (ArrayBuffer, 128 bytes) comes from Communicator.uniqueId() on rank 0 and
@@ -469,6 +487,6 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
+module.exports = { addon, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

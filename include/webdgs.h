@@ -330,6 +330,14 @@ int wdgs_downsample_rgba8(wdgs_device* dev, const void* src_dev, uint32_t src_w,
  * The reference has no scalar loss (it only visualises the gradient image, trainer.ts:695-768); PSNR = 10 log10(255^2 * 3P / SSE). */
 int wdgs_image_sse_rgb8(wdgs_device* dev, const void* a_rgba8_dev, const void* b_rgba8_dev, uint32_t num_pixels, void* out_u64_dev);
 
+/* SSIM of two rgba8 images (W x H, row-major, alpha ignored) -> *out_f64_dev (f64, device): the mean over 3 W H values of the per-pixel, per-channel
+ * map of Wang et al. as the 3DGS code base computes it -- values u8/255, 11x11 Gaussian window (sigma 1.5), zero padding, C1 = 0.01^2,
+ * C2 = 0.03^2.  map_f32_dev (nullable) receives the map, W*H*3 floats, map[(y*W + x)*3 + c].  Bit-reproducible on one device; identical
+ * images give exactly 1.  Stream-ordered, no host wait; may be recorded once a first call on the device (which allocates its fixed
+ * scratch) has run outside a recording.  No reference counterpart (held-out evaluation). */
+int wdgs_image_ssim_rgb8(wdgs_device* dev, const void* a_rgba8_dev, const void* b_rgba8_dev, uint32_t width, uint32_t height, void* out_f64_dev,
+                         void* map_f32_dev);
+
 /* Test hook, not part of the reference's surface: evaluates one pinned arithmetic primitive of the kernels elementwise over
  * `count` 32-bit patterns (0 exp, 1 log, 2 f32->f16 bits, 3 f16 bits->f32, 4 saturating f32->i32, 5 saturating f32->u32,
  * 6 sqrt, 7 1/x), so that a parity suite can compare them with its oracle directly. */

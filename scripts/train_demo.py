@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""End-to-end run of the Trainer on a synthetic scene: training steps with the reference's densify schedule, PSNR against the
-ground-truth views and the point count over time.
+"""End-to-end run of the Trainer on a synthetic scene: training steps with the reference's densify schedule, PSNR and SSIM against the
+ground-truth views (Trainer.evaluate) and the point count over time.
 
     python scripts/train_demo.py [config] [iterations] [views] [lr_scale] [report_every] [frozen_rates]   (default: c3 1200 8 1.0 100 ''; needs an MI355X)
 
@@ -57,18 +57,13 @@ def main():
         t.setOptimizerHyperparameters({k: (0.0 if k in frozen else v * lr_scale) for k, v in hp.items() if k.startswith("lr_")})
     t.start()
 
-    def psnr():
-        vals = []
-        for i in range(views):
-            t.forwardPass.setCameraBuffer(t._camera_buffers[i])
-            t.forwardPass.encode(None)
-            t.rasterizer.encode(None, cfg.width, cfg.height)
-            vals.append(ops.imagePSNR(dev, t.rasterizer.getOutputTextureView(), images[i]["texture"], cfg.width * cfg.height))
-        return float(np.mean(vals))
+    def quality():
+        r = t.evaluate(split="train")   # every training view, through the trainer's own evaluation passes
+        return f"PSNR {r['mean_psnr']:6.2f} dB  SSIM {r['mean_ssim']:.4f}"
 
     t.step()  # builds the pipelines
     print(f"{name}: {cfg.num_points} Gaussians, {cfg.width}x{cfg.height}, {views} views, lr x {lr_scale}, frozen {frozen}", flush=True)
-    print(f"iter {t.getIteration():5d}  points {t.getPointCount():8d}  PSNR {psnr():6.2f} dB", flush=True)
+    print(f"iter {t.getIteration():5d}  points {t.getPointCount():8d}  {quality()}", flush=True)
     t0, last = time.perf_counter(), 1
     while t.getIteration() < iters:
         t.step()
@@ -77,7 +72,7 @@ def main():
             dev.synchronize()
             dt = time.perf_counter() - t0
             st = t.forwardPass.check()
-            print(f"iter {it:5d}  points {t.getPointCount():8d}  PSNR {psnr():6.2f} dB  E {int(st[0]):9d}  {(it - last) / dt:7.1f} it/s"
+            print(f"iter {it:5d}  points {t.getPointCount():8d}  {quality()}  E {int(st[0]):9d}  {(it - last) / dt:7.1f} it/s"
                   f"  last densify {t.getLastDensifyPruneIteration()}", flush=True)
             t0, last = time.perf_counter(), it
 

@@ -466,6 +466,7 @@ int wdgs_device_destroy(wdgs_device* d) {
     for (hipEvent_t e : d->lane_marks) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->ticket_events) if (e) (void)hipEventDestroy(e);
     if (d->host_guard) (void)hipHostFree(d->host_guard);
+    if (d->ssim_partials) (void)hipFree(d->ssim_partials);
     for (int l = 1; l < WDGS_MAX_LANES; l++)
         if (d->lanes[l]) (void)hipStreamDestroy(d->lanes[l]);
     if (d->own_stream) (void)hipStreamDestroy(d->lanes[0]);

@@ -71,6 +71,9 @@ struct wdgs_device {
     // densify event drops one per training view; wdgs_queue_submit pays one off per call, behind its launch, where the device has work to do meanwhile
     std::vector<void*> dead_command_buffers;
     int num_cus = 256;
+    // SSIM partials (ssim.hip): one f64 per workgroup of the fixed grid, allocated at the first SSIM call and never reallocated
+    double* ssim_partials = nullptr;
+    u32 ssim_partials_count = 0;
 };
 
 // Host wait for everything submitted to the device, on either lane.
@@ -141,6 +144,9 @@ __device__ __forceinline__ u32 xcd_contiguous(u32 b, u32 g) {
 }
 
 static inline u32 ceil_div(u32 a, u32 b) { return (a + b - 1u) / b; }
+
+// SSIM (ssim.hip): workgroups per CU of its fixed grid
+constexpr u32 SSIM_WG_PER_CU = 2;
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
 int wdgs_alloc(void** p, size_t bytes, bool zero, hipStream_t stream);

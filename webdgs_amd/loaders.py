@@ -290,3 +290,19 @@ def cameraUniforms(cam: dict, width: Optional[int] = None, height: Optional[int]
     out[48:64] = synth.mat4_inverse(out[32:48])
     out[64:68] = (w, h, focal, focal)
     return out
+
+
+# ----------------------------------------------------------------------------- held-out split (no reference counterpart)
+def holdoutSplit(cameras: list, images: list, every: int = 8) -> tuple:
+    """Train / test split of a dataset by the Mip-NeRF 360 / 3DGS ``--eval`` convention: view ``i`` is a test view when ``i % every == 0``.
+    Returns ``(train_cams, train_imgs, test_cams, test_imgs)``, order kept; feed the first pair to ``Trainer.setDataset`` and the second to
+    ``Trainer.setEvaluationViews``."""
+    cameras, images = list(cameras), list(images)
+    if len(cameras) != len(images):
+        raise ValueError(f"holdoutSplit: {len(cameras)} cameras, {len(images)} images")
+    every = int(every)
+    if every < 1:
+        raise ValueError(f"holdoutSplit: every = {every}")
+    test = [i % every == 0 for i in range(len(cameras))]
+    return ([c for c, t in zip(cameras, test) if not t], [im for im, t in zip(images, test) if not t],
+            [c for c, t in zip(cameras, test) if t], [im for im, t in zip(images, test) if t])

@@ -675,6 +675,11 @@ def downsampleRGBA8(device: HipDevice, src: HipBuffer, src_w: int, src_h: int, d
     check(device.lib.wdgs_downsample_rgba8(device.handle, src.ptr, src_w, src_h, dst.ptr, dst_w, dst_h))
 
 
+def encodeImageSSE(device: HipDevice, a: HipBuffer, b: HipBuffer, num_pixels: int, out: HipBuffer) -> None:
+    """Stream-ordered ``imageSSE``: the u64 sum into the first 8 bytes of ``out``.  No host wait."""
+    check(device.lib.wdgs_image_sse_rgb8(device.handle, a.ptr, b.ptr, int(num_pixels), out.ptr))
+
+
 def imageSSE(device: HipDevice, a: HipBuffer, b: HipBuffer, num_pixels: int) -> int:
     """Exact sum of squared rgb8 differences of two rgba8 images (synchronises)."""
     out = device.createBuffer(8, "sse")
@@ -686,6 +691,28 @@ def imagePSNR(device: HipDevice, a: HipBuffer, b: HipBuffer, num_pixels: int) ->
     """PSNR in dB over the rgb channels of two rgba8 images; +inf when identical."""
     sse = imageSSE(device, a, b, num_pixels)
     return float("inf") if sse == 0 else 10.0 * float(np.log10(255.0 * 255.0 * 3.0 * num_pixels / sse))
+
+
+def psnrFromSSE(sse: int, num_pixels: int) -> float:
+    """PSNR in dB of an rgb8 sum of squared differences over ``num_pixels`` pixels; +inf for 0."""
+    return float("inf") if int(sse) == 0 else 10.0 * float(np.log10(255.0 * 255.0 * 3.0 * num_pixels / int(sse)))
+
+
+def encodeImageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: int, height: int, out: HipBuffer, map: Optional[HipBuffer] = None) -> None:
+    """Stream-ordered SSIM (``wdgs_image_ssim_rgb8``): the f64 mean into the first 8 bytes of ``out``, the per-pixel, per-channel map (W*H*3 f32,
+    ``map[(y*W + x)*3 + c]``) into ``map`` when given.  No host wait."""
+    n = int(width) * int(height)
+    if a.size < 4 * n or b.size < 4 * n or out.size < 8 or (map is not None and map.size < 12 * n):
+        raise ValueError(f"encodeImageSSIM: buffers too small for {width}x{height}")
+    check(device.lib.wdgs_image_ssim_rgb8(device.handle, a.ptr, b.ptr, int(width), int(height), out.ptr, map.ptr if map is not None else None))
+
+
+def imageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: int, height: int, map: Optional[HipBuffer] = None) -> float:
+    """SSIM of two rgba8 images over their rgb channels (11x11 Gaussian window, sigma 1.5, zero padding: the 3DGS convention); 1.0 when
+    identical.  ``map``: optional W*H*3 f32 buffer for the per-pixel, per-channel values.  Synchronises.  No reference counterpart."""
+    out = device.createBuffer(8, "ssim")
+    encodeImageSSIM(device, a, b, width, height, out, map)
+    return float(out.read(np.float64, count=1)[0])
 
 
 # ----------------------------------------------------------------------------- Optimizer

@@ -106,6 +106,15 @@ class Trainer:
         self.pendingPointCloudSwap: Optional[dict] = None
         self.trainCameras: list = []   # dicts: camera (float32[68]), width, height
         self.images: list = []         # dicts: texture (HipBuffer rgba8), width, height
+        # held-out evaluation (setEvaluationViews / evaluate): views never drawn for training, and render passes of evaluate's own, one
+        # (forward pass, rasterizer) per image size, built on first use and following the cloud
+        self.evalCameras: list = []
+        self.evalImages: list = []
+        self._eval_camera_buffers: list = []
+        self._eval_sets: dict = {}
+        self.evalMaxTileEntries = 0       # tile-entry lists of evaluate's passes (0: what the training passes get)
+        self._eval_tile_entries = 0       # (what an overflowing evaluation view has made of them)
+        self._eval_long_lists: Optional[dict] = None
 
         self.densifyPruneConfig = dict(  # trainer.ts:147-164
             schedule=dict(enabled=True, warmupIterations=500, interval=100, stopIterations=15_000),
@@ -227,15 +236,19 @@ class Trainer:
         ``CameraData`` dicts from ``loaders`` and ``images.LoadedImage`` objects (the camera block is then built for the image
         size as ``Camera.set_preset`` + ``update_buffer`` do, trainer.ts:583-586) -- or ready dicts carrying ``camera`` (68
         floats) and ``width/height/texture``."""
+        self.trainCameras, self.images = self._views(cameras, images)
+        # one resident 272-byte camera block per training view (the reference rewrites a single uniform buffer every step)
+        self._camera_buffers = [self.device.bufferFrom(np.asarray(c["camera"], np.float32)) for c in self.trainCameras]
+        self._invalidate_command_buffers()
+
+    def _views(self, cameras: list, images: list) -> tuple:
+        """(camera dicts with their 68-float block, image dicts with a device texture) from the shapes ``setDataset`` accepts."""
         cameras, images = list(cameras), list(images)
         images = [im if isinstance(im, dict) else dict(name=im.name, width=im.width, height=im.height,
                                                        texture=im.texture if im.texture is not None else self.device.bufferFrom(im.bitmap))
                   for im in images]
         cameras = [c if "camera" in c else dict(c, camera=loaders.cameraUniforms(c, im["width"], im["height"])) for c, im in zip(cameras, images)]
-        self.trainCameras, self.images = cameras, images
-        # one resident 272-byte camera block per training view (the reference rewrites a single uniform buffer every step)
-        self._camera_buffers = [self.device.bufferFrom(np.asarray(c["camera"], np.float32)) for c in self.trainCameras]
-        self._invalidate_command_buffers()
+        return cameras, images
 
     def getTrainingConfig(self) -> dict:
         return dict(self.trainingConfig)
@@ -318,8 +331,9 @@ class Trainer:
         return nxt if nxt <= stop else None
 
     # ------------------------------------------------------------------ pipelines
-    def _new_forward_pass(self, cameraBuffer, w: int, h: int) -> ops.TiledForwardPass:
-        fw = ops.TiledForwardPass(self.device, self.pointCloud, cameraBuffer, dict(viewportWidth=w, viewportHeight=h, renderMode="gaussian", maxTileEntries=self._tile_entries()))
+    def _new_forward_pass(self, cameraBuffer, w: int, h: int, maxTileEntries: Optional[int] = None) -> ops.TiledForwardPass:
+        entries = self._tile_entries() if maxTileEntries is None else int(maxTileEntries)
+        fw = ops.TiledForwardPass(self.device, self.pointCloud, cameraBuffer, dict(viewportWidth=w, viewportHeight=h, renderMode="gaussian", maxTileEntries=entries))
         fw.setDcSource(self._dc_words)
         if self.longLists is not None:   # (None: the library's defaults -- threshold 2048, room for 1024 chunk slots and 8192 rows)
             fw.setLongLists(int(self.longLists.get("threshold", 2048)), int(self.longLists.get("maxItems", 0)), int(self.longLists.get("maxRows", 0)))
@@ -855,10 +869,129 @@ class Trainer:
             setattr(self, name, None)
         self._destroy_more_op_sets()
         self._destroy_more_metric_sets()
+        self._destroy_eval_sets()
         self._dp_grad = self._dp_visible = self._dp_rows = self._dp_flag = self.metricsTarget = None
         self._camera_buffers = []
+        self._eval_camera_buffers = []
         self.pointCloud = None
         self.isTraining = False
+
+    # ------------------------------------------------------------------ held-out evaluation (no reference counterpart)
+    def setEvaluationViews(self, cameras: list, images: list) -> None:
+        """Views to evaluate on and never to train on (``loaders.holdoutSplit`` gives the every-8th test views of the 3DGS convention).  Same
+        shapes as ``setDataset``; the images may have another size than the training images."""
+        cameras, images = list(cameras), list(images)
+        if len(cameras) != len(images):
+            raise ValueError(f"setEvaluationViews: {len(cameras)} cameras, {len(images)} images")
+        self.evalCameras, self.evalImages = self._views(cameras, images)
+        self._eval_camera_buffers = [self.device.bufferFrom(np.asarray(c["camera"], np.float32)) for c in self.evalCameras]
+
+    def _destroy_eval_sets(self) -> None:
+        for fw, rast in self._eval_sets.values():
+            rast.destroy()
+            fw.destroy()
+        self._eval_sets = {}
+
+    def _eval_set(self, width: int, height: int, cameraBuffer) -> tuple:
+        """evaluate's (forward pass, rasterizer) for one image size: built through ``_new_forward_pass`` (the live SH-DC words, this trainer's
+        long-list settings), with lists of ``_eval_tile_entries`` if an evaluation view has outgrown the training passes' size.  Never a guard."""
+        key = (int(width), int(height))
+        if key not in self._eval_sets:
+            fw = self._new_forward_pass(cameraBuffer, key[0], key[1], self._eval_tile_entries or self.evalMaxTileEntries or None)
+            self._eval_sets[key] = (fw, ops.TiledRasterizer(dict(device=self.device, forwardPass=fw, format="rgba8unorm")))
+        return self._eval_sets[key]
+
+    def _eval_follow_cloud(self) -> None:
+        """Brings evaluate's passes to the current cloud (a swap after a densify event, another size) and the current long-list settings."""
+        if self._eval_long_lists != self.longLists:
+            self._destroy_eval_sets()
+            self._eval_long_lists = None if self.longLists is None else dict(self.longLists)
+        for fw, _ in list(self._eval_sets.values()):
+            if fw.pointCloud is not self.pointCloud and not fw.setPointCloud(self.pointCloud):
+                self._destroy_eval_sets()   # (another SH degree: built anew below)
+                break
+        for fw, _ in self._eval_sets.values():
+            fw.setDcSource(self._dc_words)
+
+    def _eval_overflow(self) -> Optional[int]:
+        """Waits for the evaluation renders; the entries the largest overflowing one needed, or None.  A report that also names passes of another
+        owner (a Viewer on this device) is left for that owner (ops.CapacityReports)."""
+        own = {int(fw.handle.value or 0) for fw, _ in self._eval_sets.values()}
+        try:
+            self.device.synchronize()
+            err = self.device.capacityReports.take(own) if self.device.capacityReports.pending else None
+        except ops.CapacityError as e:
+            err = e
+        if err is None:
+            return None
+        import re
+        named = re.findall(r"(\d+) entries needed, max_tile_entries = \d+ \(forward pass (0x[0-9a-fA-F]+)\)", str(err))
+        mine = [int(n) for n, h in named if int(h, 16) in own]
+        if ops.CapacityReports.passes_named(err) - own:
+            self.device.capacityReports.post(err)
+        if not mine:
+            if ops.CapacityReports.passes_named(err):
+                return None
+            raise err
+        return max(mine)
+
+    def evaluate(self, viewIds: Optional[list] = None, split: str = "eval") -> dict:
+        """PSNR and SSIM of the current model on the evaluation views (``split="eval"``, ``setEvaluationViews``) or on training views
+        (``split="train"``): ``dict(iteration, views, psnr=[...], ssim=[...], mean_psnr, mean_ssim, ms)``.  PSNR comes from the exact SSE kernel
+        (``inf`` for identical images); SSIM is ``ops.imageSSIM``'s; the means are means of the per-view values; ``ms`` the call's wall time.
+
+        Drains the pipeline, then renders every view through passes of its own and writes view i's SSE and SSIM into slot i of two device arrays,
+        read back once at the end.  A view whose tile-entry list overflowed is rendered again with larger lists -- never reported from a truncated
+        render.  Training is untouched: no RNG draw, no training pass, no recording dropped; a trainer that evaluates every few steps follows the
+        same trajectory as one that never does.  Per rank with ``world_size > 1`` (no collective)."""
+        import warnings
+        if split not in ("eval", "train"):
+            raise ValueError(f"evaluate: split must be 'eval' or 'train', not {split!r}")
+        if self.pointCloud is None:
+            raise RuntimeError("evaluate: no point cloud")
+        cams, imgs, bufs = ((self.evalCameras, self.evalImages, self._eval_camera_buffers) if split == "eval" else
+                            (self.trainCameras, self.images, self._camera_buffers))
+        ids = list(range(len(cams))) if viewIds is None else [int(v) for v in viewIds]
+        for v in ids:
+            if not 0 <= v < len(cams):
+                raise IndexError(f"evaluate: view {v} of {len(cams)} ({split})")
+        t0 = time.perf_counter()
+        try:
+            self.drain()
+        except ops.CapacityError as e:   # a training step's overflow, as step() would have met it at its next wait
+            if not self._grow_tile_entry_capacity(e):
+                raise
+        n = len(ids)
+        out = self.device.createBuffer(16 * max(1, n), "evaluation sse + ssim")
+        sse_at, ssim_at = out.ptr, out.ptr + 8 * max(1, n)
+        while n:
+            self._eval_follow_cloud()
+            for i, v in enumerate(ids):
+                im, w, h = imgs[v], int(imgs[v]["width"]), int(imgs[v]["height"])
+                fw, rast = self._eval_set(w, h, bufs[v])
+                fw.setCameraBuffer(bufs[v])
+                fw.encode(None)
+                rast.encode(None, w, h)
+                pred = rast.getOutputTextureView()
+                ops.encodeImageSSE(self.device, pred, im["texture"], w * h, self.device.view(sse_at + 8 * i, 8))
+                ops.encodeImageSSIM(self.device, pred, im["texture"], w, h, self.device.view(ssim_at + 8 * i, 8))
+            needed = self._eval_overflow()
+            if needed is None:
+                break
+            now = max([int(fw.getResources()["maxTileEntries"]) for fw, _ in self._eval_sets.values()] + [self._eval_tile_entries])
+            new = min(max(2 * now, int(needed * 1.5)), 0xFFFFF000)
+            if new <= now:
+                raise RuntimeError(f"evaluate: a view needs {needed} tile entries, more than the lists can hold")
+            warnings.warn(f"evaluation tile-entry lists grown from {now} to {new} entries after an overflow; the views are rendered again", RuntimeWarning, stacklevel=2)
+            self._eval_tile_entries = new
+            self._destroy_eval_sets()
+        sse = out.read(np.uint64, count=n) if n else np.zeros(0, np.uint64)
+        ssim = out.read(np.float64, count=n, offset=8 * max(1, n)) if n else np.zeros(0)
+        psnr = [ops.psnrFromSSE(int(sse[i]), int(imgs[v]["width"]) * int(imgs[v]["height"])) for i, v in enumerate(ids)]
+        ssim_l = [float(x) for x in ssim]
+        return dict(iteration=self.iteration, views=ids, psnr=psnr, ssim=ssim_l, sse=[int(x) for x in sse],
+                    mean_psnr=float(np.mean(psnr)) if n else float("nan"), mean_ssim=float(np.mean(ssim_l)) if n else float("nan"),
+                    ms=(time.perf_counter() - t0) * 1e3)
 
     # ------------------------------------------------------------------ densify / prune
     def runDensifyPruneMultiView(self) -> None:
