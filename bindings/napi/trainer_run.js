@@ -2,7 +2,7 @@
 // dataset written by tests/test_gpu_napi.py, with the view draws fixed by the test, and dumps the trained cloud and optimizer state
 // for a byte-for-byte comparison with the Python host's run of the same schedule.  meta.json selects the step's form: `views_per_step`
 // (a batched step), `lanes`, `pipeline_depth`, `comm` ('capi': the sliced exchange through the library's RCCL communicator in a world
-// of one), `keep_gradients`.  Also exercises get_prefix_scanner / get_dynamic_sorter and the pinned asynchronous read-back.
+// of one), `keep_gradients`, `training_config` (the Trainer's, e.g. { dssim_mode: 'gaussian' }).  Also exercises get_prefix_scanner / get_dynamic_sorter and the pinned asynchronous read-back.
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -31,7 +31,7 @@ async function main() {
   let drawn = 0;
   const random = () => { if (drawn >= draws.length) throw new Error('more view draws than the schedule holds'); return (draws[drawn++] + 0.5) / meta.views; };
   const exchange = meta.comm === 'capi' ? new parallel.CapiExchange(dev, hip.Communicator.uniqueId(), 1, 0) : new parallel.Exchange();
-  const t = new Trainer(dev, undefined, { random, viewsPerStep: meta.views_per_step || 1, lanes: meta.lanes || 0, pipelineDepth: meta.pipeline_depth || 1,
+  const t = new Trainer(dev, meta.training_config, { random, viewsPerStep: meta.views_per_step || 1, lanes: meta.lanes || 0, pipelineDepth: meta.pipeline_depth || 1,
     keepGradients: !!meta.keep_gradients, exchange });
   t.setDensifyPruneConfig(meta.densify);
   if (meta.long_lists) t.longLists = meta.long_lists;   // long tile lists (csrc/longlist.h) with the test's threshold and scratch sizes

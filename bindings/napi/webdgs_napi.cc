@@ -72,6 +72,23 @@ static void set_prop(napi_env env, napi_value obj, const char* name, napi_value 
     if (argc < n) { napi_throw_type_error(env, nullptr, "too few arguments"); return nullptr; }
 
 static napi_value js_undefined(napi_env env) { napi_value v; napi_get_undefined(env, &v); return v; }
+// trainingConfig.dssim_mode ('reference' | 'gaussian', absent = 'reference') -> WDGS_DSSIM_*; false (and a pending TypeError) for anything else
+static bool prop_dssim_mode(napi_env env, napi_value obj, uint32_t* mode) {
+    *mode = WDGS_DSSIM_REFERENCE;
+    bool has = false;
+    napi_has_named_property(env, obj, "dssim_mode", &has);
+    if (!has) return true;
+    napi_value v; napi_get_named_property(env, obj, "dssim_mode", &v);
+    napi_valuetype t; napi_typeof(env, v, &t);
+    if (t == napi_undefined || t == napi_null) return true;
+    char buf[16] = {0};
+    size_t len = 0;
+    if (t == napi_string) napi_get_value_string_utf8(env, v, buf, sizeof(buf), &len);
+    if (t == napi_string && std::strcmp(buf, "reference") == 0) return true;
+    if (t == napi_string && std::strcmp(buf, "gaussian") == 0) { *mode = WDGS_DSSIM_GAUSSIAN; return true; }
+    napi_throw_type_error(env, nullptr, "dssim_mode must be 'reference' or 'gaussian'");
+    return false;
+}
 static napi_value js_null(napi_env env) { napi_value v; napi_get_null(env, &v); return v; }
 
 // ---- device / queue ---------------------------------------------------------------------------------------------
@@ -214,8 +231,12 @@ static napi_value tiledBackwardCreate(napi_env env, napi_callback_info info) {
     c.training.c1 = (float)prop_f64(env, argv[1], "c1", 0.0001);
     c.training.c2 = (float)prop_f64(env, argv[1], "c2", 0.0009);
     c.max_splat_radius_px = (float)prop_f64(env, argv[1], "maxSplatRadiusPx", 128.0);
+    uint32_t mode = 0;
+    if (!prop_dssim_mode(env, argv[1], &mode)) return nullptr;
     wdgs_tiled_backward* op = nullptr;
     WDGS_OK_OR_THROW(wdgs_tiled_backward_create((wdgs_device*)get_ptr(env, argv[0]), &c, &op));
+    const int r = wdgs_tiled_backward_set_dssim_mode(op, mode);
+    if (r != WDGS_OK) { wdgs_tiled_backward_destroy(op); WDGS_OK_OR_THROW(r); }
     return make_ptr(env, op);
 }
 static napi_value tiledBackwardEncode(napi_env env, napi_callback_info info) {  // (op, predPtr, targetPtr, resources{...Ptr}, gaussiansPtr)
@@ -353,7 +374,9 @@ static napi_value tiledBackwardMetric(napi_env env, napi_callback_info info) {
             break;
         }
         case 3: WDGS_OK_OR_THROW(wdgs_tiled_backward_normalize_metric_counts(op, get_u32(env, argv[2]))); break;
-        case 5: {  // setTrainingConfig({lambda_l1, lambda_l2, lambda_dssim, c1, c2}): the complete config (tiled-backward-pass.ts:812-830)
+        case 5: {  // setTrainingConfig({lambda_l1, lambda_l2, lambda_dssim, c1, c2, dssim_mode}): the complete config (tiled-backward-pass.ts:812-830)
+            uint32_t mode = 0;
+            if (!prop_dssim_mode(env, argv[2], &mode)) return nullptr;
             wdgs_training_config t;
             t.lambda_l1 = (float)prop_f64(env, argv[2], "lambda_l1", 0.8);
             t.lambda_l2 = (float)prop_f64(env, argv[2], "lambda_l2", 0.0);
@@ -361,6 +384,7 @@ static napi_value tiledBackwardMetric(napi_env env, napi_callback_info info) {
             t.c1 = (float)prop_f64(env, argv[2], "c1", 0.0001);
             t.c2 = (float)prop_f64(env, argv[2], "c2", 0.0009);
             WDGS_OK_OR_THROW(wdgs_tiled_backward_set_training_config(op, &t));
+            WDGS_OK_OR_THROW(wdgs_tiled_backward_set_dssim_mode(op, mode));
             break;
         }
         default: WDGS_OK_OR_THROW(wdgs_tiled_backward_set_viewport(op, get_u32(env, argv[2]), get_u32(env, argv[3]))); break;

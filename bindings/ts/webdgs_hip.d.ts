@@ -118,7 +118,11 @@ export class TiledRasterizer {
   blitToTexture(encoder: HipEncoder | null, target: HipBuffer & { width?: number; height?: number }, clearColor?: { r: number; g: number; b: number; a: number }): void;
   destroy(): void;
 }
-export interface TrainingConfig { lambda_l1: number; lambda_l2: number; lambda_dssim: number; c1?: number; c2?: number; }  // tiled-backward-pass.ts:19-25
+export interface TrainingConfig {  // tiled-backward-pass.ts:19-25
+  lambda_l1: number; lambda_l2: number; lambda_dssim: number; c1?: number; c2?: number;
+  /** The loss the backward pass differentiates (no reference counterpart): 'reference' (default) or 'gaussian', the exact 3DGS D-SSIM loss. */
+  dssim_mode?: 'reference' | 'gaussian';
+}
 export interface TiledBackwardResources {  // tiled-backward-pass.ts:40-50
   splatBuffer: HipBuffer; tileOffsetsBuffer: HipBuffer; tileIndicesBuffer: HipBuffer; cameraBuffer?: HipBuffer; alphaTexture?: HipBuffer; nContribTexture: HipBuffer;
 }

@@ -242,8 +242,9 @@ class TiledBackwardPass {                // tiled-backward-pass.ts:71
     this.device = device; this.pointCloud = pointCloud; this.destroyed = false; this.w = config.viewportWidth; this.h = config.viewportHeight;
     this.handle = addon.tiledBackwardCreate(device.handle, { numPoints: pointCloud.num_points, shDeg: pointCloud.sh_deg || 0, viewportWidth: config.viewportWidth,
       viewportHeight: config.viewportHeight, lambda_l1: t.lambda_l1, lambda_l2: t.lambda_l2, lambda_dssim: t.lambda_dssim, c1: dflt(t.c1, 0.0001), c2: dflt(t.c2, 0.0009),
-      maxSplatRadiusPx: dflt(config.maxSplatRadiusPx, 128.0) });
-    this.trainingConfig = { lambda_l1: t.lambda_l1, lambda_l2: t.lambda_l2, lambda_dssim: t.lambda_dssim, c1: dflt(t.c1, 0.0001), c2: dflt(t.c2, 0.0009) };
+      dssim_mode: dflt(t.dssim_mode, 'reference'), maxSplatRadiusPx: dflt(config.maxSplatRadiusPx, 128.0) });
+    this.trainingConfig = { lambda_l1: t.lambda_l1, lambda_l2: t.lambda_l2, lambda_dssim: t.lambda_dssim, c1: dflt(t.c1, 0.0001), c2: dflt(t.c2, 0.0009),
+      dssim_mode: dflt(t.dssim_mode, 'reference') };
   }
   encode(_encoder, predictedTexture, targetTexture, r, _options) {   // (TiledBackwardPassOptions is an empty interface in the reference)
     addon.tiledBackwardEncode(this.handle, predictedTexture.ptr, targetTexture.ptr, resourcePtrs(r), this.pointCloud.gaussian_3d_buffer.ptr);
@@ -262,10 +263,11 @@ class TiledBackwardPass {                // tiled-backward-pass.ts:71
   /** computeMetricCounts of this pass adds into `counts` (another pass's getMetricCountsBuffer()) instead of its own array; null restores its own.
    *  Several passes can then take the metric views of one densify event on different lanes (integer atomics: any order gives the same bits). */
   setMetricCountsTarget(counts) { this.metricTarget = counts || null; addon.tiledBackwardSetMetricCountsTarget(this.handle, counts ? counts.ptr : null); }
-  /** setTrainingConfig(next) (tiled-backward-pass.ts:812-830): loss weights of the next encode. */
+  /** setTrainingConfig(next) (tiled-backward-pass.ts:812-830): loss weights and dssim_mode of the next encode. */
   setTrainingConfig(next) {
-    this.trainingConfig = Object.assign({ lambda_l1: 0.8, lambda_l2: 0.0, lambda_dssim: 0.2, c1: 0.0001, c2: 0.0009 }, this.trainingConfig || {}, next || {});
-    addon.tiledBackwardMetric(this.handle, 5, this.trainingConfig, 0, 0);
+    const cfg = Object.assign({ lambda_l1: 0.8, lambda_l2: 0.0, lambda_dssim: 0.2, c1: 0.0001, c2: 0.0009, dssim_mode: 'reference' }, this.trainingConfig || {}, next || {});
+    addon.tiledBackwardMetric(this.handle, 5, cfg, 0, 0);   // (throws for an unknown dssim_mode before it changes anything)
+    this.trainingConfig = cfg;
   }
   /** See TiledForwardPass.setPointCloud (wdgs_tiled_backward_resize). */
   setPointCloud(pointCloud) {

@@ -308,6 +308,15 @@ int wdgs_tiled_backward_compute_metric_counts(wdgs_tiled_backward* op, const wdg
 int wdgs_tiled_backward_normalize_metric_counts(wdgs_tiled_backward* op, uint32_t divisor);
 int wdgs_tiled_backward_set_viewport(wdgs_tiled_backward* op, uint32_t width, uint32_t height);
 int wdgs_tiled_backward_set_training_config(wdgs_tiled_backward* op, const wdgs_training_config* cfg);
+/* The loss an encode differentiates (no reference counterpart).  WDGS_DSSIM_REFERENCE (the default): the reference's per-pixel gradient
+ * l1 sgn(d) + l2 d + ldssim (1 - SSIM_5x5) d / 2, a 5x5 box window with clamp-to-edge.  WDGS_DSSIM_GAUSSIAN: the exact gradient of
+ * sum over pixels and channels of l1 |d| + l2 d^2 / 2 + ldssim (1 - SSIM), SSIM as wdgs_image_ssim_rgb8 defines it (11x11 Gaussian window,
+ * zero padding) with the training config's c1 and c2.  Like set_training_config, the mode is read when an encode or
+ * compute_loss_only is issued: a recording keeps the loss it was recorded with.  set returns WDGS_E_INVALID for an unknown mode. */
+#define WDGS_DSSIM_REFERENCE 0
+#define WDGS_DSSIM_GAUSSIAN 1
+int wdgs_tiled_backward_set_dssim_mode(wdgs_tiled_backward* op, uint32_t mode);
+int wdgs_tiled_backward_get_dssim_mode(const wdgs_tiled_backward* op, uint32_t* out);
 void* wdgs_tiled_backward_gradients(wdgs_tiled_backward* op);     /* getGradientsBuffer: GaussianGradient[N] */
 void* wdgs_tiled_backward_metric_counts(wdgs_tiled_backward* op); /* getMetricCountsBuffer: u32[N] */
 /* computeMetricCounts of this pass adds into `counts_dev` (u32[num_points], e.g. another pass's getMetricCountsBuffer) instead of its own

@@ -208,6 +208,8 @@ SIGNATURES = {
     "wdgs_tiled_backward_normalize_metric_counts": (_I, [_P, _U]),
     "wdgs_tiled_backward_set_viewport": (_I, [_P, _U, _U]),
     "wdgs_tiled_backward_set_training_config": (_I, [_P, C.POINTER(TrainingConfig)]),
+    "wdgs_tiled_backward_set_dssim_mode": (_I, [_P, _U]),
+    "wdgs_tiled_backward_get_dssim_mode": (_I, [_P, C.POINTER(_U)]),
     "wdgs_tiled_backward_gradients": (_P, [_P]),
     "wdgs_tiled_backward_metric_counts": (_P, [_P]),
     "wdgs_tiled_backward_set_metric_counts_target": (_I, [_P, _P]),

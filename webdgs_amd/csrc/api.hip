@@ -26,6 +26,7 @@ int launch_tile_ranges(wdgs_device*, const void*, const void*, u32, void*);
 int launch_rasterize(wdgs_device*, const RenderSettings&, const TileInfo&, const void*, u32, const void*, const void*, const void*, const void*, u32, void*,
                      void*, void*, const void*, const void*, const LongWork*);
 int launch_loss_grad(wdgs_device*, u32, u32, const void*, const void*, const wdgs_training_config&, void*, void*, u32, const void*);
+int launch_dssim_grad(wdgs_device*, u32, u32, const void*, const void*, const wdgs_training_config&, void*, void*, u32, const void*);
 int launch_backward_rasterize(wdgs_device*, const RenderSettings&, u32, u32, const void*, const void*, const void*, const void*, const void*, const void*,
                               void*, void*, const LongWork*);
 int launch_acc_clear_if_dirty(wdgs_device*, void*, u32, void*);
@@ -228,6 +229,7 @@ struct wdgs_tiled_backward {
     u32* gradients;      // GaussianGradient[N]
     bool gradient_output;  // the fused K17 + Adam step also writes the packed gradient (wdgs_tiled_backward_set_gradient_output; default on)
     float* loss_image;   // rgba32f
+    u32 dssim_mode;      // WDGS_DSSIM_*: the loss kernel an encode launches (wdgs_tiled_backward_set_dssim_mode)
     u32* metric_counts;  // u32[N]
     u32* metric_counts_into;  // nullable: computeMetricCounts adds into THIS array instead (wdgs_tiled_backward_set_metric_counts_target)
     u32* metric_err;     // u32[W*H]
@@ -1309,15 +1311,22 @@ int wdgs_tiled_backward_set_gradient_output(wdgs_tiled_backward* op, int enabled
     op->gradient_output = enabled != 0;
     return WDGS_OK;
 }
+// K15, the loss image of the pass's loss (dssim_mode): the reference's heuristic (loss.hip) or the exact D-SSIM gradient (dssim.hip); both clear
+// the accumulators when acc is given and they are dirty
+static int backward_loss(wdgs_tiled_backward* op, const void* pred, const void* targ, void* acc, u32 acc_rows, const void* acc_dirty) {
+    const u32 w = op->cfg.viewport_width, h = op->cfg.viewport_height;
+    if (op->dssim_mode == WDGS_DSSIM_GAUSSIAN) return launch_dssim_grad(op->dev, w, h, pred, targ, op->cfg.training, op->loss_image, acc, acc_rows, acc_dirty);
+    return launch_loss_grad(op->dev, w, h, pred, targ, op->cfg.training, op->loss_image, acc, acc_rows, acc_dirty);
+}
 int wdgs_tiled_backward_compute_loss_only(wdgs_tiled_backward* op, const void* pred, const void* targ) {
     WDGS_REQUIRE(op && pred && targ, WDGS_E_INVALID, "wdgs_tiled_backward_compute_loss_only: null argument");
-    return launch_loss_grad(op->dev, op->cfg.viewport_width, op->cfg.viewport_height, pred, targ, op->cfg.training, op->loss_image, nullptr, 0u, nullptr);
+    return backward_loss(op, pred, targ, nullptr, 0u, nullptr);
 }
 static int backward_encode_raster(wdgs_tiled_backward* op, const void* pred, const void* targ, const wdgs_tiled_backward_resources* res) {
     wdgs_device* d = op->dev;
     const u32 w = op->cfg.viewport_width, h = op->cfg.viewport_height, n = op->cfg.num_points;
     // K15 + clearBuffer x4 (tiled-backward-pass.ts:624-627): the clear rides on the loss kernel and is a no-op behind a consuming K17
-    if (w > 0 && h > 0) WDGS_TRY(launch_loss_grad(d, w, h, pred, targ, op->cfg.training, op->loss_image, op->acc, std::max(n, 1u), op->acc_dirty));
+    if (w > 0 && h > 0) WDGS_TRY(backward_loss(op, pred, targ, op->acc, std::max(n, 1u), op->acc_dirty));
     else WDGS_TRY(launch_acc_clear_if_dirty(d, op->acc, n, op->acc_dirty));
     // long tile lists (longlist.h): when the range table is one a forward pass of this device built, that pass's lists serve the backward walk too
     const LongWork* lw = nullptr;
@@ -1400,6 +1409,17 @@ int wdgs_tiled_backward_set_training_config(wdgs_tiled_backward* op, const wdgs_
     op->cfg.training = *cfg;
     if (op->cfg.training.c1 == 0.f) op->cfg.training.c1 = 0.01f * 0.01f;
     if (op->cfg.training.c2 == 0.f) op->cfg.training.c2 = 0.03f * 0.03f;
+    return WDGS_OK;
+}
+int wdgs_tiled_backward_set_dssim_mode(wdgs_tiled_backward* op, uint32_t mode) {
+    WDGS_REQUIRE(op, WDGS_E_INVALID, "wdgs_tiled_backward_set_dssim_mode: null op");
+    WDGS_REQUIRE(mode == WDGS_DSSIM_REFERENCE || mode == WDGS_DSSIM_GAUSSIAN, WDGS_E_INVALID, "wdgs_tiled_backward_set_dssim_mode: unknown mode %u", mode);
+    op->dssim_mode = mode;
+    return WDGS_OK;
+}
+int wdgs_tiled_backward_get_dssim_mode(const wdgs_tiled_backward* op, uint32_t* out) {
+    WDGS_REQUIRE(op && out, WDGS_E_INVALID, "wdgs_tiled_backward_get_dssim_mode: null argument");
+    *out = op->dssim_mode;
     return WDGS_OK;
 }
 void* wdgs_tiled_backward_gradients(wdgs_tiled_backward* op) { return op ? op->gradients : nullptr; }

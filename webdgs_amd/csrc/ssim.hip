@@ -27,8 +27,7 @@ constexpr u32 ST = 32;              // output tile edge
 constexpr u32 RAD = 5;              // window radius: 11 taps
 constexpr u32 HT = ST + 2u * RAD;   // staged edge (tile + halo)
 constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
-
-struct SsimWindow { float g[2u * RAD + 1u]; };
+static_assert(2u * RAD + 1u == SSIM_TAPS, "ssim window size");
 
 __global__ __launch_bounds__(256) void image_ssim_kernel(const u32* __restrict__ a, const u32* __restrict__ b, u32 W, u32 H, u32 tiles_x, u32 n_tiles,
                                                           SsimWindow win, float* __restrict__ map, double* __restrict__ partials) {
@@ -132,19 +131,23 @@ __global__ __launch_bounds__(256) void image_ssim_finish_kernel(const double* __
     if (threadIdx.x == 0) *out = s[0] / count;
 }
 
-SsimWindow ssim_window() {
+}  // namespace
+
+static SsimWindow make_ssim_window() {
     SsimWindow w;
-    double g[2u * RAD + 1u], sum = 0.0;
-    for (int k = 0; k < (int)(2u * RAD + 1u); k++) {
+    double g[SSIM_TAPS], sum = 0.0;
+    for (int k = 0; k < (int)SSIM_TAPS; k++) {
         const double d = (double)(k - (int)RAD);
         g[k] = std::exp(-d * d / (2.0 * 1.5 * 1.5));
         sum += g[k];
     }
-    for (u32 k = 0; k < 2u * RAD + 1u; k++) w.g[k] = (float)(g[k] / sum);
+    for (u32 k = 0; k < SSIM_TAPS; k++) w.g[k] = (float)(g[k] / sum);
     return w;
 }
-
-}  // namespace
+const SsimWindow& ssim_window() {
+    static const SsimWindow win = make_ssim_window();
+    return win;
+}
 
 extern "C" int wdgs_image_ssim_rgb8(wdgs_device* dev, const void* a_rgba8_dev, const void* b_rgba8_dev, uint32_t width, uint32_t height, void* out_f64_dev,
                                     void* map_f32_dev) {
@@ -157,7 +160,7 @@ extern "C" int wdgs_image_ssim_rgb8(wdgs_device* dev, const void* a_rgba8_dev, c
         WDGS_CHECK_HIP(hipMalloc(&dev->ssim_partials, sizeof(double) * (size_t)dev->num_cus * SSIM_WG_PER_CU));
         dev->ssim_partials_count = (u32)dev->num_cus * SSIM_WG_PER_CU;
     }
-    static const SsimWindow win = ssim_window();
+    const SsimWindow& win = ssim_window();
     const u32 tiles_x = ceil_div(width, ST), n_tiles = tiles_x * ceil_div(height, ST);
     WDGS_LAUNCH(dev, "image_ssim", image_ssim_kernel, dim3(dev->ssim_partials_count), dim3(256), 0, (const u32*)a_rgba8_dev, (const u32*)b_rgba8_dev, width, height,
                 tiles_x, n_tiles, win, (float*)map_f32_dev, dev->ssim_partials);

@@ -552,10 +552,26 @@ def _training_config(tc: Optional[dict]) -> _lib.TrainingConfig:
                                float(tc.get("c1", 0.01 * 0.01)), float(tc.get("c2", 0.03 * 0.03)))
 
 
+# trainingConfig["dssim_mode"] -> WDGS_DSSIM_* (include/webdgs.h): the loss the backward pass differentiates
+DSSIM_MODES = {"reference": 0, "gaussian": 1}
+
+
+def dssim_mode(tc: Optional[dict]) -> int:
+    """The ``WDGS_DSSIM_*`` value of a training config's ``dssim_mode``: ``"reference"`` (the default; the reference's heuristic gradient) or
+    ``"gaussian"`` (the exact gradient of the 3DGS loss with the 11x11 Gaussian-window SSIM).  ValueError otherwise."""
+    mode = (tc or {}).get("dssim_mode")
+    mode = "reference" if mode is None else mode
+    if not isinstance(mode, str) or mode not in DSSIM_MODES:
+        raise ValueError(f"dssim_mode must be one of {sorted(DSSIM_MODES)}, not {mode!r}")
+    return DSSIM_MODES[mode]
+
+
 class TiledBackwardPass:
-    """``TiledBackwardPass`` (``src/renderers/tiled-backward-pass.ts:71-861``)."""
+    """``TiledBackwardPass`` (``src/renderers/tiled-backward-pass.ts:71-861``).  ``trainingConfig["dssim_mode"]`` (no reference counterpart)
+    chooses the loss: ``"reference"`` (default) or ``"gaussian"``; see ``dssim_mode``."""
 
     def __init__(self, device: HipDevice, pointCloud: PointCloud, config: dict):
+        mode = dssim_mode(config.get("trainingConfig"))
         self.device, self.pointCloud = device, pointCloud
         self.destroyed = False
         self.viewportWidth, self.viewportHeight = int(config["viewportWidth"]), int(config["viewportHeight"])
@@ -566,6 +582,8 @@ class TiledBackwardPass:
         h = C.c_void_p()
         check(device.lib.wdgs_tiled_backward_create(device.handle, C.byref(cfg), C.byref(h)))
         self.handle = h
+        if mode:
+            check(device.lib.wdgs_tiled_backward_set_dssim_mode(h, mode))
 
     @staticmethod
     def _resources(res: dict) -> _lib.TiledBackwardResources:
@@ -623,9 +641,12 @@ class TiledBackwardPass:
         self.viewportWidth, self.viewportHeight = int(width), int(height)
 
     def setTrainingConfig(self, next_cfg: dict) -> None:
-        self.trainingConfig.update({k: v for k, v in next_cfg.items() if v is not None})
+        merged = dict(self.trainingConfig, **{k: v for k, v in next_cfg.items() if v is not None})
+        mode = dssim_mode(merged)
+        self.trainingConfig = merged
         tc = _training_config(self.trainingConfig)
         check(self.device.lib.wdgs_tiled_backward_set_training_config(self.handle, C.byref(tc)))
+        check(self.device.lib.wdgs_tiled_backward_set_dssim_mode(self.handle, mode))
 
     def setGradientOutput(self, enabled: bool) -> None:
         """Whether ``Optimizer.stepWithGeometry`` also writes K17's packed gradient to ``getGradientsBuffer()`` (default: yes, as the

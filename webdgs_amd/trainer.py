@@ -26,6 +26,7 @@ class Trainer:
     def __init__(self, device: ops.HipDevice, trainingConfig: Optional[dict] = None, seed: int = 0, world_size: int = 1, rank: int = 0,
                  views_per_rank: int = 1, maxTileEntries: int = 0, use_command_buffers: bool = True, exchange: Optional[parallel.Exchange] = None,
                  overlap_views: Optional[bool] = None, pipeline_depth: int = 1, batch_views: Optional[bool] = None):
+        ops.dssim_mode(trainingConfig)   # (an unknown loss is refused before anything is built)
         self.device = device
         self.trainingConfig = dict(trainingConfig or dict(lambda_l1=0.8, lambda_l2=0.0, lambda_dssim=0.2))  # trainer.ts:100-104
         self.optimizerHyperparameters = dict(ops.DEFAULT_ADAM_HYPERPARAMETERS)
@@ -254,6 +255,8 @@ class Trainer:
         return dict(self.trainingConfig)
 
     def setTrainingConfig(self, next_cfg: dict) -> None:
+        """Also ``dssim_mode`` (``ops.dssim_mode``): every backward pass of the trainer, and those it builds later, differentiate that loss."""
+        ops.dssim_mode(dict(self.trainingConfig, **{k: v for k, v in next_cfg.items() if v is not None}))
         self.trainingConfig.update({k: v for k, v in next_cfg.items() if v is not None})
         self._invalidate_command_buffers()
         for p in [self.backwardPass, self.metricsPass] + [more[2] for more in self._more_op_sets + self._more_metric_sets]:
