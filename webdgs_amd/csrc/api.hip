@@ -851,9 +851,7 @@ int wdgs_tiled_forward_create(wdgs_device* d, const wdgs_tiled_forward_config* c
     // (frame numbers start at 1: a zeroed stamp table marks nothing)
     if (r == WDGS_OK && hipMemsetD32Async((hipDeviceptr_t)(op->stats + FRAME_WORD), 1, 1, d->stream) != hipSuccess) { wdgs_set_error("hipMemsetD32Async failed"); r = WDGS_E_HIP; }
     if (r == WDGS_OK) r = forward_alloc_nf_stamp(op);
-    // (WDGS_LONG_LISTS=0: off for every pass of the process; a threshold otherwise -- same-box comparisons)
-    static const char* const ll_env = std::getenv("WDGS_LONG_LISTS");
-    if (r == WDGS_OK && !cfg->compat_caps) r = forward_alloc_long_lists(op, ll_env ? (u32)std::atoi(ll_env) : LONG_LIST_THRESHOLD, LONG_LIST_ITEMS, LONG_LIST_ROWS);
+    if (r == WDGS_OK && !cfg->compat_caps) r = forward_alloc_long_lists(op, LONG_LIST_THRESHOLD, LONG_LIST_ITEMS, LONG_LIST_ROWS);
     if (r == WDGS_OK && hipHostMalloc((void**)&op->host_stats, 16, hipHostMallocDefault) != hipSuccess) { wdgs_set_error("hipHostMalloc(16) failed"); r = WDGS_E_HIP; }
     if (r == WDGS_OK) std::memset(op->host_stats, 0, 16);
     if (r == WDGS_OK) r = forward_alloc_per_point(op, std::max(n, 1u));
@@ -941,10 +939,8 @@ static u32 bits_for(u32 v) {  // number of bits needed to represent v
 // per-column offsets, and emit writes its entries straight into column order (project.hip: emit_scatter) -- the keys are never
 // written in emission order, histogrammed and scattered.  encode(skipSort) and compat_caps keep the reference's emission order.
 static bool forward_uses_columns(const wdgs_tiled_forward* op, int skip_sort) {
-    // (WDGS_FORWARD_COLUMNS=0: the separate emit + two-pass tile sort of round 2, for same-box A/B timing; results are identical)
-    static const bool columns_enabled = !(std::getenv("WDGS_FORWARD_COLUMNS") && std::getenv("WDGS_FORWARD_COLUMNS")[0] == '0');
     const TileInfo& ti = op->tile_info;
-    return columns_enabled && !skip_sort && !op->cfg.compat_caps && op->cfg.num_points > 0 && ti.num_tiles_x >= 2u && ti.num_tiles_x <= 256u && ti.num_tiles_y <= 256u;
+    return !skip_sort && !op->cfg.compat_caps && op->cfg.num_points > 0 && ti.num_tiles_x >= 2u && ti.num_tiles_x <= 256u && ti.num_tiles_y <= 256u;
 }
 
 // Everything of TiledForwardPass.encode behind K1: scan (+ stats), emit, sort.
@@ -1137,15 +1133,6 @@ int wdgs_tiled_forward_long_list_stats(wdgs_tiled_forward* op, uint32_t stats_ou
     if (!lw.hdr) return WDGS_OK;
     WDGS_TRY(wdgs_copy_to_host(op->dev, stats_out, lw.hdr, sizeof(u32) * LL_HDR_WORDS));
     stats_out[8] = lw.max_items; stats_out[9] = lw.max_blocks; stats_out[10] = lw.max_rows; stats_out[11] = lw.threshold;
-    if (std::getenv("WDGS_LL_DEBUG")) {   // (dev aid: the block records of the frame)
-        const u32 nb = std::min(stats_out[0], lw.max_blocks);
-        std::vector<LongBlock> b(nb);
-        std::vector<LongSync> sy(nb);
-        if (nb) { WDGS_TRY(wdgs_copy_to_host(op->dev, b.data(), lw.blocks, sizeof(LongBlock) * nb)); WDGS_TRY(wdgs_copy_to_host(op->dev, sy.data(), lw.sync, sizeof(LongSync) * nb)); }
-        for (u32 i = 0; i < nb; i++)
-            std::fprintf(stderr, "[long lists] block %u: tile %u sub %u first_item %u chunks %u | counted %u row_base %u scanned %u filled %u rows %u walked %u\n", i, b[i].tile, b[i].sub,
-                         b[i].first_item, b[i].chunks, sy[i].counted, sy[i].row_base, sy[i].scanned, sy[i].filled, sy[i].rows, sy[i].walked);
-    }
     return WDGS_OK;
 }
 

@@ -71,7 +71,6 @@ WD_DEV void dssim_maps(const float v[5], float s, float c1, float c2, float& ma,
 __global__ __launch_bounds__(256) void dssim_grad_kernel(u32 W, u32 H, const u32* __restrict__ pred, const u32* __restrict__ targ, wdgs_training_config cfg,
                                                           SsimWindow win, float4* __restrict__ out, int4* __restrict__ acc, u32 acc_quads,
                                                           const u32* __restrict__ acc_dirty) {
-    WD_STREAM_PRIO();
     // the accumulator clear of loss_grad_kernel (loss.hip), which backward_rasterize relies on
     if (acc && *acc_dirty != 0u) {
         const int4 z = make_int4(0, 0, 0, 0);

@@ -7,7 +7,6 @@
 // compulsory 8 B read + 16 B write per pixel; window taps are a conflict-free ds_read_b128 + ds_read_b64, shared by four pixels per thread.
 // The window sums keep the reference's order (dy outer, dx inner); the second-moment accumulations are FMAs, the contraction the
 // parity oracle pins (WGSL leaves it open).
-#include <cstdlib>
 #include "common.h"
 #include "dmath.h"
 
@@ -29,7 +28,6 @@ template <u32 PPT>
 __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32* __restrict__ pred, const u32* __restrict__ targ,
                                                          wdgs_training_config cfg, float4* __restrict__ out, int4* __restrict__ acc, u32 acc_quads,
                                                          const u32* __restrict__ acc_dirty) {
-    WD_STREAM_PRIO();
     // clearBuffer x4 of the gradient accumulators (tiled-backward-pass.ts:624-627) rides on this kernel, which precedes the backward
     // rasterization anyway: the accumulators' state word (backward_raster.hip) says whether anything has to be cleared at all -- after a
     // consuming K17 nothing has -- so the clear is one scalar load here instead of a launch of its own.
@@ -174,13 +172,10 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32*
 int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const void* pred, const void* targ, const wdgs_training_config& cfg, void* out, void* acc, u32 acc_rows,
                      const void* acc_dirty) {
     if (W == 0 || H == 0) return WDGS_OK;
-    // WDGS_LOSS_PPT=1|2|4 forces the pixels per thread (same-box A/B)
-    static const int ppt_env = std::getenv("WDGS_LOSS_PPT") ? std::atoi(std::getenv("WDGS_LOSS_PPT")) : 0;
-    const u32 ppt = ppt_env == 1 || ppt_env == 2 || ppt_env == 4 ? (u32)ppt_env : ((size_t)W * H <= 640u * 480u ? 1u : 2u);
 #define WDGS_LOSS_LAUNCH(PPT_)                                                                                                                                       \
     WDGS_LAUNCH(dev, "loss_grad", loss_grad_kernel<PPT_>, dim3(ceil_div(W, LT), ceil_div(H, 8u * PPT_)), dim3(256), 0, W, H, (const u32*)pred, (const u32*)targ, cfg, \
                 (float4*)out, (int4*)acc, acc_rows * 3u /*12 i32 per row*/, (const u32*)acc_dirty)
-    if (ppt == 1u) { WDGS_LOSS_LAUNCH(1u); } else if (ppt == 2u) { WDGS_LOSS_LAUNCH(2u); } else { WDGS_LOSS_LAUNCH(4u); }
+    if ((size_t)W * H <= 640u * 480u) { WDGS_LOSS_LAUNCH(1u); } else { WDGS_LOSS_LAUNCH(2u); }
 #undef WDGS_LOSS_LAUNCH
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;

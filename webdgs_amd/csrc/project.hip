@@ -201,7 +201,6 @@ __global__ __launch_bounds__(256) void project_count_kernel(u32 n, const u32* __
                                                              u32* __restrict__ block_counts, u32* __restrict__ column_counts /*[num_tiles_x][gridDim.x]*/,
                                                              const u32* __restrict__ dc_words /*nullable: u32[N][2], the trained SH-DC halves (adam.h)*/,
                                                              u32* __restrict__ nf_stamp /*nullable: u32[tiles]*/, const u32* __restrict__ nf_frame) {
-    WD_STREAM_PRIO();
     const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
     const u32 stamp = nf_stamp ? *nf_frame + 1u : 0u;   // the number the scan kernel gives this frame (scan.hip: stats_epilogue)
     bool visible = false;
@@ -258,13 +257,10 @@ struct ProjectViews {
     u32* nf_stamp[WDGS_MAX_BATCH_VIEWS];        // (nullable) tiles of non-finite Splats, and each pass's frame number
     const u32* nf_frame[WDGS_MAX_BATCH_VIEWS];
 };
-// resident waves per SIMD the register allocation of the view-batched K1 aims at (make K1V_WAVES=n: a build-time choice, for same-box comparisons)
-#ifndef WDGS_K1V_WAVES
-#define WDGS_K1V_WAVES 4
-#endif
-__global__ __launch_bounds__(256, WDGS_K1V_WAVES) void project_count_views_kernel(u32 n, const u32* __restrict__ gaussians, const u32* __restrict__ sh_buffer, RenderSettings settings,
+// (256, 4): the register allocation aims at 4 resident waves per SIMD (192 us at c3); aimed at 5 or 6 it spills 56 / 120 bytes per thread
+// and takes 236 / 292 us (profiles/r05n_k1_views_occupancy_ab.txt)
+__global__ __launch_bounds__(256, 4) void project_count_views_kernel(u32 n, const u32* __restrict__ gaussians, const u32* __restrict__ sh_buffer, RenderSettings settings,
                                                                    TileInfo ti, ProjectViews pv, const u32* __restrict__ dc_words) {
-    WD_STREAM_PRIO();
     const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
     __shared__ u32 s_col[256];
     __shared__ u32 s_vis[4], s_cnt[4];
@@ -302,7 +298,6 @@ __global__ __launch_bounds__(256, WDGS_K1V_WAVES) void project_count_views_kerne
 // stats[0] = total tile entries (update_stats, src/shaders/update-stats.wgsl:19-35); stats[2] = overflow flag.
 __global__ void update_stats_kernel(u32 n, const u32* __restrict__ offsets, const u32* __restrict__ counts, u32 capacity, u32* __restrict__ stats,
                                     u32* __restrict__ visible_shards, u32* __restrict__ host_mirror) {
-    WD_STREAM_PRIO();
     // 64 threads: fold the visible-count shards (and clear them for the next encode)
     u32 v = visible_shards[threadIdx.x];
     visible_shards[threadIdx.x] = 0u;
@@ -334,7 +329,6 @@ __global__ __launch_bounds__(256) void emit_kernel(u32 n, const u32* __restrict_
                                                     const u32* __restrict__ tile_counts, u32* __restrict__ tile_offsets,
                                                     const u32* __restrict__ block_offsets, RenderSettings settings, TileInfo ti,
                                                     u32* __restrict__ keys, u32* __restrict__ values, u32 capacity) {
-    WD_STREAM_PRIO();
     __shared__ u32 s_pre[4][64], s_org[4][64], s_w[4][64], s_inv[4][64], s_dep[4][64];
     __shared__ u32 s_wtot[4];
     const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -433,7 +427,6 @@ __global__ __launch_bounds__(256) void emit_scatter_kernel(u32 n, const u32* __r
                                                             const u32* __restrict__ column_offsets /*[num_tiles_x][gridDim.x], scanned*/,
                                                             const u32* __restrict__ column_totals, u32 inv_ntx /*2^32 / num_tiles_x, rounded up*/,
                                                             u32* __restrict__ keys, u32* __restrict__ values, u32 capacity) {
-    WD_STREAM_PRIO();
     __shared__ u32 s_pre[256];                     // exclusive prefix of the entry counts over the workgroup's Gaussians
     __shared__ u32 s_box[256];                     // min_x | min_y << 8 | width << 16  (all < 256 on this path)
     __shared__ u32 s_inv[256], s_dep[256];

@@ -1,4 +1,4 @@
-// Front-to-back alpha compositing (K14), one WAVE (64-thread workgroup) per 8x8 pixel block, four per 16x16 tile.
+// Front-to-back alpha compositing (K14), one WAVE per 8x8 pixel block, four per 16x16 tile (one 256-thread workgroup).
 //
 // Replaces tiled_rasterize (src/shaders/tiled-rasterizer.wgsl:82-273): a fixed 32 x 256 batch loop with three
 // barriers per batch even when empty, a 48-byte AoS LDS record and no early-out.  Here:
@@ -19,33 +19,23 @@
 // sustains for a pure FMA stream -- not HBM.
 // Arithmetic is the pinned contraction of DESIGN.md "raster math", bit-identical to the parity oracle.
 #include "common.h"
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
 #include "dmath.h"
 #include "longlist.h"
 
 namespace {
 
-// WPW = waves per workgroup: 1 (one 8x8 block per workgroup, a tile's four blocks dispatched back to back on one XCD) or 4 (workgroup = tile);
-// see backward_raster.hip.
-// TIMELINE (measurement tool, WDGS_FWR_TIMELINE=<file>, eager launches): every wave leaves {start, end} of the 100 MHz wall clock, where it ran and how
-// many records it composited -- the format of backward_raster.hip's, read by scripts/bwr_timeline.py.
 // EXACT: the tile holds a Splat with a NaN or an infinity among its fp16 fields (project.hip marks such tiles).  The fast forms below assume
 // ordinary operands -- hardware min / max / med3 return the operand that is not a NaN, the in-range exp never sees one -- while the parity oracle
 // evaluates WGSL's own formulas (min(e1, e2) = e2 < e1 ? e2 : e1, clamp = min(max(e, lo), hi): a NaN stays a NaN) with the full exp.  EXACT takes
 // every such operation in the oracle's form, so that a tile of non-finite Splats -- what a long run of the reference's schedule collects in tile 0 --
 // composites to the same bits: a NaN alpha makes the pixel's sums NaN for good (it never saturates, n_contrib keeps following the finite alphas).
-template <bool GAUSSIAN_MODE, u32 WPW, bool TIMELINE, bool EXACT>
+template <bool GAUSSIAN_MODE, bool EXACT>
 __device__ __attribute__((always_inline)) void rasterize_body(const RenderSettings& settings, const TileInfo& ti, const u32* __restrict__ splats, u32 num_splats,
                            const u32* __restrict__ ranges, const u32* __restrict__ sorted_keys,
                            const u32* __restrict__ sorted_vals, const u32* __restrict__ count_ptr, u32 max_entries,
                            u32* __restrict__ out_rgba8, float* __restrict__ out_alpha, u32* __restrict__ out_ncontrib, u32 issue_priority,
-                           unsigned long long* __restrict__ timeline, u32 tile_id, u32 sub, u32 lane, u32 total /* *count_ptr */, u32 start /* ranges[tile_id] */,
+                           u32 tile_id, u32 sub, u32 lane, u32 total /* *count_ptr */, u32 start /* ranges[tile_id] */,
                            float4* s_geo, float4* s_con, float4* s_col) {
-    const unsigned long long t_start = TIMELINE ? wall_clock64() : 0ull;
-    u32 iterations = 0u;
     const u32 tile_x = tile_id % ti.num_tiles_x, tile_y = tile_id / ti.num_tiles_x;
     const u32 bx = tile_x * 16u + (sub & 1u) * 8u, by = tile_y * 16u + (sub >> 1) * 8u;  // block origin
     const u32 pixel_x = bx + (lane & 7u), pixel_y = by + (lane >> 3);
@@ -115,7 +105,6 @@ __device__ __attribute__((always_inline)) void rasterize_body(const RenderSettin
             }
             const unsigned long long m = __ballot(ok);
             const u32 cnt = (u32)__popcll(m);
-            if (TIMELINE) iterations += cnt;
             if (ok) {
                 const u32 slot = (u32)__popcll(m & lt_mask);
                 s_geo[slot] = make_float4(cx, cy, ex, ey);
@@ -218,13 +207,6 @@ __device__ __attribute__((always_inline)) void rasterize_body(const RenderSettin
         out_rgba8[p] = r8 | (g8 << 8) | (b8 << 16) | 0xFF000000u;
         out_alpha[p] = 1.0f - A;
         out_ncontrib[p] = last_contributor;
-    }
-    if (TIMELINE && lane == 0u) {
-        u32 hw_id, xcc_id;
-        asm volatile("s_getreg_b32 %0, hwreg(4, 0, 32)" : "=s"(hw_id));    // HW_REG_HW_ID
-        asm volatile("s_getreg_b32 %0, hwreg(20, 0, 32)" : "=s"(xcc_id));  // HW_REG_XCC_ID
-        unsigned long long* const rec = timeline + ((size_t)blockIdx.x * WPW + (threadIdx.x >> 6)) * 4u;
-        rec[0] = t_start; rec[1] = wall_clock64(); rec[2] = ((unsigned long long)xcc_id << 32) | hw_id; rec[3] = iterations;
     }
 }
 
@@ -387,11 +369,11 @@ WD_DEV void long_task_walk(const LongCtx& c, const LongWork& lw, u32 lb, u32 lan
     const u32 row_base = filled ? (u32)__builtin_amdgcn_readfirstlane((int)ll_ld(&sy->row_base)) : LL_NO_ROWS;
     if (row_base == LL_NO_ROWS) {   // no rows: the wave-per-block walk, here (the block's main wave has left it alone)
         if (c.nf_stamp == nullptr || c.nf_stamp[blk.tile] == *c.nf_frame)
-            rasterize_body<true, 4u, false, true>(c.settings, c.ti, c.splats, c.num_splats, c.ranges, c.sorted_keys, c.sorted_vals, c.count_ptr, 0u, c.out_rgba8, c.out_alpha,
-                                                  c.out_ncontrib, 0u, nullptr, blk.tile, blk.sub, lane, *c.count_ptr, c.ranges[blk.tile], s_geo, s_con, s_col);
+            rasterize_body<true, true>(c.settings, c.ti, c.splats, c.num_splats, c.ranges, c.sorted_keys, c.sorted_vals, c.count_ptr, 0u, c.out_rgba8, c.out_alpha,
+                                       c.out_ncontrib, 0u, blk.tile, blk.sub, lane, *c.count_ptr, c.ranges[blk.tile], s_geo, s_con, s_col);
         else
-            rasterize_body<true, 4u, false, false>(c.settings, c.ti, c.splats, c.num_splats, c.ranges, c.sorted_keys, c.sorted_vals, c.count_ptr, 0u, c.out_rgba8, c.out_alpha,
-                                                   c.out_ncontrib, 0u, nullptr, blk.tile, blk.sub, lane, *c.count_ptr, c.ranges[blk.tile], s_geo, s_con, s_col);
+            rasterize_body<true, false>(c.settings, c.ti, c.splats, c.num_splats, c.ranges, c.sorted_keys, c.sorted_vals, c.count_ptr, 0u, c.out_rgba8, c.out_alpha,
+                                        c.out_ncontrib, 0u, blk.tile, blk.sub, lane, *c.count_ptr, c.ranges[blk.tile], s_geo, s_con, s_col);
         return;
     }
     const u32 W = wd_to_u32(c.settings.viewport_x), H = wd_to_u32(c.settings.viewport_y);
@@ -467,49 +449,40 @@ __device__ __attribute__((always_inline)) void long_forward_help(const LongCtx c
 // Splats with the number the frame's scan kernel then gives the frame) takes the EXACT body, every other tile the fast one.  nf_stamp == nullptr:
 // nothing is known about the Splats -- every tile takes the EXACT body.  HELP: the blocks of long tiles (lw.flags) are left to the tasks of longlist.h,
 // which every wave helps to work off once its own block is done.
-template <bool GAUSSIAN_MODE, u32 WPW, bool TIMELINE = false, bool HELP = false>
-__global__ __launch_bounds__(64 * WPW, 8) void rasterize_kernel(RenderSettings settings, TileInfo ti, const u32* __restrict__ splats, u32 num_splats,
+template <bool GAUSSIAN_MODE, bool HELP>
+__global__ __launch_bounds__(256, 8) void rasterize_kernel(RenderSettings settings, TileInfo ti, const u32* __restrict__ splats, u32 num_splats,
                                                         const u32* __restrict__ ranges, const u32* __restrict__ sorted_keys,
                                                         const u32* __restrict__ sorted_vals, const u32* __restrict__ count_ptr, u32 max_entries,
                                                         u32* __restrict__ out_rgba8, float* __restrict__ out_alpha, u32* __restrict__ out_ncontrib, u32 issue_priority,
-                                                        unsigned long long* __restrict__ timeline, const u32* __restrict__ nf_stamp, const u32* __restrict__ nf_frame, LongWork lw) {
+                                                        const u32* __restrict__ nf_stamp, const u32* __restrict__ nf_frame, LongWork lw) {
     // (one record more than a chunk holds: the loop reads one record ahead)
-    __shared__ float4 s_geo_all[WPW][65];  // centre.x, centre.y, extent.x, extent.y   (pixels)
-    __shared__ float4 s_con_all[WPW][65];  // -0.5*conic.x, -conic.y, -0.5*conic.z, opacity (Gaussian mode: see the record build)
-    __shared__ float4 s_col_all[WPW][65];  // r, g, b, position in the tile list + 1 (bits)
-    const u32 slot = (WPW == 4u) ? (threadIdx.x >> 6) : 0u;
+    __shared__ float4 s_geo_all[4][65];  // centre.x, centre.y, extent.x, extent.y   (pixels)
+    __shared__ float4 s_con_all[4][65];  // -0.5*conic.x, -conic.y, -0.5*conic.z, opacity (Gaussian mode: see the record build)
+    __shared__ float4 s_col_all[4][65];  // r, g, b, position in the tile list + 1 (bits)
+    const u32 slot = threadIdx.x >> 6;
     float4* const s_geo = s_geo_all[slot];  // wave-private record sets
     float4* const s_con = s_con_all[slot];
     float4* const s_col = s_col_all[slot];
     const u32 blocks_wanted = HELP ? lw.hdr[LL_BLOCKS] : 0u, items_wanted = HELP ? lw.hdr[LL_ITEMS] : 0u;   // (requested now, looked at below)
     // (HELP: the wave's number in a scalar register for the help below, which derives everything it needs from it -- a vector register kept alive across
     // the walk for the help's sake costs the walk a spill per chunk: +3.5 us at c3, profiles/r08w_kernels_same_box.txt)
-    const u32 wave_s = (HELP && WPW == 4u) ? (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
-    // independent waves (no barrier is ever taken): one per 8x8 block
-    u32 tile_id, sub;
-    bool mine = true;
-    if (WPW == 4u) {
-        tile_id = blockIdx.x; sub = threadIdx.x >> 6;
-    } else {
-        // launch slots b, b + 8, ... share an XCD: slot j of XCD k is block (j & 3) of the XCD's tile number j >> 2; XCD k owns tiles k, k + 8, ...
-        const u32 k = blockIdx.x & 7u, j = blockIdx.x >> 3;
-        tile_id = k + 8u * (j >> 2);
-        sub = j & 3u;
-        mine = tile_id < ti.total_tiles;
-    }
+    const u32 wave_s = HELP ? (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
+    // independent waves (no barrier is ever taken): one per 8x8 block, the workgroup is the tile
+    const u32 tile_id = blockIdx.x, sub = threadIdx.x >> 6;
     // (the walk's first two words, requested together with the words that decide which walk it is: one round trip, not two in a row)
     const u32 total = *count_ptr;
-    const u32 start = mine ? ranges[tile_id] : 0xFFFFFFFFu;
-    const bool exact = nf_stamp == nullptr || (mine && nf_stamp[tile_id] == *nf_frame);   // (uniform per workgroup)
+    const u32 start = ranges[tile_id];
+    const bool exact = nf_stamp == nullptr || nf_stamp[tile_id] == *nf_frame;   // (uniform per workgroup)
     const bool long_on = HELP && ll_frame_on(lw, blocks_wanted, items_wanted);
-    if (long_on && mine && ((lw.flags[tile_id] >> sub) & 1u)) mine = false;   // (a long list: the tasks composite and write this block)
+    bool mine = true;
+    if (long_on && ((lw.flags[tile_id] >> sub) & 1u)) mine = false;   // (a long list: the tasks composite and write this block)
     if (mine) {
         if (exact)
-            rasterize_body<GAUSSIAN_MODE, WPW, TIMELINE, true>(settings, ti, splats, num_splats, ranges, sorted_keys, sorted_vals, count_ptr, max_entries, out_rgba8, out_alpha,
-                                                               out_ncontrib, issue_priority, timeline, tile_id, sub, threadIdx.x & 63u, total, start, s_geo, s_con, s_col);
+            rasterize_body<GAUSSIAN_MODE, true>(settings, ti, splats, num_splats, ranges, sorted_keys, sorted_vals, count_ptr, max_entries, out_rgba8, out_alpha,
+                                                out_ncontrib, issue_priority, tile_id, sub, threadIdx.x & 63u, total, start, s_geo, s_con, s_col);
         else
-            rasterize_body<GAUSSIAN_MODE, WPW, TIMELINE, false>(settings, ti, splats, num_splats, ranges, sorted_keys, sorted_vals, count_ptr, max_entries, out_rgba8, out_alpha,
-                                                                out_ncontrib, issue_priority, timeline, tile_id, sub, threadIdx.x & 63u, total, start, s_geo, s_con, s_col);
+            rasterize_body<GAUSSIAN_MODE, false>(settings, ti, splats, num_splats, ranges, sorted_keys, sorted_vals, count_ptr, max_entries, out_rgba8, out_alpha,
+                                                 out_ncontrib, issue_priority, tile_id, sub, threadIdx.x & 63u, total, start, s_geo, s_con, s_col);
     }
     if (long_on)
         long_forward_help(LongCtx{settings, ti, splats, ranges, sorted_keys, sorted_vals, count_ptr, num_splats, out_rgba8, out_alpha, out_ncontrib, nf_stamp, nf_frame}, lw,
@@ -524,40 +497,17 @@ int launch_rasterize(wdgs_device* dev, const RenderSettings& st, const TileInfo&
     if (ti.total_tiles == 0) return WDGS_OK;
     const u32 max_entries = max_batches * 256u;  // compat cap: 32 batches x 256 splats per tile; 0 = unlimited
     // (one-wave workgroups help backward_rasterize -- 303 -> 295.5 us -- but not this kernel: 119.2 vs 119.8 us, r03m; workgroup = tile stays)
-    static const bool one_wave = std::getenv("WDGS_RASTER_WPW") && std::getenv("WDGS_RASTER_WPW")[0] == '1';
     const u32 slots = ceil_div(ti.total_tiles, 8u) * 8u * 4u;   // 4 blocks per tile, tiles rounded up to a multiple of the 8 XCDs
-    // WDGS_FWR_PRIO=0: no issue priorities (same-box A/B)
-    static const u32 issue_priority = (std::getenv("WDGS_FWR_PRIO") && std::getenv("WDGS_FWR_PRIO")[0] == '0') ? 0u : 1u;
-    const u32 issue_priority_now = (issue_priority && slots <= 8192u) ? 1u : 0u;  // launches whose waves (4 per tile in either workgroup shape) are all resident from the start
+    const u32 issue_priority = (slots <= 8192u) ? 1u : 0u;  // launches whose waves are all resident from the start
     const LongWork lw = long_work ? *long_work : LongWork{};
 #define RASTER_ARGS st, ti, (const u32*)splats, num_splats, (const u32*)ranges, (const u32*)sorted_keys, (const u32*)sorted_vals, (const u32*)count_ptr, max_entries, \
-                    (u32*)out_rgba8, (float*)out_alpha, (u32*)out_ncontrib, issue_priority_now, (unsigned long long*)nullptr, (const u32*)nf_stamp, (const u32*)nf_frame, lw
-    // WDGS_FWR_TIMELINE=<file> (measurement tool; eager launches of the Gaussian mode in its default workgroup shape): per-wave records appended to the file
-    static const char* const timeline_file = std::getenv("WDGS_FWR_TIMELINE");
-    if (timeline_file && st.gaussian_mode >= 0.5f && !one_wave && !dev->capturing) {
-        unsigned long long* tl = nullptr;
-        const size_t bytes = (size_t)ti.total_tiles * 4u * 4u * sizeof(unsigned long long);
-        WDGS_CHECK_HIP(hipMalloc((void**)&tl, bytes));
-        WDGS_CHECK_HIP(hipMemsetAsync(tl, 0, bytes, dev->stream));
-        hipLaunchKernelGGL((rasterize_kernel<true, 4u, true>), dim3(ti.total_tiles), dim3(256), 0, dev->stream, st, ti, (const u32*)splats, num_splats, (const u32*)ranges,
-                           (const u32*)sorted_keys, (const u32*)sorted_vals, (const u32*)count_ptr, max_entries, (u32*)out_rgba8, (float*)out_alpha, (u32*)out_ncontrib,
-                           issue_priority_now, tl, (const u32*)nf_stamp, (const u32*)nf_frame, LongWork{});
-        std::vector<unsigned long long> host((size_t)ti.total_tiles * 16u);
-        WDGS_CHECK_HIP(hipMemcpyAsync(host.data(), tl, bytes, hipMemcpyDeviceToHost, dev->stream));
-        WDGS_CHECK_HIP(hipStreamSynchronize(dev->stream));
-        (void)hipFree(tl);
-        if (FILE* f = std::fopen(timeline_file, "ab")) { const u32 head[2] = {ti.total_tiles * 4u, ti.total_tiles}; std::fwrite(head, 4, 2, f); std::fwrite(host.data(), 8, host.size(), f); std::fclose(f); }
-        WDGS_CHECK_HIP(hipGetLastError());
-        return WDGS_OK;
-    }
+                    (u32*)out_rgba8, (float*)out_alpha, (u32*)out_ncontrib, issue_priority, (const u32*)nf_stamp, (const u32*)nf_frame, lw
     if (st.gaussian_mode >= 0.5f) {
-        // (long tile lists, longlist.h: Gaussian mode, uncapped lists, the default workgroup shape)
-        if (one_wave) WDGS_LAUNCH(dev, "rasterize", (rasterize_kernel<true, 1u>), dim3(slots), dim3(64), 0, RASTER_ARGS);
-        else if (lw.hdr && lw.threshold && max_entries == 0u) WDGS_LAUNCH(dev, "rasterize", (rasterize_kernel<true, 4u, false, true>), dim3(ti.total_tiles), dim3(256), 0, RASTER_ARGS);
-        else WDGS_LAUNCH(dev, "rasterize", (rasterize_kernel<true, 4u>), dim3(ti.total_tiles), dim3(256), 0, RASTER_ARGS);
+        // (long tile lists, longlist.h: Gaussian mode, uncapped lists)
+        if (lw.hdr && lw.threshold && max_entries == 0u) WDGS_LAUNCH(dev, "rasterize", (rasterize_kernel<true, true>), dim3(ti.total_tiles), dim3(256), 0, RASTER_ARGS);
+        else WDGS_LAUNCH(dev, "rasterize", (rasterize_kernel<true, false>), dim3(ti.total_tiles), dim3(256), 0, RASTER_ARGS);
     } else {
-        if (one_wave) WDGS_LAUNCH(dev, "rasterize_points", (rasterize_kernel<false, 1u>), dim3(slots), dim3(64), 0, RASTER_ARGS);
-        else WDGS_LAUNCH(dev, "rasterize_points", (rasterize_kernel<false, 4u>), dim3(ti.total_tiles), dim3(256), 0, RASTER_ARGS);
+        WDGS_LAUNCH(dev, "rasterize_points", (rasterize_kernel<false, false>), dim3(ti.total_tiles), dim3(256), 0, RASTER_ARGS);
     }
 #undef RASTER_ARGS
     WDGS_CHECK_HIP(hipGetLastError());

@@ -50,7 +50,6 @@ template <u32 ITEMS>
 __global__ __launch_bounds__(SORT_THREADS) void sort_hist_kernel(const u32* __restrict__ keys, const u32* __restrict__ count_ptr, DigitOf digit_of,
                                                                  u32 num_parts, u32* __restrict__ counts /*[RADIX][num_parts]*/, u32* __restrict__ ranges_init,
                                                                  u32 total_tiles, u32* __restrict__ marks_init) {
-    WD_STREAM_PRIO();
     constexpr u32 TILE = SORT_THREADS * ITEMS;  // keys per partition
     __shared__ u32 lh[SORT_THREADS / 64][RADIX];
     const u32 count = *count_ptr;
@@ -108,7 +107,6 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_hist_kernel(const u32* __re
 template <u32 ITEMS>
 __global__ __launch_bounds__(256) void sort_scan_rows_kernel(u32* __restrict__ counts, const u32* __restrict__ count_ptr, u32 num_parts,
                                                               u32* __restrict__ totals) {
-    WD_STREAM_PRIO();
     constexpr u32 TILE = SORT_THREADS * ITEMS;  // keys per partition
     __shared__ u32 s_w[4];
     const u32 active = (*count_ptr + TILE - 1u) / TILE;
@@ -150,7 +148,6 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u32* _
                                                                     const u32* __restrict__ count_ptr, DigitOf digit_of, u32 num_parts,
                                                                     const u32* __restrict__ offsets /*scanned rows*/, const u32* __restrict__ digit_totals,
                                                                     u32* __restrict__ ranges, u32 ranges_mode, u32 total_tiles) {
-    WD_STREAM_PRIO();
     constexpr u32 TILE = SORT_THREADS * ITEMS;  // keys per partition
     __shared__ u32 whist[SORT_THREADS / 64][RADIX];
     const u32 dmask = digit_of.dmask;
@@ -293,7 +290,6 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u32* _
 // instead of 23) -- one launch over T+1 waves instead of an init launch plus a pass over all E keys.
 __global__ __launch_bounds__(256) void tile_ranges_kernel(const u32* __restrict__ keys, const u32* __restrict__ count_ptr, u32 total_tiles,
                                                            u32* __restrict__ ranges) {
-    WD_STREAM_PRIO();
     const u32 t = blockIdx.x * 4u + (threadIdx.x >> 6);  // wave index = tile
     const u32 lane = threadIdx.x & 63u;
     if (t > total_tiles) return;
@@ -564,7 +560,6 @@ __device__ void long_list_build(const LongWork& lw, u32 t, u32 n) {
 
 __global__ __launch_bounds__(SEG_THREADS, 6) void segment_sort_kernel(u32* __restrict__ cur_k, u32* __restrict__ cur_v, u32* __restrict__ alt_k,
                                                                     u32* __restrict__ alt_v, const u32* __restrict__ ranges, u32 total_tiles, LongWork lw) {
-    WD_STREAM_PRIO();
     __shared__ u32 a_k[SEG_CAP], a_v[SEG_CAP];  // one pair: every pass reads its input into registers before anyone scatters
     __shared__ seg_hist_t whist[SEG_THREADS / 64][SEG_BINS];
     __shared__ u32 s_base[RADIX];
