@@ -307,6 +307,24 @@ static napi_value tiledRasterizerBlit(napi_env env, napi_callback_info info) {  
     WDGS_OK_OR_THROW(wdgs_tiled_rasterizer_blit((wdgs_tiled_rasterizer*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3])));
     return js_undefined(env);
 }
+// Depth images (include/webdgs.h: wdgs_tiled_rasterizer_encode_depth / get_depth, wdgs_depth_to_rgba8; the reference renders colour only and has no counterpart)
+static napi_value tiledRasterizerEncodeDepth(napi_env env, napi_callback_info info) {  // (op, kinds: WDGS_DEPTH_* bits)
+    ARGS(2);
+    WDGS_OK_OR_THROW(wdgs_tiled_rasterizer_encode_depth((wdgs_tiled_rasterizer*)get_ptr(env, argv[0]), get_u32(env, argv[1])));
+    return js_undefined(env);
+}
+static napi_value tiledRasterizerGetDepth(napi_env env, napi_callback_info info) {  // (op, kind: one WDGS_DEPTH_* bit) -> device pointer of f32[W*H]
+    ARGS(2);
+    void* p = nullptr;
+    WDGS_OK_OR_THROW(wdgs_tiled_rasterizer_get_depth((wdgs_tiled_rasterizer*)get_ptr(env, argv[0]), get_u32(env, argv[1]), &p));
+    return make_ptr(env, p);
+}
+static napi_value depthToRgba8(napi_env env, napi_callback_info info) {  // (device, depthPtr, width, height, near, far, rgba8Ptr)
+    ARGS(7);
+    WDGS_OK_OR_THROW(wdgs_depth_to_rgba8((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]), (float)get_f64(env, argv[4]),
+                                         (float)get_f64(env, argv[5]), get_ptr(env, argv[6])));
+    return js_undefined(env);
+}
 static napi_value bufferClear(napi_env env, napi_callback_info info) {  // encoder.clearBuffer: (device, ptr, byteLength)
     ARGS(3);
     WDGS_OK_OR_THROW(wdgs_memset((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), 0, (size_t)get_f64(env, argv[2])));
@@ -881,6 +899,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(tiledBackwardCreate); EXPORT_FN(tiledBackwardEncode); EXPORT_FN(tiledBackwardGradients); EXPORT_FN(tiledBackwardDestroy);
     EXPORT_FN(optimizerCreate); EXPORT_FN(optimizerStep); EXPORT_FN(optimizerGetIteration); EXPORT_FN(optimizerDestroy);
     EXPORT_FN(tiledForwardSet); EXPORT_FN(tiledForwardCheck); EXPORT_FN(tiledForwardSetLongLists); EXPORT_FN(tiledForwardLongListStats); EXPORT_FN(tiledRasterizerBlit); EXPORT_FN(bufferClear);
+    EXPORT_FN(tiledRasterizerEncodeDepth); EXPORT_FN(tiledRasterizerGetDepth); EXPORT_FN(depthToRgba8);
     EXPORT_FN(encoderBegin); EXPORT_FN(encoderFinish); EXPORT_FN(queueSubmit); EXPORT_FN(commandBufferDestroy); EXPORT_FN(queueOnSubmittedWorkDone);
     EXPORT_FN(tiledBackwardMetric); EXPORT_FN(tiledBackwardGet); EXPORT_FN(downsampleRGBA8); EXPORT_FN(imageSSE); EXPORT_FN(imageSSIM);
     EXPORT_FN(optimizerStateSizes); EXPORT_FN(optimizerCreateWithState); EXPORT_FN(optimizerState); EXPORT_FN(optimizerHyperparameters);

@@ -1,5 +1,5 @@
 // Typings of viewer.js: src/viewer.ts without the browser.
-import { HipBuffer, HipDevice, HipEncoder, PointCloud, RenderMode, TiledForwardPass } from './webdgs_hip';
+import { DepthKind, HipBuffer, HipDevice, HipEncoder, PointCloud, RenderMode, TiledForwardPass } from './webdgs_hip';
 import { Camera, CanvasLike } from './camera';
 export type FrameTarget = HipBuffer & { width: number; height: number };
 export class Viewer {
@@ -15,6 +15,8 @@ export class Viewer {
   currentTexture(): FrameTarget;
   resize(width: number, height: number): void;
   readFrame(): Uint8Array;
+  /** The current camera's depth image (width * height f32), rendered in gaussian mode; the render mode is left as it was.  No reference counterpart. */
+  renderDepth(kind?: DepthKind): Float32Array;
   savePNG(file: string): void;
   destroy(): void;
 }

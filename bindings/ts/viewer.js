@@ -73,10 +73,10 @@ class Viewer {
   }
   /** New canvas size (the ResizeObserver callback of viewer.ts:37-40). */
   resize(width, height) { this.canvas.width = width; this.canvas.height = height; if (this.canvas.clientWidth !== undefined) { this.canvas.clientWidth = width; this.canvas.clientHeight = height; } this.handleResize(); }
-  /** The presented image as a Uint8Array of width * height * 4 bytes (synchronises). */
-  readFrame() {
-    // If the frame's tile-entry list outran what the library sized for the cloud (the reference would show the truncated picture; the library reports it),
-    // the viewer's passes are rebuilt around larger lists and the frame is rendered again -- other owners' reports on the same device are left to them.
+  /** Waits for this viewer's frame.  If its tile-entry list outran what the library sized for the cloud (the reference would show the truncated picture; the
+   *  library reports it), the viewer's passes are rebuilt around larger lists and rerender() encodes the frame again -- other owners' reports on the same
+   *  device are left to them. */
+  settleCapacity(rerender) {
     for (let attempt = 0; attempt < 4 && this.forwardPass; attempt++) {   // this viewer's own pass: its word is consumed by its own check
       try {
         this.forwardPass.check();
@@ -91,11 +91,34 @@ class Viewer {
         if (!m) throw e;
         this.tileEntries = Math.min(Math.max(2 * Number(m[2]), Math.floor(Number(m[1]) * 1.5)), 0xFFFFF000);
         this.buildPasses();
-        this.render(null);
+        rerender();
       }
     }
+  }
+  /** The presented image as a Uint8Array of width * height * 4 bytes (synchronises). */
+  readFrame() {
+    this.settleCapacity(() => this.render(null));
     const f = this.currentTexture();
     return new Uint8Array(this.device.readBuffer(f, 4 * f.width * f.height));
+  }
+  /** The current camera's depth image as a Float32Array of width * height values ('expected' | 'median' | 'weight_sum'), rendered in gaussian mode
+   *  through the viewer's own passes whatever its render mode, which is left as it was (synchronises).  No reference counterpart. */
+  renderDepth(kind) {
+    if (!this.forwardPass || !this.rasterizer || !this.pointCloud) throw new Error('Viewer.renderDepth: no point cloud set');
+    const k = kind === undefined ? 'expected' : kind, w = this.canvas.width, h = this.canvas.height;
+    const encode = () => {
+      this.forwardPass.setRenderMode('gaussian');   // depth has weights in gaussian mode only; the viewer's own mode is put back below
+      try {
+        this.forwardPass.encode(null);
+        this.rasterizer.encode(null, w, h);
+        this.rasterizer.encodeDepth(null, [k]);
+      } finally {
+        this.forwardPass.setRenderMode(this.settings.renderMode === undefined ? 'pointcloud' : this.settings.renderMode);
+      }
+    };
+    encode();
+    this.settleCapacity(encode);
+    return new Float32Array(this.device.readBuffer(this.rasterizer.getDepthTextureView(k), 4 * w * h));
   }
   savePNG(file) { const f = this.currentTexture(); fs.writeFileSync(file, encodePNG(this.readFrame(), f.width, f.height)); }
   destroy() {

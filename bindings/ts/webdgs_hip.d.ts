@@ -110,11 +110,17 @@ export class TiledForwardPass {
   longListStats(): { blocksWanted: number; itemsWanted: number; forwardQueue: number; backwardQueue: number; rowsUsed: number; rowsWanted: number; stalled: number; maxItems: number; maxBlocks: number; maxRows: number; threshold: number };
   destroy(): void;
 }
+export type DepthKind = 'expected' | 'median' | 'weight_sum';
+export const DEPTH_KINDS: { expected: 1; median: 2; weight_sum: 4 };
 export class TiledRasterizer {
   constructor(config: { device: HipDevice; forwardPass: TiledForwardPass; format?: string });
   encode(encoder: HipEncoder | null, width: number, height: number): void;
   getOutputTextureView(): HipBuffer; getAlphaTextureView(): HipBuffer; getNContribTextureView(): HipBuffer; getTileOffsetsBuffer(): HipBuffer;
   /** `target` may carry its own `width` / `height` (a canvas of another size); the clear colour is accepted for signature compatibility only. */
+  /** Depth images of the frame the last encode rasterized (no reference counterpart); default kinds: ['expected']. */
+  encodeDepth(encoder: HipEncoder | null, kinds?: DepthKind | DepthKind[] | number): void;
+  /** f32[W*H] of one kind the last encodeDepth wrote (default 'expected'). */
+  getDepthTextureView(kind?: DepthKind): HipBuffer;
   blitToTexture(encoder: HipEncoder | null, target: HipBuffer & { width?: number; height?: number }, clearColor?: { r: number; g: number; b: number; a: number }): void;
   destroy(): void;
 }
@@ -210,6 +216,8 @@ export function imagePSNR(device: HipDevice, a: HipBuffer, b: HipBuffer, numPixe
 export function psnrFromSSE(sse: number | bigint, numPixels: number): number;
 export function encodeImageSSE(device: HipDevice, a: HipBuffer, b: HipBuffer, numPixels: number, out: HipBuffer): void;
 export function encodeImageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: number, height: number, out: HipBuffer, map?: HipBuffer | null): void;
+/** A depth image as rgba8 for presentation: inverse depth between near (white) and far (black), depth 0 black.  No reference counterpart. */
+export function depthToRGBA8(device: HipDevice, depth: HipBuffer, width: number, height: number, near: number, far: number, target: HipBuffer): void;
 export function imageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: number, height: number, map?: HipBuffer | null): number;
 /** The C-ABI communicator (wdgs_comm_*): RCCL on the device's stream, for the data-parallel step of a host without torch.distributed. */
 export class Communicator {

@@ -216,6 +216,17 @@ class TiledForwardPass {                 // tiled-forward-pass.ts:62
   destroy() { if (this.destroyed) return; this.destroyed = true; addon.tiledForwardDestroy(this.handle); this.handle = null; }   // (a call after destroy meets the library's null check, not freed memory)
 }
 
+const DEPTH_KINDS = { expected: 1, median: 2, weight_sum: 4 };   // WDGS_DEPTH_*
+function depthMask(kinds) {
+  if (typeof kinds === 'number') return kinds;
+  let mask = 0;
+  for (const k of (typeof kinds === 'string' ? [kinds] : kinds)) {
+    if (!(k in DEPTH_KINDS)) throw new Error(`unknown depth kind '${k}': one of ${Object.keys(DEPTH_KINDS).join(', ')}`);
+    mask |= DEPTH_KINDS[k];
+  }
+  return mask;
+}
+
 class TiledRasterizer {                  // tiled-rasterizer.ts:34
   constructor(config) {
     this.device = config.device; this.destroyed = false; this.w = 0; this.h = 0;
@@ -226,6 +237,11 @@ class TiledRasterizer {                  // tiled-rasterizer.ts:34
   getAlphaTextureView() { return this.device.view(addon.tiledRasterizerGet(this.handle, 1), 4 * this.w * this.h); }
   getNContribTextureView() { return this.device.view(addon.tiledRasterizerGet(this.handle, 2), 4 * this.w * this.h); }
   getTileOffsetsBuffer() { return this.device.view(addon.tiledRasterizerGet(this.handle, 3), 4 * (Math.ceil(this.w / 16) * Math.ceil(this.h / 16) + 1)); }
+  /** Depth images of the frame the last encode rasterized (include/webdgs.h, DESIGN.md section 10; no reference counterpart): `kinds` is an array of
+   *  DEPTH_KINDS names ('expected' | 'median' | 'weight_sum'), one name, or the bit mask.  The first use of a kind allocates its image and cannot be recorded. */
+  encodeDepth(_encoder, kinds) { addon.tiledRasterizerEncodeDepth(this.handle, depthMask(kinds === undefined ? ['expected'] : kinds)); }
+  /** f32[W*H] of one kind the last encodeDepth wrote; throws (WDGS_E_STATE) otherwise. */
+  getDepthTextureView(kind) { return this.device.view(addon.tiledRasterizerGetDepth(this.handle, depthMask([kind === undefined ? 'expected' : kind])), 4 * this.w * this.h); }
   /** blitToTexture(encoder, targetView, clearColor?) (tiled-rasterizer.ts:333-357): `target` is an rgba8 image buffer; it may carry its own
    *  `width` / `height` (a canvas of another size: the blit is a bilinear resample), otherwise it has the rasterizer's size.  The blit covers
    *  the whole target, so the reference's clear colour never shows and is accepted only for signature compatibility. */
@@ -467,6 +483,10 @@ function imageSSIM(device, a, b, width, height, map) {
   return v;
 }
 
+/** A depth image (f32, getDepthTextureView) as rgba8 for presentation: inverse depth between `near` (white) and `far` (black), depth 0 black, alpha 255
+ *  (wdgs_depth_to_rgba8).  Stream-ordered; no reference counterpart. */
+function depthToRGBA8(device, depth, width, height, near, far, target) { addon.depthToRgba8(device.handle, depth.ptr, width, height, near, far, target.ptr); }
+
 /** The C-ABI communicator (wdgs_comm_*, include/webdgs.h): RCCL queued on the device's stream by the library itself -- the transport of the
  *  data-parallel step for a host without torch.distributed.  `uniqueId` (ArrayBuffer, 128 bytes) comes from Communicator.uniqueId() on rank 0 and
  *  reaches the other ranks over any host channel (parallel.js ships it through a file). */
@@ -489,6 +509,6 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

@@ -256,6 +256,23 @@ int wdgs_tiled_rasterizer_get_tile_offsets(wdgs_tiled_rasterizer* op, void** ran
  * WDGS_E_STATE before the first encode, as the reference throws. */
 int wdgs_tiled_rasterizer_blit(wdgs_tiled_rasterizer* op, void* target_rgba8_dev, uint32_t target_width, uint32_t target_height);
 
+/* Depth images.  The reference renders colour only and has no counterpart to any of the three entries below.
+ * encode_depth composites the view-space depths of the frame the last encode rasterized, with the weights w_i = alpha_i (1 - A) the colour was
+ * composited with (same records, same order, same arithmetic): WDGS_DEPTH_WEIGHT_SUM is A = sum w_i (1.0f - A is the alpha texture bit for bit),
+ * WDGS_DEPTH_EXPECTED is (sum w_i z_i) / A (0 where A is not > 0), WDGS_DEPTH_MEDIAN the z of the first record at which A reaches 0.5 (0 if none).
+ * `kinds` is a non-empty set of these bits (WDGS_E_INVALID otherwise); only the images asked for are written, and each is allocated at the first
+ * encode_depth that asks for it -- which therefore cannot be recorded (WDGS_E_STATE); later ones can.  WDGS_E_STATE before encode, and when the
+ * forward pass is in point-cloud render mode (no weights).  No reference counterpart. */
+#define WDGS_DEPTH_EXPECTED   1u
+#define WDGS_DEPTH_MEDIAN     2u
+#define WDGS_DEPTH_WEIGHT_SUM 4u
+int wdgs_tiled_rasterizer_encode_depth(wdgs_tiled_rasterizer* op, uint32_t kinds);
+/* f32[W*H] of ONE kind; WDGS_E_STATE if the last encode_depth did not write it.  No reference counterpart. */
+int wdgs_tiled_rasterizer_get_depth(wdgs_tiled_rasterizer* op, uint32_t kind, void** f32_dev);
+/* A depth image as rgba8 for presentation: t = clamp((1/z - 1/far) / (1/near - 1/far), 0, 1), grey = round(255 t), alpha 255; depth 0 (no weight
+ * at the pixel) is black.  Requires 0 < near < far < inf.  Writes width*height pixels of any rgba8 buffer.  No reference counterpart. */
+int wdgs_depth_to_rgba8(wdgs_device* dev, const void* depth_f32_dev, uint32_t width, uint32_t height, float near_z, float far_z, void* rgba8_dev);
+
 /* ---------------------------------------------------------------- TiledBackwardPass
  * Replaces `new TiledBackwardPass(device, pointCloud, config)` (renderers/tiled-backward-pass.ts:136-140, config 27-34,
  * TrainingConfig 19-25), .encode (592-740), .computeLossOnly (383), .computeMetricMap (425), .computeMetricCounts (514),

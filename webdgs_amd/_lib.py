@@ -196,6 +196,9 @@ SIGNATURES = {
     "wdgs_tiled_rasterizer_get_alpha": (_I, [_P, C.POINTER(_P)]),
     "wdgs_tiled_rasterizer_get_n_contrib": (_I, [_P, C.POINTER(_P)]),
     "wdgs_tiled_rasterizer_get_tile_offsets": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_tiled_rasterizer_encode_depth": (_I, [_P, _U]),
+    "wdgs_tiled_rasterizer_get_depth": (_I, [_P, _U, C.POINTER(_P)]),
+    "wdgs_depth_to_rgba8": (_I, [_P, _P, _U, _U, _F, _F, _P]),
     "wdgs_tiled_backward_create": (_I, [_P, C.POINTER(TiledBackwardConfig), C.POINTER(_P)]),
     "wdgs_tiled_backward_resize": (_I, [_P, _U]),
     "wdgs_tiled_backward_destroy": (_I, [_P]),

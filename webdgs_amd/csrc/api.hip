@@ -23,6 +23,8 @@ extern "C" void sorter_set_final_out_index(wdgs_sorter* s, int i);
 int launch_update_stats(wdgs_device*, u32, const void*, const void*, u32, void*, void*, void*);
 int launch_emit(wdgs_device*, u32, const void*, const void*, const void*, void*, const void*, const RenderSettings&, const TileInfo&, void*, void*, u32);
 int launch_tile_ranges(wdgs_device*, const void*, const void*, u32, void*);
+int launch_depth_composite(wdgs_device*, const RenderSettings&, const TileInfo&, const void*, u32, const void*, const void*, const void*, const void*, const void*, u32,
+                           void*, void*, void*, const void*, const void*);
 int launch_rasterize(wdgs_device*, const RenderSettings&, const TileInfo&, const void*, u32, const void*, const void*, const void*, const void*, u32, void*,
                      void*, void*, const void*, const void*, const LongWork*);
 int launch_loss_grad(wdgs_device*, u32, u32, const void*, const void*, const wdgs_training_config&, void*, void*, u32, const void*);
@@ -218,6 +220,10 @@ struct wdgs_tiled_rasterizer {
     float* alpha;
     u32* n_contrib;
     bool encoded;
+    // depth images (depth.hip), f32[W*H] each, in the order of the WDGS_DEPTH_* bits: allocated per kind at its first encode_depth
+    float* depth[3];
+    u32 depth_width, depth_height;   // the size they were allocated for
+    u32 depth_encoded;               // the kinds the last encode_depth wrote
 };
 
 struct wdgs_tiled_backward {
@@ -1154,6 +1160,7 @@ int wdgs_tiled_rasterizer_destroy(wdgs_tiled_rasterizer* op) {
     free_dev(op->rgba8);
     free_dev(op->alpha);
     free_dev(op->n_contrib);
+    for (float* img : op->depth) free_dev(img);
     delete op;
     return WDGS_OK;
 }
@@ -1198,6 +1205,54 @@ int wdgs_tiled_rasterizer_encode(wdgs_tiled_rasterizer* op, uint32_t width, uint
                               op->alpha, op->n_contrib, f->nf_stamp, f->stats + FRAME_WORD,
                               (f->ranges_valid && f->long_lists.hdr && !op->compat_caps) ? &f->long_lists : nullptr));   // (the table this pass's sort built and marked)
     op->encoded = true;
+    return WDGS_OK;
+}
+
+// Depth images of the frame the last encode composited (depth.hip; no counterpart in the reference, which renders colour only).  The walk is
+// launch_rasterize's without the long-list work: same settings, tile grid, Splats, range table, sorted keys / values, entry count, compat cap and
+// non-finite stamps, plus the forward pass's depth words.
+int wdgs_tiled_rasterizer_encode_depth(wdgs_tiled_rasterizer* op, uint32_t kinds) {
+    WDGS_REQUIRE(op, WDGS_E_INVALID, "wdgs_tiled_rasterizer_encode_depth: null op");
+    constexpr uint32_t all = WDGS_DEPTH_EXPECTED | WDGS_DEPTH_MEDIAN | WDGS_DEPTH_WEIGHT_SUM;
+    WDGS_REQUIRE(kinds != 0u && (kinds & ~all) == 0u, WDGS_E_INVALID, "wdgs_tiled_rasterizer_encode_depth: kinds 0x%x is not a non-empty set of WDGS_DEPTH_* bits", kinds);
+    wdgs_tiled_forward* f = op->fwd;
+    WDGS_REQUIRE(op->encoded && f->encoded && op->ranges_used, WDGS_E_STATE, "TiledRasterizer.encodeDepth before encode: depth is composited from the frame encode rasterized");
+    WDGS_REQUIRE(op->width == f->cfg.viewport_width && op->height == f->cfg.viewport_height, WDGS_E_STATE,
+                 "TiledRasterizer.encodeDepth: the forward pass viewport changed to %ux%u since the last encode (%ux%u)", f->cfg.viewport_width, f->cfg.viewport_height,
+                 op->width, op->height);
+    WDGS_REQUIRE(f->settings.gaussian_mode >= 0.5f, WDGS_E_STATE, "TiledRasterizer.encodeDepth: the forward pass is in point-cloud render mode, which has no weights");
+    wdgs_device* d = op->dev;
+    if (op->depth_width != op->width || op->depth_height != op->height) {   // a size change: the images are re-made per kind below
+        bool any = false;
+        for (float* img : op->depth) any = any || img != nullptr;
+        if (any) {
+            WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledRasterizer.encodeDepth re-allocates its images after a size change: run one eager encodeDepth before recording");
+            (void)wdgs_sync_lanes(d);
+            for (float*& img : op->depth) { free_dev(img); img = nullptr; }
+        }
+        op->depth_width = op->width;
+        op->depth_height = op->height;
+    }
+    for (u32 k = 0; k < 3u; k++) {
+        if (!((kinds >> k) & 1u) || op->depth[k]) continue;
+        WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledRasterizer.encodeDepth allocates a depth image on first use of its kind: run one eager encodeDepth before recording");
+        WDGS_TRY(wdgs_alloc((void**)&op->depth[k], (size_t)op->width * op->height * 4, true, d->stream));
+    }
+    const int fo = wdgs_sorter_final_out_index(f->sorter);
+    WDGS_TRY(launch_depth_composite(d, f->settings, f->tile_info, f->splats, f->cfg.num_points, f->depths, op->ranges_used, wdgs_sorter_keys(f->sorter, fo),
+                                    wdgs_sorter_values(f->sorter, fo), f->stats, op->compat_caps ? 32u : 0u, (kinds & WDGS_DEPTH_WEIGHT_SUM) ? op->depth[2] : nullptr,
+                                    (kinds & WDGS_DEPTH_EXPECTED) ? op->depth[0] : nullptr, (kinds & WDGS_DEPTH_MEDIAN) ? op->depth[1] : nullptr, f->nf_stamp,
+                                    f->stats + FRAME_WORD));
+    op->depth_encoded = kinds;
+    return WDGS_OK;
+}
+int wdgs_tiled_rasterizer_get_depth(wdgs_tiled_rasterizer* op, uint32_t kind, void** out) {
+    WDGS_REQUIRE(op && out, WDGS_E_INVALID, "wdgs_tiled_rasterizer_get_depth: null argument");
+    WDGS_REQUIRE(kind == WDGS_DEPTH_EXPECTED || kind == WDGS_DEPTH_MEDIAN || kind == WDGS_DEPTH_WEIGHT_SUM, WDGS_E_INVALID,
+                 "wdgs_tiled_rasterizer_get_depth: kind 0x%x is not one WDGS_DEPTH_* bit", kind);
+    const u32 k = kind == WDGS_DEPTH_EXPECTED ? 0u : kind == WDGS_DEPTH_MEDIAN ? 1u : 2u;
+    WDGS_REQUIRE((op->depth_encoded & kind) && op->depth[k], WDGS_E_STATE, "TiledRasterizer: depth image of this kind not encoded yet (call encodeDepth with it first)");
+    *out = op->depth[k];
     return WDGS_OK;
 }
 #define RASTER_GETTER(fn, field, what)                                                                            \

@@ -292,6 +292,26 @@ def cameraUniforms(cam: dict, width: Optional[int] = None, height: Optional[int]
     return out
 
 
+def backprojectDepth(depth: np.ndarray, camera) -> np.ndarray:
+    """World-space points ``[K, 3]`` float32 of the pixels of a depth image ``[H, W]`` whose depth is > 0, in row-major pixel order: the inverse of the
+    forward pass's projection for a 68-float camera block (``cameraUniforms``), where a point at view-space ``(x, y, z)`` lands on pixel
+    ``((P00 x / z) / 2 + 1/2) W, (-(P11 y / z) / 2 + 1/2) H``.  The pixel centre ``(i + 0.5, j + 0.5)`` and the depth give the view-space point, the
+    block's inverse view matrix the world point.  Evaluated in binary64 from the block's float32 entries, stored as float32.  Host side (numpy); what a
+    point export or a TSDF fusion starts from.  No reference counterpart."""
+    d = np.asarray(depth, np.float32)
+    if d.ndim != 2:
+        raise ValueError("backprojectDepth expects an [H, W] depth image")
+    blk = np.asarray(camera, np.float32).reshape(68).astype(np.float64)
+    h, w = d.shape
+    ys, xs = np.nonzero(d > 0)
+    z = d[ys, xs].astype(np.float64)
+    ndc_x = 2.0 * (xs + 0.5) / w - 1.0
+    ndc_y = 1.0 - 2.0 * (ys + 0.5) / h
+    view = np.stack([ndc_x * z / blk[32], ndc_y * z / blk[37], z, np.ones_like(z)], axis=1)   # proj[0][0], proj[1][1] (column-major)
+    view_inv = blk[16:32].reshape(4, 4).T
+    return (view @ view_inv.T)[:, :3].astype(np.float32)
+
+
 # ----------------------------------------------------------------------------- held-out split (no reference counterpart)
 def holdoutSplit(cameras: list, images: list, every: int = 8) -> tuple:
     """Train / test split of a dataset by the Mip-NeRF 360 / 3DGS ``--eval`` convention: view ``i`` is a test view when ``i % every == 0``.

@@ -495,6 +495,18 @@ class TiledForwardPass:
 
 
 # ----------------------------------------------------------------------------- TiledRasterizer
+DEPTH_KINDS = {"expected": 1, "median": 2, "weight_sum": 4}  # WDGS_DEPTH_* (include/webdgs.h)
+
+
+def _depth_mask(kinds) -> int:
+    mask = 0
+    for k in ((kinds,) if isinstance(kinds, str) else kinds):
+        if k not in DEPTH_KINDS:
+            raise ValueError(f"unknown depth kind {k!r}: one of {sorted(DEPTH_KINDS)}")
+        mask |= DEPTH_KINDS[k]
+    return mask
+
+
 class TiledRasterizer:
     """``TiledRasterizer`` (``src/renderers/tiled-rasterizer.ts:34-368``) without the swap-chain blit."""
 
@@ -528,6 +540,18 @@ class TiledRasterizer:
     def getTileOffsetsBuffer(self) -> HipBuffer:
         tiles = ((self.width + 15) // 16) * ((self.height + 15) // 16)
         return self._get(self.device.lib.wdgs_tiled_rasterizer_get_tile_offsets, 4 * (tiles + 1))
+
+    def encodeDepth(self, encoder: Optional[HipEncoder], kinds=("expected",)) -> None:
+        """Depth images of the frame the last ``encode`` rasterized (no reference counterpart): ``kinds`` is a sequence of
+        ``DEPTH_KINDS`` names or the bit mask itself.  The first use of a kind allocates its image and cannot be recorded."""
+        mask = int(kinds) if isinstance(kinds, (int, np.integer)) else _depth_mask(kinds)
+        check(self.device.lib.wdgs_tiled_rasterizer_encode_depth(self.handle, mask))
+
+    def getDepthTextureView(self, kind: str = "expected") -> HipBuffer:
+        """f32[W*H] of one kind the last ``encodeDepth`` wrote; raises ``StateError`` otherwise."""
+        p = C.c_void_p()
+        check(self.device.lib.wdgs_tiled_rasterizer_get_depth(self.handle, _depth_mask((kind,)), C.byref(p)))
+        return self.device.view(p.value, 4 * self.width * self.height)
 
     def blitToTexture(self, encoder: Optional[HipEncoder], target: HipBuffer, width: Optional[int] = None, height: Optional[int] = None) -> None:
         """``blitToTexture(encoder, targetView)`` (tiled-rasterizer.ts:333-357): ``target`` is an rgba8 image buffer of
@@ -694,6 +718,15 @@ class TiledBackwardPass:
 def downsampleRGBA8(device: HipDevice, src: HipBuffer, src_w: int, src_h: int, dst: HipBuffer, dst_w: int, dst_h: int) -> None:
     """The GT down-sample render pass of ``trainer.ts:303-328`` (``blit.wgsl`` ``fs_main`` with a linear sampler)."""
     check(device.lib.wdgs_downsample_rgba8(device.handle, src.ptr, src_w, src_h, dst.ptr, dst_w, dst_h))
+
+
+def depthToRGBA8(device: HipDevice, depth: HipBuffer, width: int, height: int, near: float, far: float, target: HipBuffer) -> None:
+    """A depth image (f32, ``getDepthTextureView``) as rgba8 for presentation: inverse depth between ``near`` (white) and ``far`` (black), depth 0
+    black, alpha 255 (``wdgs_depth_to_rgba8``).  Stream-ordered; no reference counterpart."""
+    n = int(width) * int(height)
+    if depth.size < 4 * n or target.size < 4 * n:
+        raise ValueError(f"depthToRGBA8: buffers too small for {width}x{height}")
+    check(device.lib.wdgs_depth_to_rgba8(device.handle, depth.ptr, int(width), int(height), float(near), float(far), target.ptr))
 
 
 def encodeImageSSE(device: HipDevice, a: HipBuffer, b: HipBuffer, num_pixels: int, out: HipBuffer) -> None:

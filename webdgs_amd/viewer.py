@@ -16,7 +16,7 @@ import numpy as np
 
 from . import loaders
 from ._lib import CapacityError
-from .ops import HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer
+from .ops import HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer, depthToRGBA8
 
 
 def encodePNG(rgba: np.ndarray) -> bytes:
@@ -151,11 +151,11 @@ class Viewer:
             self.forwardPass.setViewport(self.width, self.height)
 
     # ---- presentation
-    def readFrame(self) -> np.ndarray:
-        """The presented image as ``[H, W, 4]`` uint8 (synchronises).  If the frame's tile-entry list outran what the library sized for the cloud
-        (the reference would show the truncated picture; the library reports it), the viewer's passes are rebuilt around larger lists and the
-        frame is rendered again.  (A report about this viewer's pass may have been consumed by another owner's wait -- a Trainer on the same device:
-        it was left in ``device.capacityReports``, and is answered here.)"""
+    def _settle_capacity(self, rerender) -> None:
+        """Waits for this viewer's frame.  If its tile-entry list outran what the library sized for the cloud (the reference would show the truncated
+        picture; the library reports it), the viewer's passes are rebuilt around larger lists and ``rerender()`` encodes the frame again.  (A report
+        about this viewer's pass may have been consumed by another owner's wait -- a Trainer on the same device: it was left in
+        ``device.capacityReports``, and is answered here.)"""
         import re
         for _ in range(4):  # this viewer's own pass: its word is consumed by its own check
             if self.forwardPass is None:
@@ -173,8 +173,51 @@ class Viewer:
                     raise
                 self._tile_entries = min(max(2 * named[0][1], int(named[0][0] * 1.5)), 0xFFFFF000)
                 self._build_passes()
-                self.render(None)
+                rerender()
+
+    def readFrame(self) -> np.ndarray:
+        """The presented image as ``[H, W, 4]`` uint8 (synchronises; a frame whose tile-entry list outran the passes is rendered again around
+        larger ones, ``_settle_capacity``)."""
+        self._settle_capacity(lambda: self.render(None))
         return self.frameBuffer.read(np.uint8, 4 * self.width * self.height).reshape(self.height, self.width, 4)
+
+    # ---- depth (DESIGN.md section 10; no reference counterpart)
+    def _encode_depth(self, kind: str) -> None:
+        self.forwardPass.setRenderMode("gaussian")   # depth has weights in gaussian mode only; the viewer's own mode is put back below
+        try:
+            self.forwardPass.encode(None)
+            self.rasterizer.encode(None, self.width, self.height)
+            self.rasterizer.encodeDepth(None, (kind,))
+        finally:
+            self.forwardPass.setRenderMode(self._settings.get("renderMode", "pointcloud"))
+
+    def renderDepth(self, kind: str = "expected") -> np.ndarray:
+        """The current camera's depth image ``[H, W]`` float32 (``ops.DEPTH_KINDS``), rendered in gaussian mode through the viewer's own passes
+        whatever its render mode, which is left as it was (synchronises).  The swap-chain image is not touched; the passes' colour images hold the
+        gaussian-mode frame afterwards, until the next ``render``."""
+        if self.forwardPass is None or self.rasterizer is None or self.pointCloud is None:
+            raise RuntimeError("Viewer.renderDepth: no point cloud set")
+        self._encode_depth(kind)
+        self._settle_capacity(lambda: self._encode_depth(kind))
+        return self.rasterizer.getDepthTextureView(kind).read(np.float32, self.width * self.height).reshape(self.height, self.width)
+
+    def saveDepthPNG(self, path: str, near: Optional[float] = None, far: Optional[float] = None, kind: str = "expected") -> None:
+        """The depth image as a grey PNG (inverse depth, near white, far black, no depth black).  ``near`` / ``far`` default to the smallest / largest
+        non-zero depth of the frame."""
+        d = self.renderDepth(kind)
+        seen = d[np.isfinite(d) & (d > 0)]
+        lo = float(near) if near is not None else (float(seen.min()) if seen.size else 1.0)
+        hi = float(far) if far is not None else (float(seen.max()) if seen.size else 2.0)
+        if not hi > lo:   # (one depth only: any range around it)
+            hi = float(np.nextafter(np.float32(lo), np.float32(np.inf))) * 2.0
+        out = self.device.createBuffer(4 * self.width * self.height, "depth presentation")
+        try:
+            depthToRGBA8(self.device, self.rasterizer.getDepthTextureView(kind), self.width, self.height, lo, hi, out)
+            rgba = out.read(np.uint8, 4 * self.width * self.height).reshape(self.height, self.width, 4)
+        finally:
+            out.destroy()
+        with open(path, "wb") as f:
+            f.write(encodePNG(rgba))
 
     def savePNG(self, path: str) -> None:
         with open(path, "wb") as f:
