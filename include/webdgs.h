@@ -369,6 +369,15 @@ int wdgs_image_ssim_rgb8(wdgs_device* dev, const void* a_rgba8_dev, const void* 
  * 6 sqrt, 7 1/x), so that a parity suite can compare them with its oracle directly. */
 int wdgs_debug_eval_math(wdgs_device* dev, uint32_t which, uint32_t count, const void* in_u32_dev, void* out_u32_dev);
 
+/* Test hook, not part of the reference's surface: runs one route of the forward pass's tile sort on the (key, value) pairs that lie in
+ * ping-pong 0 of `s` (key = (tile + 1) << 16 | depth16; the count is stats_dev[0], as always) for a grid of num_tiles_x x num_tiles_y
+ * tiles, and writes the per-tile range table into ranges_u32_dev (u32[T + 1], T = num_tiles_x * num_tiles_y: the first index of each
+ * tile, 0xFFFFFFFF for an empty one, ranges[T] = count).  route 0: the tile passes on the tile bits + the per-tile depth sort (any grid
+ * of 1..65534 tiles); route 1: one pass on the tile row + the per-tile depth sort, for pairs already in tile-column order (2..256
+ * columns, <= 256 rows); route 2: the range search alone, on keys the caller has sorted.  The sorted pairs are in
+ * ping_pong[final_out_index].  Long tile lists are not built.  WDGS_E_INVALID for a grid the forward pass never asks for. */
+int wdgs_debug_sort_tiles(wdgs_sorter* s, uint32_t route, uint32_t num_tiles_x, uint32_t num_tiles_y, void* ranges_u32_dev);
+
 /* ---------------------------------------------------------------- Optimizer
  * Replaces allocateOptimizerStateBuffers (renderers/optimizer.ts:27-38), `new Optimizer(device, pointCloud, params?,
  * initialState?)` (71-88), .step (295-350), hyperparameter accessors (256-278), .destroy (352). */

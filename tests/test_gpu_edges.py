@@ -141,9 +141,10 @@ def test_empty_point_cloud(hip_device):
 
 @pytest.mark.parametrize("w,h,fy,kind", [(96, 64, 70.0, "oversized"), (320, 208, 230.0, "lds-two-pass")])
 def test_sort_paths_wide_depth_span_and_oversized_tiles(hip_device, orc, w, h, fy, kind):
-    """The tile-structured sort has three per-tile paths (sort.hip, segment_sort): one 10-bit pass when the tile's depth span is below
-    1024 depth16 steps, two 8-bit passes when it is wider, and the same two passes through global memory for tiles with more than 2048
-    entries.  The synthetic scenes (z in [2, 10]) only ever take the first: here every Gaussian is moved along its view ray by a
+    """The tile-structured sort has five per-tile paths (sort.hip, segment_sort): one pass on an 8-, 9- or 10-bit digit of depth16 - min
+    when the tile's depth span is below 256, 512 or 1024 depth16 steps, two 8-bit passes in LDS when it is wider, and the same two passes
+    through global memory for tiles with more than 2048 entries (tests/test_gpu_sort_routes.py puts a tile on each side of every one of
+    these edges).  The synthetic scenes (z in [2, 10]) only ever take the one-pass paths: here every Gaussian is moved along its view ray by a
     factor in [0.03, 9] (same pixel footprint, depth16 spanning dozens of exponent steps); a small viewport packs thousands of
     entries into each tile ("oversized"), a larger one keeps tiles below 2048 entries ("lds-two-pass").  Keys, stable order, ranges,
     the image and a training step must equal the oracle."""

@@ -8,6 +8,7 @@ import pytest
 from webdgs_amd import _lib, ops, synth
 
 import harness
+import sortcases
 from harness import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +61,71 @@ def test_dynamic_sorter_is_a_stable_sort(hip_device, n, bits):
         order = np.argsort(keys, kind="stable")
         assert_bits_equal(gk, keys[order], "sorted keys")
         assert_bits_equal(gv, vals[order], "payload follows a STABLE sort")
+    finally:
+        so.destroy()
+
+
+def _whole_key_sort(dev, so, stats, n, bits, seed):
+    rng = np.random.default_rng(seed)
+    keys = rng.integers(0, 2**bits, max(n, 1), dtype=np.uint64).astype(np.uint32)[:n]
+    if n > 100:
+        keys[: n // 2] = keys[0]  # long runs of equal keys: stability matters
+    vals = sortcases.values_for(n, seed)
+    stats.write(np.array([n, 0, 0, 0], np.uint32))
+    if n:
+        so.ping_pong[0]["sort_depths_buffer"].write(keys)
+        so.ping_pong[0]["sort_indices_buffer"].write(vals)
+    so.sort(None, key_bits=bits)
+    out = so.ping_pong[so.final_out_index]
+    gk, gv = out["sort_depths_buffer"].read(np.uint32, count=n), out["sort_indices_buffer"].read(np.uint32, count=n)
+    dev.synchronize()
+    order = np.argsort(keys, kind="stable")
+    assert_bits_equal(gk, keys[order], f"n={n}, {bits} bits: sorted keys")
+    assert_bits_equal(gv, vals[order], f"n={n}, {bits} bits: payload follows a STABLE sort")
+
+
+def test_dynamic_sorter_small_form_beyond_one_row_scan_iteration(hip_device):
+    """A small sorter (partitions of 1024 keys) with 1025 active partitions: sort_scan_rows walks 1024 partitions per iteration, so this is
+    the first size at which its carry from one iteration to the next is used."""
+    n = 1024 * sortcases.SORT_ITEMS_SMALL * sortcases.SORT_THREADS + 1
+    assert n == 1_048_577 and n + 5000 <= sortcases.SMALL_SORTER_MAX
+    stats = hip_device.createBuffer(16)
+    so = ops.get_dynamic_sorter(n + 5000, hip_device, stats)
+    try:
+        _whole_key_sort(hip_device, so, stats, n, 32, 1)
+    finally:
+        so.destroy()
+
+
+def test_large_sorter_form_as_a_primitive(hip_device):
+    """A sorter above 8 Mi entries of capacity has partitions of 4096 keys (ITEMS = 16: what the c3 and c5 workloads run): its whole-key
+    passes around the partition size, 1025 active partitions with a 16-bit key (two passes, the row scan's second iteration), and then the
+    segment zoo of tests/sortcases.py through both tile routes of the forward pass on the same sorter."""
+    dev = hip_device
+    part = sortcases.SORT_ITEMS_MAX * sortcases.SORT_THREADS
+    stats = dev.createBuffer(16)
+    so = ops.get_dynamic_sorter(sortcases.SMALL_SORTER_MAX + 1, dev, stats)
+    try:
+        assert so.capacity > sortcases.SMALL_SORTER_MAX and so.capacity % part == 0 and part == 4096
+        for n in (0, 1, 4095, 4096, 4097, 3 * 4096 + 17):
+            _whole_key_sort(dev, so, stats, n, 32, 2 + n)
+        _whole_key_sort(dev, so, stats, 1024 * 4096 + 1, 16, 3)
+        for route, nx, ny in ((0, 8192, 1), (1, 256, 255)):
+            T = nx * ny
+            case = sortcases.zoo_case(T, nx if route == 1 else None)
+            e = case["keys"].size
+            ranges = dev.createBuffer(4 * (T + 1))
+            stats.write(np.array([e, 0, 0, 0], np.uint32))
+            so.ping_pong[0]["sort_depths_buffer"].write(case["keys"])
+            so.ping_pong[0]["sort_indices_buffer"].write(case["values"])
+            _lib.check(dev.lib.wdgs_debug_sort_tiles(so.handle, route, nx, ny, ranges.ptr))
+            out = so.ping_pong[dev.lib.wdgs_sorter_final_out_index(so.handle)]
+            gk, gv = out["sort_depths_buffer"].read(np.uint32, count=e), out["sort_indices_buffer"].read(np.uint32, count=e)
+            what = f"large sorter, zoo through route {route}, {nx} x {ny} tiles"
+            assert_bits_equal(gk, case["ref_keys"], what + ": sorted keys" + sortcases.describe_mismatch(gk, case["ref_keys"], case["names"]))
+            assert_bits_equal(gv, case["ref_values"], what + ": values follow a STABLE sort")
+            assert_bits_equal(ranges.read(np.uint32), case["ref_ranges"], what + ": range table")
+            dev.synchronize()
     finally:
         so.destroy()
 

@@ -934,12 +934,6 @@ int wdgs_tiled_forward_resize(wdgs_tiled_forward* op, uint32_t n) {
     return WDGS_OK;
 }
 
-static u32 bits_for(u32 v) {  // number of bits needed to represent v
-    u32 b = 0;
-    while (v) { b++; v >>= 1; }
-    return b;
-}
-
 // The tile sort's first pass is folded into its neighbours when the grid allows it (2..256 tile columns, <= 256 tile rows: any
 // viewport up to 4096 x 4096): project_count also counts its workgroups' entries per tile COLUMN, the scan kernel turns those into
 // per-column offsets, and emit writes its entries straight into column order (project.hip: emit_scatter) -- the keys are never

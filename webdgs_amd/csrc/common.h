@@ -132,6 +132,13 @@ __device__ __forceinline__ u32 xcd_contiguous(u32 b, u32 g) {
 }
 
 static inline u32 ceil_div(u32 a, u32 b) { return (a + b - 1u) / b; }
+// Number of bits needed to represent v: the forward pass's tile passes sort bits_for(total_tiles) bits of the key's tile field (api.hip; sort.hip's
+// test hook asks with the same function)
+static inline u32 bits_for(u32 v) {
+    u32 b = 0;
+    while (v) { b++; v >>= 1; }
+    return b;
+}
 
 // SSIM (ssim.hip): workgroups per CU of its fixed grid
 constexpr u32 SSIM_WG_PER_CU = 2;

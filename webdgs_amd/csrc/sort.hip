@@ -817,3 +817,22 @@ int launch_tile_ranges(wdgs_device* dev, const void* sorted_keys, const void* co
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
+
+// Test hook (include/webdgs.h): the forward pass's two tile routes and the range search, on whatever pairs lie in ping-pong 0.  It calls what the
+// forward pass calls, with the forward pass's own bits_for, and refuses the grids the forward pass can never ask for (api.hip: total_tiles fits the
+// key's 16-bit tile field, tile + 1 <= 65535 with the range table's terminator behind it; forward_uses_columns for the row route).
+extern "C" int wdgs_debug_sort_tiles(wdgs_sorter* s, uint32_t route, uint32_t num_tiles_x, uint32_t num_tiles_y, void* ranges_u32_dev) {
+    WDGS_REQUIRE(s && ranges_u32_dev, WDGS_E_INVALID, "wdgs_debug_sort_tiles: null argument");
+    WDGS_REQUIRE(route <= 2u, WDGS_E_INVALID, "wdgs_debug_sort_tiles: unknown route %u", route);
+    const unsigned long long tiles = (unsigned long long)num_tiles_x * num_tiles_y;
+    WDGS_REQUIRE(tiles >= 1ull && tiles <= 65534ull, WDGS_E_INVALID, "wdgs_debug_sort_tiles: %u x %u tiles (1..65534)", num_tiles_x, num_tiles_y);
+    const u32 total = (u32)tiles;
+    if (route == 0u) return sorter_sort_segmented(s, bits_for(total), total, (u32*)ranges_u32_dev, nullptr);
+    if (route == 1u) {
+        WDGS_REQUIRE(num_tiles_x >= 2u && num_tiles_x <= 256u && num_tiles_y <= 256u, WDGS_E_INVALID,
+                     "wdgs_debug_sort_tiles: the row route takes 2..256 tile columns and at most 256 tile rows, not %u x %u", num_tiles_x, num_tiles_y);
+        return sorter_sort_rows(s, num_tiles_x, num_tiles_y, (u32*)ranges_u32_dev, nullptr);
+    }
+    s->final_out_index = 0;   // the caller's sorted keys stay where they are
+    return launch_tile_ranges(s->dev, s->keys[0], s->count_ptr, total, ranges_u32_dev);
+}
