@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <mutex>
 #include <map>
+#include <memory>
 #include <set>
 #include <unordered_map>
 #include <vector>
@@ -154,114 +155,121 @@ void wdgs_free(void* p) {
     }
     (void)hipFree(p);
 }
-static void free_dev(void* p) { wdgs_free(p); }
 
+// ---- the op structs.  Every block of device memory an op owns is a DevMem member (devmem.h), so `delete op` frees what the op holds and a create
+// function that fails half way has nothing to undo; the destroy functions below keep only what is specific to their op (and the wait for the device,
+// which comes before the delete).
 struct wdgs_buffer {
-    void* ptr;
-    size_t size;
+    DevMem<char> mem;   // count() is the size in bytes
 };
 
 struct wdgs_prefix_scanner {
-    wdgs_device* dev;
-    u32 max_elements, count;
-    u32 *input, *output;
+    wdgs_device* dev = nullptr;
+    u32 max_elements = 0, count = 0;
+    DevMem<u32> input, output;
     ScanScratch scratch;
 };
 
+struct SorterDelete { void operator()(wdgs_sorter* s) const { wdgs_sorter_destroy(s); } };
+
 struct wdgs_tiled_forward {
-    wdgs_device* dev;
-    wdgs_tiled_forward_config cfg;
-    RenderSettings settings;
-    TileInfo tile_info;
-    u32* stats;   // {total_tile_entries, visible_gaussians, overflow (0 or requested total), pad} + 64 visible-count shards + the frame number (FRAME_WORD)
+    wdgs_device* dev = nullptr;
+    wdgs_tiled_forward_config cfg = {};
+    RenderSettings settings = {};
+    TileInfo tile_info = {};
+    DevMem<u32> stats;   // {total_tile_entries, visible_gaussians, overflow (0 or requested total), pad} + 64 visible-count shards + the frame number (FRAME_WORD)
     // u32[tiles]: a tile whose entry equals the frame number holds a Splat with a NaN or an infinity among its fp16 fields (project.hip stamps,
     // scan.hip advances the number, raster.hip takes such tiles in the oracle's own forms)
-    u32* nf_stamp;
-    u32 nf_capacity;
+    DevMem<u32> nf_stamp;
     // Long tile lists (longlist.h): tables, scratch and the per-tile marks; `long_lists.hdr == nullptr`: switched off.  Built by this pass's sort, used by
     // the rasterizer that composites with this pass's range table and by a backward pass that is handed that table (found through dev->range_tables).
-    LongWork long_lists;
-    u32 long_flags_capacity;
-    u32* host_stats;  // pinned, device-visible copy of stats[0..3] written by update_stats: the per-step overflow check reads host memory
-    u32* splats;
-    u32* depths;
-    u32* block_counts;  // u32[ceil(N/256)]: tile entries per project_count workgroup, scanned in place into workgroup offsets
+    // long_lists is what the kernels are handed: pointers into long_base (one allocation, the tables carved out of it), to long_flags and to nf_stamp.
+    LongWork long_lists = {};
+    DevMem<char> long_base;
+    DevMem<u32> long_flags;   // u32[tiles]
+    u32* host_stats = nullptr;  // pinned, device-visible copy of stats[0..3] written by update_stats: the per-step overflow check reads host memory
+    DevMem<u32> splats;
+    DevMem<u32> depths;
+    DevMem<u32> block_counts;  // u32[ceil(N/256)]: tile entries per project_count workgroup, scanned in place into workgroup offsets
     // u32[256][ceil(N/256)] + u32[256]: tile entries per workgroup and tile COLUMN (project_count), scanned per column into the workgroup's
     // offset inside the column, and the column totals -- the digit counts of the sort's first pass, which emit_scatter performs (project.hip)
-    u32* column_counts;
-    u32* column_totals;
-    const void* dc_source;  // nullable: the optimizer's compact SH-DC words (wdgs_tiled_forward_set_dc_source), read by project_count in place of the rows' first 6 bytes
-    u32 points_capacity;  // Gaussians the per-Gaussian buffers above and the scanner hold (>= cfg.num_points: wdgs_tiled_forward_resize)
-    wdgs_prefix_scanner* scanner;  // input = tile counts, output = per-Gaussian offsets
-    wdgs_sorter* sorter;
+    DevMem<u32> column_counts;
+    DevMem<u32> column_totals;
+    const void* dc_source = nullptr;  // nullable: the optimizer's compact SH-DC words (wdgs_tiled_forward_set_dc_source), read by project_count in place of the rows' first 6 bytes
+    // Gaussians the per-Gaussian buffers above and the scanner hold (>= cfg.num_points: wdgs_tiled_forward_resize); 0 while they are not all there
+    u32 points_capacity = 0;
+    std::unique_ptr<wdgs_prefix_scanner> scanner;  // input = tile counts, output = per-Gaussian offsets
+    std::unique_ptr<wdgs_sorter, SorterDelete> sorter;
     // Per-tile range table u32[tiles + 1].  The sort of tile-structured keys needs it half way (sort.hip, sort_segmented), so the
     // forward pass builds it and the rasterizer -- which owns K12-K13 in the reference (tiled-rasterizer.ts:213-230) -- takes it over
     // instead of searching the keys a second time.  Not valid after encode(skip_sort) or under compat_caps (plain 4-pass sort).
-    u32* ranges;
-    u32 ranges_capacity;
-    bool ranges_valid;
-    bool encoded;
-    bool projected;          // K1 of the current frame ran through wdgs_tiled_forward_project_views
-    bool projected_columns;  // ... and counted per tile column
+    DevMem<u32> ranges;
+    bool ranges_valid = false;
+    bool encoded = false;
+    bool projected = false;          // K1 of the current frame ran through wdgs_tiled_forward_project_views
+    bool projected_columns = false;  // ... and counted per tile column
+    ~wdgs_tiled_forward() { if (host_stats) (void)hipHostFree(host_stats); }
 };
 
 constexpr u32 FRAME_WORD = 4u + 64u;   // index of the frame number in wdgs_tiled_forward::stats
 constexpr size_t FORWARD_STATS_BYTES = 16 + 64 * 4 + 16;
 
 struct wdgs_tiled_rasterizer {
-    wdgs_device* dev;
-    wdgs_tiled_forward* fwd;
-    u32 compat_caps;
-    u32 width, height;       // allocated image size
-    u32 ranges_capacity;     // tiles + 1
-    u32* ranges;             // own table (used when the forward pass did not build one)
-    u32* ranges_used;        // the table the last encode composited with: own or the forward pass's
-    u32* rgba8;
-    float* alpha;
-    u32* n_contrib;
-    bool encoded;
+    wdgs_device* dev = nullptr;
+    wdgs_tiled_forward* fwd = nullptr;
+    u32 compat_caps = 0;
+    u32 width = 0, height = 0;   // size of the three images below; 0 x 0 while they are not all there
+    DevMem<u32> ranges;          // own table, u32[tiles + 1] (used when the forward pass did not build one)
+    u32* ranges_used = nullptr;  // the table the last encode composited with: own or the forward pass's
+    DevMem<u32> rgba8;
+    DevMem<float> alpha;
+    DevMem<u32> n_contrib;
+    bool encoded = false;
     // depth images (depth.hip), f32[W*H] each, in the order of the WDGS_DEPTH_* bits: allocated per kind at its first encode_depth
-    float* depth[3];
-    u32 depth_width, depth_height;   // the size they were allocated for
-    u32 depth_encoded;               // the kinds the last encode_depth wrote
+    DevMem<float> depth[3];
+    u32 depth_width = 0, depth_height = 0;   // the size they were allocated for
+    u32 depth_encoded = 0;                   // the kinds the last encode_depth wrote
 };
 
 struct wdgs_tiled_backward {
-    wdgs_device* dev;
-    wdgs_tiled_backward_config cfg;
-    RenderSettings settings;
-    int* acc;            // i32[N*12], followed by the state word below
-    u32* acc_dirty;      // device word behind the accumulators: 0 = all rows are zero (a consuming K17 left them so), 1 = they hold sums
-    u32* gradients;      // GaussianGradient[N]
-    bool gradient_output;  // the fused K17 + Adam step also writes the packed gradient (wdgs_tiled_backward_set_gradient_output; default on)
-    float* loss_image;   // rgba32f
-    u32 dssim_mode;      // WDGS_DSSIM_*: the loss kernel an encode launches (wdgs_tiled_backward_set_dssim_mode)
-    u32* metric_counts;  // u32[N]
-    u32* metric_counts_into;  // nullable: computeMetricCounts adds into THIS array instead (wdgs_tiled_backward_set_metric_counts_target)
-    u32* metric_err;     // u32[W*H]
-    u32* metric_flags;   // u32[W*H]
-    u32* metric_minmax;  // u32[2] + scratch
-    u32 img_capacity;    // pixels allocated
-    u32 points_capacity; // Gaussians acc / gradients / metric_counts hold (>= cfg.num_points: wdgs_tiled_backward_resize)
+    wdgs_device* dev = nullptr;
+    wdgs_tiled_backward_config cfg = {};
+    RenderSettings settings = {};
+    DevMem<int> acc;     // i32[capacity*12], followed by the state word below (and 12 bytes of padding)
+    // device word behind the accumulators: 0 = all rows are zero (a consuming K17 left them so), 1 = they hold sums
+    u32* acc_dirty() const { return acc ? reinterpret_cast<u32*>(acc.get() + (acc.count() - 4)) : nullptr; }
+    DevMem<u32> gradients;      // GaussianGradient[N]
+    bool gradient_output = true;  // the fused K17 + Adam step also writes the packed gradient (wdgs_tiled_backward_set_gradient_output; default on)
+    DevMem<float> loss_image;   // rgba32f
+    u32 dssim_mode = 0;  // WDGS_DSSIM_*: the loss kernel an encode launches (wdgs_tiled_backward_set_dssim_mode)
+    DevMem<u32> metric_counts;  // u32[N]
+    u32* metric_counts_into = nullptr;  // nullable: computeMetricCounts adds into THIS array instead (wdgs_tiled_backward_set_metric_counts_target)
+    DevMem<u32> metric_err;     // u32[W*H]
+    DevMem<u32> metric_flags;   // u32[W*H]: its count() is the pixels all three images hold (backward_alloc_images)
+    DevMem<u32> metric_minmax;  // u32[2] + scratch
+    u32 points_capacity = 0;  // Gaussians acc / gradients / metric_counts hold (>= cfg.num_points: wdgs_tiled_backward_resize); 0 while they are not all there
 };
 
 struct wdgs_optimizer {
-    wdgs_device* dev;
-    u32 num_points;
-    wdgs_adam_hyperparameters params;
-    wdgs_optimizer_state state;
-    bool owns_state;
-    u32 iteration;
-    float* dc;        // compact training copy, float4[7][max(N, 1)] planes: position, log-scale and SH-DC {param, m, v} (adam.h; optimizer.hip "HBM layout note"); always owned
+    wdgs_device* dev = nullptr;
+    u32 num_points = 0;
+    wdgs_adam_hyperparameters params = {0.00016f, 0.0025f, 0.05f, 0.005f, 0.001f, 0.9f, 0.999f, 1e-8f};  // adam-config.ts:12-21
+    wdgs_optimizer_state state = {};   // the view of the six arrays that kernels and wdgs_optimizer_get_state are handed
+    // ... and their owners, in the order of state's fields, when the optimizer owns them: allocated here or adopted from the host (owns_state at
+    // creation), emptied without freeing by wdgs_optimizer_release_state
+    DevMem<char> owned[6];
+    bool owns_state() const { return bool(owned[0]); }
+    u32 iteration = 0;
+    DevMem<float4> dc;  // compact training copy, float4[7][max(N, 1)] planes: position, log-scale and SH-DC {param, m, v} (adam.h; optimizer.hip "HBM layout note"); always owned
     static u32 cs_pitch(u32 n) { return (std::max(n, 1u) + 15u) & ~15u; }  // planes start on 256-byte boundaries
-    CsView cs() const { return CsView{reinterpret_cast<float4*>(dc), cs_pitch(num_points)}; }
-    bool dc_dirty;    // it is ahead of state.opt_pos / opt_scale / param_sh / state_sh
-    const void* guard;  // device word: non-zero at execution time turns step / step_f32 into a no-op (wdgs_optimizer_set_guard)
+    CsView cs() const { return CsView{dc.get(), cs_pitch(num_points)}; }
+    bool dc_dirty = false;    // it is ahead of state.opt_pos / opt_scale / param_sh / state_sh
+    const void* guard = nullptr;  // device word: non-zero at execution time turns step / step_f32 into a no-op (wdgs_optimizer_set_guard)
     // Deferred SH writes (wdgs_optimizer_set_deferred_sh): the steps write the trained DC halves to dc_words (u32[N][2]) instead of the
     // 96-byte rows; sh_stale says the rows are behind until wdgs_optimizer_flush_sh.
-    u32* dc_words;
-    bool deferred_sh;
-    bool sh_stale;
+    DevMem<u32> dc_words;
+    bool deferred_sh = false;
+    bool sh_stale = false;
 };
 
 // Brings the reference-layout arrays (position, log-scale, SH) up to date with the compact training copy (no-op when nothing was trained since).
@@ -651,36 +659,33 @@ int wdgs_copy_buffer_to_buffer(wdgs_device* d, void* dst, const void* src, size_
 // ---------------------------------------------------------------- buffers
 int wdgs_buffer_create(wdgs_device* d, size_t bytes, wdgs_buffer** out) {
     WDGS_REQUIRE(d && out, WDGS_E_INVALID, "wdgs_buffer_create: null argument");
-    wdgs_buffer* b = new wdgs_buffer{nullptr, bytes};
-    int r = wdgs_alloc(&b->ptr, bytes, true, d->stream);
-    if (r != WDGS_OK) { delete b; return r; }
-    *out = b;
+    auto b = std::make_unique<wdgs_buffer>();
+    WDGS_TRY(b->mem.alloc(bytes, true, d->stream));
+    *out = b.release();
     return WDGS_OK;
 }
 int wdgs_buffer_destroy(wdgs_buffer* b) {
-    if (!b) return WDGS_OK;
-    free_dev(b->ptr);
     delete b;
     return WDGS_OK;
 }
-void* wdgs_buffer_ptr(const wdgs_buffer* b) { return b ? b->ptr : nullptr; }
-size_t wdgs_buffer_size(const wdgs_buffer* b) { return b ? b->size : 0; }
+void* wdgs_buffer_ptr(const wdgs_buffer* b) { return b ? b->mem.get() : nullptr; }
+size_t wdgs_buffer_size(const wdgs_buffer* b) { return b ? b->mem.count() : 0; }
 int wdgs_buffer_write(wdgs_device* d, wdgs_buffer* b, size_t off, const void* src, size_t bytes) {
     WDGS_REQUIRE(d && b, WDGS_E_INVALID, "wdgs_buffer_write: null argument");
-    WDGS_REQUIRE(off + bytes <= b->size, WDGS_E_INVALID, "wdgs_buffer_write: range [%zu, %zu) exceeds buffer size %zu", off, off + bytes, b->size);
-    return wdgs_copy_to_device(d, (char*)b->ptr + off, src, bytes);
+    WDGS_REQUIRE(off + bytes <= b->mem.count(), WDGS_E_INVALID, "wdgs_buffer_write: range [%zu, %zu) exceeds buffer size %zu", off, off + bytes, b->mem.count());
+    return wdgs_copy_to_device(d, b->mem.get() + off, src, bytes);
 }
 int wdgs_buffer_read(wdgs_device* d, const wdgs_buffer* b, size_t off, void* dst, size_t bytes) {
     WDGS_REQUIRE(d && b, WDGS_E_INVALID, "wdgs_buffer_read: null argument");
-    WDGS_REQUIRE(off + bytes <= b->size, WDGS_E_INVALID, "wdgs_buffer_read: range [%zu, %zu) exceeds buffer size %zu", off, off + bytes, b->size);
-    return wdgs_copy_to_host(d, dst, (const char*)b->ptr + off, bytes);
+    WDGS_REQUIRE(off + bytes <= b->mem.count(), WDGS_E_INVALID, "wdgs_buffer_read: range [%zu, %zu) exceeds buffer size %zu", off, off + bytes, b->mem.count());
+    return wdgs_copy_to_host(d, dst, b->mem.get() + off, bytes);
 }
 int wdgs_buffer_read_async(wdgs_device* d, const wdgs_buffer* b, size_t off, void* dst, size_t bytes) {
     WDGS_REQUIRE(d && b && (bytes == 0 || dst), WDGS_E_INVALID, "wdgs_buffer_read_async: null argument");
-    WDGS_REQUIRE(off + bytes <= b->size, WDGS_E_INVALID, "wdgs_buffer_read_async: range [%zu, %zu) exceeds buffer size %zu", off, off + bytes, b->size);
+    WDGS_REQUIRE(off + bytes <= b->mem.count(), WDGS_E_INVALID, "wdgs_buffer_read_async: range [%zu, %zu) exceeds buffer size %zu", off, off + bytes, b->mem.count());
     WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "wdgs_buffer_read_async while recording a command buffer");
     if (bytes == 0) return WDGS_OK;
-    WDGS_CHECK_HIP(hipMemcpyAsync(dst, (const char*)b->ptr + off, bytes, hipMemcpyDeviceToHost, d->stream));
+    WDGS_CHECK_HIP(hipMemcpyAsync(dst, b->mem.get() + off, bytes, hipMemcpyDeviceToHost, d->stream));
     return WDGS_OK;
 }
 int wdgs_host_alloc(size_t bytes, void** out) {
@@ -696,28 +701,22 @@ int wdgs_host_free(void* p) {
 // ---------------------------------------------------------------- prefix scanner
 int wdgs_prefix_scanner_create(wdgs_device* d, uint32_t max_elements, wdgs_prefix_scanner** out) {
     WDGS_REQUIRE(d && out, WDGS_E_INVALID, "wdgs_prefix_scanner_create: null argument");
-    wdgs_prefix_scanner* s = new wdgs_prefix_scanner();
+    auto s = std::make_unique<wdgs_prefix_scanner>();
     s->dev = d;
     s->max_elements = max_elements > 0 ? max_elements : 1;
     s->count = s->max_elements;
-    s->input = s->output = nullptr;
-    int r = wdgs_alloc((void**)&s->input, sizeof(u32) * (size_t)s->max_elements, true, d->stream);
-    if (r == WDGS_OK) r = wdgs_alloc((void**)&s->output, sizeof(u32) * (size_t)s->max_elements, true, d->stream);
-    if (r == WDGS_OK) r = scan_scratch_create(&s->scratch, s->max_elements);
-    if (r != WDGS_OK) { wdgs_prefix_scanner_destroy(s); return r; }
-    *out = s;
+    WDGS_TRY(s->input.alloc(s->max_elements, true, d->stream));
+    WDGS_TRY(s->output.alloc(s->max_elements, true, d->stream));
+    WDGS_TRY(scan_scratch_create(&s->scratch, s->max_elements));
+    *out = s.release();
     return WDGS_OK;
 }
 int wdgs_prefix_scanner_destroy(wdgs_prefix_scanner* s) {
-    if (!s) return WDGS_OK;
-    free_dev(s->input);
-    free_dev(s->output);
-    scan_scratch_destroy(&s->scratch);
     delete s;
     return WDGS_OK;
 }
-void* wdgs_prefix_scanner_input(wdgs_prefix_scanner* s) { return s ? s->input : nullptr; }
-void* wdgs_prefix_scanner_output(wdgs_prefix_scanner* s) { return s ? s->output : nullptr; }
+void* wdgs_prefix_scanner_input(wdgs_prefix_scanner* s) { return s ? s->input.get() : nullptr; }
+void* wdgs_prefix_scanner_output(wdgs_prefix_scanner* s) { return s ? s->output.get() : nullptr; }
 int wdgs_prefix_scanner_set_count(wdgs_prefix_scanner* s, uint32_t count) {
     WDGS_REQUIRE(s, WDGS_E_INVALID, "null scanner");
     WDGS_REQUIRE(count <= s->max_elements, WDGS_E_CAPACITY, "scan count %u exceeds max_elements %u", count, s->max_elements);
@@ -749,16 +748,29 @@ static uint64_t forward_tile_entry_cap(const wdgs_tiled_forward_config& cfg, u32
     }
     return std::min<uint64_t>(align_up(cap, 4096), 0xFFFFF000ull);
 }
+// (Re)allocates the per-Gaussian buffers and the scanner for `capacity` Gaussians: free all, then allocate all
 static int forward_alloc_per_point(wdgs_tiled_forward* op, u32 capacity) {
     wdgs_device* d = op->dev;
-    int r = wdgs_alloc((void**)&op->splats, (size_t)24 * capacity, true, d->stream);
-    if (r == WDGS_OK) r = wdgs_alloc((void**)&op->depths, (size_t)4 * capacity, true, d->stream);
-    if (r == WDGS_OK) r = wdgs_alloc((void**)&op->block_counts, (size_t)4 * (ceil_div(capacity, 256) + 1), true, d->stream);
-    if (r == WDGS_OK) r = wdgs_alloc((void**)&op->column_counts, (size_t)4 * 256 * (ceil_div(capacity, 256) + 1), true, d->stream);
-    if (r == WDGS_OK && !op->column_totals) r = wdgs_alloc((void**)&op->column_totals, (size_t)4 * 256, true, d->stream);
-    if (r == WDGS_OK) r = wdgs_prefix_scanner_create(d, capacity, &op->scanner);
-    if (r == WDGS_OK) op->points_capacity = capacity;
-    return r;
+    op->splats.reset(); op->depths.reset(); op->block_counts.reset(); op->column_counts.reset();
+    op->scanner.reset();
+    op->points_capacity = 0;
+    const size_t blocks = ceil_div(capacity, 256) + 1;
+    WDGS_TRY(op->splats.alloc((size_t)6 * capacity, true, d->stream));
+    WDGS_TRY(op->depths.alloc(capacity, true, d->stream));
+    WDGS_TRY(op->block_counts.alloc(blocks, true, d->stream));
+    WDGS_TRY(op->column_counts.alloc(256 * blocks, true, d->stream));
+    if (!op->column_totals) WDGS_TRY(op->column_totals.alloc(256, true, d->stream));
+    wdgs_prefix_scanner* scanner = nullptr;
+    WDGS_TRY(wdgs_prefix_scanner_create(d, capacity, &scanner));
+    op->scanner.reset(scanner);
+    op->points_capacity = capacity;
+    return WDGS_OK;
+}
+static int forward_make_sorter(wdgs_tiled_forward* op, u32 capacity) {
+    wdgs_sorter* sorter = nullptr;
+    WDGS_TRY(wdgs_sorter_create(op->dev, capacity, op->stats, &sorter));
+    op->sorter.reset(sorter);
+    return WDGS_OK;
 }
 static void forward_set_viewport(wdgs_tiled_forward* op, u32 w, u32 h) {
     op->cfg.viewport_width = w;
@@ -769,29 +781,37 @@ static void forward_set_viewport(wdgs_tiled_forward* op, u32 w, u32 h) {
     op->tile_info.num_tiles_y = ceil_div(h, 16);
     op->tile_info.total_tiles = op->tile_info.num_tiles_x * op->tile_info.num_tiles_y;
 }
+// The per-tile tables that follow the viewport: the non-finite stamps and, when long lists are on, their marks.  They only grow.
 static int forward_alloc_nf_stamp(wdgs_tiled_forward* op) {
-    if (op->tile_info.total_tiles <= op->nf_capacity) return WDGS_OK;
-    free_dev(op->nf_stamp);
-    op->nf_stamp = nullptr;
-    op->nf_capacity = 0;
-    WDGS_TRY(wdgs_alloc((void**)&op->nf_stamp, sizeof(u32) * (size_t)op->tile_info.total_tiles, true, op->dev->stream));
-    op->nf_capacity = op->tile_info.total_tiles;
+    if (op->tile_info.total_tiles <= op->nf_stamp.count()) return WDGS_OK;
+    return op->nf_stamp.alloc(op->tile_info.total_tiles, true, op->dev->stream);
+}
+static int forward_alloc_per_tile(wdgs_tiled_forward* op) {
+    const u32 tiles = op->tile_info.total_tiles;
+    if (tiles > op->nf_stamp.count()) { (void)wdgs_sync_lanes(op->dev); WDGS_TRY(forward_alloc_nf_stamp(op)); }
+    if (op->long_lists.hdr && tiles > op->long_flags.count()) {
+        (void)wdgs_sync_lanes(op->dev);
+        WDGS_TRY(op->long_flags.alloc(tiles, true, op->dev->stream));
+    }
     return WDGS_OK;
 }
 
 // The long-list work of a pass lives in ONE device allocation (twelve tables carved out of it: a pass is built inside a densify event, where every
-// hipMalloc counts) plus the per-tile marks, which follow the viewport.
-static void forward_free_long_lists(wdgs_tiled_forward* op) {
+// hipMalloc counts) plus the per-tile marks, which follow the viewport.  `long_lists` is the view of both (and of the stamps) that the kernels are
+// handed by value: brought up to date whenever a block it names was re-allocated, and switched off when one of them is not there.
+static void forward_sync_long_view(wdgs_tiled_forward* op) {
     LongWork& lw = op->long_lists;
-    free_dev(lw.hdr);     // (the base of the allocation)
-    free_dev(lw.flags);
-    lw = LongWork{};
-    op->long_flags_capacity = 0;
+    if (!lw.hdr) return;
+    if (!op->long_flags || !op->nf_stamp) { lw = LongWork{}; return; }
+    lw.flags = op->long_flags;
+    lw.nf_stamp = op->nf_stamp;
 }
 // (Re)allocates the long-list work of a pass: `threshold` entries (0 = off), room for `items` (block, chunk) slots and `rows` list rows.
 static int forward_alloc_long_lists(wdgs_tiled_forward* op, u32 threshold, u32 items, u32 rows) {
     wdgs_device* d = op->dev;
-    forward_free_long_lists(op);
+    op->long_base.reset();
+    op->long_flags.reset();
+    op->long_lists = LongWork{};
     if (threshold == 0u) return WDGS_OK;
     LongWork lw{};
     lw.threshold = threshold;
@@ -805,18 +825,17 @@ static int forward_alloc_long_lists(wdgs_tiled_forward* op, u32 threshold, u32 i
                               sizeof(u32) * 64 * I, sizeof(u32) * 64 * I, sizeof(float4) * 192 * I, sizeof(u32) * 256 * R, 0};
     size_t at[12], total = 0, zeroed = 0;
     for (int i = 0; i < 11; i++) { at[i] = total; total += align_up(sizes[i], 256); if (i == 6) zeroed = total; }
-    char* base = nullptr;
-    WDGS_TRY(wdgs_alloc((void**)&base, total, false, d->stream));
-    if (hipMemsetAsync(base, 0, zeroed, d->stream) != hipSuccess) { free_dev(base); wdgs_set_error("hipMemsetAsync failed"); return WDGS_E_HIP; }
+    WDGS_TRY(op->long_base.alloc(total, false, d->stream));
+    char* const base = op->long_base;
+    WDGS_CHECK_HIP(hipMemsetAsync(base, 0, zeroed, d->stream));
+    WDGS_TRY(op->long_flags.alloc(tiles, true, d->stream));
     lw.hdr = (u32*)(base + at[0]); lw.blocks = (LongBlock*)(base + at[1]); lw.sync = (LongSync*)(base + at[2]); lw.item_block = (u32*)(base + at[3]); lw.nlist = (u32*)(base + at[4]);
     lw.total = (u32*)(base + at[5]); lw.jlast = (u32*)(base + at[6]); lw.cnt = (u32*)(base + at[7]); lw.off = (u32*)(base + at[8]); lw.records = (float4*)(base + at[9]);
     lw.rows = (u32*)(base + at[10]);
+    lw.flags = op->long_flags;
     lw.nf_stamp = op->nf_stamp;
     lw.nf_frame = op->stats + FRAME_WORD;
-    op->long_lists = lw;   // (what has been allocated is freed with the pass, also after a failure)
-    const int r = wdgs_alloc((void**)&op->long_lists.flags, sizeof(u32) * (size_t)tiles, true, d->stream);
-    if (r != WDGS_OK) { forward_free_long_lists(op); return r; }
-    op->long_flags_capacity = tiles;
+    op->long_lists = lw;   // (only now: a pass whose allocation failed has its long lists switched off)
     return WDGS_OK;
 }
 constexpr u32 LONG_LIST_THRESHOLD = 2048u, LONG_LIST_ITEMS = 1024u, LONG_LIST_ROWS = 8192u;   // defaults (include/webdgs.h: wdgs_tiled_forward_set_long_lists)
@@ -828,43 +847,27 @@ int wdgs_tiled_forward_create(wdgs_device* d, const wdgs_tiled_forward_config* c
     // the sort key keeps tile_id + 1 in 16 bits (tiled-forward.wgsl:121-136)
     const uint64_t tiles = (uint64_t)ceil_div(cfg->viewport_width, 16) * ceil_div(cfg->viewport_height, 16);
     WDGS_REQUIRE(tiles + 1 <= 0xFFFFu, WDGS_E_CAPACITY, "%llu tiles do not fit the 16-bit tile field of the sort key", (unsigned long long)tiles);
-    wdgs_tiled_forward* op = new wdgs_tiled_forward();
+    auto op = std::make_unique<wdgs_tiled_forward>();
     op->dev = d;
     op->cfg = *cfg;
-    op->stats = op->splats = op->depths = op->block_counts = op->column_counts = op->column_totals = nullptr;
-    op->dc_source = nullptr;
-    op->nf_stamp = nullptr;
-    op->nf_capacity = 0;
-    op->long_lists = LongWork{};
-    op->long_flags_capacity = 0;
-    op->host_stats = nullptr;
-    op->scanner = nullptr;
-    op->sorter = nullptr;
-    op->ranges = nullptr;
-    op->ranges_capacity = 0;
-    op->ranges_valid = false;
-    op->encoded = false;
-    op->projected = op->projected_columns = false;
     const u32 n = cfg->num_points;
     const uint64_t cap = forward_tile_entry_cap(*cfg, n);
-    op->points_capacity = std::max(n, 1u);
     op->settings = RenderSettings{cfg->gaussian_scale != 0.f ? cfg->gaussian_scale : 1.0f, (float)cfg->sh_deg, 0.f, 0.f,
                                   cfg->point_size_px != 0.f ? cfg->point_size_px : 3.0f, cfg->render_mode ? 1.0f : 0.0f,
                                   cfg->max_splat_radius_px != 0.f ? cfg->max_splat_radius_px : 128.0f};
     op->tile_info.max_tile_entries = (u32)cap;
-    forward_set_viewport(op, cfg->viewport_width, cfg->viewport_height);
-    int r = wdgs_alloc((void**)&op->stats, FORWARD_STATS_BYTES, true, d->stream);
+    forward_set_viewport(op.get(), cfg->viewport_width, cfg->viewport_height);
+    WDGS_TRY(op->stats.alloc(FORWARD_STATS_BYTES / 4, true, d->stream));
     // (frame numbers start at 1: a zeroed stamp table marks nothing)
-    if (r == WDGS_OK && hipMemsetD32Async((hipDeviceptr_t)(op->stats + FRAME_WORD), 1, 1, d->stream) != hipSuccess) { wdgs_set_error("hipMemsetD32Async failed"); r = WDGS_E_HIP; }
-    if (r == WDGS_OK) r = forward_alloc_nf_stamp(op);
-    if (r == WDGS_OK && !cfg->compat_caps) r = forward_alloc_long_lists(op, LONG_LIST_THRESHOLD, LONG_LIST_ITEMS, LONG_LIST_ROWS);
-    if (r == WDGS_OK && hipHostMalloc((void**)&op->host_stats, 16, hipHostMallocDefault) != hipSuccess) { wdgs_set_error("hipHostMalloc(16) failed"); r = WDGS_E_HIP; }
-    if (r == WDGS_OK) std::memset(op->host_stats, 0, 16);
-    if (r == WDGS_OK) r = forward_alloc_per_point(op, std::max(n, 1u));
-    if (r == WDGS_OK) r = wdgs_sorter_create(d, (u32)cap, op->stats, &op->sorter);
-    if (r != WDGS_OK) { wdgs_tiled_forward_destroy(op); return r; }
-    d->forwards.push_back(op);
-    *out = op;
+    WDGS_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(op->stats + FRAME_WORD), 1, 1, d->stream));
+    WDGS_TRY(forward_alloc_nf_stamp(op.get()));
+    if (!cfg->compat_caps) WDGS_TRY(forward_alloc_long_lists(op.get(), LONG_LIST_THRESHOLD, LONG_LIST_ITEMS, LONG_LIST_ROWS));
+    WDGS_CHECK_HIP(hipHostMalloc((void**)&op->host_stats, 16, hipHostMallocDefault));
+    std::memset(op->host_stats, 0, 16);
+    WDGS_TRY(forward_alloc_per_point(op.get(), std::max(n, 1u)));
+    WDGS_TRY(forward_make_sorter(op.get(), (u32)cap));
+    d->forwards.push_back(op.get());
+    *out = op.release();
     return WDGS_OK;
 }
 
@@ -875,19 +878,7 @@ int wdgs_tiled_forward_destroy(wdgs_tiled_forward* op) {
         v.erase(std::remove(v.begin(), v.end(), op), v.end());
     }
     sync_if_alive(op->dev);
-    if (op->ranges && wdgs_device_alive(op->dev)) op->dev->range_tables.erase(op->ranges);
-    free_dev(op->stats);
-    free_dev(op->nf_stamp);
-    forward_free_long_lists(op);
-    if (op->host_stats) (void)hipHostFree(op->host_stats);
-    free_dev(op->splats);
-    free_dev(op->depths);
-    free_dev(op->block_counts);
-    free_dev(op->column_counts);
-    free_dev(op->column_totals);
-    free_dev(op->ranges);
-    wdgs_prefix_scanner_destroy(op->scanner);
-    wdgs_sorter_destroy(op->sorter);
+    if (op->ranges && wdgs_device_alive(op->dev)) op->dev->range_tables.erase(op->ranges.get());
     delete op;
     return WDGS_OK;
 }
@@ -904,11 +895,6 @@ int wdgs_tiled_forward_resize(wdgs_tiled_forward* op, uint32_t n) {
     WDGS_CHECK_HIP(wdgs_sync_lanes(d));
     const u32 need = std::max(n, 1u);
     if (need > op->points_capacity) {
-        free_dev(op->splats); free_dev(op->depths); free_dev(op->block_counts); free_dev(op->column_counts);
-        op->splats = op->depths = op->block_counts = op->column_counts = nullptr;
-        wdgs_prefix_scanner_destroy(op->scanner);
-        op->scanner = nullptr;
-        op->points_capacity = 0;
         WDGS_TRY(forward_alloc_per_point(op, (u32)std::min<uint64_t>((uint64_t)need + need / 4, 0xFFFFFFFFull)));
     } else {
         WDGS_CHECK_HIP(hipMemsetAsync(op->splats, 0, (size_t)24 * need, d->stream));
@@ -918,11 +904,10 @@ int wdgs_tiled_forward_resize(wdgs_tiled_forward* op, uint32_t n) {
         WDGS_CHECK_HIP(hipMemsetAsync(op->scanner->output, 0, (size_t)4 * need, d->stream));
     }
     const uint64_t cap = forward_tile_entry_cap(op->cfg, n);
-    if (cap > wdgs_sorter_capacity(op->sorter)) {
-        wdgs_sorter_destroy(op->sorter);
-        op->sorter = nullptr;
+    if (cap > wdgs_sorter_capacity(op->sorter.get())) {
+        op->sorter.reset();
         const uint64_t roomy = op->cfg.compat_caps || op->cfg.max_tile_entries ? cap : std::min<uint64_t>(align_up(cap + cap / 4, 4096), 0xFFFFF000ull);
-        WDGS_TRY(wdgs_sorter_create(d, (u32)roomy, op->stats, &op->sorter));
+        WDGS_TRY(forward_make_sorter(op, (u32)roomy));
     }
     op->tile_info.max_tile_entries = (u32)cap;
     op->cfg.num_points = n;
@@ -959,34 +944,31 @@ static int forward_encode_rest(wdgs_tiled_forward* op, int skip_sort, bool colum
     op->ranges_valid = false;
     if (!skip_sort && !op->cfg.compat_caps) {
         const u32 tiles = op->tile_info.total_tiles;
-        if (tiles + 1 > op->ranges_capacity) {
+        if (tiles + 1 > op->ranges.count()) {
             WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledForwardPass.encode allocates its range table on first use: run one eager encode before recording");
             (void)wdgs_sync_lanes(d);
-            if (op->ranges) d->range_tables.erase(op->ranges);
-            free_dev(op->ranges);
-            op->ranges = nullptr;
-            WDGS_TRY(wdgs_alloc((void**)&op->ranges, sizeof(u32) * (size_t)(tiles + 1), true, d->stream));
-            op->ranges_capacity = tiles + 1;
-            d->range_tables[op->ranges] = op;   // (a backward pass handed this table finds the pass's long-list work through it)
+            if (op->ranges) d->range_tables.erase(op->ranges.get());
+            WDGS_TRY(op->ranges.alloc((size_t)tiles + 1, true, d->stream));
+            d->range_tables[op->ranges.get()] = op;   // (a backward pass handed this table finds the pass's long-list work through it)
         }
     }
     if (columns) {
         WDGS_TRY(launch_emit_scatter(d, n, op->splats, op->depths, op->scanner->input, op->scanner->output, op->block_counts, op->settings, op->tile_info,
-                                     op->column_counts, op->column_totals, wdgs_sorter_keys(op->sorter, 0), wdgs_sorter_values(op->sorter, 0), op->tile_info.max_tile_entries));
+                                     op->column_counts, op->column_totals, wdgs_sorter_keys(op->sorter.get(), 0), wdgs_sorter_values(op->sorter.get(), 0), op->tile_info.max_tile_entries));
         // one stable pass on the tile row (it builds the range table), then the per-tile depth sort: the order of a stable sort of the full key
-        WDGS_TRY(sorter_sort_rows(op->sorter, ti.num_tiles_x, ti.num_tiles_y, op->ranges, op->long_lists.hdr ? &op->long_lists : nullptr));
+        WDGS_TRY(sorter_sort_rows(op->sorter.get(), ti.num_tiles_x, ti.num_tiles_y, op->ranges, op->long_lists.hdr ? &op->long_lists : nullptr));
         op->ranges_valid = true;
     } else {
         WDGS_TRY(launch_emit(d, n, op->splats, op->depths, op->scanner->input, op->scanner->output, op->block_counts, op->settings, op->tile_info,
-                             wdgs_sorter_keys(op->sorter, 0), wdgs_sorter_values(op->sorter, 0), op->tile_info.max_tile_entries));
-        if (skip_sort) sorter_set_final_out_index(op->sorter, 0);  // the unsorted entries are in ping-pong 0
+                             wdgs_sorter_keys(op->sorter.get(), 0), wdgs_sorter_values(op->sorter.get(), 0), op->tile_info.max_tile_entries));
+        if (skip_sort) sorter_set_final_out_index(op->sorter.get(), 0);  // the unsorted entries are in ping-pong 0
         if (!skip_sort) {
             // key = (tile_id + 1) << 16 | depth16: only 16 + bits(total_tiles) bits are ever set
             if (op->cfg.compat_caps) {
-                WDGS_TRY(wdgs_sorter_sort(op->sorter, 32u));  // the reference's four 8-bit passes over the whole key
+                WDGS_TRY(wdgs_sorter_sort(op->sorter.get(), 32u));  // the reference's four 8-bit passes over the whole key
             } else {
                 // tile passes, range table, per-tile depth sort (sort.hip): the order of a stable sort of the full key
-                WDGS_TRY(sorter_sort_segmented(op->sorter, bits_for(op->tile_info.total_tiles), op->tile_info.total_tiles, op->ranges, op->long_lists.hdr ? &op->long_lists : nullptr));
+                WDGS_TRY(sorter_sort_segmented(op->sorter.get(), bits_for(op->tile_info.total_tiles), op->tile_info.total_tiles, op->ranges, op->long_lists.hdr ? &op->long_lists : nullptr));
                 op->ranges_valid = true;
             }
         }
@@ -1059,15 +1041,9 @@ int wdgs_tiled_forward_set_viewport(wdgs_tiled_forward* op, uint32_t w, uint32_t
     WDGS_REQUIRE((uint64_t)ceil_div(w, 16) * ceil_div(h, 16) + 1 <= 0xFFFFu, WDGS_E_CAPACITY, "viewport %ux%u has too many tiles for the 16-bit tile field", w, h);
     WDGS_REQUIRE(!op->dev->capturing, WDGS_E_STATE, "wdgs_tiled_forward_set_viewport while recording a command buffer");
     forward_set_viewport(op, w, h);
-    if (op->tile_info.total_tiles > op->nf_capacity) { (void)wdgs_sync_lanes(op->dev); WDGS_TRY(forward_alloc_nf_stamp(op)); op->long_lists.nf_stamp = op->long_lists.hdr ? op->nf_stamp : nullptr; }
-    if (op->long_lists.hdr && op->tile_info.total_tiles > op->long_flags_capacity) {
-        (void)wdgs_sync_lanes(op->dev);
-        free_dev(op->long_lists.flags);
-        op->long_lists.flags = nullptr;
-        WDGS_TRY(wdgs_alloc((void**)&op->long_lists.flags, sizeof(u32) * (size_t)op->tile_info.total_tiles, true, op->dev->stream));
-        op->long_flags_capacity = op->tile_info.total_tiles;
-    }
-    return WDGS_OK;
+    const int r = forward_alloc_per_tile(op);
+    forward_sync_long_view(op);   // (after a failure too: the view never names a block that has been freed)
+    return r;
 }
 int wdgs_tiled_forward_set_render_mode(wdgs_tiled_forward* op, uint32_t mode) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "null op");
@@ -1088,11 +1064,11 @@ int wdgs_tiled_forward_set_gaussian_scale(wdgs_tiled_forward* op, float v) {
 
 int wdgs_tiled_forward_get_resources(wdgs_tiled_forward* op, wdgs_tiled_forward_resources* out) {
     WDGS_REQUIRE(op && out, WDGS_E_INVALID, "null argument");
-    const int fo = wdgs_sorter_final_out_index(op->sorter);
+    const int fo = wdgs_sorter_final_out_index(op->sorter.get());
     out->splat_buffer = op->splats;
     out->depths_buffer = op->depths;
-    out->tile_keys_buffer = wdgs_sorter_keys(op->sorter, fo);
-    out->tile_indices_buffer = wdgs_sorter_values(op->sorter, fo);
+    out->tile_keys_buffer = wdgs_sorter_keys(op->sorter.get(), fo);
+    out->tile_indices_buffer = wdgs_sorter_values(op->sorter.get(), fo);
     out->tile_offsets_buffer = op->scanner->output;
     out->tile_counts_buffer = op->scanner->input;
     out->stats_buffer = op->stats;
@@ -1139,22 +1115,16 @@ int wdgs_tiled_forward_long_list_stats(wdgs_tiled_forward* op, uint32_t stats_ou
 // ---------------------------------------------------------------- TiledRasterizer
 int wdgs_tiled_rasterizer_create(wdgs_device* d, wdgs_tiled_forward* fwd, uint32_t compat_caps, wdgs_tiled_rasterizer** out) {
     WDGS_REQUIRE(d && fwd && out, WDGS_E_INVALID, "wdgs_tiled_rasterizer_create: null argument");
-    wdgs_tiled_rasterizer* op = new wdgs_tiled_rasterizer();
-    std::memset(op, 0, sizeof(*op));
+    auto op = std::make_unique<wdgs_tiled_rasterizer>();
     op->dev = d;
     op->fwd = fwd;
     op->compat_caps = compat_caps;
-    *out = op;
+    *out = op.release();
     return WDGS_OK;
 }
 int wdgs_tiled_rasterizer_destroy(wdgs_tiled_rasterizer* op) {
     if (!op) return WDGS_OK;
     sync_if_alive(op->dev);
-    free_dev(op->ranges);
-    free_dev(op->rgba8);
-    free_dev(op->alpha);
-    free_dev(op->n_contrib);
-    for (float* img : op->depth) free_dev(img);
     delete op;
     return WDGS_OK;
 }
@@ -1169,28 +1139,26 @@ int wdgs_tiled_rasterizer_encode(wdgs_tiled_rasterizer* op, uint32_t width, uint
     if (width != op->width || height != op->height) {  // ensureTextures (tiled-rasterizer.ts:244-306)
         WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledRasterizer.encode allocates its textures on first use: run one eager encode before recording");
         (void)wdgs_sync_lanes(d);
-        free_dev(op->rgba8); free_dev(op->alpha); free_dev(op->n_contrib);
-        op->rgba8 = nullptr; op->alpha = nullptr; op->n_contrib = nullptr;
+        op->rgba8.reset(); op->alpha.reset(); op->n_contrib.reset();   // free all, then allocate all
+        op->width = op->height = 0;   // (the size of the images the pass HOLDS: none until all three are there)
         const size_t px = (size_t)width * height;
-        WDGS_TRY(wdgs_alloc((void**)&op->rgba8, px * 4, true, d->stream));
-        WDGS_TRY(wdgs_alloc((void**)&op->alpha, px * 4, true, d->stream));
-        WDGS_TRY(wdgs_alloc((void**)&op->n_contrib, px * 4, true, d->stream));
+        WDGS_TRY(op->rgba8.alloc(px, true, d->stream));
+        WDGS_TRY(op->alpha.alloc(px, true, d->stream));
+        WDGS_TRY(op->n_contrib.alloc(px, true, d->stream));
         op->width = width;
         op->height = height;
     }
-    const int fo = wdgs_sorter_final_out_index(f->sorter);
-    const void* keys = wdgs_sorter_keys(f->sorter, fo);
-    const void* vals = wdgs_sorter_values(f->sorter, fo);
+    const int fo = wdgs_sorter_final_out_index(f->sorter.get());
+    const void* keys = wdgs_sorter_keys(f->sorter.get(), fo);
+    const void* vals = wdgs_sorter_values(f->sorter.get(), fo);
     if (f->ranges_valid) {
         op->ranges_used = f->ranges;  // built by the forward pass's sort
     } else {
-        if (ti.total_tiles + 1 > op->ranges_capacity) {
+        if (ti.total_tiles + 1 > op->ranges.count()) {
             WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledRasterizer.encode allocates its range table on first use: run one eager encode before recording");
             (void)wdgs_sync_lanes(d);
-            free_dev(op->ranges);
-            op->ranges = nullptr;
-            WDGS_TRY(wdgs_alloc((void**)&op->ranges, sizeof(u32) * (size_t)(ti.total_tiles + 1), true, d->stream));
-            op->ranges_capacity = ti.total_tiles + 1;
+            op->ranges_used = nullptr;
+            WDGS_TRY(op->ranges.alloc((size_t)ti.total_tiles + 1, true, d->stream));
         }
         WDGS_TRY(launch_tile_ranges(d, keys, f->stats, ti.total_tiles, op->ranges));
         op->ranges_used = op->ranges;
@@ -1218,11 +1186,11 @@ int wdgs_tiled_rasterizer_encode_depth(wdgs_tiled_rasterizer* op, uint32_t kinds
     wdgs_device* d = op->dev;
     if (op->depth_width != op->width || op->depth_height != op->height) {   // a size change: the images are re-made per kind below
         bool any = false;
-        for (float* img : op->depth) any = any || img != nullptr;
+        for (const DevMem<float>& img : op->depth) any = any || img;
         if (any) {
             WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledRasterizer.encodeDepth re-allocates its images after a size change: run one eager encodeDepth before recording");
             (void)wdgs_sync_lanes(d);
-            for (float*& img : op->depth) { free_dev(img); img = nullptr; }
+            for (DevMem<float>& img : op->depth) img.reset();
         }
         op->depth_width = op->width;
         op->depth_height = op->height;
@@ -1230,11 +1198,11 @@ int wdgs_tiled_rasterizer_encode_depth(wdgs_tiled_rasterizer* op, uint32_t kinds
     for (u32 k = 0; k < 3u; k++) {
         if (!((kinds >> k) & 1u) || op->depth[k]) continue;
         WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledRasterizer.encodeDepth allocates a depth image on first use of its kind: run one eager encodeDepth before recording");
-        WDGS_TRY(wdgs_alloc((void**)&op->depth[k], (size_t)op->width * op->height * 4, true, d->stream));
+        WDGS_TRY(op->depth[k].alloc((size_t)op->width * op->height, true, d->stream));
     }
-    const int fo = wdgs_sorter_final_out_index(f->sorter);
-    WDGS_TRY(launch_depth_composite(d, f->settings, f->tile_info, f->splats, f->cfg.num_points, f->depths, op->ranges_used, wdgs_sorter_keys(f->sorter, fo),
-                                    wdgs_sorter_values(f->sorter, fo), f->stats, op->compat_caps ? 32u : 0u, (kinds & WDGS_DEPTH_WEIGHT_SUM) ? op->depth[2] : nullptr,
+    const int fo = wdgs_sorter_final_out_index(f->sorter.get());
+    WDGS_TRY(launch_depth_composite(d, f->settings, f->tile_info, f->splats, f->cfg.num_points, f->depths, op->ranges_used, wdgs_sorter_keys(f->sorter.get(), fo),
+                                    wdgs_sorter_values(f->sorter.get(), fo), f->stats, op->compat_caps ? 32u : 0u, (kinds & WDGS_DEPTH_WEIGHT_SUM) ? op->depth[2] : nullptr,
                                     (kinds & WDGS_DEPTH_EXPECTED) ? op->depth[0] : nullptr, (kinds & WDGS_DEPTH_MEDIAN) ? op->depth[1] : nullptr, f->nf_stamp,
                                     f->stats + FRAME_WORD));
     op->depth_encoded = kinds;
@@ -1272,25 +1240,26 @@ int wdgs_tiled_rasterizer_blit(wdgs_tiled_rasterizer* op, void* target, uint32_t
 // ---------------------------------------------------------------- TiledBackwardPass
 static int backward_alloc_images(wdgs_tiled_backward* op, u32 w, u32 h) {
     const u32 px = w * h;
-    if (px <= op->img_capacity) return WDGS_OK;
+    if (px <= op->metric_flags.count()) return WDGS_OK;   // (the image allocated last: when it is there, all three are)
+    hipStream_t stream = op->dev->stream;
     (void)wdgs_sync_lanes(op->dev);
-    free_dev(op->loss_image); free_dev(op->metric_err); free_dev(op->metric_flags);
-    op->loss_image = nullptr; op->metric_err = nullptr; op->metric_flags = nullptr;
-    WDGS_TRY(wdgs_alloc((void**)&op->loss_image, (size_t)px * 16, true, op->dev->stream));
-    WDGS_TRY(wdgs_alloc((void**)&op->metric_err, (size_t)px * 4, true, op->dev->stream));
-    WDGS_TRY(wdgs_alloc((void**)&op->metric_flags, (size_t)px * 4, true, op->dev->stream));
-    op->img_capacity = px;
+    op->loss_image.reset(); op->metric_err.reset(); op->metric_flags.reset();   // free all, then allocate all
+    WDGS_TRY(op->loss_image.alloc((size_t)px * 4, true, stream));
+    WDGS_TRY(op->metric_err.alloc(px, true, stream));
+    WDGS_TRY(op->metric_flags.alloc(px, true, stream));
     return WDGS_OK;
 }
 
+// (Re)allocates the per-Gaussian buffers for `capacity` Gaussians: free all, then allocate all
 static int backward_alloc_per_point(wdgs_tiled_backward* op, u32 capacity) {
-    wdgs_device* d = op->dev;
-    int r = wdgs_alloc((void**)&op->acc, (size_t)capacity * 48 + 16, true, d->stream);
-    if (r == WDGS_OK) op->acc_dirty = reinterpret_cast<u32*>(reinterpret_cast<char*>(op->acc) + (size_t)capacity * 48);
-    if (r == WDGS_OK) r = wdgs_alloc((void**)&op->gradients, (size_t)capacity * 32, true, d->stream);
-    if (r == WDGS_OK) r = wdgs_alloc((void**)&op->metric_counts, (size_t)capacity * 4, true, d->stream);
-    if (r == WDGS_OK) op->points_capacity = capacity;
-    return r;
+    hipStream_t stream = op->dev->stream;
+    op->acc.reset(); op->gradients.reset(); op->metric_counts.reset();
+    op->points_capacity = 0;
+    WDGS_TRY(op->acc.alloc((size_t)capacity * 12 + 4, true, stream));
+    WDGS_TRY(op->gradients.alloc((size_t)capacity * 8, true, stream));
+    WDGS_TRY(op->metric_counts.alloc(capacity, true, stream));
+    op->points_capacity = capacity;
+    return WDGS_OK;
 }
 // Counterpart of wdgs_tiled_forward_resize for the backward pass's per-Gaussian buffers (accumulators, packed gradients, metric counts).
 int wdgs_tiled_backward_resize(wdgs_tiled_backward* op, uint32_t n) {
@@ -1301,13 +1270,10 @@ int wdgs_tiled_backward_resize(wdgs_tiled_backward* op, uint32_t n) {
     WDGS_CHECK_HIP(wdgs_sync_lanes(d));
     const u32 need = std::max(n, 1u);
     if (need > op->points_capacity) {
-        free_dev(op->acc); free_dev(op->gradients); free_dev(op->metric_counts);
-        op->acc = nullptr; op->gradients = nullptr; op->metric_counts = nullptr;
-        op->points_capacity = 0;
         WDGS_TRY(backward_alloc_per_point(op, (u32)std::min<uint64_t>((uint64_t)need + need / 4, 0xFFFFFFFFull)));
     } else {
         WDGS_CHECK_HIP(hipMemsetAsync(op->acc, 0, (size_t)need * 48, d->stream));
-        WDGS_CHECK_HIP(hipMemsetAsync(op->acc_dirty, 0, 16, d->stream));
+        WDGS_CHECK_HIP(hipMemsetAsync(op->acc_dirty(), 0, 16, d->stream));
         WDGS_CHECK_HIP(hipMemsetAsync(op->gradients, 0, (size_t)need * 32, d->stream));
         WDGS_CHECK_HIP(hipMemsetAsync(op->metric_counts, 0, (size_t)need * 4, d->stream));
     }
@@ -1317,28 +1283,23 @@ int wdgs_tiled_backward_resize(wdgs_tiled_backward* op, uint32_t n) {
 int wdgs_tiled_backward_create(wdgs_device* d, const wdgs_tiled_backward_config* cfg, wdgs_tiled_backward** out) {
     WDGS_REQUIRE(d && cfg && out, WDGS_E_INVALID, "wdgs_tiled_backward_create: null argument");
     WDGS_REQUIRE(cfg->viewport_width > 0 && cfg->viewport_height > 0, WDGS_E_INVALID, "viewport must be non-empty");
-    wdgs_tiled_backward* op = new wdgs_tiled_backward();
-    std::memset(op, 0, sizeof(*op));
+    auto op = std::make_unique<wdgs_tiled_backward>();
     op->dev = d;
     op->cfg = *cfg;
-    op->gradient_output = true;
     if (op->cfg.training.c1 == 0.f) op->cfg.training.c1 = 0.01f * 0.01f;  // tiled-backward-pass.ts:172-173
     if (op->cfg.training.c2 == 0.f) op->cfg.training.c2 = 0.03f * 0.03f;
     op->settings = RenderSettings{cfg->gaussian_scale != 0.f ? cfg->gaussian_scale : 1.0f, (float)cfg->sh_deg, (float)cfg->viewport_width,
                                   (float)cfg->viewport_height, cfg->point_size_px != 0.f ? cfg->point_size_px : 3.0f, 0.0f,
                                   cfg->max_splat_radius_px != 0.f ? cfg->max_splat_radius_px : 128.0f};
-    int r = backward_alloc_per_point(op, std::max(cfg->num_points, 1u));
-    if (r == WDGS_OK) r = wdgs_alloc((void**)&op->metric_minmax, 4096, true, d->stream);
-    if (r == WDGS_OK) r = backward_alloc_images(op, cfg->viewport_width, cfg->viewport_height);
-    if (r != WDGS_OK) { wdgs_tiled_backward_destroy(op); return r; }
-    *out = op;
+    WDGS_TRY(backward_alloc_per_point(op.get(), std::max(cfg->num_points, 1u)));
+    WDGS_TRY(op->metric_minmax.alloc(1024, true, d->stream));
+    WDGS_TRY(backward_alloc_images(op.get(), cfg->viewport_width, cfg->viewport_height));
+    *out = op.release();
     return WDGS_OK;
 }
 int wdgs_tiled_backward_destroy(wdgs_tiled_backward* op) {
     if (!op) return WDGS_OK;
     sync_if_alive(op->dev);
-    free_dev(op->acc); free_dev(op->gradients); free_dev(op->loss_image); free_dev(op->metric_counts);
-    free_dev(op->metric_err); free_dev(op->metric_flags); free_dev(op->metric_minmax);
     delete op;
     return WDGS_OK;
 }
@@ -1362,14 +1323,14 @@ static int backward_encode_raster(wdgs_tiled_backward* op, const void* pred, con
     wdgs_device* d = op->dev;
     const u32 w = op->cfg.viewport_width, h = op->cfg.viewport_height, n = op->cfg.num_points;
     // K15 + clearBuffer x4 (tiled-backward-pass.ts:624-627): the clear rides on the loss kernel and is a no-op behind a consuming K17
-    if (w > 0 && h > 0) WDGS_TRY(backward_loss(op, pred, targ, op->acc, std::max(n, 1u), op->acc_dirty));
-    else WDGS_TRY(launch_acc_clear_if_dirty(d, op->acc, n, op->acc_dirty));
+    if (w > 0 && h > 0) WDGS_TRY(backward_loss(op, pred, targ, op->acc, std::max(n, 1u), op->acc_dirty()));
+    else WDGS_TRY(launch_acc_clear_if_dirty(d, op->acc, n, op->acc_dirty()));
     // long tile lists (longlist.h): when the range table is one a forward pass of this device built, that pass's lists serve the backward walk too
     const LongWork* lw = nullptr;
     auto owner = d->range_tables.find(res->tile_offsets_buffer);
     if (owner != d->range_tables.end() && owner->second->ranges_valid && owner->second->long_lists.hdr) lw = &owner->second->long_lists;
     return launch_backward_rasterize(d, op->settings, ceil_div(w, 16), ceil_div(h, 16), res->tile_offsets_buffer, res->tile_indices_buffer, res->splat_buffer,
-                                     res->alpha_texture, res->n_contrib_texture, op->loss_image, op->acc, op->acc_dirty, lw);
+                                     res->alpha_texture, res->n_contrib_texture, op->loss_image, op->acc, op->acc_dirty(), lw);
 }
 int wdgs_tiled_backward_encode(wdgs_tiled_backward* op, const void* pred, const void* targ, const wdgs_tiled_backward_resources* res,
                                const void* gaussians) {
@@ -1392,7 +1353,7 @@ int wdgs_tiled_backward_encode_geometry(wdgs_tiled_backward* op, const void* cam
     if (!into) return launch_geometry_backward(op->dev, op->cfg.num_points, camera, op->settings, gaussians, op->acc, op->gradients);
     WDGS_REQUIRE(into->sums && into->visible && into->tile_counts && into->guard && into->overflow_word, WDGS_E_INVALID,
                  "wdgs_tiled_backward_encode_geometry: incomplete accumulate target");
-    return launch_geometry_backward_accumulate(op->dev, op->cfg.num_points, camera, op->settings, gaussians, op->acc, op->acc_dirty, op->gradients, into->sums, into->visible,
+    return launch_geometry_backward_accumulate(op->dev, op->cfg.num_points, camera, op->settings, gaussians, op->acc, op->acc_dirty(), op->gradients, into->sums, into->visible,
                                                into->tile_counts, into->guard, into->overflow_word, into->first ? 1u : 2u);
 }
 // ---- view-batched K17 (include/webdgs.h)
@@ -1409,7 +1370,7 @@ int wdgs_tiled_backward_encode_geometry_views(wdgs_tiled_backward* const* ops, c
         for (u32 u = 0; u < v; u++) WDGS_REQUIRE(ops[u] != b, WDGS_E_INVALID, "wdgs_tiled_backward_encode_geometry_views: pass %u is given twice (every view has accumulators of its own)", v);
         WDGS_REQUIRE(b->dev == b0->dev && b->cfg.num_points == b0->cfg.num_points && std::memcmp(&b->settings, &b0->settings, sizeof(RenderSettings)) == 0, WDGS_E_STATE,
                      "wdgs_tiled_backward_encode_geometry_views: pass %u differs from pass 0 (cloud size, viewport or settings)", v);
-        accs[v] = b->acc; dirty[v] = b->acc_dirty; grads[v] = b->gradients;
+        accs[v] = b->acc; dirty[v] = b->acc_dirty(); grads[v] = b->gradients;
     }
     return launch_geometry_backward_views(b0->dev, b0->cfg.num_points, count, cameras, b0->settings, gaussians, accs, dirty, tile_counts, overflow_words,
                                           write_gradients ? grads : nullptr, sums, visible, guard, continues ? 1u : 0u);
@@ -1486,56 +1447,38 @@ int wdgs_optimizer_state_sizes(uint32_t n, size_t sizes[6]) {
     return WDGS_OK;
 }
 
-static void optimizer_free_state(wdgs_optimizer* op) {
-    free_dev(op->state.opt_pos); free_dev(op->state.opt_rot); free_dev(op->state.opt_scale);
-    free_dev(op->state.opt_opacity); free_dev(op->state.param_sh); free_dev(op->state.state_sh);
-    std::memset(&op->state, 0, sizeof(op->state));
-}
-
 int wdgs_optimizer_create(wdgs_device* d, uint32_t n, const wdgs_adam_hyperparameters* params, const void* gaussians, const void* sh,
                           const wdgs_optimizer_state* initial, int owns_state, uint32_t initial_iteration, wdgs_optimizer** out) {
     WDGS_REQUIRE(d && out, WDGS_E_INVALID, "wdgs_optimizer_create: null argument");
-    wdgs_optimizer* op = new wdgs_optimizer();
-    std::memset(op, 0, sizeof(*op));
+    auto op = std::make_unique<wdgs_optimizer>();
     op->dev = d;
     op->num_points = n;
-    const wdgs_adam_hyperparameters defaults = {0.00016f, 0.0025f, 0.05f, 0.005f, 0.001f, 0.9f, 0.999f, 1e-8f};  // adam-config.ts:12-21
-    op->params = params ? *params : defaults;
+    if (params) op->params = *params;
+    size_t sz[6];
+    wdgs_optimizer_state_sizes(n, sz);
     if (initial) {
         WDGS_REQUIRE(initial->opt_pos && initial->opt_rot && initial->opt_scale && initial->opt_opacity && initial->param_sh && initial->state_sh,
                      WDGS_E_INVALID, "wdgs_optimizer_create: incomplete initial state");
         op->state = *initial;
-        op->owns_state = owns_state != 0;
+        void* const given[6] = {initial->opt_pos, initial->opt_rot, initial->opt_scale, initial->opt_opacity, initial->param_sh, initial->state_sh};
+        for (int i = 0; owns_state && i < 6; i++) op->owned[i].adopt(static_cast<char*>(given[i]), sz[i]);
         op->iteration = initial_iteration;
     } else {
-        if (!(gaussians && sh)) { delete op; wdgs_set_error("wdgs_optimizer_create: point cloud required when no initial state is given"); return WDGS_E_INVALID; }
-        size_t sz[6];
-        wdgs_optimizer_state_sizes(n, sz);
-        void** fields[6] = {&op->state.opt_pos, &op->state.opt_rot, &op->state.opt_scale, &op->state.opt_opacity, &op->state.param_sh, &op->state.state_sh};
-        op->owns_state = true;
-        for (int i = 0; i < 6; i++) {
-            int r = wdgs_alloc(fields[i], sz[i], true, d->stream);
-            if (r != WDGS_OK) { optimizer_free_state(op); delete op; return r; }
-        }
-        int r = launch_unpack(d, n, gaussians, sh, op->state);
-        if (r != WDGS_OK) { optimizer_free_state(op); delete op; return r; }
-        op->iteration = 0;
+        WDGS_REQUIRE(gaussians && sh, WDGS_E_INVALID, "wdgs_optimizer_create: point cloud required when no initial state is given");
+        for (int i = 0; i < 6; i++) WDGS_TRY(op->owned[i].alloc(sz[i], true, d->stream));
+        op->state = wdgs_optimizer_state{op->owned[0].get(), op->owned[1].get(), op->owned[2].get(), op->owned[3].get(), op->owned[4].get(), op->owned[5].get()};
+        WDGS_TRY(launch_unpack(d, n, gaussians, sh, op->state));
     }
-    int r = wdgs_alloc((void**)&op->dc, sizeof(float4) * CS_PLANES * (size_t)wdgs_optimizer::cs_pitch(n), true, d->stream);
-    if (r == WDGS_OK) r = launch_cs_load(d, n, op->state, op->cs());
-    if (r != WDGS_OK) { free_dev(op->dc); if (op->owns_state) optimizer_free_state(op); delete op; return r; }
-    op->dc_dirty = false;
-    *out = op;
+    WDGS_TRY(op->dc.alloc(CS_PLANES * (size_t)wdgs_optimizer::cs_pitch(n), true, d->stream));
+    WDGS_TRY(launch_cs_load(d, n, op->state, op->cs()));
+    *out = op.release();
     return WDGS_OK;
 }
 int wdgs_optimizer_destroy(wdgs_optimizer* op) {
     if (!op) return WDGS_OK;
     const bool live = wdgs_device_alive(op->dev) && !op->dev->capturing;
-    if (!op->owns_state && live) (void)optimizer_flush_dc(op);  // adopted buffers outlive the optimizer: leave them current
+    if (!op->owns_state() && live) (void)optimizer_flush_dc(op);  // adopted buffers outlive the optimizer: leave them current
     sync_if_alive(op->dev);
-    if (op->owns_state) optimizer_free_state(op);
-    free_dev(op->dc);
-    free_dev(op->dc_words);
     delete op;
     return WDGS_OK;
 }
@@ -1560,7 +1503,7 @@ int wdgs_optimizer_step_with_geometry(wdgs_optimizer* op, wdgs_tiled_backward* b
     op->iteration++;  // optimizer.ts:301
     op->dc_dirty = true;
     if (op->deferred_sh) op->sh_stale = true;
-    return launch_geometry_backward_adam(op->dev, op->num_points, camera, bwd->settings, gaussians, bwd->acc, bwd->acc_dirty, bwd->gradient_output ? bwd->gradients : nullptr,
+    return launch_geometry_backward_adam(op->dev, op->num_points, camera, bwd->settings, gaussians, bwd->acc, bwd->acc_dirty(), bwd->gradient_output ? bwd->gradients : nullptr,
                                          op->params, tile_counts, op->state,
                                          op->cs(), sh, op->guard, op->deferred_sh ? op->dc_words : nullptr);
 }
@@ -1614,7 +1557,7 @@ int wdgs_optimizer_set_deferred_sh(wdgs_optimizer* op, void* sh, int enabled) {
         op->sh_stale = false;
         return WDGS_OK;
     }
-    if (!op->dc_words) WDGS_TRY(wdgs_alloc((void**)&op->dc_words, sizeof(u32) * 2 * (size_t)std::max(op->num_points, 1u), true, op->dev->stream));
+    if (!op->dc_words) WDGS_TRY(op->dc_words.alloc((size_t)2 * std::max(op->num_points, 1u), true, op->dev->stream));
     if (!op->deferred_sh || !op->sh_stale) WDGS_TRY(launch_dc_words_load(op->dev, op->num_points, sh, op->dc_words));  // the rows are current: take their DC halves
     op->deferred_sh = true;
     return WDGS_OK;
@@ -1673,7 +1616,7 @@ int wdgs_optimizer_release_state(wdgs_optimizer* op, wdgs_optimizer_state* out) 
     WDGS_REQUIRE(op && out, WDGS_E_INVALID, "null argument");
     WDGS_TRY(optimizer_flush_dc(op));
     *out = op->state;
-    op->owns_state = false;
+    for (auto& m : op->owned) (void)m.release();   // the arrays are the caller's from here on: `state` stays the view of them
     return WDGS_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/webdgs.h"
+#include "devmem.h"   // wdgs_alloc / wdgs_free and DevMem<T>, the owner of every block they hand out
 
 typedef uint32_t u32;
 typedef int32_t i32;
@@ -149,15 +150,16 @@ struct SsimWindow { float g[SSIM_TAPS]; };
 const SsimWindow& ssim_window();
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
-int wdgs_alloc(void** p, size_t bytes, bool zero, hipStream_t stream);
-void wdgs_free(void* p);   // the counterpart of wdgs_alloc (api.hip: freed blocks are kept by size class)
+using wdgs::DevMem;
 // true between wdgs_device_create and wdgs_device_destroy (api.hip): destroy functions check it before touching op->dev
 bool wdgs_device_alive(const wdgs_device* d);
 
 // ---- primitives implemented in scan.hip / sort.hip, used by the ops
-struct ScanScratch { u32* block_sums = nullptr; u32 capacity_blocks = 0; };
+struct ScanScratch {
+    DevMem<u32> block_sums;   // one sum per block of the scan, and the grand total behind them
+    u32 capacity_blocks() const { return block_sums ? (u32)block_sums.count() - 1u : 0u; }
+};
 int scan_scratch_create(ScanScratch* s, u32 max_elements);
-void scan_scratch_destroy(ScanScratch* s);
 // Exclusive u32 scan of `count` (host-known) elements.  If total_out != nullptr, writes the grand total there.
 int scan_exclusive_u32(wdgs_device* dev, ScanScratch* s, const u32* in, u32* out, u32 count, u32* total_out);
 // Same, with the forward pass's stats epilogue folded into the single-block middle kernel (count must be > 0 for it to run).

@@ -8,6 +8,7 @@
 // order-free u32 atomicMin/atomicMax, and its six scatter launches (each re-reading offsets/counts/actions) become one.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 
 #include "common.h"
 #include "wgslm.h"
@@ -409,43 +410,31 @@ int launch_metric_normalize(wdgs_device* dev, u32 n, u32 divisor, void* counts) 
 
 // ------------------------------------------------------------------ DensifyPrunePass (C ABI)
 struct wdgs_densify_prune {
-    wdgs_device* dev;
-    wdgs_densify_config cfg;
-    u32 capacity;  // points the work buffers are sized for
-    u32 *actions, *counts, *offsets, *total;
+    wdgs_device* dev = nullptr;
+    wdgs_densify_config cfg = {1, 0, 0.f, 0.f, 0, 128ull * 1024 * 1024};  // densify-prune.ts:110-119
+    DevMem<u32> actions, counts, offsets;   // work buffers of one size: actions.count() is the points they hold
+    DevMem<u32> total;
     ScanScratch scan;
-    u32 last_max_out;
+    u32 last_max_out = 0;
+    // the four work buffers are freed together and allocated in one order (ensure_size): when the last one is there, all are
+    bool holds(u32 n) const { return scan.block_sums && n <= actions.count(); }
 };
-
-static void densify_free(wdgs_densify_prune* op) {
-    if (op->actions) wdgs_free(op->actions);
-    if (op->counts) wdgs_free(op->counts);
-    if (op->offsets) wdgs_free(op->offsets);
-    op->actions = op->counts = op->offsets = nullptr;
-    scan_scratch_destroy(&op->scan);
-    op->capacity = 0;
-}
 
 extern "C" {
 
 int wdgs_densify_prune_create(wdgs_device* dev, const wdgs_densify_config* cfg, wdgs_densify_prune** out) {
     WDGS_REQUIRE(dev && out, WDGS_E_INVALID, "wdgs_densify_prune_create: null argument");
-    wdgs_densify_prune* op = new wdgs_densify_prune();
-    std::memset(op, 0, sizeof(*op));
+    auto op = std::make_unique<wdgs_densify_prune>();
     op->dev = dev;
     if (cfg) op->cfg = *cfg;
-    else op->cfg = wdgs_densify_config{1, 0, 0.f, 0.f, 0, 128ull * 1024 * 1024};  // densify-prune.ts:110-119
-    int r = wdgs_alloc((void**)&op->total, 16, true, dev->stream);
-    if (r != WDGS_OK) { delete op; return r; }
-    *out = op;
+    WDGS_TRY(op->total.alloc(4, true, dev->stream));
+    *out = op.release();
     return WDGS_OK;
 }
 
 int wdgs_densify_prune_destroy(wdgs_densify_prune* op) {
     if (!op) return WDGS_OK;
     if (wdgs_device_alive(op->dev) && !op->dev->capturing) (void)wdgs_sync_lanes(op->dev);
-    densify_free(op);
-    if (op->total) wdgs_free(op->total);
     delete op;
     return WDGS_OK;
 }
@@ -458,16 +447,14 @@ int wdgs_densify_prune_set_config(wdgs_densify_prune* op, const wdgs_densify_con
 
 int wdgs_densify_prune_ensure_size(wdgs_densify_prune* op, uint32_t n) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "null op");
-    if (n <= op->capacity && op->actions) return WDGS_OK;
+    if (op->holds(n)) return WDGS_OK;
     (void)wdgs_sync_lanes(op->dev);
-    densify_free(op);
+    op->actions.reset(); op->counts.reset(); op->offsets.reset(); op->scan.block_sums.reset();   // (free all, then allocate all)
     const size_t N = std::max(n, 1u);
-    WDGS_TRY(wdgs_alloc((void**)&op->actions, N * 4, true, op->dev->stream));
-    WDGS_TRY(wdgs_alloc((void**)&op->counts, N * 4, true, op->dev->stream));
-    WDGS_TRY(wdgs_alloc((void**)&op->offsets, N * 4, true, op->dev->stream));
-    WDGS_TRY(scan_scratch_create(&op->scan, (u32)N));
-    op->capacity = (u32)N;
-    return WDGS_OK;
+    WDGS_TRY(op->actions.alloc(N, true, op->dev->stream));
+    WDGS_TRY(op->counts.alloc(N, true, op->dev->stream));
+    WDGS_TRY(op->offsets.alloc(N, true, op->dev->stream));
+    return scan_scratch_create(&op->scan, (u32)N);
 }
 
 // computeMaxOutPoints (densify-prune.ts:390-410): 24 B Gaussian, 96 B SH per point; max_buffer_bytes = 0 lifts the cap.
@@ -491,14 +478,14 @@ int wdgs_densify_prune_encode_decision(wdgs_densify_prune* op, uint32_t n, const
 
 int wdgs_densify_prune_encode_prefix_sum(wdgs_densify_prune* op, uint32_t n) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "null op");
-    WDGS_REQUIRE(op->actions && n <= op->capacity, WDGS_E_STATE, "encodePrefixSum before encodeDecision/ensureSize for %u points", n);
+    WDGS_REQUIRE(op->holds(n), WDGS_E_STATE, "encodePrefixSum before encodeDecision/ensureSize for %u points", n);
     if (n == 0) return WDGS_OK;
     return scan_exclusive_u32(op->dev, &op->scan, op->counts, op->offsets, n, nullptr);
 }
 
 int wdgs_densify_prune_encode_cap_to_max(wdgs_densify_prune* op, uint32_t n, uint32_t max_out_points) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "null op");
-    WDGS_REQUIRE(op->actions && n <= op->capacity, WDGS_E_STATE, "encodeCapToMax before encodeDecision/ensureSize for %u points", n);
+    WDGS_REQUIRE(op->holds(n), WDGS_E_STATE, "encodeCapToMax before encodeDecision/ensureSize for %u points", n);
     op->last_max_out = max_out_points;
     if (n == 0) return WDGS_OK;
     WDGS_LAUNCH(op->dev, "densify_cap", cap_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, max_out_points, op->offsets, op->counts, op->actions);
@@ -508,7 +495,7 @@ int wdgs_densify_prune_encode_cap_to_max(wdgs_densify_prune* op, uint32_t n, uin
 
 int wdgs_densify_prune_encode_total_out(wdgs_densify_prune* op, uint32_t n) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "null op");
-    WDGS_REQUIRE(n == 0 || (op->actions && n <= op->capacity), WDGS_E_STATE, "encodeTotalOut before encodeDecision/ensureSize for %u points", n);
+    WDGS_REQUIRE(n == 0 || (op->holds(n)), WDGS_E_STATE, "encodeTotalOut before encodeDecision/ensureSize for %u points", n);
     WDGS_LAUNCH(op->dev, "densify_total", total_kernel, dim3(1), dim3(64), 0, n, op->offsets, op->counts, op->total);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
@@ -522,7 +509,7 @@ int wdgs_densify_prune_compute_max_out_points(wdgs_densify_prune* op, uint32_t n
 
 int wdgs_densify_prune_get_buffers(wdgs_densify_prune* op, wdgs_densify_prepared* out) {
     WDGS_REQUIRE(op && out, WDGS_E_INVALID, "null argument");
-    WDGS_REQUIRE(op->actions, WDGS_E_STATE, "DensifyPrunePass: buffers not created yet (call ensureSize or an encode first)");
+    WDGS_REQUIRE(op->holds(0), WDGS_E_STATE, "DensifyPrunePass: buffers not created yet (call ensureSize or an encode first)");
     out->action_buffer = op->actions;
     out->out_count_buffer = op->counts;
     out->out_offset_buffer = op->offsets;
@@ -556,7 +543,7 @@ int wdgs_densify_prune_encode_scatter(wdgs_densify_prune* op, uint32_t in_points
                                       const wdgs_optimizer_state* in_state, uint32_t out_num_points, int reset_new, void* out_gaussians, void* out_sh,
                                       const wdgs_optimizer_state* out_state) {
     WDGS_REQUIRE(op && in_gaussians && in_sh && out_gaussians && out_sh, WDGS_E_INVALID, "wdgs_densify_prune_encode_scatter: null argument");
-    WDGS_REQUIRE(op->actions && in_points <= op->capacity, WDGS_E_STATE, "encode_scatter before encode_prepare for %u points", in_points);
+    WDGS_REQUIRE(op->holds(in_points), WDGS_E_STATE, "encode_scatter before encode_prepare for %u points", in_points);
     WDGS_REQUIRE((in_state == nullptr) == (out_state == nullptr), WDGS_E_INVALID, "in_state and out_state must both be given or both be null");
     WDGS_REQUIRE(out_num_points > 0, WDGS_E_INVALID, "encodeScatter: outPointCloud.num_points must be > 0");
     if (in_points == 0) return WDGS_OK;

@@ -166,14 +166,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_downsweep_kernel(const u32*
 }  // namespace
 
 int scan_scratch_create(ScanScratch* s, u32 max_elements) {
-    s->capacity_blocks = ceil_div(max_elements > 0 ? max_elements : 1, SCAN_TILE);
-    return wdgs_alloc((void**)&s->block_sums, sizeof(u32) * (size_t)(s->capacity_blocks + 1), true, nullptr);
-}
-
-void scan_scratch_destroy(ScanScratch* s) {
-    if (s->block_sums) wdgs_free(s->block_sums);
-    s->block_sums = nullptr;
-    s->capacity_blocks = 0;
+    return s->block_sums.alloc((size_t)ceil_div(max_elements > 0 ? max_elements : 1, SCAN_TILE) + 1, true, nullptr);
 }
 
 // In-place exclusive scan of `num_blocks` per-workgroup sums by one workgroup, with the forward pass's stats epilogue: the middle
@@ -200,7 +193,7 @@ int scan_exclusive_u32_stats(wdgs_device* dev, ScanScratch* s, const u32* in, u3
         return WDGS_OK;
     }
     const u32 blocks = ceil_div(count, SCAN_TILE);
-    WDGS_REQUIRE(blocks <= s->capacity_blocks, WDGS_E_CAPACITY, "scan: %u elements exceed the scanner's capacity (%u blocks)", count, s->capacity_blocks);
+    WDGS_REQUIRE(blocks <= s->capacity_blocks(), WDGS_E_CAPACITY, "scan: %u elements exceed the scanner's capacity (%u blocks)", count, s->capacity_blocks());
     WDGS_LAUNCH(dev, "scan_reduce", scan_reduce_kernel, dim3(blocks), dim3(SCAN_THREADS), 0, in, count, s->block_sums);
     WDGS_LAUNCH(dev, "scan_block_sums", scan_block_sums_kernel, dim3(1), dim3(SCAN_THREADS), 0, s->block_sums, blocks, total_out, ep);
     WDGS_LAUNCH(dev, "scan_downsweep", scan_downsweep_kernel, dim3(blocks), dim3(SCAN_THREADS), 0, in, out, count, s->block_sums);

@@ -21,6 +21,7 @@
 // The result is the order a stable sort of the full 32-bit key gives -- (tile, depth16, emission order) -- for 4E + 16E per tile
 // pass + 16E for the segment sort = 56E bytes instead of 84E, and 9 launches instead of 12.
 #include <algorithm>
+#include <memory>
 
 #include "common.h"
 #include "longlist.h"
@@ -633,16 +634,16 @@ __global__ __launch_bounds__(SEG_THREADS, 6) void segment_sort_kernel(u32* __res
 }  // namespace
 
 struct wdgs_sorter {
-    wdgs_device* dev;
-    u32 capacity;       // elements (multiple of SORT_TILE_MAX)
-    u32 items;          // keys per thread of a partition: SORT_ITEMS_MAX, or 4 for a small sorter
-    u32 num_parts;
-    const u32* count_ptr;
-    u32* keys[2];
-    u32* vals[2];
-    u32* counts;        // [RADIX][num_parts], scanned in place per pass
-    u32* totals;        // [RADIX]
-    int final_out_index;
+    wdgs_device* dev = nullptr;
+    u32 capacity = 0;       // elements (multiple of SORT_TILE_MAX)
+    u32 items = 0;          // keys per thread of a partition: SORT_ITEMS_MAX, or 4 for a small sorter
+    u32 num_parts = 0;
+    const u32* count_ptr = nullptr;
+    DevMem<u32> keys[2];
+    DevMem<u32> vals[2];
+    DevMem<u32> counts;     // [RADIX][num_parts], scanned in place per pass
+    DevMem<u32> totals;     // [RADIX]
+    int final_out_index = 0;
 };
 
 extern "C" {
@@ -650,42 +651,29 @@ extern "C" {
 int wdgs_sorter_create(wdgs_device* dev, uint32_t max_capacity, const void* stats_dev, wdgs_sorter** out) {
     WDGS_REQUIRE(dev && out && stats_dev, WDGS_E_INVALID, "wdgs_sorter_create: null argument");
     WDGS_REQUIRE(max_capacity <= 0xFFFFF000u, WDGS_E_CAPACITY, "sorter capacity %u too large", max_capacity);
-    wdgs_sorter* s = new wdgs_sorter();
+    auto s = std::make_unique<wdgs_sorter>();
     s->dev = dev;
     s->capacity = (u32)align_up(max_capacity > 0 ? max_capacity : 1, SORT_TILE_MAX);
     s->items = s->capacity <= (8u << 20) ? 4u : SORT_ITEMS_MAX;  // (c2's passes: 3.75 M entries of capacity, 0.36 M used; c3's: 37.5 M)
     s->num_parts = s->capacity / (SORT_THREADS * s->items);
     s->count_ptr = (const u32*)stats_dev;
-    s->final_out_index = 0;
-    for (int i = 0; i < 2; i++) { s->keys[i] = nullptr; s->vals[i] = nullptr; }
-    s->counts = nullptr;
-    s->totals = nullptr;
-    int r = WDGS_OK;
-    for (int i = 0; i < 2 && r == WDGS_OK; i++) {
-        r = wdgs_alloc((void**)&s->keys[i], sizeof(u32) * (size_t)s->capacity, true, dev->stream);
-        if (r == WDGS_OK) r = wdgs_alloc((void**)&s->vals[i], sizeof(u32) * (size_t)s->capacity, true, dev->stream);
+    for (int i = 0; i < 2; i++) {
+        WDGS_TRY(s->keys[i].alloc(s->capacity, true, dev->stream));
+        WDGS_TRY(s->vals[i].alloc(s->capacity, true, dev->stream));
     }
-    if (r == WDGS_OK) r = wdgs_alloc((void**)&s->counts, sizeof(u32) * (size_t)RADIX * s->num_parts, true, dev->stream);
-    if (r == WDGS_OK) r = wdgs_alloc((void**)&s->totals, sizeof(u32) * RADIX, true, dev->stream);
-    if (r != WDGS_OK) { wdgs_sorter_destroy(s); return r; }
-    *out = s;
+    WDGS_TRY(s->counts.alloc((size_t)RADIX * s->num_parts, true, dev->stream));
+    WDGS_TRY(s->totals.alloc(RADIX, true, dev->stream));
+    *out = s.release();
     return WDGS_OK;
 }
 
 int wdgs_sorter_destroy(wdgs_sorter* s) {
-    if (!s) return WDGS_OK;
-    for (int i = 0; i < 2; i++) {
-        if (s->keys[i]) wdgs_free(s->keys[i]);
-        if (s->vals[i]) wdgs_free(s->vals[i]);
-    }
-    if (s->counts) wdgs_free(s->counts);
-    if (s->totals) wdgs_free(s->totals);
     delete s;
     return WDGS_OK;
 }
 
-void* wdgs_sorter_keys(wdgs_sorter* s, int i) { return s ? s->keys[i & 1] : nullptr; }
-void* wdgs_sorter_values(wdgs_sorter* s, int i) { return s ? s->vals[i & 1] : nullptr; }
+void* wdgs_sorter_keys(wdgs_sorter* s, int i) { return s ? s->keys[i & 1].get() : nullptr; }
+void* wdgs_sorter_values(wdgs_sorter* s, int i) { return s ? s->vals[i & 1].get() : nullptr; }
 int wdgs_sorter_final_out_index(wdgs_sorter* s) { return s ? s->final_out_index : 0; }
 // (internal) the forward pass left unsorted entries in ping-pong 0 (encode(skipSort)): that is what the getters hand out
 void sorter_set_final_out_index(wdgs_sorter* s, int i) { if (s) s->final_out_index = i & 1; }
