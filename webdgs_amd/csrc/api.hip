@@ -11,58 +11,9 @@
 #include <unordered_map>
 #include <vector>
 
-#include "common.h"
+#include "launch.h"   // the kernel launchers and scan / sort primitives this file sequences: void* from the C ABI is cast where it meets one
 #include "alloc_cache.h"
 #include "longlist.h"
-
-// ---- kernel launchers (project.hip, sort.hip, raster.hip, loss.hip, backward.hip, optimizer.hip)
-int launch_project_count(wdgs_device*, u32, const void*, const void*, const void*, const RenderSettings&, const TileInfo&, void*, void*, void*, void*, void*, void*,
-                         const void*, void*, const void*);
-int launch_emit_scatter(wdgs_device*, u32, const void*, const void*, const void*, void*, const void*, const RenderSettings&, const TileInfo&, const void*, const void*, void*, void*, u32);
-int sorter_sort_rows(wdgs_sorter* s, u32 num_tiles_x, u32 num_tiles_y, u32* ranges, const LongWork* lw);
-extern "C" void sorter_set_final_out_index(wdgs_sorter* s, int i);
-int launch_update_stats(wdgs_device*, u32, const void*, const void*, u32, void*, void*, void*);
-int launch_emit(wdgs_device*, u32, const void*, const void*, const void*, void*, const void*, const RenderSettings&, const TileInfo&, void*, void*, u32);
-int launch_tile_ranges(wdgs_device*, const void*, const void*, u32, void*);
-int launch_depth_composite(wdgs_device*, const RenderSettings&, const TileInfo&, const void*, u32, const void*, const void*, const void*, const void*, const void*, u32,
-                           void*, void*, void*, const void*, const void*);
-int launch_rasterize(wdgs_device*, const RenderSettings&, const TileInfo&, const void*, u32, const void*, const void*, const void*, const void*, u32, void*,
-                     void*, void*, const void*, const void*, const LongWork*);
-int launch_loss_grad(wdgs_device*, u32, u32, const void*, const void*, const wdgs_training_config&, void*, void*, u32, const void*);
-int launch_dssim_grad(wdgs_device*, u32, u32, const void*, const void*, const wdgs_training_config&, void*, void*, u32, const void*);
-int launch_backward_rasterize(wdgs_device*, const RenderSettings&, u32, u32, const void*, const void*, const void*, const void*, const void*, const void*,
-                              void*, void*, const LongWork*);
-int launch_acc_clear_if_dirty(wdgs_device*, void*, u32, void*);
-int launch_geometry_backward_views(wdgs_device*, u32, u32, const void* const*, const RenderSettings&, const void*, void* const*, void* const*, const void* const*,
-                                   const void* const*, void* const*, void*, void*, void*, u32);
-int launch_project_count_views(wdgs_device*, u32, u32, const void*, const void*, const void* const*, const RenderSettings&, const TileInfo&, void* const*, void* const*,
-                               void* const*, void* const*, void* const*, void* const*, const void*, void* const*, const void* const*);
-int launch_geometry_backward(wdgs_device*, u32, const void*, const RenderSettings&, const void*, void*, void*);
-int launch_geometry_backward_adam(wdgs_device*, u32, const void*, const RenderSettings&, void*, void*, void*, void*, const wdgs_adam_hyperparameters&, const void*,
-                                  const wdgs_optimizer_state&, const CsView&, void*, const void*, void*);
-int launch_geometry_backward_accumulate(wdgs_device*, u32, const void*, const RenderSettings&, const void*, void*, void*, void*, void*, void*, const void*, void*,
-                                        const void*, u32);
-int launch_adam_repack(wdgs_device*, u32, const wdgs_adam_hyperparameters&, const void*, const void*, const wdgs_optimizer_state&, const CsView&, void*, void*,
-                       const void*, void*);
-int launch_adam_repack_f32(wdgs_device*, u32, u32, const wdgs_adam_hyperparameters&, const void*, const void*, const wdgs_optimizer_state&, const CsView&, void*,
-                           void*, const void*, void*, void*, void*);
-int launch_apply_rows(wdgs_device*, u32, const void*, u32, u32, const void*, void*, void*, void*, void*);
-int launch_dc_words_load(wdgs_device*, u32, const void*, void*);
-int launch_dc_words_flush(wdgs_device*, u32, const void*, void*);
-int launch_guard_accumulate(wdgs_device*, void*, const void*, u32);
-int launch_cs_load(wdgs_device*, u32, const wdgs_optimizer_state&, const CsView&);
-int launch_cs_flush(wdgs_device*, u32, const CsView&, const wdgs_optimizer_state&);
-int launch_accumulate_gradients(wdgs_device*, u32, const void*, const void*, void*, void*);
-int launch_store_gradients(wdgs_device*, u32, const void*, const void*, void*, void*);
-int launch_unpack(wdgs_device*, u32, const void*, const void*, const wdgs_optimizer_state&);
-int launch_metric_map(wdgs_device*, u32, u32, const void*, const void*, float, float, void*, void*, void*, void*);
-int launch_metric_count(wdgs_device*, const RenderSettings&, u32, u32, const void*, const void*, u32, const void*, u32, const void*, const void*, void*, u32);
-int launch_metric_normalize(wdgs_device*, u32, u32, void*);
-int launch_downsample(wdgs_device*, const void*, u32, u32, void*, u32, u32);
-
-int sorter_sort_segmented(wdgs_sorter* s, u32 segment_bits, u32 num_segments, u32* ranges, const LongWork* lw);
-extern "C" int wdgs_sorter_final_out_index(wdgs_sorter* s);
-extern "C" uint32_t wdgs_sorter_capacity(wdgs_sorter* s);
 
 static thread_local char g_last_error[512] = "";
 
@@ -195,7 +146,7 @@ struct wdgs_tiled_forward {
     // offset inside the column, and the column totals -- the digit counts of the sort's first pass, which emit_scatter performs (project.hip)
     DevMem<u32> column_counts;
     DevMem<u32> column_totals;
-    const void* dc_source = nullptr;  // nullable: the optimizer's compact SH-DC words (wdgs_tiled_forward_set_dc_source), read by project_count in place of the rows' first 6 bytes
+    const u32* dc_source = nullptr;  // nullable: the optimizer's compact SH-DC words (wdgs_tiled_forward_set_dc_source), read by project_count in place of the rows' first 6 bytes
     // Gaussians the per-Gaussian buffers above and the scanner hold (>= cfg.num_points: wdgs_tiled_forward_resize); 0 while they are not all there
     u32 points_capacity = 0;
     std::unique_ptr<wdgs_prefix_scanner> scanner;  // input = tile counts, output = per-Gaussian offsets
@@ -240,7 +191,7 @@ struct wdgs_tiled_backward {
     u32* acc_dirty() const { return acc ? reinterpret_cast<u32*>(acc.get() + (acc.count() - 4)) : nullptr; }
     DevMem<u32> gradients;      // GaussianGradient[N]
     bool gradient_output = true;  // the fused K17 + Adam step also writes the packed gradient (wdgs_tiled_backward_set_gradient_output; default on)
-    DevMem<float> loss_image;   // rgba32f
+    DevMem<float4> loss_image;  // rgba32f[W*H]
     u32 dssim_mode = 0;  // WDGS_DSSIM_*: the loss kernel an encode launches (wdgs_tiled_backward_set_dssim_mode)
     DevMem<u32> metric_counts;  // u32[N]
     u32* metric_counts_into = nullptr;  // nullable: computeMetricCounts adds into THIS array instead (wdgs_tiled_backward_set_metric_counts_target)
@@ -264,7 +215,7 @@ struct wdgs_optimizer {
     static u32 cs_pitch(u32 n) { return (std::max(n, 1u) + 15u) & ~15u; }  // planes start on 256-byte boundaries
     CsView cs() const { return CsView{dc.get(), cs_pitch(num_points)}; }
     bool dc_dirty = false;    // it is ahead of state.opt_pos / opt_scale / param_sh / state_sh
-    const void* guard = nullptr;  // device word: non-zero at execution time turns step / step_f32 into a no-op (wdgs_optimizer_set_guard)
+    const u32* guard = nullptr;  // device word: non-zero at execution time turns step / step_f32 into a no-op (wdgs_optimizer_set_guard)
     // Deferred SH writes (wdgs_optimizer_set_deferred_sh): the steps write the trained DC halves to dc_words (u32[N][2]) instead of the
     // 96-byte rows; sh_stale says the rows are behind until wdgs_optimizer_flush_sh.
     DevMem<u32> dc_words;
@@ -730,7 +681,7 @@ int wdgs_prefix_scanner_scan(wdgs_prefix_scanner* s) {
 int wdgs_prefix_scanner_scan_ptr(wdgs_prefix_scanner* s, const void* in, void* out, uint32_t count) {
     WDGS_REQUIRE(s && in && out, WDGS_E_INVALID, "null argument");
     WDGS_REQUIRE(count <= s->max_elements, WDGS_E_CAPACITY, "scan count %u exceeds max_elements %u", count, s->max_elements);
-    return scan_exclusive_u32(s->dev, &s->scratch, (const u32*)in, (u32*)out, count, nullptr);
+    return scan_exclusive_u32(s->dev, &s->scratch, static_cast<const u32*>(in), static_cast<u32*>(out), count, nullptr);
 }
 
 // ---------------------------------------------------------------- TiledForwardPass
@@ -952,15 +903,17 @@ static int forward_encode_rest(wdgs_tiled_forward* op, int skip_sort, bool colum
             d->range_tables[op->ranges.get()] = op;   // (a backward pass handed this table finds the pass's long-list work through it)
         }
     }
+    u32* const keys0 = static_cast<u32*>(wdgs_sorter_keys(op->sorter.get(), 0));   // emit writes the entries into ping-pong 0
+    u32* const values0 = static_cast<u32*>(wdgs_sorter_values(op->sorter.get(), 0));
     if (columns) {
         WDGS_TRY(launch_emit_scatter(d, n, op->splats, op->depths, op->scanner->input, op->scanner->output, op->block_counts, op->settings, op->tile_info,
-                                     op->column_counts, op->column_totals, wdgs_sorter_keys(op->sorter.get(), 0), wdgs_sorter_values(op->sorter.get(), 0), op->tile_info.max_tile_entries));
+                                     op->column_counts, op->column_totals, keys0, values0, op->tile_info.max_tile_entries));
         // one stable pass on the tile row (it builds the range table), then the per-tile depth sort: the order of a stable sort of the full key
         WDGS_TRY(sorter_sort_rows(op->sorter.get(), ti.num_tiles_x, ti.num_tiles_y, op->ranges, op->long_lists.hdr ? &op->long_lists : nullptr));
         op->ranges_valid = true;
     } else {
-        WDGS_TRY(launch_emit(d, n, op->splats, op->depths, op->scanner->input, op->scanner->output, op->block_counts, op->settings, op->tile_info,
-                             wdgs_sorter_keys(op->sorter.get(), 0), wdgs_sorter_values(op->sorter.get(), 0), op->tile_info.max_tile_entries));
+        WDGS_TRY(launch_emit(d, n, op->splats, op->depths, op->scanner->input, op->scanner->output, op->block_counts, op->settings, op->tile_info, keys0, values0,
+                             op->tile_info.max_tile_entries));
         if (skip_sort) sorter_set_final_out_index(op->sorter.get(), 0);  // the unsorted entries are in ping-pong 0
         if (!skip_sort) {
             // key = (tile_id + 1) << 16 | depth16: only 16 + bits(total_tiles) bits are ever set
@@ -988,8 +941,9 @@ int wdgs_tiled_forward_encode(wdgs_tiled_forward* op, const void* gaussians, con
     // its own in-workgroup prefix -- writing the per-Gaussian offsets table on the way.  Three launches instead of five.
     const bool columns = forward_uses_columns(op, skip_sort);
     op->projected = false;  // (K1 overwrites whatever projection the buffers held)
-    WDGS_TRY(launch_project_count(d, n, gaussians, sh, camera, op->settings, op->tile_info, op->splats, op->depths, op->scanner->input, op->stats + 4,
-                                  op->block_counts, columns ? op->column_counts : nullptr, op->dc_source, op->nf_stamp, op->stats + FRAME_WORD));
+    WDGS_TRY(launch_project_count(d, n, static_cast<const u32*>(gaussians), static_cast<const u32*>(sh), static_cast<const float*>(camera), op->settings, op->tile_info,
+                                  op->splats, op->depths, op->scanner->input, op->stats + 4, op->block_counts, columns ? op->column_counts : nullptr, op->dc_source,
+                                  op->nf_stamp, op->stats + FRAME_WORD));
     return forward_encode_rest(op, skip_sort, columns);
 }
 
@@ -999,9 +953,7 @@ int wdgs_tiled_forward_project_views(wdgs_tiled_forward* const* ops, const void*
     wdgs_tiled_forward* f0 = ops[0];
     WDGS_REQUIRE(f0, WDGS_E_INVALID, "wdgs_tiled_forward_project_views: null pass");
     const bool columns = forward_uses_columns(f0, 0);
-    void *splats[WDGS_MAX_BATCH_VIEWS], *depths[WDGS_MAX_BATCH_VIEWS], *counts[WDGS_MAX_BATCH_VIEWS], *shards[WDGS_MAX_BATCH_VIEWS], *blocks[WDGS_MAX_BATCH_VIEWS],
-        *cols[WDGS_MAX_BATCH_VIEWS], *stamps[WDGS_MAX_BATCH_VIEWS];
-    const void* frames[WDGS_MAX_BATCH_VIEWS];
+    ProjectViews pv{count};
     for (u32 v = 0; v < count; v++) {
         wdgs_tiled_forward* f = ops[v];
         WDGS_REQUIRE(f && cameras[v], WDGS_E_INVALID, "wdgs_tiled_forward_project_views: null pass or camera %u", v);
@@ -1010,11 +962,12 @@ int wdgs_tiled_forward_project_views(wdgs_tiled_forward* const* ops, const void*
                          std::memcmp(&f->settings, &f0->settings, sizeof(RenderSettings)) == 0 && f->tile_info.num_tiles_x == f0->tile_info.num_tiles_x &&
                          f->tile_info.num_tiles_y == f0->tile_info.num_tiles_y && f->dc_source == f0->dc_source,
                      WDGS_E_STATE, "wdgs_tiled_forward_project_views: pass %u differs from pass 0 (cloud size, SH degree, viewport, settings or dc source)", v);
-        splats[v] = f->splats; depths[v] = f->depths; counts[v] = f->scanner->input; shards[v] = f->stats + 4; blocks[v] = f->block_counts; cols[v] = f->column_counts;
-        stamps[v] = f->nf_stamp; frames[v] = f->stats + FRAME_WORD;
+        pv.camera[v] = static_cast<const float*>(cameras[v]); pv.splats[v] = f->splats; pv.depths[v] = f->depths; pv.tile_counts[v] = f->scanner->input;
+        pv.visible_shards[v] = f->stats + 4; pv.block_counts[v] = f->block_counts; pv.column_counts[v] = columns ? f->column_counts.get() : nullptr;
+        pv.nf_stamp[v] = f->nf_stamp; pv.nf_frame[v] = f->stats + FRAME_WORD;
     }
-    WDGS_TRY(launch_project_count_views(f0->dev, f0->cfg.num_points, count, gaussians, sh, cameras, f0->settings, f0->tile_info, splats, depths, counts, shards, blocks,
-                                        columns ? cols : nullptr, f0->dc_source, stamps, frames));
+    WDGS_TRY(launch_project_count_views(f0->dev, f0->cfg.num_points, static_cast<const u32*>(gaussians), static_cast<const u32*>(sh), f0->settings, f0->tile_info, pv,
+                                        f0->dc_source));
     for (u32 v = 0; v < count; v++) { ops[v]->projected = true; ops[v]->projected_columns = columns; }
     return WDGS_OK;
 }
@@ -1149,8 +1102,8 @@ int wdgs_tiled_rasterizer_encode(wdgs_tiled_rasterizer* op, uint32_t width, uint
         op->height = height;
     }
     const int fo = wdgs_sorter_final_out_index(f->sorter.get());
-    const void* keys = wdgs_sorter_keys(f->sorter.get(), fo);
-    const void* vals = wdgs_sorter_values(f->sorter.get(), fo);
+    const u32* keys = static_cast<const u32*>(wdgs_sorter_keys(f->sorter.get(), fo));
+    const u32* vals = static_cast<const u32*>(wdgs_sorter_values(f->sorter.get(), fo));
     if (f->ranges_valid) {
         op->ranges_used = f->ranges;  // built by the forward pass's sort
     } else {
@@ -1201,8 +1154,8 @@ int wdgs_tiled_rasterizer_encode_depth(wdgs_tiled_rasterizer* op, uint32_t kinds
         WDGS_TRY(op->depth[k].alloc((size_t)op->width * op->height, true, d->stream));
     }
     const int fo = wdgs_sorter_final_out_index(f->sorter.get());
-    WDGS_TRY(launch_depth_composite(d, f->settings, f->tile_info, f->splats, f->cfg.num_points, f->depths, op->ranges_used, wdgs_sorter_keys(f->sorter.get(), fo),
-                                    wdgs_sorter_values(f->sorter.get(), fo), f->stats, op->compat_caps ? 32u : 0u, (kinds & WDGS_DEPTH_WEIGHT_SUM) ? op->depth[2] : nullptr,
+    WDGS_TRY(launch_depth_composite(d, f->settings, f->tile_info, f->splats, f->cfg.num_points, f->depths, op->ranges_used, static_cast<const u32*>(wdgs_sorter_keys(f->sorter.get(), fo)),
+                                    static_cast<const u32*>(wdgs_sorter_values(f->sorter.get(), fo)), f->stats, op->compat_caps ? 32u : 0u, (kinds & WDGS_DEPTH_WEIGHT_SUM) ? op->depth[2] : nullptr,
                                     (kinds & WDGS_DEPTH_EXPECTED) ? op->depth[0] : nullptr, (kinds & WDGS_DEPTH_MEDIAN) ? op->depth[1] : nullptr, f->nf_stamp,
                                     f->stats + FRAME_WORD));
     op->depth_encoded = kinds;
@@ -1234,7 +1187,7 @@ int wdgs_tiled_rasterizer_blit(wdgs_tiled_rasterizer* op, void* target, uint32_t
     WDGS_REQUIRE(op && target, WDGS_E_INVALID, "wdgs_tiled_rasterizer_blit: null argument");
     WDGS_REQUIRE(op->encoded && op->rgba8, WDGS_E_STATE, "TiledRasterizer: no output texture to blit from. Call encode() first.");
     WDGS_REQUIRE(tw > 0 && th > 0, WDGS_E_INVALID, "wdgs_tiled_rasterizer_blit: empty target %ux%u", tw, th);
-    return launch_downsample(op->dev, op->rgba8, op->width, op->height, target, tw, th);
+    return launch_downsample(op->dev, op->rgba8, op->width, op->height, static_cast<u32*>(target), tw, th);
 }
 
 // ---------------------------------------------------------------- TiledBackwardPass
@@ -1244,7 +1197,7 @@ static int backward_alloc_images(wdgs_tiled_backward* op, u32 w, u32 h) {
     hipStream_t stream = op->dev->stream;
     (void)wdgs_sync_lanes(op->dev);
     op->loss_image.reset(); op->metric_err.reset(); op->metric_flags.reset();   // free all, then allocate all
-    WDGS_TRY(op->loss_image.alloc((size_t)px * 4, true, stream));
+    WDGS_TRY(op->loss_image.alloc(px, true, stream));
     WDGS_TRY(op->metric_err.alloc(px, true, stream));
     WDGS_TRY(op->metric_flags.alloc(px, true, stream));
     return WDGS_OK;
@@ -1310,10 +1263,10 @@ int wdgs_tiled_backward_set_gradient_output(wdgs_tiled_backward* op, int enabled
 }
 // K15, the loss image of the pass's loss (dssim_mode): the reference's heuristic (loss.hip) or the exact D-SSIM gradient (dssim.hip); both clear
 // the accumulators when acc is given and they are dirty
-static int backward_loss(wdgs_tiled_backward* op, const void* pred, const void* targ, void* acc, u32 acc_rows, const void* acc_dirty) {
+static int backward_loss(wdgs_tiled_backward* op, const void* pred, const void* targ, int* acc, u32 acc_rows, const u32* acc_dirty) {
     const u32 w = op->cfg.viewport_width, h = op->cfg.viewport_height;
-    if (op->dssim_mode == WDGS_DSSIM_GAUSSIAN) return launch_dssim_grad(op->dev, w, h, pred, targ, op->cfg.training, op->loss_image, acc, acc_rows, acc_dirty);
-    return launch_loss_grad(op->dev, w, h, pred, targ, op->cfg.training, op->loss_image, acc, acc_rows, acc_dirty);
+    const auto launch = op->dssim_mode == WDGS_DSSIM_GAUSSIAN ? launch_dssim_grad : launch_loss_grad;
+    return launch(op->dev, w, h, static_cast<const u32*>(pred), static_cast<const u32*>(targ), op->cfg.training, op->loss_image, acc, acc_rows, acc_dirty);
 }
 int wdgs_tiled_backward_compute_loss_only(wdgs_tiled_backward* op, const void* pred, const void* targ) {
     WDGS_REQUIRE(op && pred && targ, WDGS_E_INVALID, "wdgs_tiled_backward_compute_loss_only: null argument");
@@ -1329,8 +1282,9 @@ static int backward_encode_raster(wdgs_tiled_backward* op, const void* pred, con
     const LongWork* lw = nullptr;
     auto owner = d->range_tables.find(res->tile_offsets_buffer);
     if (owner != d->range_tables.end() && owner->second->ranges_valid && owner->second->long_lists.hdr) lw = &owner->second->long_lists;
-    return launch_backward_rasterize(d, op->settings, ceil_div(w, 16), ceil_div(h, 16), res->tile_offsets_buffer, res->tile_indices_buffer, res->splat_buffer,
-                                     res->alpha_texture, res->n_contrib_texture, op->loss_image, op->acc, op->acc_dirty(), lw);
+    return launch_backward_rasterize(d, op->settings, ceil_div(w, 16), ceil_div(h, 16), static_cast<const u32*>(res->tile_offsets_buffer),
+                                     static_cast<const u32*>(res->tile_indices_buffer), static_cast<const u32*>(res->splat_buffer), static_cast<const float*>(res->alpha_texture),
+                                     static_cast<const u32*>(res->n_contrib_texture), op->loss_image, op->acc, op->acc_dirty(), lw);
 }
 int wdgs_tiled_backward_encode(wdgs_tiled_backward* op, const void* pred, const void* targ, const wdgs_tiled_backward_resources* res,
                                const void* gaussians) {
@@ -1338,7 +1292,8 @@ int wdgs_tiled_backward_encode(wdgs_tiled_backward* op, const void* pred, const 
     WDGS_REQUIRE(res->splat_buffer && res->tile_offsets_buffer && res->tile_indices_buffer && res->camera_buffer && res->alpha_texture && res->n_contrib_texture,
                  WDGS_E_INVALID, "wdgs_tiled_backward_encode: incomplete resources");
     WDGS_TRY(backward_encode_raster(op, pred, targ, res));
-    return launch_geometry_backward(op->dev, op->cfg.num_points, res->camera_buffer, op->settings, gaussians, op->acc, op->gradients);
+    return launch_geometry_backward(op->dev, op->cfg.num_points, static_cast<const float*>(res->camera_buffer), op->settings, static_cast<const u32*>(gaussians), op->acc,
+                                    op->gradients);
 }
 // The two halves of wdgs_tiled_backward_encode, for a batched step: K15 + clear + K16 may run (and be recorded) on any lane at any
 // time; K17 of view k also adds the view's gradient to the step's fp32 block, which has to follow view k-1's K17.
@@ -1350,11 +1305,14 @@ int wdgs_tiled_backward_encode_raster(wdgs_tiled_backward* op, const void* pred,
 }
 int wdgs_tiled_backward_encode_geometry(wdgs_tiled_backward* op, const void* camera, const void* gaussians, const wdgs_view_accumulate* into) {
     WDGS_REQUIRE(op && camera && gaussians, WDGS_E_INVALID, "wdgs_tiled_backward_encode_geometry: null argument");
-    if (!into) return launch_geometry_backward(op->dev, op->cfg.num_points, camera, op->settings, gaussians, op->acc, op->gradients);
+    const float* const cam = static_cast<const float*>(camera);
+    const u32* const g = static_cast<const u32*>(gaussians);
+    if (!into) return launch_geometry_backward(op->dev, op->cfg.num_points, cam, op->settings, g, op->acc, op->gradients);
     WDGS_REQUIRE(into->sums && into->visible && into->tile_counts && into->guard && into->overflow_word, WDGS_E_INVALID,
                  "wdgs_tiled_backward_encode_geometry: incomplete accumulate target");
-    return launch_geometry_backward_accumulate(op->dev, op->cfg.num_points, camera, op->settings, gaussians, op->acc, op->acc_dirty(), op->gradients, into->sums, into->visible,
-                                               into->tile_counts, into->guard, into->overflow_word, into->first ? 1u : 2u);
+    return launch_geometry_backward_accumulate(op->dev, op->cfg.num_points, cam, op->settings, g, op->acc, op->acc_dirty(), op->gradients, static_cast<float*>(into->sums),
+                                               static_cast<u32*>(into->visible), static_cast<const u32*>(into->tile_counts), static_cast<u32*>(into->guard),
+                                               static_cast<const u32*>(into->overflow_word), into->first ? 1u : 2u);
 }
 // ---- view-batched K17 (include/webdgs.h)
 int wdgs_tiled_backward_encode_geometry_views(wdgs_tiled_backward* const* ops, const void* const* cameras, const void* const* tile_counts, const void* const* overflow_words,
@@ -1363,22 +1321,23 @@ int wdgs_tiled_backward_encode_geometry_views(wdgs_tiled_backward* const* ops, c
                  "wdgs_tiled_backward_encode_geometry_views: invalid argument");
     wdgs_tiled_backward* b0 = ops[0];
     WDGS_REQUIRE(b0, WDGS_E_INVALID, "wdgs_tiled_backward_encode_geometry_views: null pass");
-    void *accs[WDGS_MAX_BATCH_VIEWS], *dirty[WDGS_MAX_BATCH_VIEWS], *grads[WDGS_MAX_BATCH_VIEWS];
+    GeometryViews gv{count};
     for (u32 v = 0; v < count; v++) {
         wdgs_tiled_backward* b = ops[v];
         WDGS_REQUIRE(b && cameras[v] && tile_counts[v] && overflow_words[v], WDGS_E_INVALID, "wdgs_tiled_backward_encode_geometry_views: null argument for view %u", v);
         for (u32 u = 0; u < v; u++) WDGS_REQUIRE(ops[u] != b, WDGS_E_INVALID, "wdgs_tiled_backward_encode_geometry_views: pass %u is given twice (every view has accumulators of its own)", v);
         WDGS_REQUIRE(b->dev == b0->dev && b->cfg.num_points == b0->cfg.num_points && std::memcmp(&b->settings, &b0->settings, sizeof(RenderSettings)) == 0, WDGS_E_STATE,
                      "wdgs_tiled_backward_encode_geometry_views: pass %u differs from pass 0 (cloud size, viewport or settings)", v);
-        accs[v] = b->acc; dirty[v] = b->acc_dirty(); grads[v] = b->gradients;
+        gv.camera[v] = static_cast<const float*>(cameras[v]); gv.acc[v] = b->acc; gv.acc_dirty[v] = b->acc_dirty(); gv.tile_counts[v] = static_cast<const u32*>(tile_counts[v]);
+        gv.overflow[v] = static_cast<const u32*>(overflow_words[v]); gv.gradients[v] = write_gradients ? b->gradients.get() : nullptr;
     }
-    return launch_geometry_backward_views(b0->dev, b0->cfg.num_points, count, cameras, b0->settings, gaussians, accs, dirty, tile_counts, overflow_words,
-                                          write_gradients ? grads : nullptr, sums, visible, guard, continues ? 1u : 0u);
+    return launch_geometry_backward_views(b0->dev, b0->cfg.num_points, b0->settings, static_cast<const u32*>(gaussians), gv, static_cast<float*>(sums),
+                                          static_cast<u32*>(visible), static_cast<u32*>(guard), continues ? 1u : 0u);
 }
 int wdgs_tiled_backward_compute_metric_map(wdgs_tiled_backward* op, const void* pred, const void* targ, float threshold) {
     WDGS_REQUIRE(op && pred && targ, WDGS_E_INVALID, "wdgs_tiled_backward_compute_metric_map: null argument");
-    return launch_metric_map(op->dev, op->cfg.viewport_width, op->cfg.viewport_height, pred, targ, 1000000.0f, threshold, op->metric_err, op->metric_minmax,
-                             op->metric_minmax + 2, op->metric_flags);
+    return launch_metric_map(op->dev, op->cfg.viewport_width, op->cfg.viewport_height, static_cast<const u32*>(pred), static_cast<const u32*>(targ), 1000000.0f, threshold,
+                             op->metric_err, op->metric_minmax, op->metric_minmax + 2, op->metric_flags);
 }
 int wdgs_tiled_backward_compute_metric_counts(wdgs_tiled_backward* op, const wdgs_tiled_backward_resources* res, uint32_t num_instances, int clear) {
     WDGS_REQUIRE(op && res && res->splat_buffer && res->tile_offsets_buffer && res->tile_indices_buffer && res->n_contrib_texture, WDGS_E_INVALID,
@@ -1386,8 +1345,9 @@ int wdgs_tiled_backward_compute_metric_counts(wdgs_tiled_backward* op, const wdg
     const u32 n = op->cfg.num_points;
     u32* const counts = op->metric_counts_into ? op->metric_counts_into : op->metric_counts;
     if (clear) WDGS_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)std::max(n, 1u) * 4, op->dev->stream));
-    return launch_metric_count(op->dev, op->settings, ceil_div(op->cfg.viewport_width, 16), ceil_div(op->cfg.viewport_height, 16), res->tile_offsets_buffer,
-                               res->tile_indices_buffer, num_instances, res->splat_buffer, n, op->metric_flags, res->n_contrib_texture, counts, n);
+    return launch_metric_count(op->dev, op->settings, ceil_div(op->cfg.viewport_width, 16), ceil_div(op->cfg.viewport_height, 16),
+                               static_cast<const u32*>(res->tile_offsets_buffer), static_cast<const u32*>(res->tile_indices_buffer), num_instances,
+                               static_cast<const u32*>(res->splat_buffer), n, op->metric_flags, static_cast<const u32*>(res->n_contrib_texture), counts, n);
 }
 int wdgs_tiled_backward_normalize_metric_counts(wdgs_tiled_backward* op, uint32_t divisor) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "null op");
@@ -1423,7 +1383,7 @@ void* wdgs_tiled_backward_gradients(wdgs_tiled_backward* op) { return op ? op->g
 void* wdgs_tiled_backward_metric_counts(wdgs_tiled_backward* op) { return op ? op->metric_counts : nullptr; }
 int wdgs_tiled_backward_set_metric_counts_target(wdgs_tiled_backward* op, void* counts_dev) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "wdgs_tiled_backward_set_metric_counts_target: null op");
-    op->metric_counts_into = (u32*)counts_dev;
+    op->metric_counts_into = static_cast<u32*>(counts_dev);
     return WDGS_OK;
 }
 void* wdgs_tiled_backward_loss_image(wdgs_tiled_backward* op) { return op ? op->loss_image : nullptr; }
@@ -1433,7 +1393,7 @@ void* wdgs_tiled_backward_metric_minmax(wdgs_tiled_backward* op) { return op ? o
 
 int wdgs_downsample_rgba8(wdgs_device* d, const void* src, uint32_t sw, uint32_t sh, void* dst, uint32_t dw, uint32_t dh) {
     WDGS_REQUIRE(d && src && dst && sw && sh && dw && dh, WDGS_E_INVALID, "wdgs_downsample_rgba8: invalid argument");
-    return launch_downsample(d, src, sw, sh, dst, dw, dh);
+    return launch_downsample(d, static_cast<const u32*>(src), sw, sh, static_cast<u32*>(dst), dw, dh);
 }
 
 // ---------------------------------------------------------------- Optimizer
@@ -1467,7 +1427,7 @@ int wdgs_optimizer_create(wdgs_device* d, uint32_t n, const wdgs_adam_hyperparam
         WDGS_REQUIRE(gaussians && sh, WDGS_E_INVALID, "wdgs_optimizer_create: point cloud required when no initial state is given");
         for (int i = 0; i < 6; i++) WDGS_TRY(op->owned[i].alloc(sz[i], true, d->stream));
         op->state = wdgs_optimizer_state{op->owned[0].get(), op->owned[1].get(), op->owned[2].get(), op->owned[3].get(), op->owned[4].get(), op->owned[5].get()};
-        WDGS_TRY(launch_unpack(d, n, gaussians, sh, op->state));
+        WDGS_TRY(launch_unpack(d, n, static_cast<const u32*>(gaussians), static_cast<const u32*>(sh), op->state));
     }
     WDGS_TRY(op->dc.alloc(CS_PLANES * (size_t)wdgs_optimizer::cs_pitch(n), true, d->stream));
     WDGS_TRY(launch_cs_load(d, n, op->state, op->cs()));
@@ -1484,7 +1444,7 @@ int wdgs_optimizer_destroy(wdgs_optimizer* op) {
 }
 int wdgs_optimizer_init_from_point_cloud(wdgs_optimizer* op, const void* gaussians, const void* sh) {
     WDGS_REQUIRE(op && gaussians && sh, WDGS_E_INVALID, "wdgs_optimizer_init_from_point_cloud: null argument");
-    WDGS_TRY(launch_unpack(op->dev, op->num_points, gaussians, sh, op->state));
+    WDGS_TRY(launch_unpack(op->dev, op->num_points, static_cast<const u32*>(gaussians), static_cast<const u32*>(sh), op->state));
     op->dc_dirty = false;
     return launch_cs_load(op->dev, op->num_points, op->state, op->cs());
 }
@@ -1493,7 +1453,8 @@ int wdgs_optimizer_step(wdgs_optimizer* op, void* gaussians, void* sh, const voi
     op->iteration++;  // optimizer.ts:301
     op->dc_dirty = true;
     if (op->deferred_sh) op->sh_stale = true;
-    return launch_adam_repack(op->dev, op->num_points, op->params, tile_counts, gradients, op->state, op->cs(), gaussians, sh, op->guard, op->deferred_sh ? op->dc_words : nullptr);
+    return launch_adam_repack(op->dev, op->num_points, op->params, static_cast<const u32*>(tile_counts), static_cast<const u32*>(gradients), op->state, op->cs(),
+                              static_cast<u32*>(gaussians), static_cast<u32*>(sh), op->guard, op->deferred_sh ? op->dc_words : nullptr);
 }
 // K17 + K18 + K19 in one pass over the Gaussians (the single-view step): `bwd` must have run wdgs_tiled_backward_encode_raster for this view.
 int wdgs_optimizer_step_with_geometry(wdgs_optimizer* op, wdgs_tiled_backward* bwd, const void* camera, void* gaussians, void* sh, const void* tile_counts) {
@@ -1503,17 +1464,17 @@ int wdgs_optimizer_step_with_geometry(wdgs_optimizer* op, wdgs_tiled_backward* b
     op->iteration++;  // optimizer.ts:301
     op->dc_dirty = true;
     if (op->deferred_sh) op->sh_stale = true;
-    return launch_geometry_backward_adam(op->dev, op->num_points, camera, bwd->settings, gaussians, bwd->acc, bwd->acc_dirty(), bwd->gradient_output ? bwd->gradients : nullptr,
-                                         op->params, tile_counts, op->state,
-                                         op->cs(), sh, op->guard, op->deferred_sh ? op->dc_words : nullptr);
+    return launch_geometry_backward_adam(op->dev, op->num_points, static_cast<const float*>(camera), bwd->settings, static_cast<u32*>(gaussians), bwd->acc, bwd->acc_dirty(),
+                                         bwd->gradient_output ? bwd->gradients : nullptr, op->params, static_cast<const u32*>(tile_counts), op->state, op->cs(),
+                                         static_cast<u32*>(sh), op->guard, op->deferred_sh ? op->dc_words : nullptr);
 }
 int wdgs_optimizer_step_f32(wdgs_optimizer* op, void* gaussians, void* sh, const void* grad_f32, const void* visible) {
     WDGS_REQUIRE(op && gaussians && sh && grad_f32 && visible, WDGS_E_INVALID, "wdgs_optimizer_step_f32: null argument");
     op->iteration++;
     op->dc_dirty = true;
     if (op->deferred_sh) op->sh_stale = true;
-    return launch_adam_repack_f32(op->dev, 0, op->num_points, op->params, visible, grad_f32, op->state, op->cs(), gaussians, sh, op->guard, op->dev->host_guard, nullptr,
-                                  op->deferred_sh ? op->dc_words : nullptr);
+    return launch_adam_repack_f32(op->dev, 0, op->num_points, op->params, static_cast<const u32*>(visible), static_cast<const float*>(grad_f32), op->state, op->cs(),
+                                  static_cast<u32*>(gaussians), static_cast<u32*>(sh), op->guard, op->dev->host_guard, nullptr, op->deferred_sh ? op->dc_words : nullptr);
 }
 int wdgs_optimizer_step_f32_range(wdgs_optimizer* op, void* gaussians, void* sh, const void* grad_f32, const void* visible, uint32_t first, uint32_t count,
                                   void* rows_out) {
@@ -1523,12 +1484,13 @@ int wdgs_optimizer_step_f32_range(wdgs_optimizer* op, void* gaussians, void* sh,
     op->iteration++;
     op->dc_dirty = true;
     if (op->deferred_sh) op->sh_stale = true;
-    return launch_adam_repack_f32(op->dev, first, count, op->params, visible, grad_f32, op->state, op->cs(), gaussians, sh, op->guard, op->dev->host_guard, rows_out,
+    return launch_adam_repack_f32(op->dev, first, count, op->params, static_cast<const u32*>(visible), static_cast<const float*>(grad_f32), op->state, op->cs(),
+                                  static_cast<u32*>(gaussians), static_cast<u32*>(sh), op->guard, op->dev->host_guard, static_cast<u32*>(rows_out),
                                   op->deferred_sh ? op->dc_words : nullptr);
 }
 int wdgs_optimizer_set_guard(wdgs_optimizer* op, const void* flag) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "null op");
-    op->guard = flag;
+    op->guard = static_cast<const u32*>(flag);
     return WDGS_OK;
 }
 int wdgs_optimizer_state_changed(wdgs_optimizer* op) {
@@ -1539,26 +1501,28 @@ int wdgs_optimizer_state_changed(wdgs_optimizer* op) {
 int wdgs_apply_repacked_rows(wdgs_device* d, uint32_t n, const void* rows, uint32_t skip_first, uint32_t skip_count, const void* guard, void* gaussians,
                              void* sh) {
     WDGS_REQUIRE(d && rows && gaussians && sh, WDGS_E_INVALID, "wdgs_apply_repacked_rows: null argument");
-    return launch_apply_rows(d, n, rows, skip_first, skip_count, guard, d->host_guard, gaussians, sh, nullptr);
+    return launch_apply_rows(d, n, static_cast<const u32*>(rows), skip_first, skip_count, static_cast<const u32*>(guard), d->host_guard, static_cast<u32*>(gaussians),
+                             static_cast<u32*>(sh), nullptr);
 }
 // The same for a replica whose optimizer defers its SH writes: the gathered DC halves go to its compact words as well.
 int wdgs_optimizer_apply_repacked_rows(wdgs_optimizer* op, const void* rows, uint32_t skip_first, uint32_t skip_count, const void* guard, void* gaussians, void* sh) {
     WDGS_REQUIRE(op && rows && gaussians && sh, WDGS_E_INVALID, "wdgs_optimizer_apply_repacked_rows: null argument");
     if (op->deferred_sh) op->sh_stale = true;
-    return launch_apply_rows(op->dev, op->num_points, rows, skip_first, skip_count, guard, op->dev->host_guard, gaussians, sh, op->deferred_sh ? op->dc_words : nullptr);
+    return launch_apply_rows(op->dev, op->num_points, static_cast<const u32*>(rows), skip_first, skip_count, static_cast<const u32*>(guard), op->dev->host_guard,
+                             static_cast<u32*>(gaussians), static_cast<u32*>(sh), op->deferred_sh ? op->dc_words : nullptr);
 }
 // ---- deferred SH writes (no reference counterpart)
 int wdgs_optimizer_set_deferred_sh(wdgs_optimizer* op, void* sh, int enabled) {
     WDGS_REQUIRE(op && sh, WDGS_E_INVALID, "wdgs_optimizer_set_deferred_sh: null argument");
     WDGS_REQUIRE(!op->dev->capturing, WDGS_E_STATE, "wdgs_optimizer_set_deferred_sh while recording a command buffer");
     if (!enabled) {
-        if (op->deferred_sh && op->sh_stale) WDGS_TRY(launch_dc_words_flush(op->dev, op->num_points, op->dc_words, sh));
+        if (op->deferred_sh && op->sh_stale) WDGS_TRY(launch_dc_words_flush(op->dev, op->num_points, op->dc_words, static_cast<u32*>(sh)));
         op->deferred_sh = false;
         op->sh_stale = false;
         return WDGS_OK;
     }
     if (!op->dc_words) WDGS_TRY(op->dc_words.alloc((size_t)2 * std::max(op->num_points, 1u), true, op->dev->stream));
-    if (!op->deferred_sh || !op->sh_stale) WDGS_TRY(launch_dc_words_load(op->dev, op->num_points, sh, op->dc_words));  // the rows are current: take their DC halves
+    if (!op->deferred_sh || !op->sh_stale) WDGS_TRY(launch_dc_words_load(op->dev, op->num_points, static_cast<const u32*>(sh), op->dc_words));  // the rows are current: take their DC halves
     op->deferred_sh = true;
     return WDGS_OK;
 }
@@ -1567,26 +1531,26 @@ int wdgs_optimizer_flush_sh(wdgs_optimizer* op, void* sh) {
     WDGS_REQUIRE(op && sh, WDGS_E_INVALID, "wdgs_optimizer_flush_sh: null argument");
     if (!op->deferred_sh || !op->sh_stale) return WDGS_OK;
     WDGS_REQUIRE(!op->dev->capturing, WDGS_E_STATE, "wdgs_optimizer_flush_sh while recording a command buffer");
-    WDGS_TRY(launch_dc_words_flush(op->dev, op->num_points, op->dc_words, sh));  // stream-ordered: later kernels and copies on this device see current rows
+    WDGS_TRY(launch_dc_words_flush(op->dev, op->num_points, op->dc_words, static_cast<u32*>(sh)));  // stream-ordered: later kernels and copies on this device see current rows
     op->sh_stale = false;
     return WDGS_OK;
 }
 int wdgs_tiled_forward_set_dc_source(wdgs_tiled_forward* op, const void* dc_words) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "wdgs_tiled_forward_set_dc_source: null op");
-    op->dc_source = dc_words;
+    op->dc_source = static_cast<const u32*>(dc_words);
     return WDGS_OK;
 }
 int wdgs_guard_accumulate(wdgs_device* d, void* flag, const void* src, int overwrite) {
     WDGS_REQUIRE(d && flag && src, WDGS_E_INVALID, "wdgs_guard_accumulate: null argument");
-    return launch_guard_accumulate(d, flag, src, overwrite ? 1u : 0u);
+    return launch_guard_accumulate(d, static_cast<u32*>(flag), static_cast<const u32*>(src), overwrite ? 1u : 0u);
 }
 int wdgs_accumulate_gradients(wdgs_device* d, uint32_t n, const void* gradients, const void* tile_counts, void* acc, void* visible) {
     WDGS_REQUIRE(d && gradients && tile_counts && acc && visible, WDGS_E_INVALID, "wdgs_accumulate_gradients: null argument");
-    return launch_accumulate_gradients(d, n, gradients, tile_counts, acc, visible);
+    return launch_accumulate_gradients(d, n, static_cast<const u32*>(gradients), static_cast<const u32*>(tile_counts), static_cast<float*>(acc), static_cast<u32*>(visible));
 }
 int wdgs_store_gradients(wdgs_device* d, uint32_t n, const void* gradients, const void* tile_counts, void* acc, void* visible) {
     WDGS_REQUIRE(d && gradients && tile_counts && acc && visible, WDGS_E_INVALID, "wdgs_store_gradients: null argument");
-    return launch_store_gradients(d, n, gradients, tile_counts, acc, visible);
+    return launch_store_gradients(d, n, static_cast<const u32*>(gradients), static_cast<const u32*>(tile_counts), static_cast<float*>(acc), static_cast<u32*>(visible));
 }
 uint32_t wdgs_optimizer_get_iteration(const wdgs_optimizer* op) { return op ? op->iteration : 0; }
 int wdgs_optimizer_advance_iteration(wdgs_optimizer* op, uint32_t count) {

@@ -4,7 +4,7 @@
 // Replaces main_geometry_backward (src/shaders/tiled-backward.wgsl:41-298): N-wide, HBM-bound (24 B Gaussian + 48 B
 // accumulators in, 32 B packed fp16 gradient out), runs on culled Gaussians too.  The reference's quirks are
 // kept: W = view3x3 here vs its transpose in the forward (Q10), +0.5*viewport for both NDC axes (Q11), fp16 output (Q13).
-#include "common.h"
+#include "launch.h"
 #include "wgslm.h"
 #include "adam.h"
 
@@ -246,15 +246,6 @@ __global__ __launch_bounds__(256, 6) void geometry_backward_kernel(u32 n, const 
 // stored, later ones added: exactly the sequence of the per-view accumulate kernels -- into a register copy of the step's fp32 block,
 // which is written once.  The Gaussian is read once instead of once per view, the 60-byte fp32 row is written once instead of being
 // read-modify-written per view, and the per-view kernels' cross-lane ordering (view k's sums behind view k-1's) disappears.
-struct GeometryViews {
-    u32 count;
-    const float* camera[WDGS_MAX_BATCH_VIEWS];
-    int* acc[WDGS_MAX_BATCH_VIEWS];
-    u32* acc_dirty[WDGS_MAX_BATCH_VIEWS];
-    const u32* tile_counts[WDGS_MAX_BATCH_VIEWS];
-    const u32* overflow[WDGS_MAX_BATCH_VIEWS];
-    u32* gradients[WDGS_MAX_BATCH_VIEWS];   // nullable per view: the packed per-view GaussianGradient, for readers of getGradientsBuffer()
-};
 __global__ __launch_bounds__(256, 3) void geometry_backward_views_kernel(u32 n, RenderSettings settings, const u32* __restrict__ gaussians, GeometryViews gv,
                                                                         float* __restrict__ sums, u32* __restrict__ visible, u32* __restrict__ guard,
                                                                         u32 continues /*0: these are the step's first views; 1: the block already holds earlier views*/) {
@@ -316,48 +307,39 @@ __global__ __launch_bounds__(256, 3) void geometry_backward_views_kernel(u32 n, 
 
 }  // namespace
 
-int launch_geometry_backward_adam(wdgs_device* dev, u32 n, const void* camera, const RenderSettings& st, void* gaussians, void* acc, void* acc_dirty, void* gradients,
-                                  const wdgs_adam_hyperparameters& h, const void* tile_counts, const wdgs_optimizer_state& state, const CsView& cs, void* sh,
-                                  const void* guard, void* dc_words) {
+int launch_geometry_backward_adam(wdgs_device* dev, u32 n, const float* camera, const RenderSettings& st, u32* gaussians, int* acc, u32* acc_dirty, u32* gradients,
+                                  const wdgs_adam_hyperparameters& h, const u32* tile_counts, const wdgs_optimizer_state& state, const CsView& cs, u32* sh,
+                                  const u32* guard, u32* dc_words) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "geometry_backward_adam", geometry_backward_kernel<2>, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const float*)camera, st,
-                (const u32*)gaussians, (int*)acc, (u32*)acc_dirty, (u32*)gradients, ViewAccumulate{},
-                (ViewAdam{h, (const u32*)tile_counts, (float4*)state.opt_rot, (float*)state.opt_opacity, cs, (u32*)gaussians, (u32*)sh, (const u32*)guard,
-                          (u32*)dc_words}));
+    WDGS_LAUNCH(dev, "geometry_backward_adam", geometry_backward_kernel<2>, dim3(ceil_div(n, 256)), dim3(256), 0, n, camera, st, gaussians, acc, acc_dirty, gradients,
+                ViewAccumulate{},
+                (ViewAdam{h, tile_counts, static_cast<float4*>(state.opt_rot), static_cast<float*>(state.opt_opacity), cs, gaussians, sh, guard, dc_words}));
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_geometry_backward(wdgs_device* dev, u32 n, const void* camera, const RenderSettings& st, const void* gaussians, void* acc, void* gradients) {
+int launch_geometry_backward(wdgs_device* dev, u32 n, const float* camera, const RenderSettings& st, const u32* gaussians, int* acc, u32* gradients) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "geometry_backward", geometry_backward_kernel<0>, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const float*)camera, st, (const u32*)gaussians,
-                (int*)acc, (u32*)nullptr, (u32*)gradients, ViewAccumulate{}, ViewAdam{});
+    WDGS_LAUNCH(dev, "geometry_backward", geometry_backward_kernel<0>, dim3(ceil_div(n, 256)), dim3(256), 0, n, camera, st, gaussians, acc, nullptr, gradients,
+                ViewAccumulate{}, ViewAdam{});
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_geometry_backward_accumulate(wdgs_device* dev, u32 n, const void* camera, const RenderSettings& st, const void* gaussians, void* acc, void* acc_dirty,
-                                        void* gradients, void* sums, void* visible, const void* tile_counts, void* guard, const void* overflow, u32 mode) {
+int launch_geometry_backward_accumulate(wdgs_device* dev, u32 n, const float* camera, const RenderSettings& st, const u32* gaussians, int* acc, u32* acc_dirty,
+                                        u32* gradients, float* sums, u32* visible, const u32* tile_counts, u32* guard, const u32* overflow, u32 mode) {
     // (n == 0 still runs one workgroup: the guard word must be written)
-    WDGS_LAUNCH(dev, "geometry_backward", geometry_backward_kernel<1>, dim3(std::max(ceil_div(n, 256), 1u)), dim3(256), 0, n, (const float*)camera, st,
-                (const u32*)gaussians, (int*)acc, (u32*)acc_dirty, (u32*)gradients,
-                (ViewAccumulate{(float*)sums, (u32*)visible, (const u32*)tile_counts, (u32*)guard, (const u32*)overflow, mode}), ViewAdam{});
+    WDGS_LAUNCH(dev, "geometry_backward", geometry_backward_kernel<1>, dim3(std::max(ceil_div(n, 256), 1u)), dim3(256), 0, n, camera, st, gaussians, acc, acc_dirty,
+                gradients, (ViewAccumulate{sums, visible, tile_counts, guard, overflow, mode}), ViewAdam{});
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_geometry_backward_views(wdgs_device* dev, u32 n, u32 count, const void* const* cameras, const RenderSettings& st, const void* gaussians, void* const* accs,
-                                   void* const* acc_dirtys, const void* const* tile_counts, const void* const* overflows, void* const* gradients, void* sums, void* visible,
-                                   void* guard, u32 continues) {
-    GeometryViews gv{};
-    gv.count = count;
-    for (u32 v = 0; v < count; v++) {
-        gv.camera[v] = (const float*)cameras[v]; gv.acc[v] = (int*)accs[v]; gv.acc_dirty[v] = (u32*)acc_dirtys[v]; gv.tile_counts[v] = (const u32*)tile_counts[v];
-        gv.overflow[v] = (const u32*)overflows[v]; gv.gradients[v] = gradients ? (u32*)gradients[v] : nullptr;
-    }
+int launch_geometry_backward_views(wdgs_device* dev, u32 n, const RenderSettings& st, const u32* gaussians, const GeometryViews& gv, float* sums, u32* visible,
+                                   u32* guard, u32 continues) {
     // (n == 0 still runs one workgroup: the guard word must be written)
-    WDGS_LAUNCH(dev, "geometry_backward_views", geometry_backward_views_kernel, dim3(std::max(ceil_div(n, 256), 1u)), dim3(256), 0, n, st, (const u32*)gaussians, gv,
-                (float*)sums, (u32*)visible, (u32*)guard, continues);
+    WDGS_LAUNCH(dev, "geometry_backward_views", geometry_backward_views_kernel, dim3(std::max(ceil_div(n, 256), 1u)), dim3(256), 0, n, st, gaussians, gv, sums, visible,
+                guard, continues);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }

@@ -24,7 +24,7 @@
 // around them, at 0.96-0.99 of the rate this chip sustains for a pure FMA stream; DESIGN.md section 4 has the counters.
 #include <algorithm>
 
-#include "common.h"
+#include "launch.h"
 #include "dmath.h"
 #include "blockcull.h"
 #include "longlist.h"
@@ -412,15 +412,15 @@ __global__ __launch_bounds__(256) void acc_clear_if_dirty_kernel(int4* __restric
 
 }  // namespace
 
-int launch_acc_clear_if_dirty(wdgs_device* dev, void* acc, u32 n, void* acc_dirty) {
+int launch_acc_clear_if_dirty(wdgs_device* dev, int* acc, u32 n, const u32* acc_dirty) {
     const u32 quads = std::max(n, 1u) * (ACC_STRIDE / 4u);
-    WDGS_LAUNCH(dev, "acc_clear", acc_clear_if_dirty_kernel, dim3(std::min(ceil_div(quads, 256u * 8u), 2048u)), dim3(256), 0, (int4*)acc, quads, (const u32*)acc_dirty);
+    WDGS_LAUNCH(dev, "acc_clear", acc_clear_if_dirty_kernel, dim3(std::min(ceil_div(quads, 256u * 8u), 2048u)), dim3(256), 0, reinterpret_cast<int4*>(acc), quads, acc_dirty);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_backward_rasterize(wdgs_device* dev, const RenderSettings& st, u32 num_tiles_x, u32 num_tiles_y, const void* ranges, const void* instances,
-                              const void* splats, const void* final_t, const void* n_contrib, const void* loss_grad, void* acc, void* acc_dirty, const LongWork* long_work) {
+int launch_backward_rasterize(wdgs_device* dev, const RenderSettings& st, u32 num_tiles_x, u32 num_tiles_y, const u32* ranges, const u32* instances, const u32* splats,
+                              const float* final_t, const u32* n_contrib, const float4* loss_grad, int* acc, u32* acc_dirty, const LongWork* long_work) {
     const u32 tiles = num_tiles_x * num_tiles_y;
     if (tiles == 0) return WDGS_OK;
     // one 8x8 block (one wave) per workgroup: nothing is shared inside a tile's workgroup but cache lines, and single-wave workgroups are
@@ -428,8 +428,7 @@ int launch_backward_rasterize(wdgs_device* dev, const RenderSettings& st, u32 nu
     const u32 slots = ceil_div(tiles, 8u) * 8u * 4u;   // 4 blocks per tile, tiles rounded up to a multiple of the 8 XCDs
     const bool prio = slots <= 8192u;  // (a launch that does not fit the chip's 8 192 wave slots gains nothing: c3 +-0)
     const LongWork lw = long_work ? *long_work : LongWork{};
-#define BWR_ARGS st, num_tiles_x, tiles, (const u32*)ranges, (const u32*)instances, (const u32*)splats, (const float*)final_t, (const u32*)n_contrib, (const float4*)loss_grad, \
-                 (int*)acc, (u32*)acc_dirty, lw
+#define BWR_ARGS st, num_tiles_x, tiles, ranges, instances, splats, final_t, n_contrib, loss_grad, acc, acc_dirty, lw
     if (lw.hdr && lw.threshold) {   // (long tile lists, longlist.h)
         if (prio) WDGS_LAUNCH(dev, "backward_rasterize", (backward_rasterize_kernel<true, true>), dim3(slots), dim3(64), 0, BWR_ARGS);
         else WDGS_LAUNCH(dev, "backward_rasterize", (backward_rasterize_kernel<false, true>), dim3(slots), dim3(64), 0, BWR_ARGS);

@@ -154,24 +154,6 @@ using wdgs::DevMem;
 // true between wdgs_device_create and wdgs_device_destroy (api.hip): destroy functions check it before touching op->dev
 bool wdgs_device_alive(const wdgs_device* d);
 
-// ---- primitives implemented in scan.hip / sort.hip, used by the ops
-struct ScanScratch {
-    DevMem<u32> block_sums;   // one sum per block of the scan, and the grand total behind them
-    u32 capacity_blocks() const { return block_sums ? (u32)block_sums.count() - 1u : 0u; }
-};
-int scan_scratch_create(ScanScratch* s, u32 max_elements);
-// Exclusive u32 scan of `count` (host-known) elements.  If total_out != nullptr, writes the grand total there.
-int scan_exclusive_u32(wdgs_device* dev, ScanScratch* s, const u32* in, u32* out, u32 count, u32* total_out);
-// Same, with the forward pass's stats epilogue folded into the single-block middle kernel (count must be > 0 for it to run).
-// frame (nullable): the forward pass's frame number, advanced by the scan kernel -- project.hip stamps the tiles of non-finite Splats with the number
-// the frame is ABOUT to get, so a stamp never has to be cleared (raster.hip compares)
-// long_hdr (nullable): the header of the pass's long-list work (longlist.h), zeroed for the frame by the same kernel
-struct ScanStatsEpilogue { u32* stats; u32* visible_shards; u32* host_mirror; u32 capacity; u32* frame = nullptr; u32* long_hdr = nullptr; };
-int scan_exclusive_u32_stats(wdgs_device* dev, ScanScratch* s, const u32* in, u32* out, u32 count, u32* total_out, const ScanStatsEpilogue& ep);
-
-int scan_block_sums_inplace(wdgs_device* dev, u32* block_sums, u32 num_blocks, const ScanStatsEpilogue& ep);
-// scan_block_sums_inplace + the row scans of the per-workgroup tile-column counts (column_counts[columns][num_blocks] -> offsets in place, totals)
-int forward_scan(wdgs_device* dev, u32* block_sums, u32 num_blocks, u32* column_counts, u32* column_totals, u32 columns, const ScanStatsEpilogue& ep);
-
+// (kernel arguments; the host functions that take them are declared in launch.h)
 struct RenderSettings { float gaussian_scaling, sh_deg, viewport_x, viewport_y, point_size_px, gaussian_mode, max_splat_radius_px; };
 struct TileInfo { u32 num_tiles_x, num_tiles_y, total_tiles, max_tile_entries; };

@@ -10,7 +10,7 @@
 #include <cstring>
 #include <memory>
 
-#include "common.h"
+#include "launch.h"
 #include "wgslm.h"
 #include "blockcull.h"
 
@@ -371,39 +371,39 @@ __global__ __launch_bounds__(256) void scatter_kernel(ScatterArgs a) {
 
 }  // namespace
 
-int launch_downsample(wdgs_device* dev, const void* src, u32 sw, u32 sh, void* dst, u32 dw, u32 dh) {
-    WDGS_LAUNCH(dev, "downsample_rgba8", downsample_kernel, dim3(ceil_div(dw, 16), ceil_div(dh, 16)), dim3(256), 0, (const u32*)src, sw, sh, (u32*)dst, dw, dh);
+int launch_downsample(wdgs_device* dev, const u32* src, u32 sw, u32 sh, u32* dst, u32 dw, u32 dh) {
+    WDGS_LAUNCH(dev, "downsample_rgba8", downsample_kernel, dim3(ceil_div(dw, 16), ceil_div(dh, 16)), dim3(256), 0, src, sw, sh, dst, dw, dh);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_metric_map(wdgs_device* dev, u32 W, u32 H, const void* pred, const void* targ, float err_scale, float threshold, void* err, void* minmax,
-                      void* /*scratch*/, void* flags) {
+int launch_metric_map(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, float err_scale, float threshold, u32* err, u32* minmax, u32* /*scratch*/,
+                      u32* flags) {
     const u32 npix = W * H;
     if (npix == 0) return WDGS_OK;
     const u32 grid = std::min<u32>(ceil_div(npix, 256), (u32)dev->num_cus * 8);
     // one workgroup per CU for the pass that ends in two atomics on the same pair of words: 2000 of them queue up behind each other
     // at the L2 (40 of the kernel's 51 us at 960x540); min / max are order-free, so the grid does not change the result
     const u32 grid_minmax = std::min<u32>(grid, (u32)dev->num_cus);
-    WDGS_LAUNCH(dev, "metric_init", metric_init_kernel, dim3(1), dim3(64), 0, (u32*)minmax);
-    WDGS_LAUNCH(dev, "metric_error", metric_error_kernel, dim3(grid_minmax), dim3(256), 0, npix, (const u32*)pred, (const u32*)targ, err_scale, (u32*)err, (u32*)minmax);
-    WDGS_LAUNCH(dev, "metric_threshold", metric_threshold_kernel, dim3(grid), dim3(256), 0, npix, (const u32*)err, (const u32*)minmax, threshold, (u32*)flags);
+    WDGS_LAUNCH(dev, "metric_init", metric_init_kernel, dim3(1), dim3(64), 0, minmax);
+    WDGS_LAUNCH(dev, "metric_error", metric_error_kernel, dim3(grid_minmax), dim3(256), 0, npix, pred, targ, err_scale, err, minmax);
+    WDGS_LAUNCH(dev, "metric_threshold", metric_threshold_kernel, dim3(grid), dim3(256), 0, npix, err, minmax, threshold, flags);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_metric_count(wdgs_device* dev, const RenderSettings& st, u32 ntx, u32 nty, const void* ranges, const void* instances, u32 num_instances,
-                        const void* splats, u32 num_splats, const void* flags, const void* n_contrib, void* counts, u32 num_counts) {
+int launch_metric_count(wdgs_device* dev, const RenderSettings& st, u32 ntx, u32 nty, const u32* ranges, const u32* instances, u32 num_instances, const u32* splats,
+                        u32 num_splats, const u32* flags, const u32* n_contrib, u32* counts, u32 num_counts) {
     if (ntx * nty == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "metric_count", metric_count_kernel, dim3(ntx * nty), dim3(256), 0, st, ntx, (const u32*)ranges, (const u32*)instances, num_instances,
-                (const u32*)splats, num_splats, (const u32*)flags, (const u32*)n_contrib, (u32*)counts, num_counts);
+    WDGS_LAUNCH(dev, "metric_count", metric_count_kernel, dim3(ntx * nty), dim3(256), 0, st, ntx, ranges, instances, num_instances, splats, num_splats, flags,
+                n_contrib, counts, num_counts);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_metric_normalize(wdgs_device* dev, u32 n, u32 divisor, void* counts) {
+int launch_metric_normalize(wdgs_device* dev, u32 n, u32 divisor, u32* counts) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "metric_normalize", metric_normalize_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, divisor, (u32*)counts);
+    WDGS_LAUNCH(dev, "metric_normalize", metric_normalize_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, divisor, counts);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }

@@ -16,7 +16,7 @@
 // rasterizer's: 1 - A is its alpha texture bit for bit.  On top of it one FMA (S = fma(z, w, S)) and the median's two compares and a select; the
 // three colour FMAs and the n_contrib select of rasterize are gone.  Outputs: A, S / A (one correctly rounded division; 0 where A is not > 0), and
 // the z of the first record at which A reaches 0.5 (0 if none does).  Only the images asked for (non-null) are stored.
-#include "common.h"
+#include "launch.h"
 #include "dmath.h"
 
 namespace {
@@ -196,14 +196,13 @@ __global__ __launch_bounds__(256) void depth_to_rgba8_kernel(const float* __rest
 
 }  // namespace
 
-int launch_depth_composite(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const void* splats, u32 num_splats, const void* depths, const void* ranges,
-                           const void* sorted_keys, const void* sorted_vals, const void* count_ptr, u32 max_batches, void* out_weight, void* out_expected,
-                           void* out_median, const void* nf_stamp, const void* nf_frame) {
+int launch_depth_composite(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const u32* splats, u32 num_splats, const u32* depths, const u32* ranges,
+                           const u32* sorted_keys, const u32* sorted_vals, const u32* count_ptr, u32 max_batches, float* out_weight, float* out_expected,
+                           float* out_median, const u32* nf_stamp, const u32* nf_frame) {
     if (ti.total_tiles == 0) return WDGS_OK;
     const u32 max_entries = max_batches * 256u;  // compat cap, as launch_rasterize
-    WDGS_LAUNCH(dev, "depth_composite", depth_composite_kernel, dim3(ti.total_tiles), dim3(256), 0, st, ti, (const u32*)splats, num_splats, (const u32*)depths,
-                (const u32*)ranges, (const u32*)sorted_keys, (const u32*)sorted_vals, (const u32*)count_ptr, max_entries, (float*)out_weight, (float*)out_expected,
-                (float*)out_median, (const u32*)nf_stamp, (const u32*)nf_frame);
+    WDGS_LAUNCH(dev, "depth_composite", depth_composite_kernel, dim3(ti.total_tiles), dim3(256), 0, st, ti, splats, num_splats, depths, ranges, sorted_keys,
+                sorted_vals, count_ptr, max_entries, out_weight, out_expected, out_median, nf_stamp, nf_frame);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }

@@ -19,7 +19,7 @@
 // (11 words each); per channel the workgroup converts it to shifted f32 in LDS, filters the five moments over the tile + 5-pixel halo (42 x 42,
 // horizontal then vertical pass, several outputs per thread so that neighbouring outputs share their taps), evaluates the three maps there,
 // and filters the maps down to the tile (horizontal, then vertical).  LDS: 65 KB, two workgroups per CU.
-#include "common.h"
+#include "launch.h"
 #include "dmath.h"
 
 namespace {
@@ -254,16 +254,14 @@ __global__ __launch_bounds__(256) void dssim_grad_kernel(u32 W, u32 H, const u32
 
 }  // namespace
 
-int launch_loss_grad(wdgs_device*, u32, u32, const void*, const void*, const wdgs_training_config&, void*, void*, u32, const void*);
-
 // Same arguments and contract as launch_loss_grad (loss.hip), including the accumulator clear when acc is given.  lambda_dssim == 0 leaves
 // only the L1 and L2 terms, which loss_grad computes with the same expressions: that launch is taken then, so the two modes agree bit for bit.
-int launch_dssim_grad(wdgs_device* dev, u32 W, u32 H, const void* pred, const void* targ, const wdgs_training_config& cfg, void* out, void* acc, u32 acc_rows,
-                      const void* acc_dirty) {
+int launch_dssim_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
+                      const u32* acc_dirty) {
     if (W == 0 || H == 0) return WDGS_OK;
     if (cfg.lambda_dssim == 0.0f) return launch_loss_grad(dev, W, H, pred, targ, cfg, out, acc, acc_rows, acc_dirty);
-    WDGS_LAUNCH(dev, "dssim_grad", dssim_grad_kernel, dim3(ceil_div(W, DT), ceil_div(H, DT)), dim3(256), 0, W, H, (const u32*)pred, (const u32*)targ, cfg,
-                ssim_window(), (float4*)out, (int4*)acc, acc_rows * 3u /*12 i32 per row*/, (const u32*)acc_dirty);
+    WDGS_LAUNCH(dev, "dssim_grad", dssim_grad_kernel, dim3(ceil_div(W, DT), ceil_div(H, DT)), dim3(256), 0, W, H, pred, targ, cfg, ssim_window(), out,
+                reinterpret_cast<int4*>(acc), acc_rows * 3u /*12 i32 per row: cleared as int4*/, acc_dirty);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }

@@ -1,0 +1,129 @@
+// The host functions one .hip file defines and another calls: the kernel launchers api.hip sequences (on dev->stream) and the scan / sort primitives the ops
+// share.  Declared once, with the element types their kernels take, and included by api.hip and every defining file: a definition that drifts from its declaration
+// is another overload and fails the link (-Wl,--no-undefined).  void* stops at the C ABI: api.hip casts what came in through include/webdgs.h where it hands it on.
+#pragma once
+#include "common.h"
+
+struct LongWork;   // longlist.h
+
+// ---- scan.hip
+struct ScanScratch {
+    DevMem<u32> block_sums;   // one sum per block of the scan, and the grand total behind them
+    u32 capacity_blocks() const { return block_sums ? (u32)block_sums.count() - 1u : 0u; }
+};
+int scan_scratch_create(ScanScratch* s, u32 max_elements);
+// Exclusive u32 scan of `count` (host-known) elements.  If total_out != nullptr, writes the grand total there.
+int scan_exclusive_u32(wdgs_device* dev, ScanScratch* s, const u32* in, u32* out, u32 count, u32* total_out);
+// Same, with the forward pass's stats epilogue folded into the single-block middle kernel (count must be > 0 for it to run).
+// frame (nullable): the forward pass's frame number, advanced by the scan kernel -- project.hip stamps the tiles of non-finite Splats with the number
+// the frame is ABOUT to get, so a stamp never has to be cleared (raster.hip compares)
+// long_hdr (nullable): the header of the pass's long-list work (longlist.h), zeroed for the frame by the same kernel
+struct ScanStatsEpilogue { u32* stats; u32* visible_shards; u32* host_mirror; u32 capacity; u32* frame = nullptr; u32* long_hdr = nullptr; };
+int scan_exclusive_u32_stats(wdgs_device* dev, ScanScratch* s, const u32* in, u32* out, u32 count, u32* total_out, const ScanStatsEpilogue& ep);
+int scan_block_sums_inplace(wdgs_device* dev, u32* block_sums, u32 num_blocks, const ScanStatsEpilogue& ep);
+// scan_block_sums_inplace + the row scans of the per-workgroup tile-column counts (column_counts[columns][num_blocks] -> offsets in place, totals)
+int forward_scan(wdgs_device* dev, u32* block_sums, u32 num_blocks, u32* column_counts, u32* column_totals, u32 columns, const ScanStatsEpilogue& ep);
+
+// ---- sort.hip.  ranges: u32[segments + 1] / u32[total_tiles + 1], written; lw nullable (no long-list marks); sorted_keys: u32[*count_ptr]
+int sorter_sort_segmented(wdgs_sorter* s, u32 segment_bits, u32 num_segments, u32* ranges, const LongWork* lw);
+int sorter_sort_rows(wdgs_sorter* s, u32 num_tiles_x, u32 num_tiles_y, u32* ranges, const LongWork* lw);
+void sorter_set_final_out_index(wdgs_sorter* s, int i);
+int launch_tile_ranges(wdgs_device* dev, const u32* sorted_keys, const u32* count_ptr, u32 total_tiles, u32* ranges);
+
+// ---- project.hip.  Per Gaussian: gaussians 6 words, sh 24 words, splats 6 words, depths / counts / offsets 1 word
+// column_counts nullable (no per-column counts); dc_words nullable (SH-DC read from sh); nf_stamp u32[tiles], nf_frame one word
+int launch_project_count(wdgs_device* dev, u32 n, const u32* gaussians, const u32* sh, const float* camera, const RenderSettings& st, const TileInfo& ti, u32* splats,
+                         u32* depths, u32* counts, u32* visible_shards, u32* block_counts, u32* column_counts, const u32* dc_words, u32* nf_stamp, const u32* nf_frame);
+// The per-view buffers of launch_project_count, for `count` views; the struct is project_count_views_kernel's argument
+struct ProjectViews {
+    u32 count;
+    const float* camera[WDGS_MAX_BATCH_VIEWS];
+    u32* splats[WDGS_MAX_BATCH_VIEWS];
+    u32* depths[WDGS_MAX_BATCH_VIEWS];
+    u32* tile_counts[WDGS_MAX_BATCH_VIEWS];
+    u32* visible_shards[WDGS_MAX_BATCH_VIEWS];
+    u32* block_counts[WDGS_MAX_BATCH_VIEWS];
+    u32* column_counts[WDGS_MAX_BATCH_VIEWS];   // all null or none null
+    u32* nf_stamp[WDGS_MAX_BATCH_VIEWS];        // (nullable) tiles of non-finite Splats, and each pass's frame number
+    const u32* nf_frame[WDGS_MAX_BATCH_VIEWS];
+};
+int launch_project_count_views(wdgs_device* dev, u32 n, const u32* gaussians, const u32* sh, const RenderSettings& st, const TileInfo& ti, const ProjectViews& pv,
+                               const u32* dc_words /*nullable*/);
+int launch_update_stats(wdgs_device* dev, u32 n, const u32* offsets, const u32* counts, u32 capacity, u32* stats, u32* visible_shards, u32* host_mirror);
+// offsets u32[n], written; block_offsets / column_offsets / column_totals: the scanned counts of project_count; keys, values: u32[capacity], written
+int launch_emit_scatter(wdgs_device* dev, u32 n, const u32* splats, const u32* depths, const u32* counts, u32* offsets, const u32* block_offsets,
+                        const RenderSettings& st, const TileInfo& ti, const u32* column_offsets, const u32* column_totals, u32* keys, u32* values, u32 capacity);
+int launch_emit(wdgs_device* dev, u32 n, const u32* splats, const u32* depths, const u32* counts, u32* offsets, const u32* block_offsets, const RenderSettings& st,
+                const TileInfo& ti, u32* keys, u32* values, u32 capacity);
+
+// ---- raster.hip, depth.hip.  ranges u32[tiles + 1]; sorted_keys / sorted_vals u32[*count_ptr]; max_batches: 0 = unlimited; images are [W*H]; long_work nullable
+int launch_rasterize(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const u32* splats, u32 num_splats, const u32* ranges, const u32* sorted_keys,
+                     const u32* sorted_vals, const u32* count_ptr, u32 max_batches, u32* out_rgba8, float* out_alpha, u32* out_ncontrib, const u32* nf_stamp,
+                     const u32* nf_frame, const LongWork* long_work);
+// depths: the forward pass's depth words, u32[num_splats]; each of the three images nullable (that kind is not wanted)
+int launch_depth_composite(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const u32* splats, u32 num_splats, const u32* depths, const u32* ranges,
+                           const u32* sorted_keys, const u32* sorted_vals, const u32* count_ptr, u32 max_batches, float* out_weight, float* out_expected,
+                           float* out_median, const u32* nf_stamp, const u32* nf_frame);
+
+// ---- loss.hip, dssim.hip.  pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
+int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
+                     const u32* acc_dirty);
+int launch_dssim_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
+                      const u32* acc_dirty);
+
+// ---- backward_raster.hip.  acc: i32[max(n, 1) * 12]; acc_dirty: its state word
+int launch_acc_clear_if_dirty(wdgs_device* dev, int* acc, u32 n, const u32* acc_dirty);
+// ranges u32[tiles + 1]; instances: the sorted indices; final_t f32[W*H], n_contrib u32[W*H], loss_grad rgba32f[W*H]; long_work nullable
+int launch_backward_rasterize(wdgs_device* dev, const RenderSettings& st, u32 num_tiles_x, u32 num_tiles_y, const u32* ranges, const u32* instances, const u32* splats,
+                              const float* final_t, const u32* n_contrib, const float4* loss_grad, int* acc, u32* acc_dirty, const LongWork* long_work);
+
+// ---- backward.hip.  gradients: GaussianGradient[n], 8 words each; tile_counts u32[n]
+int launch_geometry_backward(wdgs_device* dev, u32 n, const float* camera, const RenderSettings& st, const u32* gaussians, int* acc, u32* gradients);
+// gradients, guard, dc_words nullable; gaussians and sh are rewritten
+int launch_geometry_backward_adam(wdgs_device* dev, u32 n, const float* camera, const RenderSettings& st, u32* gaussians, int* acc, u32* acc_dirty, u32* gradients,
+                                  const wdgs_adam_hyperparameters& h, const u32* tile_counts, const wdgs_optimizer_state& state, const CsView& cs, u32* sh,
+                                  const u32* guard, u32* dc_words);
+// sums f32[n][14], visible u32[n]; guard, overflow: one word each; mode: 1 = the step's first view (store), 2 = a later one (add)
+int launch_geometry_backward_accumulate(wdgs_device* dev, u32 n, const float* camera, const RenderSettings& st, const u32* gaussians, int* acc, u32* acc_dirty,
+                                        u32* gradients, float* sums, u32* visible, const u32* tile_counts, u32* guard, const u32* overflow, u32 mode);
+// The per-view arguments of launch_geometry_backward_accumulate, for `count` views; the struct is geometry_backward_views_kernel's argument
+struct GeometryViews {
+    u32 count;
+    const float* camera[WDGS_MAX_BATCH_VIEWS];
+    int* acc[WDGS_MAX_BATCH_VIEWS];
+    u32* acc_dirty[WDGS_MAX_BATCH_VIEWS];
+    const u32* tile_counts[WDGS_MAX_BATCH_VIEWS];
+    const u32* overflow[WDGS_MAX_BATCH_VIEWS];
+    u32* gradients[WDGS_MAX_BATCH_VIEWS];   // nullable per view: the packed per-view GaussianGradient, for readers of getGradientsBuffer()
+};
+int launch_geometry_backward_views(wdgs_device* dev, u32 n, const RenderSettings& st, const u32* gaussians, const GeometryViews& gv, float* sums, u32* visible,
+                                   u32* guard, u32 continues);
+
+// ---- optimizer.hip.  guard, dc_words (u32[n][2]) and rows_out nullable; guard_seen_host: the device's pinned host_guard word
+int launch_adam_repack(wdgs_device* dev, u32 n, const wdgs_adam_hyperparameters& h, const u32* tile_counts, const u32* gradients, const wdgs_optimizer_state& st,
+                       const CsView& cs, u32* gaussians, u32* sh, const u32* guard, u32* dc_words);
+// steps the Gaussians [first, first + count); visible: u32 per Gaussian, grad_f32: 14 floats per Gaussian
+int launch_adam_repack_f32(wdgs_device* dev, u32 first, u32 count, const wdgs_adam_hyperparameters& h, const u32* visible, const float* grad_f32,
+                           const wdgs_optimizer_state& st, const CsView& cs, u32* gaussians, u32* sh, const u32* guard, u32* guard_seen_host, u32* rows_out,
+                           u32* dc_words);
+int launch_apply_rows(wdgs_device* dev, u32 n, const u32* rows, u32 skip_first, u32 skip_count, const u32* guard, u32* guard_seen_host, u32* gaussians, u32* sh,
+                      u32* dc_words);
+int launch_dc_words_load(wdgs_device* dev, u32 n, const u32* sh, u32* dc_words);
+int launch_dc_words_flush(wdgs_device* dev, u32 n, const u32* dc_words, u32* sh);
+int launch_guard_accumulate(wdgs_device* dev, u32* flag, const u32* src, u32 overwrite);   // one word each
+int launch_cs_load(wdgs_device* dev, u32 n, const wdgs_optimizer_state& st, const CsView& cs);
+int launch_cs_flush(wdgs_device* dev, u32 n, const CsView& cs, const wdgs_optimizer_state& st);
+// gradients: GaussianGradient[n]; acc f32[n][14], visible u32[n]
+int launch_accumulate_gradients(wdgs_device* dev, u32 n, const u32* gradients, const u32* tile_counts, float* acc, u32* visible);
+int launch_store_gradients(wdgs_device* dev, u32 n, const u32* gradients, const u32* tile_counts, float* acc, u32* visible);
+int launch_unpack(wdgs_device* dev, u32 n, const u32* gaussians, const u32* sh, const wdgs_optimizer_state& st);
+
+// ---- densify.hip.  rgba8 images: src sw x sh, dst dw x dh
+int launch_downsample(wdgs_device* dev, const u32* src, u32 sw, u32 sh, u32* dst, u32 dw, u32 dh);
+// pred, targ rgba8[W*H]; err, flags u32[W*H], written; minmax u32[2]; scratch unused
+int launch_metric_map(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, float err_scale, float threshold, u32* err, u32* minmax, u32* scratch,
+                      u32* flags);
+// ranges u32[tiles + 1]; flags, n_contrib u32[W*H]; counts u32[num_counts], added to
+int launch_metric_count(wdgs_device* dev, const RenderSettings& st, u32 ntx, u32 nty, const u32* ranges, const u32* instances, u32 num_instances, const u32* splats,
+                        u32 num_splats, const u32* flags, const u32* n_contrib, u32* counts, u32 num_counts);
+int launch_metric_normalize(wdgs_device* dev, u32 n, u32 divisor, u32* counts);

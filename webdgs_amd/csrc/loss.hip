@@ -7,7 +7,7 @@
 // compulsory 8 B read + 16 B write per pixel; window taps are a conflict-free ds_read_b128 + ds_read_b64, shared by four pixels per thread.
 // The window sums keep the reference's order (dy outer, dx inner); the second-moment accumulations are FMAs, the contraction the
 // parity oracle pins (WGSL leaves it open).
-#include "common.h"
+#include "launch.h"
 #include "dmath.h"
 
 namespace {
@@ -169,12 +169,12 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32*
 
 }  // namespace
 
-int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const void* pred, const void* targ, const wdgs_training_config& cfg, void* out, void* acc, u32 acc_rows,
-                     const void* acc_dirty) {
+int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
+                     const u32* acc_dirty) {
     if (W == 0 || H == 0) return WDGS_OK;
-#define WDGS_LOSS_LAUNCH(PPT_)                                                                                                                                       \
-    WDGS_LAUNCH(dev, "loss_grad", loss_grad_kernel<PPT_>, dim3(ceil_div(W, LT), ceil_div(H, 8u * PPT_)), dim3(256), 0, W, H, (const u32*)pred, (const u32*)targ, cfg, \
-                (float4*)out, (int4*)acc, acc_rows * 3u /*12 i32 per row*/, (const u32*)acc_dirty)
+#define WDGS_LOSS_LAUNCH(PPT_)                                                                                                                \
+    WDGS_LAUNCH(dev, "loss_grad", loss_grad_kernel<PPT_>, dim3(ceil_div(W, LT), ceil_div(H, 8u * PPT_)), dim3(256), 0, W, H, pred, targ, cfg, out, \
+                reinterpret_cast<int4*>(acc), acc_rows * 3u /*12 i32 per row: cleared as int4*/, acc_dirty)
     if ((size_t)W * H <= 640u * 480u) { WDGS_LOSS_LAUNCH(1u); } else { WDGS_LOSS_LAUNCH(2u); }
 #undef WDGS_LOSS_LAUNCH
     WDGS_CHECK_HIP(hipGetLastError());

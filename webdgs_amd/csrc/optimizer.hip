@@ -13,7 +13,7 @@
 // release_state / destroy), loaded by cs_load when state is adopted, unpacked or rewritten from outside.
 // Arithmetic and visible results are unchanged.  Per visible Gaussian: 32 B gradient + 4 B visibility + 2 x (3 x 48 + 12
 // + 36) B state; per Gaussian 24 B + 8 B re-pack writes.
-#include "common.h"
+#include "launch.h"
 #include "wgslm.h"
 #include "adam.h"
 
@@ -206,91 +206,88 @@ __global__ __launch_bounds__(256) void unpack_kernel(u32 n, const u32* __restric
 
 }  // namespace
 
-int launch_adam_repack(wdgs_device* dev, u32 n, const wdgs_adam_hyperparameters& h, const void* tile_counts, const void* gradients,
-                       const wdgs_optimizer_state& st, const CsView& cs, void* gaussians, void* sh, const void* guard, void* dc_words) {
+int launch_adam_repack(wdgs_device* dev, u32 n, const wdgs_adam_hyperparameters& h, const u32* tile_counts, const u32* gradients, const wdgs_optimizer_state& st,
+                       const CsView& cs, u32* gaussians, u32* sh, const u32* guard, u32* dc_words) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "adam_repack", adam_repack_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, h, (const u32*)tile_counts, (const u32*)gradients,
-                (float4*)st.opt_rot, (float*)st.opt_opacity, cs, (u32*)gaussians, (u32*)sh, (const u32*)guard, (u32*)dc_words);
+    WDGS_LAUNCH(dev, "adam_repack", adam_repack_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, h, tile_counts, gradients, static_cast<float4*>(st.opt_rot),
+                static_cast<float*>(st.opt_opacity), cs, gaussians, sh, guard, dc_words);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_adam_repack_f32(wdgs_device* dev, u32 first, u32 count, const wdgs_adam_hyperparameters& h, const void* visible, const void* grad_f32,
-                           const wdgs_optimizer_state& st, const CsView& cs, void* gaussians, void* sh, const void* guard, void* guard_seen_host, void* rows_out,
-                           void* dc_words) {
+int launch_adam_repack_f32(wdgs_device* dev, u32 first, u32 count, const wdgs_adam_hyperparameters& h, const u32* visible, const float* grad_f32,
+                           const wdgs_optimizer_state& st, const CsView& cs, u32* gaussians, u32* sh, const u32* guard, u32* guard_seen_host, u32* rows_out,
+                           u32* dc_words) {
     if (count == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "adam_repack_f32", adam_repack_f32_kernel, dim3(ceil_div(count, 256)), dim3(256), 0, first, count, h, (const u32*)visible,
-                (const float*)grad_f32, (float4*)st.opt_rot, (float*)st.opt_opacity, cs, (u32*)gaussians,
-                (u32*)sh, (const u32*)guard, (u32*)guard_seen_host, (u32*)rows_out, (u32*)dc_words);
+    WDGS_LAUNCH(dev, "adam_repack_f32", adam_repack_f32_kernel, dim3(ceil_div(count, 256)), dim3(256), 0, first, count, h, visible, grad_f32,
+                static_cast<float4*>(st.opt_rot), static_cast<float*>(st.opt_opacity), cs, gaussians, sh, guard, guard_seen_host, rows_out, dc_words);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_apply_rows(wdgs_device* dev, u32 n, const void* rows, u32 skip_first, u32 skip_count, const void* guard, void* guard_seen_host, void* gaussians, void* sh,
-                      void* dc_words) {
+int launch_apply_rows(wdgs_device* dev, u32 n, const u32* rows, u32 skip_first, u32 skip_count, const u32* guard, u32* guard_seen_host, u32* gaussians, u32* sh,
+                      u32* dc_words) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "apply_repacked_rows", apply_rows_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)rows, skip_first, skip_count,
-                (const u32*)guard, (u32*)guard_seen_host, (u32*)gaussians, (u32*)sh, (u32*)dc_words);
+    WDGS_LAUNCH(dev, "apply_repacked_rows", apply_rows_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, rows, skip_first, skip_count, guard, guard_seen_host, gaussians,
+                sh, dc_words);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_dc_words_load(wdgs_device* dev, u32 n, const void* sh, void* dc_words) {
+int launch_dc_words_load(wdgs_device* dev, u32 n, const u32* sh, u32* dc_words) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "optimizer_dc_words_load", dc_words_load_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)sh, (u32*)dc_words);
+    WDGS_LAUNCH(dev, "optimizer_dc_words_load", dc_words_load_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, sh, dc_words);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_dc_words_flush(wdgs_device* dev, u32 n, const void* dc_words, void* sh) {
+int launch_dc_words_flush(wdgs_device* dev, u32 n, const u32* dc_words, u32* sh) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "optimizer_dc_words_flush", dc_words_flush_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)dc_words, (u32*)sh);
+    WDGS_LAUNCH(dev, "optimizer_dc_words_flush", dc_words_flush_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, dc_words, sh);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_guard_accumulate(wdgs_device* dev, void* flag, const void* src, u32 overwrite) {
-    WDGS_LAUNCH(dev, "guard_accumulate", guard_accumulate_kernel, dim3(1), dim3(1), 0, (u32*)flag, (const u32*)src, overwrite);
+int launch_guard_accumulate(wdgs_device* dev, u32* flag, const u32* src, u32 overwrite) {
+    WDGS_LAUNCH(dev, "guard_accumulate", guard_accumulate_kernel, dim3(1), dim3(1), 0, flag, src, overwrite);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
 int launch_cs_load(wdgs_device* dev, u32 n, const wdgs_optimizer_state& st, const CsView& cs) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "optimizer_cs_load", cs_load_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const float4*)st.opt_pos, (const float4*)st.opt_scale,
-                (const float*)st.param_sh, (const float2*)st.state_sh, cs);
+    WDGS_LAUNCH(dev, "optimizer_cs_load", cs_load_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, static_cast<const float4*>(st.opt_pos),
+                static_cast<const float4*>(st.opt_scale), static_cast<const float*>(st.param_sh), static_cast<const float2*>(st.state_sh), cs);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
 int launch_cs_flush(wdgs_device* dev, u32 n, const CsView& cs, const wdgs_optimizer_state& st) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "optimizer_cs_flush", cs_flush_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, cs, (float4*)st.opt_pos, (float4*)st.opt_scale,
-                (float*)st.param_sh, (float2*)st.state_sh);
+    WDGS_LAUNCH(dev, "optimizer_cs_flush", cs_flush_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, cs, static_cast<float4*>(st.opt_pos), static_cast<float4*>(st.opt_scale),
+                static_cast<float*>(st.param_sh), static_cast<float2*>(st.state_sh));
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_accumulate_gradients(wdgs_device* dev, u32 n, const void* gradients, const void* tile_counts, void* acc, void* visible) {
+int launch_accumulate_gradients(wdgs_device* dev, u32 n, const u32* gradients, const u32* tile_counts, float* acc, u32* visible) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "accumulate_gradients", accumulate_gradients_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)gradients,
-                (const u32*)tile_counts, (float*)acc, (u32*)visible);
+    WDGS_LAUNCH(dev, "accumulate_gradients", accumulate_gradients_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, gradients, tile_counts, acc, visible);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_store_gradients(wdgs_device* dev, u32 n, const void* gradients, const void* tile_counts, void* acc, void* visible) {
+int launch_store_gradients(wdgs_device* dev, u32 n, const u32* gradients, const u32* tile_counts, float* acc, u32* visible) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "store_gradients", store_gradients_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)gradients, (const u32*)tile_counts,
-                (float*)acc, (u32*)visible);
+    WDGS_LAUNCH(dev, "store_gradients", store_gradients_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, gradients, tile_counts, acc, visible);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_unpack(wdgs_device* dev, u32 n, const void* gaussians, const void* sh, const wdgs_optimizer_state& st) {
+int launch_unpack(wdgs_device* dev, u32 n, const u32* gaussians, const u32* sh, const wdgs_optimizer_state& st) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "optimizer_unpack", unpack_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)gaussians, (const u32*)sh, (float4*)st.opt_pos,
-                (float4*)st.opt_rot, (float4*)st.opt_scale, (float*)st.opt_opacity, (float*)st.param_sh);
+    WDGS_LAUNCH(dev, "optimizer_unpack", unpack_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, gaussians, sh, static_cast<float4*>(st.opt_pos),
+                static_cast<float4*>(st.opt_rot), static_cast<float4*>(st.opt_scale), static_cast<float*>(st.opt_opacity), static_cast<float*>(st.param_sh));
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }

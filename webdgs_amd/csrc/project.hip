@@ -5,7 +5,7 @@
 //   project: reads 24 B Gaussian + 6K B SH (K = (deg+1)^2, visible only), writes 24 B Splat + 4 B depth (visible)
 //            and 4 B tile count (all)           -> N(24+4) + V(6K+28) bytes
 //   emit:    reads 24 B Splat + 4 B depth + 8 B count/offset, writes 8 B per tile entry -> 16V + 8N + 8E bytes
-#include "common.h"
+#include "launch.h"
 #include "wgslm.h"
 
 namespace {
@@ -245,18 +245,6 @@ __global__ __launch_bounds__(256) void project_count_kernel(u32 n, const u32* __
 // K1 for ALL the views of a batched step (wdgs_tiled_forward_project_views): the thread fetches its Gaussian and SH row once and projects
 // it under each camera in turn into that view's own buffers.  Per view the epilogue of project_count: tile count, visible-count shard,
 // the workgroup's entry count and its per-column counts.
-struct ProjectViews {
-    u32 count;
-    const float* camera[WDGS_MAX_BATCH_VIEWS];
-    u32* splats[WDGS_MAX_BATCH_VIEWS];
-    u32* depths[WDGS_MAX_BATCH_VIEWS];
-    u32* tile_counts[WDGS_MAX_BATCH_VIEWS];
-    u32* visible_shards[WDGS_MAX_BATCH_VIEWS];
-    u32* block_counts[WDGS_MAX_BATCH_VIEWS];
-    u32* column_counts[WDGS_MAX_BATCH_VIEWS];   // all null or none null
-    u32* nf_stamp[WDGS_MAX_BATCH_VIEWS];        // (nullable) tiles of non-finite Splats, and each pass's frame number
-    const u32* nf_frame[WDGS_MAX_BATCH_VIEWS];
-};
 // (256, 4): the register allocation aims at 4 resident waves per SIMD (192 us at c3); aimed at 5 or 6 it spills 56 / 120 bytes per thread
 // and takes 236 / 292 us (profiles/r05n_k1_views_occupancy_ab.txt)
 __global__ __launch_bounds__(256, 4) void project_count_views_kernel(u32 n, const u32* __restrict__ gaussians, const u32* __restrict__ sh_buffer, RenderSettings settings,
@@ -626,56 +614,42 @@ __global__ __launch_bounds__(256) void emit_scatter_kernel(u32 n, const u32* __r
 
 }  // namespace
 
-int launch_project_count(wdgs_device* dev, u32 n, const void* gaussians, const void* sh, const void* camera, const RenderSettings& st,
-                         const TileInfo& ti, void* splats, void* depths, void* counts, void* visible_shards, void* block_counts, void* column_counts,
-                         const void* dc_words, void* nf_stamp, const void* nf_frame) {
+int launch_project_count(wdgs_device* dev, u32 n, const u32* gaussians, const u32* sh, const float* camera, const RenderSettings& st, const TileInfo& ti, u32* splats,
+                         u32* depths, u32* counts, u32* visible_shards, u32* block_counts, u32* column_counts, const u32* dc_words, u32* nf_stamp, const u32* nf_frame) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "project_count", project_count_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)gaussians, (const u32*)sh,
-                (const float*)camera, st, ti, (u32*)splats, (u32*)depths, (u32*)counts, (u32*)visible_shards, (u32*)block_counts, (u32*)column_counts,
-                (const u32*)dc_words, (u32*)nf_stamp, (const u32*)nf_frame);
+    WDGS_LAUNCH(dev, "project_count", project_count_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, gaussians, sh, camera, st, ti, splats, depths, counts, visible_shards,
+                block_counts, column_counts, dc_words, nf_stamp, nf_frame);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_project_count_views(wdgs_device* dev, u32 n, u32 count, const void* gaussians, const void* sh, const void* const* cameras, const RenderSettings& st,
-                               const TileInfo& ti, void* const* splats, void* const* depths, void* const* counts, void* const* visible_shards, void* const* block_counts,
-                               void* const* column_counts, const void* dc_words, void* const* nf_stamp, const void* const* nf_frame) {
-    if (n == 0 || count == 0) return WDGS_OK;
-    ProjectViews pv{};
-    pv.count = count;
-    for (u32 v = 0; v < count; v++) {
-        pv.camera[v] = (const float*)cameras[v]; pv.splats[v] = (u32*)splats[v]; pv.depths[v] = (u32*)depths[v]; pv.tile_counts[v] = (u32*)counts[v];
-        pv.visible_shards[v] = (u32*)visible_shards[v]; pv.block_counts[v] = (u32*)block_counts[v]; pv.column_counts[v] = column_counts ? (u32*)column_counts[v] : nullptr;
-        pv.nf_stamp[v] = nf_stamp ? (u32*)nf_stamp[v] : nullptr; pv.nf_frame[v] = nf_frame ? (const u32*)nf_frame[v] : nullptr;
-    }
-    WDGS_LAUNCH(dev, "project_count_views", project_count_views_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)gaussians, (const u32*)sh, st, ti, pv,
-                (const u32*)dc_words);
+int launch_project_count_views(wdgs_device* dev, u32 n, const u32* gaussians, const u32* sh, const RenderSettings& st, const TileInfo& ti, const ProjectViews& pv,
+                               const u32* dc_words) {
+    if (n == 0 || pv.count == 0) return WDGS_OK;
+    WDGS_LAUNCH(dev, "project_count_views", project_count_views_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, gaussians, sh, st, ti, pv, dc_words);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_update_stats(wdgs_device* dev, u32 n, const void* offsets, const void* counts, u32 capacity, void* stats, void* visible_shards, void* host_mirror) {
-    WDGS_LAUNCH(dev, "update_stats", update_stats_kernel, dim3(1), dim3(64), 0, n, (const u32*)offsets, (const u32*)counts, capacity, (u32*)stats,
-                (u32*)visible_shards, (u32*)host_mirror);
+int launch_update_stats(wdgs_device* dev, u32 n, const u32* offsets, const u32* counts, u32 capacity, u32* stats, u32* visible_shards, u32* host_mirror) {
+    WDGS_LAUNCH(dev, "update_stats", update_stats_kernel, dim3(1), dim3(64), 0, n, offsets, counts, capacity, stats, visible_shards, host_mirror);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_emit_scatter(wdgs_device* dev, u32 n, const void* splats, const void* depths, const void* counts, void* offsets, const void* block_offsets,
-                        const RenderSettings& st, const TileInfo& ti, const void* column_offsets, const void* column_totals, void* keys, void* values, u32 capacity) {
+int launch_emit_scatter(wdgs_device* dev, u32 n, const u32* splats, const u32* depths, const u32* counts, u32* offsets, const u32* block_offsets,
+                        const RenderSettings& st, const TileInfo& ti, const u32* column_offsets, const u32* column_totals, u32* keys, u32* values, u32 capacity) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "emit_scatter", emit_scatter_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)splats, (const u32*)depths, (const u32*)counts,
-                (u32*)offsets, (const u32*)block_offsets, st, ti, (const u32*)column_offsets, (const u32*)column_totals, 0xFFFFFFFFu / ti.num_tiles_x + 1u /*num_tiles_x >= 2 on this path*/,
-                (u32*)keys, (u32*)values, capacity);
+    WDGS_LAUNCH(dev, "emit_scatter", emit_scatter_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, splats, depths, counts, offsets, block_offsets, st, ti, column_offsets,
+                column_totals, 0xFFFFFFFFu / ti.num_tiles_x + 1u /*num_tiles_x >= 2 on this path*/, keys, values, capacity);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
 
-int launch_emit(wdgs_device* dev, u32 n, const void* splats, const void* depths, const void* counts, void* offsets, const void* block_offsets,
-                const RenderSettings& st, const TileInfo& ti, void* keys, void* values, u32 capacity) {
+int launch_emit(wdgs_device* dev, u32 n, const u32* splats, const u32* depths, const u32* counts, u32* offsets, const u32* block_offsets, const RenderSettings& st,
+                const TileInfo& ti, u32* keys, u32* values, u32 capacity) {
     if (n == 0) return WDGS_OK;
-    WDGS_LAUNCH(dev, "emit", emit_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)splats, (const u32*)depths, (const u32*)counts,
-                (u32*)offsets, (const u32*)block_offsets, st, ti, (u32*)keys, (u32*)values, capacity);
+    WDGS_LAUNCH(dev, "emit", emit_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, splats, depths, counts, offsets, block_offsets, st, ti, keys, values, capacity);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }

@@ -1,7 +1,7 @@
 // Exclusive u32 prefix scan (replaces src/prefix/prefix.ts + prefix_sum.wgsl K2-K4: 3-phase Blelloch, <= 2 097 152
 // elements).  Here: reduce -> scan of block sums -> down-sweep, 4096 elements per 256-thread block, 16-byte
 // loads/stores, wave64 shuffle scans, no element cap.  HBM traffic 12 B/element (read, read, write).
-#include "common.h"
+#include "launch.h"
 
 namespace {
 

@@ -23,7 +23,7 @@
 #include <algorithm>
 #include <memory>
 
-#include "common.h"
+#include "launch.h"
 #include "longlist.h"
 
 namespace {
@@ -675,11 +675,12 @@ int wdgs_sorter_destroy(wdgs_sorter* s) {
 void* wdgs_sorter_keys(wdgs_sorter* s, int i) { return s ? s->keys[i & 1].get() : nullptr; }
 void* wdgs_sorter_values(wdgs_sorter* s, int i) { return s ? s->vals[i & 1].get() : nullptr; }
 int wdgs_sorter_final_out_index(wdgs_sorter* s) { return s ? s->final_out_index : 0; }
-// (internal) the forward pass left unsorted entries in ping-pong 0 (encode(skipSort)): that is what the getters hand out
-void sorter_set_final_out_index(wdgs_sorter* s, int i) { if (s) s->final_out_index = i & 1; }
 uint32_t wdgs_sorter_capacity(wdgs_sorter* s) { return s ? s->capacity : 0; }
 
 }  // extern "C"
+
+// the forward pass left unsorted entries in ping-pong 0 (encode(skipSort)): that is what the getters hand out
+void sorter_set_final_out_index(wdgs_sorter* s, int i) { if (s) s->final_out_index = i & 1; }
 
 // Stable sort of keys laid out as (segment id << 16 | 16-bit minor key): LSD passes over the segment bits, the range table of
 // the segments, then one workgroup per segment for the minor key.  `ranges` = u32[num_segments + 1], written here.
@@ -799,9 +800,8 @@ int wdgs_sorter_sort(wdgs_sorter* s, uint32_t key_bits) {
 
 }  // extern "C"
 
-int launch_tile_ranges(wdgs_device* dev, const void* sorted_keys, const void* count_ptr, u32 total_tiles, void* ranges) {
-    WDGS_LAUNCH(dev, "tile_ranges", tile_ranges_kernel, dim3(ceil_div(total_tiles + 1, 4)), dim3(256), 0, (const u32*)sorted_keys, (const u32*)count_ptr,
-                total_tiles, (u32*)ranges);
+int launch_tile_ranges(wdgs_device* dev, const u32* sorted_keys, const u32* count_ptr, u32 total_tiles, u32* ranges) {
+    WDGS_LAUNCH(dev, "tile_ranges", tile_ranges_kernel, dim3(ceil_div(total_tiles + 1, 4)), dim3(256), 0, sorted_keys, count_ptr, total_tiles, ranges);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
@@ -815,12 +815,13 @@ extern "C" int wdgs_debug_sort_tiles(wdgs_sorter* s, uint32_t route, uint32_t nu
     const unsigned long long tiles = (unsigned long long)num_tiles_x * num_tiles_y;
     WDGS_REQUIRE(tiles >= 1ull && tiles <= 65534ull, WDGS_E_INVALID, "wdgs_debug_sort_tiles: %u x %u tiles (1..65534)", num_tiles_x, num_tiles_y);
     const u32 total = (u32)tiles;
-    if (route == 0u) return sorter_sort_segmented(s, bits_for(total), total, (u32*)ranges_u32_dev, nullptr);
+    u32* const ranges = static_cast<u32*>(ranges_u32_dev);
+    if (route == 0u) return sorter_sort_segmented(s, bits_for(total), total, ranges, nullptr);
     if (route == 1u) {
         WDGS_REQUIRE(num_tiles_x >= 2u && num_tiles_x <= 256u && num_tiles_y <= 256u, WDGS_E_INVALID,
                      "wdgs_debug_sort_tiles: the row route takes 2..256 tile columns and at most 256 tile rows, not %u x %u", num_tiles_x, num_tiles_y);
-        return sorter_sort_rows(s, num_tiles_x, num_tiles_y, (u32*)ranges_u32_dev, nullptr);
+        return sorter_sort_rows(s, num_tiles_x, num_tiles_y, ranges, nullptr);
     }
     s->final_out_index = 0;   // the caller's sorted keys stay where they are
-    return launch_tile_ranges(s->dev, s->keys[0], s->count_ptr, total, ranges_u32_dev);
+    return launch_tile_ranges(s->dev, s->keys[0], s->count_ptr, total, ranges);
 }
