@@ -30,6 +30,22 @@ const DEFAULT_DENSIFY = {   // trainer.ts:147-164
   pruneOpacity: 0.01, cloneThresholdCount: 500, splitScaleThreshold: 1.0,
 };
 
+/** The passes that render one view at a time, and what they own between them (webdgs_amd/trainer.py PassSet).  A training set has all three passes; a
+ *  metric set (one per metric lane of a densify event) has the metric pass as backwardPass, its down-sampled ground truth as target and its camera
+ *  block; an evaluation set has no backward pass. */
+class PassSet {
+  constructor(forwardPass, rasterizer, backwardPass) {
+    this.forwardPass = forwardPass; this.rasterizer = rasterizer; this.backwardPass = backwardPass || null;
+    this.target = null; this.cameraBuffer = null;
+    this.ownsCamera = false;   // (metric set 0 renders through the trainer's own metricsCameraBuffer, which outlives it)
+  }
+  destroy() {
+    for (const owned of [this.forwardPass, this.rasterizer, this.backwardPass, this.target, this.ownsCamera ? this.cameraBuffer : null]) if (owned) owned.destroy();
+  }
+}
+/** Destroys every pass of `sets`, in set order. */
+function destroyPassSets(sets) { for (const s of sets) s.destroy(); }
+
 class Trainer {
   /** options: random, useCommandBuffers, maxTileEntries, reusePasses, deferredSH, fuseGeometryAdam, keepGradients, pipelineDepth (1..4),
    *  viewsPerStep (views per rank per global step), lanes (device lanes of a batched step; default 3), batchViews (view-batched K1 / K17;
@@ -64,17 +80,16 @@ class Trainer {
     this.lanes = Math.max(1, Math.min(Math.floor(lanes), this.viewsPerRank, hip.MAX_LANES));
     this.batchViews = this.viewsPerRank > 1 && o.batchViews !== false;
     this.opSets = this.batchViews ? Math.min(this.viewsPerRank, hip.MAX_BATCH_VIEWS) : this.lanes;
-    this.moreOpSets = [];   // [forwardPass, rasterizer, backwardPass] of op sets 1.. (set 0 is the three below)
+    this.trainSets = [];   // PassSet per op set of a step (set 0: the single-view step's, the public forwardPass / rasterizer / backwardPass)
     // The metric views of a densify event are independent until normalizeMetricCounts (integer atomics: any order gives the same bits): they are
     // dealt to `metricLanes` op sets, each on a device lane of its own, all adding into set 0's counts (TiledBackwardPass.setMetricCountsTarget).
     this.metricLanes = Math.max(1, Math.min(Math.floor(o.metricLanes || Trainer.DEFAULT_LANES), hip.MAX_LANES));
     this.longLists = null;      // long tile lists (csrc/longlist.h): null = the library's defaults; { threshold, maxItems, maxRows } for the passes this trainer builds
-    this.moreMetricSets = [];   // [forwardPass, rasterizer, metricsPass, target, cameraBuffer] of metric lanes 1..
+    this.metricSets = [];   // PassSet per metric lane (set 0: the public metricsForwardPass / metricsRasterizer / metricsPass / metricsTarget)
     this.dpGrad = null; this.dpVisible = null; this.dpRows = null; this.dpFlag = null; this.stateSliced = false;
     this.dcWords = null;
-    this.forwardPass = null; this.rasterizer = null; this.backwardPass = null; this.optimizer = null; this.pointCloud = null;
-    this.metricsForwardPass = null; this.metricsRasterizer = null; this.metricsPass = null;
-    this.metricsViewportWidth = 0; this.metricsViewportHeight = 0; this.metricsTarget = null;
+    this.optimizer = null; this.pointCloud = null;
+    this.metricsViewportWidth = 0; this.metricsViewportHeight = 0;
     this.metricsCameraBuffer = device.createBuffer({ size: 272, label: 'metrics camera uniform' });
     this.densifyPruneConfig = JSON.parse(JSON.stringify(DEFAULT_DENSIFY));
     this.densifyPrune = new hip.DensifyPrunePass(device, this.densifyOpConfig());
@@ -83,7 +98,7 @@ class Trainer {
     this.trainCameras = []; this.images = []; this.cameraBuffers = [];
     this.commandBuffers = new Map(); this.eagerSteps = 0;
     // held-out evaluation (setEvaluationViews / evaluate): views never drawn for training, and render passes of evaluate's own, one
-    // [forwardPass, rasterizer] per image size, built on first use and following the cloud
+    // PassSet (no backward pass) per image size, built on first use and following the cloud
     this.evalCameras = []; this.evalImages = []; this.evalCameraBuffers = []; this.evalOwnedTextures = [];
     this.evalSets = new Map();
     this.evalMaxTileEntries = 0;   // tile-entry lists of evaluate's passes (0: what the training passes get)
@@ -105,9 +120,20 @@ class Trainer {
     if (!this.pointCloud) return;
     this.requestPointCloudSwap(hip.allocatePointCloudLike(this.device, this.pointCloud, { numPoints }));
   }
-  destroyMoreOpSets() { for (const set of this.moreOpSets) for (const op of set) op.destroy(); this.moreOpSets = []; }
-  destroyMoreMetricSets() { for (const set of this.moreMetricSets) for (const op of set) op.destroy(); this.moreMetricSets = []; }
-  forwardPasses() { return [this.forwardPass, this.metricsForwardPass].concat(this.moreOpSets.map((m) => m[0]), this.moreMetricSets.map((m) => m[0])).filter((p) => p); }
+  // ---- the pass sets (the reference's names are views of set 0)
+  get forwardPass() { return this.trainSets.length ? this.trainSets[0].forwardPass : null; }
+  get rasterizer() { return this.trainSets.length ? this.trainSets[0].rasterizer : null; }
+  get backwardPass() { return this.trainSets.length ? this.trainSets[0].backwardPass : null; }
+  get metricsForwardPass() { return this.metricSets.length ? this.metricSets[0].forwardPass : null; }
+  get metricsRasterizer() { return this.metricSets.length ? this.metricSets[0].rasterizer : null; }
+  get metricsPass() { return this.metricSets.length ? this.metricSets[0].backwardPass : null; }
+  get metricsTarget() { return this.metricSets.length ? this.metricSets[0].target : null; }
+  /** The training and metric sets: what a step and a densify event run.  (evaluate's sets follow the cloud and answer capacity reports on their own,
+   *  evalFollowCloud / evalOverflow.) */
+  allSets() { return this.trainSets.concat(this.metricSets); }
+  forwardPasses() { return this.allSets().map((s) => s.forwardPass); }
+  /** Every pass but the optimizer's and evaluate's goes; ensurePipelines and the first use of a metric set build them anew. */
+  destroyPassSets() { destroyPassSets(this.allSets()); this.trainSets = []; this.metricSets = []; }
   applyPointCloudSwap(request) {   // trainer.ts:201-237
     this.drain();
     this.synchronize();
@@ -118,18 +144,9 @@ class Trainer {
     this.pointCloud = request.pointCloud;
     // The reference destroys every pass and constructs new ones; the passes here can follow a cloud of another size
     // (setPointCloud: buffers reused, or re-allocated with headroom), so only the optimizer -- which adopts the rebuilt state -- is new.
-    const passes = [this.forwardPass, this.backwardPass, this.metricsForwardPass, this.metricsPass];
-    for (const m of this.moreOpSets.concat(this.moreMetricSets)) passes.push(m[0], m[2]);
-    const kept = this.reusePasses && old && !this.recreateBackward && passes.filter((p) => p).every((p) => p.setPointCloud(this.pointCloud));
-    if (!kept) {
-      for (const name of ['forwardPass', 'rasterizer', 'backwardPass', 'metricsForwardPass', 'metricsRasterizer', 'metricsPass']) {
-        if (this[name]) this[name].destroy();
-        this[name] = null;
-      }
-      this.destroyMoreOpSets();
-      this.destroyMoreMetricSets();
-      this.gradientOutputApplied = null;
-    }
+    const kept = this.reusePasses && old && !this.recreateBackward &&
+      this.allSets().every((s) => s.forwardPass.setPointCloud(this.pointCloud) && s.backwardPass.setPointCloud(this.pointCloud));
+    if (!kept) this.destroyPassSets();
     this.optimizer = new hip.Optimizer(this.device, this.pointCloud, oldParams || this.optimizerHyperparameters, request.optimizerInitialState);
     this.optimizerHyperparameters = this.optimizer.getHyperparameters();
     this.dcWords = this.deferredSH ? this.optimizer.setDeferredSH(this.pointCloud, true) : null;
@@ -252,10 +269,11 @@ class Trainer {
     for (const fw of this.forwardPasses()) fw.setLongLists(this.longLists.threshold === undefined ? 2048 : this.longLists.threshold, this.longLists.maxItems, this.longLists.maxRows);
   }
 
-  newOpSet(w, h) {
-    const fw = this.newForwardPass(this.cameraBuffers.length ? this.cameraBuffers[0] : this.metricsCameraBuffer, w, h);
-    return [fw, new hip.TiledRasterizer({ device: this.device, forwardPass: fw, format: 'rgba8unorm' }),
-      new hip.TiledBackwardPass(this.device, this.pointCloud, { viewportWidth: w, viewportHeight: h, trainingConfig: this.trainingConfig })];
+  newBackwardPass(w, h) { return new hip.TiledBackwardPass(this.device, this.pointCloud, { viewportWidth: w, viewportHeight: h, trainingConfig: this.trainingConfig }); }
+  /** Forward pass, rasterizer and (`backward`) backward pass for a w x h viewport: the only place the trainer constructs them. */
+  newPassSet(cameraBuffer, w, h, backward, maxTileEntries) {
+    const fw = this.newForwardPass(cameraBuffer, w, h, maxTileEntries);
+    return new PassSet(fw, new hip.TiledRasterizer({ device: this.device, forwardPass: fw, format: 'rgba8unorm' }), backward ? this.newBackwardPass(w, h) : null);
   }
 
   ensurePipelines(width, height) {   // trainer.ts:662-692 (the rasterizer follows the viewport here: SURVEY Q19)
@@ -263,57 +281,46 @@ class Trainer {
     if (w !== this.lastViewportWidth || h !== this.lastViewportHeight) this.invalidateCommandBuffers();
     this.lastViewportWidth = w; this.lastViewportHeight = h;
     const cam = this.cameraBuffers.length ? this.cameraBuffers[0] : this.metricsCameraBuffer;
-    if (!this.forwardPass) {
-      this.forwardPass = this.newForwardPass(cam, w, h);
-    } else this.forwardPass.setViewport(w, h);
-    if (!this.rasterizer) this.rasterizer = new hip.TiledRasterizer({ device: this.device, forwardPass: this.forwardPass, format: 'rgba8unorm' });
-    if (!this.backwardPass || this.recreateBackward) {
-      if (this.backwardPass) this.backwardPass.destroy();
-      this.backwardPass = new hip.TiledBackwardPass(this.device, this.pointCloud, { viewportWidth: w, viewportHeight: h, trainingConfig: this.trainingConfig });
-      for (const m of this.moreOpSets) { m[2].destroy(); m[2] = new hip.TiledBackwardPass(this.device, this.pointCloud, { viewportWidth: w, viewportHeight: h, trainingConfig: this.trainingConfig }); }
-      this.recreateBackward = false; this.gradientOutputApplied = null;
-    } else this.backwardPass.setViewport(w, h);
-    for (const m of this.moreOpSets) { m[0].setViewport(w, h); m[2].setViewport(w, h); }
-    while (this.moreOpSets.length < this.opSets - 1) this.moreOpSets.push(this.newOpSet(w, h));
+    for (const s of this.trainSets) {
+      s.forwardPass.setViewport(w, h);
+      if (this.recreateBackward) { s.backwardPass.destroy(); s.backwardPass = this.newBackwardPass(w, h); } else s.backwardPass.setViewport(w, h);   // (setTrainingConfig)
+    }
+    if (this.recreateBackward || !this.trainSets.length) this.gradientOutputApplied = null;   // (a fresh pass writes the packed gradient: applyGradientOutput decides)
+    this.recreateBackward = false;
+    while (this.trainSets.length < this.opSets) this.trainSets.push(this.newPassSet(cam, w, h, true));
     // a step whose tile-entry list overflowed is skipped on the device and reported by the next synchronize()
-    if (this.optimizer && this.worldSize * this.viewsPerRank === 1) this.optimizer.setGuard(this.forwardPass.getStatsBuffer(), 8);
+    if (this.optimizer && this.worldSize * this.viewsPerRank === 1) this.optimizer.setGuard(this.trainSets[0].forwardPass.getStatsBuffer(), 8);
   }
 
   ensureMetricsPipelines(baseWidth, baseHeight) {   // trainer.ts:330-371
     const down = Math.max(1, Math.floor(this.densifyPruneConfig.metricDownscale));
     const w = Math.max(1, Math.floor(baseWidth / down)), h = Math.max(1, Math.floor(baseHeight / down));
-    if (this.metricsForwardPass && this.metricsViewportWidth === w && this.metricsViewportHeight === h) return { width: w, height: h };
-    for (const name of ['metricsForwardPass', 'metricsRasterizer', 'metricsPass']) { if (this[name]) this[name].destroy(); this[name] = null; }
-    this.destroyMoreMetricSets();
-    if (this.metricsTarget) this.metricsTarget.destroy();
+    if (this.metricSets.length && this.metricsViewportWidth === w && this.metricsViewportHeight === h) return { width: w, height: h };
+    destroyPassSets(this.metricSets);
+    this.metricSets = [];
     this.metricsViewportWidth = w; this.metricsViewportHeight = h;
-    this.metricsForwardPass = this.newForwardPass(this.metricsCameraBuffer, w, h);
-    this.metricsRasterizer = new hip.TiledRasterizer({ device: this.device, forwardPass: this.metricsForwardPass, format: 'rgba8unorm' });
-    this.metricsPass = new hip.TiledBackwardPass(this.device, this.pointCloud, { viewportWidth: w, viewportHeight: h, trainingConfig: this.trainingConfig });
-    this.metricsTarget = this.device.createBuffer({ size: 4 * w * h, label: 'metrics-gt-downsampled' });
+    this.metricSet(0);
     return { width: w, height: h };
   }
 
-  /** [forwardPass, rasterizer, metricsPass, downsampled-GT buffer, camera buffer] of metric lane k; sets 1.. are built on first use. */
+  /** The pass set of metric lane k (backwardPass: its metric pass), at the metrics viewport; built on first use.  Set 0 renders through the trainer's
+   *  metricsCameraBuffer, the others through a camera block of their own. */
   metricSet(k) {
-    if (k === 0) return [this.metricsForwardPass, this.metricsRasterizer, this.metricsPass, this.metricsTarget, this.metricsCameraBuffer];
     const w = this.metricsViewportWidth, h = this.metricsViewportHeight;
-    while (this.moreMetricSets.length < k) {
-      const cam = this.device.createBuffer({ size: 272, label: 'metrics camera uniform' });
-      const fw = this.newForwardPass(cam, w, h);
-      this.moreMetricSets.push([fw, new hip.TiledRasterizer({ device: this.device, forwardPass: fw, format: 'rgba8unorm' }),
-        new hip.TiledBackwardPass(this.device, this.pointCloud, { viewportWidth: w, viewportHeight: h, trainingConfig: this.trainingConfig }),
-        this.device.createBuffer({ size: 4 * w * h, label: 'metrics-gt-downsampled' }), cam]);
+    while (this.metricSets.length <= k) {
+      const own = this.metricSets.length > 0;
+      const cam = own ? this.device.createBuffer({ size: 272, label: 'metrics camera uniform' }) : this.metricsCameraBuffer;
+      const s = this.newPassSet(cam, w, h, true);
+      s.target = this.device.createBuffer({ size: 4 * w * h, label: 'metrics-gt-downsampled' }); s.cameraBuffer = cam; s.ownsCamera = own;
+      this.metricSets.push(s);
     }
-    return this.moreMetricSets[k - 1];
+    return this.metricSets[k];
   }
-
-  opsOf(opSet) { return opSet > 0 ? this.moreOpSets[opSet - 1] : [this.forwardPass, this.rasterizer, this.backwardPass]; }
 
   /** trainer.ts:606-628 for one view on one op set.  geometry = false: the view ends with K16 (K17 follows separately: fused with Adam, or batched);
    *  projected = true: K1 ran for all the views of the step at once (hip.projectViews), scan / emit / sort remain. */
   encodeView(encoder, index, opSet, geometry, projected) {
-    const ops = this.opsOf(opSet || 0), forwardPass = ops[0], rasterizer = ops[1], backwardPass = ops[2];
+    const { forwardPass, rasterizer, backwardPass } = this.trainSets[opSet || 0];
     const image = this.images[index], cam = this.cameraBuffers[index];
     forwardPass.setCameraBuffer(cam);
     if (projected) forwardPass.encodeProjected(encoder); else forwardPass.encode(encoder);
@@ -390,13 +397,7 @@ class Trainer {
     try { this.device.synchronize(); } catch (_e) { /* a step still in flight overflowed as well */ }
     this.invalidateCommandBuffers();
     // forward passes own the lists: every pass set is rebuilt around lists of the new size (as a cloud the passes cannot follow rebuilds them)
-    for (const name of ['forwardPass', 'rasterizer', 'backwardPass', 'metricsForwardPass', 'metricsRasterizer', 'metricsPass']) {
-      if (this[name]) this[name].destroy();
-      this[name] = null;
-    }
-    this.destroyMoreOpSets();
-    this.destroyMoreMetricSets();
-    this.gradientOutputApplied = null;
+    this.destroyPassSets();
     this.ensurePipelines(this.lastViewportWidth, this.lastViewportHeight);
     for (const fw of this.forwardPasses()) fw.setDcSource(this.dcWords);
     return true;
@@ -446,14 +447,11 @@ class Trainer {
     if (this.iteration >= this.maxIterations) this.stop();
   }
 
-  /** The entries needed by THIS trainer's passes among those a capacity report names (csrc/api.hip: deferred_checks names every pass that overflowed),
+  /** What THIS trainer's passes needed (entries) among the passes a capacity report names (csrc/api.hip: deferred_checks names every pass that overflowed),
    *  [] if it names only other owners' passes, null if it names none (a step skipped on every rank). */
   ownOverflow(error) {
-    const named = [], re = /(\d+) entries needed, max_tile_entries = \d+ \(forward pass (0x[0-9a-fA-F]+)\)/g, text = String(error && error.message);
-    for (let m = re.exec(text); m; m = re.exec(text)) named.push([Number(m[1]), BigInt(m[2])]);
-    if (!named.length) return null;
-    const own = this.forwardPasses().map((fw) => BigInt(fw.handle));
-    return named.filter((n) => own.some((h) => h === n[1])).map((n) => n[0]);
+    const { mine, others } = hip.CapacityReports.split(error, this.forwardPasses().map((fw) => fw.handle));
+    return mine.length || others ? mine.map((o) => o.needed) : null;
   }
   /** true (after saying so once) for a capacity report about passes this trainer does not own -- a Viewer rendering the same cloud on this device: the
    *  report is device-wide, whoever waits first gets it, and it is the pass's owner who has to enlarge its lists. */
@@ -500,7 +498,7 @@ class Trainer {
   /** The reference's step (trainer.ts:603-645): one view, Adam straight from the packed fp16 gradients. */
   stepSingleView(view) {
     this.applyGradientOutput();
-    const tileCounts = this.forwardPass.getResources().tileCountsBuffer;
+    const tileCounts = this.trainSets[0].forwardPass.getResources().tileCountsBuffer;
     const replayed = this.run('step/' + view, (encoder) => {
       if (this.fuseGeometryAdam) {   // K1..K16, then K17 + Adam + re-pack in one pass over the Gaussians
         this.encodeView(encoder, view, 0, false, false);
@@ -544,7 +542,7 @@ class Trainer {
    *  lane of their own; each view waits only for the projection, K17 for every view. */
   viewsBatched(mine) {
     const dev = this.device, L = this.lanes;
-    const sets = mine.map((_v, k) => this.opsOf(k));
+    const sets = this.trainSets.slice(0, mine.length);
     const cams = mine.map((v) => this.cameraBuffers[v]);
     const lanes = L > 1 && this.useCommandBuffers && mine.every((v, k) => this.commandBuffers.has(`viewp/${v}/${k}`));
     const U = L < hip.MAX_LANES ? L : 0;   // the lane of the batched launches
@@ -552,7 +550,7 @@ class Trainer {
     try {
       if (lanes) for (let s = 1; s < joinFrom; s++) dev.laneOrder(s, 0);   // every lane starts behind whatever lane 0 holds
       if (lanes) dev.selectLane(U);
-      hip.projectViews(sets.map((s) => s[0]), cams, this.pointCloud);
+      hip.projectViews(sets.map((s) => s.forwardPass), cams, this.pointCloud);
       if (lanes) dev.laneMark(U, 0);
       mine.forEach((v, k) => {
         if (lanes) { dev.laneWaitMark(k % L, 0); dev.selectLane(k % L); }
@@ -560,7 +558,7 @@ class Trainer {
         if (lanes) dev.laneOrder(U, k % L);   // K17 follows every view
       });
       if (lanes) dev.selectLane(U);
-      hip.geometryViews(sets.map((s) => s[2]), cams, sets.map((s) => s[0]), this.dpGrad, this.dpVisible, this.dpFlag, this.pointCloud, false, false);
+      hip.geometryViews(sets.map((s) => s.backwardPass), cams, sets.map((s) => s.forwardPass), this.dpGrad, this.dpVisible, this.dpFlag, this.pointCloud, false, false);
     } finally {
       if (lanes) {
         hip.addon.encoderAbort(dev.handle);   // (a no-op unless an encode above failed mid-recording)
@@ -578,12 +576,12 @@ class Trainer {
     try {
       if (lanes) for (let s = 1; s < L; s++) dev.laneOrder(s, 0);
       mine.forEach((v, k) => {
-        const s = k % L, ops = this.opsOf(s);
+        const s = k % L, { forwardPass, backwardPass } = this.trainSets[s];
         if (lanes) dev.selectLane(s);
         this.run(`view/${v}/${s}`, (encoder) => this.encodeView(encoder, v, s, false, false));
         if (lanes && k > 0) dev.laneOrder(s, (k - 1) % L);   // the fp32 block is filled in view order
-        ops[2].encodeGeometry(null, this.cameraBuffers[v], { sums: this.dpGrad, visible: this.dpVisible, first: k === 0,
-          tileCounts: ops[0].getResources().tileCountsBuffer, guard: this.dpFlag, stats: ops[0].getStatsBuffer() });
+        backwardPass.encodeGeometry(null, this.cameraBuffers[v], { sums: this.dpGrad, visible: this.dpVisible, first: k === 0,
+          tileCounts: forwardPass.getResources().tileCountsBuffer, guard: this.dpFlag, stats: forwardPass.getStatsBuffer() });
       });
     } finally {
       if (lanes) {
@@ -612,9 +610,8 @@ class Trainer {
   /** The capacity report of this rank's metric forward passes (their sticky words are consumed), or null.  Synchronises. */
   metricOverflow() {
     let found = null;
-    for (const fw of [this.metricsForwardPass].concat(this.moreMetricSets.map((m) => m[0]))) {
-      if (!fw) continue;
-      try { fw.check(); } catch (e) { if (e && e.code === 'WDGS_E_CAPACITY') found = found || e; else throw e; }
+    for (const s of this.metricSets) {
+      try { s.forwardPass.check(); } catch (e) { if (e && e.code === 'WDGS_E_CAPACITY') found = found || e; else throw e; }
     }
     return found;
   }
@@ -652,7 +649,7 @@ class Trainer {
         if (!take) continue;
         const k = taken % L;   // this rank's views in turn on its metric lanes; every lane's pass adds into set 0's counts
         taken++;
-        const set = this.metricSet(k), fw = set[0], rast = set[1], mpass = set[2], target = set[3], cam = set[4];
+        const { forwardPass: fw, rasterizer: rast, backwardPass: mpass, target, cameraBuffer: cam } = this.metricSet(k);
         if (k > 0) {
           if (taken <= L) { mpass.setMetricCountsTarget(counts); dev.laneOrder(k, 0); }   // the lane's first view of this event: behind the clear
           dev.selectLane(k);
@@ -727,17 +724,11 @@ class Trainer {
       return b;
     });
   }
-  destroyEvalSets() {
-    for (const [fw, rast] of this.evalSets.values()) { rast.destroy(); fw.destroy(); }
-    this.evalSets = new Map();
-  }
-  /** evaluate's [forwardPass, rasterizer] for one image size, built through newForwardPass (live SH-DC words, this trainer's long-list settings).  Never a guard. */
+  destroyEvalSets() { destroyPassSets(this.evalSets.values()); this.evalSets = new Map(); }
+  /** evaluate's pass set (no backward pass) for one image size, built through newForwardPass (live SH-DC words, this trainer's long-list settings).  Never a guard. */
   evalSet(w, h, cam) {
     const key = `${w}x${h}`;
-    if (!this.evalSets.has(key)) {
-      const fw = this.newForwardPass(cam, w, h, this.evalTileEntries || this.evalMaxTileEntries || null);
-      this.evalSets.set(key, [fw, new hip.TiledRasterizer({ device: this.device, forwardPass: fw, format: 'rgba8unorm' })]);
-    }
+    if (!this.evalSets.has(key)) this.evalSets.set(key, this.newPassSet(cam, w, h, false, this.evalTileEntries || this.evalMaxTileEntries || null));
     return this.evalSets.get(key);
   }
   evalFollowCloud() {
@@ -745,14 +736,14 @@ class Trainer {
       this.destroyEvalSets();
       this.evalLongLists = this.longLists ? Object.assign({}, this.longLists) : null;
     }
-    for (const [fw] of this.evalSets.values()) {
+    for (const { forwardPass: fw } of this.evalSets.values()) {
       if (fw.pointCloud !== this.pointCloud && !fw.setPointCloud(this.pointCloud)) { this.destroyEvalSets(); break; }
     }
-    for (const [fw] of this.evalSets.values()) fw.setDcSource(this.dcWords);
+    for (const s of this.evalSets.values()) s.forwardPass.setDcSource(this.dcWords);
   }
   /** Waits for the evaluation renders; the entries the largest overflowing one needed, or null (Trainer.py _eval_overflow). */
   evalOverflow() {
-    const own = [...this.evalSets.values()].map(([fw]) => BigInt(fw.handle));
+    const own = [...this.evalSets.values()].map((s) => s.forwardPass.handle);
     let err = null;
     try {
       this.device.synchronize();
@@ -762,13 +753,10 @@ class Trainer {
       err = e;
     }
     if (!err) return null;
-    const named = [], re = /(\d+) entries needed, max_tile_entries = \d+ \(forward pass (0x[0-9a-fA-F]+)\)/g, text = String(err.message);
-    for (let m = re.exec(text); m; m = re.exec(text)) named.push([Number(m[1]), BigInt(m[2])]);
-    const mine = named.filter((n) => own.some((h) => h === n[1])).map((n) => n[0]);
-    const all = hip.CapacityReports.passesNamed(err);
-    if (all.some((h) => !own.some((o) => o === h))) this.device.capacityReports.post(err);
-    if (!mine.length) { if (all.length) return null; throw err; }
-    return Math.max(...mine);
+    const { mine, others } = hip.CapacityReports.split(err, own);
+    if (others) this.device.capacityReports.post(err);
+    if (!mine.length && !others) throw err;
+    return mine.length ? Math.max(...mine.map((o) => o.needed)) : null;
   }
   /** PSNR and SSIM of the current model on the evaluation views (split 'eval') or on training views (split 'train'): { iteration, views, psnr, ssim,
    *  sse, mean_psnr, mean_ssim, ms }.  Drains the pipeline, renders every view through passes of its own, writes view i's SSE and SSIM into slot i
@@ -789,7 +777,7 @@ class Trainer {
       this.evalFollowCloud();
       ids.forEach((v, i) => {
         const im = imgs[v], w = im.width, h = im.height;
-        const [fw, rast] = this.evalSet(w, h, bufs[v]);
+        const { forwardPass: fw, rasterizer: rast } = this.evalSet(w, h, bufs[v]);
         fw.setCameraBuffer(bufs[v]);
         fw.encode(null);
         rast.encode(null, w, h);
@@ -799,7 +787,7 @@ class Trainer {
       });
       const needed = this.evalOverflow();
       if (needed === null) break;
-      const now = Math.max(this.evalTileEntries, ...[...this.evalSets.values()].map(([fw]) => Number(fw.getResources().maxTileEntries)));
+      const now = Math.max(this.evalTileEntries, ...[...this.evalSets.values()].map((s) => Number(s.forwardPass.getResources().maxTileEntries)));
       const next = Math.min(Math.max(2 * now, Math.floor(needed * 1.5)), 0xFFFFF000);
       if (next <= now) throw new Error(`evaluate: a view needs ${needed} tile entries, more than the lists can hold`);
       console.warn(`evaluation tile-entry lists grown from ${now} to ${next} entries after an overflow; the views are rendered again`);
@@ -823,18 +811,13 @@ class Trainer {
       try { this.device.synchronize(); } catch (_e) { /* a deferred report about a step of a trainer that is going away */ }
     }
     this.invalidateCommandBuffers();
-    for (const name of ['forwardPass', 'rasterizer', 'backwardPass', 'metricsForwardPass', 'metricsRasterizer', 'metricsPass', 'optimizer', 'densifyPrune']) {
-      if (this[name]) this[name].destroy();
-      this[name] = null;
-    }
-    this.destroyMoreOpSets();
-    this.destroyMoreMetricSets();
-    this.destroyEvalSets();
+    this.destroyPassSets(); this.destroyEvalSets();
+    for (const name of ['optimizer', 'densifyPrune']) { if (this[name]) this[name].destroy(); this[name] = null; }
     for (const b of this.cameraBuffers.concat(this.evalCameraBuffers, this.evalOwnedTextures)) b.destroy();
     this.cameraBuffers = []; this.evalCameraBuffers = []; this.evalOwnedTextures = [];
     for (const t of this.ownedTextures || []) t.destroy();
     this.ownedTextures = [];
-    for (const name of ['dpGrad', 'dpVisible', 'dpRows', 'dpFlag', 'metricsTarget', 'agreeWord']) { if (this[name]) this[name].destroy(); this[name] = null; }
+    for (const name of ['dpGrad', 'dpVisible', 'dpRows', 'dpFlag', 'agreeWord']) { if (this[name]) this[name].destroy(); this[name] = null; }
     this.metricsCameraBuffer.destroy();
     this.isTraining = false;
   }

@@ -84,12 +84,9 @@ class Viewer {
         if (left) throw left;
         break;
       } catch (e) {
-        // (a report names up to four passes: this viewer's line)
-        const own = BigInt(this.forwardPass.handle), re = /(\d+) entries needed, max_tile_entries = (\d+) \(forward pass (0x[0-9a-fA-F]+)\)/g, text = String(e && e.message);
-        let m = null;
-        if (e && e.code === 'WDGS_E_CAPACITY') for (let x = re.exec(text); x && !m; x = re.exec(text)) if (BigInt(x[3]) === own) m = x;
-        if (!m) throw e;
-        this.tileEntries = Math.min(Math.max(2 * Number(m[2]), Math.floor(Number(m[1]) * 1.5)), 0xFFFFF000);
+        const mine = e && e.code === 'WDGS_E_CAPACITY' ? hip.CapacityReports.split(e, [this.forwardPass.handle]).mine : [];   // (a report names up to four passes: this viewer's line)
+        if (!mine.length) throw e;
+        this.tileEntries = Math.min(Math.max(2 * mine[0].capacity, Math.floor(mine[0].needed * 1.5)), 0xFFFFF000);
         this.buildPasses();
         rerender();
       }

@@ -65,17 +65,28 @@ class HipEncoder {
  *  that name their own passes -- and leave the others here, where the passes' owner looks at its own next wait. */
 class CapacityReports {
   constructor(keep) { this.pending = []; this.keep = keep || 16; }
-  static passesNamed(error) {
-    const out = [], re = /\(forward pass (0x[0-9a-fA-F]+)\)/g, text = String(error && error.message);
-    for (let m = re.exec(text); m; m = re.exec(text)) out.push(BigInt(m[1]));
+  /** [{ needed, capacity, handle }] -- one record per pass the report names, in the report's order (handle: a BigInt); [] for any other error.  The one
+   *  reader of report text (webdgs_amd/ops.py has its twin).  It follows two format strings of csrc/api.hip:
+   *    deferred_checks:          "tile entries overflow: " + "%u entries needed, max_tile_entries = %u (forward pass %p)" joined by "; " + " (raise ...)"
+   *    wdgs_tiled_forward_check: "tile entries overflow: %u entries needed, max_tile_entries = %u (forward pass %p)"
+   *  Known limit: the library names at most four passes per report; a fifth that overflowed in the same wait is consumed unnamed. */
+  static parse(error) {
+    const out = [], re = /(\d+) entries needed, max_tile_entries = (\d+) \(forward pass (0x[0-9a-fA-F]+)\)/g, text = String(error && error.message);
+    for (let m = re.exec(text); m; m = re.exec(text)) out.push({ needed: Number(m[1]), capacity: Number(m[2]), handle: BigInt(m[3]) });
     return out;
   }
+  /** { mine, others }: the records about `ownHandles`' passes, and whether the report also names passes of another owner. */
+  static split(error, ownHandles) {
+    const own = ownHandles.map((h) => BigInt(h)), named = CapacityReports.parse(error);
+    const mine = named.filter((o) => own.some((h) => h === o.handle));
+    return { mine, others: mine.length < named.length };
+  }
+  static passesNamed(error) { return CapacityReports.parse(error).map((o) => o.handle); }
   post(error) { this.pending.push(error); if (this.pending.length > this.keep) this.pending.splice(0, this.pending.length - this.keep); }
   /** The oldest pending report that names one of `ownHandles` (removed), or null. */
   take(ownHandles) {
-    const own = ownHandles.map((h) => BigInt(h));
     for (let i = 0; i < this.pending.length; i++) {
-      if (CapacityReports.passesNamed(this.pending[i]).some((h) => own.some((o) => o === h))) return this.pending.splice(i, 1)[0];
+      if (CapacityReports.split(this.pending[i], ownHandles).mine.length) return this.pending.splice(i, 1)[0];
     }
     return null;
   }

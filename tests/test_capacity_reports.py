@@ -56,3 +56,99 @@ def test_the_node_host_keeps_the_same_mailbox():
         pytest.skip("the addon needs the HIP runtime to load")
     assert r.returncode == 0, r.stderr[-2000:]
     assert json.loads(r.stdout.strip().splitlines()[-1]) == [True] * 5
+
+
+# ---- the report parser (ops.CapacityReports.parse / split; webdgs_hip.js mirrors it), on exact copies of the library's two message forms (csrc/api.hip)
+def _line(needed, capacity, handle):
+    return f"{needed} entries needed, max_tile_entries = {capacity} (forward pass {handle:#x})"   # "%u entries needed, max_tile_entries = %u (forward pass %p)"
+
+
+def _deferred(*passes):
+    """deferred_checks: "tile entries overflow: %s (raise wdgs_tiled_forward_config.max_tile_entries)" over the passes' lines joined by "; "."""
+    return RuntimeError("[wdgs -3] tile entries overflow: " + "; ".join(_line(*p) for p in passes) + " (raise wdgs_tiled_forward_config.max_tile_entries)")
+
+
+def _checked(needed, capacity, handle):
+    """wdgs_tiled_forward_check: "tile entries overflow: %u entries needed, max_tile_entries = %u (forward pass %p)"."""
+    return RuntimeError("[wdgs -3] tile entries overflow: " + _line(needed, capacity, handle))
+
+
+PASSES = [(1_924_441, 1_921_024, 0x7f3a12345000), (0xFFFFF000, 1 << 20, 0x7f3a12346f80), (1_048_577, 1_048_576, 0x55d0c0ffee10), (3, 2, 0x7f3a00000010)]
+SKIPPED = "[wdgs -3] an optimizer step was skipped on every rank: tile entries overflowed on another rank (its own error names the size)"
+
+
+@pytest.mark.parametrize("n", [1, 2, 4])
+def test_parse_reads_every_pass_of_a_deferred_report_in_order(n):
+    from webdgs_amd.ops import CapacityReports, Overflow
+    got = CapacityReports.parse(_deferred(*PASSES[:n]))
+    assert got == [Overflow(*p) for p in PASSES[:n]]
+    assert [(o.needed, o.capacity, o.handle) for o in got] == PASSES[:n]
+    assert CapacityReports.passes_named(_deferred(*PASSES[:n])) == {p[2] for p in PASSES[:n]}
+
+
+def test_parse_reads_the_single_pass_form_and_nothing_from_other_errors():
+    from webdgs_amd.ops import CapacityReports, Overflow
+    assert CapacityReports.parse(_checked(*PASSES[1])) == [Overflow(0xFFFFF000, 1 << 20, 0x7f3a12346f80)]
+    assert CapacityReports.parse(RuntimeError(SKIPPED)) == []
+    assert CapacityReports.parse(RuntimeError("[wdgs -1] wdgs_buffer_create: size must be positive")) == []
+
+
+def test_split_tells_own_passes_from_other_owners():
+    from webdgs_amd.ops import CapacityReports, Overflow
+    a, b, c = PASSES[:3]
+    assert CapacityReports.split(_deferred(a, b), [a[2], b[2], 0x1234]) == ([Overflow(*a), Overflow(*b)], False)   # own handles only
+    assert CapacityReports.split(_deferred(a, b), [c[2]]) == ([], True)                                            # others only
+    assert CapacityReports.split(_deferred(a, b, c), iter([b[2]])) == ([Overflow(*b)], True)                       # both (any iterable of handles)
+    assert CapacityReports.split(_deferred(a), []) == ([], True)                                                   # an empty own set
+    assert CapacityReports.split(RuntimeError(SKIPPED), [a[2]]) == ([], False)                                     # names no pass: nobody's
+
+
+def test_the_node_host_parses_and_splits_the_same():
+    node = shutil.which("node")
+    if not node or not os.path.exists(os.path.join(ROOT, "bindings", "napi", "webdgs_napi.node")):
+        pytest.skip("node or the N-API addon is not available")
+    src = """
+      const { CapacityReports } = require(process.argv[1]);
+      const passes = JSON.parse(process.argv[2]).map((p) => ({ needed: p[0], capacity: p[1], handle: BigInt(p[2]) }));
+      const line = (p) => `${p.needed} entries needed, max_tile_entries = ${p.capacity} (forward pass 0x${p.handle.toString(16)})`;
+      const deferred = (ps) => new Error('[wdgs -3] tile entries overflow: ' + ps.map(line).join('; ') + ' (raise wdgs_tiled_forward_config.max_tile_entries)');
+      const same = (got, want) => got.length === want.length && got.every((o, i) => o.needed === want[i].needed && o.capacity === want[i].capacity && o.handle === want[i].handle);
+      const [a, b, c] = passes, out = [];
+      for (const n of [1, 2, 4]) out.push(same(CapacityReports.parse(deferred(passes.slice(0, n))), passes.slice(0, n)));
+      out.push(same(CapacityReports.parse(new Error('[wdgs -3] tile entries overflow: ' + line(b))), [b]));
+      out.push(CapacityReports.parse(new Error(process.argv[3])).length === 0, CapacityReports.parse(new Error('[wdgs -1] wdgs_buffer_create: size must be positive')).length === 0);
+      let s = CapacityReports.split(deferred([a, b]), [a.handle, b.handle, 0x1234]); out.push(same(s.mine, [a, b]) && s.others === false);
+      s = CapacityReports.split(deferred([a, b]), [c.handle]); out.push(s.mine.length === 0 && s.others === true);
+      s = CapacityReports.split(deferred([a, b, c]), [b.handle]); out.push(same(s.mine, [b]) && s.others === true);
+      s = CapacityReports.split(deferred([a]), []); out.push(s.mine.length === 0 && s.others === true);
+      console.log(JSON.stringify(out));
+    """
+    r = subprocess.run([node, "-e", src, os.path.join(ROOT, "bindings", "ts", "webdgs_hip.js"), json.dumps([[n, c, hex(h)] for n, c, h in PASSES]), SKIPPED],
+                       capture_output=True, text=True, timeout=120)
+    if r.returncode != 0 and "libamdhip64" in r.stderr + r.stdout:
+        pytest.skip("the addon needs the HIP runtime to load")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1]) == [True] * 10
+
+
+# ---- the pass sets of the trainer (trainer.PassSet), without a device: stub ops that record their destroy()
+def test_destroying_pass_sets_destroys_every_op_once_in_set_order():
+    from webdgs_amd.trainer import PassSet, destroy_pass_sets
+    log = []
+
+    class Stub:
+        def __init__(self, name):
+            self.name = name
+
+        def destroy(self):
+            log.append(self.name)
+
+    shared_camera = Stub("camera of the trainer")
+    sets = [PassSet(Stub("t0.fw"), Stub("t0.rast"), Stub("t0.bw")), PassSet(Stub("t1.fw"), Stub("t1.rast"), Stub("t1.bw")),
+            PassSet(Stub("m0.fw"), Stub("m0.rast"), Stub("m0.metric"), target=Stub("m0.target"), cameraBuffer=shared_camera),
+            PassSet(Stub("m1.fw"), Stub("m1.rast"), Stub("m1.metric"), target=Stub("m1.target"), cameraBuffer=Stub("m1.camera"), ownsCamera=True),
+            PassSet(Stub("e0.fw"), Stub("e0.rast"))]
+    destroy_pass_sets(sets)
+    assert log == ["t0.fw", "t0.rast", "t0.bw", "t1.fw", "t1.rast", "t1.bw", "m0.fw", "m0.rast", "m0.metric", "m0.target",
+                   "m1.fw", "m1.rast", "m1.metric", "m1.target", "m1.camera", "e0.fw", "e0.rast"]
+    assert "camera of the trainer" not in log, "metric set 0 renders through the trainer's own camera block, which outlives it"

@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import re
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -165,21 +165,44 @@ class _Queue:
         buf.write(data, offset)
 
 
+class Overflow(NamedTuple):
+    """One pass's line of a capacity report: the entries its frame needed, what its lists hold, the forward pass's handle."""
+    needed: int
+    capacity: int
+    handle: int
+
+
 class CapacityReports:
     """Capacity reports that reached the wrong owner.  The library reports a truncated tile-entry list at the next host wait on the DEVICE, to whoever
     waits (csrc/api.hip: deferred_checks consumes every pass's word and names the passes); a Trainer and a Viewer that share a device each handle the
     reports that name their own passes -- and leave the others HERE, where the passes' owner looks at its own next wait (dropped instead, a
     report consumed by the wrong owner was lost to the right one)."""
 
-    _NAMED = re.compile(r"\(forward pass (0x[0-9a-fA-F]+)\)")
-
     def __init__(self, keep: int = 16):
         self.pending: list = []
         self.keep = keep
 
+    @staticmethod
+    def parse(error) -> list:
+        """One ``Overflow(needed, capacity, handle)`` per pass the report names, in the report's order; ``[]`` for any other error."""
+        # The one reader of report text (bindings/ts/webdgs_hip.js has its twin).  It follows two format strings of csrc/api.hip:
+        #   deferred_checks:          "tile entries overflow: " + "; ".join("%u entries needed, max_tile_entries = %u (forward pass %p)") + " (raise ...)"
+        #   wdgs_tiled_forward_check: "tile entries overflow: %u entries needed, max_tile_entries = %u (forward pass %p)"
+        # Known limit: the library names at most four passes per report; a fifth that overflowed in the same wait is consumed unnamed.
+        named = re.findall(r"(\d+) entries needed, max_tile_entries = (\d+) \(forward pass (0x[0-9a-fA-F]+)\)", str(error))
+        return [Overflow(int(n), int(c), int(h, 16)) for n, c, h in named]
+
+    @classmethod
+    def split(cls, error, own_handles) -> tuple:
+        """``(mine, others)``: the records about ``own_handles``' passes, and whether the report also names passes of another owner."""
+        own = {int(h) for h in own_handles}
+        named = cls.parse(error)
+        mine = [o for o in named if o.handle in own]
+        return mine, len(mine) < len(named)
+
     @classmethod
     def passes_named(cls, error) -> set:
-        return {int(h, 16) for h in cls._NAMED.findall(str(error))}
+        return {o.handle for o in cls.parse(error)}
 
     def post(self, error) -> None:
         self.pending.append(error)

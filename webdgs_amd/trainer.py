@@ -10,16 +10,42 @@ produced it instead of on the next animation frame.  New: ``world_size > 1`` run
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 import random
 import time
+import warnings
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import loaders, ops, parallel
+
+
+@dataclasses.dataclass
+class PassSet:
+    """The passes that render one view at a time, and what they own between them.  A training set has all three passes; a metric set (one per
+    metric lane of a densify event) has the metric pass as ``backwardPass``, its down-sampled ground truth as ``target`` and its camera block;
+    an evaluation set has no backward pass."""
+    forwardPass: ops.TiledForwardPass
+    rasterizer: ops.TiledRasterizer
+    backwardPass: Optional[ops.TiledBackwardPass] = None
+    target: Optional[ops.HipBuffer] = None
+    cameraBuffer: Optional[ops.HipBuffer] = None
+    ownsCamera: bool = False   # (metric set 0 renders through the trainer's own ``metricsCameraBuffer``, which outlives it)
+
+    def destroy(self) -> None:
+        for owned in (self.forwardPass, self.rasterizer, self.backwardPass, self.target, self.cameraBuffer if self.ownsCamera else None):
+            if owned is not None:
+                owned.destroy()
+
+
+def destroy_pass_sets(sets) -> None:
+    """Destroys every pass of ``sets``, in set order."""
+    for s in sets:
+        s.destroy()
 
 
 class Trainer:
@@ -69,7 +95,8 @@ class Trainer:
         # every rank draws the same view sequence (same seed), then takes its shard
         self._rng = random.Random(seed)
 
-        self.forwardPass = self.rasterizer = self.backwardPass = self.optimizer = None
+        self._train_sets: list = []  # PassSet per op set of a step (set 0: the single-view step's, the public forwardPass / rasterizer / backwardPass)
+        self.optimizer = None
         # pipeline_depth 1: every step awaits its own completion, as trainer.ts:639-645 does.  2: step() returns once the PREVIOUS
         # step has finished, so the host prepares and submits step k+1 while step k runs (the device never idles across the step
         # boundary); a capacity error then surfaces one step late -- the device-side guard has already kept that step's Adam from
@@ -84,15 +111,12 @@ class Trainer:
         self._dc_words: Optional[ops.HipBuffer] = None
         self._gradient_output_applied: Optional[bool] = None
         self._tickets: list = []
-        self._more_op_sets: list = []  # [forwardPass, rasterizer, backwardPass] of lanes 1.. (set 0 is the three above)
-        self.metricsForwardPass = self.metricsRasterizer = self.metricsPass = None
         self.metricsViewportWidth = self.metricsViewportHeight = 0
-        self.metricsTarget: Optional[ops.HipBuffer] = None
         # The metric views of a densify event are independent until normalizeMetricCounts (counts are integer atomics: any order gives the
         # same bits): they are dealt to `metric_lanes` op sets, each on a device lane of its own, all adding into set 0's counts
         # (TiledBackwardPass.setMetricCountsTarget).  The reference walks them one after the other through one pass (trainer.ts:391-430).
         self.metric_lanes = max(1, min(int(os.environ.get("WDGS_METRIC_LANES", self.DEFAULT_LANES)), ops.MAX_LANES))
-        self._more_metric_sets: list = []  # [forwardPass, rasterizer, metricsPass, target, cameraBuffer] of metric lanes 1..
+        self._metric_sets: list = []  # PassSet per metric lane (set 0: the public metricsForwardPass / metricsRasterizer / metricsPass / metricsTarget)
         self.pointCloud: Optional[ops.PointCloud] = None
         self.cameraBuffer = device.createBuffer(272, "camera uniform")
         self.metricsCameraBuffer = device.createBuffer(272, "metrics camera uniform")
@@ -108,7 +132,7 @@ class Trainer:
         self.trainCameras: list = []   # dicts: camera (float32[68]), width, height
         self.images: list = []         # dicts: texture (HipBuffer rgba8), width, height
         # held-out evaluation (setEvaluationViews / evaluate): views never drawn for training, and render passes of evaluate's own, one
-        # (forward pass, rasterizer) per image size, built on first use and following the cloud
+        # PassSet (no backward pass) per image size, built on first use and following the cloud
         self.evalCameras: list = []
         self.evalImages: list = []
         self._eval_camera_buffers: list = []
@@ -135,19 +159,28 @@ class Trainer:
         self._exchange_events: list = []
 
     DEFAULT_LANES = 3
-    _OP_NAMES = ("forwardPass", "rasterizer", "backwardPass", "metricsForwardPass", "metricsRasterizer", "metricsPass", "optimizer")
 
-    def _destroy_more_metric_sets(self) -> None:
-        for more in self._more_metric_sets:
-            for op in more[:3]:
-                op.destroy()
-        self._more_metric_sets = []
+    # ------------------------------------------------------------------ the pass sets (the reference's names are views of set 0)
+    forwardPass = property(lambda self: self._train_sets[0].forwardPass if self._train_sets else None)
+    rasterizer = property(lambda self: self._train_sets[0].rasterizer if self._train_sets else None)
+    backwardPass = property(lambda self: self._train_sets[0].backwardPass if self._train_sets else None)
+    metricsForwardPass = property(lambda self: self._metric_sets[0].forwardPass if self._metric_sets else None)
+    metricsRasterizer = property(lambda self: self._metric_sets[0].rasterizer if self._metric_sets else None)
+    metricsPass = property(lambda self: self._metric_sets[0].backwardPass if self._metric_sets else None)
+    metricsTarget = property(lambda self: self._metric_sets[0].target if self._metric_sets else None)
 
-    def _destroy_more_op_sets(self) -> None:
-        for ops_of_lane in self._more_op_sets:
-            for op in ops_of_lane:
-                op.destroy()
-        self._more_op_sets = []
+    def _all_sets(self) -> list:
+        """The training and metric sets: what a step and a densify event run.  (evaluate's sets follow the cloud and answer capacity reports on their
+        own, ``_eval_follow_cloud`` / ``_eval_overflow``.)"""
+        return self._train_sets + self._metric_sets
+
+    def _forward_passes(self) -> list:
+        return [s.forwardPass for s in self._all_sets()]
+
+    def _destroy_pass_sets(self) -> None:
+        """Every pass but the optimizer's and evaluate's goes; ``ensurePipelines`` and the first use of a metric set build them anew."""
+        destroy_pass_sets(self._all_sets())
+        self._train_sets, self._metric_sets = [], []
 
     # ------------------------------------------------------------------ configuration
     def _densify_op_config(self) -> dict:
@@ -184,16 +217,9 @@ class Trainer:
         old = self.pointCloud
         self.pointCloud = request["pointCloud"]
         self._invalidate_command_buffers()
-        passes = [self.forwardPass, self.backwardPass, self.metricsForwardPass, self.metricsPass] + [op for more in self._more_op_sets + self._more_metric_sets for op in (more[0], more[2])]
-        kept = self.reuse_passes and old is not None and all(p.setPointCloud(self.pointCloud) for p in passes if p is not None)
+        kept = self.reuse_passes and old is not None and all(p.setPointCloud(self.pointCloud) for s in self._all_sets() for p in (s.forwardPass, s.backwardPass))
         if not kept:
-            for name in self._OP_NAMES:
-                op = getattr(self, name)
-                if op is not None:
-                    op.destroy()
-                setattr(self, name, None)
-            self._destroy_more_op_sets()
-            self._destroy_more_metric_sets()
+            self._destroy_pass_sets()
         self.optimizer = ops.Optimizer(self.device, self.pointCloud, oldParams or self.optimizerHyperparameters, request.get("optimizerInitialState"))
         self.optimizerHyperparameters = dict(self.optimizer.getHyperparameters())
         self._dc_words = self.optimizer.setDeferredSH(self.pointCloud, True) if self.deferred_sh else None
@@ -205,9 +231,6 @@ class Trainer:
         self._dp_grad = self._dp_visible = self._dp_rows = self._dp_flag = None
         self._state_sliced = False
         self.ensurePipelines(self.lastViewportWidth, self.lastViewportHeight)
-
-    def _forward_passes(self) -> list:
-        return [p for p in [self.forwardPass, self.metricsForwardPass] + [more[0] for more in self._more_op_sets + self._more_metric_sets] if p is not None]
 
     def flushPointCloud(self) -> None:
         """Brings the point cloud's SH rows up to date with what has been trained (``Optimizer.flushSH``): call before a device-side reader
@@ -259,9 +282,8 @@ class Trainer:
         ops.dssim_mode(dict(self.trainingConfig, **{k: v for k, v in next_cfg.items() if v is not None}))
         self.trainingConfig.update({k: v for k, v in next_cfg.items() if v is not None})
         self._invalidate_command_buffers()
-        for p in [self.backwardPass, self.metricsPass] + [more[2] for more in self._more_op_sets + self._more_metric_sets]:
-            if p is not None:
-                p.setTrainingConfig(next_cfg)
+        for s in self._all_sets():
+            s.backwardPass.setTrainingConfig(next_cfg)
 
     def getOptimizerHyperparameters(self) -> dict:
         return dict(self.optimizer.getHyperparameters() if self.optimizer else self.optimizerHyperparameters)
@@ -342,13 +364,19 @@ class Trainer:
             fw.setLongLists(int(self.longLists.get("threshold", 2048)), int(self.longLists.get("maxItems", 0)), int(self.longLists.get("maxRows", 0)))
         return fw
 
+    def _new_pass_set(self, cameraBuffer, w: int, h: int, *, backward: bool, max_tile_entries: Optional[int] = None) -> PassSet:
+        """Forward pass, rasterizer and (``backward``) backward pass for a ``w`` x ``h`` viewport: the only place the trainer constructs them."""
+        fw = self._new_forward_pass(cameraBuffer, w, h, max_tile_entries)
+        rast = ops.TiledRasterizer(dict(device=self.device, forwardPass=fw, format="rgba8unorm"))
+        bw = ops.TiledBackwardPass(self.device, self.pointCloud, dict(viewportWidth=w, viewportHeight=h, trainingConfig=self.trainingConfig)) if backward else None
+        return PassSet(fw, rast, bw)
+
     def _grow_long_lists(self) -> None:
         """Long tile lists (csrc/longlist.h) work in scratch of a fixed size; a frame whose long tiles find no room is composited the ordinary way --
         correct, but as slow as its longest list.  The work's header says what the last frame wanted: looked at where the host waits anyway (a densify
         event), and every pass is given room for 1.5 x that -- up to ``longLists.maxItemsCap`` / ``maxRowsCap`` (8 192 chunk slots: 33 000 entries of
         long tiles; 65 536 rows).  A frame that wants more than the caps is FULL of long tiles (a dense cloud at a small viewport): the path is not for
         it (longlist.h: ll_frame_on) and the scratch is left alone.  (Command buffers recorded against the old scratch are dropped.)"""
-        import warnings
         cap_items, cap_rows = int((self.longLists or {}).get("maxItemsCap", 8192)), int((self.longLists or {}).get("maxRowsCap", 65536))
         have_items = have_rows = need_items = need_rows = 0
         for fw in self._forward_passes():
@@ -375,58 +403,38 @@ class Trainer:
             self._invalidate_command_buffers()
         self.lastViewportWidth, self.lastViewportHeight = max(1, int(width)), max(1, int(height))
         w, h = self.lastViewportWidth, self.lastViewportHeight
-        if self.forwardPass is None:
-            self.forwardPass = self._new_forward_pass(self.cameraBuffer, w, h)
-        else:
-            self.forwardPass.setViewport(w, h)
-        if self.rasterizer is None:
-            self.rasterizer = ops.TiledRasterizer(dict(device=self.device, forwardPass=self.forwardPass, format="rgba8unorm"))
-        if self.backwardPass is None:
-            self.backwardPass = ops.TiledBackwardPass(self.device, self.pointCloud, dict(viewportWidth=w, viewportHeight=h, trainingConfig=self.trainingConfig))
+        for s in self._train_sets:
+            s.forwardPass.setViewport(w, h)
+            s.backwardPass.setViewport(w, h)
+        while len(self._train_sets) < self._op_sets:
+            self._train_sets.append(self._new_pass_set(self.cameraBuffer, w, h, backward=True))
             self._gradient_output_applied = None  # (a fresh pass writes the packed gradient, the C ABI's default: _apply_gradient_output decides)
-        else:
-            self.backwardPass.setViewport(w, h)
-        for more in self._more_op_sets:
-            more[0].setViewport(w, h)
-            more[2].setViewport(w, h)
-        while len(self._more_op_sets) < self._op_sets - 1:
-            fw = self._new_forward_pass(self.cameraBuffer, w, h)
-            self._more_op_sets.append([fw, ops.TiledRasterizer(dict(device=self.device, forwardPass=fw, format="rgba8unorm")),
-                                       ops.TiledBackwardPass(self.device, self.pointCloud, dict(viewportWidth=w, viewportHeight=h, trainingConfig=self.trainingConfig))])
         if self.optimizer is not None and self.world_size * self.views_per_rank == 1:
             # a step whose tile-entry list overflowed is skipped on the device (and reported by the next synchronize)
-            self.optimizer.setGuard(self.forwardPass.getStatsBuffer(), 8)
+            self.optimizer.setGuard(self._train_sets[0].forwardPass.getStatsBuffer(), 8)
 
     def ensureMetricsPipelines(self, baseWidth: int, baseHeight: int) -> tuple[int, int]:
         down = max(1, int(self.densifyPruneConfig["metricDownscale"]))
         w, h = max(1, baseWidth // down), max(1, baseHeight // down)
-        if self.metricsForwardPass and self.metricsViewportWidth == w and self.metricsViewportHeight == h:
+        if self._metric_sets and self.metricsViewportWidth == w and self.metricsViewportHeight == h:
             return w, h
-        for name in ("metricsForwardPass", "metricsRasterizer", "metricsPass"):
-            op = getattr(self, name)
-            if op is not None:
-                op.destroy()
-            setattr(self, name, None)
-        self._destroy_more_metric_sets()
+        destroy_pass_sets(self._metric_sets)
+        self._metric_sets = []
         self.metricsViewportWidth, self.metricsViewportHeight = w, h
-        self.metricsForwardPass = self._new_forward_pass(self.metricsCameraBuffer, w, h)
-        self.metricsRasterizer = ops.TiledRasterizer(dict(device=self.device, forwardPass=self.metricsForwardPass, format="rgba8unorm"))
-        self.metricsPass = ops.TiledBackwardPass(self.device, self.pointCloud, dict(viewportWidth=w, viewportHeight=h, trainingConfig=self.trainingConfig))
-        self.metricsTarget = self.device.createBuffer(4 * w * h, "metrics-gt-downsampled")
+        self._metric_set(0)
         return w, h
 
-    def _metric_set(self, k: int) -> tuple:
-        """(forwardPass, rasterizer, metricsPass, downsampled-GT buffer, camera buffer) of metric lane ``k``; sets 1.. are built on first use."""
-        if k == 0:
-            return self.metricsForwardPass, self.metricsRasterizer, self.metricsPass, self.metricsTarget, self.metricsCameraBuffer
+    def _metric_set(self, k: int) -> PassSet:
+        """The pass set of metric lane ``k`` (``backwardPass``: its metric pass), at the metrics viewport; built on first use.  Set 0 renders through
+        the trainer's ``metricsCameraBuffer``, the others through a camera block of their own."""
         w, h = self.metricsViewportWidth, self.metricsViewportHeight
-        while len(self._more_metric_sets) < k:
-            cam = self.device.createBuffer(272, "metrics camera uniform")
-            fw = self._new_forward_pass(cam, w, h)
-            self._more_metric_sets.append([fw, ops.TiledRasterizer(dict(device=self.device, forwardPass=fw, format="rgba8unorm")),
-                                           ops.TiledBackwardPass(self.device, self.pointCloud, dict(viewportWidth=w, viewportHeight=h, trainingConfig=self.trainingConfig)),
-                                           self.device.createBuffer(4 * w * h, "metrics-gt-downsampled"), cam])
-        return tuple(self._more_metric_sets[k - 1])
+        while len(self._metric_sets) <= k:
+            own = len(self._metric_sets) > 0
+            cam = self.device.createBuffer(272, "metrics camera uniform") if own else self.metricsCameraBuffer
+            s = self._new_pass_set(cam, w, h, backward=True)
+            s.target, s.cameraBuffer, s.ownsCamera = self.device.createBuffer(4 * w * h, "metrics-gt-downsampled"), cam, own
+            self._metric_sets.append(s)
+        return self._metric_sets[k]
 
     @staticmethod
     def metrics_camera(camera: np.ndarray, width: int, height: int) -> np.ndarray:
@@ -451,11 +459,9 @@ class Trainer:
         return out
 
     # ------------------------------------------------------------------ one training step
-    def _ops_of(self, op_set: int) -> tuple:
-        return tuple(self._more_op_sets[op_set - 1]) if op_set > 0 else (self.forwardPass, self.rasterizer, self.backwardPass)
-
     def _encode_view(self, encoder, index: int, op_set: int = 0, geometry: bool = True, projected: bool = False) -> None:
-        forwardPass, rasterizer, backwardPass = self._ops_of(op_set)
+        s = self._train_sets[op_set]
+        forwardPass, rasterizer, backwardPass = s.forwardPass, s.rasterizer, s.backwardPass
         image = self.images[index]
         cam = self._camera_buffers[index]  # camera.set_preset + update_buffer (trainer.ts:583-586): the view's resident block
         forwardPass.setCameraBuffer(cam)
@@ -507,8 +513,6 @@ class Trainer:
         return self.maxTileEntries or self._grown_tile_entries
 
     def _grow_tile_entry_capacity(self, error) -> bool:
-        import re
-        import warnings
         if self.maxTileEntries != 0 or not self.device.handle:
             return False
         mine = self._own_overflow(error) or []   # (a report about other owners' passes only never gets here: _wait / _synchronize)
@@ -525,13 +529,7 @@ class Trainer:
             pass  # (a step still in flight overflowed as well)
         self._invalidate_command_buffers()
         # forward passes own the lists: every pass set is rebuilt around lists of the new size (as a cloud the passes cannot follow rebuilds them)
-        for name in self._OP_NAMES:
-            if name != "optimizer" and getattr(self, name) is not None:
-                getattr(self, name).destroy()
-                setattr(self, name, None)
-        self._destroy_more_op_sets()
-        self._destroy_more_metric_sets()
-        self._gradient_output_applied = None
+        self._destroy_pass_sets()
         self.ensurePipelines(self.lastViewportWidth, self.lastViewportHeight)
         for fw in self._forward_passes():
             fw.setDcSource(self._dc_words)
@@ -625,7 +623,7 @@ class Trainer:
     def _step_single_view(self, view: int) -> None:
         """The reference's step (trainer.ts:603-645): one view, Adam straight from the packed fp16 gradients."""
         self._apply_gradient_output()
-        tileCounts = self.forwardPass.getResources()["tileCountsBuffer"]
+        tileCounts = self._train_sets[0].forwardPass.getResources()["tileCountsBuffer"]
 
         def encode(encoder):
             if self.fuse_geometry_adam:  # K1..K16, then K17 + Adam + re-pack in one pass over the Gaussians
@@ -675,7 +673,7 @@ class Trainer:
         the previous group's K17 -- bandwidth- and latency-bound -- execute beside the other groups' rasterization kernels; each view
         waits only for its group's K1, each K17 only for its group's views."""
         dev, L = self.device, self._lanes
-        sets = [self._ops_of(k) for k in range(len(mine))]
+        sets = self._train_sets[:len(mine)]
         cams = [self._camera_buffers[v] for v in mine]
         lanes = L > 1 and self.use_command_buffers and all(("viewp", v, k) in self._cmd_cache for k, v in enumerate(mine))
         U = L if L < ops.MAX_LANES else 0          # the lane of the batched launches
@@ -688,7 +686,7 @@ class Trainer:
             for gi, grp in enumerate(groups):   # every group's projection first, back to back on the batched launches' lane
                 if lanes:
                     dev.selectLane(U)
-                ops.projectViews([sets[k][0] for k in grp], [cams[k] for k in grp], self.pointCloud)
+                ops.projectViews([sets[k].forwardPass for k in grp], [cams[k] for k in grp], self.pointCloud)
                 if lanes:
                     dev.laneMark(U, gi)
             for gi, grp in enumerate(groups):
@@ -701,7 +699,7 @@ class Trainer:
                         dev.laneOrder(U, k % L)      # the group's K17 follows its views (and the earlier groups' K17: lane order)
                 if lanes:
                     dev.selectLane(U)
-                ops.geometryViews([sets[k][2] for k in grp], [cams[k] for k in grp], [sets[k][0] for k in grp], self._dp_grad, self._dp_visible, self._dp_flag,
+                ops.geometryViews([sets[k].backwardPass for k in grp], [cams[k] for k in grp], [sets[k].forwardPass for k in grp], self._dp_grad, self._dp_visible, self._dp_flag,
                                   self.pointCloud, continues=gi > 0)
         finally:
             if lanes:
@@ -721,7 +719,7 @@ class Trainer:
                 dev.laneOrder(s, 0)  # every lane starts behind whatever lane 0 holds (the previous step's Adam, a densify rebuild)
             for k, v in enumerate(mine):
                 s = k % L
-                forwardPass, _, backwardPass = self._ops_of(s)
+                forwardPass, backwardPass = self._train_sets[s].forwardPass, self._train_sets[s].backwardPass
                 if lanes:
                     dev.selectLane(s)
                 self._run(("view", v, s), lambda encoder, v=v, s=s: self._encode_view(encoder, v, s, geometry=False))
@@ -759,11 +757,9 @@ class Trainer:
     def _metric_overflow(self):
         """The capacity report of this rank's metric forward passes (their sticky words are consumed), or None.  Synchronises."""
         found = None
-        for fw in [self.metricsForwardPass] + [more[0] for more in self._more_metric_sets]:
-            if fw is None:
-                continue
+        for s in self._metric_sets:
             try:
-                fw.check()
+                s.forwardPass.check()
             except ops.CapacityError as e:
                 found = found or e
         return found
@@ -780,14 +776,10 @@ class Trainer:
         return int(self._agree_word.read(np.uint32, 1)[0]) != 0
 
     def _own_overflow(self, error) -> Optional[list]:
-        """The entries needed by THIS trainer's passes among those a capacity report names (csrc/api.hip: deferred_checks names every pass that
+        """What THIS trainer's passes needed (entries) among the passes a capacity report names (csrc/api.hip: deferred_checks names every pass that
         overflowed), ``[]`` if it names only other owners' passes, ``None`` if it names none (a step skipped on every rank)."""
-        import re
-        named = re.findall(r"(\d+) entries needed, max_tile_entries = \d+ \(forward pass (0x[0-9a-fA-F]+)\)", str(error))
-        if not named:
-            return None
-        own = {int(fw.handle.value or 0) for fw in self._forward_passes()}
-        return [int(n) for n, h in named if int(h, 16) in own]
+        mine, others = ops.CapacityReports.split(error, (int(fw.handle.value or 0) for fw in self._forward_passes()))
+        return [o.needed for o in mine] if mine or others else None
 
     def _not_ours(self, error) -> bool:
         """True (after saying so once) for a capacity report about passes this trainer does not own -- a Viewer rendering the same cloud on this
@@ -796,7 +788,6 @@ class Trainer:
             return False
         self.device.capacityReports.post(error)   # (for the passes' owner: it looks there at its own next wait)
         if not self._foreign_overflow_warned:
-            import warnings
             warnings.warn(f"a forward pass that is not this trainer's overflowed its tile-entry lists ({error}); its owner has to enlarge them", RuntimeWarning, stacklevel=4)
             self._foreign_overflow_warned = True
         return True
@@ -865,15 +856,13 @@ class Trainer:
             except ops.CapacityError:
                 pass  # (a deferred report about a step of a trainer that is going away)
         self._invalidate_command_buffers()
-        for name in self._OP_NAMES + ("densifyPrune",):
-            op = getattr(self, name, None)
+        self._destroy_pass_sets()
+        self._destroy_eval_sets()
+        for op in (self.optimizer, self.densifyPrune):
             if op is not None:
                 op.destroy()
-            setattr(self, name, None)
-        self._destroy_more_op_sets()
-        self._destroy_more_metric_sets()
-        self._destroy_eval_sets()
-        self._dp_grad = self._dp_visible = self._dp_rows = self._dp_flag = self.metricsTarget = None
+        self.optimizer = self.densifyPrune = None
+        self._dp_grad = self._dp_visible = self._dp_rows = self._dp_flag = None
         self._camera_buffers = []
         self._eval_camera_buffers = []
         self.pointCloud = None
@@ -890,18 +879,15 @@ class Trainer:
         self._eval_camera_buffers = [self.device.bufferFrom(np.asarray(c["camera"], np.float32)) for c in self.evalCameras]
 
     def _destroy_eval_sets(self) -> None:
-        for fw, rast in self._eval_sets.values():
-            rast.destroy()
-            fw.destroy()
+        destroy_pass_sets(self._eval_sets.values())
         self._eval_sets = {}
 
-    def _eval_set(self, width: int, height: int, cameraBuffer) -> tuple:
-        """evaluate's (forward pass, rasterizer) for one image size: built through ``_new_forward_pass`` (the live SH-DC words, this trainer's
+    def _eval_set(self, width: int, height: int, cameraBuffer) -> PassSet:
+        """evaluate's pass set (no backward pass) for one image size: built through ``_new_forward_pass`` (the live SH-DC words, this trainer's
         long-list settings), with lists of ``_eval_tile_entries`` if an evaluation view has outgrown the training passes' size.  Never a guard."""
         key = (int(width), int(height))
         if key not in self._eval_sets:
-            fw = self._new_forward_pass(cameraBuffer, key[0], key[1], self._eval_tile_entries or self.evalMaxTileEntries or None)
-            self._eval_sets[key] = (fw, ops.TiledRasterizer(dict(device=self.device, forwardPass=fw, format="rgba8unorm")))
+            self._eval_sets[key] = self._new_pass_set(cameraBuffer, key[0], key[1], backward=False, max_tile_entries=self._eval_tile_entries or self.evalMaxTileEntries or None)
         return self._eval_sets[key]
 
     def _eval_follow_cloud(self) -> None:
@@ -909,17 +895,17 @@ class Trainer:
         if self._eval_long_lists != self.longLists:
             self._destroy_eval_sets()
             self._eval_long_lists = None if self.longLists is None else dict(self.longLists)
-        for fw, _ in list(self._eval_sets.values()):
-            if fw.pointCloud is not self.pointCloud and not fw.setPointCloud(self.pointCloud):
+        for s in list(self._eval_sets.values()):
+            if s.forwardPass.pointCloud is not self.pointCloud and not s.forwardPass.setPointCloud(self.pointCloud):
                 self._destroy_eval_sets()   # (another SH degree: built anew below)
                 break
-        for fw, _ in self._eval_sets.values():
-            fw.setDcSource(self._dc_words)
+        for s in self._eval_sets.values():
+            s.forwardPass.setDcSource(self._dc_words)
 
     def _eval_overflow(self) -> Optional[int]:
         """Waits for the evaluation renders; the entries the largest overflowing one needed, or None.  A report that also names passes of another
         owner (a Viewer on this device) is left for that owner (ops.CapacityReports)."""
-        own = {int(fw.handle.value or 0) for fw, _ in self._eval_sets.values()}
+        own = {int(s.forwardPass.handle.value or 0) for s in self._eval_sets.values()}
         try:
             self.device.synchronize()
             err = self.device.capacityReports.take(own) if self.device.capacityReports.pending else None
@@ -927,16 +913,12 @@ class Trainer:
             err = e
         if err is None:
             return None
-        import re
-        named = re.findall(r"(\d+) entries needed, max_tile_entries = \d+ \(forward pass (0x[0-9a-fA-F]+)\)", str(err))
-        mine = [int(n) for n, h in named if int(h, 16) in own]
-        if ops.CapacityReports.passes_named(err) - own:
+        mine, others = ops.CapacityReports.split(err, own)
+        if others:
             self.device.capacityReports.post(err)
-        if not mine:
-            if ops.CapacityReports.passes_named(err):
-                return None
+        if not mine and not others:
             raise err
-        return max(mine)
+        return max(o.needed for o in mine) if mine else None
 
     def evaluate(self, viewIds: Optional[list] = None, split: str = "eval") -> dict:
         """PSNR and SSIM of the current model on the evaluation views (``split="eval"``, ``setEvaluationViews``) or on training views
@@ -947,7 +929,6 @@ class Trainer:
         read back once at the end.  A view whose tile-entry list overflowed is rendered again with larger lists -- never reported from a truncated
         render.  Training is untouched: no RNG draw, no training pass, no recording dropped; a trainer that evaluates every few steps follows the
         same trajectory as one that never does.  Per rank with ``world_size > 1`` (no collective)."""
-        import warnings
         if split not in ("eval", "train"):
             raise ValueError(f"evaluate: split must be 'eval' or 'train', not {split!r}")
         if self.pointCloud is None:
@@ -971,7 +952,8 @@ class Trainer:
             self._eval_follow_cloud()
             for i, v in enumerate(ids):
                 im, w, h = imgs[v], int(imgs[v]["width"]), int(imgs[v]["height"])
-                fw, rast = self._eval_set(w, h, bufs[v])
+                s = self._eval_set(w, h, bufs[v])
+                fw, rast = s.forwardPass, s.rasterizer
                 fw.setCameraBuffer(bufs[v])
                 fw.encode(None)
                 rast.encode(None, w, h)
@@ -981,7 +963,7 @@ class Trainer:
             needed = self._eval_overflow()
             if needed is None:
                 break
-            now = max([int(fw.getResources()["maxTileEntries"]) for fw, _ in self._eval_sets.values()] + [self._eval_tile_entries])
+            now = max([int(s.forwardPass.getResources()["maxTileEntries"]) for s in self._eval_sets.values()] + [self._eval_tile_entries])
             new = min(max(2 * now, int(needed * 1.5)), 0xFFFFF000)
             if new <= now:
                 raise RuntimeError(f"evaluate: a view needs {needed} tile entries, more than the lists can hold")
@@ -1023,7 +1005,8 @@ class Trainer:
                     continue
                 k = taken % L   # this rank's views in turn on its metric lanes; every lane's pass adds into set 0's counts
                 taken += 1
-                fw, rast, mpass, target, cam = self._metric_set(k)
+                s = self._metric_set(k)
+                fw, rast, mpass, target, cam = s.forwardPass, s.rasterizer, s.backwardPass, s.target, s.cameraBuffer
                 if k > 0:
                     if taken <= L:   # the lane's first view of this event: behind the clear (and whatever else lane 0 holds)
                         mpass.setMetricCountsTarget(counts)

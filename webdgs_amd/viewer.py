@@ -16,7 +16,7 @@ import numpy as np
 
 from . import loaders
 from ._lib import CapacityError
-from .ops import HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer, depthToRGBA8
+from .ops import CapacityReports, HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer, depthToRGBA8
 
 
 def encodePNG(rgba: np.ndarray) -> bytes:
@@ -156,7 +156,6 @@ class Viewer:
         picture; the library reports it), the viewer's passes are rebuilt around larger lists and ``rerender()`` encodes the frame again.  (A report
         about this viewer's pass may have been consumed by another owner's wait -- a Trainer on the same device: it was left in
         ``device.capacityReports``, and is answered here.)"""
-        import re
         for _ in range(4):  # this viewer's own pass: its word is consumed by its own check
             if self.forwardPass is None:
                 break
@@ -167,11 +166,10 @@ class Viewer:
                     raise left
                 break
             except CapacityError as e:
-                own = int(self.forwardPass.handle.value or 0)   # (a report names up to four passes: this viewer's line)
-                named = [(int(n), int(c)) for n, c, h in re.findall(r"(\d+) entries needed, max_tile_entries = (\d+) \(forward pass (0x[0-9a-fA-F]+)\)", str(e)) if int(h, 16) == own]
-                if not named:
+                mine, _ = CapacityReports.split(e, [int(self.forwardPass.handle.value or 0)])   # (a report names up to four passes: this viewer's line)
+                if not mine:
                     raise
-                self._tile_entries = min(max(2 * named[0][1], int(named[0][0] * 1.5)), 0xFFFFF000)
+                self._tile_entries = min(max(2 * mine[0].capacity, int(mine[0].needed * 1.5)), 0xFFFFF000)
                 self._build_passes()
                 rerender()
 
