@@ -325,6 +325,13 @@ static napi_value depthToRgba8(napi_env env, napi_callback_info info) {  // (dev
                                          (float)get_f64(env, argv[5]), get_ptr(env, argv[6])));
     return js_undefined(env);
 }
+// Per-Gaussian render contribution (include/webdgs.h: wdgs_tiled_rasterizer_encode_contribution, wdgs_contribution_rule,
+// wdgs_densify_prune_encode_contribution_decision; no reference counterpart)
+static napi_value tiledRasterizerEncodeContribution(napi_env env, napi_callback_info info) {  // (op, statsPtr): adds into the caller's records
+    ARGS(2);
+    WDGS_OK_OR_THROW(wdgs_tiled_rasterizer_encode_contribution((wdgs_tiled_rasterizer*)get_ptr(env, argv[0]), get_ptr(env, argv[1])));
+    return js_undefined(env);
+}
 static napi_value bufferClear(napi_env env, napi_callback_info info) {  // encoder.clearBuffer: (device, ptr, byteLength)
     ARGS(3);
     WDGS_OK_OR_THROW(wdgs_memset((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), 0, (size_t)get_f64(env, argv[2])));
@@ -564,6 +571,30 @@ static napi_value densifyStage(napi_env env, napi_callback_info info) {
     set_prop(env, o, "actionBuffer", make_ptr(env, p.action_buffer)); set_prop(env, o, "outCountBuffer", make_ptr(env, p.out_count_buffer));
     set_prop(env, o, "outOffsetBuffer", make_ptr(env, p.out_offset_buffer)); set_prop(env, o, "outTotalBuffer", make_ptr(env, p.out_total_buffer));
     set_prop(env, o, "maxOutPoints", make_u32(env, max_out));
+    return o;
+}
+static napi_value densifyContributionDecision(napi_env env, napi_callback_info info) {
+    // (op, numPoints, statsPtr, minMaxWeight, minWeightSum, minPixels, minSumQ: number or bigint) -> the pass's work buffers, as densifyStage
+    ARGS(7);
+    wdgs_densify_prune* op = (wdgs_densify_prune*)get_ptr(env, argv[0]);
+    const uint32_t n = get_u32(env, argv[1]);
+    wdgs_contribution_rule rule;
+    rule.min_max_weight = (float)get_f64(env, argv[3]);
+    rule.min_weight_sum = (float)get_f64(env, argv[4]);
+    rule.min_pixels = get_u32(env, argv[5]);
+    napi_valuetype t;
+    napi_typeof(env, argv[6], &t);
+    uint64_t q = 0;
+    bool lossless = true;
+    if (t == napi_bigint) napi_get_value_bigint_uint64(env, argv[6], &q, &lossless); else q = (uint64_t)get_f64(env, argv[6]);
+    rule.min_sum_q = q;
+    WDGS_OK_OR_THROW(wdgs_densify_prune_encode_contribution_decision(op, n, get_ptr(env, argv[2]), &rule));
+    wdgs_densify_prepared p;
+    WDGS_OK_OR_THROW(wdgs_densify_prune_get_buffers(op, &p));
+    napi_value o; napi_create_object(env, &o);
+    set_prop(env, o, "actionBuffer", make_ptr(env, p.action_buffer)); set_prop(env, o, "outCountBuffer", make_ptr(env, p.out_count_buffer));
+    set_prop(env, o, "outOffsetBuffer", make_ptr(env, p.out_offset_buffer)); set_prop(env, o, "outTotalBuffer", make_ptr(env, p.out_total_buffer));
+    set_prop(env, o, "maxOutPoints", make_u32(env, p.max_out_points));
     return o;
 }
 static napi_value densifyReadTotal(napi_env env, napi_callback_info info) {
@@ -900,6 +931,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(optimizerCreate); EXPORT_FN(optimizerStep); EXPORT_FN(optimizerGetIteration); EXPORT_FN(optimizerDestroy);
     EXPORT_FN(tiledForwardSet); EXPORT_FN(tiledForwardCheck); EXPORT_FN(tiledForwardSetLongLists); EXPORT_FN(tiledForwardLongListStats); EXPORT_FN(tiledRasterizerBlit); EXPORT_FN(bufferClear);
     EXPORT_FN(tiledRasterizerEncodeDepth); EXPORT_FN(tiledRasterizerGetDepth); EXPORT_FN(depthToRgba8);
+    EXPORT_FN(tiledRasterizerEncodeContribution); EXPORT_FN(densifyContributionDecision);
     EXPORT_FN(encoderBegin); EXPORT_FN(encoderFinish); EXPORT_FN(queueSubmit); EXPORT_FN(commandBufferDestroy); EXPORT_FN(queueOnSubmittedWorkDone);
     EXPORT_FN(tiledBackwardMetric); EXPORT_FN(tiledBackwardGet); EXPORT_FN(downsampleRGBA8); EXPORT_FN(imageSSE); EXPORT_FN(imageSSIM);
     EXPORT_FN(optimizerStateSizes); EXPORT_FN(optimizerCreateWithState); EXPORT_FN(optimizerState); EXPORT_FN(optimizerHyperparameters);

@@ -1,5 +1,5 @@
 // Typings of trainer.js: the public surface of the reference's Trainer (src/trainer.ts:177-566).
-import { AdamHyperparameters, HipBuffer, HipDevice, OptimizerInitialState, PointCloud, TrainingConfig } from './webdgs_hip';
+import { AdamHyperparameters, ContributionRecords, HipBuffer, HipDevice, OptimizerInitialState, PointCloud, TrainingConfig } from './webdgs_hip';
 import { CameraData } from './loaders';
 import { LoadedImage } from './images';
 import { Exchange } from './parallel';
@@ -67,6 +67,10 @@ export class Trainer {
   /** PSNR (exact SSE kernel) and SSIM (imageSSIM) of the current model on the evaluation views ('eval') or training views ('train'); drains the
    *  pipeline, leaves the training trajectory untouched. */
   evaluate(viewIds?: number[] | null, split?: 'eval' | 'train'): EvaluationResult;
+  /** Per-Gaussian render contribution accumulated over the views (default: all training views); no reference counterpart. */
+  contributionStats(viewIds?: number[] | null, split?: 'eval' | 'train'): ContributionRecords & { views: number[] };
+  /** Contribution-based pruning: kept iff every criterion given is met; fraction f prunes the Gaussians below the k-th smallest sum_q, k = floor(f N). */
+  pruneByContribution(options: { minMaxWeight?: number; minWeightSum?: number; minPixels?: number; fraction?: number; viewIds?: number[] | null }): { before: number; after: number; pruned: number };
   /** Tile-entry lists of evaluate's own passes (0: what the training passes get); an overflowing view grows them and is rendered again. */
   evalMaxTileEntries: number;
   getTrainingConfig(): TrainingConfig; setTrainingConfig(next: Partial<TrainingConfig>): void;

@@ -773,27 +773,11 @@ class Trainer {
     try { this.drain(); } catch (e) { if (!this.growTileEntryCapacity(e)) throw e; }
     const n = ids.length, slots = Math.max(1, n);
     const out = this.device.createBuffer({ size: 16 * slots, label: 'evaluation sse + ssim' });
-    while (n) {
-      this.evalFollowCloud();
-      ids.forEach((v, i) => {
-        const im = imgs[v], w = im.width, h = im.height;
-        const { forwardPass: fw, rasterizer: rast } = this.evalSet(w, h, bufs[v]);
-        fw.setCameraBuffer(bufs[v]);
-        fw.encode(null);
-        rast.encode(null, w, h);
-        const pred = rast.getOutputTextureView();
-        hip.encodeImageSSE(this.device, pred, im.texture, w * h, this.device.view(out.ptr + BigInt(8 * i), 8));
-        hip.encodeImageSSIM(this.device, pred, im.texture, w, h, this.device.view(out.ptr + BigInt(8 * (slots + i)), 8));
-      });
-      const needed = this.evalOverflow();
-      if (needed === null) break;
-      const now = Math.max(this.evalTileEntries, ...[...this.evalSets.values()].map((s) => Number(s.forwardPass.getResources().maxTileEntries)));
-      const next = Math.min(Math.max(2 * now, Math.floor(needed * 1.5)), 0xFFFFF000);
-      if (next <= now) throw new Error(`evaluate: a view needs ${needed} tile entries, more than the lists can hold`);
-      console.warn(`evaluation tile-entry lists grown from ${now} to ${next} entries after an overflow; the views are rendered again`);
-      this.evalTileEntries = next;
-      this.destroyEvalSets();
-    }
+    this.renderEvalViews(ids, imgs, bufs, (i, v, s, w, h) => {
+      const pred = s.rasterizer.getOutputTextureView();
+      hip.encodeImageSSE(this.device, pred, imgs[v].texture, w * h, this.device.view(out.ptr + BigInt(8 * i), 8));
+      hip.encodeImageSSIM(this.device, pred, imgs[v].texture, w, h, this.device.view(out.ptr + BigInt(8 * (slots + i)), 8));
+    }, null, 'evaluate');
     const raw = n ? this.device.readBuffer(out, 16 * slots) : new ArrayBuffer(16);
     out.destroy();
     const sse = [...new BigUint64Array(raw, 0, n)].map(Number);
@@ -801,6 +785,91 @@ class Trainer {
     const psnr = ids.map((v, i) => hip.psnrFromSSE(sse[i], imgs[v].width * imgs[v].height));
     const mean = (a) => (a.length ? a.reduce((x, y) => x + y, 0) / a.length : NaN);
     return { iteration: this.iteration, views: ids, psnr, ssim, sse, mean_psnr: mean(psnr), mean_ssim: mean(ssim), ms: Date.now() - t0 };
+  }
+
+  /** evaluate's render loop, shared with contributionStats: every view of `ids` through the evaluation pass set of its size, then
+   *  each(i, v, passSet, width, height); after an overflow the lists are grown, restart() is called and ALL views are rendered again. */
+  renderEvalViews(ids, imgs, bufs, each, restart, what) {
+    while (ids.length) {
+      this.evalFollowCloud();
+      ids.forEach((v, i) => {
+        const im = imgs[v], w = im.width, h = im.height;
+        const s = this.evalSet(w, h, bufs[v]);
+        s.forwardPass.setCameraBuffer(bufs[v]);
+        s.forwardPass.encode(null);
+        s.rasterizer.encode(null, w, h);
+        each(i, v, s, w, h);
+      });
+      const needed = this.evalOverflow();
+      if (needed === null) break;
+      const now = Math.max(this.evalTileEntries, ...[...this.evalSets.values()].map((s) => Number(s.forwardPass.getResources().maxTileEntries)));
+      const next = Math.min(Math.max(2 * now, Math.floor(needed * 1.5)), 0xFFFFF000);
+      if (next <= now) throw new Error(`${what}: a view needs ${needed} tile entries, more than the lists can hold`);
+      console.warn(`evaluation tile-entry lists grown from ${now} to ${next} entries after an overflow; the views are rendered again`);
+      this.evalTileEntries = next;
+      this.destroyEvalSets();
+      if (restart) restart();
+    }
+  }
+
+  // ---------------------------------------------------------------- render contribution and contribution-based pruning (no reference counterpart)
+  /** { stats, ids }: the views' contribution records (DESIGN.md section 11) accumulated into one new device buffer. */
+  contributionBuffer(viewIds, split, what) {
+    if (split !== 'eval' && split !== 'train') throw new Error(`${what}: split must be 'eval' or 'train', not ${split}`);
+    if (!this.pointCloud) throw new Error(`${what}: no point cloud`);
+    const [cams, imgs, bufs] = split === 'eval' ? [this.evalCameras, this.evalImages, this.evalCameraBuffers] : [this.trainCameras, this.images, this.cameraBuffers];
+    const ids = viewIds === undefined || viewIds === null ? cams.map((_, i) => i) : viewIds.map((v) => Math.floor(v));
+    for (const v of ids) if (!(v >= 0 && v < cams.length)) throw new RangeError(`${what}: view ${v} of ${cams.length} (${split})`);
+    if (ids.reduce((a, v) => a + imgs[v].width * imgs[v].height, 0) >= 2 ** 32) throw new RangeError(`${what}: the views hold 2^32 pixels or more; the per-Gaussian pixel count is 32 bits wide`);
+    try { this.drain(); } catch (e) { if (!this.growTileEntryCapacity(e)) throw e; }
+    const stats = hip.createContributionBuffer(this.device, this.pointCloud.num_points);
+    try {
+      this.renderEvalViews(ids, imgs, bufs, (i, v, s) => s.rasterizer.encodeContribution(null, stats), () => hip.addon.bufferClear(this.device.handle, stats.ptr, stats.size), what);
+    } catch (e) { stats.destroy(); throw e; }
+    return { stats, ids };
+  }
+  /** How much of each Gaussian the views' images hold: { sum_q, weight_sum, max_weight, pixels, views }, one entry per Gaussian, accumulated over
+   *  the views (default: all training views).  Rendered through evaluate's passes with its isolation (drained pipeline, overflow-and-regrow with the
+   *  records cleared and every view walked again, no random draw, no training pass, no recording dropped).  Same results as the Python host's. */
+  contributionStats(viewIds, split) {
+    const { stats, ids } = this.contributionBuffer(viewIds, split || 'train', 'contributionStats');
+    try { return Object.assign(hip.readContribution(stats, this.pointCloud.num_points), { views: ids }); } finally { stats.destroy(); }
+  }
+  /** Removes the Gaussians the training views need least: kept iff the Gaussian meets every criterion given -- { minMaxWeight, minWeightSum,
+   *  minPixels, fraction, viewIds }; with fraction f, sum_q not below the k-th smallest sum_q, k = floor(f N) (at most k go; ties stay).  Survivors,
+   *  SH rows and optimizer state are compacted in index order, bit for bit, and the cloud is swapped as after a densify event.  { before, after,
+   *  pruned }; pruning nothing or everything (a warning) leaves the cloud as it is.  Single rank only.  Same results as the Python host's. */
+  pruneByContribution(options) {
+    const o = options || {};
+    const minMaxWeight = o.minMaxWeight || 0, minWeightSum = o.minWeightSum || 0, minPixels = o.minPixels || 0, fraction = o.fraction || 0;
+    if (this.worldSize > 1) throw new Error('pruneByContribution: worldSize > 1 is not supported (the replicas would have to agree on the statistics)');
+    if (!(minMaxWeight >= 0 && minWeightSum >= 0 && minPixels >= 0 && fraction >= 0 && fraction < 1)) throw new RangeError('pruneByContribution: the thresholds must be >= 0 and fraction in [0, 1)');
+    if (!(minMaxWeight || minWeightSum || minPixels || fraction)) throw new Error('pruneByContribution: give at least one of minMaxWeight, minWeightSum, minPixels, fraction');
+    if (!this.optimizer || !this.densifyPrune) throw new Error('pruneByContribution: no point cloud');
+    const { stats } = this.contributionBuffer(o.viewIds, 'train', 'pruneByContribution');
+    try {
+      const n = this.pointCloud.num_points, unchanged = { before: n, after: n, pruned: 0 };
+      const rule = { minMaxWeight, minWeightSum, minPixels: Math.floor(minPixels), minSumQ: 0n };
+      const k = Math.floor(fraction * n);
+      if (k > 0) rule.minSumQ = hip.readContribution(stats, n).sum_q.sort()[k - 1];
+      if (!(rule.minMaxWeight || rule.minWeightSum || rule.minPixels || rule.minSumQ)) return unchanged;
+      const dp = this.densifyPrune;
+      dp.ensureSize(n);
+      dp.encodeContributionDecision(null, n, stats, rule);
+      const offsets = dp.encodePrefixSum(null);
+      dp.encodeTotalOut(null);
+      const outN = dp.readTotal();
+      if (outN === n) return unchanged;
+      if (outN === 0) { console.warn('pruneByContribution: the criteria would remove every Gaussian; the cloud is left as it is'); return unchanged; }
+      this.flushPointCloud();   // the rebuild copies the cloud's SH rows: bring the deferred DC halves in first
+      const outPointCloud = hip.allocatePointCloudLike(this.device, this.pointCloud, { numPoints: outN });
+      const outOptimizerState = hip.allocateOptimizerStateBuffers(this.device, outN);
+      dp.encodeScatter(null, { pointCloud: this.pointCloud, optimizerState: this.optimizer.getStateBuffers(), outOffsetBuffer: offsets, outNumPoints: outN,
+        resetNewOptimizerState: false }, { outPointCloud, outOptimizerState });
+      this.synchronize();
+      this.applyPointCloudSwap({ pointCloud: outPointCloud, optimizerInitialState: { iteration: this.optimizer.getIteration(), buffers: outOptimizerState } });
+      return { before: n, after: outN, pruned: n - outN };
+    } finally { stats.destroy(); }
   }
 
   /** Deterministic teardown: command buffers, ops, the buffers this trainer allocated (the device and the exchange belong to the caller). */

@@ -124,6 +124,8 @@ export class TiledRasterizer {
   /** `target` may carry its own `width` / `height` (a canvas of another size); the clear colour is accepted for signature compatibility only. */
   /** Depth images of the frame the last encode rasterized (no reference counterpart); default kinds: ['expected']. */
   encodeDepth(encoder: HipEncoder | null, kinds?: DepthKind | DepthKind[] | number): void;
+  /** Adds the per-Gaussian contribution of the frame the last encode rasterized into `statsBuffer` (no reference counterpart); records. */
+  encodeContribution(encoder: HipEncoder | null, statsBuffer: HipBuffer): void;
   /** f32[W*H] of one kind the last encodeDepth wrote (default 'expected'). */
   getDepthTextureView(kind?: DepthKind): HipBuffer;
   blitToTexture(encoder: HipEncoder | null, target: HipBuffer & { width?: number; height?: number }, clearColor?: { r: number; g: number; b: number; a: number }): void;
@@ -197,6 +199,8 @@ export class DensifyPrunePass {
   setConfig(next: Partial<DensifyPruneConfig>): void; getConfig(): DensifyPruneConfig;
   ensureSize(numPoints: number): void; computeMaxOutPoints(pointCloud: PointCloud): number;
   encodeDecision(encoder: HipEncoder | null, inputs: { pointCloud: PointCloud; metricCountsBuffer?: HipBuffer }): { actionBuffer: HipBuffer; outCountBuffer: HipBuffer };
+  /** Contribution-based pruning's decision (no reference counterpart): kept iff the record meets every non-zero field of the rule. */
+  encodeContributionDecision(encoder: HipEncoder | null, numPoints: number, statsBuffer: HipBuffer, rule: ContributionRule): { actionBuffer: HipBuffer; outCountBuffer: HipBuffer };
   encodePrefixSum(encoder: HipEncoder | null): HipBuffer;
   encodeCapToMax(encoder: HipEncoder | null, outOffsetBuffer: HipBuffer, maxOutPoints: number): void;
   encodeTotalOut(encoder: HipEncoder | null, outOffsetBuffer: HipBuffer | null): HipBuffer;
@@ -221,6 +225,12 @@ export function imagePSNR(device: HipDevice, a: HipBuffer, b: HipBuffer, numPixe
 export function psnrFromSSE(sse: number | bigint, numPixels: number): number;
 export function encodeImageSSE(device: HipDevice, a: HipBuffer, b: HipBuffer, numPixels: number, out: HipBuffer): void;
 export function encodeImageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: number, height: number, out: HipBuffer, map?: HipBuffer | null): void;
+export interface ContributionRule { minMaxWeight?: number; minWeightSum?: number; minPixels?: number; minSumQ?: number | bigint }
+export interface ContributionRecords { sum_q: BigUint64Array; weight_sum: Float64Array; max_weight: Float32Array; pixels: Uint32Array }
+export const CONTRIBUTION_RECORD_BYTES: 16;
+/** One zeroed record { u64 sum_q; u32 max_bits; u32 pixels } per Gaussian, for TiledRasterizer.encodeContribution.  No reference counterpart. */
+export function createContributionBuffer(device: HipDevice, numPoints: number): HipBuffer;
+export function readContribution(buffer: HipBuffer, n: number): ContributionRecords;
 /** A depth image as rgba8 for presentation: inverse depth between near (white) and far (black), depth 0 black.  No reference counterpart. */
 export function depthToRGBA8(device: HipDevice, depth: HipBuffer, width: number, height: number, near: number, far: number, target: HipBuffer): void;
 export function imageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: number, height: number, map?: HipBuffer | null): number;

@@ -228,6 +228,7 @@ class TiledForwardPass {                 // tiled-forward-pass.ts:62
 }
 
 const DEPTH_KINDS = { expected: 1, median: 2, weight_sum: 4 };   // WDGS_DEPTH_*
+const CONTRIBUTION_RECORD_BYTES = 16;   // { u64 sum_q; u32 max_bits; u32 pixels } per Gaussian (include/webdgs.h)
 function depthMask(kinds) {
   if (typeof kinds === 'number') return kinds;
   let mask = 0;
@@ -240,7 +241,7 @@ function depthMask(kinds) {
 
 class TiledRasterizer {                  // tiled-rasterizer.ts:34
   constructor(config) {
-    this.device = config.device; this.destroyed = false; this.w = 0; this.h = 0;
+    this.device = config.device; this.forwardPass = config.forwardPass; this.destroyed = false; this.w = 0; this.h = 0;
     this.handle = addon.tiledRasterizerCreate(config.device.handle, config.forwardPass.nativeHandle);
   }
   encode(_encoder, width, height) { addon.tiledRasterizerEncode(this.handle, width, height); this.w = width; this.h = height; }
@@ -253,6 +254,13 @@ class TiledRasterizer {                  // tiled-rasterizer.ts:34
   encodeDepth(_encoder, kinds) { addon.tiledRasterizerEncodeDepth(this.handle, depthMask(kinds === undefined ? ['expected'] : kinds)); }
   /** f32[W*H] of one kind the last encodeDepth wrote; throws (WDGS_E_STATE) otherwise. */
   getDepthTextureView(kind) { return this.device.view(addon.tiledRasterizerGetDepth(this.handle, depthMask([kind === undefined ? 'expected' : kind])), 4 * this.w * this.h); }
+  /** Adds the per-Gaussian contribution of the frame the last encode rasterized into `statsBuffer` (createContributionBuffer; include/webdgs.h,
+   *  DESIGN.md section 11; no reference counterpart).  Allocates nothing, so it records. */
+  encodeContribution(_encoder, statsBuffer) {
+    const n = this.forwardPass.pointCloud.num_points;
+    if (statsBuffer.size < CONTRIBUTION_RECORD_BYTES * n) throw new Error(`encodeContribution: the statistics buffer holds ${statsBuffer.size} bytes, ${n} Gaussians need ${CONTRIBUTION_RECORD_BYTES * n}`);
+    addon.tiledRasterizerEncodeContribution(this.handle, statsBuffer.ptr);
+  }
   /** blitToTexture(encoder, targetView, clearColor?) (tiled-rasterizer.ts:333-357): `target` is an rgba8 image buffer; it may carry its own
    *  `width` / `height` (a canvas of another size: the blit is a bilinear resample), otherwise it has the rasterizer's size.  The blit covers
    *  the whole target, so the reference's clear colour never shows and is accepted only for signature compatibility. */
@@ -430,6 +438,16 @@ class DensifyPrunePass {                 // densify-prune.ts:75
     const p = this.stage(0, this.numPoints, inputs.pointCloud.gaussian_3d_buffer.ptr, inputs.metricCountsBuffer ? inputs.metricCountsBuffer.ptr : null);
     return { actionBuffer: p.actionBuffer, outCountBuffer: p.outCountBuffer };
   }
+  /** The decision of contribution-based pruning (DESIGN.md section 11; no reference counterpart): a Gaussian is kept iff its record in `statsBuffer`
+   *  meets every non-zero field of `rule` ({ minMaxWeight, minWeightSum, minPixels, minSumQ: number | bigint }).  encodePrefixSum, encodeTotalOut,
+   *  readTotal and encodeScatter then compact the cloud; what this stage keeps is copied bit for bit. */
+  encodeContributionDecision(_encoder, numPoints, statsBuffer, rule) {
+    for (const k of Object.keys(rule)) if (!['minMaxWeight', 'minWeightSum', 'minPixels', 'minSumQ'].includes(k)) throw new Error(`encodeContributionDecision: unknown rule field '${k}'`);
+    if (statsBuffer.size < CONTRIBUTION_RECORD_BYTES * numPoints) throw new Error(`encodeContributionDecision: the statistics buffer holds ${statsBuffer.size} bytes, ${numPoints} Gaussians need ${CONTRIBUTION_RECORD_BYTES * numPoints}`);
+    const p = this.wrap(addon.densifyContributionDecision(this.handle, numPoints, statsBuffer.ptr, rule.minMaxWeight || 0, rule.minWeightSum || 0, rule.minPixels || 0, rule.minSumQ || 0), numPoints);
+    this.numPoints = numPoints;
+    return { actionBuffer: p.actionBuffer, outCountBuffer: p.outCountBuffer };
+  }
   encodePrefixSum(_encoder) { return this.stage(1, this.numPoints).outOffsetBuffer; }
   encodeCapToMax(_encoder, _outOffsetBuffer, maxOutPoints) { this.stage(2, this.numPoints, Math.max(0, Math.floor(maxOutPoints))); }
   encodeTotalOut(_encoder, _outOffsetBuffer) { return this.stage(3, this.numPoints).outTotalBuffer; }
@@ -498,6 +516,25 @@ function imageSSIM(device, a, b, width, height, map) {
  *  (wdgs_depth_to_rgba8).  Stream-ordered; no reference counterpart. */
 function depthToRGBA8(device, depth, width, height, near, far, target) { addon.depthToRgba8(device.handle, depth.ptr, width, height, near, far, target.ptr); }
 
+/** One zeroed 16-byte record { u64 sum_q; u32 max_bits; u32 pixels } per Gaussian, for TiledRasterizer.encodeContribution.  No reference counterpart. */
+function createContributionBuffer(device, numPoints) {
+  const buf = device.createBuffer({ size: CONTRIBUTION_RECORD_BYTES * Math.max(1, numPoints), label: 'contribution' });
+  addon.bufferClear(device.handle, buf.ptr, buf.size);
+  return buf;
+}
+/** The first n records: { sum_q: BigUint64Array, weight_sum: Float64Array (sum_q * 2^-24), max_weight: Float32Array, pixels: Uint32Array }. */
+function readContribution(buffer, n) {
+  const raw = buffer.device.readBuffer(buffer, CONTRIBUTION_RECORD_BYTES * n);
+  const q = new BigUint64Array(raw), w = new Uint32Array(raw);
+  const out = { sum_q: new BigUint64Array(n), weight_sum: new Float64Array(n), max_weight: new Float32Array(n), pixels: new Uint32Array(n) };
+  const bits = new Uint32Array(out.max_weight.buffer);
+  for (let i = 0; i < n; i++) {
+    out.sum_q[i] = q[2 * i]; out.weight_sum[i] = Number(q[2 * i]) * 2 ** -24;   // (sum_q < 2^53: exact)
+    bits[i] = w[4 * i + 2]; out.pixels[i] = w[4 * i + 3];
+  }
+  return out;
+}
+
 /** The C-ABI communicator (wdgs_comm_*, include/webdgs.h): RCCL queued on the device's stream by the library itself -- the transport of the
  *  data-parallel step for a host without torch.distributed.  `uniqueId` (ArrayBuffer, 128 bytes) comes from Communicator.uniqueId() on rank 0 and
  *  reaches the other ranks over any host channel (parallel.js ships it through a file). */
@@ -520,6 +557,6 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

@@ -273,6 +273,16 @@ int wdgs_tiled_rasterizer_get_depth(wdgs_tiled_rasterizer* op, uint32_t kind, vo
  * at the pixel) is black.  Requires 0 < near < far < inf.  Writes width*height pixels of any rgba8 buffer.  No reference counterpart. */
 int wdgs_depth_to_rgba8(wdgs_device* dev, const void* depth_f32_dev, uint32_t width, uint32_t height, float near_z, float far_z, void* rgba8_dev);
 
+/* Per-Gaussian render contribution.  No reference counterpart: the reference prunes by opacity alone.
+ * Attributes the weights w = alpha (1 - A) of the frame the last encode rasterized -- the active (pixel, record) pairs of section 10, w with the
+ * compositing weight's bits -- to their Gaussians.  `stats_dev` holds one 16-byte record per Gaussian of the forward pass, 16-byte aligned:
+ *     { uint64 sum_q; uint32 max_bits; uint32 pixels; }
+ * sum_q += (uint32)(w * 2^24) (truncating; the weight sum is sum_q * 2^-24), max_bits = max(max_bits, the f32 bits of w), pixels += 1 (modulo 2^32)
+ * per active pair; a NaN weight adds to none.  The call ADDS into the buffer, which the caller owns and clears: views accumulate, and the result does
+ * not depend on the order of views, waves or launches (integer atomics only).  Nothing is allocated, so the call records into a command buffer.
+ * WDGS_E_STATE before encode, and when the forward pass is in point-cloud render mode (no weights); WDGS_E_INVALID on a null or misaligned pointer. */
+int wdgs_tiled_rasterizer_encode_contribution(wdgs_tiled_rasterizer* op, void* stats_dev);
+
 /* ---------------------------------------------------------------- TiledBackwardPass
  * Replaces `new TiledBackwardPass(device, pointCloud, config)` (renderers/tiled-backward-pass.ts:136-140, config 27-34,
  * TrainingConfig 19-25), .encode (592-740), .computeLossOnly (383), .computeMetricMap (425), .computeMetricCounts (514),
@@ -522,6 +532,20 @@ int wdgs_densify_prune_compute_max_out_points(wdgs_densify_prune* op, uint32_t n
 int wdgs_densify_prune_get_buffers(wdgs_densify_prune* op, wdgs_densify_prepared* out);
 /* Reads the 4-byte total back (the one device->host crossing of the densify path, trainer.ts:440-458). */
 int wdgs_densify_prune_read_total(wdgs_densify_prune* op, uint32_t* total_out);
+/* Contribution-based pruning.  No reference counterpart.  A decision stage in place of encode_decision that reads the
+ * records wdgs_tiled_rasterizer_encode_contribution accumulated: a Gaussian is KEPT iff it meets every non-zero field of the rule -- max weight >=
+ * min_max_weight, sum_q * 2^-24 >= min_weight_sum (compared in float64), pixels >= min_pixels, sum_q >= min_sum_q.  Writes action_buffer (0 keep,
+ * 3 prune) and out_count_buffer (1 or 0); encode_prefix_sum, encode_total_out, read_total and encode_scatter then compact the cloud, the SH rows
+ * and the optimizer arrays.  A Gaussian this stage keeps is copied by the next encode_scatter bit for bit (the densify decision's survivors have
+ * their opacity clamped and its moments reset, densify-prune-scatter; here nothing but the pruned rows may change).  An all-zero rule is
+ * WDGS_E_INVALID. */
+typedef struct wdgs_contribution_rule {
+    float min_max_weight;
+    float min_weight_sum;
+    uint32_t min_pixels;
+    uint64_t min_sum_q;
+} wdgs_contribution_rule;
+int wdgs_densify_prune_encode_contribution_decision(wdgs_densify_prune* op, uint32_t num_points, const void* stats_dev, const wdgs_contribution_rule* rule);
 /* encodeScatter: out_num_points must equal the size of the output buffers (the reference throws otherwise,
  * densify-prune.ts:478-480).  in_state/out_state may both be NULL (point cloud only). */
 int wdgs_densify_prune_encode_scatter(wdgs_densify_prune* op, uint32_t in_points, const void* in_gaussians_dev, const void* in_sh_dev,

@@ -86,6 +86,10 @@ class DensifyPrepared(C.Structure):
                 ("max_out_points", C.c_uint32)]
 
 
+class ContributionRule(C.Structure):
+    _fields_ = [("min_max_weight", C.c_float), ("min_weight_sum", C.c_float), ("min_pixels", C.c_uint32), ("min_sum_q", C.c_uint64)]
+
+
 _P = C.c_void_p
 _U = C.c_uint32
 _I = C.c_int
@@ -121,6 +125,7 @@ SIGNATURES = {
     "wdgs_host_free": (_I, [_P]),
     "wdgs_tiled_rasterizer_blit": (_I, [_P, _P, _U, _U]),
     "wdgs_densify_prune_encode_decision": (_I, [_P, _U, _P, _P]),
+    "wdgs_densify_prune_encode_contribution_decision": (_I, [_P, _U, _P, C.POINTER(ContributionRule)]),
     "wdgs_densify_prune_encode_prefix_sum": (_I, [_P, _U]),
     "wdgs_densify_prune_encode_cap_to_max": (_I, [_P, _U, _U]),
     "wdgs_densify_prune_encode_total_out": (_I, [_P, _U]),
@@ -200,6 +205,7 @@ SIGNATURES = {
     "wdgs_tiled_rasterizer_encode_depth": (_I, [_P, _U]),
     "wdgs_tiled_rasterizer_get_depth": (_I, [_P, _U, C.POINTER(_P)]),
     "wdgs_depth_to_rgba8": (_I, [_P, _P, _U, _U, _F, _F, _P]),
+    "wdgs_tiled_rasterizer_encode_contribution": (_I, [_P, _P]),
     "wdgs_tiled_backward_create": (_I, [_P, C.POINTER(TiledBackwardConfig), C.POINTER(_P)]),
     "wdgs_tiled_backward_resize": (_I, [_P, _U]),
     "wdgs_tiled_backward_destroy": (_I, [_P]),

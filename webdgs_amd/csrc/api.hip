@@ -1161,6 +1161,24 @@ int wdgs_tiled_rasterizer_encode_depth(wdgs_tiled_rasterizer* op, uint32_t kinds
     op->depth_encoded = kinds;
     return WDGS_OK;
 }
+// Per-Gaussian contribution of the frame the last encode composited (contrib.hip; no counterpart in the reference).  depth's walk and arguments without
+// the depth words; the records are the caller's, added to, and nothing is allocated: the call records.
+int wdgs_tiled_rasterizer_encode_contribution(wdgs_tiled_rasterizer* op, void* stats_dev) {
+    WDGS_REQUIRE(op, WDGS_E_INVALID, "wdgs_tiled_rasterizer_encode_contribution: null op");
+    WDGS_REQUIRE(stats_dev && ((uintptr_t)stats_dev & 15u) == 0u, WDGS_E_INVALID,
+                 "wdgs_tiled_rasterizer_encode_contribution: the statistics buffer must be non-null and 16-byte aligned (got %p)", stats_dev);
+    wdgs_tiled_forward* f = op->fwd;
+    WDGS_REQUIRE(op->encoded && f->encoded && op->ranges_used, WDGS_E_STATE,
+                 "TiledRasterizer.encodeContribution before encode: the weights are those of the frame encode rasterized");
+    WDGS_REQUIRE(op->width == f->cfg.viewport_width && op->height == f->cfg.viewport_height, WDGS_E_STATE,
+                 "TiledRasterizer.encodeContribution: the forward pass viewport changed to %ux%u since the last encode (%ux%u)", f->cfg.viewport_width,
+                 f->cfg.viewport_height, op->width, op->height);
+    WDGS_REQUIRE(f->settings.gaussian_mode >= 0.5f, WDGS_E_STATE, "TiledRasterizer.encodeContribution: the forward pass is in point-cloud render mode, which has no weights");
+    const int fo = wdgs_sorter_final_out_index(f->sorter.get());
+    return launch_contribution(op->dev, f->settings, f->tile_info, f->splats, f->cfg.num_points, op->ranges_used,
+                               static_cast<const u32*>(wdgs_sorter_keys(f->sorter.get(), fo)), static_cast<const u32*>(wdgs_sorter_values(f->sorter.get(), fo)),
+                               f->stats, op->compat_caps ? 32u : 0u, stats_dev, f->nf_stamp, f->stats + FRAME_WORD);
+}
 int wdgs_tiled_rasterizer_get_depth(wdgs_tiled_rasterizer* op, uint32_t kind, void** out) {
     WDGS_REQUIRE(op && out, WDGS_E_INVALID, "wdgs_tiled_rasterizer_get_depth: null argument");
     WDGS_REQUIRE(kind == WDGS_DEPTH_EXPECTED || kind == WDGS_DEPTH_MEDIAN || kind == WDGS_DEPTH_WEIGHT_SUM, WDGS_E_INVALID,

@@ -193,6 +193,23 @@ __global__ __launch_bounds__(256) void decide_kernel(u32 n, const u32* __restric
     out_actions[idx] = action;
 }
 
+// The decision of contribution-based pruning (no reference counterpart): keep iff every non-zero field of the rule is met by the record
+// contrib.hip accumulated.  Every comparison is exact: the weight sum sum_q * 2^-24 in f64 (sum_q < 2^53 for any buffer that did not wrap its pixel count).
+__global__ __launch_bounds__(256) void contribution_decide_kernel(u32 n, const uint4* __restrict__ stats, wdgs_contribution_rule rule, u32* __restrict__ out_counts,
+                                                                   u32* __restrict__ out_actions) {
+    const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const uint4 r = stats[idx];   // { sum_q lo, sum_q hi, max_bits, pixels }
+    const unsigned long long sum_q = ((unsigned long long)r.y << 32) | r.x;
+    bool keep = true;
+    if (rule.min_max_weight != 0.0f) keep = keep && wd_bits2f(r.z) >= rule.min_max_weight;
+    if (rule.min_weight_sum != 0.0f) keep = keep && (double)sum_q * (1.0 / 16777216.0) >= (double)rule.min_weight_sum;
+    if (rule.min_pixels != 0u) keep = keep && r.w >= rule.min_pixels;
+    if (rule.min_sum_q != 0ull) keep = keep && sum_q >= rule.min_sum_q;
+    out_counts[idx] = keep ? 1u : 0u;
+    out_actions[idx] = keep ? 0u : 3u;
+}
+
 __global__ __launch_bounds__(256) void cap_kernel(u32 n, u32 max_out, const u32* __restrict__ offsets, u32* __restrict__ counts, u32* __restrict__ actions) {
     const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
@@ -250,6 +267,7 @@ constexpr float OPACITY_MAX_RAW = 1.38629436112f;
 
 struct ScatterArgs {
     u32 in_points, out_points, reset_new_state;
+    u32 verbatim;   // the decision was contribution_decide_kernel's: a kept Gaussian is copied bit for bit (no opacity clamp, opacity moments kept)
     const u32 *offsets, *counts, *actions;
     const u32 *in_gaussians, *in_sh;
     u32 *out_gaussians, *out_sh;
@@ -270,7 +288,7 @@ WD_DEV void scatter_slot(const ScatterArgs& a, u32 dst, u32 src, u32 variant, u3
         const u32* gi = a.in_gaussians + (size_t)src * 6;
         uint2 w01 = *reinterpret_cast<const uint2*>(gi), w23 = *reinterpret_cast<const uint2*>(gi + 2), w45 = *reinterpret_cast<const uint2*>(gi + 4);
         const float raw = wd_unpack_hi(w01.y);
-        const bool clamped = sigmoidf(raw) > OPACITY_MAX;
+        const bool clamped = a.verbatim == 0u && sigmoidf(raw) > OPACITY_MAX;
         const bool needs_transform = (action == 2u) || (action == 1u && variant == 1u);
         if (needs_transform || clamped) {
             const vec4 q = V4(wd_unpack_lo(w23.x), wd_unpack_hi(w23.x), wd_unpack_lo(w23.y), wd_unpack_hi(w23.y));
@@ -321,9 +339,10 @@ WD_DEV void scatter_slot(const ScatterArgs& a, u32 dst, u32 src, u32 variant, u3
     }
     {   // opacity: clamp in sigmoid space; m and v are zeroed for every survivor
         const float raw = a.in_opacity[(size_t)src * 3];
-        a.out_opacity[(size_t)dst * 3] = (sigmoidf(raw) > OPACITY_MAX) ? OPACITY_MAX_RAW : raw;
-        a.out_opacity[(size_t)dst * 3 + 1] = 0.0f;
-        a.out_opacity[(size_t)dst * 3 + 2] = 0.0f;
+        const bool copy = a.verbatim != 0u;
+        a.out_opacity[(size_t)dst * 3] = (!copy && sigmoidf(raw) > OPACITY_MAX) ? OPACITY_MAX_RAW : raw;
+        a.out_opacity[(size_t)dst * 3 + 1] = copy ? a.in_opacity[(size_t)src * 3 + 1] : 0.0f;
+        a.out_opacity[(size_t)dst * 3 + 2] = copy ? a.in_opacity[(size_t)src * 3 + 2] : 0.0f;
     }
     // (param_sh 192 B and state_sh 384 B are copied by the wave: scatter_kernel)
 }
@@ -416,6 +435,7 @@ struct wdgs_densify_prune {
     DevMem<u32> total;
     ScanScratch scan;
     u32 last_max_out = 0;
+    bool verbatim = false;   // the last decision stage was encode_contribution_decision: encode_scatter copies what it keeps bit for bit
     // the four work buffers are freed together and allocated in one order (ensure_size): when the last one is there, all are
     bool holds(u32 n) const { return scan.block_sums && n <= actions.count(); }
 };
@@ -469,9 +489,27 @@ static u32 compute_max_out(const wdgs_densify_config& c, u32 n) {
 int wdgs_densify_prune_encode_decision(wdgs_densify_prune* op, uint32_t n, const void* gaussians, const void* metric_counts) {
     WDGS_REQUIRE(op && gaussians, WDGS_E_INVALID, "wdgs_densify_prune_encode_decision: null argument");
     WDGS_TRY(wdgs_densify_prune_ensure_size(op, n));
+    op->verbatim = false;
     if (n == 0) return WDGS_OK;
     WDGS_LAUNCH(op->dev, "densify_decide", decide_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const u32*)gaussians, (const u32*)metric_counts,
                 op->cfg.clone_threshold, op->cfg.prune_threshold, op->cfg.split_threshold, op->counts, op->actions);
+    WDGS_CHECK_HIP(hipGetLastError());
+    return WDGS_OK;
+}
+
+// Contribution-based pruning's decision (no reference counterpart): the same two work buffers, from the records of wdgs_tiled_rasterizer_encode_contribution.
+int wdgs_densify_prune_encode_contribution_decision(wdgs_densify_prune* op, uint32_t n, const void* stats, const wdgs_contribution_rule* rule) {
+    WDGS_REQUIRE(op && stats && rule, WDGS_E_INVALID, "wdgs_densify_prune_encode_contribution_decision: null argument");
+    WDGS_REQUIRE(((uintptr_t)stats & 15u) == 0u, WDGS_E_INVALID, "wdgs_densify_prune_encode_contribution_decision: the statistics buffer must be 16-byte aligned");
+    WDGS_REQUIRE(rule->min_max_weight != 0.0f || rule->min_weight_sum != 0.0f || rule->min_pixels != 0u || rule->min_sum_q != 0ull, WDGS_E_INVALID,
+                 "wdgs_densify_prune_encode_contribution_decision: an all-zero rule keeps everything; set at least one criterion");
+    WDGS_REQUIRE(rule->min_max_weight >= 0.0f && rule->min_weight_sum >= 0.0f, WDGS_E_INVALID,
+                 "wdgs_densify_prune_encode_contribution_decision: thresholds must be >= 0 and not NaN (got %g, %g)", (double)rule->min_max_weight,
+                 (double)rule->min_weight_sum);
+    WDGS_TRY(wdgs_densify_prune_ensure_size(op, n));
+    op->verbatim = true;
+    if (n == 0) return WDGS_OK;
+    WDGS_LAUNCH(op->dev, "contribution_decide", contribution_decide_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, n, (const uint4*)stats, *rule, op->counts, op->actions);
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }
@@ -550,6 +588,7 @@ int wdgs_densify_prune_encode_scatter(wdgs_densify_prune* op, uint32_t in_points
     ScatterArgs a;
     std::memset(&a, 0, sizeof(a));
     a.in_points = in_points; a.out_points = out_num_points; a.reset_new_state = reset_new ? 1u : 0u;
+    a.verbatim = op->verbatim ? 1u : 0u;
     a.offsets = op->offsets; a.counts = op->counts; a.actions = op->actions;
     a.in_gaussians = (const u32*)in_gaussians; a.in_sh = (const u32*)in_sh;
     a.out_gaussians = (u32*)out_gaussians; a.out_sh = (u32*)out_sh;

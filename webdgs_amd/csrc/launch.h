@@ -64,6 +64,9 @@ int launch_rasterize(wdgs_device* dev, const RenderSettings& st, const TileInfo&
 int launch_depth_composite(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const u32* splats, u32 num_splats, const u32* depths, const u32* ranges,
                            const u32* sorted_keys, const u32* sorted_vals, const u32* count_ptr, u32 max_batches, float* out_weight, float* out_expected,
                            float* out_median, const u32* nf_stamp, const u32* nf_frame);
+// contrib.hip.  stats: one 16-byte record { u64 sum_q; u32 max_bits; u32 pixels; } per Gaussian, added to
+int launch_contribution(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const u32* splats, u32 num_splats, const u32* ranges, const u32* sorted_keys,
+                        const u32* sorted_vals, const u32* count_ptr, u32 max_batches, void* stats, const u32* nf_stamp, const u32* nf_frame);
 
 // ---- loss.hip, dssim.hip.  pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
 int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,

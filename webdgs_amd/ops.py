@@ -576,6 +576,14 @@ class TiledRasterizer:
         check(self.device.lib.wdgs_tiled_rasterizer_get_depth(self.handle, _depth_mask((kind,)), C.byref(p)))
         return self.device.view(p.value, 4 * self.width * self.height)
 
+    def encodeContribution(self, encoder: Optional[HipEncoder], statsBuffer: HipBuffer) -> None:
+        """Adds the per-Gaussian contribution of the frame the last ``encode`` rasterized into ``statsBuffer`` (``createContributionBuffer``; DESIGN.md
+        section 11; no reference counterpart).  Allocates nothing, so it records."""
+        n = self.forwardPass.pointCloud.num_points
+        if statsBuffer.size < CONTRIBUTION_RECORD_BYTES * n:
+            raise ValueError(f"encodeContribution: the statistics buffer holds {statsBuffer.size} bytes, {n} Gaussians need {CONTRIBUTION_RECORD_BYTES * n}")
+        check(self.device.lib.wdgs_tiled_rasterizer_encode_contribution(self.handle, statsBuffer.ptr))
+
     def blitToTexture(self, encoder: Optional[HipEncoder], target: HipBuffer, width: Optional[int] = None, height: Optional[int] = None) -> None:
         """``blitToTexture(encoder, targetView)`` (tiled-rasterizer.ts:333-357): ``target`` is an rgba8 image buffer of
         ``width x height`` (default: the rasterizer's own size); raises before the first ``encode`` like the reference."""
@@ -750,6 +758,26 @@ def depthToRGBA8(device: HipDevice, depth: HipBuffer, width: int, height: int, n
     if depth.size < 4 * n or target.size < 4 * n:
         raise ValueError(f"depthToRGBA8: buffers too small for {width}x{height}")
     check(device.lib.wdgs_depth_to_rgba8(device.handle, depth.ptr, int(width), int(height), float(near), float(far), target.ptr))
+
+
+# ----------------------------------------------------------------------------- per-Gaussian contribution (no reference counterpart)
+CONTRIBUTION_RECORD_BYTES = 16
+CONTRIBUTION_DTYPE = np.dtype([("sum_q", "<u8"), ("max_bits", "<u4"), ("pixels", "<u4")])
+
+
+def createContributionBuffer(device: HipDevice, numPoints: int) -> HipBuffer:
+    """One zeroed 16-byte record ``{u64 sum_q; u32 max_bits; u32 pixels}`` per Gaussian, for ``TiledRasterizer.encodeContribution``."""
+    buf = device.createBuffer(CONTRIBUTION_RECORD_BYTES * max(1, int(numPoints)), label="contribution")
+    buf.clear()
+    return buf
+
+
+def readContribution(buffer: HipBuffer, n: int) -> dict:
+    """The first ``n`` records: ``sum_q`` uint64, ``weight_sum`` float64 (``sum_q * 2^-24``), ``max_weight`` float32, ``pixels`` uint32."""
+    rec = buffer.read(np.uint8, CONTRIBUTION_RECORD_BYTES * int(n)).view(CONTRIBUTION_DTYPE)
+    sum_q = np.ascontiguousarray(rec["sum_q"])
+    return dict(sum_q=sum_q, weight_sum=sum_q.astype(np.float64) * 2.0 ** -24, max_weight=np.ascontiguousarray(rec["max_bits"]).view(np.float32),
+                pixels=np.ascontiguousarray(rec["pixels"]))
 
 
 def encodeImageSSE(device: HipDevice, a: HipBuffer, b: HipBuffer, num_pixels: int, out: HipBuffer) -> None:
@@ -1041,6 +1069,23 @@ class DensifyPrunePass:
         mc = inputs.get("metricCountsBuffer")
         check(self.device.lib.wdgs_densify_prune_encode_decision(self.handle, pc.num_points, pc.gaussian_3d_buffer.ptr, mc.ptr if mc is not None else None))
         self.numPoints = pc.num_points
+        b = self._buffers()
+        return dict(actionBuffer=b["actionBuffer"], outCountBuffer=b["outCountBuffer"])
+
+    def encodeContributionDecision(self, encoder, numPoints: int, statsBuffer: HipBuffer, rule: dict) -> dict:
+        """The decision of contribution-based pruning (no reference counterpart): a Gaussian is kept iff its record in
+        ``statsBuffer`` meets every non-zero field of ``rule`` (``minMaxWeight``, ``minWeightSum``, ``minPixels``, ``minSumQ``).  Then ``encodePrefixSum``,
+        ``encodeTotalOut``, ``readTotal`` and ``encodeScatter`` compact the cloud; what this stage keeps is copied bit for bit."""
+        unknown = set(rule) - {"minMaxWeight", "minWeightSum", "minPixels", "minSumQ"}
+        if unknown:
+            raise ValueError(f"encodeContributionDecision: unknown rule fields {sorted(unknown)}")
+        n = int(numPoints)
+        if statsBuffer.size < CONTRIBUTION_RECORD_BYTES * n:
+            raise ValueError(f"encodeContributionDecision: the statistics buffer holds {statsBuffer.size} bytes, {n} Gaussians need {CONTRIBUTION_RECORD_BYTES * n}")
+        r = _lib.ContributionRule(float(rule.get("minMaxWeight") or 0.0), float(rule.get("minWeightSum") or 0.0), int(rule.get("minPixels") or 0),
+                                  int(rule.get("minSumQ") or 0))
+        check(self.device.lib.wdgs_densify_prune_encode_contribution_decision(self.handle, n, statsBuffer.ptr, C.byref(r)))
+        self.numPoints = n
         b = self._buffers()
         return dict(actionBuffer=b["actionBuffer"], outCountBuffer=b["outCountBuffer"])
 

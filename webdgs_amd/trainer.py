@@ -948,28 +948,12 @@ class Trainer:
         n = len(ids)
         out = self.device.createBuffer(16 * max(1, n), "evaluation sse + ssim")
         sse_at, ssim_at = out.ptr, out.ptr + 8 * max(1, n)
-        while n:
-            self._eval_follow_cloud()
-            for i, v in enumerate(ids):
-                im, w, h = imgs[v], int(imgs[v]["width"]), int(imgs[v]["height"])
-                s = self._eval_set(w, h, bufs[v])
-                fw, rast = s.forwardPass, s.rasterizer
-                fw.setCameraBuffer(bufs[v])
-                fw.encode(None)
-                rast.encode(None, w, h)
-                pred = rast.getOutputTextureView()
-                ops.encodeImageSSE(self.device, pred, im["texture"], w * h, self.device.view(sse_at + 8 * i, 8))
-                ops.encodeImageSSIM(self.device, pred, im["texture"], w, h, self.device.view(ssim_at + 8 * i, 8))
-            needed = self._eval_overflow()
-            if needed is None:
-                break
-            now = max([int(s.forwardPass.getResources()["maxTileEntries"]) for s in self._eval_sets.values()] + [self._eval_tile_entries])
-            new = min(max(2 * now, int(needed * 1.5)), 0xFFFFF000)
-            if new <= now:
-                raise RuntimeError(f"evaluate: a view needs {needed} tile entries, more than the lists can hold")
-            warnings.warn(f"evaluation tile-entry lists grown from {now} to {new} entries after an overflow; the views are rendered again", RuntimeWarning, stacklevel=2)
-            self._eval_tile_entries = new
-            self._destroy_eval_sets()
+
+        def measure(i, v, s, w, h):
+            pred = s.rasterizer.getOutputTextureView()
+            ops.encodeImageSSE(self.device, pred, imgs[v]["texture"], w * h, self.device.view(sse_at + 8 * i, 8))
+            ops.encodeImageSSIM(self.device, pred, imgs[v]["texture"], w, h, self.device.view(ssim_at + 8 * i, 8))
+        self._render_eval_views(ids, imgs, bufs, measure, what="evaluate")
         sse = out.read(np.uint64, count=n) if n else np.zeros(0, np.uint64)
         ssim = out.read(np.float64, count=n, offset=8 * max(1, n)) if n else np.zeros(0)
         psnr = [ops.psnrFromSSE(int(sse[i]), int(imgs[v]["width"]) * int(imgs[v]["height"])) for i, v in enumerate(ids)]
@@ -977,6 +961,122 @@ class Trainer:
         return dict(iteration=self.iteration, views=ids, psnr=psnr, ssim=ssim_l, sse=[int(x) for x in sse],
                     mean_psnr=float(np.mean(psnr)) if n else float("nan"), mean_ssim=float(np.mean(ssim_l)) if n else float("nan"),
                     ms=(time.perf_counter() - t0) * 1e3)
+
+    def _render_eval_views(self, ids: list, imgs: list, bufs: list, each, restart=None, what: str = "evaluate") -> None:
+        """evaluate's render loop, shared with contributionStats: every view of ``ids`` through the evaluation pass set of its size, then
+        ``each(i, v, passSet, width, height)``; after an overflow the lists are grown, ``restart()`` is called and ALL views are rendered again."""
+        while ids:
+            self._eval_follow_cloud()
+            for i, v in enumerate(ids):
+                w, h = int(imgs[v]["width"]), int(imgs[v]["height"])
+                s = self._eval_set(w, h, bufs[v])
+                fw, rast = s.forwardPass, s.rasterizer
+                fw.setCameraBuffer(bufs[v])
+                fw.encode(None)
+                rast.encode(None, w, h)
+                each(i, v, s, w, h)
+            needed = self._eval_overflow()
+            if needed is None:
+                break
+            now = max([int(s.forwardPass.getResources()["maxTileEntries"]) for s in self._eval_sets.values()] + [self._eval_tile_entries])
+            new = min(max(2 * now, int(needed * 1.5)), 0xFFFFF000)
+            if new <= now:
+                raise RuntimeError(f"{what}: a view needs {needed} tile entries, more than the lists can hold")
+            warnings.warn(f"evaluation tile-entry lists grown from {now} to {new} entries after an overflow; the views are rendered again", RuntimeWarning, stacklevel=3)
+            self._eval_tile_entries = new
+            self._destroy_eval_sets()
+            if restart is not None:
+                restart()
+
+    # ------------------------------------------------------------------ render contribution and contribution-based pruning (no reference counterpart)
+    def _contribution_buffer(self, viewIds: Optional[list], split: str, what: str) -> tuple:
+        """(buffer, view ids): the views' contribution records accumulated into one new device buffer."""
+        if split not in ("eval", "train"):
+            raise ValueError(f"{what}: split must be 'eval' or 'train', not {split!r}")
+        if self.pointCloud is None:
+            raise RuntimeError(f"{what}: no point cloud")
+        cams, imgs, bufs = ((self.evalCameras, self.evalImages, self._eval_camera_buffers) if split == "eval" else
+                            (self.trainCameras, self.images, self._camera_buffers))
+        ids = list(range(len(cams))) if viewIds is None else [int(v) for v in viewIds]
+        for v in ids:
+            if not 0 <= v < len(cams):
+                raise IndexError(f"{what}: view {v} of {len(cams)} ({split})")
+        if sum(int(imgs[v]["width"]) * int(imgs[v]["height"]) for v in ids) >= 2 ** 32:
+            raise ValueError(f"{what}: the views hold 2^32 pixels or more; the per-Gaussian pixel count is 32 bits wide")
+        try:
+            self.drain()
+        except ops.CapacityError as e:   # a training step's overflow, as step() would have met it at its next wait
+            if not self._grow_tile_entry_capacity(e):
+                raise
+        stats = ops.createContributionBuffer(self.device, self.pointCloud.num_points)
+        try:
+            self._render_eval_views(ids, imgs, bufs, lambda i, v, s, w, h: s.rasterizer.encodeContribution(None, stats), restart=stats.clear, what=what)
+        except BaseException:
+            stats.destroy()
+            raise
+        return stats, ids
+
+    def contributionStats(self, viewIds: Optional[list] = None, split: str = "train") -> dict:
+        """How much of each Gaussian the views' images hold: ``dict(sum_q, weight_sum, max_weight, pixels, views)``, one
+        entry per Gaussian, accumulated over the views -- the sum and the maximum of the compositing weights ``alpha (1 - A)`` and the number of
+        (pixel, Gaussian) pairs composited.  Rendered through evaluate's passes, with its isolation: the pipeline is drained, a view whose lists
+        overflowed is rendered again (the records are cleared and every view is walked again), no RNG draw, no training pass, no recording
+        dropped.  Per rank with ``world_size > 1``."""
+        stats, ids = self._contribution_buffer(viewIds, split, "contributionStats")
+        try:
+            out = ops.readContribution(stats, self.pointCloud.num_points)
+        finally:
+            stats.destroy()
+        out["views"] = ids
+        return out
+
+    def pruneByContribution(self, minMaxWeight: float = 0.0, minWeightSum: float = 0.0, minPixels: int = 0, fraction: float = 0.0,
+                            viewIds: Optional[list] = None) -> dict:
+        """Removes the Gaussians the training views (``viewIds``: all) need least: a Gaussian is kept iff it meets every criterion given --
+        its largest weight ``>= minMaxWeight``, its weight sum ``>= minWeightSum``, its pixel count ``>= minPixels``, and, with ``fraction`` f,
+        its ``sum_q`` not below the k-th smallest ``sum_q`` of the cloud, k = floor(f N) (at most k go; ties at the boundary stay).  The
+        survivors, their SH rows and their optimizer state are compacted in index order, bit for bit, and the cloud is swapped as after a densify
+        event (optimizer iteration and state handed over).  ``dict(before, after, pruned)``; pruning nothing or everything (a warning) leaves the
+        cloud as it is.  Single rank only."""
+        if self.world_size > 1:
+            raise RuntimeError("pruneByContribution: world_size > 1 is not supported (the replicas would have to agree on the statistics)")
+        if not (minMaxWeight >= 0 and minWeightSum >= 0 and minPixels >= 0 and 0 <= fraction < 1):
+            raise ValueError("pruneByContribution: the thresholds must be >= 0 and fraction in [0, 1)")
+        if not (minMaxWeight or minWeightSum or minPixels or fraction):
+            raise ValueError("pruneByContribution: give at least one of minMaxWeight, minWeightSum, minPixels, fraction")
+        if self.optimizer is None or self.densifyPrune is None:
+            raise RuntimeError("pruneByContribution: no point cloud")
+        stats, _ = self._contribution_buffer(viewIds, "train", "pruneByContribution")
+        try:
+            n = self.pointCloud.num_points
+            unchanged = dict(before=n, after=n, pruned=0)
+            rule = dict(minMaxWeight=float(minMaxWeight), minWeightSum=float(minWeightSum), minPixels=int(minPixels), minSumQ=0)
+            k = int(math.floor(fraction * n))
+            if k > 0:
+                rule["minSumQ"] = int(np.partition(ops.readContribution(stats, n)["sum_q"], k - 1)[k - 1])
+            if not any(rule.values()):
+                return unchanged   # (only a fraction was given, and it selects nothing: k = 0, or the k-th smallest sum is 0)
+            dp = self.densifyPrune
+            dp.ensureSize(n)
+            dp.encodeContributionDecision(None, n, stats, rule)
+            offsets = dp.encodePrefixSum(None)
+            dp.encodeTotalOut(None)
+            outN = dp.readTotal()
+            if outN == n:
+                return unchanged
+            if outN == 0:
+                warnings.warn("pruneByContribution: the criteria would remove every Gaussian; the cloud is left as it is", RuntimeWarning, stacklevel=2)
+                return unchanged
+            self.optimizer.flushSH(self.pointCloud)  # the rebuild copies the cloud's SH rows: bring the deferred DC halves in first
+            outPointCloud = ops.allocatePointCloudLike(self.device, self.pointCloud, dict(numPoints=outN))
+            outState = ops.allocateOptimizerStateBuffers(self.device, outN)
+            dp.encodeScatter(None, dict(pointCloud=self.pointCloud, optimizerState=self.optimizer.getStateBuffers(), outOffsetBuffer=offsets, outNumPoints=outN,
+                                        resetNewOptimizerState=False), dict(outPointCloud=outPointCloud, outOptimizerState=outState))
+            self._synchronize()
+            self.applyPointCloudSwap(dict(pointCloud=outPointCloud, optimizerInitialState=dict(iteration=self.optimizer.getIteration(), buffers=outState)))
+            return dict(before=n, after=outN, pruned=n - outN)
+        finally:
+            stats.destroy()
 
     # ------------------------------------------------------------------ densify / prune
     def runDensifyPruneMultiView(self) -> None:
