@@ -14,7 +14,7 @@ from harness import assert_bits_equal
 from test_contrib_reference import SCENES, contrib64_of
 from test_depth_reference import scene_config
 from test_gpu_eval import _trainer, _views
-from test_gpu_nan import NAN16, long_list_scene, poisoned
+from test_gpu_nan import CHUNK_EDGE_PILES, NAN16, chunk_edge_scene, long_list_scene, poisoned, tile_list_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +34,31 @@ def _raw(buf, n):
     return buf.read(np.uint8, 16 * n).view(ops.CONTRIBUTION_DTYPE)
 
 
+def _assert_records_match_float64(pipe, buf, name, exact_pixels):
+    cfg = pipe.cfg
+    got = ops.readContribution(buf, cfg.num_points)
+    c = contrib64_of(pipe.collect_forward(), cfg)
+    b_sum = c["pixels"] * EPS + c["slack_sum"]
+    e_sum = np.abs(got["weight_sum"] - c["weight_sum"])
+    b_max = EPS + c["slack_max"]
+    e_max = np.abs(got["max_weight"].astype(np.float64) - c["max_weight"])
+    e_pix = np.abs(got["pixels"].astype(np.int64) - c["pixels"])
+    seen = c["pixels"] > 0
+    r_sum = (e_sum[seen] / b_sum[seen]).max() if seen.any() else 0.0
+    print(f"contribution accuracy {name}: worst |weight_sum - ws64| / (pixels eps + slack) = {r_sum:.3f}, worst |max_weight - max64| / (eps + slack) = "
+          f"{(e_max / b_max).max():.3f}, pixel counts differing on {int((e_pix > 0).sum())} Gaussians (slack allows {int((c['slack_pixels'] > 0).sum())}), "
+          f"Gaussians with weight {int(seen.sum())} of {cfg.num_points}, surely_zero {int(c['surely_zero'].sum())}, slack {c['slack_sum'].sum():.4g}")
+    assert np.all(e_sum <= b_sum), f"{name}: weight sum off by {r_sum:.2f} x the bound"
+    assert np.all(e_max <= b_max), f"{name}: max weight off by {(e_max / b_max).max():.2f} x the bound"
+    assert np.all(e_pix <= c["slack_pixels"]), f"{name}: pixel counts differ beyond the slack on {int((e_pix > c['slack_pixels']).sum())} Gaussians"
+    if exact_pixels:
+        assert c["slack_pixels"].sum() == 0 and np.array_equal(got["pixels"].astype(np.int64), c["pixels"])
+    z = c["surely_zero"]
+    assert not got["sum_q"][z].any() and not got["max_weight"][z].any() and not got["pixels"][z].any(), f"{name}: weight on a Gaussian behind saturated pixels"
+    assert got["max_weight"].max() <= np.float32(0.99)
+    assert np.array_equal(got["weight_sum"], got["sum_q"].astype(np.float64) * 2.0 ** -24)
+
+
 @pytest.mark.parametrize("name", SCENES)
 def test_records_match_float64(hip_device, name):
     cfg = scene_config(name)
@@ -41,27 +66,7 @@ def test_records_match_float64(hip_device, name):
     pipe = harness.HipPipeline(hip_device, cfg, g, sh, cam)
     try:
         buf = _records(pipe)
-        got = ops.readContribution(buf, cfg.num_points)
-        c = contrib64_of(pipe.collect_forward(), cfg)
-        b_sum = c["pixels"] * EPS + c["slack_sum"]
-        e_sum = np.abs(got["weight_sum"] - c["weight_sum"])
-        b_max = EPS + c["slack_max"]
-        e_max = np.abs(got["max_weight"].astype(np.float64) - c["max_weight"])
-        e_pix = np.abs(got["pixels"].astype(np.int64) - c["pixels"])
-        seen = c["pixels"] > 0
-        r_sum = (e_sum[seen] / b_sum[seen]).max() if seen.any() else 0.0
-        print(f"contribution accuracy {name}: worst |weight_sum - ws64| / (pixels eps + slack) = {r_sum:.3f}, worst |max_weight - max64| / (eps + slack) = "
-              f"{(e_max / b_max).max():.3f}, pixel counts differing on {int((e_pix > 0).sum())} Gaussians (slack allows {int((c['slack_pixels'] > 0).sum())}), "
-              f"Gaussians with weight {int(seen.sum())} of {cfg.num_points}, surely_zero {int(c['surely_zero'].sum())}, slack {c['slack_sum'].sum():.4g}")
-        assert np.all(e_sum <= b_sum), f"{name}: weight sum off by {r_sum:.2f} x the bound"
-        assert np.all(e_max <= b_max), f"{name}: max weight off by {(e_max / b_max).max():.2f} x the bound"
-        assert np.all(e_pix <= c["slack_pixels"]), f"{name}: pixel counts differ beyond the slack on {int((e_pix > c['slack_pixels']).sum())} Gaussians"
-        if name in ("sparse", "c1"):
-            assert c["slack_pixels"].sum() == 0 and np.array_equal(got["pixels"].astype(np.int64), c["pixels"])
-        z = c["surely_zero"]
-        assert not got["sum_q"][z].any() and not got["max_weight"][z].any() and not got["pixels"][z].any(), f"{name}: weight on a Gaussian behind saturated pixels"
-        assert got["max_weight"].max() <= np.float32(0.99)
-        assert np.array_equal(got["weight_sum"], got["sum_q"].astype(np.float64) * 2.0 ** -24)
+        _assert_records_match_float64(pipe, buf, name, exact_pixels=name in ("sparse", "c1"))
         buf.destroy()
     finally:
         pipe.destroy()
@@ -85,25 +90,48 @@ def _identity_scenes():
     yield "long lists (10 400 entries in one tile)", cfg, g, sh, cam
 
 
+def _assert_weights_sum_to_the_weight_image(pipe, buf, what, least_entries):
+    """buf: the records of pipe's last frame."""
+    cfg = pipe.cfg
+    pipe.rast.encodeDepth(None, ("weight_sum",))
+    pipe.dev.synchronize()
+    image = pipe.rast.getDepthTextureView("weight_sum").read(np.float32).astype(np.float64)
+    got = ops.readContribution(buf, cfg.num_points)
+    fw = pipe.collect_forward()
+    assert int(fw["stats"][0]) >= least_entries
+    bound = _list_lengths(fw, cfg) * 1.5 * 2.0 ** -24
+    diff = abs(float(got["sum_q"].sum()) * 2.0 ** -24 - image.sum())
+    print(f"contribution vs depth {what}: |sum_g - sum_p| = {diff:.3e}, bound {bound:.3e} ({diff / bound:.3f})")
+    assert np.isfinite(image).all() and diff <= bound, f"{what}: {diff} > {bound}"
+
+
 def test_weights_sum_to_the_depth_kernels_weight_image(hip_device):
     """GPU only, no float64: every active pair's w is added to one pixel's weight sum by depth.hip and, truncated to 2^-24, to one Gaussian's sum_q here."""
     for what, cfg, g, sh, cam in _identity_scenes():
         pipe = harness.HipPipeline(hip_device, cfg, g, sh, cam)
         try:
             buf = _records(pipe)
-            pipe.rast.encodeDepth(None, ("weight_sum",))
-            hip_device.synchronize()
-            image = pipe.rast.getDepthTextureView("weight_sum").read(np.float32).astype(np.float64)
-            got = ops.readContribution(buf, cfg.num_points)
-            fw = pipe.collect_forward()
-            assert int(fw["stats"][0]) >= (10_400 if what.startswith("long") else 1)
-            bound = _list_lengths(fw, cfg) * 1.5 * 2.0 ** -24
-            diff = abs(float(got["sum_q"].sum()) * 2.0 ** -24 - image.sum())
-            print(f"contribution vs depth {what}: |sum_g - sum_p| = {diff:.3e}, bound {bound:.3e} ({diff / bound:.3f})")
-            assert np.isfinite(image).all() and diff <= bound, f"{what}: {diff} > {bound}"
+            _assert_weights_sum_to_the_weight_image(pipe, buf, what, 10_400 if what.startswith("long") else 1)
             buf.destroy()
         finally:
             pipe.destroy()
+
+
+def test_lists_that_end_at_the_chunk_edges(hip_device):
+    """Tile lists of 1, 63, 64, 65, 128 and 129 entries (test_gpu_nan.chunk_edge_scene), none of which saturates a pixel: the walk's chunks of 64 end with
+    the list, one entry before it and one entry after it.  The records against float64, pixel counts exactly, and against the depth kernel's weight image."""
+    cfg, g, sh, cam = chunk_edge_scene()
+    pipe = harness.HipPipeline(hip_device, cfg, g, sh, cam)
+    try:
+        buf = _records(pipe)
+        lens = tile_list_lengths(pipe.collect_forward()["tile_ranges"])
+        ntx = (cfg.width + 15) // 16
+        assert {t: int(lens[t[1] * ntx + t[0]]) for t in CHUNK_EDGE_PILES} == CHUNK_EDGE_PILES, "the scene is not the one this test is about"
+        _assert_records_match_float64(pipe, buf, "chunk edges", exact_pixels=True)
+        _assert_weights_sum_to_the_weight_image(pipe, buf, "chunk edges", 581)
+        buf.destroy()
+    finally:
+        pipe.destroy()
 
 
 def test_determinism_accumulation_and_replay(hip_device):

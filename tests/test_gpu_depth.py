@@ -12,7 +12,7 @@ import harness
 from harness import assert_bits_equal
 from test_depth_reference import MASK_CAP, SCENES, depth64_of, scene_config
 from test_gpu_eval import _trainer, _views
-from test_gpu_nan import INF16, NAN16, long_list_scene, poisoned
+from test_gpu_nan import CHUNK_EDGE_PILES, INF16, NAN16, chunk_edge_scene, long_list_scene, poisoned, tile_list_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -127,6 +127,35 @@ def test_weight_sum_on_long_lists_and_non_finite_scenes(hip_device, compat):
         finally:
             pipe.destroy()
     assert nan_pixels > 0, "the non-finite scenes are there for their NaN pixels"
+
+
+def test_lists_that_end_at_the_chunk_edges(hip_device):
+    """Tile lists of 1, 63, 64, 65, 128 and 129 entries (test_gpu_nan.chunk_edge_scene), none of which saturates a pixel: the walk's chunks of 64 end with
+    the list, one entry before it and one entry after it.  The weight sum is the rasterizer's bit for bit, the expected depth within the float64 bound, and the median a record's z (here 0: no weight sum reaches one half)."""
+    cfg, g, sh, cam = chunk_edge_scene()
+    pipe = harness.HipPipeline(hip_device, cfg, g, sh, cam)
+    try:
+        got = _depth(pipe)
+        fw = pipe.collect_forward()
+        lens = tile_list_lengths(fw["tile_ranges"])
+        ntx = (cfg.width + 15) // 16
+        assert {t: int(lens[t[1] * ntx + t[0]]) for t in CHUNK_EDGE_PILES} == CHUNK_EDGE_PILES, "the scene is not the one this test is about"
+        assert _assert_weight_sum_is_alpha(pipe, got, "chunk edges") == 0
+        assert got["weight_sum"].max() < 0.99, "no pixel is to saturate: every chunk is walked to its end"
+        A, D, M, near_sat, near_half, stats = depth64_of(fw, cfg, probe=got["median"])
+        # expected depth, test_depth_images_match_float64's bound: the z kept beside each record, through every chunk of the list
+        zmax = float(np.abs(d64.decode_depths(fw["depths"])[fw["sorted_values"]]).max())
+        tol = (stats["n_active"] + 32) * 2.0 ** -23
+        err = np.abs(got["expected"].astype(np.float64) - D) / zmax
+        keep = ~near_sat
+        print(f"depth accuracy chunk edges: worst share of the bound (n_p + 32) 2^-23 = {(err / tol)[keep].max():.3f}, max n_p = {int(stats['n_active'].max())}")
+        assert int(stats["n_active"].max()) > 0 and np.all(err[keep] <= tol[keep]), f"chunk edges: expected depth off by {(err / tol)[keep].max():.2f} x the bound"
+        assert np.all(got["expected"][stats["n_active"] == 0] == 0)
+        sure = ~(near_sat | near_half)
+        assert_bits_equal(got["median"][sure], M.astype(np.float32)[sure], "chunk edges: median depth")
+        assert np.all(stats["probe_in_box"][(got["median"] != 0)]), "chunk edges: a median that is no record's z"
+    finally:
+        pipe.destroy()
 
 
 def test_rerun_and_replay(hip_device):

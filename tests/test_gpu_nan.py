@@ -162,6 +162,38 @@ def long_list_scene(kind, big=10_400, second=4_097):
     return cfg, g, sh, synth.identity_camera(cfg), rng
 
 
+CHUNK_EDGE_PILES = {(0, 0): 1, (2, 0): 63, (4, 0): 64, (0, 2): 65, (2, 2): 128, (4, 2): 129}   # tile -> list length: around the walk's chunks of 64
+
+
+def chunk_edge_scene():
+    """Gaussians, SH, camera and config of a 96 x 64 scene whose six non-neighbouring tiles hold lists of 1, 63, 64, 65, 128 and 129 entries: piles of
+    long_list_scene's "sparse" splats within 2 px of the point 4 px up and left of the tile's centre, faint enough that no pixel saturates, so every
+    chunk of every list is walked to its end.  No other Gaussians: 581 entries (the piles' tiles and what spills over their edges)."""
+    cfg = harness.small_config("c1", num_points=1, width=96, height=64, fy=90.0, sh_deg=0)
+    rng = np.random.default_rng(23)
+    rows = []
+    for (tx, ty), count in CHUNK_EDGE_PILES.items():
+        for i in range(count):
+            z = 2.0 + 6.0 * rng.random()
+            cx, cy = _tile_centre(cfg, tx, ty, z)
+            rows.append((cx + (rng.uniform(-2, 2) - 4.0) * z / cfg.fy, cy + (rng.uniform(-2, 2) - 4.0) * z / cfg.fy, z, rng.uniform(-4.5, -3.5), np.log(0.001 * z)))
+    g, sh = _rows(rows)
+    cfg = harness.small_config("c1", num_points=len(rows), width=96, height=64, fy=90.0, sh_deg=0)
+    return cfg, g, sh, synth.identity_camera(cfg)
+
+
+def tile_list_lengths(ranges):
+    """Per tile, the length of its list, from a range table (start per tile, 0xFFFFFFFF for an empty one, the entry count behind the last)."""
+    ranges = np.asarray(ranges, np.int64)
+    lens = np.zeros(len(ranges) - 1, np.int64)
+    end = ranges[-1]
+    for t in range(len(lens) - 1, -1, -1):
+        if ranges[t] != 0xFFFFFFFF:
+            lens[t] = end - ranges[t]
+            end = ranges[t]
+    return lens
+
+
 @pytest.mark.parametrize("kind", ["sparse", "faint", "pile-up"])
 def test_tile_lists_past_the_reference_cap(hip_device, orc, kind):
     """One tile with more than 10 000 entries (the reference stages at most 32 x 256 = 8 192 per tile, SURVEY Q3: lifted here), one with 4 097, short

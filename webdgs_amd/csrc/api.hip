@@ -1081,6 +1081,23 @@ int wdgs_tiled_rasterizer_destroy(wdgs_tiled_rasterizer* op) {
     delete op;
     return WDGS_OK;
 }
+// The frame op's last encode composited (or is about to: op->ranges_used is set), as the walkers of its tile lists take it (launch.h)
+static CompositedFrame composited_frame(const wdgs_tiled_rasterizer* op) {
+    const wdgs_tiled_forward* f = op->fwd;
+    const int fo = wdgs_sorter_final_out_index(f->sorter.get());
+    return CompositedFrame{f->settings, f->tile_info, f->splats, f->cfg.num_points, op->ranges_used, static_cast<const u32*>(wdgs_sorter_keys(f->sorter.get(), fo)),
+                           static_cast<const u32*>(wdgs_sorter_values(f->sorter.get(), fo)), f->stats, op->compat_caps ? 32u : 0u, f->nf_stamp, f->stats + FRAME_WORD};
+}
+// What encodeDepth and encodeContribution (`what`) need of the last encode: that there was one, of the viewport the forward pass still has, in Gaussian mode
+static int require_composited_frame(const wdgs_tiled_rasterizer* op, const char* what) {
+    const wdgs_tiled_forward* f = op->fwd;
+    WDGS_REQUIRE(op->encoded && f->encoded && op->ranges_used, WDGS_E_STATE, "TiledRasterizer.%s before encode: it composites the frame encode rasterized", what);
+    WDGS_REQUIRE(op->width == f->cfg.viewport_width && op->height == f->cfg.viewport_height, WDGS_E_STATE,
+                 "TiledRasterizer.%s: the forward pass viewport changed to %ux%u since the last encode (%ux%u)", what, f->cfg.viewport_width, f->cfg.viewport_height,
+                 op->width, op->height);
+    WDGS_REQUIRE(f->settings.gaussian_mode >= 0.5f, WDGS_E_STATE, "TiledRasterizer.%s: the forward pass is in point-cloud render mode, which has no weights", what);
+    return WDGS_OK;
+}
 int wdgs_tiled_rasterizer_encode(wdgs_tiled_rasterizer* op, uint32_t width, uint32_t height) {
     WDGS_REQUIRE(op && width > 0 && height > 0, WDGS_E_INVALID, "wdgs_tiled_rasterizer_encode: invalid argument");
     wdgs_tiled_forward* f = op->fwd;
@@ -1103,7 +1120,6 @@ int wdgs_tiled_rasterizer_encode(wdgs_tiled_rasterizer* op, uint32_t width, uint
     }
     const int fo = wdgs_sorter_final_out_index(f->sorter.get());
     const u32* keys = static_cast<const u32*>(wdgs_sorter_keys(f->sorter.get(), fo));
-    const u32* vals = static_cast<const u32*>(wdgs_sorter_values(f->sorter.get(), fo));
     if (f->ranges_valid) {
         op->ranges_used = f->ranges;  // built by the forward pass's sort
     } else {
@@ -1116,26 +1132,19 @@ int wdgs_tiled_rasterizer_encode(wdgs_tiled_rasterizer* op, uint32_t width, uint
         WDGS_TRY(launch_tile_ranges(d, keys, f->stats, ti.total_tiles, op->ranges));
         op->ranges_used = op->ranges;
     }
-    WDGS_TRY(launch_rasterize(d, f->settings, ti, f->splats, f->cfg.num_points, op->ranges_used, keys, vals, f->stats, op->compat_caps ? 32u : 0u, op->rgba8,
-                              op->alpha, op->n_contrib, f->nf_stamp, f->stats + FRAME_WORD,
+    WDGS_TRY(launch_rasterize(d, composited_frame(op), op->rgba8, op->alpha, op->n_contrib,
                               (f->ranges_valid && f->long_lists.hdr && !op->compat_caps) ? &f->long_lists : nullptr));   // (the table this pass's sort built and marked)
     op->encoded = true;
     return WDGS_OK;
 }
 
 // Depth images of the frame the last encode composited (depth.hip; no counterpart in the reference, which renders colour only).  The walk is
-// launch_rasterize's without the long-list work: same settings, tile grid, Splats, range table, sorted keys / values, entry count, compat cap and
-// non-finite stamps, plus the forward pass's depth words.
+// launch_rasterize's without the long-list work (tilewalk.h): the same CompositedFrame, plus the forward pass's depth words.
 int wdgs_tiled_rasterizer_encode_depth(wdgs_tiled_rasterizer* op, uint32_t kinds) {
     WDGS_REQUIRE(op, WDGS_E_INVALID, "wdgs_tiled_rasterizer_encode_depth: null op");
     constexpr uint32_t all = WDGS_DEPTH_EXPECTED | WDGS_DEPTH_MEDIAN | WDGS_DEPTH_WEIGHT_SUM;
     WDGS_REQUIRE(kinds != 0u && (kinds & ~all) == 0u, WDGS_E_INVALID, "wdgs_tiled_rasterizer_encode_depth: kinds 0x%x is not a non-empty set of WDGS_DEPTH_* bits", kinds);
-    wdgs_tiled_forward* f = op->fwd;
-    WDGS_REQUIRE(op->encoded && f->encoded && op->ranges_used, WDGS_E_STATE, "TiledRasterizer.encodeDepth before encode: depth is composited from the frame encode rasterized");
-    WDGS_REQUIRE(op->width == f->cfg.viewport_width && op->height == f->cfg.viewport_height, WDGS_E_STATE,
-                 "TiledRasterizer.encodeDepth: the forward pass viewport changed to %ux%u since the last encode (%ux%u)", f->cfg.viewport_width, f->cfg.viewport_height,
-                 op->width, op->height);
-    WDGS_REQUIRE(f->settings.gaussian_mode >= 0.5f, WDGS_E_STATE, "TiledRasterizer.encodeDepth: the forward pass is in point-cloud render mode, which has no weights");
+    WDGS_TRY(require_composited_frame(op, "encodeDepth"));
     wdgs_device* d = op->dev;
     if (op->depth_width != op->width || op->depth_height != op->height) {   // a size change: the images are re-made per kind below
         bool any = false;
@@ -1153,11 +1162,8 @@ int wdgs_tiled_rasterizer_encode_depth(wdgs_tiled_rasterizer* op, uint32_t kinds
         WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledRasterizer.encodeDepth allocates a depth image on first use of its kind: run one eager encodeDepth before recording");
         WDGS_TRY(op->depth[k].alloc((size_t)op->width * op->height, true, d->stream));
     }
-    const int fo = wdgs_sorter_final_out_index(f->sorter.get());
-    WDGS_TRY(launch_depth_composite(d, f->settings, f->tile_info, f->splats, f->cfg.num_points, f->depths, op->ranges_used, static_cast<const u32*>(wdgs_sorter_keys(f->sorter.get(), fo)),
-                                    static_cast<const u32*>(wdgs_sorter_values(f->sorter.get(), fo)), f->stats, op->compat_caps ? 32u : 0u, (kinds & WDGS_DEPTH_WEIGHT_SUM) ? op->depth[2] : nullptr,
-                                    (kinds & WDGS_DEPTH_EXPECTED) ? op->depth[0] : nullptr, (kinds & WDGS_DEPTH_MEDIAN) ? op->depth[1] : nullptr, f->nf_stamp,
-                                    f->stats + FRAME_WORD));
+    WDGS_TRY(launch_depth_composite(d, composited_frame(op), op->fwd->depths, (kinds & WDGS_DEPTH_WEIGHT_SUM) ? op->depth[2] : nullptr,
+                                    (kinds & WDGS_DEPTH_EXPECTED) ? op->depth[0] : nullptr, (kinds & WDGS_DEPTH_MEDIAN) ? op->depth[1] : nullptr));
     op->depth_encoded = kinds;
     return WDGS_OK;
 }
@@ -1167,17 +1173,8 @@ int wdgs_tiled_rasterizer_encode_contribution(wdgs_tiled_rasterizer* op, void* s
     WDGS_REQUIRE(op, WDGS_E_INVALID, "wdgs_tiled_rasterizer_encode_contribution: null op");
     WDGS_REQUIRE(stats_dev && ((uintptr_t)stats_dev & 15u) == 0u, WDGS_E_INVALID,
                  "wdgs_tiled_rasterizer_encode_contribution: the statistics buffer must be non-null and 16-byte aligned (got %p)", stats_dev);
-    wdgs_tiled_forward* f = op->fwd;
-    WDGS_REQUIRE(op->encoded && f->encoded && op->ranges_used, WDGS_E_STATE,
-                 "TiledRasterizer.encodeContribution before encode: the weights are those of the frame encode rasterized");
-    WDGS_REQUIRE(op->width == f->cfg.viewport_width && op->height == f->cfg.viewport_height, WDGS_E_STATE,
-                 "TiledRasterizer.encodeContribution: the forward pass viewport changed to %ux%u since the last encode (%ux%u)", f->cfg.viewport_width,
-                 f->cfg.viewport_height, op->width, op->height);
-    WDGS_REQUIRE(f->settings.gaussian_mode >= 0.5f, WDGS_E_STATE, "TiledRasterizer.encodeContribution: the forward pass is in point-cloud render mode, which has no weights");
-    const int fo = wdgs_sorter_final_out_index(f->sorter.get());
-    return launch_contribution(op->dev, f->settings, f->tile_info, f->splats, f->cfg.num_points, op->ranges_used,
-                               static_cast<const u32*>(wdgs_sorter_keys(f->sorter.get(), fo)), static_cast<const u32*>(wdgs_sorter_values(f->sorter.get(), fo)),
-                               f->stats, op->compat_caps ? 32u : 0u, stats_dev, f->nf_stamp, f->stats + FRAME_WORD);
+    WDGS_TRY(require_composited_frame(op, "encodeContribution"));
+    return launch_contribution(op->dev, composited_frame(op), stats_dev);
 }
 int wdgs_tiled_rasterizer_get_depth(wdgs_tiled_rasterizer* op, uint32_t kind, void** out) {
     WDGS_REQUIRE(op && out, WDGS_E_INVALID, "wdgs_tiled_rasterizer_get_depth: null argument");

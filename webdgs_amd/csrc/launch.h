@@ -56,17 +56,27 @@ int launch_emit_scatter(wdgs_device* dev, u32 n, const u32* splats, const u32* d
 int launch_emit(wdgs_device* dev, u32 n, const u32* splats, const u32* depths, const u32* counts, u32* offsets, const u32* block_offsets, const RenderSettings& st,
                 const TileInfo& ti, u32* keys, u32* values, u32 capacity);
 
-// ---- raster.hip, depth.hip.  ranges u32[tiles + 1]; sorted_keys / sorted_vals u32[*count_ptr]; max_batches: 0 = unlimited; images are [W*H]; long_work nullable
-int launch_rasterize(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const u32* splats, u32 num_splats, const u32* ranges, const u32* sorted_keys,
-                     const u32* sorted_vals, const u32* count_ptr, u32 max_batches, u32* out_rgba8, float* out_alpha, u32* out_ncontrib, const u32* nf_stamp,
-                     const u32* nf_frame, const LongWork* long_work);
+// ---- raster.hip, depth.hip, contrib.hip: the kernels that walk the tiles' sorted entry lists (depth's and contribution's walk: tilewalk.h)
+// The frame the last encode composited, as its three walkers are handed it
+struct CompositedFrame {
+    RenderSettings st;
+    TileInfo ti;
+    const u32* splats;        // 6 words per Gaussian
+    u32 num_splats;
+    const u32* ranges;        // u32[tiles + 1]: the range table the encode used
+    const u32* sorted_keys;   // u32[*count_ptr]
+    const u32* sorted_vals;
+    const u32* count_ptr;     // the entry count
+    u32 max_batches;          // compat cap on a tile's list, in batches of 256 entries; 0 = unlimited
+    const u32* nf_stamp;      // (nullable) tiles of non-finite Splats
+    const u32* nf_frame;      // the frame word the stamps are compared with
+};
+// images are [W*H]; long_work nullable
+int launch_rasterize(wdgs_device* dev, const CompositedFrame& f, u32* out_rgba8, float* out_alpha, u32* out_ncontrib, const LongWork* long_work);
 // depths: the forward pass's depth words, u32[num_splats]; each of the three images nullable (that kind is not wanted)
-int launch_depth_composite(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const u32* splats, u32 num_splats, const u32* depths, const u32* ranges,
-                           const u32* sorted_keys, const u32* sorted_vals, const u32* count_ptr, u32 max_batches, float* out_weight, float* out_expected,
-                           float* out_median, const u32* nf_stamp, const u32* nf_frame);
-// contrib.hip.  stats: one 16-byte record { u64 sum_q; u32 max_bits; u32 pixels; } per Gaussian, added to
-int launch_contribution(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const u32* splats, u32 num_splats, const u32* ranges, const u32* sorted_keys,
-                        const u32* sorted_vals, const u32* count_ptr, u32 max_batches, void* stats, const u32* nf_stamp, const u32* nf_frame);
+int launch_depth_composite(wdgs_device* dev, const CompositedFrame& f, const u32* depths, float* out_weight, float* out_expected, float* out_median);
+// stats: one 16-byte record { u64 sum_q; u32 max_bits; u32 pixels; } per Gaussian, added to
+int launch_contribution(wdgs_device* dev, const CompositedFrame& f, void* stats);
 
 // ---- loss.hip, dssim.hip.  pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
 int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,

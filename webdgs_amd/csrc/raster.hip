@@ -491,16 +491,16 @@ __global__ __launch_bounds__(256, 8) void rasterize_kernel(RenderSettings settin
 
 }  // namespace
 
-int launch_rasterize(wdgs_device* dev, const RenderSettings& st, const TileInfo& ti, const u32* splats, u32 num_splats, const u32* ranges, const u32* sorted_keys,
-                     const u32* sorted_vals, const u32* count_ptr, u32 max_batches, u32* out_rgba8, float* out_alpha, u32* out_ncontrib, const u32* nf_stamp,
-                     const u32* nf_frame, const LongWork* long_work) {
+int launch_rasterize(wdgs_device* dev, const CompositedFrame& f, u32* out_rgba8, float* out_alpha, u32* out_ncontrib, const LongWork* long_work) {
+    const RenderSettings& st = f.st;
+    const TileInfo& ti = f.ti;
     if (ti.total_tiles == 0) return WDGS_OK;
-    const u32 max_entries = max_batches * 256u;  // compat cap: 32 batches x 256 splats per tile; 0 = unlimited
+    const u32 max_entries = f.max_batches * 256u;  // compat cap: 32 batches x 256 splats per tile; 0 = unlimited
     // (one-wave workgroups help backward_rasterize -- 303 -> 295.5 us -- but not this kernel: 119.2 vs 119.8 us, r03m; workgroup = tile stays)
     const u32 slots = ceil_div(ti.total_tiles, 8u) * 8u * 4u;   // 4 blocks per tile, tiles rounded up to a multiple of the 8 XCDs
     const u32 issue_priority = (slots <= 8192u) ? 1u : 0u;  // launches whose waves are all resident from the start
     const LongWork lw = long_work ? *long_work : LongWork{};
-#define RASTER_ARGS st, ti, splats, num_splats, ranges, sorted_keys, sorted_vals, count_ptr, max_entries, out_rgba8, out_alpha, out_ncontrib, issue_priority, nf_stamp, nf_frame, lw
+#define RASTER_ARGS st, ti, f.splats, f.num_splats, f.ranges, f.sorted_keys, f.sorted_vals, f.count_ptr, max_entries, out_rgba8, out_alpha, out_ncontrib, issue_priority, f.nf_stamp, f.nf_frame, lw
     if (st.gaussian_mode >= 0.5f) {
         // (long tile lists, longlist.h: Gaussian mode, uncapped lists)
         if (lw.hdr && lw.threshold && max_entries == 0u) WDGS_LAUNCH(dev, "rasterize", (rasterize_kernel<true, true>), dim3(ti.total_tiles), dim3(256), 0, RASTER_ARGS);
