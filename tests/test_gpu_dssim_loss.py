@@ -10,7 +10,7 @@ import dssim64
 import harness
 import ssim64
 from harness import assert_bits_equal
-from test_gpu_eval import KINDS, SIZES, _pair, _trainer, _views
+from test_gpu_eval import EDGE_SIZES, KINDS, SIZES, _pair, _trainer, _views
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +32,7 @@ def _loss_image(bwd, pred, targ, w, h):
     return bwd.getLossTextureView().read(np.float32).reshape(h, w, 4)
 
 
-@pytest.mark.parametrize("w,h", SIZES)
+@pytest.mark.parametrize("w,h", SIZES + EDGE_SIZES)
 def test_loss_image_matches_float64(hip_device, w, h):
     dev = hip_device
     bwd = _pass(dev, w, h, dssim_mode="gaussian")

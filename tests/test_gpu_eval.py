@@ -16,6 +16,10 @@ from harness import assert_bits_equal
 pytestmark = pytest.mark.gpu
 
 SIZES = [(1, 1), (7, 5), (10, 11), (33, 17), (160, 96), (1920, 1080), (3840, 2160)]
+# Image edges against the 32x32 tiles of ssim.hip and dssim.hip and the window's radius of 5: 32x33 a second tile row of one image row (three of a
+# thread's four vertical outputs outside the image); 37x38 a second tile column and row of 5 and 6 pixels (the edge at and just past the radius
+# inside the D-SSIM map region's halo); 65x43 a third tile column one pixel wide and a second tile row of exactly 11 rows, one full window.
+EDGE_SIZES = [(32, 33), (37, 38), (65, 43)]
 KINDS = ["noise", "smooth", "flat", "identical"]
 
 
@@ -37,7 +41,7 @@ def _pair(kind, w, h, seed):
     return a, b
 
 
-@pytest.mark.parametrize("w,h", SIZES)
+@pytest.mark.parametrize("w,h", SIZES + EDGE_SIZES)
 def test_image_ssim_matches_float64(hip_device, w, h):
     dev = hip_device
     for k, kind in enumerate(KINDS):

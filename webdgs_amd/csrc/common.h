@@ -141,13 +141,8 @@ static inline u32 bits_for(u32 v) {
     return b;
 }
 
-// SSIM (ssim.hip): workgroups per CU of its fixed grid
+// SSIM (ssim.hip): workgroups per CU of its fixed grid (the window itself: ssimwin.h)
 constexpr u32 SSIM_WG_PER_CU = 2;
-// The SSIM window (ssim.hip): 11 taps of a Gaussian of sigma 1.5, normalised to sum 1, each rounded once to f32.  The held-out SSIM and the
-// exact D-SSIM loss (dssim.hip) filter with the same values.
-constexpr u32 SSIM_TAPS = 11;
-struct SsimWindow { float g[SSIM_TAPS]; };
-const SsimWindow& ssim_window();
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
 using wdgs::DevMem;

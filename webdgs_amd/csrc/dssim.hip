@@ -1,7 +1,7 @@
 // Exact D-SSIM loss gradient (dssim_mode "gaussian"; no reference counterpart -- the reference's loss is loss.hip's heuristic).
 //
 // Loss per view: L = sum over pixels p and rgb channels c of  l1 |d| + l2 d^2 / 2 + ldssim (1 - S[p,c]),  d = x - y, values u8/255 through the
-// per-byte table of loss.hip and ssim.hip, S the SSIM map of wdgs_image_ssim_rgb8 (11x11 Gaussian window w, sigma 1.5, zero padding, C1 and C2
+// per-byte table of lossimage.h, S the SSIM map of wdgs_image_ssim_rgb8 (11x11 Gaussian window w, sigma 1.5, zero padding, C1 and C2
 // from the training config).  The loss image holds  xyz = l1 sgn(d) + l2 d - ldssim dSum(S)/dx,  w = 1.
 //
 // Gradient.  With A1 = 2 mx my + C1, A2 = 2 sxy + C2, B1 = mx^2 + my^2 + C1, B2 = sx^2 + sy^2 + C2, S = A1 A2 / (B1 B2), three per-pixel maps
@@ -20,15 +20,12 @@
 // horizontal then vertical pass, several outputs per thread so that neighbouring outputs share their taps), evaluates the three maps there,
 // and filters the maps down to the tile (horizontal, then vertical).  LDS: 65 KB, two workgroups per CU.
 #include "launch.h"
-#include "dmath.h"
+#include "lossimage.h"
+#include "ssimwin.h"
 
 namespace {
 
-WD_DEV float sgn(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
-
-constexpr u32 DT = 32;                    // output tile edge
-constexpr u32 DR = 5;                     // window radius
-constexpr u32 DK = SSIM_TAPS;             // 11 taps
+constexpr u32 DT = SSIM_TILE, DR = SSIM_RAD, DK = SSIM_TAPS;   // output tile edge, window radius, 11 taps
 constexpr u32 ME = DT + 2u * DR;          // 42: map region edge (tile + 5-pixel halo)
 constexpr u32 IE = ME + 2u * DR;          // 52: staged input edge (tile + 10-pixel halo)
 constexpr u32 IN_WORDS = IE * IE;         // 2704 texels per image
@@ -71,18 +68,13 @@ WD_DEV void dssim_maps(const float v[5], float s, float c1, float c2, float& ma,
 __global__ __launch_bounds__(256) void dssim_grad_kernel(u32 W, u32 H, const u32* __restrict__ pred, const u32* __restrict__ targ, wdgs_training_config cfg,
                                                           SsimWindow win, float4* __restrict__ out, int4* __restrict__ acc, u32 acc_quads,
                                                           const u32* __restrict__ acc_dirty) {
-    // the accumulator clear of loss_grad_kernel (loss.hip), which backward_rasterize relies on
-    if (acc && *acc_dirty != 0u) {
-        const int4 z = make_int4(0, 0, 0, 0);
-        const u32 nblk = gridDim.x * gridDim.y, blk = blockIdx.y * gridDim.x + blockIdx.x;
-        for (u32 i = blk * 256u + threadIdx.x; i < acc_quads; i += nblk * 256u) acc[i] = z;
-    }
+    clear_dirty_accumulators(acc, acc_quads, acc_dirty);   // as loss_grad_kernel: backward_rasterize relies on it
     __shared__ float s_lut[256];
     __shared__ float s_p[P_FLOATS];
     __shared__ float s_h[H_FLOATS];
     float* const s_x = s_p;              // [52][52]
     float* const s_y = s_p + IN_WORDS;   // [52][52]
-    s_lut[threadIdx.x] = wd_div((float)threadIdx.x, 255.0f);   // (each entry one correctly rounded division, as loss.hip)
+    unorm8_table_fill(s_lut);
 
     const int bx = (int)(blockIdx.x * DT), by = (int)(blockIdx.y * DT);
     // this thread's share of the staged texels (0 outside the image: zero padding)
@@ -118,14 +110,14 @@ __global__ __launch_bounds__(256) void dssim_grad_kernel(u32 W, u32 H, const u32
 #pragma unroll 1
     for (u32 c = 0; c < 3u; c++) {
         const u32 sh = 8u * c;
-        const float s = (s_lut[(a0 >> sh) & 0xFFu] + s_lut[(b0 >> sh) & 0xFFu]) * 0.5f;
+        const float s = (unorm8(s_lut, a0, sh) + unorm8(s_lut, b0, sh)) * 0.5f;
         // 1. the channel, shifted, into P
 #pragma unroll
         for (u32 i = 0; i < IN_PER_THREAD; i++) {
             const u32 t = threadIdx.x + 256u * i;
             if (t < IN_WORDS) {
-                s_x[t] = s_lut[(ra[i] >> sh) & 0xFFu] - s;
-                s_y[t] = s_lut[(rb[i] >> sh) & 0xFFu] - s;
+                s_x[t] = unorm8(s_lut, ra[i], sh) - s;
+                s_y[t] = unorm8(s_lut, rb[i], sh) - s;
             }
         }
         __syncthreads();
@@ -137,18 +129,10 @@ __global__ __launch_bounds__(256) void dssim_grad_kernel(u32 W, u32 H, const u32
             for (u32 j = 0; j < H1_OUT + DK - 1u; j++) { xs[j] = s_x[r * IE + c0 + j]; ys[j] = s_y[r * IE + c0 + j]; }
 #pragma unroll
             for (u32 o = 0; o < H1_OUT; o++) {
-                float mx = 0.f, my = 0.f, xx = 0.f, yy = 0.f, xy = 0.f;
+                float m[5];
+                window_moments(win, xs + o, ys + o, m);
 #pragma unroll
-                for (u32 k = 0; k < DK; k++) {
-                    const float x = xs[o + k], y = ys[o + k], w = win.g[k];
-                    mx = __builtin_fmaf(w, x, mx);
-                    my = __builtin_fmaf(w, y, my);
-                    xx = __builtin_fmaf(w, x * x, xx);
-                    yy = __builtin_fmaf(w, y * y, yy);
-                    xy = __builtin_fmaf(w, x * y, xy);
-                }
-                const u32 h = r * ME + c0 + o;
-                s_h[0u * IE * ME + h] = mx; s_h[1u * IE * ME + h] = my; s_h[2u * IE * ME + h] = xx; s_h[3u * IE * ME + h] = yy; s_h[4u * IE * ME + h] = xy;
+                for (u32 q = 0; q < 5u; q++) s_h[q * IE * ME + r * ME + c0 + o] = m[q];
             }
         }
         __syncthreads();
@@ -156,22 +140,7 @@ __global__ __launch_bounds__(256) void dssim_grad_kernel(u32 W, u32 H, const u32
         if (threadIdx.x < V1_ITEMS) {
             const u32 col = threadIdx.x % ME, r0 = (threadIdx.x / ME) * V1_OUT;
             float v[V1_OUT][5];
-#pragma unroll
-            for (u32 o = 0; o < V1_OUT; o++)
-#pragma unroll
-                for (u32 q = 0; q < 5u; q++) v[o][q] = 0.f;
-#pragma unroll
-            for (u32 j = 0; j < V1_OUT + DK - 1u; j++) {
-                float hq[5];
-#pragma unroll
-                for (u32 q = 0; q < 5u; q++) hq[q] = s_h[q * IE * ME + (r0 + j) * ME + col];
-#pragma unroll
-                for (u32 o = 0; o < V1_OUT; o++)
-                    if (j >= o && j - o < DK) {
-#pragma unroll
-                        for (u32 q = 0; q < 5u; q++) v[o][q] = __builtin_fmaf(win.g[j - o], hq[q], v[o][q]);
-                    }
-            }
+            window_slide(win, v, [&](u32 q, u32 j) { return s_h[q * IE * ME + (r0 + j) * ME + col]; });
             const int gx = bx - (int)DR + (int)col;
 #pragma unroll
             for (u32 o = 0; o < V1_OUT; o++) {
@@ -186,52 +155,22 @@ __global__ __launch_bounds__(256) void dssim_grad_kernel(u32 W, u32 H, const u32
         // 4. horizontal pass of the maps: N[m][r][col] for rows 0..41, columns 0..31, pitch NP, into H (lanes walk down the rows)
         for (u32 it = threadIdx.x; it < ME * (DT / H2_OUT); it += 256u) {
             const u32 r = it % ME, c0 = (it / ME) * H2_OUT;
-            float n[3][H2_OUT];
+            float n[H2_OUT][3];
+            window_slide(win, n, [&](u32 m, u32 j) { return s_p[m * ME * MP + r * MP + c0 + j]; });
 #pragma unroll
             for (u32 m = 0; m < 3u; m++)
 #pragma unroll
-                for (u32 o = 0; o < H2_OUT; o++) n[m][o] = 0.f;
-#pragma unroll
-            for (u32 j = 0; j < H2_OUT + DK - 1u; j++) {
-                float t[3];
-#pragma unroll
-                for (u32 m = 0; m < 3u; m++) t[m] = s_p[m * ME * MP + r * MP + c0 + j];
-#pragma unroll
-                for (u32 o = 0; o < H2_OUT; o++)
-                    if (j >= o && j - o < DK) {
-#pragma unroll
-                        for (u32 m = 0; m < 3u; m++) n[m][o] = __builtin_fmaf(win.g[j - o], t[m], n[m][o]);
-                    }
-            }
-#pragma unroll
-            for (u32 m = 0; m < 3u; m++)
-#pragma unroll
-                for (u32 o = 0; o < H2_OUT; o++) s_h[m * ME * NP + r * NP + c0 + o] = n[m][o];
+                for (u32 o = 0; o < H2_OUT; o++) s_h[m * ME * NP + r * NP + c0 + o] = n[o][m];
         }
         __syncthreads();
         // 5. vertical pass of the maps down to this thread's four pixels, and the gradient of the channel's SSIM sum
         {
-            float n[3][V2_OUT];
-#pragma unroll
-            for (u32 m = 0; m < 3u; m++)
-#pragma unroll
-                for (u32 o = 0; o < V2_OUT; o++) n[m][o] = 0.f;
-#pragma unroll
-            for (u32 j = 0; j < V2_OUT + DK - 1u; j++) {
-                float t[3];
-#pragma unroll
-                for (u32 m = 0; m < 3u; m++) t[m] = s_h[m * ME * NP + (ly0 + j) * NP + lx];
-#pragma unroll
-                for (u32 o = 0; o < V2_OUT; o++)
-                    if (j >= o && j - o < DK) {
-#pragma unroll
-                        for (u32 m = 0; m < 3u; m++) n[m][o] = __builtin_fmaf(win.g[j - o], t[m], n[m][o]);
-                    }
-            }
+            float n[V2_OUT][3];
+            window_slide(win, n, [&](u32 m, u32 j) { return s_h[m * ME * NP + (ly0 + j) * NP + lx]; });
 #pragma unroll
             for (u32 o = 0; o < V2_OUT; o++) {
-                const float xp = s_lut[(pa[o] >> sh) & 0xFFu] - s, yp = s_lut[(pb[o] >> sh) & 0xFFu] - s;
-                g[c][o] = (n[0][o] + xp * n[1][o]) + (yp - xp) * n[2][o];
+                const float xp = unorm8(s_lut, pa[o], sh) - s, yp = unorm8(s_lut, pb[o], sh) - s;
+                g[c][o] = (n[o][0] + xp * n[o][1]) + (yp - xp) * n[o][2];
             }
         }
         // (no barrier here: the next channel writes P, last read in pass 4, and reads H only after its own first barrier)
@@ -240,13 +179,10 @@ __global__ __launch_bounds__(256) void dssim_grad_kernel(u32 W, u32 H, const u32
     for (u32 o = 0; o < V2_OUT; o++) {
         const u32 oy = (u32)by + ly0 + o;
         if (ox >= W || oy >= H) continue;
-        const float d[3] = {s_lut[pa[o] & 0xFFu] - s_lut[pb[o] & 0xFFu], s_lut[(pa[o] >> 8) & 0xFFu] - s_lut[(pb[o] >> 8) & 0xFFu],
-                            s_lut[(pa[o] >> 16) & 0xFFu] - s_lut[(pb[o] >> 16) & 0xFFu]};
         float4 r;
-        // the L1 and L2 terms are loss.hip's expressions
-        r.x = cfg.lambda_l1 * sgn(d[0]) + cfg.lambda_l2 * d[0] - cfg.lambda_dssim * g[0][o];
-        r.y = cfg.lambda_l1 * sgn(d[1]) + cfg.lambda_l2 * d[1] - cfg.lambda_dssim * g[1][o];
-        r.z = cfg.lambda_l1 * sgn(d[2]) + cfg.lambda_l2 * d[2] - cfg.lambda_dssim * g[2][o];
+        r.x = loss_l1_l2(cfg, unorm8(s_lut, pa[o], 0u) - unorm8(s_lut, pb[o], 0u)) - cfg.lambda_dssim * g[0][o];
+        r.y = loss_l1_l2(cfg, unorm8(s_lut, pa[o], 8u) - unorm8(s_lut, pb[o], 8u)) - cfg.lambda_dssim * g[1][o];
+        r.z = loss_l1_l2(cfg, unorm8(s_lut, pa[o], 16u) - unorm8(s_lut, pb[o], 16u)) - cfg.lambda_dssim * g[2][o];
         r.w = 1.0f;
         out[(size_t)oy * W + ox] = r;
     }
@@ -255,7 +191,7 @@ __global__ __launch_bounds__(256) void dssim_grad_kernel(u32 W, u32 H, const u32
 }  // namespace
 
 // Same arguments and contract as launch_loss_grad (loss.hip), including the accumulator clear when acc is given.  lambda_dssim == 0 leaves
-// only the L1 and L2 terms, which loss_grad computes with the same expressions: that launch is taken then, so the two modes agree bit for bit.
+// only the L1 and L2 terms, which loss_grad computes with the same function (lossimage.h): that launch is taken then, so the two modes agree bit for bit.
 int launch_dssim_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
                       const u32* acc_dirty) {
     if (W == 0 || H == 0) return WDGS_OK;

@@ -8,13 +8,11 @@
 // The window sums keep the reference's order (dy outer, dx inner); the second-moment accumulations are FMAs, the contraction the
 // parity oracle pins (WGSL leaves it open).
 #include "launch.h"
-#include "dmath.h"
+#include "lossimage.h"
 
 namespace {
 
 typedef wd_pair f2;  // component-wise scalar arithmetic (dmath.h)
-
-WD_DEV float sgn(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
 
 constexpr u32 LT = 32;       // tile width in pixels
 constexpr u32 LH = LT + 4;   // halo width in texels
@@ -28,14 +26,7 @@ template <u32 PPT>
 __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32* __restrict__ pred, const u32* __restrict__ targ,
                                                          wdgs_training_config cfg, float4* __restrict__ out, int4* __restrict__ acc, u32 acc_quads,
                                                          const u32* __restrict__ acc_dirty) {
-    // clearBuffer x4 of the gradient accumulators (tiled-backward-pass.ts:624-627) rides on this kernel, which precedes the backward
-    // rasterization anyway: the accumulators' state word (backward_raster.hip) says whether anything has to be cleared at all -- after a
-    // consuming K17 nothing has -- so the clear is one scalar load here instead of a launch of its own.
-    if (acc && *acc_dirty != 0u) {
-        const int4 z = make_int4(0, 0, 0, 0);
-        const u32 nblk = gridDim.x * gridDim.y, blk = blockIdx.y * gridDim.x + blockIdx.x;
-        for (u32 i = blk * 256u + threadIdx.x; i < acc_quads; i += nblk * 256u) acc[i] = z;
-    }
+    clear_dirty_accumulators(acc, acc_quads, acc_dirty);   // (lossimage.h: why it rides on this kernel)
     __shared__ float s_lut[256];
     // A thread row is 32 lanes on 32 consecutive texels, so each 16-lane group of a ds_read_b128 covers 256 contiguous
     // bytes = every bank once, whatever the row stride.
@@ -45,7 +36,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32*
     constexpr u32 TH = 8u * PPT, HH = TH + 4u;   // tile and halo height
     __shared__ float4 sp[HH][LH];
     __shared__ float2 st[HH][LH];
-    s_lut[threadIdx.x] = wd_div((float)threadIdx.x, 255.0f);
+    unorm8_table_fill(s_lut);
     __syncthreads();
     const int bx = blockIdx.x * LT, by = blockIdx.y * TH;
     for (u32 t = threadIdx.x; t < HH * LH; t += 256u) {
@@ -54,8 +45,8 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32*
         gx = gx < 0 ? 0 : (gx > (int)W - 1 ? (int)W - 1 : gx);
         gy = gy < 0 ? 0 : (gy > (int)H - 1 ? (int)H - 1 : gy);
         const u32 a = pred[(size_t)gy * W + gx], b = targ[(size_t)gy * W + gx];
-        sp[hy][hx] = make_float4(s_lut[a & 0xFFu], s_lut[(a >> 8) & 0xFFu], s_lut[(a >> 16) & 0xFFu], s_lut[b & 0xFFu]);
-        st[hy][hx] = make_float2(s_lut[(b >> 8) & 0xFFu], s_lut[(b >> 16) & 0xFFu]);
+        sp[hy][hx] = make_float4(unorm8(s_lut, a, 0u), unorm8(s_lut, a, 8u), unorm8(s_lut, a, 16u), unorm8(s_lut, b, 0u));
+        st[hy][hx] = make_float2(unorm8(s_lut, b, 8u), unorm8(s_lut, b, 16u));
     }
     __syncthreads();
     // Each thread owns PPT vertically adjacent pixels: their 5x5 windows share 8 x 5 texels, so a texel is read from LDS once
@@ -159,9 +150,9 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32*
             }
         }
         float4 o;
-        o.x = cfg.lambda_l1 * sgn(d[0]) + cfg.lambda_l2 * d[0] + cfg.lambda_dssim * g[0];
-        o.y = cfg.lambda_l1 * sgn(d[1]) + cfg.lambda_l2 * d[1] + cfg.lambda_dssim * g[1];
-        o.z = cfg.lambda_l1 * sgn(d[2]) + cfg.lambda_l2 * d[2] + cfg.lambda_dssim * g[2];
+        o.x = loss_l1_l2(cfg, d[0]) + cfg.lambda_dssim * g[0];
+        o.y = loss_l1_l2(cfg, d[1]) + cfg.lambda_dssim * g[1];
+        o.z = loss_l1_l2(cfg, d[2]) + cfg.lambda_dssim * g[2];
         o.w = 1.0f;
         out[(size_t)y * W + x] = o;
     }

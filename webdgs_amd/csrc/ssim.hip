@@ -18,16 +18,14 @@
 // that never computes an SSIM allocates nothing.
 #include <cmath>
 
-#include "common.h"
-#include "dmath.h"
+#include "lossimage.h"
+#include "ssimwin.h"
 
 namespace {
 
-constexpr u32 ST = 32;              // output tile edge
-constexpr u32 RAD = 5;              // window radius: 11 taps
-constexpr u32 HT = ST + 2u * RAD;   // staged edge (tile + halo)
+constexpr u32 ST = SSIM_TILE, RAD = SSIM_RAD;   // output tile edge, window radius
+constexpr u32 HT = ST + 2u * RAD;               // staged edge (tile + halo)
 constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
-static_assert(2u * RAD + 1u == SSIM_TAPS, "ssim window size");
 
 __global__ __launch_bounds__(256) void image_ssim_kernel(const u32* __restrict__ a, const u32* __restrict__ b, u32 W, u32 H, u32 tiles_x, u32 n_tiles,
                                                           SsimWindow win, float* __restrict__ map, double* __restrict__ partials) {
@@ -36,7 +34,7 @@ __global__ __launch_bounds__(256) void image_ssim_kernel(const u32* __restrict__
     __shared__ float s_x[HT][HT], s_y[HT][HT];     // one channel, shifted
     __shared__ float s_h[5][HT][ST];               // horizontal pass: E[x], E[y], E[x^2], E[y^2], E[xy] along rows
     __shared__ double s_w[4];
-    s_lut[threadIdx.x] = wd_div((float)threadIdx.x, 255.0f);   // (each entry one correctly rounded division, as loss.hip)
+    unorm8_table_fill(s_lut);
     const u32 lx = threadIdx.x & (ST - 1u), ly0 = (threadIdx.x / ST) * 4u;
     double acc = 0.0;
     for (u32 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -54,46 +52,24 @@ __global__ __launch_bounds__(256) void image_ssim_kernel(const u32* __restrict__
 #pragma unroll 1
         for (u32 c = 0; c < 3u; c++) {
             const u32 sh = 8u * c;
-            const float s = (s_lut[(s_a[RAD][RAD] >> sh) & 0xFFu] + s_lut[(s_b[RAD][RAD] >> sh) & 0xFFu]) * 0.5f;
+            const float s = (unorm8(s_lut, s_a[RAD][RAD], sh) + unorm8(s_lut, s_b[RAD][RAD], sh)) * 0.5f;
             for (u32 t = threadIdx.x; t < HT * HT; t += 256u) {
                 const u32 hy = t / HT, hx = t % HT;
-                s_x[hy][hx] = s_lut[(s_a[hy][hx] >> sh) & 0xFFu] - s;
-                s_y[hy][hx] = s_lut[(s_b[hy][hx] >> sh) & 0xFFu] - s;
+                s_x[hy][hx] = unorm8(s_lut, s_a[hy][hx], sh) - s;
+                s_y[hy][hx] = unorm8(s_lut, s_b[hy][hx], sh) - s;
             }
             __syncthreads();
             for (u32 t = threadIdx.x; t < HT * ST; t += 256u) {
                 const u32 r = t / ST, col = t % ST;
-                float mx = 0.f, my = 0.f, xx = 0.f, yy = 0.f, xy = 0.f;
+                float m[5];
+                window_moments(win, &s_x[r][col], &s_y[r][col], m);
 #pragma unroll
-                for (u32 k = 0; k < 2u * RAD + 1u; k++) {
-                    const float x = s_x[r][col + k], y = s_y[r][col + k], g = win.g[k];
-                    mx = __builtin_fmaf(g, x, mx);
-                    my = __builtin_fmaf(g, y, my);
-                    xx = __builtin_fmaf(g, x * x, xx);
-                    yy = __builtin_fmaf(g, y * y, yy);
-                    xy = __builtin_fmaf(g, x * y, xy);
-                }
-                s_h[0][r][col] = mx; s_h[1][r][col] = my; s_h[2][r][col] = xx; s_h[3][r][col] = yy; s_h[4][r][col] = xy;
+                for (u32 q = 0; q < 5u; q++) s_h[q][r][col] = m[q];
             }
             __syncthreads();
-            // vertical: four vertically adjacent output pixels per thread share 14 rows of the horizontal moments; each pixel's taps in order k = 0..10
+            // vertical: four vertically adjacent output pixels per thread share 14 rows of the horizontal moments
             float v[4][5];
-#pragma unroll
-            for (u32 p = 0; p < 4u; p++)
-#pragma unroll
-                for (u32 q = 0; q < 5u; q++) v[p][q] = 0.f;
-#pragma unroll
-            for (u32 j = 0; j < 4u + 2u * RAD; j++) {
-                float hq[5];
-#pragma unroll
-                for (u32 q = 0; q < 5u; q++) hq[q] = s_h[q][ly0 + j][lx];
-#pragma unroll
-                for (u32 p = 0; p < 4u; p++)
-                    if (j >= p && j - p <= 2u * RAD) {
-#pragma unroll
-                        for (u32 q = 0; q < 5u; q++) v[p][q] = __builtin_fmaf(win.g[j - p], hq[q], v[p][q]);
-                    }
-            }
+            window_slide(win, v, [&](u32 q, u32 j) { return s_h[q][ly0 + j][lx]; });
             const u32 gx = (u32)bx + lx;
 #pragma unroll
             for (u32 p = 0; p < 4u; p++) {
