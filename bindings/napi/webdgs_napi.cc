@@ -325,6 +325,37 @@ static napi_value depthToRgba8(napi_env env, napi_callback_info info) {  // (dev
                                          (float)get_f64(env, argv[5]), get_ptr(env, argv[6])));
     return js_undefined(env);
 }
+// Normal maps (include/webdgs.h: wdgs_tiled_rasterizer_encode_normal / get_normal / get_gaussian_normals, wdgs_depth_to_normals, wdgs_normal_agreement,
+// wdgs_normal_to_rgba8; the reference renders colour only and has no counterpart)
+static napi_value tiledRasterizerEncodeNormal(napi_env env, napi_callback_info info) {  // (op, gaussiansPtr, cameraPtr)
+    ARGS(3);
+    WDGS_OK_OR_THROW(wdgs_tiled_rasterizer_encode_normal((wdgs_tiled_rasterizer*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2])));
+    return js_undefined(env);
+}
+static napi_value tiledRasterizerGetNormal(napi_env env, napi_callback_info info) {  // (op, which: 0 = the rgba32f image, 1 = the packed per-Gaussian words) -> device pointer
+    ARGS(2);
+    void* p = nullptr;
+    wdgs_tiled_rasterizer* op = (wdgs_tiled_rasterizer*)get_ptr(env, argv[0]);
+    WDGS_OK_OR_THROW(get_u32(env, argv[1]) ? wdgs_tiled_rasterizer_get_gaussian_normals(op, &p) : wdgs_tiled_rasterizer_get_normal(op, &p));
+    return make_ptr(env, p);
+}
+static napi_value depthToNormals(napi_env env, napi_callback_info info) {  // (device, depthPtr, width, height, p00, p11, normalsPtr)
+    ARGS(7);
+    WDGS_OK_OR_THROW(wdgs_depth_to_normals((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]), (float)get_f64(env, argv[4]),
+                                           (float)get_f64(env, argv[5]), get_ptr(env, argv[6])));
+    return js_undefined(env);
+}
+static napi_value normalAgreement(napi_env env, napi_callback_info info) {  // (device, normalPtr, depthNormalsPtr, width, height, outPtr: u64[3])
+    ARGS(6);
+    WDGS_OK_OR_THROW(wdgs_normal_agreement((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_u32(env, argv[3]), get_u32(env, argv[4]),
+                                           get_ptr(env, argv[5])));
+    return js_undefined(env);
+}
+static napi_value normalToRgba8(napi_env env, napi_callback_info info) {  // (device, normalPtr, width, height, rgba8Ptr)
+    ARGS(5);
+    WDGS_OK_OR_THROW(wdgs_normal_to_rgba8((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]), get_ptr(env, argv[4])));
+    return js_undefined(env);
+}
 // Per-Gaussian render contribution (include/webdgs.h: wdgs_tiled_rasterizer_encode_contribution, wdgs_contribution_rule,
 // wdgs_densify_prune_encode_contribution_decision; no reference counterpart)
 static napi_value tiledRasterizerEncodeContribution(napi_env env, napi_callback_info info) {  // (op, statsPtr): adds into the caller's records
@@ -931,6 +962,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(optimizerCreate); EXPORT_FN(optimizerStep); EXPORT_FN(optimizerGetIteration); EXPORT_FN(optimizerDestroy);
     EXPORT_FN(tiledForwardSet); EXPORT_FN(tiledForwardCheck); EXPORT_FN(tiledForwardSetLongLists); EXPORT_FN(tiledForwardLongListStats); EXPORT_FN(tiledRasterizerBlit); EXPORT_FN(bufferClear);
     EXPORT_FN(tiledRasterizerEncodeDepth); EXPORT_FN(tiledRasterizerGetDepth); EXPORT_FN(depthToRgba8);
+    EXPORT_FN(tiledRasterizerEncodeNormal); EXPORT_FN(tiledRasterizerGetNormal); EXPORT_FN(depthToNormals); EXPORT_FN(normalAgreement); EXPORT_FN(normalToRgba8);
     EXPORT_FN(tiledRasterizerEncodeContribution); EXPORT_FN(densifyContributionDecision);
     EXPORT_FN(encoderBegin); EXPORT_FN(encoderFinish); EXPORT_FN(queueSubmit); EXPORT_FN(commandBufferDestroy); EXPORT_FN(queueOnSubmittedWorkDone);
     EXPORT_FN(tiledBackwardMetric); EXPORT_FN(tiledBackwardGet); EXPORT_FN(downsampleRGBA8); EXPORT_FN(imageSSE); EXPORT_FN(imageSSIM);

@@ -67,6 +67,9 @@ export class Trainer {
   /** PSNR (exact SSE kernel) and SSIM (imageSSIM) of the current model on the evaluation views ('eval') or training views ('train'); drains the
    *  pipeline, leaves the training trajectory untouched. */
   evaluate(viewIds?: number[] | null, split?: 'eval' | 'train'): EvaluationResult;
+  /** Agreement of the composited normals with the normals of the model's own depth map, per view and weight-averaged over all (1 - cos: a surface
+   *  scores near 0); rendered through evaluate's passes, training untouched.  No reference counterpart. */
+  normalConsistency(viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): NormalConsistencyResult;
   /** Per-Gaussian render contribution accumulated over the views (default: all training views); no reference counterpart. */
   contributionStats(viewIds?: number[] | null, split?: 'eval' | 'train'): ContributionRecords & { views: number[] };
   /** Contribution-based pruning: kept iff every criterion given is met; fraction f prunes the Gaussians below the k-th smallest sum_q, k = floor(f N). */
@@ -85,6 +88,9 @@ export class Trainer {
 }
 export interface EvaluationResult {
   iteration: number; views: number[]; psnr: number[]; ssim: number[]; sse: number[]; mean_psnr: number; mean_ssim: number; ms: number;
+}
+export interface NormalConsistencyResult {
+  iteration: number; views: number[]; value: number[]; pixels: number[]; sum_e: number[]; sum_a: number[]; mean: number; ms: number;
 }
 export function cameraBlockFor(block: Float32Array, width: number, height: number): Float32Array;
 export function mat4Inverse(m: ArrayLike<number>): Float32Array;

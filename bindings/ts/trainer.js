@@ -762,15 +762,21 @@ class Trainer {
    *  sse, mean_psnr, mean_ssim, ms }.  Drains the pipeline, renders every view through passes of its own, writes view i's SSE and SSIM into slot i
    *  of two device arrays and reads them back once; a view that overflowed its tile-entry lists is rendered again with larger lists.  Training is
    *  untouched (no random draw, no training pass, no recording dropped).  Per rank, no collective.  Same results as the Python host's. */
-  evaluate(viewIds, split) {
-    split = split || 'eval';
-    if (split !== 'eval' && split !== 'train') throw new Error(`evaluate: split must be 'eval' or 'train', not ${split}`);
-    if (!this.pointCloud) throw new Error('evaluate: no point cloud');
-    const t0 = Date.now();
+  /** { cams, imgs, bufs, ids } of a split, checked: what evaluate, normalConsistency and contributionStats start with. */
+  evalViews(what, viewIds, split) {
+    if (split !== 'eval' && split !== 'train') throw new Error(`${what}: split must be 'eval' or 'train', not ${split}`);
+    if (!this.pointCloud) throw new Error(`${what}: no point cloud`);
     const [cams, imgs, bufs] = split === 'eval' ? [this.evalCameras, this.evalImages, this.evalCameraBuffers] : [this.trainCameras, this.images, this.cameraBuffers];
     const ids = viewIds === undefined || viewIds === null ? cams.map((_, i) => i) : viewIds.map((v) => Math.floor(v));
-    for (const v of ids) if (!(v >= 0 && v < cams.length)) throw new RangeError(`evaluate: view ${v} of ${cams.length} (${split})`);
-    try { this.drain(); } catch (e) { if (!this.growTileEntryCapacity(e)) throw e; }
+    for (const v of ids) if (!(v >= 0 && v < cams.length)) throw new RangeError(`${what}: view ${v} of ${cams.length} (${split})`);
+    return { cams, imgs, bufs, ids };
+  }
+  /** Drains the pipeline in front of renders through the evaluation passes (a training step's overflow is met as step() would have met it). */
+  evalDrain() { try { this.drain(); } catch (e) { if (!this.growTileEntryCapacity(e)) throw e; } }
+  evaluate(viewIds, split) {
+    const { imgs, bufs, ids } = this.evalViews('evaluate', viewIds, split || 'eval');
+    const t0 = Date.now();
+    this.evalDrain();
     const n = ids.length, slots = Math.max(1, n);
     const out = this.device.createBuffer({ size: 16 * slots, label: 'evaluation sse + ssim' });
     this.renderEvalViews(ids, imgs, bufs, (i, v, s, w, h) => {
@@ -812,16 +818,43 @@ class Trainer {
     }
   }
 
+  // ---------------------------------------------------------------- normal consistency (DESIGN.md section 12; no reference counterpart)
+  /** How well the composited normals of the current model agree with the normals of its own depth map, per view: { iteration, views, value, pixels,
+   *  sum_e, sum_a, mean, ms } -- value[i] the weight-averaged 1 - cos of normalAgreement between encodeNormal's image and depthToNormals of the
+   *  `depthKind` ('median' | 'expected') depth image, mean the same average over all views' pixels.  Rendered through evaluate's passes with its
+   *  isolation; evaluate()'s result is what it was.  Same results as the Python host's. */
+  normalConsistency(viewIds, split, depthKind) {
+    split = split || 'eval'; depthKind = depthKind || 'median';
+    if (depthKind !== 'median' && depthKind !== 'expected') throw new Error(`normalConsistency: depthKind must be 'median' or 'expected', not ${depthKind}`);
+    const { cams, imgs, bufs, ids } = this.evalViews('normalConsistency', viewIds, split);
+    const t0 = Date.now();
+    this.evalDrain();
+    const n = ids.length, slots = Math.max(1, n);
+    const out = this.device.createBuffer({ size: 24 * slots, label: 'normal agreement sums' });
+    const scratch = this.device.createBuffer({ size: 16 * Math.max(1, ...ids.map((v) => imgs[v].width * imgs[v].height)), label: 'depth normals' });
+    let raw;
+    try {
+      this.renderEvalViews(ids, imgs, bufs, (i, v, s, w, h) => {
+        s.rasterizer.encodeDepth(null, [depthKind]);
+        s.rasterizer.encodeNormal(null);
+        hip.depthToNormals(this.device, s.rasterizer.getDepthTextureView(depthKind), w, h, cams[v].camera, scratch);
+        hip.encodeNormalAgreement(this.device, s.rasterizer.getNormalTextureView(), scratch, w, h, this.device.view(out.ptr + BigInt(24 * i), 24));
+      }, null, 'normalConsistency');
+      raw = n ? this.device.readBuffer(out, 24 * slots) : new ArrayBuffer(24);
+    } finally { scratch.destroy(); out.destroy(); }
+    const sums = [...new BigUint64Array(raw, 0, 3 * n)].map(Number);
+    const col = (k) => ids.map((_, i) => sums[3 * i + k]);
+    const sum_e = col(0), sum_a = col(1), pixels = col(2), total = (a) => a.reduce((x, y) => x + y, 0);
+    return { iteration: this.iteration, views: ids, value: sum_e.map((e, i) => (sum_a[i] ? e / sum_a[i] : NaN)), pixels, sum_e, sum_a,
+      mean: total(sum_a) ? total(sum_e) / total(sum_a) : NaN, ms: Date.now() - t0 };
+  }
+
   // ---------------------------------------------------------------- render contribution and contribution-based pruning (no reference counterpart)
   /** { stats, ids }: the views' contribution records (DESIGN.md section 11) accumulated into one new device buffer. */
   contributionBuffer(viewIds, split, what) {
-    if (split !== 'eval' && split !== 'train') throw new Error(`${what}: split must be 'eval' or 'train', not ${split}`);
-    if (!this.pointCloud) throw new Error(`${what}: no point cloud`);
-    const [cams, imgs, bufs] = split === 'eval' ? [this.evalCameras, this.evalImages, this.evalCameraBuffers] : [this.trainCameras, this.images, this.cameraBuffers];
-    const ids = viewIds === undefined || viewIds === null ? cams.map((_, i) => i) : viewIds.map((v) => Math.floor(v));
-    for (const v of ids) if (!(v >= 0 && v < cams.length)) throw new RangeError(`${what}: view ${v} of ${cams.length} (${split})`);
+    const { imgs, bufs, ids } = this.evalViews(what, viewIds, split);
     if (ids.reduce((a, v) => a + imgs[v].width * imgs[v].height, 0) >= 2 ** 32) throw new RangeError(`${what}: the views hold 2^32 pixels or more; the per-Gaussian pixel count is 32 bits wide`);
-    try { this.drain(); } catch (e) { if (!this.growTileEntryCapacity(e)) throw e; }
+    this.evalDrain();
     const stats = hip.createContributionBuffer(this.device, this.pointCloud.num_points);
     try {
       this.renderEvalViews(ids, imgs, bufs, (i, v, s) => s.rasterizer.encodeContribution(null, stats), () => hip.addon.bufferClear(this.device.handle, stats.ptr, stats.size), what);

@@ -17,6 +17,10 @@ export class Viewer {
   readFrame(): Uint8Array;
   /** The current camera's depth image (width * height f32), rendered in gaussian mode; the render mode is left as it was.  No reference counterpart. */
   renderDepth(kind?: DepthKind): Float32Array;
+  /** The current camera's normal map (width * height * 4 f32: N.x, N.y, N.z, A), rendered in gaussian mode; the render mode is left as it was.  No reference counterpart. */
+  renderNormals(): Float32Array;
+  /** The normal map as a colour PNG (facing the camera: blue).  No reference counterpart. */
+  saveNormalPNG(file: string): void;
   savePNG(file: string): void;
   destroy(): void;
 }

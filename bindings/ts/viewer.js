@@ -117,6 +117,36 @@ class Viewer {
     this.settleCapacity(encode);
     return new Float32Array(this.device.readBuffer(this.rasterizer.getDepthTextureView(k), 4 * w * h));
   }
+  /** The current camera's normal map as a Float32Array of width * height * 4 values { N.x, N.y, N.z, A } (view space: x right, y down, z forward; N
+   *  un-normalised, |N| <= A), rendered in gaussian mode through the viewer's own passes whatever its render mode, which is left as it was
+   *  (synchronises).  No reference counterpart. */
+  renderNormals() {
+    if (!this.forwardPass || !this.rasterizer || !this.pointCloud) throw new Error('Viewer.renderNormals: no point cloud set');
+    const w = this.canvas.width, h = this.canvas.height;
+    const encode = () => {
+      this.forwardPass.setRenderMode('gaussian');   // as depth: weights exist in gaussian mode only; the viewer's own mode is put back below
+      try {
+        this.forwardPass.encode(null);
+        this.rasterizer.encode(null, w, h);
+        this.rasterizer.encodeNormal(null);
+      } finally {
+        this.forwardPass.setRenderMode(this.settings.renderMode === undefined ? 'pointcloud' : this.settings.renderMode);
+      }
+    };
+    encode();
+    this.settleCapacity(encode);
+    return new Float32Array(this.device.readBuffer(this.rasterizer.getNormalTextureView(), 16 * w * h));
+  }
+  /** The normal map as the usual colour PNG (normalToRGBA8: a surface that faces the camera is blue, no normal black). */
+  saveNormalPNG(file) {
+    this.renderNormals();
+    const w = this.canvas.width, h = this.canvas.height;
+    const out = this.device.createBuffer({ size: 4 * w * h, label: 'normal presentation' });
+    try {
+      hip.normalToRGBA8(this.device, this.rasterizer.getNormalTextureView(), w, h, out);
+      fs.writeFileSync(file, encodePNG(new Uint8Array(this.device.readBuffer(out, 4 * w * h)), w, h));
+    } finally { out.destroy(); }
+  }
   savePNG(file) { const f = this.currentTexture(); fs.writeFileSync(file, encodePNG(this.readFrame(), f.width, f.height)); }
   destroy() {
     if (this.forwardPass) this.forwardPass.destroy();

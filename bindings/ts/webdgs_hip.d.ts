@@ -128,6 +128,12 @@ export class TiledRasterizer {
   encodeContribution(encoder: HipEncoder | null, statsBuffer: HipBuffer): void;
   /** f32[W*H] of one kind the last encodeDepth wrote (default 'expected'). */
   getDepthTextureView(kind?: DepthKind): HipBuffer;
+  /** The normal map of the frame the last encode rasterized (no reference counterpart): per-Gaussian view-space normals, composited with the colour's weights. */
+  encodeNormal(encoder: HipEncoder | null): void;
+  /** rgba32f[W*H] { N.x, N.y, N.z, A } of the last encodeNormal (N un-normalised: |N| <= A). */
+  getNormalTextureView(): HipBuffer;
+  /** u32[numPoints]: the packed per-Gaussian normals of the last encodeNormal (NO_NORMAL: none). */
+  getGaussianNormals(): HipBuffer;
   blitToTexture(encoder: HipEncoder | null, target: HipBuffer & { width?: number; height?: number }, clearColor?: { r: number; g: number; b: number; a: number }): void;
   destroy(): void;
 }
@@ -234,6 +240,18 @@ export function readContribution(buffer: HipBuffer, n: number): ContributionReco
 /** A depth image as rgba8 for presentation: inverse depth between near (white) and far (black), depth 0 black.  No reference counterpart. */
 export function depthToRGBA8(device: HipDevice, depth: HipBuffer, width: number, height: number, near: number, far: number, target: HipBuffer): void;
 export function imageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: number, height: number, map?: HipBuffer | null): number;
+/** The packed word of a Gaussian without a normal.  No reference counterpart. */
+export const NO_NORMAL: 0x80008000;
+export interface NormalAgreement { sum_e: number; sum_a: number; pixels: number; value: number }
+/** The normals of an f32 depth image (central differences of its back-projection): rgba32f { n, 1 }, zero where a neighbour is missing.  `camera`: the
+ *  68-float block or [proj[0][0], proj[1][1]].  No reference counterpart. */
+export function depthToNormals(device: HipDevice, depth: HipBuffer, width: number, height: number, camera: ArrayLike<number>, target: HipBuffer): void;
+/** Stream-ordered normalAgreement: three u64 { sum e, sum a, pixels } into the first 24 bytes of `out`. */
+export function encodeNormalAgreement(device: HipDevice, normal: HipBuffer, depthNormals: HipBuffer, width: number, height: number, out: HipBuffer): void;
+/** The weight-averaged 1 - cos between a composited normal image and a depth-normal image, with its exact integer sums (synchronises).  No reference counterpart. */
+export function normalAgreement(device: HipDevice, normal: HipBuffer, depthNormals: HipBuffer, width: number, height: number): NormalAgreement;
+/** A normal image as rgba8 for presentation (facing the camera: blue; no normal: black).  No reference counterpart. */
+export function normalToRGBA8(device: HipDevice, normal: HipBuffer, width: number, height: number, target: HipBuffer): void;
 /** The C-ABI communicator (wdgs_comm_*): RCCL on the device's stream, for the data-parallel step of a host without torch.distributed. */
 export class Communicator {
   constructor(device: HipDevice, uniqueId: ArrayBuffer, worldSize: number, rank: number);

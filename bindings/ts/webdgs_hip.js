@@ -228,6 +228,7 @@ class TiledForwardPass {                 // tiled-forward-pass.ts:62
 }
 
 const DEPTH_KINDS = { expected: 1, median: 2, weight_sum: 4 };   // WDGS_DEPTH_*
+const NO_NORMAL = 0x80008000;   // the packed word of a Gaussian without a normal (include/webdgs.h)
 const CONTRIBUTION_RECORD_BYTES = 16;   // { u64 sum_q; u32 max_bits; u32 pixels } per Gaussian (include/webdgs.h)
 function depthMask(kinds) {
   if (typeof kinds === 'number') return kinds;
@@ -254,6 +255,14 @@ class TiledRasterizer {                  // tiled-rasterizer.ts:34
   encodeDepth(_encoder, kinds) { addon.tiledRasterizerEncodeDepth(this.handle, depthMask(kinds === undefined ? ['expected'] : kinds)); }
   /** f32[W*H] of one kind the last encodeDepth wrote; throws (WDGS_E_STATE) otherwise. */
   getDepthTextureView(kind) { return this.device.view(addon.tiledRasterizerGetDepth(this.handle, depthMask([kind === undefined ? 'expected' : kind])), 4 * this.w * this.h); }
+  /** The normal map of the frame the last encode rasterized (include/webdgs.h, DESIGN.md section 12; no reference counterpart): one packed view-space
+   *  normal per Gaussian of the forward pass's cloud under its camera, composited with the colour image's weights.  The first use, and the first after
+   *  the point count or the size changed, allocates and cannot be recorded. */
+  encodeNormal(_encoder) { addon.tiledRasterizerEncodeNormal(this.handle, this.forwardPass.pointCloud.gaussian_3d_buffer.ptr, this.forwardPass.cameraBuffer.ptr); }
+  /** rgba32f[W*H] { N.x, N.y, N.z, A } of the last encodeNormal (N un-normalised: |N| <= A); throws (WDGS_E_STATE) before it. */
+  getNormalTextureView() { return this.device.view(addon.tiledRasterizerGetNormal(this.handle, 0), 16 * this.w * this.h); }
+  /** u32[numPoints]: the packed per-Gaussian normals of the last encodeNormal (0x80008000: no normal); throws (WDGS_E_STATE) before it. */
+  getGaussianNormals() { return this.device.view(addon.tiledRasterizerGetNormal(this.handle, 1), 4 * Math.max(1, this.forwardPass.pointCloud.num_points)); }
   /** Adds the per-Gaussian contribution of the frame the last encode rasterized into `statsBuffer` (createContributionBuffer; include/webdgs.h,
    *  DESIGN.md section 11; no reference counterpart).  Allocates nothing, so it records. */
   encodeContribution(_encoder, statsBuffer) {
@@ -516,6 +525,38 @@ function imageSSIM(device, a, b, width, height, map) {
  *  (wdgs_depth_to_rgba8).  Stream-ordered; no reference counterpart. */
 function depthToRGBA8(device, depth, width, height, near, far, target) { addon.depthToRgba8(device.handle, depth.ptr, width, height, near, far, target.ptr); }
 
+/** The normals of an f32 depth image by central differences of its back-projection (loaders.backprojectDepth's convention): rgba32f { n, 1 } into
+ *  `target`, all zero where a neighbour is missing (wdgs_depth_to_normals).  `camera`: the 68-float block, or [proj[0][0], proj[1][1]].
+ *  Stream-ordered; no reference counterpart. */
+function depthToNormals(device, depth, width, height, camera, target) {
+  if (depth.size < 4 * width * height || target.size < 16 * width * height) throw new Error(`depthToNormals: buffers too small for ${width}x${height}`);
+  const p = camera.length === 68 ? [camera[32], camera[37]] : [camera[0], camera[1]];
+  addon.depthToNormals(device.handle, depth.ptr, width, height, p[0], p[1], target.ptr);
+}
+/** Stream-ordered normalAgreement: the three u64 sums into the first 24 bytes of `out` (no host wait). */
+function encodeNormalAgreement(device, normal, depthNormals, width, height, out) {
+  if (normal.size < 16 * width * height || depthNormals.size < 16 * width * height || out.size < 24) throw new Error(`normalAgreement: buffers too small for ${width}x${height}`);
+  addon.normalAgreement(device.handle, normal.ptr, depthNormals.ptr, width, height, out.ptr);
+}
+/** How well a composited normal image (getNormalTextureView) agrees with a depth-normal image (depthToNormals), over the pixels with A >= 0.5, |N| > 0
+ *  and a valid depth normal: { sum_e, sum_a, pixels } (exact integer sums of rint(A (1 - cos) 2^24) and rint(A 2^24), as Numbers: below 2^53 for any
+ *  image) and value = sum_e / sum_a, the weight-averaged 1 - cos (NaN when nothing counts).  Synchronises.  No reference counterpart. */
+function normalAgreement(device, normal, depthNormals, width, height) {
+  const out = device.createBuffer({ size: 24 });
+  try {
+    encodeNormalAgreement(device, normal, depthNormals, width, height, out);
+    const v = new BigUint64Array(device.readBuffer(out, 24));
+    const e = Number(v[0]), a = Number(v[1]);
+    return { sum_e: e, sum_a: a, pixels: Number(v[2]), value: a ? e / a : NaN };
+  } finally { out.destroy(); }
+}
+/** A normal image as rgba8 for presentation: round(255 (0.5 + 0.5 (n_x, -n_y, -n_z))) of the normalised normal (facing the camera: blue), black where
+ *  |N| = 0, alpha 255 (wdgs_normal_to_rgba8).  Stream-ordered; no reference counterpart. */
+function normalToRGBA8(device, normal, width, height, target) {
+  if (normal.size < 16 * width * height || target.size < 4 * width * height) throw new Error(`normalToRGBA8: buffers too small for ${width}x${height}`);
+  addon.normalToRgba8(device.handle, normal.ptr, width, height, target.ptr);
+}
+
 /** One zeroed 16-byte record { u64 sum_q; u32 max_bits; u32 pixels } per Gaussian, for TiledRasterizer.encodeContribution.  No reference counterpart. */
 function createContributionBuffer(device, numPoints) {
   const buf = device.createBuffer({ size: CONTRIBUTION_RECORD_BYTES * Math.max(1, numPoints), label: 'contribution' });
@@ -557,6 +598,6 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

@@ -283,6 +283,38 @@ int wdgs_depth_to_rgba8(wdgs_device* dev, const void* depth_f32_dev, uint32_t wi
  * WDGS_E_STATE before encode, and when the forward pass is in point-cloud render mode (no weights); WDGS_E_INVALID on a null or misaligned pointer. */
 int wdgs_tiled_rasterizer_encode_contribution(wdgs_tiled_rasterizer* op, void* stats_dev);
 
+/* Normal maps.  The reference renders colour only and has no counterpart to any of the six entries below.
+ * encode_normal first gives every Gaussian of `gaussians_dev` one packed view-space normal under `camera_dev` -- the cloud and the 68-float block the
+ * forward pass was last encoded with, which the caller names again as in wdgs_tiled_forward_encode.  The normal is the Gaussian's shortest axis
+ * (row k of R(q / |q|), k the index of the smallest log-scale, ties to the lowest index), in view space, unit length, turned toward the camera, packed
+ * octahedrally into snorm16 x 2; the word 0x80008000 means "no normal" (zero quaternion, a non-finite half among position, quaternion and log-scales).
+ * It then composites them over the frame the last encode rasterized with the weights w_i = alpha_i (1 - A) of the colour image: an rgba32f image
+ * { N.x, N.y, N.z, A }, N = sum w_i n_i un-normalised (|N| <= A), A bit-identical to WDGS_DEPTH_WEIGHT_SUM.  The words and the image are allocated at
+ * the first call, after a change of the point count (words) and of the size (image): such a call cannot be recorded (WDGS_E_STATE); others can.
+ * WDGS_E_STATE before encode, and when the forward pass is in point-cloud render mode (no weights).  The two pointers are taken on trust: another
+ * cloud, or a camera block rewritten since the forward encode, is NOT detected and gives the normals of a frame that was not composited.  No
+ * reference counterpart. */
+int wdgs_tiled_rasterizer_encode_normal(wdgs_tiled_rasterizer* op, const void* gaussians_dev, const void* camera_dev);
+/* rgba32f[W*H] of the last encode_normal; WDGS_E_STATE before it, and after an encode of another size until the next encode_normal.  No reference counterpart. */
+int wdgs_tiled_rasterizer_get_normal(wdgs_tiled_rasterizer* op, void** rgba32f_dev);
+/* u32[num_points]: the packed per-Gaussian normals of the last encode_normal; WDGS_E_STATE before it, and after the forward pass changed its point
+ * count until the next encode_normal.  No reference counterpart. */
+int wdgs_tiled_rasterizer_get_gaussian_normals(wdgs_tiled_rasterizer* op, void** u32_dev);
+/* The normals of any f32 depth image, by central differences of its back-projection V(i,j) = (ndc_x z / p00, ndc_y z / p11, z), ndc_x = 2(i+.5)/W - 1,
+ * ndc_y = 1 - 2(j+.5)/H (p00 = proj[0][0], p11 = proj[1][1] of the camera block): n = normalize(cross(V(i+1,j) - V(i-1,j), V(i,j+1) - V(i,j-1))),
+ * negated where n . V(i,j) > 0.  Writes rgba32f { n, 1 }, and { 0, 0, 0, 0 } where one of the five pixels is outside the image or has a depth that is
+ * not > 0 or not finite, or the cross product is zero or not finite.  p00 and p11 finite and non-zero; the output 16-byte aligned.  No reference counterpart. */
+int wdgs_depth_to_normals(wdgs_device* dev, const void* depth_f32_dev, uint32_t width, uint32_t height, float p00, float p11, void* normals_rgba32f_dev);
+/* How well a composited normal image (get_normal) and a depth-normal image (wdgs_depth_to_normals) agree.  A pixel counts when A >= 0.5, |N| > 0 and
+ * the depth normal is valid (w != 0); with c = (N / |N|) . n_d it adds e = rint(A max(1 - c, 0) 2^24) and a = rint(A 2^24).  Writes three uint64
+ * { sum e, sum a, pixels } (cleared first; integer atomics, so any order gives the same bits); sum e / sum a is the weight-averaged 1 - cos.
+ * Images 16-byte aligned, the sums 8-byte aligned.  No reference counterpart. */
+int wdgs_normal_agreement(wdgs_device* dev, const void* normal_rgba32f_dev, const void* depth_normals_rgba32f_dev, uint32_t width, uint32_t height,
+                          void* out_u64x3_dev);
+/* A normal image as rgba8 for presentation: rgb = round(255 (0.5 + 0.5 (n_x, -n_y, -n_z))), n = N / |N| (a surface that faces the camera is blue),
+ * black where |N| is not > 0, alpha 255.  No reference counterpart. */
+int wdgs_normal_to_rgba8(wdgs_device* dev, const void* normal_rgba32f_dev, uint32_t width, uint32_t height, void* rgba8_dev);
+
 /* ---------------------------------------------------------------- TiledBackwardPass
  * Replaces `new TiledBackwardPass(device, pointCloud, config)` (renderers/tiled-backward-pass.ts:136-140, config 27-34,
  * TrainingConfig 19-25), .encode (592-740), .computeLossOnly (383), .computeMetricMap (425), .computeMetricCounts (514),

@@ -206,6 +206,12 @@ SIGNATURES = {
     "wdgs_tiled_rasterizer_get_depth": (_I, [_P, _U, C.POINTER(_P)]),
     "wdgs_depth_to_rgba8": (_I, [_P, _P, _U, _U, _F, _F, _P]),
     "wdgs_tiled_rasterizer_encode_contribution": (_I, [_P, _P]),
+    "wdgs_tiled_rasterizer_encode_normal": (_I, [_P, _P, _P]),
+    "wdgs_tiled_rasterizer_get_normal": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_tiled_rasterizer_get_gaussian_normals": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_depth_to_normals": (_I, [_P, _P, _U, _U, _F, _F, _P]),
+    "wdgs_normal_agreement": (_I, [_P, _P, _P, _U, _U, _P]),
+    "wdgs_normal_to_rgba8": (_I, [_P, _P, _U, _U, _P]),
     "wdgs_tiled_backward_create": (_I, [_P, C.POINTER(TiledBackwardConfig), C.POINTER(_P)]),
     "wdgs_tiled_backward_resize": (_I, [_P, _U]),
     "wdgs_tiled_backward_destroy": (_I, [_P]),

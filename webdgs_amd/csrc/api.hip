@@ -180,6 +180,12 @@ struct wdgs_tiled_rasterizer {
     DevMem<float> depth[3];
     u32 depth_width = 0, depth_height = 0;   // the size they were allocated for
     u32 depth_encoded = 0;                   // the kinds the last encode_depth wrote
+    // normals (normal.hip): one packed word per Gaussian and the composited image { N.xyz, A }, allocated at the first encode_normal
+    DevMem<u32> normals;
+    u32 normals_points = 0;                  // the point count the words were allocated for
+    DevMem<float4> normal_image;
+    u32 normal_width = 0, normal_height = 0; // the size it was allocated for
+    bool normal_encoded = false;
 };
 
 struct wdgs_tiled_backward {
@@ -1175,6 +1181,55 @@ int wdgs_tiled_rasterizer_encode_contribution(wdgs_tiled_rasterizer* op, void* s
                  "wdgs_tiled_rasterizer_encode_contribution: the statistics buffer must be non-null and 16-byte aligned (got %p)", stats_dev);
     WDGS_TRY(require_composited_frame(op, "encodeContribution"));
     return launch_contribution(op->dev, composited_frame(op), stats_dev);
+}
+// Normal map of the frame the last encode composited (normal.hip; no counterpart in the reference): the per-Gaussian words from the cloud and the camera
+// the forward pass was encoded with -- the caller's, as in wdgs_tiled_forward_encode, which keeps neither -- then depth's walk over them.  The words and the
+// image are allocated at first use, under the depth images' rules.
+int wdgs_tiled_rasterizer_encode_normal(wdgs_tiled_rasterizer* op, const void* gaussians, const void* camera) {
+    WDGS_REQUIRE(op && gaussians && camera, WDGS_E_INVALID, "wdgs_tiled_rasterizer_encode_normal: null argument");
+    WDGS_TRY(require_composited_frame(op, "encodeNormal"));
+    wdgs_device* d = op->dev;
+    const u32 n = op->fwd->cfg.num_points;
+    if (!op->normals || op->normals_points != n) {   // first use, or the point count changed: the words are re-made
+        WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledRasterizer.encodeNormal allocates its per-Gaussian normals on first use and after a point-count change: run one eager encodeNormal before recording");
+        if (op->normals) (void)wdgs_sync_lanes(d);
+        op->normals_points = 0;
+        op->normal_encoded = false;
+        WDGS_TRY(op->normals.alloc(std::max(n, 1u), true, d->stream));
+        op->normals_points = n;
+    }
+    if (!op->normal_image || op->normal_width != op->width || op->normal_height != op->height) {
+        WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "TiledRasterizer.encodeNormal allocates its image on first use and after a size change: run one eager encodeNormal before recording");
+        if (op->normal_image) (void)wdgs_sync_lanes(d);
+        op->normal_width = op->normal_height = 0;
+        op->normal_encoded = false;
+        WDGS_TRY(op->normal_image.alloc((size_t)op->width * op->height, true, d->stream));
+        op->normal_width = op->width;
+        op->normal_height = op->height;
+    }
+    WDGS_TRY(launch_gaussian_normals(d, n, static_cast<const u32*>(gaussians), static_cast<const float*>(camera), op->normals));
+    WDGS_TRY(launch_normal_composite(d, composited_frame(op), op->normals, op->normal_image));
+    op->normal_encoded = true;
+    return WDGS_OK;
+}
+int wdgs_tiled_rasterizer_get_normal(wdgs_tiled_rasterizer* op, void** out) {
+    WDGS_REQUIRE(op && out, WDGS_E_INVALID, "wdgs_tiled_rasterizer_get_normal: null argument");
+    WDGS_REQUIRE(op->normal_encoded && op->normal_image, WDGS_E_STATE, "TiledRasterizer: normal image not encoded yet (call encodeNormal first)");
+    WDGS_REQUIRE(op->normal_width == op->width && op->normal_height == op->height, WDGS_E_STATE,
+                 "TiledRasterizer: the normal image is %ux%u, the rasterizer's images %ux%u since the last encode (call encodeNormal again)", op->normal_width, op->normal_height,
+                 op->width, op->height);
+    *out = op->normal_image;
+    return WDGS_OK;
+}
+int wdgs_tiled_rasterizer_get_gaussian_normals(wdgs_tiled_rasterizer* op, void** out) {
+    WDGS_REQUIRE(op && out, WDGS_E_INVALID, "wdgs_tiled_rasterizer_get_gaussian_normals: null argument");
+    WDGS_REQUIRE(op->normal_encoded && op->normals, WDGS_E_STATE, "TiledRasterizer: per-Gaussian normals not encoded yet (call encodeNormal first)");
+    // (the rasterizer is not told of a resize of the forward pass: the words of another point count are not handed out -- the next encode_normal re-makes them)
+    WDGS_REQUIRE(op->normals_points == op->fwd->cfg.num_points, WDGS_E_STATE,
+                 "TiledRasterizer: the per-Gaussian normals hold %u Gaussians, the forward pass %u since its point count changed (call encodeNormal again)", op->normals_points,
+                 op->fwd->cfg.num_points);
+    *out = op->normals;
+    return WDGS_OK;
 }
 int wdgs_tiled_rasterizer_get_depth(wdgs_tiled_rasterizer* op, uint32_t kind, void** out) {
     WDGS_REQUIRE(op && out, WDGS_E_INVALID, "wdgs_tiled_rasterizer_get_depth: null argument");

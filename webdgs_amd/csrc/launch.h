@@ -56,7 +56,7 @@ int launch_emit_scatter(wdgs_device* dev, u32 n, const u32* splats, const u32* d
 int launch_emit(wdgs_device* dev, u32 n, const u32* splats, const u32* depths, const u32* counts, u32* offsets, const u32* block_offsets, const RenderSettings& st,
                 const TileInfo& ti, u32* keys, u32* values, u32 capacity);
 
-// ---- raster.hip, depth.hip, contrib.hip: the kernels that walk the tiles' sorted entry lists (depth's and contribution's walk: tilewalk.h)
+// ---- raster.hip, depth.hip, contrib.hip, normal.hip: the kernels that walk the tiles' sorted entry lists (all but rasterize's walk: tilewalk.h)
 // The frame the last encode composited, as its three walkers are handed it
 struct CompositedFrame {
     RenderSettings st;
@@ -77,6 +77,11 @@ int launch_rasterize(wdgs_device* dev, const CompositedFrame& f, u32* out_rgba8,
 int launch_depth_composite(wdgs_device* dev, const CompositedFrame& f, const u32* depths, float* out_weight, float* out_expected, float* out_median);
 // stats: one 16-byte record { u64 sum_q; u32 max_bits; u32 pixels; } per Gaussian, added to
 int launch_contribution(wdgs_device* dev, const CompositedFrame& f, void* stats);
+
+// ---- normal.hip.  gaussians 6 words per Gaussian, camera the 68-float block; normals u32[n], written: one packed view-space normal per Gaussian
+int launch_gaussian_normals(wdgs_device* dev, u32 n, const u32* gaussians, const float* camera, u32* normals);
+// normals: u32[num_splats] of launch_gaussian_normals; out: rgba32f[W*H] { N.xyz, A }.  depth's walk (tilewalk.h)
+int launch_normal_composite(wdgs_device* dev, const CompositedFrame& f, const u32* normals, float4* out);
 
 // ---- loss.hip, dssim.hip.  pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
 int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,

@@ -584,6 +584,21 @@ class TiledRasterizer:
             raise ValueError(f"encodeContribution: the statistics buffer holds {statsBuffer.size} bytes, {n} Gaussians need {CONTRIBUTION_RECORD_BYTES * n}")
         check(self.device.lib.wdgs_tiled_rasterizer_encode_contribution(self.handle, statsBuffer.ptr))
 
+    def encodeNormal(self, encoder: Optional[HipEncoder]) -> None:
+        """The normal map of the frame the last ``encode`` rasterized (no reference counterpart): one packed view-space normal
+        per Gaussian of the forward pass's cloud under its camera, composited with the colour image's weights.  The first use, and the first after
+        the point count or the size changed, allocates and cannot be recorded."""
+        f = self.forwardPass
+        check(self.device.lib.wdgs_tiled_rasterizer_encode_normal(self.handle, f.pointCloud.gaussian_3d_buffer.ptr, f.cameraBuffer.ptr))
+
+    def getNormalTextureView(self) -> HipBuffer:
+        """rgba32f[W*H] ``{N.x, N.y, N.z, A}`` of the last ``encodeNormal`` (``N`` un-normalised: ``|N| <= A``); raises ``StateError`` before it."""
+        return self._get(self.device.lib.wdgs_tiled_rasterizer_get_normal, 16 * self.width * self.height)
+
+    def getGaussianNormals(self) -> HipBuffer:
+        """u32[numPoints]: the packed per-Gaussian normals of the last ``encodeNormal`` (``decodeNormals``); raises ``StateError`` before it."""
+        return self._get(self.device.lib.wdgs_tiled_rasterizer_get_gaussian_normals, 4 * max(1, self.forwardPass.pointCloud.num_points))
+
     def blitToTexture(self, encoder: Optional[HipEncoder], target: HipBuffer, width: Optional[int] = None, height: Optional[int] = None) -> None:
         """``blitToTexture(encoder, targetView)`` (tiled-rasterizer.ts:333-357): ``target`` is an rgba8 image buffer of
         ``width x height`` (default: the rasterizer's own size); raises before the first ``encode`` like the reference."""
@@ -758,6 +773,71 @@ def depthToRGBA8(device: HipDevice, depth: HipBuffer, width: int, height: int, n
     if depth.size < 4 * n or target.size < 4 * n:
         raise ValueError(f"depthToRGBA8: buffers too small for {width}x{height}")
     check(device.lib.wdgs_depth_to_rgba8(device.handle, depth.ptr, int(width), int(height), float(near), float(far), target.ptr))
+
+
+# ----------------------------------------------------------------------------- normal maps (no reference counterpart)
+NO_NORMAL = 0x80008000  # the packed word of a Gaussian without a normal
+
+
+def decodeNormals(words) -> np.ndarray:
+    """Packed per-Gaussian normals (``getGaussianNormals``) as float32 ``[n, 3]`` unit vectors, by the decode of DESIGN.md section 12, operation by
+    operation in float32 as the compositing kernel evaluates it; ``NO_NORMAL`` gives the zero vector.  Host side (numpy)."""
+    w = np.ascontiguousarray(words, np.uint32).reshape(-1)
+    one, q = np.float32(1), np.float32(32767)
+    u = (w & np.uint32(0xFFFF)).astype(np.uint16).view(np.int16).astype(np.float32) / q
+    v = (w >> np.uint32(16)).astype(np.uint16).view(np.int16).astype(np.float32) / q
+    au, av = np.abs(u), np.abs(v)
+    t = (one - au) - av
+    fold = t < 0
+    x = np.where(fold, np.copysign(one - av, u), u)
+    y = np.where(fold, np.copysign(one - au, v), v)
+    z = -t
+    length = np.sqrt((x * x + y * y) + z * z)
+    out = np.stack([x / length, y / length, z / length], axis=1).astype(np.float32)
+    out[w == np.uint32(NO_NORMAL)] = 0
+    return out
+
+
+def depthToNormals(device: HipDevice, depth: HipBuffer, width: int, height: int, camera, target: HipBuffer) -> None:
+    """The normals of an f32 depth image (``getDepthTextureView``, or any other) by central differences of its back-projection
+    (``loaders.backprojectDepth``'s convention): rgba32f ``{n, 1}`` into ``target``, all zero where a neighbour is missing
+    (``wdgs_depth_to_normals``).  ``camera``: the 68-float block, or the pair ``(proj[0][0], proj[1][1])``.  Stream-ordered."""
+    n = int(width) * int(height)
+    if depth.size < 4 * n or target.size < 16 * n:
+        raise ValueError(f"depthToNormals: buffers too small for {width}x{height}")
+    c = np.asarray(camera, np.float32).reshape(-1)
+    p00, p11 = (c[32], c[37]) if c.size == 68 else (c[0], c[1])
+    check(device.lib.wdgs_depth_to_normals(device.handle, depth.ptr, int(width), int(height), float(p00), float(p11), target.ptr))
+
+
+def encodeNormalAgreement(device: HipDevice, normal: HipBuffer, depthNormals: HipBuffer, width: int, height: int, out: HipBuffer) -> None:
+    """Stream-ordered ``normalAgreement``: the three u64 sums into the first 24 bytes of ``out``.  No host wait."""
+    n = int(width) * int(height)
+    if normal.size < 16 * n or depthNormals.size < 16 * n or out.size < 24:
+        raise ValueError(f"normalAgreement: buffers too small for {width}x{height}")
+    check(device.lib.wdgs_normal_agreement(device.handle, normal.ptr, depthNormals.ptr, int(width), int(height), out.ptr))
+
+
+def normalAgreement(device: HipDevice, normal: HipBuffer, depthNormals: HipBuffer, width: int, height: int) -> dict:
+    """How well a composited normal image (``getNormalTextureView``) agrees with a depth-normal image (``depthToNormals``), over the pixels with
+    ``A >= 0.5``, ``|N| > 0`` and a valid depth normal: the exact integer sums ``sum_e`` (of ``rint(A (1 - cos) 2^24)``) and ``sum_a`` (of
+    ``rint(A 2^24)``), ``pixels``, and ``value = sum_e / sum_a``, the weight-averaged ``1 - cos`` (nan when nothing counts).  Synchronises."""
+    out = device.createBuffer(24, "normal agreement")
+    try:
+        encodeNormalAgreement(device, normal, depthNormals, width, height, out)
+        e, a, cnt = (int(x) for x in out.read(np.uint64, count=3))
+    finally:
+        out.destroy()
+    return dict(sum_e=e, sum_a=a, pixels=cnt, value=(e / a) if a else float("nan"))
+
+
+def normalToRGBA8(device: HipDevice, normal: HipBuffer, width: int, height: int, target: HipBuffer) -> None:
+    """A normal image as rgba8 for presentation: ``round(255 (0.5 + 0.5 (n_x, -n_y, -n_z)))`` of the normalised normal (facing the camera: blue), black
+    where ``|N| = 0``, alpha 255 (``wdgs_normal_to_rgba8``).  Stream-ordered."""
+    n = int(width) * int(height)
+    if normal.size < 16 * n or target.size < 4 * n:
+        raise ValueError(f"normalToRGBA8: buffers too small for {width}x{height}")
+    check(device.lib.wdgs_normal_to_rgba8(device.handle, normal.ptr, int(width), int(height), target.ptr))
 
 
 # ----------------------------------------------------------------------------- per-Gaussian contribution (DESIGN.md section 11; no reference counterpart)

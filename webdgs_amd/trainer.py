@@ -920,6 +920,28 @@ class Trainer:
             raise err
         return max(o.needed for o in mine) if mine else None
 
+    def _eval_views(self, what: str, viewIds: Optional[list], split: str) -> tuple:
+        """(cameras, images, camera buffers, view ids) of a split, checked: what ``evaluate``, ``normalConsistency`` and ``contributionStats`` start with."""
+        if split not in ("eval", "train"):
+            raise ValueError(f"{what}: split must be 'eval' or 'train', not {split!r}")
+        if self.pointCloud is None:
+            raise RuntimeError(f"{what}: no point cloud")
+        cams, imgs, bufs = ((self.evalCameras, self.evalImages, self._eval_camera_buffers) if split == "eval" else
+                            (self.trainCameras, self.images, self._camera_buffers))
+        ids = list(range(len(cams))) if viewIds is None else [int(v) for v in viewIds]
+        for v in ids:
+            if not 0 <= v < len(cams):
+                raise IndexError(f"{what}: view {v} of {len(cams)} ({split})")
+        return cams, imgs, bufs, ids
+
+    def _eval_drain(self) -> None:
+        """Drains the pipeline in front of renders through the evaluation passes."""
+        try:
+            self.drain()
+        except ops.CapacityError as e:   # a training step's overflow, as step() would have met it at its next wait
+            if not self._grow_tile_entry_capacity(e):
+                raise
+
     def evaluate(self, viewIds: Optional[list] = None, split: str = "eval") -> dict:
         """PSNR and SSIM of the current model on the evaluation views (``split="eval"``, ``setEvaluationViews``) or on training views
         (``split="train"``): ``dict(iteration, views, psnr=[...], ssim=[...], mean_psnr, mean_ssim, ms)``.  PSNR comes from the exact SSE kernel
@@ -929,22 +951,9 @@ class Trainer:
         read back once at the end.  A view whose tile-entry list overflowed is rendered again with larger lists -- never reported from a truncated
         render.  Training is untouched: no RNG draw, no training pass, no recording dropped; a trainer that evaluates every few steps follows the
         same trajectory as one that never does.  Per rank with ``world_size > 1`` (no collective)."""
-        if split not in ("eval", "train"):
-            raise ValueError(f"evaluate: split must be 'eval' or 'train', not {split!r}")
-        if self.pointCloud is None:
-            raise RuntimeError("evaluate: no point cloud")
-        cams, imgs, bufs = ((self.evalCameras, self.evalImages, self._eval_camera_buffers) if split == "eval" else
-                            (self.trainCameras, self.images, self._camera_buffers))
-        ids = list(range(len(cams))) if viewIds is None else [int(v) for v in viewIds]
-        for v in ids:
-            if not 0 <= v < len(cams):
-                raise IndexError(f"evaluate: view {v} of {len(cams)} ({split})")
+        cams, imgs, bufs, ids = self._eval_views("evaluate", viewIds, split)
         t0 = time.perf_counter()
-        try:
-            self.drain()
-        except ops.CapacityError as e:   # a training step's overflow, as step() would have met it at its next wait
-            if not self._grow_tile_entry_capacity(e):
-                raise
+        self._eval_drain()
         n = len(ids)
         out = self.device.createBuffer(16 * max(1, n), "evaluation sse + ssim")
         sse_at, ssim_at = out.ptr, out.ptr + 8 * max(1, n)
@@ -988,26 +997,45 @@ class Trainer:
             if restart is not None:
                 restart()
 
+    # ------------------------------------------------------------------ normal consistency (no reference counterpart)
+    def normalConsistency(self, viewIds: Optional[list] = None, split: str = "eval", depthKind: str = "median") -> dict:
+        """How well the composited normals of the current model agree with the normals of its own depth map, per view: a geometry score that needs no
+        ground truth (a surface scores near 0, a fog near 1).  ``dict(iteration, views, value=[...], pixels=[...], sum_e=[...], sum_a=[...], mean, ms)``:
+        ``value`` is ``ops.normalAgreement``'s weight-averaged ``1 - cos`` between ``encodeNormal``'s image and ``ops.depthToNormals`` of the
+        ``depthKind`` depth image (nan for a view where no pixel counts), ``mean`` the same average over all views' pixels (``sum sum_e / sum sum_a``).
+
+        Rendered through evaluate's passes, with its isolation: the pipeline is drained, a view whose lists overflowed is rendered again, no RNG draw,
+        no training pass, no recording dropped; ``evaluate()``'s result is what it was.  Per rank with ``world_size > 1``."""
+        if depthKind not in ("median", "expected"):
+            raise ValueError(f"normalConsistency: depthKind must be 'median' or 'expected', not {depthKind!r}")
+        cams, imgs, bufs, ids = self._eval_views("normalConsistency", viewIds, split)
+        t0 = time.perf_counter()
+        self._eval_drain()
+        n = len(ids)
+        out = self.device.createBuffer(24 * max(1, n), "normal agreement sums")
+        scratch = self.device.createBuffer(16 * max([1] + [int(imgs[v]["width"]) * int(imgs[v]["height"]) for v in ids]), "depth normals")
+        try:
+            def measure(i, v, s, w, h):
+                s.rasterizer.encodeDepth(None, (depthKind,))
+                s.rasterizer.encodeNormal(None)
+                ops.depthToNormals(self.device, s.rasterizer.getDepthTextureView(depthKind), w, h, cams[v]["camera"], scratch)
+                ops.encodeNormalAgreement(self.device, s.rasterizer.getNormalTextureView(), scratch, w, h, self.device.view(out.ptr + 24 * i, 24))
+            self._render_eval_views(ids, imgs, bufs, measure, what="normalConsistency")
+            sums = (out.read(np.uint64, count=3 * n) if n else np.zeros(0, np.uint64)).reshape(n, 3)
+        finally:
+            scratch.destroy()
+            out.destroy()
+        sum_e, sum_a, pixels = ([int(x) for x in sums[:, k]] for k in range(3))
+        return dict(iteration=self.iteration, views=ids, value=[(e / a) if a else float("nan") for e, a in zip(sum_e, sum_a)], pixels=pixels,
+                    sum_e=sum_e, sum_a=sum_a, mean=(sum(sum_e) / sum(sum_a)) if sum(sum_a) else float("nan"), ms=(time.perf_counter() - t0) * 1e3)
+
     # ------------------------------------------------------------------ render contribution and contribution-based pruning (no reference counterpart)
     def _contribution_buffer(self, viewIds: Optional[list], split: str, what: str) -> tuple:
         """(buffer, view ids): the views' contribution records accumulated into one new device buffer."""
-        if split not in ("eval", "train"):
-            raise ValueError(f"{what}: split must be 'eval' or 'train', not {split!r}")
-        if self.pointCloud is None:
-            raise RuntimeError(f"{what}: no point cloud")
-        cams, imgs, bufs = ((self.evalCameras, self.evalImages, self._eval_camera_buffers) if split == "eval" else
-                            (self.trainCameras, self.images, self._camera_buffers))
-        ids = list(range(len(cams))) if viewIds is None else [int(v) for v in viewIds]
-        for v in ids:
-            if not 0 <= v < len(cams):
-                raise IndexError(f"{what}: view {v} of {len(cams)} ({split})")
+        cams, imgs, bufs, ids = self._eval_views(what, viewIds, split)
         if sum(int(imgs[v]["width"]) * int(imgs[v]["height"]) for v in ids) >= 2 ** 32:
             raise ValueError(f"{what}: the views hold 2^32 pixels or more; the per-Gaussian pixel count is 32 bits wide")
-        try:
-            self.drain()
-        except ops.CapacityError as e:   # a training step's overflow, as step() would have met it at its next wait
-            if not self._grow_tile_entry_capacity(e):
-                raise
+        self._eval_drain()
         stats = ops.createContributionBuffer(self.device, self.pointCloud.num_points)
         try:
             self._render_eval_views(ids, imgs, bufs, lambda i, v, s, w, h: s.rasterizer.encodeContribution(None, stats), restart=stats.clear, what=what)

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import loaders
 from ._lib import CapacityError
-from .ops import CapacityReports, HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer, depthToRGBA8
+from .ops import CapacityReports, HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer, depthToRGBA8, normalToRGBA8
 
 
 def encodePNG(rgba: np.ndarray) -> bytes:
@@ -211,6 +211,38 @@ class Viewer:
         out = self.device.createBuffer(4 * self.width * self.height, "depth presentation")
         try:
             depthToRGBA8(self.device, self.rasterizer.getDepthTextureView(kind), self.width, self.height, lo, hi, out)
+            rgba = out.read(np.uint8, 4 * self.width * self.height).reshape(self.height, self.width, 4)
+        finally:
+            out.destroy()
+        with open(path, "wb") as f:
+            f.write(encodePNG(rgba))
+
+    # ---- normals (no reference counterpart)
+    def _encode_normal(self) -> None:
+        self.forwardPass.setRenderMode("gaussian")   # as depth: weights exist in gaussian mode only; the viewer's own mode is put back below
+        try:
+            self.forwardPass.encode(None)
+            self.rasterizer.encode(None, self.width, self.height)
+            self.rasterizer.encodeNormal(None)
+        finally:
+            self.forwardPass.setRenderMode(self._settings.get("renderMode", "pointcloud"))
+
+    def renderNormals(self) -> np.ndarray:
+        """The current camera's normal map ``[H, W, 4]`` float32 ``{N.x, N.y, N.z, A}`` (view space: x right, y down, z forward; ``N`` un-normalised,
+        ``|N| <= A``), rendered in gaussian mode through the viewer's own passes whatever its render mode, which is left as it was (synchronises).
+        The swap-chain image is not touched."""
+        if self.forwardPass is None or self.rasterizer is None or self.pointCloud is None:
+            raise RuntimeError("Viewer.renderNormals: no point cloud set")
+        self._encode_normal()
+        self._settle_capacity(self._encode_normal)
+        return self.rasterizer.getNormalTextureView().read(np.float32, 4 * self.width * self.height).reshape(self.height, self.width, 4)
+
+    def saveNormalPNG(self, path: str) -> None:
+        """The normal map as the usual colour PNG (``ops.normalToRGBA8``: a surface that faces the camera is blue, no normal black)."""
+        self.renderNormals()
+        out = self.device.createBuffer(4 * self.width * self.height, "normal presentation")
+        try:
+            normalToRGBA8(self.device, self.rasterizer.getNormalTextureView(), self.width, self.height, out)
             rgba = out.read(np.uint8, 4 * self.width * self.height).reshape(self.height, self.width, 4)
         finally:
             out.destroy()
