@@ -356,6 +356,55 @@ static napi_value normalToRgba8(napi_env env, napi_callback_info info) {  // (de
     WDGS_OK_OR_THROW(wdgs_normal_to_rgba8((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]), get_ptr(env, argv[4])));
     return js_undefined(env);
 }
+// TSDF volume (include/webdgs.h: wdgs_tsdf_volume_*; the reference renders colour only and has no counterpart)
+static napi_value tsdfVolumeCreate(napi_env env, napi_callback_info info) {  // (device, ox, oy, oz, voxelSize, nx, ny, nz, truncation, maxWeight, colour) -> handle
+    ARGS(11);
+    const float origin[3] = {(float)get_f64(env, argv[1]), (float)get_f64(env, argv[2]), (float)get_f64(env, argv[3])};
+    wdgs_tsdf_volume* v = nullptr;
+    WDGS_OK_OR_THROW(wdgs_tsdf_volume_create((wdgs_device*)get_ptr(env, argv[0]), origin, (float)get_f64(env, argv[4]), get_u32(env, argv[5]), get_u32(env, argv[6]),
+                                             get_u32(env, argv[7]), (float)get_f64(env, argv[8]), (float)get_f64(env, argv[9]), get_u32(env, argv[10]), &v));
+    return make_ptr(env, v);
+}
+static napi_value tsdfVolumeDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_tsdf_volume_destroy((wdgs_tsdf_volume*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value tsdfVolumeReset(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    WDGS_OK_OR_THROW(wdgs_tsdf_volume_reset((wdgs_tsdf_volume*)get_ptr(env, argv[0])));
+    return js_undefined(env);
+}
+static napi_value tsdfVolumeGet(napi_env env, napi_callback_info info) {  // (volume, which: 0 = tsdf, 1 = weight, 2 = rgb) -> device pointer
+    ARGS(2);
+    void* p = nullptr;
+    wdgs_tsdf_volume* v = (wdgs_tsdf_volume*)get_ptr(env, argv[0]);
+    const uint32_t which = get_u32(env, argv[1]);
+    WDGS_OK_OR_THROW(which == 0 ? wdgs_tsdf_volume_get_tsdf(v, &p) : (which == 1 ? wdgs_tsdf_volume_get_weight(v, &p) : wdgs_tsdf_volume_get_rgb(v, &p)));
+    return make_ptr(env, p);
+}
+static napi_value tsdfVolumeGetDims(napi_env env, napi_callback_info info) {  // (volume) -> [nx, ny, nz]
+    ARGS(1);
+    uint32_t d[3] = {0, 0, 0};
+    WDGS_OK_OR_THROW(wdgs_tsdf_volume_get_dims((const wdgs_tsdf_volume*)get_ptr(env, argv[0]), d));
+    napi_value a; napi_create_array_with_length(env, 3, &a);
+    for (uint32_t i = 0; i < 3; i++) napi_set_element(env, a, i, make_u32(env, d[i]));
+    return a;
+}
+static napi_value tsdfVolumeIntegrate(napi_env env, napi_callback_info info) {  // (volume, depthPtr, weightSumPtr | null, colourPtr | null, width, height, cameraPtr, minWeightSum)
+    ARGS(8);
+    WDGS_OK_OR_THROW(wdgs_tsdf_volume_integrate((wdgs_tsdf_volume*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_ptr(env, argv[3]),
+                                                get_u32(env, argv[4]), get_u32(env, argv[5]), get_ptr(env, argv[6]), (float)get_f64(env, argv[7])));
+    return js_undefined(env);
+}
+static napi_value tsdfVolumeCountTriangles(napi_env env, napi_callback_info info) {  // (volume, minWeight) -> total
+    ARGS(2);
+    uint32_t total = 0;
+    WDGS_OK_OR_THROW(wdgs_tsdf_volume_count_triangles((wdgs_tsdf_volume*)get_ptr(env, argv[0]), (float)get_f64(env, argv[1]), &total));
+    return make_u32(env, total);
+}
+static napi_value tsdfVolumeEmitTriangles(napi_env env, napi_callback_info info) {  // (volume, positionsPtr, keysPtr | null, coloursPtr | null, capacityTriangles)
+    ARGS(5);
+    WDGS_OK_OR_THROW(wdgs_tsdf_volume_emit_triangles((wdgs_tsdf_volume*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_ptr(env, argv[3]),
+                                                     get_u32(env, argv[4])));
+    return js_undefined(env);
+}
 // Per-Gaussian render contribution (include/webdgs.h: wdgs_tiled_rasterizer_encode_contribution, wdgs_contribution_rule,
 // wdgs_densify_prune_encode_contribution_decision; no reference counterpart)
 static napi_value tiledRasterizerEncodeContribution(napi_env env, napi_callback_info info) {  // (op, statsPtr): adds into the caller's records
@@ -963,6 +1012,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(tiledForwardSet); EXPORT_FN(tiledForwardCheck); EXPORT_FN(tiledForwardSetLongLists); EXPORT_FN(tiledForwardLongListStats); EXPORT_FN(tiledRasterizerBlit); EXPORT_FN(bufferClear);
     EXPORT_FN(tiledRasterizerEncodeDepth); EXPORT_FN(tiledRasterizerGetDepth); EXPORT_FN(depthToRgba8);
     EXPORT_FN(tiledRasterizerEncodeNormal); EXPORT_FN(tiledRasterizerGetNormal); EXPORT_FN(depthToNormals); EXPORT_FN(normalAgreement); EXPORT_FN(normalToRgba8);
+    EXPORT_FN(tsdfVolumeCreate); EXPORT_FN(tsdfVolumeDestroy); EXPORT_FN(tsdfVolumeReset); EXPORT_FN(tsdfVolumeGet); EXPORT_FN(tsdfVolumeGetDims);
+    EXPORT_FN(tsdfVolumeIntegrate); EXPORT_FN(tsdfVolumeCountTriangles); EXPORT_FN(tsdfVolumeEmitTriangles);
     EXPORT_FN(tiledRasterizerEncodeContribution); EXPORT_FN(densifyContributionDecision);
     EXPORT_FN(encoderBegin); EXPORT_FN(encoderFinish); EXPORT_FN(queueSubmit); EXPORT_FN(commandBufferDestroy); EXPORT_FN(queueOnSubmittedWorkDone);
     EXPORT_FN(tiledBackwardMetric); EXPORT_FN(tiledBackwardGet); EXPORT_FN(downsampleRGBA8); EXPORT_FN(imageSSE); EXPORT_FN(imageSSIM);

@@ -26,5 +26,8 @@ export function mergeColmap(images: CameraData[], cameras: CameraData[]): Camera
 export function loadCamera(fileOrFiles: { name?: string; data: Bytes } | { name?: string; data: Bytes }[]): CameraData[];
 export function cameraUniforms(cam: Partial<CameraData>, width?: number, height?: number): Float32Array;
 /** Train / test split, every `every`-th view (index % every === 0) to test: [trainCams, trainImgs, testCams, testImgs]. */
+/** A mesh { vertices, faces, colours } as a binary little-endian PLY (x y z float, red green blue uchar if coloured, vertex_indices list uchar uint). */
+export function meshPLYBytes(mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null }): Buffer;
+export function saveMeshPLY(path: string, mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null }): void;
 export function holdoutSplit<C, I>(cameras: C[], images: I[], every?: number): [C[], I[], C[], I[]];
 export function fromQuat(qx: number, qy: number, qz: number, qw: number): Float32Array;

@@ -310,5 +310,29 @@ function holdoutSplit(cameras, images, every = 8) {
   return [cameras.filter((_, i) => !test(i)), images.filter((_, i) => !test(i)), cameras.filter((_, i) => test(i)), images.filter((_, i) => test(i))];
 }
 
-module.exports = { holdoutSplit, C0, f16Bits, f16ToNumber, decodeHeader, readRawVertex, nShCoeffs, loadPly, loadColmapBin, loadPointCloud, exportPly, loadCameraJson, loadColmapImagesBin,
+/** A mesh { vertices: Float32Array[V*3], faces: Uint32Array[F*3], colours: Uint8Array[V*3] | null } (TSDFVolume.extractMesh) as a binary
+ *  little-endian PLY: the vertex element x y z float and, with colours, red green blue uchar; the face element vertex_indices as list uchar uint.
+ *  The bytes the Python host's loaders.meshPLYBytes writes.  No reference counterpart. */
+function meshPLYBytes(mesh) {
+  const V = mesh.vertices.length / 3, F = mesh.faces.length / 3, c = mesh.colours || null;
+  if (c && c.length !== 3 * V) throw new Error(`meshPLYBytes: ${V} vertices, ${c.length / 3} colours`);
+  const header = ['ply', 'format binary_little_endian 1.0', `element vertex ${V}`, 'property float x', 'property float y', 'property float z']
+    .concat(c ? ['property uchar red', 'property uchar green', 'property uchar blue'] : [])
+    .concat([`element face ${F}`, 'property list uchar uint vertex_indices', 'end_header']).join('\n') + '\n';
+  const vs = c ? 15 : 12, head = Buffer.from(header, 'ascii'), out = Buffer.alloc(head.length + vs * V + 13 * F);
+  head.copy(out, 0);
+  let o = head.length;
+  for (let v = 0; v < V; v++, o += vs) {
+    for (let a = 0; a < 3; a++) out.writeFloatLE(mesh.vertices[3 * v + a], o + 4 * a);
+    if (c) for (let a = 0; a < 3; a++) out[o + 12 + a] = c[3 * v + a];
+  }
+  for (let f = 0; f < F; f++, o += 13) {
+    out[o] = 3;
+    for (let a = 0; a < 3; a++) out.writeUInt32LE(mesh.faces[3 * f + a], o + 1 + 4 * a);
+  }
+  return out;
+}
+function saveMeshPLY(path, mesh) { require('fs').writeFileSync(path, meshPLYBytes(mesh)); }
+
+module.exports = { meshPLYBytes, saveMeshPLY, holdoutSplit, C0, f16Bits, f16ToNumber, decodeHeader, readRawVertex, nShCoeffs, loadPly, loadColmapBin, loadPointCloud, exportPly, loadCameraJson, loadColmapImagesBin,
   loadColmapCamerasBin, mergeColmap, loadCamera, cameraUniforms, fromQuat };

@@ -70,6 +70,13 @@ export class Trainer {
   /** Agreement of the composited normals with the normals of the model's own depth map, per view and weight-averaged over all (1 - cos: a surface
    *  scores near 0); rendered through evaluate's passes, training untouched.  No reference counterpart. */
   normalConsistency(viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): NormalConsistencyResult;
+  /** Fuses the current model's depth maps (and the rendered colour) into a TSDFVolume, view by view in the order given; rendered through evaluate's
+   *  passes, training untouched.  Returns the view list.  No reference counterpart. */
+  fuseDepth(volume: import('./webdgs_hip').TSDFVolume, viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): number[];
+  /** TSDFVolume.fromBounds -> fuseDepth -> extractMesh -> destroy: the current model as a triangle mesh of the box [lo, hi].  No reference counterpart. */
+  extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number,
+              options?: { viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected'; minWeight?: number; truncation?: number; maxWeight?: number;
+                          colour?: boolean }): import('./webdgs_hip').TriangleMesh;
   /** Per-Gaussian render contribution accumulated over the views (default: all training views); no reference counterpart. */
   contributionStats(viewIds?: number[] | null, split?: 'eval' | 'train'): ContributionRecords & { views: number[] };
   /** Contribution-based pruning: kept iff every criterion given is met; fraction f prunes the Gaussians below the k-th smallest sum_q, k = floor(f N). */

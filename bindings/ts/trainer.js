@@ -849,6 +849,36 @@ class Trainer {
       mean: total(sum_a) ? total(sum_e) / total(sum_a) : NaN, ms: Date.now() - t0 };
   }
 
+  // ---------------------------------------------------------------- TSDF fusion and mesh extraction (DESIGN.md section 13; no reference counterpart)
+  /** Fuses the current model's depth maps into `volume` (hip.TSDFVolume): for each view in the order given, the forward pass, rasterize,
+   *  encodeDepth([depthKind, 'weight_sum']) and volume.integrate with the weight sum and the rasterizer's output texture as colour (where the volume
+   *  has colour).  Returns the view list.  Rendered through evaluate's passes with its isolation; a view is integrated only once its render is known
+   *  not to have overflowed its tile-entry lists (one wait per view).  Same results as the Python host's. */
+  fuseDepth(volume, viewIds, split, depthKind) {
+    split = split || 'train'; depthKind = depthKind || 'median';
+    if (depthKind !== 'median' && depthKind !== 'expected') throw new Error(`fuseDepth: depthKind must be 'median' or 'expected', not ${depthKind}`);
+    const { imgs, bufs, ids } = this.evalViews('fuseDepth', viewIds, split);
+    this.evalDrain();
+    for (const v of ids) {
+      this.renderEvalViews([v], imgs, bufs, () => {}, null, 'fuseDepth');   // (returns with the view's complete frame in its pass set)
+      const w = imgs[v].width, h = imgs[v].height, rast = this.evalSet(w, h, bufs[v]).rasterizer;
+      rast.encodeDepth(null, [depthKind, 'weight_sum']);
+      volume.integrate(rast.getDepthTextureView(depthKind), bufs[v], w, h, { weightSum: rast.getDepthTextureView('weight_sum'),
+        colour: volume.colour ? rast.getOutputTextureView() : null });
+    }
+    return ids;
+  }
+  /** The current model as a triangle mesh of the box [lo, hi]: TSDFVolume.fromBounds, fuseDepth over the views, extractMesh(minWeight); the volume is
+   *  destroyed.  options: { viewIds, split, depthKind, minWeight, truncation, maxWeight, colour }.  loaders.saveMeshPLY writes the result. */
+  extractMesh(lo, hi, voxelSize, options) {
+    const o = options || {};
+    const volume = hip.TSDFVolume.fromBounds(this.device, lo, hi, voxelSize, { truncation: o.truncation, maxWeight: o.maxWeight, colour: o.colour });
+    try {
+      this.fuseDepth(volume, o.viewIds, o.split, o.depthKind);
+      return volume.extractMesh(o.minWeight);
+    } finally { volume.destroy(); }
+  }
+
   // ---------------------------------------------------------------- render contribution and contribution-based pruning (no reference counterpart)
   /** { stats, ids }: the views' contribution records (DESIGN.md section 11) accumulated into one new device buffer. */
   contributionBuffer(viewIds, split, what) {

@@ -240,6 +240,28 @@ export function readContribution(buffer: HipBuffer, n: number): ContributionReco
 /** A depth image as rgba8 for presentation: inverse depth between near (white) and far (black), depth 0 black.  No reference counterpart. */
 export function depthToRGBA8(device: HipDevice, depth: HipBuffer, width: number, height: number, near: number, far: number, target: HipBuffer): void;
 export function imageSSIM(device: HipDevice, a: HipBuffer, b: HipBuffer, width: number, height: number, map?: HipBuffer | null): number;
+export interface TSDFVolumeOptions { truncation?: number | null; maxWeight?: number | null; colour?: boolean | null }
+export interface TSDFTriangles { positions: Float32Array; keys: BigUint64Array; colours: Uint8Array | null; count: number }
+export interface TriangleMesh { vertices: Float32Array; faces: Uint32Array; colours: Uint8Array | null; keys?: BigUint64Array }
+/** A device TSDF volume (wdgs_tsdf_volume): fuses depth maps view by view, extracts the zero level set by marching tetrahedra.  No reference counterpart. */
+export class TSDFVolume {
+  constructor(device: HipDevice, origin: ArrayLike<number>, voxelSize: number, dims: ArrayLike<number>, options?: TSDFVolumeOptions);
+  static fromBounds(device: HipDevice, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, options?: TSDFVolumeOptions): TSDFVolume;
+  readonly origin: Float32Array; readonly voxelSize: number; readonly dims: number[]; readonly truncation: number; readonly maxWeight: number;
+  readonly colour: boolean; readonly numVoxels: number;
+  getTSDFBuffer(): HipBuffer;
+  getWeightBuffer(): HipBuffer;
+  getColourBuffer(): HipBuffer;
+  reset(): void;
+  integrate(depth: HipBuffer, camera: HipBuffer, width: number, height: number,
+            options?: { weightSum?: HipBuffer | null; colour?: HipBuffer | null; minWeightSum?: number | null }): void;
+  countTriangles(minWeight?: number | null): number;
+  extractTriangles(minWeight?: number | null): TSDFTriangles;
+  extractMesh(minWeight?: number | null): TriangleMesh;
+  destroy(): void;
+}
+/** extractTriangles' output as an indexed mesh: vertices are the distinct edge keys in ascending order.  No reference counterpart. */
+export function weldTriangles(tri: TSDFTriangles): TriangleMesh;
 /** The packed word of a Gaussian without a normal.  No reference counterpart. */
 export const NO_NORMAL: 0x80008000;
 export interface NormalAgreement { sum_e: number; sum_a: number; pixels: number; value: number }

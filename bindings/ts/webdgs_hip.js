@@ -525,6 +525,95 @@ function imageSSIM(device, a, b, width, height, map) {
  *  (wdgs_depth_to_rgba8).  Stream-ordered; no reference counterpart. */
 function depthToRGBA8(device, depth, width, height, near, far, target) { addon.depthToRgba8(device.handle, depth.ptr, width, height, near, far, target.ptr); }
 
+// ---------------------------------------------------------------- TSDF fusion and mesh extraction (include/webdgs.h, DESIGN.md section 13; no reference counterpart)
+/** A device TSDF volume (wdgs_tsdf_volume): an axis-aligned grid of dims = [nx, ny, nz] voxels of voxelSize in world space, x fastest, voxel (i, j, k)
+ *  centred at origin + (i + .5, j + .5, k + .5) voxelSize.  integrate fuses one depth image per call; extractTriangles / extractMesh take the zero level
+ *  set as triangles by marching tetrahedra.  options: { truncation (default 4 voxels), maxWeight (64), colour (true) }. */
+class TSDFVolume {
+  constructor(device, origin, voxelSize, dims, options) {
+    const o = options || {};
+    this.device = device;
+    this.origin = Float32Array.from(origin);
+    this.voxelSize = Math.fround(voxelSize);
+    this.dims = Array.from(dims, (d) => Math.floor(d));
+    if (this.origin.length !== 3 || this.dims.length !== 3) throw new Error('TSDFVolume: origin and dims must have three entries');
+    this.truncation = Math.fround(o.truncation === undefined || o.truncation === null ? 4.0 * voxelSize : o.truncation);
+    this.maxWeight = o.maxWeight === undefined || o.maxWeight === null ? 64.0 : o.maxWeight;
+    this.colour = o.colour === undefined || o.colour === null ? true : !!o.colour;
+    this.numVoxels = this.dims[0] * this.dims[1] * this.dims[2];
+    this.destroyed = false;
+    this.handle = addon.tsdfVolumeCreate(device.handle, this.origin[0], this.origin[1], this.origin[2], this.voxelSize, this.dims[0], this.dims[1], this.dims[2],
+      this.truncation, this.maxWeight, this.colour ? 1 : 0);
+  }
+  /** The volume that covers the box [lo, hi] with voxels of voxelSize: origin lo, dimensions rounded up (at least 2). */
+  static fromBounds(device, lo, hi, voxelSize, options) {
+    if (!(voxelSize > 0) || ![0, 1, 2].every((a) => Number.isFinite(lo[a]) && Number.isFinite(hi[a]) && hi[a] > lo[a])) {
+      throw new Error('TSDFVolume.fromBounds: needs finite lo < hi and a positive voxel size');
+    }
+    return new TSDFVolume(device, lo, voxelSize, [0, 1, 2].map((a) => Math.max(2, Math.ceil((hi[a] - lo[a]) / voxelSize))), options);
+  }
+  /** f32[nz][ny][nx].  Handing it out counts as a write of the volume: extractTriangles counts anew after it. */
+  getTSDFBuffer() { return this.device.view(addon.tsdfVolumeGet(this.handle, 0), 4 * this.numVoxels); }
+  getWeightBuffer() { return this.device.view(addon.tsdfVolumeGet(this.handle, 1), 4 * this.numVoxels); }
+  /** f32[3][nz][ny][nx]: the r, g and b planes; throws (WDGS_E_STATE) for a volume without colour. */
+  getColourBuffer() { return this.device.view(addon.tsdfVolumeGet(this.handle, 2), 12 * this.numVoxels); }
+  /** tsdf = 1, weight = 0, colour = 0.  Stream-ordered. */
+  reset() { addon.tsdfVolumeReset(this.handle); }
+  /** Fuses one view: depth f32[H*W], camera the 68-float block on the device; options { weightSum, colour (rgba8), minWeightSum (0.5) }.  One pass over
+   *  the volume, no atomics; allocates nothing, so it records; an eager call waits once (it checks the block's size). */
+  integrate(depth, camera, width, height, options) {
+    const o = options || {}, n = width * height;
+    if (depth.size < 4 * n || (o.weightSum && o.weightSum.size < 4 * n) || (o.colour && o.colour.size < 4 * n) || camera.size < 272) {
+      throw new Error(`TSDFVolume.integrate: buffers too small for ${width}x${height}`);
+    }
+    addon.tsdfVolumeIntegrate(this.handle, depth.ptr, o.weightSum ? o.weightSum.ptr : null, o.colour ? o.colour.ptr : null, width, height, camera.ptr,
+      o.minWeightSum === undefined || o.minWeightSum === null ? 0.5 : o.minWeightSum);
+  }
+  /** Counts the mesh's triangles over the cells whose eight corners have weight >= minWeight (count, scan; waits). */
+  countTriangles(minWeight) { return addon.tsdfVolumeCountTriangles(this.handle, minWeight === undefined || minWeight === null ? 1.0 : minWeight); }
+  /** The raw device output: { positions: Float32Array[F*9], keys: BigUint64Array[F*3], colours: Uint8Array[F*12] | null, count: F }, triangles in cell,
+   *  tetrahedron and case order, wound counter-clockwise seen from outside. */
+  extractTriangles(minWeight) {
+    const total = this.countTriangles(minWeight), room = Math.max(total, 1);
+    const pos = this.device.createBuffer({ size: 36 * room }), keys = this.device.createBuffer({ size: 24 * room });
+    const cols = this.colour ? this.device.createBuffer({ size: 12 * room }) : null;
+    try {
+      addon.tsdfVolumeEmitTriangles(this.handle, pos.ptr, keys.ptr, cols ? cols.ptr : null, total);
+      const bytes = (b, n) => (n ? this.device.readBuffer(b, n) : new ArrayBuffer(0));
+      return { positions: new Float32Array(bytes(pos, 36 * total)), keys: new BigUint64Array(bytes(keys, 24 * total)),
+        colours: cols ? new Uint8Array(bytes(cols, 12 * total)) : null, count: total };
+    } finally { pos.destroy(); keys.destroy(); if (cols) cols.destroy(); }
+  }
+  /** The welded mesh (weldTriangles of extractTriangles). */
+  extractMesh(minWeight) { return weldTriangles(this.extractTriangles(minWeight)); }
+  destroy() {
+    if (this.destroyed) return;
+    this.destroyed = true;
+    addon.tsdfVolumeDestroy(this.handle);
+    this.handle = null;
+  }
+}
+/** extractTriangles' output as an indexed mesh: { vertices: Float32Array[V*3], faces: Uint32Array[F*3], colours: Uint8Array[V*3] | null,
+ *  keys: BigUint64Array[V] }.  Vertices are the triangles' distinct edge keys in ascending order (equal keys carry equal position bits); triangles are kept
+ *  as emitted, zero-area ones included.  Host side. */
+function weldTriangles(tri) {
+  const n = tri.keys.length;
+  const order = Array.from({ length: n }, (_, i) => i).sort((a, b) => (tri.keys[a] < tri.keys[b] ? -1 : (tri.keys[a] > tri.keys[b] ? 1 : a - b)));
+  const faces = new Uint32Array(n), first = [];
+  for (let r = 0; r < n; r++) {
+    const i = order[r];
+    if (r === 0 || tri.keys[i] !== tri.keys[order[r - 1]]) first.push(i);   // (the sort is stable in the index: the first occurrence, as np.unique's)
+    faces[i] = first.length - 1;
+  }
+  const V = first.length, vertices = new Float32Array(3 * V), keys = new BigUint64Array(V), colours = tri.colours ? new Uint8Array(3 * V) : null;
+  first.forEach((i, v) => {
+    keys[v] = tri.keys[i];
+    for (let a = 0; a < 3; a++) vertices[3 * v + a] = tri.positions[3 * i + a];
+    if (colours) for (let a = 0; a < 3; a++) colours[3 * v + a] = tri.colours[4 * i + a];
+  });
+  return { vertices, faces, colours, keys };
+}
+
 /** The normals of an f32 depth image by central differences of its back-projection (loaders.backprojectDepth's convention): rgba32f { n, 1 } into
  *  `target`, all zero where a neighbour is missing (wdgs_depth_to_normals).  `camera`: the 68-float block, or [proj[0][0], proj[1][1]].
  *  Stream-ordered; no reference counterpart. */
@@ -598,6 +687,6 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

@@ -618,6 +618,48 @@ int wdgs_comm_broadcast(wdgs_comm* comm, void* ptr_dev, size_t bytes, int root);
 int wdgs_comm_group_start(void);
 int wdgs_comm_group_end(void);
 
+/* ---------------------------------------------------------------- TSDF volume: fusion of depth maps and a triangle mesh
+ * The reference renders colour only and has no counterpart to any of the ten entries below.  The volume is an axis-aligned grid of nx x ny x nz voxels in
+ * world space, x fastest: voxel (i, j, k) has the linear index (k ny + j) nx + i and its centre at origin + (i + 1/2, j + 1/2, k + 1/2) voxel_size.  It holds
+ * tsdf f32 (in units of `truncation`, 1 = free or unseen) and weight f32 per voxel and, with `colour` != 0, rgb as three f32 planes (r, g, b; nx ny nz floats
+ * each).  create allocates everything the other entries use, and resets.  WDGS_E_INVALID when a dimension is < 2, nx ny nz > 2^28 (the mesh has at most 12
+ * triangles per cell: their u32 count cannot overflow), voxel_size or truncation is not positive and finite, max_weight is not >= 1, or the origin is not finite.
+ * No reference counterpart. */
+typedef struct wdgs_tsdf_volume wdgs_tsdf_volume;
+int wdgs_tsdf_volume_create(wdgs_device* dev, const float* origin3, float voxel_size, uint32_t nx, uint32_t ny, uint32_t nz, float truncation, float max_weight,
+                            uint32_t colour, wdgs_tsdf_volume** out);
+int wdgs_tsdf_volume_destroy(wdgs_tsdf_volume* vol);
+/* tsdf = 1, weight = 0, rgb = 0; stream-ordered, recordable.  No reference counterpart. */
+int wdgs_tsdf_volume_reset(wdgs_tsdf_volume* vol);
+/* The device arrays: f32[nx ny nz], f32[nx ny nz], f32[3][nx ny nz] (WDGS_E_STATE for a volume without colour).  A host may write through them, so each call
+ * counts as a write of the volume for emit_triangles' state rule.  No reference counterpart. */
+int wdgs_tsdf_volume_get_tsdf(wdgs_tsdf_volume* vol, void** f32_dev);
+int wdgs_tsdf_volume_get_weight(wdgs_tsdf_volume* vol, void** f32_dev);
+int wdgs_tsdf_volume_get_rgb(wdgs_tsdf_volume* vol, void** f32x3_dev);
+int wdgs_tsdf_volume_get_dims(const wdgs_tsdf_volume* vol, uint32_t* dims3);
+/* Fuses ONE view: a pass over the volume, one thread per voxel, no atomics, f32 in the order given here.  For a voxel centre c: v = view (c, 1) from the 68-float
+ * camera block (view = floats 0-15, column-major; products summed left to right), z = v.z, skipped unless z > 0; px = (((P00 v.x) / z) / 2 + 1/2) W,
+ * py = ((((-P11) v.y) / z) / 2 + 1/2) H (P00 = block[32], P11 = block[37]), the pixel (floor px, floor py), skipped outside the image; d the depth there, skipped
+ * unless d > 0 and finite, and -- with a weight-sum image -- unless its value there is >= min_weight_sum; sdf = d - z, skipped if sdf < -truncation;
+ * t = min(sdf / truncation, 1); then T = (T Wt + t) / (Wt + 1), each colour plane likewise from the pixel's byte / 255 when a colour image is given, and
+ * Wt = min(Wt + 1, max_weight).  A skipped voxel is not written.  The result depends only on the order of the calls.  weight_sum and colour are nullable.
+ * WDGS_E_STATE when colour is given to a volume without colour, and when width, height disagree with the block's floats 64-65: an eager call reads those two
+ * back (a host wait); a call recorded into a command buffer cannot, and writes nothing when they disagree.  No allocation: recordable.  No reference counterpart. */
+int wdgs_tsdf_volume_integrate(wdgs_tsdf_volume* vol, const void* depth_f32_dev, const void* weight_sum_f32_dev, const void* colour_rgba8_dev, uint32_t width,
+                               uint32_t height, const void* camera_dev, float min_weight_sum);
+/* Marching tetrahedra over the cells (i, j, k), 0 <= i < nx - 1 and likewise, whose eight corner voxels all have weight >= min_weight (> 0, finite): each cell is cut
+ * into the six tetrahedra {0, e_a, e_a + e_b, (1,1,1)} of the axis permutations xyz, xzy, yxz, yzx, zxy, zyx; a corner is inside when T < 0 (0 is outside); one or
+ * three inside corners give one triangle, two give two, wound counter-clockwise seen from the outside.  count_triangles counts per cell, scans, waits and returns
+ * the total; it cannot be recorded (WDGS_E_STATE).  No reference counterpart. */
+int wdgs_tsdf_volume_count_triangles(wdgs_tsdf_volume* vol, float min_weight, uint32_t* total);
+/* Writes the `total` triangles of the last count_triangles -- cells in linear order, then tetrahedron order, then triangle order -- as
+ * positions f32[total][3][3], keys u64[total][3] (nullable) and colours rgba8[total][3] (nullable; alpha 255).  A vertex lies on the lattice edge between the
+ * corners A and B, A the one of lower linear index: p = pA + (pB - pA) (T_A / (T_A - T_B)), key = linear_index(A) 8 + (dx + 2 dy + 4 dz - 1) with (dx, dy, dz) the
+ * offset from A to B; equal keys have equal position bits.  WDGS_E_CAPACITY when capacity_triangles < total (nothing is written); WDGS_E_STATE when no count
+ * precedes it, when the volume was integrated, reset or handed out by a getter since the count (the replay of a recorded integrate is not seen), and when colours
+ * are asked of a volume without colour.  No reference counterpart. */
+int wdgs_tsdf_volume_emit_triangles(wdgs_tsdf_volume* vol, void* positions_f32_dev, void* keys_u64_dev, void* colours_rgba8_dev, uint32_t capacity_triangles);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,16 @@ SIGNATURES = {
     "wdgs_comm_broadcast": (_I, [_P, _P, _Z, _I]),
     "wdgs_comm_group_start": (_I, []),
     "wdgs_comm_group_end": (_I, []),
+    "wdgs_tsdf_volume_create": (_I, [_P, C.POINTER(_F), _F, _U, _U, _U, _F, _F, _U, C.POINTER(_P)]),
+    "wdgs_tsdf_volume_destroy": (_I, [_P]),
+    "wdgs_tsdf_volume_reset": (_I, [_P]),
+    "wdgs_tsdf_volume_get_tsdf": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_tsdf_volume_get_weight": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_tsdf_volume_get_rgb": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_tsdf_volume_get_dims": (_I, [_P, C.POINTER(_U)]),
+    "wdgs_tsdf_volume_integrate": (_I, [_P, _P, _P, _P, _U, _U, _P, _F]),
+    "wdgs_tsdf_volume_count_triangles": (_I, [_P, _F, C.POINTER(_U)]),
+    "wdgs_tsdf_volume_emit_triangles": (_I, [_P, _P, _P, _P, _U]),
     "wdgs_optimizer_step_f32_range": (_I, [_P, _P, _P, _P, _P, _U, _U, _P]),
     "wdgs_apply_repacked_rows": (_I, [_P, _U, _P, _U, _U, _P, _P, _P]),
     "wdgs_optimizer_set_guard": (_I, [_P, _P]),

@@ -83,6 +83,18 @@ int launch_gaussian_normals(wdgs_device* dev, u32 n, const u32* gaussians, const
 // normals: u32[num_splats] of launch_gaussian_normals; out: rgba32f[W*H] { N.xyz, A }.  depth's walk (tilewalk.h)
 int launch_normal_composite(wdgs_device* dev, const CompositedFrame& f, const u32* normals, float4* out);
 
+// ---- tsdf.hip.  A volume of dims[0] x dims[1] x dims[2] voxels, x fastest: tsdf, weight f32 per voxel, rgb (nullable) three f32 planes
+int launch_tsdf_reset(wdgs_device* dev, size_t voxels, float* tsdf, float* weight, float* rgb);
+// camera the 68-float block; depth f32[W*H]; weight_sum f32[W*H] and colour rgba8[W*H] nullable
+int launch_tsdf_integrate(wdgs_device* dev, const float origin[3], float voxel_size, const u32 dims[3], float truncation, float max_weight, const float* camera,
+                          const float* depth, const float* weight_sum, const u32* colour, u32 width, u32 height, float min_weight_sum, float* tsdf, float* weight,
+                          float* rgb);
+// counts: u32 per cell, (dims[0]-1)(dims[1]-1)(dims[2]-1) of them, written
+int launch_tsdf_count(wdgs_device* dev, const float origin[3], float voxel_size, const u32 dims[3], const float* tsdf, const float* weight, float min_weight, u32* counts);
+// counts, offsets: launch_tsdf_count's and their scan; positions f32[total][3][3], keys u64[total][3] and colours rgba8[total][3] (both nullable; colours needs rgb)
+int launch_tsdf_emit(wdgs_device* dev, const float origin[3], float voxel_size, const u32 dims[3], const float* tsdf, const float* weight, const float* rgb, float min_weight,
+                     const u32* counts, const u32* offsets, float* positions, unsigned long long* keys, u32* colours);
+
 // ---- loss.hip, dssim.hip.  pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
 int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
                      const u32* acc_dirty);

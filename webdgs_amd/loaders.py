@@ -312,6 +312,75 @@ def backprojectDepth(depth: np.ndarray, camera) -> np.ndarray:
     return (view @ view_inv.T)[:, :3].astype(np.float32)
 
 
+# ----------------------------------------------------------------------------- triangle meshes (no reference counterpart)
+def meshPLYBytes(mesh: dict) -> bytes:
+    """A mesh ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None)`` (``ops.TSDFVolume.extractMesh``) as a binary little-endian PLY: the
+    vertex element ``x y z`` float and, with colours, ``red green blue`` uchar; the face element ``vertex_indices`` as ``list uchar uint``."""
+    v = np.ascontiguousarray(mesh["vertices"], "<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(mesh["faces"], "<u4").reshape(-1, 3)
+    c = mesh.get("colours")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y", "property float z"]
+    if c is not None:
+        c = np.ascontiguousarray(c, np.uint8).reshape(-1, 3)
+        if c.shape[0] != v.shape[0]:
+            raise ValueError(f"meshPLYBytes: {v.shape[0]} vertices, {c.shape[0]} colours")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header += [f"element face {f.shape[0]}", "property list uchar uint vertex_indices", "end_header"]
+    vert = np.empty(v.shape[0], np.dtype(fields))
+    vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if c is not None:
+        vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    face = np.empty(f.shape[0], np.dtype([("n", "u1"), ("i", "<u4", (3,))]))
+    face["n"] = 3
+    face["i"] = f
+    return ("\n".join(header) + "\n").encode("ascii") + vert.tobytes() + face.tobytes()
+
+
+def saveMeshPLY(path: str, mesh: dict) -> None:
+    """Writes ``meshPLYBytes(mesh)`` to ``path``; ``loadMeshPLY`` reads it back exactly."""
+    with open(path, "wb") as fh:
+        fh.write(meshPLYBytes(mesh))
+
+
+def loadMeshPLY(path: str) -> dict:
+    """Reads a mesh PLY as ``saveMeshPLY`` writes it (triangles only): ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None)``."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError("loadMeshPLY: not a PLY file")
+    lines = data[:end].decode("ascii").split("\n")
+    body = data[end + len(b"end_header\n"):]
+    if "format binary_little_endian 1.0" not in lines:
+        raise ValueError("loadMeshPLY: only binary little-endian PLY is read")
+    elements, props = {}, {}
+    for ln in lines:
+        w = ln.split()
+        if w[:1] == ["element"]:
+            cur = w[1]
+            elements[cur] = int(w[2])
+            props[cur] = []
+        elif w[:1] == ["property"]:
+            props[cur].append(" ".join(w[1:]))
+    xyz, rgb = ["float x", "float y", "float z"], ["uchar red", "uchar green", "uchar blue"]
+    if list(elements) != ["vertex", "face"] or props["vertex"] not in (xyz, xyz + rgb) or props["face"] != ["list uchar uint vertex_indices"]:
+        raise ValueError("loadMeshPLY: not a mesh as saveMeshPLY writes it")
+    coloured = props["vertex"] == xyz + rgb
+    vdt = np.dtype([("p", "<f4", (3,))] + ([("c", "u1", (3,))] if coloured else []))
+    fdt = np.dtype([("n", "u1"), ("i", "<u4", (3,))])
+    nv, nf = elements["vertex"], elements["face"]
+    if len(body) != nv * vdt.itemsize + nf * fdt.itemsize:
+        raise ValueError("loadMeshPLY: the body's length disagrees with the header")
+    vert = np.frombuffer(body, vdt, count=nv)
+    face = np.frombuffer(body, fdt, count=nf, offset=nv * vdt.itemsize)
+    if nf and not np.all(face["n"] == 3):
+        raise ValueError("loadMeshPLY: only triangles are read")
+    return dict(vertices=np.ascontiguousarray(vert["p"], np.float32), faces=np.ascontiguousarray(face["i"], np.uint32),
+                colours=np.ascontiguousarray(vert["c"]) if coloured else None)
+
+
 # ----------------------------------------------------------------------------- held-out split (no reference counterpart)
 def holdoutSplit(cameras: list, images: list, every: int = 8) -> tuple:
     """Train / test split of a dataset by the Mip-NeRF 360 / 3DGS ``--eval`` convention: view ``i`` is a test view when ``i % every == 0``.

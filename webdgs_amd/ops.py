@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import math
 import re
 from typing import NamedTuple, Optional
 
@@ -838,6 +839,121 @@ def normalToRGBA8(device: HipDevice, normal: HipBuffer, width: int, height: int,
     if normal.size < 16 * n or target.size < 4 * n:
         raise ValueError(f"normalToRGBA8: buffers too small for {width}x{height}")
     check(device.lib.wdgs_normal_to_rgba8(device.handle, normal.ptr, int(width), int(height), target.ptr))
+
+
+# ----------------------------------------------------------------------------- TSDF fusion and mesh extraction (no reference counterpart)
+class TSDFVolume:
+    """A device TSDF volume (``wdgs_tsdf_volume``): an axis-aligned grid of ``dims = (nx, ny, nz)`` voxels of ``voxelSize`` in world space, x fastest,
+    voxel ``(i, j, k)`` centred at ``origin + (i + .5, j + .5, k + .5) voxelSize``.  ``integrate`` fuses one depth image per call, ``extractTriangles`` /
+    ``extractMesh`` take the zero level set as triangles by marching tetrahedra.  ``truncation=None``: 4 voxels."""
+
+    def __init__(self, device: HipDevice, origin, voxelSize: float, dims, truncation: Optional[float] = None, maxWeight: float = 64.0, colour: bool = True):
+        self.device = device
+        self.origin = np.asarray(origin, np.float32).reshape(3).copy()
+        self.voxelSize = float(np.float32(voxelSize))
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3:
+            raise ValueError("TSDFVolume: dims must be (nx, ny, nz)")
+        self.truncation = float(np.float32(4.0 * voxelSize if truncation is None else truncation))
+        self.maxWeight = float(maxWeight)
+        self.colour = bool(colour)
+        self.numVoxels = self.dims[0] * self.dims[1] * self.dims[2]
+        self.destroyed = False
+        h = C.c_void_p()
+        o = (C.c_float * 3)(*[float(x) for x in self.origin])
+        for d in self.dims:
+            if not 0 <= d < 2 ** 32:
+                raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"TSDFVolume: bad dimensions {self.dims}")
+        check(device.lib.wdgs_tsdf_volume_create(device.handle, o, self.voxelSize, self.dims[0], self.dims[1], self.dims[2], self.truncation, self.maxWeight,
+                                                 1 if self.colour else 0, C.byref(h)))
+        self.handle = h
+
+    @classmethod
+    def fromBounds(cls, device: HipDevice, lo, hi, voxelSize: float, **kwargs) -> "TSDFVolume":
+        """The volume that covers the box ``[lo, hi]`` with voxels of ``voxelSize``: origin ``lo``, dimensions rounded up (at least 2)."""
+        lo64, hi64 = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+        if not (np.all(np.isfinite(lo64)) and np.all(np.isfinite(hi64)) and np.all(hi64 > lo64) and voxelSize > 0):
+            raise ValueError("TSDFVolume.fromBounds: needs finite lo < hi and a positive voxel size")
+        dims = [max(2, int(math.ceil(float(e) / float(voxelSize)))) for e in (hi64 - lo64)]
+        return cls(device, lo64, voxelSize, dims, **kwargs)
+
+    def _get(self, fn, nbytes: int) -> HipBuffer:
+        p = C.c_void_p()
+        check(fn(self.handle, C.byref(p)))
+        return self.device.view(p.value, nbytes)
+
+    def getTSDFBuffer(self) -> HipBuffer:
+        """f32[nz][ny][nx].  Handing it out counts as a write of the volume: ``extractTriangles`` counts anew after it."""
+        return self._get(self.device.lib.wdgs_tsdf_volume_get_tsdf, 4 * self.numVoxels)
+
+    def getWeightBuffer(self) -> HipBuffer:
+        """f32[nz][ny][nx]."""
+        return self._get(self.device.lib.wdgs_tsdf_volume_get_weight, 4 * self.numVoxels)
+
+    def getColourBuffer(self) -> HipBuffer:
+        """f32[3][nz][ny][nx]: the r, g and b planes; raises ``StateError`` for a volume without colour."""
+        return self._get(self.device.lib.wdgs_tsdf_volume_get_rgb, 12 * self.numVoxels)
+
+    def reset(self) -> None:
+        """tsdf = 1, weight = 0, colour = 0.  Stream-ordered."""
+        check(self.device.lib.wdgs_tsdf_volume_reset(self.handle))
+
+    def integrate(self, depth: HipBuffer, camera: HipBuffer, width: int, height: int, weightSum: Optional[HipBuffer] = None, colour: Optional[HipBuffer] = None,
+                  minWeightSum: float = 0.5) -> None:
+        """Fuses one view: ``depth`` f32[H*W] (``getDepthTextureView``), ``camera`` the 68-float block on the device, ``weightSum`` (optional) the
+        weight-sum image whose pixels below ``minWeightSum`` are ignored, ``colour`` (optional) an rgba8 image.  One pass over the volume, no atomics:
+        the result depends only on the order of the calls.  Allocates nothing, so it records; an eager call waits once (it checks the block's size)."""
+        n = int(width) * int(height)
+        if depth.size < 4 * n or (weightSum is not None and weightSum.size < 4 * n) or (colour is not None and colour.size < 4 * n) or camera.size < 272:
+            raise ValueError(f"TSDFVolume.integrate: buffers too small for {width}x{height}")
+        check(self.device.lib.wdgs_tsdf_volume_integrate(self.handle, depth.ptr, weightSum.ptr if weightSum is not None else None,
+                                                         colour.ptr if colour is not None else None, int(width), int(height), camera.ptr, float(minWeightSum)))
+
+    def countTriangles(self, minWeight: float = 1.0) -> int:
+        """Counts the mesh's triangles over the cells whose eight corners have ``weight >= minWeight`` (count, scan; waits)."""
+        n = C.c_uint32(0)
+        check(self.device.lib.wdgs_tsdf_volume_count_triangles(self.handle, float(minWeight), C.byref(n)))
+        return int(n.value)
+
+    def extractTriangles(self, minWeight: float = 1.0) -> dict:
+        """The raw device output as numpy: ``dict(positions f32[F,3,3], keys u64[F,3], colours u8[F,3,4] | None)``, triangles in cell, tetrahedron
+        and case order, wound counter-clockwise seen from outside."""
+        total = self.countTriangles(minWeight)
+        pos = self.device.createBuffer(36 * max(total, 1), "tsdf triangle positions")
+        keys = self.device.createBuffer(24 * max(total, 1), "tsdf triangle keys")
+        cols = self.device.createBuffer(12 * max(total, 1), "tsdf triangle colours") if self.colour else None
+        try:
+            check(self.device.lib.wdgs_tsdf_volume_emit_triangles(self.handle, pos.ptr, keys.ptr, cols.ptr if cols is not None else None, total))
+            return dict(positions=pos.read(np.float32, count=9 * total).reshape(total, 3, 3), keys=keys.read(np.uint64, count=3 * total).reshape(total, 3),
+                        colours=cols.read(np.uint8, count=12 * total).reshape(total, 3, 4) if cols is not None else None)
+        finally:
+            pos.destroy()
+            keys.destroy()
+            if cols is not None:
+                cols.destroy()
+
+    def extractMesh(self, minWeight: float = 1.0) -> dict:
+        """The welded mesh: ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None, keys u64[V])``.  Vertices are the triangles' distinct edge
+        keys in ascending order (equal keys carry equal position bits); triangles are kept as emitted, zero-area ones included.  Welded on the host."""
+        return weldTriangles(self.extractTriangles(minWeight))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_tsdf_volume_destroy(self.handle)
+        self.handle = None
+
+
+def weldTriangles(tri: dict) -> dict:
+    """``TSDFVolume.extractTriangles``'s output as an indexed mesh (see ``TSDFVolume.extractMesh``).  Host side (numpy)."""
+    keys = np.ascontiguousarray(tri["keys"], np.uint64).reshape(-1)
+    uniq, first, inverse = np.unique(keys, return_index=True, return_inverse=True)
+    if uniq.size >= 2 ** 32:
+        raise ValueError("weldTriangles: 2^32 vertices or more")
+    vertices = np.ascontiguousarray(tri["positions"], np.float32).reshape(-1, 3)[first]
+    colours = None if tri.get("colours") is None else np.ascontiguousarray(np.asarray(tri["colours"], np.uint8).reshape(-1, 4)[first, :3])
+    return dict(vertices=np.ascontiguousarray(vertices), faces=inverse.reshape(-1, 3).astype(np.uint32), colours=colours, keys=uniq)
 
 
 # ----------------------------------------------------------------------------- per-Gaussian contribution (DESIGN.md section 11; no reference counterpart)

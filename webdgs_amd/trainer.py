@@ -1029,6 +1029,39 @@ class Trainer:
         return dict(iteration=self.iteration, views=ids, value=[(e / a) if a else float("nan") for e, a in zip(sum_e, sum_a)], pixels=pixels,
                     sum_e=sum_e, sum_a=sum_a, mean=(sum(sum_e) / sum(sum_a)) if sum(sum_a) else float("nan"), ms=(time.perf_counter() - t0) * 1e3)
 
+    # ------------------------------------------------------------------ TSDF fusion and mesh extraction (no reference counterpart)
+    def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
+        """Fuses the current model's depth maps into ``volume``: for each view in the order given, the forward pass, rasterize,
+        ``encodeDepth((depthKind, "weight_sum"))`` and ``volume.integrate`` with the weight sum and the rasterizer's output texture as colour (where the
+        volume has colour).  Returns the view list.
+
+        Rendered through evaluate's passes, with its isolation: the pipeline is drained, no RNG draw, no training pass, no recording dropped, the
+        iteration counter untouched.  A view is integrated only once its render is known not to have overflowed its tile-entry lists (one wait per view):
+        a fusion cannot be taken back, so it never sees a truncated render.  Per rank with ``world_size > 1``."""
+        if depthKind not in ("median", "expected"):
+            raise ValueError(f"fuseDepth: depthKind must be 'median' or 'expected', not {depthKind!r}")
+        cams, imgs, bufs, ids = self._eval_views("fuseDepth", viewIds, split)
+        self._eval_drain()
+        for v in ids:
+            self._render_eval_views([v], imgs, bufs, lambda i, v, s, w, h: None, what="fuseDepth")   # (returns with the view's complete frame in its pass set)
+            w, h = int(imgs[v]["width"]), int(imgs[v]["height"])
+            rast = self._eval_set(w, h, bufs[v]).rasterizer
+            rast.encodeDepth(None, (depthKind, "weight_sum"))
+            volume.integrate(rast.getDepthTextureView(depthKind), bufs[v], w, h, weightSum=rast.getDepthTextureView("weight_sum"),
+                             colour=rast.getOutputTextureView() if volume.colour else None)
+        return ids
+
+    def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
+                    **volumeOptions) -> dict:
+        """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
+        ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result."""
+        volume = ops.TSDFVolume.fromBounds(self.device, lo, hi, voxelSize, **volumeOptions)
+        try:
+            self.fuseDepth(volume, viewIds, split, depthKind)
+            return volume.extractMesh(minWeight)
+        finally:
+            volume.destroy()
+
     # ------------------------------------------------------------------ render contribution and contribution-based pruning (no reference counterpart)
     def _contribution_buffer(self, viewIds: Optional[list], split: str, what: str) -> tuple:
         """(buffer, view ids): the views' contribution records accumulated into one new device buffer."""
