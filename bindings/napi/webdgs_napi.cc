@@ -405,6 +405,66 @@ static napi_value tsdfVolumeEmitTriangles(napi_env env, napi_callback_info info)
                                                      get_u32(env, argv[4])));
     return js_undefined(env);
 }
+// Mesh accuracy metrics (include/webdgs.h: wdgs_mesh_sampler_*, wdgs_point_index_*, wdgs_point_distance_stats; no reference counterpart)
+static napi_value meshSamplerCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_mesh_sampler* s = nullptr;
+    WDGS_OK_OR_THROW(wdgs_mesh_sampler_create((wdgs_device*)get_ptr(env, argv[0]), &s));
+    return make_ptr(env, s);
+}
+static napi_value meshSamplerDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_mesh_sampler_destroy((wdgs_mesh_sampler*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value meshSamplerCount(napi_env env, napi_callback_info info) {  // (sampler, verticesPtr, numVertices, facesPtr, numFaces, density, seed) -> total
+    ARGS(7);
+    uint64_t total = 0;
+    WDGS_OK_OR_THROW(wdgs_mesh_sampler_count((wdgs_mesh_sampler*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_ptr(env, argv[3]),
+                                             get_u32(env, argv[4]), (float)get_f64(env, argv[5]), get_u32(env, argv[6]), &total));
+    napi_value v; napi_create_double(env, (double)total, &v);   // (below 2^31 whenever the call succeeds)
+    return v;
+}
+static napi_value meshSamplerEmit(napi_env env, napi_callback_info info) {  // (sampler, verticesPtr, numVertices, facesPtr, numFaces, density, seed, pointsPtr, facePtr | null, capacity)
+    ARGS(10);
+    WDGS_OK_OR_THROW(wdgs_mesh_sampler_emit((wdgs_mesh_sampler*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_ptr(env, argv[3]),
+                                            get_u32(env, argv[4]), (float)get_f64(env, argv[5]), get_u32(env, argv[6]), get_ptr(env, argv[7]), get_ptr(env, argv[8]),
+                                            get_u32(env, argv[9])));
+    return js_undefined(env);
+}
+static napi_value pointIndexCreate(napi_env env, napi_callback_info info) {  // (device, pointsPtr, numPoints, cellSize: 0 = chosen by the first query) -> handle
+    ARGS(4);
+    wdgs_point_index* ix = nullptr;
+    const double n = get_f64(env, argv[2]);
+    WDGS_OK_OR_THROW(wdgs_point_index_create((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), n >= 0 ? (uint64_t)n : ~0ull, (float)get_f64(env, argv[3]), &ix));
+    return make_ptr(env, ix);
+}
+static napi_value pointIndexDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_point_index_destroy((wdgs_point_index*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value pointIndexReserveQueries(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    WDGS_OK_OR_THROW(wdgs_point_index_reserve_queries((wdgs_point_index*)get_ptr(env, argv[0]), get_u32(env, argv[1])));
+    return js_undefined(env);
+}
+static napi_value pointIndexInfo(napi_env env, napi_callback_info info) {  // (index) -> [cellSize, nx, ny, nz, indexed]
+    ARGS(1);
+    float cell = 0.f;
+    uint32_t d[3] = {0, 0, 0}, indexed = 0;
+    WDGS_OK_OR_THROW(wdgs_point_index_info((const wdgs_point_index*)get_ptr(env, argv[0]), &cell, d, &indexed));
+    napi_value a, c; napi_create_array_with_length(env, 5, &a);
+    napi_create_double(env, (double)cell, &c);
+    napi_set_element(env, a, 0, c);
+    for (uint32_t i = 0; i < 3; i++) napi_set_element(env, a, 1 + i, make_u32(env, d[i]));
+    napi_set_element(env, a, 4, make_u32(env, indexed));
+    return a;
+}
+static napi_value pointIndexNearest(napi_env env, napi_callback_info info) {  // (index, queriesPtr, numQueries, maxDistance, d2Ptr, indexPtr, pairsPtr | null)
+    ARGS(7);
+    WDGS_OK_OR_THROW(wdgs_point_index_nearest((wdgs_point_index*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), (float)get_f64(env, argv[3]),
+                                              get_ptr(env, argv[4]), get_ptr(env, argv[5]), get_ptr(env, argv[6])));
+    return js_undefined(env);
+}
+static napi_value pointDistanceStats(napi_env env, napi_callback_info info) {  // (device, d2Ptr, count, maxDistance, threshold, outPtr): u64 {n_found, n_within, sum_q}
+    ARGS(6);
+    WDGS_OK_OR_THROW(wdgs_point_distance_stats((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), (float)get_f64(env, argv[3]),
+                                               (float)get_f64(env, argv[4]), get_ptr(env, argv[5])));
+    return js_undefined(env);
+}
 // Per-Gaussian render contribution (include/webdgs.h: wdgs_tiled_rasterizer_encode_contribution, wdgs_contribution_rule,
 // wdgs_densify_prune_encode_contribution_decision; no reference counterpart)
 static napi_value tiledRasterizerEncodeContribution(napi_env env, napi_callback_info info) {  // (op, statsPtr): adds into the caller's records
@@ -1014,6 +1074,9 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(tiledRasterizerEncodeNormal); EXPORT_FN(tiledRasterizerGetNormal); EXPORT_FN(depthToNormals); EXPORT_FN(normalAgreement); EXPORT_FN(normalToRgba8);
     EXPORT_FN(tsdfVolumeCreate); EXPORT_FN(tsdfVolumeDestroy); EXPORT_FN(tsdfVolumeReset); EXPORT_FN(tsdfVolumeGet); EXPORT_FN(tsdfVolumeGetDims);
     EXPORT_FN(tsdfVolumeIntegrate); EXPORT_FN(tsdfVolumeCountTriangles); EXPORT_FN(tsdfVolumeEmitTriangles);
+    EXPORT_FN(meshSamplerCreate); EXPORT_FN(meshSamplerDestroy); EXPORT_FN(meshSamplerCount); EXPORT_FN(meshSamplerEmit);
+    EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
+    EXPORT_FN(pointDistanceStats);
     EXPORT_FN(tiledRasterizerEncodeContribution); EXPORT_FN(densifyContributionDecision);
     EXPORT_FN(encoderBegin); EXPORT_FN(encoderFinish); EXPORT_FN(queueSubmit); EXPORT_FN(commandBufferDestroy); EXPORT_FN(queueOnSubmittedWorkDone);
     EXPORT_FN(tiledBackwardMetric); EXPORT_FN(tiledBackwardGet); EXPORT_FN(downsampleRGBA8); EXPORT_FN(imageSSE); EXPORT_FN(imageSSIM);

@@ -334,5 +334,48 @@ function meshPLYBytes(mesh) {
 }
 function saveMeshPLY(path, mesh) { require('fs').writeFileSync(path, meshPLYBytes(mesh)); }
 
-module.exports = { meshPLYBytes, saveMeshPLY, holdoutSplit, C0, f16Bits, f16ToNumber, decodeHeader, readRawVertex, nShCoeffs, loadPly, loadColmapBin, loadPointCloud, exportPly, loadCameraJson, loadColmapImagesBin,
+// ---------------------------------------------------------------- point sets (no reference counterpart)
+const PLY_SCALAR = { char: 1, int8: 1, uchar: 1, uint8: 1, short: 2, int16: 2, ushort: 2, uint16: 2, int: 4, int32: 4, uint: 4, uint32: 4, float: 4, float32: 4, double: 8, float64: 8 };
+/** Points (Float32Array [N*3]) as a binary little-endian PLY with the one element `vertex` of x y z float. */
+function pointsPLYBytes(points) {
+  const p = points instanceof Float32Array ? points : Float32Array.from(points);
+  if (p.length % 3 !== 0) throw new Error(`pointsPLYBytes: expected 3 values per point, got ${p.length} values`);
+  const header = ['ply', 'format binary_little_endian 1.0', `element vertex ${p.length / 3}`, 'property float x', 'property float y', 'property float z', 'end_header'];
+  return Buffer.concat([Buffer.from(header.join('\n') + '\n', 'ascii'), Buffer.from(p.buffer, p.byteOffset, p.byteLength)]);
+}
+/** Writes pointsPLYBytes(points) to `path`; loadPointsPLY reads it back exactly. */
+function savePointsPLY(path, points) { require('fs').writeFileSync(path, pointsPLYBytes(points)); }
+/** The vertex positions (Float32Array [N*3]) of a binary little-endian PLY: a reference scan, savePointsPLY's output, or a mesh (its faces are not read).
+ *  The vertex element comes first and holds float x y z among scalar properties; its other properties are skipped. */
+function loadPointsPLY(path) {
+  const data = require('fs').readFileSync(path);
+  const end = data.indexOf('end_header\n');
+  if (data.slice(0, 4).toString('ascii') !== 'ply\n' || end < 0) throw new Error('loadPointsPLY: not a PLY file');
+  const lines = data.slice(0, end).toString('ascii').split('\n');
+  if (!lines.includes('format binary_little_endian 1.0')) throw new Error('loadPointsPLY: only binary little-endian PLY is read');
+  let first = null, count = 0, stride = 0;
+  const at = {};
+  for (const ln of lines) {
+    const w = ln.split(/\s+/).filter((x) => x.length);
+    if (w[0] === 'element') {
+      if (first !== null) break;
+      first = w[1]; count = parseInt(w[2], 10);
+    } else if (w[0] === 'property' && first !== null) {
+      if (w.length !== 3 || !(w[1] in PLY_SCALAR)) throw new Error(`loadPointsPLY: vertex property '${w.slice(1).join(' ')}' is not a scalar`);
+      if (w[1] === 'float' || w[1] === 'float32') at[w[2]] = stride;
+      stride += PLY_SCALAR[w[1]];
+    }
+  }
+  if (first !== 'vertex') throw new Error("loadPointsPLY: the first element must be 'vertex'");
+  if (at.x === undefined || at.y === undefined || at.z === undefined) throw new Error('loadPointsPLY: the vertex element needs float x, y and z');
+  const body = data.slice(end + 'end_header\n'.length);
+  if (body.length < count * stride) throw new Error('loadPointsPLY: the body is shorter than the header says');
+  const out = new Float32Array(3 * count), bits = new Uint32Array(out.buffer);
+  for (let i = 0; i < count; i++) {   // (bit patterns, so that a NaN's payload survives)
+    bits[3 * i] = body.readUInt32LE(i * stride + at.x); bits[3 * i + 1] = body.readUInt32LE(i * stride + at.y); bits[3 * i + 2] = body.readUInt32LE(i * stride + at.z);
+  }
+  return out;
+}
+
+module.exports = { pointsPLYBytes, savePointsPLY, loadPointsPLY, meshPLYBytes, saveMeshPLY, holdoutSplit, C0, f16Bits, f16ToNumber, decodeHeader, readRawVertex, nShCoeffs, loadPly, loadColmapBin, loadPointCloud, exportPly, loadCameraJson, loadColmapImagesBin,
   loadColmapCamerasBin, mergeColmap, loadCamera, cameraUniforms, fromQuat };

@@ -868,6 +868,23 @@ class Trainer {
     }
     return ids;
   }
+  /** Scores the current model's geometry against `reference` -- a Float32Array [M*3] of surface points, or the path of a PLY that holds them:
+   *  extractMesh(lo, hi, voxelSize, options), hip.sampleMesh at options.density samples per unit area (default 1 / (voxelSize / 2)^2, a spacing of half a
+   *  voxel; options.seed, default 0) and hip.geometryMetrics(samples, reference, maxDistance, threshold).  Returns its object -- accuracy, completeness,
+   *  chamfer, precision, recall, fscore and the counts -- with vertices, faces, samples (the mesh's and the sample count) and ms.  extractMesh's isolation
+   *  (fuseDepth's); no alignment is attempted: the reference is taken to be in the scene's frame. */
+  evaluateGeometry(reference, lo, hi, voxelSize, maxDistance, threshold, options) {
+    const o = options || {}, t0 = Date.now();
+    const ref = typeof reference === 'string' ? require('./loaders.js').loadPointsPLY(reference) : reference;
+    const density = o.density === undefined || o.density === null ? 1.0 / (0.5 * voxelSize) ** 2 : o.density;
+    const mesh = this.extractMesh(lo, hi, voxelSize, o);
+    const samples = hip.sampleMesh(this.device, mesh, density, o.seed || 0, { asBuffers: true });
+    let out;
+    try {
+      out = hip.geometryMetrics(this.device, samples.points, ref, maxDistance, threshold, { numPoints: samples.count });
+    } finally { samples.points.destroy(); samples.face.destroy(); }
+    return Object.assign(out, { vertices: mesh.vertices.length / 3, faces: mesh.faces.length / 3, samples: samples.count, ms: Date.now() - t0 });
+  }
   /** The current model as a triangle mesh of the box [lo, hi]: TSDFVolume.fromBounds, fuseDepth over the views, extractMesh(minWeight); the volume is
    *  destroyed.  options: { viewIds, split, depthKind, minWeight, truncation, maxWeight, colour }.  loaders.saveMeshPLY writes the result. */
   extractMesh(lo, hi, voxelSize, options) {

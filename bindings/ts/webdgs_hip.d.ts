@@ -262,6 +262,45 @@ export class TSDFVolume {
 }
 /** extractTriangles' output as an indexed mesh: vertices are the distinct edge keys in ascending order.  No reference counterpart. */
 export function weldTriangles(tri: TSDFTriangles): TriangleMesh;
+/** The index of "no point found" (PointIndex.nearest).  No reference counterpart. */
+export const NO_INDEX: 0xFFFFFFFF;
+export interface MeshSamples { points: Float32Array; face: Uint32Array; count: number }
+export interface MeshSampleBuffers { points: HipBuffer; face: HipBuffer; count: number }
+/** Area-weighted surface sampling of a triangle mesh on the device (wdgs_mesh_sampler): count, then emit with the same arguments.  No reference counterpart. */
+export class MeshSampler {
+  constructor(device: HipDevice);
+  count(vertices: HipBuffer, numVertices: number, faces: HipBuffer, numFaces: number, density: number, seed?: number): number;
+  emit(vertices: HipBuffer, numVertices: number, faces: HipBuffer, numFaces: number, density: number, seed: number, points: HipBuffer, face?: HipBuffer | null,
+       capacity?: number | null): void;
+  destroy(): void;
+}
+/** Points on the surface of a mesh, `density` per unit area on average; a function of its arguments alone, bit for bit.  No reference counterpart. */
+export function sampleMesh(device: HipDevice, mesh: { vertices: Float32Array | HipBuffer; faces: Uint32Array | HipBuffer }, density: number, seed?: number,
+                           options?: { asBuffers?: false }): MeshSamples;
+export function sampleMesh(device: HipDevice, mesh: { vertices: Float32Array | HipBuffer; faces: Uint32Array | HipBuffer }, density: number, seed: number,
+                           options: { asBuffers: true }): MeshSampleBuffers;
+/** A uniform grid over points for exact nearest-point queries under a cutoff (wdgs_point_index); the cell edge is a speed parameter only.  No reference
+ *  counterpart. */
+export class PointIndex {
+  constructor(device: HipDevice, points: Float32Array | HipBuffer, options?: { cellSize?: number | null; count?: number | null });
+  readonly numPoints: number;
+  info(): { cellSize: number; dims: number[]; indexed: number };
+  reserveQueries(count: number): void;
+  nearestInto(encoder: HipEncoder | null, queries: HipBuffer, count: number, maxDistance: number, d2: HipBuffer, index: HipBuffer, pairs?: HipBuffer | null): void;
+  nearest(queries: Float32Array | HipBuffer, maxDistance: number): { d2: Float32Array; index: Uint32Array };
+  destroy(): void;
+}
+export interface PointDistanceStats { n: number; n_found: number; n_within: number; sum_q: number; mean: number }
+/** Stream-ordered pointDistanceStats: three u64 { n_found, n_within, sum_q } into the first 24 bytes of `out`. */
+export function encodePointDistanceStats(device: HipDevice, d2: HipBuffer, count: number, maxDistance: number, threshold: number, out: HipBuffer): void;
+export function pointDistanceStats(device: HipDevice, d2: Float32Array | HipBuffer, maxDistance: number, threshold: number, count?: number | null): PointDistanceStats;
+export interface GeometryMetrics {
+  accuracy: number; completeness: number; chamfer: number; precision: number; recall: number; fscore: number;
+  n_points: number; n_reference: number; outliers_points: number; outliers_reference: number;
+}
+/** Accuracy, completeness, Chamfer distance and precision / recall / F-score of a point set against a reference set.  No reference counterpart. */
+export function geometryMetrics(device: HipDevice, points: Float32Array | HipBuffer, reference: Float32Array | HipBuffer, maxDistance: number, threshold: number,
+                                options?: { numPoints?: number | null; numReference?: number | null }): GeometryMetrics;
 /** The packed word of a Gaussian without a normal.  No reference counterpart. */
 export const NO_NORMAL: 0x80008000;
 export interface NormalAgreement { sum_e: number; sum_a: number; pixels: number; value: number }

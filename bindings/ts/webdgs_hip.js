@@ -614,6 +614,159 @@ function weldTriangles(tri) {
   return { vertices, faces, colours, keys };
 }
 
+// ---------------------------------------------------------------- mesh accuracy metrics (include/webdgs.h, DESIGN.md section 14; no reference counterpart)
+const NO_INDEX = 0xFFFFFFFF;
+/** { buf, rows, owned } of a [rows, width] array given as a typed array (uploaded; owned) or as a HipBuffer (whole rows of it). */
+function asDevice(device, array, Type, width, what) {
+  if (array instanceof HipBuffer) return { buf: array, rows: Math.floor(array.size / (Type.BYTES_PER_ELEMENT * width)), owned: false };
+  const a = array instanceof Type ? array : Type.from(array);
+  if (a.length % width !== 0) throw new Error(`${what}: expected ${width} values per row, got ${a.length} values`);
+  const buf = device.createBuffer({ size: Math.max(a.byteLength, 4), label: what });
+  if (a.byteLength) device.queue.writeBuffer(buf, 0, a);
+  return { buf, rows: a.length / width, owned: true };
+}
+/** Area-weighted surface sampling of a triangle mesh on the device (wdgs_mesh_sampler): count gives every triangle its dithered share of `density`
+ *  samples per unit area and returns the total (it waits), emit writes them, one thread per sample.  sampleMesh is the one-call form. */
+class MeshSampler {
+  constructor(device) { this.device = device; this.destroyed = false; this.handle = addon.meshSamplerCreate(device.handle); }
+  count(vertices, numVertices, faces, numFaces, density, seed) {
+    if (vertices.size < 12 * numVertices || faces.size < 12 * numFaces) throw new Error('MeshSampler.count: buffers too small for the mesh');
+    return addon.meshSamplerCount(this.handle, vertices.ptr, numVertices, faces.ptr, numFaces, density, (seed || 0) >>> 0);
+  }
+  /** points f32[total][3] and face u32[total] (optional) for the arguments of the count before it (WDGS_E_STATE otherwise; WDGS_E_CAPACITY when there
+   *  is too little room).  Stream-ordered. */
+  emit(vertices, numVertices, faces, numFaces, density, seed, points, face, capacity) {
+    const cap = capacity === undefined || capacity === null ? Math.min(Math.floor(points.size / 12), face ? Math.floor(face.size / 4) : 0xFFFFFFFF) : capacity;
+    if (cap * 12 > points.size || (face && cap * 4 > face.size)) throw new Error('MeshSampler.emit: the capacity exceeds the buffers');
+    addon.meshSamplerEmit(this.handle, vertices.ptr, numVertices, faces.ptr, numFaces, density, (seed || 0) >>> 0, points.ptr, face ? face.ptr : null, cap);
+  }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.meshSamplerDestroy(this.handle); this.handle = null; }
+}
+/** Points on the surface of `mesh` ({ vertices, faces } as extractMesh returns them, or as HipBuffers), `density` per unit area on average, every triangle
+ *  getting floor(area density + dither) of them: { points: Float32Array[N*3], face: Uint32Array[N], count: N }, the samples of a triangle consecutive,
+ *  triangles in order; a function of its arguments alone, bit for bit.  options.asBuffers: points and face stay on the device as HipBuffers. */
+function sampleMesh(device, mesh, density, seed, options) {
+  const o = options || {};
+  const v = asDevice(device, mesh.vertices, Float32Array, 3, 'sampleMesh: vertices'), f = asDevice(device, mesh.faces, Uint32Array, 3, 'sampleMesh: faces');
+  const sampler = new MeshSampler(device);
+  let points = null, face = null;
+  try {
+    const total = sampler.count(v.buf, v.rows, f.buf, f.rows, density, seed);
+    points = device.createBuffer({ size: 12 * Math.max(total, 1), label: 'mesh samples' });
+    face = device.createBuffer({ size: 4 * Math.max(total, 1), label: 'mesh sample faces' });
+    sampler.emit(v.buf, v.rows, f.buf, f.rows, density, seed, points, face, total);
+    if (o.asBuffers) {
+      device.synchronize();   // (the uploaded mesh is released below)
+      const out = { points, face, count: total };
+      points = face = null;
+      return out;
+    }
+    const bytes = (b, n) => (n ? device.readBuffer(b, n) : new ArrayBuffer(0));
+    return { points: new Float32Array(bytes(points, 12 * total)), face: new Uint32Array(bytes(face, 4 * total)), count: total };
+  } finally {
+    sampler.destroy();
+    if (v.owned) v.buf.destroy();
+    if (f.owned) f.buf.destroy();
+    if (points) points.destroy();
+    if (face) face.destroy();
+  }
+}
+/** A uniform grid over `points` ([M*3] Float32Array, or a HipBuffer) for exact nearest-point queries under a cutoff (wdgs_point_index).  options:
+ *  { cellSize, count }.  cellSize is a speed parameter only -- no result depends on it; without one it is chosen by the first query (its cutoff, or less
+ *  for many points), which then finishes the build.  Non-finite points are left out.  The build waits once; queries are stream-ordered. */
+class PointIndex {
+  constructor(device, points, options) {
+    const o = options || {};
+    this.device = device; this.destroyed = false;
+    const p = asDevice(device, points, Float32Array, 3, 'PointIndex: points');
+    this.points = p.buf; this.owned = p.owned;
+    this.numPoints = o.count === undefined || o.count === null ? p.rows : o.count;
+    if (this.numPoints > p.rows) throw new Error('PointIndex: the count exceeds the buffer');
+    this.handle = addon.pointIndexCreate(device.handle, this.points.ptr, this.numPoints, o.cellSize === undefined || o.cellSize === null ? 0 : o.cellSize);
+  }
+  /** { cellSize, dims, indexed }: the cell edge in use (0 before the first query of an index made without one), the grid, the finite points. */
+  info() { const a = addon.pointIndexInfo(this.handle); return { cellSize: a[0], dims: [a[1], a[2], a[3]], indexed: a[4] }; }
+  /** Room for queries of `count` points: what a recorded nearestInto needs beforehand (an eager query makes its own). */
+  reserveQueries(count) { addon.pointIndexReserveQueries(this.handle, count); }
+  /** Stream-ordered nearest: for the first `count` points of `queries` the squared distance (f32) to the nearest indexed point within maxDistance into
+   *  d2 and that point's index into index -- the lowest index among equally near ones; +inf and 0xFFFFFFFF when there is none or the query is not finite.
+   *  pairs (optional, 8 bytes): the number of pairs examined is added to it.  No host wait; records. */
+  nearestInto(encoder, queries, count, maxDistance, d2, index, pairs) {
+    if (queries.size < 12 * count || d2.size < 4 * count || index.size < 4 * count || (pairs && pairs.size < 8)) throw new Error(`PointIndex.nearest: buffers too small for ${count} queries`);
+    addon.pointIndexNearest(this.handle, queries.ptr, count, maxDistance, d2.ptr, index.ptr, pairs ? pairs.ptr : null);
+  }
+  /** { d2: Float32Array[K], index: Uint32Array[K] } for `queries` ([K*3] Float32Array or a HipBuffer).  Synchronises. */
+  nearest(queries, maxDistance) {
+    const q = asDevice(this.device, queries, Float32Array, 3, 'PointIndex.nearest: queries'), k = q.rows;
+    const d2 = this.device.createBuffer({ size: 4 * Math.max(k, 1) }), index = this.device.createBuffer({ size: 4 * Math.max(k, 1) });
+    try {
+      this.nearestInto(null, q.buf, k, maxDistance, d2, index);
+      const bytes = (b, n) => (n ? this.device.readBuffer(b, n) : new ArrayBuffer(0));
+      return { d2: new Float32Array(bytes(d2, 4 * k)), index: new Uint32Array(bytes(index, 4 * k)) };
+    } finally { d2.destroy(); index.destroy(); if (q.owned) q.buf.destroy(); }
+  }
+  destroy() {
+    if (this.destroyed) return;
+    this.destroyed = true;
+    addon.pointIndexDestroy(this.handle);
+    this.handle = null;
+    if (this.owned) this.points.destroy();
+    this.points = null;
+  }
+}
+/** Stream-ordered pointDistanceStats: the three u64 sums into the first 24 bytes of `out` (no host wait). */
+function encodePointDistanceStats(device, d2, count, maxDistance, threshold, out) {
+  if (d2.size < 4 * count || out.size < 24) throw new Error(`pointDistanceStats: buffers too small for ${count} distances`);
+  addon.pointDistanceStats(device.handle, d2.ptr, count, maxDistance, threshold, out.ptr);
+}
+/** Exact integer statistics of PointIndex.nearest's squared distances (a Float32Array, or a HipBuffer with `count`): { n, n_found (finite), n_within
+ *  (d2 <= threshold^2), sum_q (the sum of u32(sqrt(d2) / maxDistance 2^24) over the found; a Number, exact below 2^53), mean = sum_q maxDistance / 2^24 /
+ *  n_found (NaN when nothing was found) }.  0 < threshold <= maxDistance.  Synchronises. */
+function pointDistanceStats(device, d2, maxDistance, threshold, count) {
+  const d = d2 instanceof HipBuffer ? { buf: d2, rows: count === undefined || count === null ? Math.floor(d2.size / 4) : count, owned: false }
+    : asDevice(device, d2, Float32Array, 1, 'pointDistanceStats: d2');
+  const out = device.createBuffer({ size: 24 });
+  try {
+    encodePointDistanceStats(device, d.buf, d.rows, maxDistance, threshold, out);
+    const v = new BigUint64Array(device.readBuffer(out, 24));
+    const found = Number(v[0]), sum = Number(v[2]);
+    return { n: d.rows, n_found: found, n_within: Number(v[1]), sum_q: sum, mean: found ? sum * Math.fround(maxDistance) / 2 ** 24 / found : NaN };
+  } finally { out.destroy(); if (d.owned) d.buf.destroy(); }
+}
+/** How far a point set is from a reference set, in both directions: accuracy the mean distance from `points` to their nearest `reference` point over
+ *  the points that have one within maxDistance (the others are outliers: counted, not averaged), completeness the same from the reference to the points,
+ *  chamfer their mean, precision / recall the share of points / reference points within `threshold`, fscore = 2PR / (P + R) (0 when both are 0); a
+ *  direction with nothing found gives NaN.  Both sets: [N*3] Float32Array or HipBuffer (options: { numPoints, numReference } for buffers used in part). */
+function geometryMetrics(device, points, reference, maxDistance, threshold, options) {
+  const o = options || {};
+  const p = asDevice(device, points, Float32Array, 3, 'geometryMetrics: points'), r = asDevice(device, reference, Float32Array, 3, 'geometryMetrics: reference');
+  const np = o.numPoints === undefined || o.numPoints === null ? p.rows : o.numPoints, nr = o.numReference === undefined || o.numReference === null ? r.rows : o.numReference;
+  const room = 4 * Math.max(np, nr, 1);
+  const d2 = device.createBuffer({ size: room }), idx = device.createBuffer({ size: room }), out = device.createBuffer({ size: 48 });
+  const indices = [];
+  let s;
+  try {
+    [[p.buf, np, r.buf, nr], [r.buf, nr, p.buf, np]].forEach(([src, nSrc, dst, nDst], k) => {
+      const index = new PointIndex(device, dst, { count: nDst });
+      indices.push(index);
+      index.nearestInto(null, src, nSrc, maxDistance, d2, idx);
+      addon.pointDistanceStats(device.handle, d2.ptr, nSrc, maxDistance, threshold, out.ptr + BigInt(24 * k));
+    });
+    s = Array.from(new BigUint64Array(device.readBuffer(out, 48)), Number);
+  } finally {
+    for (const index of indices) index.destroy();
+    d2.destroy(); idx.destroy(); out.destroy();
+    if (p.owned) p.buf.destroy();
+    if (r.owned) r.buf.destroy();
+  }
+  const scale = Math.fround(maxDistance) / 2 ** 24;
+  const accuracy = s[0] ? s[2] * scale / s[0] : NaN, completeness = s[3] ? s[5] * scale / s[3] : NaN;
+  const precision = np ? s[1] / np : NaN, recall = nr ? s[4] / nr : NaN;
+  return { accuracy, completeness, chamfer: (accuracy + completeness) / 2, precision, recall,
+    fscore: precision === 0 && recall === 0 ? 0 : 2 * precision * recall / (precision + recall),
+    n_points: np, n_reference: nr, outliers_points: np - s[0], outliers_reference: nr - s[3] };
+}
+
 /** The normals of an f32 depth image by central differences of its back-projection (loaders.backprojectDepth's convention): rgba32f { n, 1 } into
  *  `target`, all zero where a neighbour is missing (wdgs_depth_to_normals).  `camera`: the 68-float block, or [proj[0][0], proj[1][1]].
  *  Stream-ordered; no reference counterpart. */
@@ -687,6 +840,7 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, NO_INDEX, MeshSampler, sampleMesh, PointIndex, encodePointDistanceStats, pointDistanceStats,
+  geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

@@ -660,6 +660,53 @@ int wdgs_tsdf_volume_count_triangles(wdgs_tsdf_volume* vol, float min_weight, ui
  * are asked of a volume without colour.  No reference counterpart. */
 int wdgs_tsdf_volume_emit_triangles(wdgs_tsdf_volume* vol, void* positions_f32_dev, void* keys_u64_dev, void* colours_rgba8_dev, uint32_t capacity_triangles);
 
+/* ---------------------------------------------------------------- Mesh accuracy metrics: surface sampling, nearest points, distance sums
+ *
+ * Three device pieces, each defined so that a float32 restatement reproduces its output bit for bit (every f32 operation rounded once in the order written,
+ * sums as integers).  No reference counterpart. */
+
+/* Area-weighted sampling of a triangle mesh: vertices f32[V][3], faces u32[F][3], `density` samples per unit area (positive, finite), a u32 seed.
+ *   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16                      (u32, wrapping)
+ *   h(seed, t, k, j) = mix(mix(mix(mix(seed + 0x9E3779B9) ^ t) + k) ^ (j * 0x85EBCA6B + 1));   unit(h) = ((float)(h >> 9) + 0.5f) * 2^-23
+ * Triangle t with corners A, B, C: e1 = B - A, e2 = C - A, n = e1 x e2, area = 0.5f sqrt((n.x n.x + n.y n.y) + n.z n.z), and it gets
+ * n_t = u32(floor(area density + unit(h(seed, t, 0xFFFFFFFF, 0)))) samples, at most 2^31 - 1; 0 when it names a vertex >= V or the sum is not finite.
+ * Sample k of triangle t is output element offsets[t] + k (offsets: the exclusive scan of n_t): u = unit(h(seed, t, k, 1)), v = unit(h(seed, t, k, 2)),
+ * both replaced by 1 - u, 1 - v when u + v > 1, and per axis p = (A + u e1) + v e2. */
+typedef struct wdgs_mesh_sampler wdgs_mesh_sampler;
+int wdgs_mesh_sampler_create(wdgs_device* dev, wdgs_mesh_sampler** out);
+int wdgs_mesh_sampler_destroy(wdgs_mesh_sampler* sampler);
+/* Counts and scans; waits for the u64 total and returns it, so it cannot be recorded (WDGS_E_STATE).  WDGS_E_CAPACITY for a total of 2^31 or more: no emit
+ * is possible after it.  The mesh is read again by the emit and must stay as it is until then. */
+int wdgs_mesh_sampler_count(wdgs_mesh_sampler* sampler, const void* vertices_f32_dev, uint32_t num_vertices, const void* faces_u32_dev, uint32_t num_faces, float density,
+                            uint32_t seed, uint64_t* total);
+/* Writes points f32[total][3] and face u32[total] (nullable: the triangle of each sample), one thread per sample.  WDGS_E_STATE unless the last count
+ * succeeded with these very arguments; WDGS_E_CAPACITY when capacity_samples < total; nothing is written in either case.  Stream-ordered, recordable. */
+int wdgs_mesh_sampler_emit(wdgs_mesh_sampler* sampler, const void* vertices_f32_dev, uint32_t num_vertices, const void* faces_u32_dev, uint32_t num_faces, float density,
+                           uint32_t seed, void* points_f32_dev, void* face_u32_dev, uint32_t capacity_samples);
+
+/* A uniform grid over points f32[M][3] (M <= 2^31 - 1, else WDGS_E_INVALID; M = 0 is allowed) holding a cell-sorted copy of the finite points as 16-byte records
+ * { x, y, z, original index }; non-finite points are left out.  The build reads the points' bounds back with one wait and cannot be recorded (WDGS_E_STATE); the
+ * points are not read after it.  cell_size: the cell edge, a speed parameter only -- no result depends on it; the library enlarges it until the grid has at most
+ * 2^26 cells; 0 = chosen by the first query, which then completes the build (and cannot be recorded either; the points must be unchanged until then): its
+ * cutoff, or w / cbrt(n) if that is smaller (w the widest extent of the n finite points: a cube of that extent then has n cells). */
+typedef struct wdgs_point_index wdgs_point_index;
+int wdgs_point_index_create(wdgs_device* dev, const void* points_f32_dev, uint64_t num_points, float cell_size, wdgs_point_index** out);
+int wdgs_point_index_destroy(wdgs_point_index* index);
+/* Room for queries of up to num_queries points.  A query grows the room by itself except while recording, where it fails with WDGS_E_STATE instead. */
+int wdgs_point_index_reserve_queries(wdgs_point_index* index, uint32_t num_queries);
+/* The cell edge in use (0 before the grid exists), the grid's dimensions and the number of points indexed; each pointer nullable. */
+int wdgs_point_index_info(const wdgs_point_index* index, float* cell_size, uint32_t* dims3, uint32_t* indexed_points);
+/* For each query p of queries f32[K][3]: over the indexed points q with d2(p, q) = ((dx dx + dy dy) + dz dz) <= r2, dx = p.x - q.x ..., r2 = max_distance
+ * max_distance (all f32), the smallest d2 and, among equal d2, the lowest original index, into d2 f32[K] and index u32[K]; +inf and 0xFFFFFFFF when there is none
+ * or the query is not finite.  pairs_u64_dev (nullable): the number of (query, point) pairs examined is added to it.  max_distance must be positive and finite
+ * (WDGS_E_INVALID).  Stream-ordered, recordable once the grid exists and the room is reserved. */
+int wdgs_point_index_nearest(wdgs_point_index* index, const void* queries_f32_dev, uint32_t num_queries, float max_distance, void* d2_f32_dev, void* index_u32_dev,
+                             void* pairs_u64_dev);
+/* out u64[3] = { n_found: the finite d2;  n_within: those with d2 <= threshold threshold (f32);  sum_q: the sum over the found of
+ * u32((sqrt(d2) / max_distance) * 2^24) }, exact integer sums; the mean distance is sum_q max_distance / 2^24 / n_found.  0 < threshold <= max_distance, both
+ * finite (WDGS_E_INVALID).  Stream-ordered, no host wait, recordable. */
+int wdgs_point_distance_stats(wdgs_device* dev, const void* d2_f32_dev, uint32_t count, float max_distance, float threshold, void* out_u64x3_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,16 @@ SIGNATURES = {
     "wdgs_tsdf_volume_integrate": (_I, [_P, _P, _P, _P, _U, _U, _P, _F]),
     "wdgs_tsdf_volume_count_triangles": (_I, [_P, _F, C.POINTER(_U)]),
     "wdgs_tsdf_volume_emit_triangles": (_I, [_P, _P, _P, _P, _U]),
+    "wdgs_mesh_sampler_create": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_mesh_sampler_destroy": (_I, [_P]),
+    "wdgs_mesh_sampler_count": (_I, [_P, _P, _U, _P, _U, _F, _U, C.POINTER(C.c_uint64)]),
+    "wdgs_mesh_sampler_emit": (_I, [_P, _P, _U, _P, _U, _F, _U, _P, _P, _U]),
+    "wdgs_point_index_create": (_I, [_P, _P, C.c_uint64, _F, C.POINTER(_P)]),
+    "wdgs_point_index_destroy": (_I, [_P]),
+    "wdgs_point_index_reserve_queries": (_I, [_P, _U]),
+    "wdgs_point_index_info": (_I, [_P, C.POINTER(_F), C.POINTER(_U), C.POINTER(_U)]),
+    "wdgs_point_index_nearest": (_I, [_P, _P, _U, _F, _P, _P, _P]),
+    "wdgs_point_distance_stats": (_I, [_P, _P, _U, _F, _F, _P]),
     "wdgs_optimizer_step_f32_range": (_I, [_P, _P, _P, _P, _P, _U, _U, _P]),
     "wdgs_apply_repacked_rows": (_I, [_P, _U, _P, _U, _U, _P, _P, _P]),
     "wdgs_optimizer_set_guard": (_I, [_P, _P]),

@@ -95,7 +95,16 @@ int launch_tsdf_count(wdgs_device* dev, const float origin[3], float voxel_size,
 int launch_tsdf_emit(wdgs_device* dev, const float origin[3], float voxel_size, const u32 dims[3], const float* tsdf, const float* weight, const float* rgb, float min_weight,
                      const u32* counts, const u32* offsets, float* positions, unsigned long long* keys, u32* colours);
 
-// ---- loss.hip, dssim.hip.  pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
+// ---- geometry.hip.  vertices f32[V][3], faces u32[F][3]; counts u32[F], written; total: one u64, cleared and added to
+int launch_sample_count(wdgs_device* dev, const float* vertices, u32 V, const u32* faces, u32 F, float density, u32 seed, u32* counts, unsigned long long* total);
+// offsets: the exclusive scan of counts; points f32[total][3], face_out u32[total] (nullable)
+int launch_sample_emit(wdgs_device* dev, const float* vertices, u32 V, const u32* faces, u32 F, u32 seed, const u32* offsets, u32 total, float* points, u32* face_out);
+// bounds7: min x, y, z and max x, y, z of the finite points as order-preserving bit patterns, and their number
+int launch_point_bounds(wdgs_device* dev, const float* points, u32 M, u32* bounds7);
+// out3: u64 { n_found, n_within, sum_q }, cleared and added to
+int launch_point_distance_stats(wdgs_device* dev, const float* d2, u32 K, float max_distance, float threshold, unsigned long long* out3);
+
+// ---- loss.hip, dssim.hip. pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
 int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
                      const u32* acc_dirty);
 int launch_dssim_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,

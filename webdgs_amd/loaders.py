@@ -381,6 +381,61 @@ def loadMeshPLY(path: str) -> dict:
                 colours=np.ascontiguousarray(vert["c"]) if coloured else None)
 
 
+# ----------------------------------------------------------------------------- point sets (no reference counterpart)
+_PLY_SCALAR = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2", "int": "<i4", "int32": "<i4",
+               "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def pointsPLYBytes(points) -> bytes:
+    """Points ``f32[N,3]`` as a binary little-endian PLY with the one element ``vertex`` of ``x y z`` float."""
+    p = np.ascontiguousarray(points, "<f4")
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError(f"pointsPLYBytes: expected [N, 3] points, got {p.shape}")
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {p.shape[0]}", "property float x", "property float y", "property float z", "end_header"]
+    return ("\n".join(header) + "\n").encode("ascii") + p.tobytes()
+
+
+def savePointsPLY(path: str, points) -> None:
+    """Writes ``pointsPLYBytes(points)`` to ``path``; ``loadPointsPLY`` reads it back exactly."""
+    with open(path, "wb") as fh:
+        fh.write(pointsPLYBytes(points))
+
+
+def loadPointsPLY(path: str) -> np.ndarray:
+    """The vertex positions ``f32[N,3]`` of a binary little-endian PLY: a reference scan, ``savePointsPLY``'s output, or a mesh (its faces are not read).  The
+    vertex element comes first and holds float ``x y z`` among scalar properties; its other properties are skipped."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError("loadPointsPLY: not a PLY file")
+    lines = data[:end].decode("ascii").split("\n")
+    body = data[end + len(b"end_header\n"):]
+    if "format binary_little_endian 1.0" not in lines:
+        raise ValueError("loadPointsPLY: only binary little-endian PLY is read")
+    first, count, fields = None, 0, []
+    for ln in lines:
+        w = ln.split()
+        if w[:1] == ["element"]:
+            if first is not None:
+                break
+            first, count = w[1], int(w[2])
+        elif w[:1] == ["property"] and first is not None:
+            if len(w) != 3 or w[1] not in _PLY_SCALAR:
+                raise ValueError(f"loadPointsPLY: vertex property {' '.join(w[1:])!r} is not a scalar")
+            fields.append((w[2], _PLY_SCALAR[w[1]]))
+    if first != "vertex":
+        raise ValueError("loadPointsPLY: the first element must be 'vertex'")
+    dt = np.dtype(fields)
+    for axis in ("x", "y", "z"):
+        if axis not in dt.names or dt[axis] != np.dtype("<f4"):
+            raise ValueError("loadPointsPLY: the vertex element needs float x, y and z")
+    if len(body) < count * dt.itemsize:
+        raise ValueError("loadPointsPLY: the body is shorter than the header says")
+    vert = np.frombuffer(body, dt, count=count)
+    return np.ascontiguousarray(np.stack([vert["x"], vert["y"], vert["z"]], axis=1), np.float32).reshape(count, 3)
+
+
 # ----------------------------------------------------------------------------- held-out split (no reference counterpart)
 def holdoutSplit(cameras: list, images: list, every: int = 8) -> tuple:
     """Train / test split of a dataset by the Mip-NeRF 360 / 3DGS ``--eval`` convention: view ``i`` is a test view when ``i % every == 0``.

@@ -956,6 +956,207 @@ def weldTriangles(tri: dict) -> dict:
     return dict(vertices=np.ascontiguousarray(vertices), faces=inverse.reshape(-1, 3).astype(np.uint32), colours=colours, keys=uniq)
 
 
+# ----------------------------------------------------------------------------- mesh accuracy metrics (no reference counterpart)
+NO_INDEX = 0xFFFFFFFF
+
+
+def _as_device(device: HipDevice, array, dtype, width: int, what: str) -> tuple:
+    """``(buffer, rows, owned)`` of a ``[rows, width]`` array given as numpy (uploaded; ``owned``) or as a ``HipBuffer`` (whole rows of it)."""
+    if isinstance(array, HipBuffer):
+        return array, array.size // (np.dtype(dtype).itemsize * width), False
+    a = np.ascontiguousarray(array, dtype)
+    if a.ndim != 2 or a.shape[1] != width:
+        raise ValueError(f"{what}: expected an array of shape [N, {width}], got {a.shape}")
+    return device.bufferFrom(a, what), a.shape[0], True
+
+
+class MeshSampler:
+    """Area-weighted surface sampling of a triangle mesh on the device (``wdgs_mesh_sampler``): ``count`` gives every triangle its dithered share of
+    ``density`` samples per unit area and returns the total, ``emit`` writes them, one thread per sample.  ``sampleMesh`` is the one-call form."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        h = C.c_void_p()
+        check(device.lib.wdgs_mesh_sampler_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def count(self, vertices: HipBuffer, numVertices: int, faces: HipBuffer, numFaces: int, density: float, seed: int = 0) -> int:
+        """The number of samples (count, scan; waits).  ``CapacityError`` for 2^31 or more."""
+        if vertices.size < 12 * int(numVertices) or faces.size < 12 * int(numFaces):
+            raise ValueError("MeshSampler.count: buffers too small for the mesh")
+        n = C.c_uint64(0)
+        check(self.device.lib.wdgs_mesh_sampler_count(self.handle, vertices.ptr, int(numVertices), faces.ptr, int(numFaces), float(density), int(seed) & 0xFFFFFFFF, C.byref(n)))
+        return int(n.value)
+
+    def emit(self, vertices: HipBuffer, numVertices: int, faces: HipBuffer, numFaces: int, density: float, seed: int, points: HipBuffer,
+             face: Optional[HipBuffer] = None, capacity: Optional[int] = None) -> None:
+        """Writes ``points`` f32[total][3] and ``face`` u32[total] (optional) for the arguments of the count before it (``StateError`` otherwise;
+        ``CapacityError`` when there is too little room).  Stream-ordered."""
+        cap = min(points.size // 12, face.size // 4 if face is not None else 2 ** 32 - 1) if capacity is None else int(capacity)
+        if cap * 12 > points.size or (face is not None and cap * 4 > face.size):
+            raise ValueError("MeshSampler.emit: the capacity exceeds the buffers")
+        check(self.device.lib.wdgs_mesh_sampler_emit(self.handle, vertices.ptr, int(numVertices), faces.ptr, int(numFaces), float(density), int(seed) & 0xFFFFFFFF,
+                                                     points.ptr, face.ptr if face is not None else None, cap))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_mesh_sampler_destroy(self.handle)
+        self.handle = None
+
+
+def sampleMesh(device: HipDevice, mesh: dict, density: float, seed: int = 0, asBuffers: bool = False) -> dict:
+    """Points on the surface of ``mesh`` -- the dict ``extractMesh`` and ``loaders.loadMeshPLY`` return, or ``dict(vertices=HipBuffer, faces=HipBuffer)`` on the
+    device -- ``density`` per unit area on average, every triangle getting ``floor(area density + dither)`` of them: ``dict(points f32[N,3], face u32[N])``,
+    the samples of a triangle consecutive, triangles in order.  A function of its arguments alone, bit for bit (include/webdgs.h states it).
+    ``asBuffers``: ``points`` and ``face`` stay on the device as ``HipBuffer`` and ``count`` is added."""
+    vbuf, nv, own_v = _as_device(device, mesh["vertices"], np.float32, 3, "sampleMesh: vertices")
+    fbuf, nf, own_f = _as_device(device, mesh["faces"], np.uint32, 3, "sampleMesh: faces")
+    sampler = MeshSampler(device)
+    points = face = None
+    try:
+        total = sampler.count(vbuf, nv, fbuf, nf, density, seed)
+        points = device.createBuffer(12 * max(total, 1), "mesh samples")
+        face = device.createBuffer(4 * max(total, 1), "mesh sample faces")
+        sampler.emit(vbuf, nv, fbuf, nf, density, seed, points, face, total)
+        if asBuffers:
+            device.synchronize()   # (the uploaded mesh is released below)
+            out = dict(points=points, face=face, count=total)
+            points = face = None
+            return out
+        return dict(points=points.read(np.float32, count=3 * total).reshape(total, 3), face=face.read(np.uint32, count=total))
+    finally:
+        sampler.destroy()
+        for b, own in ((vbuf, own_v), (fbuf, own_f), (points, True), (face, True)):
+            if own and b is not None:
+                b.destroy()
+
+
+class PointIndex:
+    """A uniform grid over ``points`` ([M,3] float32 as numpy, or a ``HipBuffer``) for exact nearest-point queries under a cutoff (``wdgs_point_index``).
+    ``cellSize`` is a speed parameter only -- no result depends on it; ``None``: chosen by the first query (its cutoff, or less for many points), which then
+    finishes the build.  Non-finite
+    points are left out.  The build waits once (it reads the points' bounds back); queries are stream-ordered."""
+
+    def __init__(self, device: HipDevice, points, cellSize: Optional[float] = None, count: Optional[int] = None):
+        self.device = device
+        self.destroyed = False
+        self._points, n, self._owned = _as_device(device, points, np.float32, 3, "PointIndex: points")
+        self.numPoints = n if count is None else int(count)
+        if self.numPoints > n:
+            raise ValueError("PointIndex: the count exceeds the buffer")
+        h = C.c_void_p()
+        check(device.lib.wdgs_point_index_create(device.handle, self._points.ptr, self.numPoints, 0.0 if cellSize is None else float(cellSize), C.byref(h)))
+        self.handle = h
+
+    def info(self) -> dict:
+        """``dict(cellSize, dims, indexed)``: the cell edge in use (0 before the first query of an index made without one), the grid, the finite points."""
+        c, d, n = C.c_float(0), (C.c_uint32 * 3)(), C.c_uint32(0)
+        check(self.device.lib.wdgs_point_index_info(self.handle, C.byref(c), d, C.byref(n)))
+        return dict(cellSize=float(c.value), dims=tuple(int(x) for x in d), indexed=int(n.value))
+
+    def reserveQueries(self, count: int) -> None:
+        """Room for queries of ``count`` points: what a recorded ``nearestInto`` needs beforehand (an eager query makes its own)."""
+        check(self.device.lib.wdgs_point_index_reserve_queries(self.handle, int(count)))
+
+    def nearestInto(self, encoder: Optional[HipEncoder], queries: HipBuffer, count: int, maxDistance: float, d2: HipBuffer, index: HipBuffer,
+                    pairs: Optional[HipBuffer] = None) -> None:
+        """Stream-ordered ``nearest``: for the first ``count`` points of ``queries`` the squared distance (f32, in f32 arithmetic) to the nearest indexed point
+        within ``maxDistance`` into ``d2`` and that point's index into ``index`` -- the lowest index among equally near ones; ``+inf`` and ``0xFFFFFFFF`` when there
+        is none or the query is not finite.  ``pairs`` (optional, 8 bytes): the number of pairs examined is added to it.  No host wait; records."""
+        k = int(count)
+        if queries.size < 12 * k or d2.size < 4 * k or index.size < 4 * k or (pairs is not None and pairs.size < 8):
+            raise ValueError(f"PointIndex.nearest: buffers too small for {k} queries")
+        check(self.device.lib.wdgs_point_index_nearest(self.handle, queries.ptr, k, float(maxDistance), d2.ptr, index.ptr, pairs.ptr if pairs is not None else None))
+
+    def nearest(self, queries, maxDistance: float) -> dict:
+        """``dict(d2 f32[K], index u32[K])`` for ``queries`` ([K,3] numpy or a ``HipBuffer``).  Synchronises."""
+        qbuf, k, owned = _as_device(self.device, queries, np.float32, 3, "PointIndex.nearest: queries")
+        d2 = self.device.createBuffer(4 * max(k, 1), "nearest d2")
+        index = self.device.createBuffer(4 * max(k, 1), "nearest index")
+        try:
+            self.nearestInto(None, qbuf, k, maxDistance, d2, index)
+            return dict(d2=d2.read(np.float32, count=k), index=index.read(np.uint32, count=k))
+        finally:
+            d2.destroy()
+            index.destroy()
+            if owned:
+                qbuf.destroy()
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_point_index_destroy(self.handle)
+        self.handle = None
+        if self._owned:
+            self._points.destroy()
+        self._points = None
+
+
+def encodePointDistanceStats(device: HipDevice, d2: HipBuffer, count: int, maxDistance: float, threshold: float, out: HipBuffer) -> None:
+    """Stream-ordered ``pointDistanceStats``: the three u64 sums into the first 24 bytes of ``out``.  No host wait."""
+    if d2.size < 4 * int(count) or out.size < 24:
+        raise ValueError(f"pointDistanceStats: buffers too small for {count} distances")
+    check(device.lib.wdgs_point_distance_stats(device.handle, d2.ptr, int(count), float(maxDistance), float(threshold), out.ptr))
+
+
+def pointDistanceStats(device: HipDevice, d2, maxDistance: float, threshold: float, count: Optional[int] = None) -> dict:
+    """Exact integer statistics of ``PointIndex.nearest``'s squared distances (numpy, or a ``HipBuffer`` with ``count``): ``n`` of them, ``n_found`` finite,
+    ``n_within`` with ``d2 <= threshold^2``, ``sum_q`` the sum of ``u32(sqrt(d2) / maxDistance 2^24)`` over the found, and ``mean = sum_q maxDistance / 2^24 /
+    n_found`` (nan when nothing was found).  ``0 < threshold <= maxDistance``.  Synchronises."""
+    if isinstance(d2, HipBuffer):
+        buf, n, owned = d2, (d2.size // 4 if count is None else int(count)), False
+    else:
+        a = np.ascontiguousarray(d2, np.float32).reshape(-1)
+        buf, n, owned = device.bufferFrom(a, "d2"), a.size, True
+    out = device.createBuffer(24, "distance stats")
+    try:
+        encodePointDistanceStats(device, buf, n, maxDistance, threshold, out)
+        found, within, sum_q = (int(x) for x in out.read(np.uint64, count=3))
+    finally:
+        out.destroy()
+        if owned:
+            buf.destroy()
+    mean = (sum_q * float(np.float32(maxDistance)) / 2.0 ** 24 / found) if found else float("nan")
+    return dict(n=n, n_found=found, n_within=within, sum_q=sum_q, mean=mean)
+
+
+def geometryMetrics(device: HipDevice, points, reference, maxDistance: float, threshold: float) -> dict:
+    """How far a point set is from a reference set, in both directions (the DTU and Tanks-and-Temples numbers): ``accuracy`` the mean distance from ``points``
+    to their nearest ``reference`` point, over the points that have one within ``maxDistance`` (the others are outliers: counted, not averaged),
+    ``completeness`` the same from the reference to the points, ``chamfer`` their mean, ``precision`` / ``recall`` the share of points / reference points within
+    ``threshold``, ``fscore = 2PR / (P + R)`` (0 when both are 0); a direction with nothing found gives nan.  Both sets: [N,3] float32 numpy or ``HipBuffer``."""
+    pbuf, np_, own_p = _as_device(device, points, np.float32, 3, "geometryMetrics: points")
+    rbuf, nr, own_r = _as_device(device, reference, np.float32, 3, "geometryMetrics: reference")
+    d2 = device.createBuffer(4 * max(np_, nr, 1), "metrics d2")
+    idx = device.createBuffer(4 * max(np_, nr, 1), "metrics index")
+    out = device.createBuffer(48, "metrics sums")
+    indices = []
+    try:
+        for k, (src, n_src, dst, n_dst) in enumerate(((pbuf, np_, rbuf, nr), (rbuf, nr, pbuf, np_))):
+            index = PointIndex(device, dst, count=n_dst)
+            indices.append(index)
+            index.nearestInto(None, src, n_src, maxDistance, d2, idx)
+            check(device.lib.wdgs_point_distance_stats(device.handle, d2.ptr, n_src, float(maxDistance), float(threshold), out.ptr + 24 * k))
+        s = [int(x) for x in out.read(np.uint64, count=6)]
+    finally:
+        for index in indices:
+            index.destroy()
+        for b, own in ((d2, True), (idx, True), (out, True), (pbuf, own_p), (rbuf, own_r)):
+            if own:
+                b.destroy()
+    scale = float(np.float32(maxDistance)) / 2.0 ** 24
+    acc = s[2] * scale / s[0] if s[0] else float("nan")
+    comp = s[5] * scale / s[3] if s[3] else float("nan")
+    p = s[1] / np_ if np_ else float("nan")
+    r = s[4] / nr if nr else float("nan")
+    return dict(accuracy=acc, completeness=comp, chamfer=(acc + comp) / 2, precision=p, recall=r, fscore=0.0 if (p == 0 and r == 0) else 2 * p * r / (p + r),
+                n_points=np_, n_reference=nr, outliers_points=np_ - s[0], outliers_reference=nr - s[3])
+
+
 # ----------------------------------------------------------------------------- per-Gaussian contribution (DESIGN.md section 11; no reference counterpart)
 CONTRIBUTION_RECORD_BYTES = 16
 CONTRIBUTION_DTYPE = np.dtype([("sum_q", "<u8"), ("max_bits", "<u4"), ("pixels", "<u4")])

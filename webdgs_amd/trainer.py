@@ -1062,6 +1062,33 @@ class Trainer:
         finally:
             volume.destroy()
 
+    # ------------------------------------------------------------------ mesh accuracy against a reference point set (no reference counterpart)
+    def evaluateGeometry(self, reference, lo, hi, voxelSize: float, maxDistance: float, threshold: float, density: Optional[float] = None, seed: int = 0,
+                         **extractMeshOptions) -> dict:
+        """Scores the current model's geometry against ``reference`` -- an ``[M,3]`` array of surface points, or the path of a PLY that holds them:
+        ``extractMesh(lo, hi, voxelSize, **extractMeshOptions)``, ``ops.sampleMesh`` at ``density`` samples per unit area (``None``: ``1 / (voxelSize / 2)^2``,
+        a spacing of half a voxel) and ``ops.geometryMetrics(samples, reference, maxDistance, threshold)``.  Returns its dict -- accuracy, completeness,
+        chamfer, precision, recall, fscore and the counts -- with ``vertices``, ``faces``, ``samples`` (the mesh's and the sample count) and ``ms``.
+
+        ``extractMesh``'s isolation (``fuseDepth``'s): the pipeline is drained, no RNG draw, no training pass, no recording dropped, the iteration counter
+        untouched.  No alignment is attempted: the reference is taken to be in the scene's frame."""
+        t0 = time.perf_counter()
+        ref = loaders.loadPointsPLY(reference) if isinstance(reference, (str, bytes)) or hasattr(reference, "__fspath__") else np.ascontiguousarray(reference, np.float32)
+        if ref.ndim != 2 or ref.shape[1] != 3:
+            raise ValueError(f"evaluateGeometry: the reference must be [M, 3] points, got {ref.shape}")
+        if density is None:
+            density = 1.0 / (0.5 * float(voxelSize)) ** 2
+        mesh = self.extractMesh(lo, hi, voxelSize, **extractMeshOptions)
+        samples = ops.sampleMesh(self.device, mesh, density, seed, asBuffers=True)
+        try:
+            n = samples["count"]
+            out = ops.geometryMetrics(self.device, self.device.view(samples["points"].ptr, 12 * n), ref, maxDistance, threshold)
+        finally:
+            samples["points"].destroy()
+            samples["face"].destroy()
+        out.update(vertices=int(mesh["vertices"].shape[0]), faces=int(mesh["faces"].shape[0]), samples=int(n), ms=(time.perf_counter() - t0) * 1e3)
+        return out
+
     # ------------------------------------------------------------------ render contribution and contribution-based pruning (no reference counterpart)
     def _contribution_buffer(self, viewIds: Optional[list], split: str, what: str) -> tuple:
         """(buffer, view ids): the views' contribution records accumulated into one new device buffer."""
