@@ -459,6 +459,31 @@ static napi_value pointIndexNearest(napi_env env, napi_callback_info info) {  //
                                               get_ptr(env, argv[4]), get_ptr(env, argv[5]), get_ptr(env, argv[6])));
     return js_undefined(env);
 }
+static napi_value pointIndexBounds(napi_env env, napi_callback_info info) {  // (index) -> [lo x, y, z, hi x, y, z]
+    ARGS(1);
+    float b[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    WDGS_OK_OR_THROW(wdgs_point_index_bounds((const wdgs_point_index*)get_ptr(env, argv[0]), b, b + 3));
+    napi_value a; napi_create_array_with_length(env, 6, &a);
+    for (uint32_t i = 0; i < 6; i++) { napi_value c; napi_create_double(env, (double)b[i], &c); napi_set_element(env, a, i, c); }
+    return a;
+}
+static napi_value pointIndexKNearest(napi_env env, napi_callback_info info) {  // (index, queriesPtr, numQueries, k, maxDistance, flags, d2Ptr, indexPtr, pairsPtr | null)
+    ARGS(9);
+    WDGS_OK_OR_THROW(wdgs_point_index_k_nearest((wdgs_point_index*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]),
+                                                (float)get_f64(env, argv[4]), get_u32(env, argv[5]), get_ptr(env, argv[6]), get_ptr(env, argv[7]), get_ptr(env, argv[8])));
+    return js_undefined(env);
+}
+static napi_value pointCloudPositions(napi_env env, napi_callback_info info) {  // (device, gaussiansPtr, numPoints, positionsPtr)
+    ARGS(4);
+    WDGS_OK_OR_THROW(wdgs_point_cloud_positions((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_ptr(env, argv[3])));
+    return js_undefined(env);
+}
+static napi_value pointCloudNeighbourScales(napi_env env, napi_callback_info info) {  // (device, gaussiansPtr, numPoints, d2Ptr, k, minD2, meanD2Ptr | null)
+    ARGS(7);
+    WDGS_OK_OR_THROW(wdgs_point_cloud_neighbour_scales((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_ptr(env, argv[3]),
+                                                       get_u32(env, argv[4]), (float)get_f64(env, argv[5]), get_ptr(env, argv[6])));
+    return js_undefined(env);
+}
 static napi_value pointDistanceStats(napi_env env, napi_callback_info info) {  // (device, d2Ptr, count, maxDistance, threshold, outPtr): u64 {n_found, n_within, sum_q}
     ARGS(6);
     WDGS_OK_OR_THROW(wdgs_point_distance_stats((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), (float)get_f64(env, argv[3]),
@@ -1077,6 +1102,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(meshSamplerCreate); EXPORT_FN(meshSamplerDestroy); EXPORT_FN(meshSamplerCount); EXPORT_FN(meshSamplerEmit);
     EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
     EXPORT_FN(pointDistanceStats);
+    EXPORT_FN(pointIndexBounds); EXPORT_FN(pointIndexKNearest); EXPORT_FN(pointCloudPositions); EXPORT_FN(pointCloudNeighbourScales);
     EXPORT_FN(tiledRasterizerEncodeContribution); EXPORT_FN(densifyContributionDecision);
     EXPORT_FN(encoderBegin); EXPORT_FN(encoderFinish); EXPORT_FN(queueSubmit); EXPORT_FN(commandBufferDestroy); EXPORT_FN(queueOnSubmittedWorkDone);
     EXPORT_FN(tiledBackwardMetric); EXPORT_FN(tiledBackwardGet); EXPORT_FN(downsampleRGBA8); EXPORT_FN(imageSSE); EXPORT_FN(imageSSIM);

@@ -288,8 +288,21 @@ export class PointIndex {
   reserveQueries(count: number): void;
   nearestInto(encoder: HipEncoder | null, queries: HipBuffer, count: number, maxDistance: number, d2: HipBuffer, index: HipBuffer, pairs?: HipBuffer | null): void;
   nearest(queries: Float32Array | HipBuffer, maxDistance: number): { d2: Float32Array; index: Uint32Array };
+  /** The bounding box of the finite points. */
+  bounds(): { lo: Float32Array; hi: Float32Array };
+  /** The k (1 to 16) nearest within maxDistance by (squared distance, index) into rows of d2 f32[count][k] and index u32[count][k], padded with +inf and
+   *  NO_INDEX; excludeSelf: query i leaves out the indexed point i.  Stream-ordered; records. */
+  kNearestInto(encoder: HipEncoder | null, queries: HipBuffer, count: number, k: number, maxDistance: number, d2: HipBuffer, index: HipBuffer,
+               excludeSelf?: boolean, pairs?: HipBuffer | null): void;
+  kNearest(queries: Float32Array | HipBuffer, k: number, maxDistance: number, excludeSelf?: boolean): { d2: Float32Array; index: Uint32Array };
   destroy(): void;
 }
+/** wdgs_point_index_k_nearest's flag bit 0.  No reference counterpart. */
+export const KNN_EXCLUDE_SELF: 1;
+/** 3DGS's scale initialisation from the k nearest neighbours, written in place into pointCloud.gaussian_3d_buffer (DESIGN.md section 15).  No reference
+ *  counterpart. */
+export function initScalesFromNeighbours(device: HipDevice, pointCloud: PointCloud,
+                                         options?: { k?: number; maxDistance?: number | null; minD2?: number; count?: number | null }): { meanD2: Float32Array; found: Uint32Array };
 export interface PointDistanceStats { n: number; n_found: number; n_within: number; sum_q: number; mean: number }
 /** Stream-ordered pointDistanceStats: three u64 { n_found, n_within, sum_q } into the first 24 bytes of `out`. */
 export function encodePointDistanceStats(device: HipDevice, d2: HipBuffer, count: number, maxDistance: number, threshold: number, out: HipBuffer): void;

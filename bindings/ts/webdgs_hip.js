@@ -616,6 +616,7 @@ function weldTriangles(tri) {
 
 // ---------------------------------------------------------------- mesh accuracy metrics (include/webdgs.h, DESIGN.md section 14; no reference counterpart)
 const NO_INDEX = 0xFFFFFFFF;
+const KNN_EXCLUDE_SELF = 1;   // WDGS_KNN_EXCLUDE_SELF
 /** { buf, rows, owned } of a [rows, width] array given as a typed array (uploaded; owned) or as a HipBuffer (whole rows of it). */
 function asDevice(device, array, Type, width, what) {
   if (array instanceof HipBuffer) return { buf: array, rows: Math.floor(array.size / (Type.BYTES_PER_ELEMENT * width)), owned: false };
@@ -705,6 +706,29 @@ class PointIndex {
       return { d2: new Float32Array(bytes(d2, 4 * k)), index: new Uint32Array(bytes(index, 4 * k)) };
     } finally { d2.destroy(); index.destroy(); if (q.owned) q.buf.destroy(); }
   }
+  /** { lo, hi }: the bounding box of the finite points (Float32Array[3] each; zeros when there is none).  No device work. */
+  bounds() { const a = addon.pointIndexBounds(this.handle); return { lo: Float32Array.from(a.slice(0, 3)), hi: Float32Array.from(a.slice(3, 6)) }; }
+  /** Stream-ordered kNearest: for each of the first `count` points of `queries` the k (1 to 16) nearest indexed points within maxDistance, ordered by
+   *  (squared distance, index), into row i of d2 f32[count][k] and index u32[count][k]; slots beyond the candidates, and every slot of a non-finite
+   *  query, hold +inf and 0xFFFFFFFF.  excludeSelf: query i leaves out the indexed point i (the self-query).  pairs (optional, 8 bytes): the number of
+   *  pairs examined is added to it.  No host wait; records. */
+  kNearestInto(encoder, queries, count, k, maxDistance, d2, index, excludeSelf, pairs) {
+    if (!(k >= 0 && k <= 0xFFFFFFFF) || queries.size < 12 * count || d2.size < 4 * count * k || index.size < 4 * count * k || (pairs && pairs.size < 8)) {
+      throw new Error(`PointIndex.kNearest: buffers too small for ${count} queries with k = ${k}`);
+    }
+    addon.pointIndexKNearest(this.handle, queries.ptr, count, k, maxDistance, excludeSelf ? KNN_EXCLUDE_SELF : 0, d2.ptr, index.ptr, pairs ? pairs.ptr : null);
+  }
+  /** { d2: Float32Array[K*k], index: Uint32Array[K*k] }, row-major, for `queries` ([K*3] Float32Array or a HipBuffer).  Synchronises. */
+  kNearest(queries, k, maxDistance, excludeSelf) {
+    const q = asDevice(this.device, queries, Float32Array, 3, 'PointIndex.kNearest: queries'), n = q.rows;
+    const room = 4 * Math.max(n * Math.max(0, Math.min(k, 1024)), 1);   // (the library refuses a k outside [1, 16])
+    const d2 = this.device.createBuffer({ size: room }), index = this.device.createBuffer({ size: room });
+    try {
+      this.kNearestInto(null, q.buf, n, k, maxDistance, d2, index, excludeSelf);
+      const bytes = (b, len) => (len ? this.device.readBuffer(b, len) : new ArrayBuffer(0));
+      return { d2: new Float32Array(bytes(d2, 4 * n * k)), index: new Uint32Array(bytes(index, 4 * n * k)) };
+    } finally { d2.destroy(); index.destroy(); if (q.owned) q.buf.destroy(); }
+  }
   destroy() {
     if (this.destroyed) return;
     this.destroyed = true;
@@ -712,6 +736,40 @@ class PointIndex {
     this.handle = null;
     if (this.owned) this.points.destroy();
     this.points = null;
+  }
+}
+/** 3DGS's scale initialisation, in place: every point of `pointCloud` gets log sigma = 0.5 log(max(mean, minD2)) on all three axes, mean the mean squared
+ *  distance to its k nearest other points within maxDistance (fewer when fewer are there; a point without any keeps its scales).  The distances are those
+ *  of the records' fp16 positions.  options: { k = 3, maxDistance (default: twice the widest extent of the finite positions, every other point a candidate;
+ *  for a cloud with far outliers pass a cutoff), minD2 = 1e-7, count }.  Only halves 8, 9, 10 of each record of gaussian_3d_buffer change.  Returns
+ *  { meanD2: Float32Array[N] (+inf without a neighbour), found: Uint32Array[N] }.  Synchronises. */
+function initScalesFromNeighbours(device, pointCloud, options) {
+  const o = options || {};
+  const n = o.count === undefined || o.count === null ? pointCloud.num_points : o.count;
+  if (n < 0 || n > pointCloud.num_points) throw new Error('initScalesFromNeighbours: the count exceeds the point cloud');
+  const k = o.k === undefined || o.k === null ? 3 : o.k, minD2 = o.minD2 === undefined || o.minD2 === null ? 1e-7 : o.minD2;
+  const g = pointCloud.gaussian_3d_buffer, slots = n * Math.max(0, Math.min(k, 1024));
+  const positions = device.createBuffer({ size: 12 * Math.max(n, 1) }), d2 = device.createBuffer({ size: 4 * Math.max(slots, 1) });
+  const idx = device.createBuffer({ size: 4 * Math.max(slots, 1) }), mean = device.createBuffer({ size: 4 * Math.max(n, 1) });
+  let index = null;
+  try {
+    addon.pointCloudPositions(device.handle, g.ptr, n, positions.ptr);
+    index = new PointIndex(device, positions, { count: n });
+    let maxDistance = o.maxDistance;
+    if (maxDistance === undefined || maxDistance === null) {
+      const b = index.bounds();
+      const widest = Math.max(b.hi[0] - b.lo[0], b.hi[1] - b.lo[1], b.hi[2] - b.lo[2]);
+      maxDistance = widest > 0 ? 2 * widest : 1;
+    }
+    index.kNearestInto(null, positions, n, k, maxDistance, d2, idx, true);
+    addon.pointCloudNeighbourScales(device.handle, g.ptr, n, d2.ptr, k, minD2, mean.ptr);
+    const bytes = (b, len) => (len ? device.readBuffer(b, len) : new ArrayBuffer(0));
+    const rows = new Float32Array(bytes(d2, 4 * n * k)), found = new Uint32Array(n);
+    for (let i = 0; i < n; i++) for (let s = 0; s < k; s++) if (Number.isFinite(rows[i * k + s])) found[i]++;
+    return { meanD2: new Float32Array(bytes(mean, 4 * n)), found };
+  } finally {
+    if (index) index.destroy();
+    positions.destroy(); d2.destroy(); idx.destroy(); mean.destroy();
   }
 }
 /** Stream-ordered pointDistanceStats: the three u64 sums into the first 24 bytes of `out` (no host wait). */
@@ -840,7 +898,7 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, NO_INDEX, MeshSampler, sampleMesh, PointIndex, encodePointDistanceStats, pointDistanceStats,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
   geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

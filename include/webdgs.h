@@ -702,6 +702,25 @@ int wdgs_point_index_info(const wdgs_point_index* index, float* cell_size, uint3
  * (WDGS_E_INVALID).  Stream-ordered, recordable once the grid exists and the room is reserved. */
 int wdgs_point_index_nearest(wdgs_point_index* index, const void* queries_f32_dev, uint32_t num_queries, float max_distance, void* d2_f32_dev, void* index_u32_dev,
                              void* pairs_u64_dev);
+/* The bounding box of the finite points as the build read it back: lo f32[3] and hi f32[3], each nullable; all zero when no point is finite.  No device work. */
+int wdgs_point_index_bounds(const wdgs_point_index* index, float* lo3, float* hi3);
+/* The k nearest.  For query i of queries f32[K][3] the candidates are the indexed points j with d2 <= r2 (d2, r2 as for nearest), with
+ * WDGS_KNN_EXCLUDE_SELF only those with original index j != i -- the self-query, where the queries are the indexed points.  Ordered by (d2, j), the lower index
+ * first among equal d2, the first min(k, count) of them go to slots 0 .. of row i of d2 f32[K][k] and index u32[K][k]; the remaining slots, and every slot of a
+ * non-finite query, receive +inf and 0xFFFFFFFF.  1 <= k <= WDGS_KNN_MAX_K, K k <= 2^32 - 1, max_distance positive and finite, no unknown flag bit
+ * (WDGS_E_INVALID; nothing is written).  pairs_u64_dev and recording as for nearest; with k = 1 and no flag the outputs and the pair count are nearest's. */
+#define WDGS_KNN_EXCLUDE_SELF 1u
+#define WDGS_KNN_MAX_K 16u
+int wdgs_point_index_k_nearest(wdgs_point_index* index, const void* queries_f32_dev, uint32_t num_queries, uint32_t k, float max_distance, uint32_t flags,
+                               void* d2_f32_dev, void* index_u32_dev, void* pairs_u64_dev);
+/* positions f32[N][3] = halves 0, 1, 2 (fp16) of each record of gaussians u32[N][6], exactly: the positions the renderer sees.  Stream-ordered, recordable. */
+int wdgs_point_cloud_positions(wdgs_device* dev, const void* gaussians_dev, uint32_t num_points, void* positions_f32_dev);
+/* 3DGS's scale initialisation from k_nearest's d2 f32[N][k] of a self-query.  Per point: found = the finite slots, s = their f32 sum from slot 0 on,
+ * mean = s / (float)found, log sigma = 0.5f log(max(mean, min_d2)) (the library's log, DESIGN.md "dmath"), rounded to fp16 (nearest even) into halves 8, 9, 10
+ * of its record; half 11 and halves 0 - 7 keep their bytes.  A point with found = 0 keeps its whole record.  mean_d2 f32[N] (nullable) receives mean, +inf for
+ * found = 0.  min_d2 positive and finite, 1 <= k <= WDGS_KNN_MAX_K (WDGS_E_INVALID).  Stream-ordered, recordable. */
+int wdgs_point_cloud_neighbour_scales(wdgs_device* dev, void* gaussians_dev, uint32_t num_points, const void* d2_f32_dev, uint32_t k, float min_d2,
+                                      void* mean_d2_f32_dev);
 /* out u64[3] = { n_found: the finite d2;  n_within: those with d2 <= threshold threshold (f32);  sum_q: the sum over the found of
  * u32((sqrt(d2) / max_distance) * 2^24) }, exact integer sums; the mean distance is sum_q max_distance / 2^24 / n_found.  0 < threshold <= max_distance, both
  * finite (WDGS_E_INVALID).  Stream-ordered, no host wait, recordable. */

@@ -165,6 +165,10 @@ SIGNATURES = {
     "wdgs_point_index_info": (_I, [_P, C.POINTER(_F), C.POINTER(_U), C.POINTER(_U)]),
     "wdgs_point_index_nearest": (_I, [_P, _P, _U, _F, _P, _P, _P]),
     "wdgs_point_distance_stats": (_I, [_P, _P, _U, _F, _F, _P]),
+    "wdgs_point_index_bounds": (_I, [_P, C.POINTER(_F), C.POINTER(_F)]),
+    "wdgs_point_index_k_nearest": (_I, [_P, _P, _U, _U, _F, _U, _P, _P, _P]),
+    "wdgs_point_cloud_positions": (_I, [_P, _P, _U, _P]),
+    "wdgs_point_cloud_neighbour_scales": (_I, [_P, _P, _U, _P, _U, _F, _P]),
     "wdgs_optimizer_step_f32_range": (_I, [_P, _P, _P, _P, _P, _U, _U, _P]),
     "wdgs_apply_repacked_rows": (_I, [_P, _U, _P, _U, _U, _P, _P, _P]),
     "wdgs_optimizer_set_guard": (_I, [_P, _P]),

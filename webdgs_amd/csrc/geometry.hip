@@ -1,5 +1,6 @@
 // Mesh accuracy metrics (no counterpart in the reference, which renders colour only): area-weighted sampling of a triangle mesh, a
-// uniform-grid point index with exact nearest-point queries under a cutoff, and exact integer distance statistics.
+// uniform-grid point index with exact nearest-point queries under a cutoff, and exact integer distance statistics; and on the same index (section 15) the
+// k nearest points of a query and 3DGS's scale initialisation from them.
 //
 // Everything here is f32 in the order written (-ffp-contract=off, no FMA), square roots and quotients through wd_sqrt / wd_div, and every sum an integer:
 // tests/geometry_ref.py restates the three pieces in numpy float32 and the GPU tests compare bytes.  The grid of the index is a speed choice only -- the
@@ -193,22 +194,100 @@ __global__ __launch_bounds__(256) void query_order_kernel(u32 n, const u32* __re
     order[starts[cell_of[i]] + rank[i]] = i;
 }
 
+// The running best of a query is a policy of nearest_kernel.  start() is the state of a query that finds nothing; search(r2) opens it for candidates --
+// every place then holds { r2, NO_INDEX }, so the cutoff "d2 <= r2", the tie rule and "not yet full" are one comparison, whatever order the records come
+// in; offer() is one candidate; worst() is what the early exit compares; finish() and write() close the search and store the query's row.
 struct Best {
+    struct Args {};
     float d2;
     u32 index;
+    __device__ __forceinline__ void start(u32, Args) { d2 = __builtin_inff(); index = NO_INDEX; }
+    __device__ __forceinline__ void search(float r2) { d2 = r2; }
+    // kept when smaller, or equal with a lower original index
+    __device__ __forceinline__ void offer(float c, u32 j) {
+        const bool take = (c < d2) | ((c == d2) & (j < index));
+        d2 = take ? c : d2;
+        index = take ? j : index;
+    }
+    __device__ __forceinline__ float worst() const { return d2; }
+    __device__ __forceinline__ void finish() { if (index == NO_INDEX) d2 = __builtin_inff(); }
+    __device__ __forceinline__ void write(u32 q, float* __restrict__ d2_out, u32* __restrict__ index_out) const {
+        d2_out[q] = d2;
+        index_out[q] = index;
+    }
 };
-// One record against the query: d2 = ((dx dx + dy dy) + dz dz); kept when smaller, or equal with a lower original index.  best starts at { r2, NO_INDEX }, so
-// "d2 <= r2" and the tie rule are this one comparison, whatever order the records come in.
-__device__ __forceinline__ void test_record(const float4 r, float px, float py, float pz, Best& best) {
+
+// The k nearest (section 15): CAP slots in registers, sorted ascending by (d2, index).  The first CAP - k slots hold { -1, 0 }, which sorts before every
+// candidate (d2 >= 0) and never moves, so the k-th nearest so far is always slot CAP - 1, a compile-time place.  `self`: the original index left out
+// (NO_INDEX, which no record carries, leaves nothing out).  Every slot access is unrolled: nothing is indexed dynamically and nothing goes to scratch.
+template <u32 CAP>
+struct BestK {
+    struct Args { u32 k, exclude_self; };
+    float d2[CAP];
+    u32 index[CAP];
+    u32 k, self;
+    __device__ __forceinline__ bool live(u32 s) const { return s + k >= CAP; }
+    __device__ __forceinline__ void start(u32 q, Args a) {
+        k = a.k;
+        self = a.exclude_self ? q : NO_INDEX;
+#pragma unroll
+        for (u32 s = 0; s < CAP; s++) {
+            d2[s] = live(s) ? __builtin_inff() : -1.0f;
+            index[s] = live(s) ? NO_INDEX : 0u;
+        }
+    }
+    __device__ __forceinline__ void search(float r2) {
+#pragma unroll
+        for (u32 s = 0; s < CAP; s++) d2[s] = live(s) ? r2 : d2[s];
+    }
+    // The excluded record fails before the comparison: it never enters the list and so never lets the search end early.  A candidate that beats the worst
+    // replaces it and sinks to its place by CAP - 1 compare-and-swap steps of selects.
+    __device__ __forceinline__ void offer(float c, u32 j) {
+        const bool take = (j != self) & ((c < d2[CAP - 1u]) | ((c == d2[CAP - 1u]) & (j < index[CAP - 1u])));
+        if (take) {
+            d2[CAP - 1u] = c;
+            index[CAP - 1u] = j;
+#pragma unroll
+            for (u32 s = CAP - 1u; s >= 1u; s--) {
+                const float a = d2[s - 1u], b = d2[s];
+                const u32 ia = index[s - 1u], ib = index[s];
+                const bool swap = (b < a) | ((b == a) & (ib < ia));
+                d2[s - 1u] = swap ? b : a;
+                index[s - 1u] = swap ? ib : ia;
+                d2[s] = swap ? a : b;
+                index[s] = swap ? ia : ib;
+            }
+        }
+    }
+    __device__ __forceinline__ float worst() const { return d2[CAP - 1u]; }
+    __device__ __forceinline__ void finish() {
+#pragma unroll
+        for (u32 s = 0; s < CAP; s++) d2[s] = index[s] == NO_INDEX ? __builtin_inff() : d2[s];
+    }
+    // row q of [K][k]: the live slots in order
+    __device__ __forceinline__ void write(u32 q, float* __restrict__ d2_out, u32* __restrict__ index_out) const {
+        float* d2_row = d2_out + (size_t)q * k;
+        u32* index_row = index_out + (size_t)q * k;
+#pragma unroll
+        for (u32 s = 0; s < CAP; s++) {
+            if (live(s)) {
+                d2_row[s + k - CAP] = d2[s];
+                index_row[s + k - CAP] = index[s];
+            }
+        }
+    }
+};
+
+// One record against the query: d2 = ((dx dx + dy dy) + dz dz), offered to the running best.
+template <class B>
+__device__ __forceinline__ void test_record(const float4 r, float px, float py, float pz, B& best) {
     const float dx = px - r.x, dy = py - r.y, dz = pz - r.z;
     const float d2 = (dx * dx + dy * dy) + dz * dz;
-    const u32 j = __float_as_uint(r.w);
-    const bool take = (d2 < best.d2) | ((d2 == best.d2) & (j < best.index));
-    best.d2 = take ? d2 : best.d2;
-    best.index = take ? j : best.index;
+    best.offer(d2, __float_as_uint(r.w));
 }
 // The records [first, last) against the query, four 16-byte loads in flight at a time: the loop is bound by its arithmetic, not by one load's latency.
-__device__ __forceinline__ void scan_records(const float4* __restrict__ records, u32 first, u32 last, float px, float py, float pz, Best& best) {
+template <class B>
+__device__ __forceinline__ void scan_records(const float4* __restrict__ records, u32 first, u32 last, float px, float py, float pz, B& best) {
     u32 i = first;
     for (; i + 4u <= last; i += 4u) {
         const float4 r0 = records[i], r1 = records[i + 1u], r2 = records[i + 2u], r3 = records[i + 3u];
@@ -223,19 +302,21 @@ __device__ __forceinline__ void scan_records(const float4* __restrict__ records,
 // One thread per query, the queries taken in cell order (a wave's 64 queries walk the same few cells).  The cells searched are, per axis, those from
 // cell(p - R) to cell(p + R), R a little above the cutoff: every point with d2 <= r2 lies in them (section 14: cell() is monotone).  They are visited in rings
 // of growing Chebyshev distance k from the query's own cell; after ring k every unvisited point is farther than T_k = (k cell - slack) 0.9999, and the search
-// ends once best.d2 < T_k^2 STRICTLY -- a point of an outer ring with the same d2 and a lower index must still be seen.
-template <bool COUNT>
+// ends once best.worst() < T_k^2 STRICTLY -- a point of an outer ring with the same d2 and a lower index must still be seen.  B: Best for the nearest point,
+// BestK<CAP> for the k nearest (section 15) -- one walk, two ways of keeping what it finds.
+template <class B, bool COUNT>
 __global__ __launch_bounds__(256) void nearest_kernel(PointGrid g, const float4* __restrict__ records, const u32* __restrict__ starts, const float* __restrict__ queries,
                                                       const u32* __restrict__ order, u32 K, float r, float r2, float* __restrict__ d2_out, u32* __restrict__ index_out,
-                                                      unsigned long long* __restrict__ pairs) {
+                                                      unsigned long long* __restrict__ pairs, typename B::Args args) {
     const u32 tid = blockIdx.x * 256u + threadIdx.x;
     unsigned long long examined = 0ull;
     if (tid < K) {
         const u32 q = order[tid];
         const float px = queries[3u * (size_t)q], py = queries[3u * (size_t)q + 1u], pz = queries[3u * (size_t)q + 2u];
-        Best best = {__builtin_inff(), NO_INDEX};
+        B best;
+        best.start(q, args);
         if (finite3(px, py, pz)) {
-            best.d2 = r2;
+            best.search(r2);
             const float R = fmaxf(r * 1.0001f, 2.0e-18f);
             const int qx = (int)cell_coord(px, g.lox, g.cell, g.nx), qy = (int)cell_coord(py, g.loy, g.cell, g.ny), qz = (int)cell_coord(pz, g.loz, g.cell, g.nz);
             const int x0 = (int)cell_coord(px - R, g.lox, g.cell, g.nx), x1 = (int)cell_coord(px + R, g.lox, g.cell, g.nx);
@@ -267,12 +348,11 @@ __global__ __launch_bounds__(256) void nearest_kernel(PointGrid g, const float4*
                     }
                 }
                 const float T = ((float)k * g.cell - g.slack) * 0.9999f;
-                if (T > 0.0f && best.d2 < T * T) break;
+                if (T > 0.0f && best.worst() < T * T) break;
             }
-            if (best.index == NO_INDEX) best.d2 = __builtin_inff();
+            best.finish();
         }
-        d2_out[q] = best.d2;
-        index_out[q] = best.index;
+        best.write(q, d2_out, index_out);
     }
     if (COUNT) {
 #pragma unroll
@@ -313,6 +393,44 @@ __global__ __launch_bounds__(256) void distance_stats_kernel(const float* __rest
         const unsigned long long s = s_w[threadIdx.x][0] + s_w[threadIdx.x][1] + s_w[threadIdx.x][2] + s_w[threadIdx.x][3];
         if (s) atomicAdd(out + threadIdx.x, s);
     }
+}
+
+// ---------------------------------------------------------------- 4. scales from the neighbours (section 15)
+// positions[i] = halves 0, 1, 2 of record i (u32[6]: position and opacity, rotation, log scale and one spare half) as f32: what the renderer sees
+__global__ __launch_bounds__(256) void unpack_positions_kernel(const u32* __restrict__ gaussians, u32 N, float* __restrict__ positions) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= N) return;
+    const u32 w0 = gaussians[6u * (size_t)i], w1 = gaussians[6u * (size_t)i + 1u];
+    positions[3u * (size_t)i] = wd_unpack_lo(w0);
+    positions[3u * (size_t)i + 1u] = wd_unpack_hi(w0);
+    positions[3u * (size_t)i + 2u] = wd_unpack_lo(w1);
+}
+
+// One thread per point: the mean of the finite slots of its row of d2 (summed from slot 0; the finite slots come first), clamped from below, and
+// log sigma = 0.5 log(mean) as fp16 into halves 8, 9, 10 of its record.  A row without a finite slot leaves the record alone.
+__global__ __launch_bounds__(256) void neighbour_scales_kernel(u32* __restrict__ gaussians, u32 N, const float* __restrict__ d2, u32 k, float min_d2,
+                                                               float* __restrict__ mean_out) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= N) return;
+    const float* row = d2 + (size_t)i * k;
+    float s = 0.0f;
+    u32 found = 0u;
+    for (u32 j = 0; j < k; j++) {
+        const float v = row[j];
+        if (fabsf(v) < __builtin_inff()) {
+            s = s + v;
+            found++;
+        }
+    }
+    float mean = __builtin_inff();
+    if (found) {
+        mean = wd_div(s, (float)found);
+        const u32 h = wd_f16bits(0.5f * wd_log(fmaxf(mean, min_d2)));
+        u32* w = gaussians + 6u * (size_t)i;
+        w[4] = h | (h << 16);
+        w[5] = (w[5] & 0xFFFF0000u) | h;
+    }
+    if (mean_out) mean_out[i] = mean;
 }
 
 bool positive_finite(float x) { return x > 0.0f && x < __builtin_inff(); }
@@ -445,7 +563,7 @@ struct wdgs_point_index {
     wdgs_device* dev = nullptr;
     const float* points = nullptr;   // the caller's, read by the build only
     u32 M = 0, indexed = 0;          // points given, finite points kept
-    float lo[3] = {0.f, 0.f, 0.f};
+    float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f};
     double extent[3] = {0., 0., 0.};
     bool built = false;
     PointGrid g = {0.f, 0.f, 0.f, 1.f, 1u, 1u, 1u, 0.f};
@@ -538,7 +656,8 @@ extern "C" int wdgs_point_index_create(wdgs_device* dev, const void* points_f32_
     if (ix->indexed) {
         for (int a = 0; a < 3; a++) {
             ix->lo[a] = from_ordered_bits(b[a]);
-            ix->extent[a] = (double)from_ordered_bits(b[3 + a]) - (double)ix->lo[a];
+            ix->hi[a] = from_ordered_bits(b[3 + a]);
+            ix->extent[a] = (double)ix->hi[a] - (double)ix->lo[a];
         }
     }
     if (cell_size != 0.0f) WDGS_TRY(point_index_build_grid(ix.get(), cell_size));
@@ -567,6 +686,42 @@ extern "C" int wdgs_point_index_info(const wdgs_point_index* ix, float* cell_siz
     return WDGS_OK;
 }
 
+extern "C" int wdgs_point_index_bounds(const wdgs_point_index* ix, float* lo3, float* hi3) {
+    WDGS_REQUIRE(ix, WDGS_E_INVALID, "wdgs_point_index_bounds: null index");
+    for (int a = 0; a < 3; a++) {
+        if (lo3) lo3[a] = ix->lo[a];
+        if (hi3) hi3[a] = ix->hi[a];
+    }
+    return WDGS_OK;
+}
+
+// What both queries do before their kernel: the grid of an index created with a cell edge of 0 (the first query's cutoff, or the edge at which a cube of
+// the widest extent holds one cell per point if smaller), and the queries bucketed by cell into ix->order.  Not called for K = 0 or an empty index.
+static int point_index_ensure_grid(wdgs_point_index* ix, float max_distance, const char* who) {
+    if (ix->built) return WDGS_OK;
+    WDGS_REQUIRE(!ix->dev->capturing, WDGS_E_STATE, "PointIndex.%s: the index has no grid yet (cell edge 0) and its first query, which builds it, cannot be recorded", who);
+    float edge = max_distance;
+    const double widest = std::max(ix->extent[0], std::max(ix->extent[1], ix->extent[2]));
+    if (ix->indexed && std::isfinite(widest)) {
+        const float by_count = (float)(widest / std::cbrt((double)ix->indexed));
+        if (positive_finite(by_count) && by_count < edge) edge = by_count;
+    }
+    return point_index_build_grid(ix, edge);
+}
+
+static int point_index_order_queries(wdgs_point_index* ix, const float* queries, u32 K) {
+    wdgs_device* d = ix->dev;
+    const u32 blocks = ceil_div(K, 256u);
+    WDGS_TRY(point_index_reserve(ix, K));
+    WDGS_CHECK_HIP(hipMemsetAsync(ix->counts, 0, (size_t)ix->cells * sizeof(u32), d->stream));
+    WDGS_LAUNCH(d, "query_cell", point_cell_kernel, dim3(blocks), dim3(256), 0, ix->g, queries, K, 1u, ix->cell_of, ix->rank, ix->counts);
+    WDGS_CHECK_HIP(hipGetLastError());
+    WDGS_TRY(scan_exclusive_u32(d, &ix->scan, ix->counts, ix->query_starts, ix->cells, ix->scan_total));
+    WDGS_LAUNCH(d, "query_order", query_order_kernel, dim3(blocks), dim3(256), 0, K, ix->cell_of, ix->rank, ix->query_starts, ix->order);
+    WDGS_CHECK_HIP(hipGetLastError());
+    return WDGS_OK;
+}
+
 extern "C" int wdgs_point_index_nearest(wdgs_point_index* ix, const void* queries_f32_dev, uint32_t num_queries, float max_distance, void* d2_f32_dev, void* index_u32_dev,
                                         void* pairs_u64_dev) {
     WDGS_REQUIRE(ix, WDGS_E_INVALID, "wdgs_point_index_nearest: null index");
@@ -576,16 +731,7 @@ extern "C" int wdgs_point_index_nearest(wdgs_point_index* ix, const void* querie
     WDGS_REQUIRE((((uintptr_t)queries_f32_dev | (uintptr_t)d2_f32_dev | (uintptr_t)index_u32_dev) & 3u) == 0u && ((uintptr_t)pairs_u64_dev & 7u) == 0u, WDGS_E_INVALID,
                  "wdgs_point_index_nearest: misaligned argument");
     wdgs_device* d = ix->dev;
-    if (!ix->built) {   // created with a cell edge of 0: the first query's cutoff, or the edge at which a cube of the widest extent holds one cell per point if smaller
-        WDGS_REQUIRE(!d->capturing, WDGS_E_STATE, "PointIndex.nearest: the index has no grid yet (cell edge 0) and its first query, which builds it, cannot be recorded");
-        float edge = max_distance;
-        const double widest = std::max(ix->extent[0], std::max(ix->extent[1], ix->extent[2]));
-        if (ix->indexed && std::isfinite(widest)) {
-            const float by_count = (float)(widest / std::cbrt((double)ix->indexed));
-            if (positive_finite(by_count) && by_count < edge) edge = by_count;
-        }
-        WDGS_TRY(point_index_build_grid(ix, edge));
-    }
+    WDGS_TRY(point_index_ensure_grid(ix, max_distance, "nearest"));
     if (num_queries == 0) return WDGS_OK;
     const u32 K = num_queries, blocks = ceil_div(K, 256u);
     float* d2 = static_cast<float*>(d2_f32_dev);
@@ -595,21 +741,78 @@ extern "C" int wdgs_point_index_nearest(wdgs_point_index* ix, const void* querie
         WDGS_CHECK_HIP(hipGetLastError());
         return WDGS_OK;
     }
-    WDGS_TRY(point_index_reserve(ix, K));
     const float* queries = static_cast<const float*>(queries_f32_dev);
-    WDGS_CHECK_HIP(hipMemsetAsync(ix->counts, 0, (size_t)ix->cells * sizeof(u32), d->stream));
-    WDGS_LAUNCH(d, "query_cell", point_cell_kernel, dim3(blocks), dim3(256), 0, ix->g, queries, K, 1u, ix->cell_of, ix->rank, ix->counts);
-    WDGS_CHECK_HIP(hipGetLastError());
-    WDGS_TRY(scan_exclusive_u32(d, &ix->scan, ix->counts, ix->query_starts, ix->cells, ix->scan_total));
-    WDGS_LAUNCH(d, "query_order", query_order_kernel, dim3(blocks), dim3(256), 0, K, ix->cell_of, ix->rank, ix->query_starts, ix->order);
-    WDGS_CHECK_HIP(hipGetLastError());
+    WDGS_TRY(point_index_order_queries(ix, queries, K));
     const float r2 = max_distance * max_distance;
-    if (pairs_u64_dev)
-        WDGS_LAUNCH(d, "nearest", nearest_kernel<true>, dim3(blocks), dim3(256), 0, ix->g, ix->records, ix->starts, queries, ix->order, K, max_distance, r2, d2, index,
-                    static_cast<unsigned long long*>(pairs_u64_dev));
-    else
-        WDGS_LAUNCH(d, "nearest", nearest_kernel<false>, dim3(blocks), dim3(256), 0, ix->g, ix->records, ix->starts, queries, ix->order, K, max_distance, r2, d2, index,
-                    static_cast<unsigned long long*>(nullptr));
+    unsigned long long* pairs = static_cast<unsigned long long*>(pairs_u64_dev);
+    const auto kernel = pairs ? nearest_kernel<Best, true> : nearest_kernel<Best, false>;
+    WDGS_LAUNCH(d, "nearest", kernel, dim3(blocks), dim3(256), 0, ix->g, ix->records, ix->starts, queries, ix->order, K, max_distance, r2, d2, index, pairs, Best::Args{});
+    WDGS_CHECK_HIP(hipGetLastError());
+    return WDGS_OK;
+}
+
+template <u32 CAP>
+static int launch_k_nearest(wdgs_point_index* ix, const float* queries, u32 K, u32 k, u32 exclude_self, float r, float* d2, u32* index, unsigned long long* pairs) {
+    wdgs_device* d = ix->dev;
+    const float r2 = r * r;
+    const auto kernel = pairs ? nearest_kernel<BestK<CAP>, true> : nearest_kernel<BestK<CAP>, false>;
+    WDGS_LAUNCH(d, "k_nearest", kernel, dim3(ceil_div(K, 256u)), dim3(256), 0, ix->g, ix->records, ix->starts, queries, ix->order, K, r, r2, d2, index, pairs,
+                (typename BestK<CAP>::Args{k, exclude_self}));
+    WDGS_CHECK_HIP(hipGetLastError());
+    return WDGS_OK;
+}
+
+extern "C" int wdgs_point_index_k_nearest(wdgs_point_index* ix, const void* queries_f32_dev, uint32_t num_queries, uint32_t k, float max_distance, uint32_t flags,
+                                          void* d2_f32_dev, void* index_u32_dev, void* pairs_u64_dev) {
+    WDGS_REQUIRE(ix, WDGS_E_INVALID, "wdgs_point_index_k_nearest: null index");
+    WDGS_REQUIRE(k >= 1u && k <= WDGS_KNN_MAX_K, WDGS_E_INVALID, "PointIndex.kNearest: k must lie in [1, %u] (got %u)", (unsigned)WDGS_KNN_MAX_K, k);
+    WDGS_REQUIRE((flags & ~(uint32_t)WDGS_KNN_EXCLUDE_SELF) == 0u, WDGS_E_INVALID, "PointIndex.kNearest: unknown flag bits 0x%x", flags);
+    WDGS_REQUIRE(positive_finite(max_distance), WDGS_E_INVALID, "PointIndex.kNearest: max_distance must be positive and finite (got %g)", (double)max_distance);
+    WDGS_REQUIRE(num_queries <= 0x7FFFFFFFu, WDGS_E_INVALID, "PointIndex.kNearest: %u queries, more than 2^31 - 1", num_queries);
+    WDGS_REQUIRE((uint64_t)num_queries * k <= 0xFFFFFFFFull, WDGS_E_INVALID, "PointIndex.kNearest: %u queries times k = %u, more than 2^32 - 1 slots", num_queries, k);
+    WDGS_REQUIRE(num_queries == 0 || (queries_f32_dev && d2_f32_dev && index_u32_dev), WDGS_E_INVALID, "wdgs_point_index_k_nearest: null argument");
+    WDGS_REQUIRE((((uintptr_t)queries_f32_dev | (uintptr_t)d2_f32_dev | (uintptr_t)index_u32_dev) & 3u) == 0u && ((uintptr_t)pairs_u64_dev & 7u) == 0u, WDGS_E_INVALID,
+                 "wdgs_point_index_k_nearest: misaligned argument");
+    wdgs_device* d = ix->dev;
+    WDGS_TRY(point_index_ensure_grid(ix, max_distance, "kNearest"));
+    if (num_queries == 0) return WDGS_OK;
+    const u32 K = num_queries;
+    float* d2 = static_cast<float*>(d2_f32_dev);
+    u32* index = static_cast<u32*>(index_u32_dev);
+    if (ix->indexed == 0) {
+        WDGS_LAUNCH(d, "nearest_fill", fill_nothing_found_kernel, dim3(ceil_div(K * k, 256u)), dim3(256), 0, K * k, d2, index);
+        WDGS_CHECK_HIP(hipGetLastError());
+        return WDGS_OK;
+    }
+    const float* queries = static_cast<const float*>(queries_f32_dev);
+    WDGS_TRY(point_index_order_queries(ix, queries, K));
+    const u32 exclude_self = flags & WDGS_KNN_EXCLUDE_SELF;
+    unsigned long long* pairs = static_cast<unsigned long long*>(pairs_u64_dev);
+    if (k <= 4u) return launch_k_nearest<4>(ix, queries, K, k, exclude_self, max_distance, d2, index, pairs);
+    if (k <= 8u) return launch_k_nearest<8>(ix, queries, K, k, exclude_self, max_distance, d2, index, pairs);
+    return launch_k_nearest<16>(ix, queries, K, k, exclude_self, max_distance, d2, index, pairs);
+}
+
+extern "C" int wdgs_point_cloud_positions(wdgs_device* dev, const void* gaussians_dev, uint32_t num_points, void* positions_f32_dev) {
+    WDGS_REQUIRE(dev && (num_points == 0 || (gaussians_dev && positions_f32_dev)), WDGS_E_INVALID, "wdgs_point_cloud_positions: null argument");
+    WDGS_REQUIRE((((uintptr_t)gaussians_dev | (uintptr_t)positions_f32_dev) & 3u) == 0u, WDGS_E_INVALID, "wdgs_point_cloud_positions: misaligned argument");
+    if (num_points == 0) return WDGS_OK;
+    WDGS_LAUNCH(dev, "unpack_positions", unpack_positions_kernel, dim3(ceil_div(num_points, 256u)), dim3(256), 0, static_cast<const u32*>(gaussians_dev), num_points,
+                static_cast<float*>(positions_f32_dev));
+    WDGS_CHECK_HIP(hipGetLastError());
+    return WDGS_OK;
+}
+
+extern "C" int wdgs_point_cloud_neighbour_scales(wdgs_device* dev, void* gaussians_dev, uint32_t num_points, const void* d2_f32_dev, uint32_t k, float min_d2,
+                                                 void* mean_d2_f32_dev) {
+    WDGS_REQUIRE(dev && (num_points == 0 || (gaussians_dev && d2_f32_dev)), WDGS_E_INVALID, "wdgs_point_cloud_neighbour_scales: null argument");
+    WDGS_REQUIRE(k >= 1u && k <= WDGS_KNN_MAX_K, WDGS_E_INVALID, "initScalesFromNeighbours: k must lie in [1, %u] (got %u)", (unsigned)WDGS_KNN_MAX_K, k);
+    WDGS_REQUIRE(positive_finite(min_d2), WDGS_E_INVALID, "initScalesFromNeighbours: min_d2 must be positive and finite (got %g)", (double)min_d2);
+    WDGS_REQUIRE((((uintptr_t)gaussians_dev | (uintptr_t)d2_f32_dev | (uintptr_t)mean_d2_f32_dev) & 3u) == 0u, WDGS_E_INVALID,
+                 "wdgs_point_cloud_neighbour_scales: misaligned argument");
+    if (num_points == 0) return WDGS_OK;
+    WDGS_LAUNCH(dev, "neighbour_scales", neighbour_scales_kernel, dim3(ceil_div(num_points, 256u)), dim3(256), 0, static_cast<u32*>(gaussians_dev), num_points,
+                static_cast<const float*>(d2_f32_dev), k, min_d2, static_cast<float*>(mean_d2_f32_dev));
     WDGS_CHECK_HIP(hipGetLastError());
     return WDGS_OK;
 }

@@ -26,7 +26,10 @@ C0 = 0.28209479177387814
 
 @dataclasses.dataclass
 class PointCloudData:
-    """Host copy of a ``PointCloud`` (``utils/load-pointcloud.ts:16-23``): upload with ``ops.createPointCloud``."""
+    """Host copy of a ``PointCloud`` (``utils/load-pointcloud.ts:16-23``): upload with ``ops.createPointCloud``.
+
+    A ``'normal'`` cloud carries the reference's default splat parameters, ``log sigma = -5`` on every axis whatever the scene's scale: it is meant to be
+    passed through ``ops.initScalesFromNeighbours`` after ``createPointCloud``, which sets each point's scales from its nearest neighbours as 3DGS does."""
 
     type: str                 # 'full' (splats) or 'normal' (points with default splat parameters)
     num_points: int

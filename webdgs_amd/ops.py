@@ -958,6 +958,7 @@ def weldTriangles(tri: dict) -> dict:
 
 # ----------------------------------------------------------------------------- mesh accuracy metrics (no reference counterpart)
 NO_INDEX = 0xFFFFFFFF
+KNN_EXCLUDE_SELF = 1   # WDGS_KNN_EXCLUDE_SELF
 
 
 def _as_device(device: HipDevice, array, dtype, width: int, what: str) -> tuple:
@@ -1085,6 +1086,42 @@ class PointIndex:
             if owned:
                 qbuf.destroy()
 
+    def bounds(self) -> dict:
+        """``dict(lo, hi)``: the bounding box of the finite points (f32[3] each; zeros when there is none).  No device work."""
+        lo, hi = (C.c_float * 3)(), (C.c_float * 3)()
+        check(self.device.lib.wdgs_point_index_bounds(self.handle, lo, hi))
+        return dict(lo=np.array(lo, np.float32), hi=np.array(hi, np.float32))
+
+    def kNearestInto(self, encoder: Optional[HipEncoder], queries: HipBuffer, count: int, k: int, maxDistance: float, d2: HipBuffer, index: HipBuffer,
+                     excludeSelf: bool = False, pairs: Optional[HipBuffer] = None) -> None:
+        """Stream-ordered ``kNearest``: for each of the first ``count`` points of ``queries`` the ``k`` (1 to 16) nearest indexed points within ``maxDistance``,
+        ordered by (squared distance, index), into row ``i`` of ``d2`` f32[count, k] and ``index`` u32[count, k]; slots beyond the candidates, and every slot of
+        a non-finite query, hold ``+inf`` and ``0xFFFFFFFF``.  ``excludeSelf``: query ``i`` leaves out the indexed point ``i`` (the self-query, where the
+        queries are the indexed points).  ``pairs`` (optional, 8 bytes): the number of pairs examined is added to it.  No host wait; records."""
+        n, kk = int(count), int(k)
+        if kk < 0 or kk > 0xFFFFFFFF:
+            raise ValueError(f"PointIndex.kNearest: k = {k}")
+        if queries.size < 12 * n or d2.size < 4 * n * kk or index.size < 4 * n * kk or (pairs is not None and pairs.size < 8):
+            raise ValueError(f"PointIndex.kNearest: buffers too small for {n} queries with k = {kk}")
+        check(self.device.lib.wdgs_point_index_k_nearest(self.handle, queries.ptr, n, kk, float(maxDistance), KNN_EXCLUDE_SELF if excludeSelf else 0, d2.ptr, index.ptr,
+                                                         pairs.ptr if pairs is not None else None))
+
+    def kNearest(self, queries, k: int, maxDistance: float, excludeSelf: bool = False) -> dict:
+        """``dict(d2 f32[K, k], index u32[K, k])`` for ``queries`` ([K,3] numpy or a ``HipBuffer``).  Synchronises."""
+        qbuf, n, owned = _as_device(self.device, queries, np.float32, 3, "PointIndex.kNearest: queries")
+        kk = int(k)
+        slots = n * max(0, min(kk, 1024))   # (the library refuses a k outside [1, 16])
+        d2 = self.device.createBuffer(4 * max(slots, 1), "kNearest d2")
+        index = self.device.createBuffer(4 * max(slots, 1), "kNearest index")
+        try:
+            self.kNearestInto(None, qbuf, n, kk, maxDistance, d2, index, excludeSelf)
+            return dict(d2=d2.read(np.float32, count=n * kk).reshape(n, kk), index=index.read(np.uint32, count=n * kk).reshape(n, kk))
+        finally:
+            d2.destroy()
+            index.destroy()
+            if owned:
+                qbuf.destroy()
+
     def destroy(self) -> None:
         if self.destroyed:
             return
@@ -1094,6 +1131,44 @@ class PointIndex:
         if self._owned:
             self._points.destroy()
         self._points = None
+
+
+def initScalesFromNeighbours(device: HipDevice, pointCloud, k: int = 3, maxDistance: Optional[float] = None, minD2: float = 1e-7, count: Optional[int] = None) -> dict:
+    """3DGS's scale initialisation, in place: every point of ``pointCloud`` gets ``log sigma = 0.5 log(max(mean, minD2))`` on all three axes, ``mean`` the
+    mean squared distance to its ``k`` nearest other points within ``maxDistance`` (fewer when fewer are there; a point without any keeps its scales).  The
+    distances are those of the records' fp16 positions, which is what the renderer sees.  ``maxDistance=None``: twice the widest extent of the finite
+    positions, so every other finite point is a candidate -- for a cloud with far outliers pass a cutoff instead.  Only halves 8, 9, 10
+    of each record of ``gaussian_3d_buffer`` change.  Returns ``dict(meanD2 f32[N], found u32[N])``: ``mean`` (``+inf`` without a neighbour) and the number
+    of neighbours it was taken over.  Synchronises."""
+    n = int(pointCloud.num_points) if count is None else int(count)
+    if n < 0 or n > int(pointCloud.num_points):
+        raise ValueError("initScalesFromNeighbours: the count exceeds the point cloud")
+    if pointCloud.gaussian_3d_buffer.size < 24 * n:
+        raise ValueError("initScalesFromNeighbours: the Gaussian buffer is too small for the count")
+    kk = int(k)
+    lib, g = device.lib, pointCloud.gaussian_3d_buffer
+    slots = n * max(0, min(kk, 1024))   # (the library refuses a k outside [1, 16])
+    positions = device.createBuffer(12 * max(n, 1), "neighbour positions")
+    d2 = device.createBuffer(4 * max(slots, 1), "neighbour d2")
+    idx = device.createBuffer(4 * max(slots, 1), "neighbour index")
+    mean = device.createBuffer(4 * max(n, 1), "neighbour mean d2")
+    index = None
+    try:
+        check(lib.wdgs_point_cloud_positions(device.handle, g.ptr, n, positions.ptr))
+        index = PointIndex(device, positions, count=n)
+        if maxDistance is None:
+            b = index.bounds()
+            widest = float(np.max(b["hi"].astype(np.float64) - b["lo"].astype(np.float64)))
+            maxDistance = 2.0 * widest if widest > 0.0 else 1.0
+        index.kNearestInto(None, positions, n, kk, maxDistance, d2, idx, excludeSelf=True)
+        check(lib.wdgs_point_cloud_neighbour_scales(device.handle, g.ptr, n, d2.ptr, kk, float(minD2), mean.ptr))
+        found = np.isfinite(d2.read(np.float32, count=n * kk).reshape(n, kk)).sum(axis=1).astype(np.uint32)
+        return dict(meanD2=mean.read(np.float32, count=n), found=found)
+    finally:
+        if index is not None:
+            index.destroy()
+        for b in (positions, d2, idx, mean):
+            b.destroy()
 
 
 def encodePointDistanceStats(device: HipDevice, d2: HipBuffer, count: int, maxDistance: float, threshold: float, out: HipBuffer) -> None:
