@@ -428,6 +428,48 @@ static napi_value meshSamplerEmit(napi_env env, napi_callback_info info) {  // (
                                             get_u32(env, argv[9])));
     return js_undefined(env);
 }
+// Mesh connected components (include/webdgs.h: wdgs_mesh_components_*; no reference counterpart)
+static napi_value meshComponentsCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_mesh_components* c = nullptr;
+    WDGS_OK_OR_THROW(wdgs_mesh_components_create((wdgs_device*)get_ptr(env, argv[0]), &c));
+    return make_ptr(env, c);
+}
+static napi_value meshComponentsDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_mesh_components_destroy((wdgs_mesh_components*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value meshComponentsLabel(napi_env env, napi_callback_info info) {  // (components, facesPtr, numFaces, numVertices) -> [count, invalidFaces]
+    ARGS(4);
+    uint32_t r[2] = {0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_components_label((wdgs_mesh_components*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]), &r[0], &r[1]));
+    napi_value a; napi_create_array_with_length(env, 2, &a);
+    for (uint32_t i = 0; i < 2; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
+    return a;
+}
+static napi_value meshComponentsGet(napi_env env, napi_callback_info info) {  // (components) -> [faceComponentPtr, vertexComponentPtr, trianglesPtr, verticesPtr]
+    ARGS(1);
+    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    WDGS_OK_OR_THROW(wdgs_mesh_components_get((wdgs_mesh_components*)get_ptr(env, argv[0]), &p[0], &p[1], &p[2], &p[3]));
+    napi_value a; napi_create_array_with_length(env, 4, &a);
+    for (uint32_t i = 0; i < 4; i++) napi_set_element(env, a, i, make_ptr(env, p[i]));
+    return a;
+}
+static napi_value meshComponentsSelect(napi_env env, napi_callback_info info) {  // (components, keep: Uint8Array[C]) -> [keptVertices, keptFaces]
+    ARGS(2);
+    void* data = nullptr; size_t len = 0; napi_typedarray_type tt; napi_value ab; size_t off;
+    NAPI_OK(napi_get_typedarray_info(env, argv[1], &tt, &len, &data, &ab, &off));
+    if (tt != napi_uint8_array) { napi_throw_type_error(env, nullptr, "meshComponentsSelect: keep must be a Uint8Array"); return nullptr; }
+    uint32_t r[2] = {0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_components_select((wdgs_mesh_components*)get_ptr(env, argv[0]), (const uint8_t*)data, (uint32_t)len, &r[0], &r[1]));
+    napi_value a; napi_create_array_with_length(env, 2, &a);
+    for (uint32_t i = 0; i < 2; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
+    return a;
+}
+static napi_value meshComponentsCompact(napi_env env, napi_callback_info info) {
+    // (components, verticesPtr | null, verticesOutPtr | null, facesOutPtr, vertexMapPtr | null, faceMapPtr | null, capacityVertices, capacityFaces)
+    ARGS(8);
+    WDGS_OK_OR_THROW(wdgs_mesh_components_compact((wdgs_mesh_components*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_ptr(env, argv[3]),
+                                                  get_ptr(env, argv[4]), get_ptr(env, argv[5]), get_u32(env, argv[6]), get_u32(env, argv[7])));
+    return js_undefined(env);
+}
 static napi_value pointIndexCreate(napi_env env, napi_callback_info info) {  // (device, pointsPtr, numPoints, cellSize: 0 = chosen by the first query) -> handle
     ARGS(4);
     wdgs_point_index* ix = nullptr;
@@ -1100,6 +1142,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(tsdfVolumeCreate); EXPORT_FN(tsdfVolumeDestroy); EXPORT_FN(tsdfVolumeReset); EXPORT_FN(tsdfVolumeGet); EXPORT_FN(tsdfVolumeGetDims);
     EXPORT_FN(tsdfVolumeIntegrate); EXPORT_FN(tsdfVolumeCountTriangles); EXPORT_FN(tsdfVolumeEmitTriangles);
     EXPORT_FN(meshSamplerCreate); EXPORT_FN(meshSamplerDestroy); EXPORT_FN(meshSamplerCount); EXPORT_FN(meshSamplerEmit);
+    EXPORT_FN(meshComponentsCreate); EXPORT_FN(meshComponentsDestroy); EXPORT_FN(meshComponentsLabel); EXPORT_FN(meshComponentsGet); EXPORT_FN(meshComponentsSelect);
+    EXPORT_FN(meshComponentsCompact);
     EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
     EXPORT_FN(pointDistanceStats);
     EXPORT_FN(pointIndexBounds); EXPORT_FN(pointIndexKNearest); EXPORT_FN(pointCloudPositions); EXPORT_FN(pointCloudNeighbourScales);

@@ -872,7 +872,7 @@ class Trainer {
    *  extractMesh(lo, hi, voxelSize, options), hip.sampleMesh at options.density samples per unit area (default 1 / (voxelSize / 2)^2, a spacing of half a
    *  voxel; options.seed, default 0) and hip.geometryMetrics(samples, reference, maxDistance, threshold).  Returns its object -- accuracy, completeness,
    *  chamfer, precision, recall, fscore and the counts -- with vertices, faces, samples (the mesh's and the sample count) and ms.  extractMesh's isolation
-   *  (fuseDepth's); no alignment is attempted: the reference is taken to be in the scene's frame. */
+   *  (fuseDepth's) and its keepLargest, minTriangles, minFraction; no alignment is attempted: the reference is taken to be in the scene's frame. */
   evaluateGeometry(reference, lo, hi, voxelSize, maxDistance, threshold, options) {
     const o = options || {}, t0 = Date.now();
     const ref = typeof reference === 'string' ? require('./loaders.js').loadPointsPLY(reference) : reference;
@@ -886,14 +886,20 @@ class Trainer {
     return Object.assign(out, { vertices: mesh.vertices.length / 3, faces: mesh.faces.length / 3, samples: samples.count, ms: Date.now() - t0 });
   }
   /** The current model as a triangle mesh of the box [lo, hi]: TSDFVolume.fromBounds, fuseDepth over the views, extractMesh(minWeight); the volume is
-   *  destroyed.  options: { viewIds, split, depthKind, minWeight, truncation, maxWeight, colour }.  loaders.saveMeshPLY writes the result. */
+   *  destroyed.  options: { viewIds, split, depthKind, minWeight, truncation, maxWeight, colour, keepLargest, minTriangles, minFraction }.  With one of the
+   *  last three set the mesh goes through hip.removeSmallComponents (the floaters of a fused mesh are small components of their own) and its object is
+   *  returned; otherwise the raw level set, as before, and nothing more is launched.  loaders.saveMeshPLY writes the result. */
   extractMesh(lo, hi, voxelSize, options) {
     const o = options || {};
     const volume = hip.TSDFVolume.fromBounds(this.device, lo, hi, voxelSize, { truncation: o.truncation, maxWeight: o.maxWeight, colour: o.colour });
+    let mesh;
     try {
       this.fuseDepth(volume, o.viewIds, o.split, o.depthKind);
-      return volume.extractMesh(o.minWeight);
+      mesh = volume.extractMesh(o.minWeight);
     } finally { volume.destroy(); }
+    const unset = (x) => x === undefined || x === null;
+    if (unset(o.keepLargest) && !(o.minTriangles > 0) && !(o.minFraction > 0)) return mesh;
+    return hip.removeSmallComponents(this.device, mesh, { keepLargest: o.keepLargest, minTriangles: o.minTriangles, minFraction: o.minFraction });
   }
 
   // ---------------------------------------------------------------- render contribution and contribution-based pruning (no reference counterpart)

@@ -279,6 +279,29 @@ export function sampleMesh(device: HipDevice, mesh: { vertices: Float32Array | H
                            options?: { asBuffers?: false }): MeshSamples;
 export function sampleMesh(device: HipDevice, mesh: { vertices: Float32Array | HipBuffer; faces: Uint32Array | HipBuffer }, density: number, seed: number,
                            options: { asBuffers: true }): MeshSampleBuffers;
+export interface MeshComponentLabels { count: number; faceComponent: Uint32Array; vertexComponent: Uint32Array; triangles: Uint32Array; vertices: Uint32Array;
+                                       invalidFaces: number }
+export interface ComponentSelection { keepLargest?: number | null; minTriangles?: number; minFraction?: number }
+export interface CompactedMesh extends TriangleMesh { vertexMap: Uint32Array; faceMap: Uint32Array; components: Uint32Array }
+/** Connected components of an indexed mesh on the device (wdgs_mesh_components): label, select, compact.  No reference counterpart. */
+export class MeshComponents {
+  constructor(device: HipDevice);
+  readonly numFaces: number; readonly numVertices: number; readonly count: number; readonly invalidFaces: number;
+  label(faces: HipBuffer | null, numFaces: number, numVertices: number): number;
+  read(): MeshComponentLabels;
+  select(keep: ArrayLike<number | boolean>): { vertices: number; faces: number };
+  compact(vertices: HipBuffer | null, verticesOut: HipBuffer | null, facesOut: HipBuffer, vertexMap?: HipBuffer | null, faceMap?: HipBuffer | null,
+          capacityVertices?: number | null, capacityFaces?: number | null): void;
+  destroy(): void;
+}
+/** The connected components of a mesh: connectivity through shared vertices, components numbered in ascending order of their lowest vertex; a function of
+ *  the mesh alone, bit for bit.  No reference counterpart. */
+export function meshComponents(device: HipDevice, mesh: { vertices: Float32Array | HipBuffer; faces: Uint32Array | HipBuffer }): MeshComponentLabels;
+/** Which components to keep (Uint8Array[C] of 0 / 1), ranked by (triangles descending, component number ascending).  Host side.  No reference counterpart. */
+export function selectComponents(triangles: ArrayLike<number>, options?: ComponentSelection): Uint8Array;
+/** The mesh without the components selectComponents does not keep; colours and keys follow vertexMap.  No reference counterpart. */
+export function removeSmallComponents(device: HipDevice, mesh: { vertices: Float32Array | HipBuffer; faces: Uint32Array | HipBuffer; colours?: Uint8Array | null;
+                                      keys?: BigUint64Array | null }, options?: ComponentSelection): CompactedMesh;
 /** A uniform grid over points for exact nearest-point queries under a cutoff (wdgs_point_index); the cell edge is a speed parameter only.  No reference
  *  counterpart. */
 export class PointIndex {

@@ -672,6 +672,110 @@ function sampleMesh(device, mesh, density, seed, options) {
     if (face) face.destroy();
   }
 }
+// ---------------------------------------------------------------- mesh connected components (include/webdgs.h, DESIGN.md section 16; no reference counterpart)
+/** Connected components of an indexed mesh on the device (wdgs_mesh_components): label cuts the faces into components (a lock-free union-find, one
+ *  wait), select takes the components to keep, compact writes the kept part.  meshComponents and removeSmallComponents are the one-call forms. */
+class MeshComponents {
+  constructor(device) {
+    this.device = device; this.destroyed = false; this.numFaces = 0; this.numVertices = 0; this.count = 0; this.invalidFaces = 0;
+    this.handle = addon.meshComponentsCreate(device.handle);
+  }
+  /** Labels faces u32[numFaces][3] over numVertices vertices and returns the number of components (waits once). */
+  label(faces, numFaces, numVertices) {
+    if (faces && numFaces < 2 ** 31 && faces.size < 12 * numFaces) throw new Error('MeshComponents.label: buffer too small for the faces');
+    const r = addon.meshComponentsLabel(this.handle, faces ? faces.ptr : null, numFaces, numVertices);
+    this.numFaces = numFaces; this.numVertices = numVertices; this.count = r[0]; this.invalidFaces = r[1];
+    return this.count;
+  }
+  /** The last labelling: { count, faceComponent: Uint32Array[F], vertexComponent: Uint32Array[V], triangles: Uint32Array[C], vertices: Uint32Array[C],
+   *  invalidFaces }. */
+  read() {
+    const p = addon.meshComponentsGet(this.handle);
+    const words = (ptr, n) => new Uint32Array(n ? this.device.readBuffer(this.device.view(ptr, 4 * n), 4 * n) : new ArrayBuffer(0));
+    return { count: this.count, faceComponent: words(p[0], this.numFaces), vertexComponent: words(p[1], this.numVertices), triangles: words(p[2], this.count),
+      vertices: words(p[3], this.count), invalidFaces: this.invalidFaces };
+  }
+  /** keep: one entry per component, truthy = kept.  Returns { vertices, faces }, the numbers kept (flags, scans; waits). */
+  select(keep) {
+    const r = addon.meshComponentsSelect(this.handle, Uint8Array.from(keep, (k) => (k ? 1 : 0)));
+    return { vertices: r[0], faces: r[1] };
+  }
+  /** Writes the kept part for the last select: verticesOut f32[V'][3] gathered from vertices (both nullable together), facesOut u32[F'][3] renumbered,
+   *  vertexMap u32[V'], faceMap u32[F'] (nullable).  WDGS_E_CAPACITY, with nothing written, when there is too little room.  Stream-ordered. */
+  compact(vertices, verticesOut, facesOut, vertexMap, faceMap, capacityVertices, capacityFaces) {
+    const room = (pairs) => Math.min(0xFFFFFFFF, ...pairs.filter(([b]) => b).map(([b, s]) => Math.floor(b.size / s)));
+    const cv = capacityVertices === undefined || capacityVertices === null ? room([[verticesOut, 12], [vertexMap, 4]]) : capacityVertices;
+    const cf = capacityFaces === undefined || capacityFaces === null ? room([[facesOut, 12], [faceMap, 4]]) : capacityFaces;
+    for (const [b, s, n] of [[verticesOut, 12, cv], [vertexMap, 4, cv], [facesOut, 12, cf], [faceMap, 4, cf]]) {
+      if (b && n * s > b.size) throw new Error('MeshComponents.compact: the capacity exceeds the buffers');
+    }
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshComponentsCompact(this.handle, ptr(vertices), ptr(verticesOut), ptr(facesOut), ptr(vertexMap), ptr(faceMap), cv, cf);
+  }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.meshComponentsDestroy(this.handle); this.handle = null; }
+}
+/** The connected components of `mesh` ({ vertices, faces } as extractMesh returns them, or as HipBuffers): two vertices are connected when a face names
+ *  both (shared vertices, not shared edges), components are numbered in ascending order of their lowest vertex, 0xFFFFFFFF marks a face that names a
+ *  vertex >= V and a vertex that no face names.  A function of the mesh alone, bit for bit (include/webdgs.h states it). */
+function meshComponents(device, mesh) {
+  const v = asDevice(device, mesh.vertices, Float32Array, 3, 'meshComponents: vertices'), f = asDevice(device, mesh.faces, Uint32Array, 3, 'meshComponents: faces');
+  const comp = new MeshComponents(device);
+  try {
+    comp.label(f.buf, f.rows, v.rows);
+    return comp.read();
+  } finally {
+    comp.destroy();
+    if (v.owned) v.buf.destroy();
+    if (f.owned) f.buf.destroy();
+  }
+}
+/** Which components to keep, from their sizes: ranked by (triangles descending, component number ascending), a component is kept when it is among the
+ *  first keepLargest (null: all), has triangles >= minTriangles and triangles >= minFraction * largest (doubles).  options: { keepLargest, minTriangles,
+ *  minFraction }.  Returns a Uint8Array[C] of 0 / 1.  Host side. */
+function selectComponents(triangles, options) {
+  const o = options || {}, C = triangles.length, keep = new Uint8Array(C);
+  const all = o.keepLargest === undefined || o.keepLargest === null;
+  if (!all && !(o.keepLargest >= 0)) throw new RangeError('selectComponents: keepLargest must be null or >= 0');
+  const ranking = Array.from({ length: C }, (_, c) => c).sort((a, b) => (triangles[b] - triangles[a]) || (a - b));
+  const largest = C ? triangles[ranking[0]] : 0, minTriangles = o.minTriangles || 0, minFraction = o.minFraction || 0;
+  ranking.forEach((c, rank) => {
+    if ((all || rank < o.keepLargest) && triangles[c] >= minTriangles && triangles[c] >= minFraction * largest) keep[c] = 1;
+  });
+  return keep;
+}
+/** `mesh` without the components selectComponents does not keep: { vertices, faces, vertexMap, faceMap, components } and colours / keys gathered through
+ *  vertexMap when the input has them.  Kept faces stay in their order, kept vertices in ascending original index, faces are rewritten to the new indices;
+ *  components holds the kept components' triangle counts.  Keeping everything still drops invalid faces and unreferenced vertices; a second call
+ *  reproduces the first.  options: { keepLargest, minTriangles, minFraction }. */
+function removeSmallComponents(device, mesh, options) {
+  const v = asDevice(device, mesh.vertices, Float32Array, 3, 'removeSmallComponents: vertices');
+  const f = asDevice(device, mesh.faces, Uint32Array, 3, 'removeSmallComponents: faces');
+  const comp = new MeshComponents(device);
+  const outs = [];
+  let out;
+  try {
+    comp.label(f.buf, f.rows, v.rows);
+    const sizes = comp.read().triangles, keep = selectComponents(sizes, options);
+    const kept = comp.select(keep);
+    for (const n of [12 * kept.vertices, 12 * kept.faces, 4 * kept.vertices, 4 * kept.faces]) outs.push(device.createBuffer({ size: Math.max(n, 4), label: 'compacted mesh' }));
+    comp.compact(v.buf, outs[0], outs[1], outs[2], outs[3], kept.vertices, kept.faces);
+    const bytes = (b, n) => (n ? device.readBuffer(b, n) : new ArrayBuffer(0));
+    out = { vertices: new Float32Array(bytes(outs[0], 12 * kept.vertices)), faces: new Uint32Array(bytes(outs[1], 12 * kept.faces)),
+      vertexMap: new Uint32Array(bytes(outs[2], 4 * kept.vertices)), faceMap: new Uint32Array(bytes(outs[3], 4 * kept.faces)),
+      components: sizes.filter((_, c) => keep[c]) };
+  } finally {
+    comp.destroy();
+    if (v.owned) v.buf.destroy();
+    if (f.owned) f.buf.destroy();
+    outs.forEach((b) => b.destroy());
+  }
+  if (mesh.colours !== undefined) {
+    out.colours = mesh.colours ? new Uint8Array(3 * out.vertexMap.length) : null;
+    if (out.colours) out.vertexMap.forEach((old, i) => { for (let a = 0; a < 3; a++) out.colours[3 * i + a] = mesh.colours[3 * old + a]; });
+  }
+  if (mesh.keys !== undefined) out.keys = mesh.keys ? BigUint64Array.from(out.vertexMap, (old) => mesh.keys[old]) : null;
+  return out;
+}
 /** A uniform grid over `points` ([M*3] Float32Array, or a HipBuffer) for exact nearest-point queries under a cutoff (wdgs_point_index).  options:
  *  { cellSize, count }.  cellSize is a speed parameter only -- no result depends on it; without one it is chosen by the first query (its cutoff, or less
  *  for many points), which then finishes the build.  Non-finite points are left out.  The build waits once; queries are stream-ordered. */
@@ -898,7 +1002,7 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
   geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

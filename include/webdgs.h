@@ -726,6 +726,39 @@ int wdgs_point_cloud_neighbour_scales(wdgs_device* dev, void* gaussians_dev, uin
  * finite (WDGS_E_INVALID).  Stream-ordered, no host wait, recordable. */
 int wdgs_point_distance_stats(wdgs_device* dev, const void* d2_f32_dev, uint32_t count, float max_distance, float threshold, void* out_u64x3_dev);
 
+/* ---------------------------------------------------------------- Mesh connected components and small-component removal
+ *
+ * Input: an indexed mesh, faces u32[F][3] over V vertices, 0 <= F, V < 2^31.  A face is VALID when its three indices are < V.  An invalid face joins nothing,
+ * is counted in invalid_faces, gets the component 0xFFFFFFFF, is never kept and never read as an address.  Degenerate faces such as (a, a, a) and (a, a, b) are
+ * valid and connect what they name.  Two vertices are CONNECTED when a valid face names both, taken transitively: connectivity through shared vertices (two
+ * cones that touch at one vertex are one component), not through shared edges.  A COMPONENT is a connectivity class that holds at least one valid face; its
+ * representative is its lowest vertex index, and components are numbered 0 .. C - 1 in ascending order of representative.  A vertex that no valid face names
+ * belongs to no component (0xFFFFFFFF).  Outputs: face_component u32[F], vertex_component u32[V], triangles u32[C] and vertices u32[C] (the valid faces and the
+ * vertices of each component), C and invalid_faces -- each a function of the input alone, bit for bit, whatever the launch geometry or the order in which
+ * threads ran (a lock-free union-find that links the larger root under the smaller; integer atomics only).  No reference counterpart. */
+typedef struct wdgs_mesh_components wdgs_mesh_components;
+int wdgs_mesh_components_create(wdgs_device* dev, wdgs_mesh_components** out);
+int wdgs_mesh_components_destroy(wdgs_mesh_components* components);
+/* Labels the mesh into arrays the object owns (it grows them as needed).  Waits once, to read C and invalid_faces, so it cannot be recorded (WDGS_E_STATE).
+ * WDGS_E_INVALID for null faces with num_faces != 0 and for num_faces or num_vertices >= 2^31.  The faces are read again by compact and must stay as they are
+ * until then. */
+int wdgs_mesh_components_label(wdgs_mesh_components* components, const void* faces_u32_dev, uint32_t num_faces, uint32_t num_vertices, uint32_t* num_components,
+                               uint32_t* invalid_faces);
+/* The device arrays of the last label (each pointer nullable; an array of no elements is handed out as null): valid until the next label or destroy, complete
+ * once the stream has run.  WDGS_E_STATE when no label precedes it.  No device work. */
+int wdgs_mesh_components_get(wdgs_mesh_components* components, void** face_component_u32_dev, void** vertex_component_u32_dev, void** triangles_u32_dev,
+                             void** vertices_u32_dev);
+/* Chooses the components to keep: keep_host u8[C], non-zero = kept, C the last label's count (WDGS_E_INVALID otherwise).  A face is kept when its component is;
+ * a vertex is kept exactly when its component is.  Flags and scans both, waits and returns the numbers of kept vertices and faces; cannot be recorded
+ * (WDGS_E_STATE, also when no label precedes it). */
+int wdgs_mesh_components_select(wdgs_mesh_components* components, const uint8_t* keep_host, uint32_t num_components, uint32_t* kept_vertices, uint32_t* kept_faces);
+/* Writes the kept part of the mesh for the last select: kept faces in their original order with their indices rewritten to the new numbering, faces_out
+ * u32[F'][3]; kept vertices in ascending original index, vertices_out f32[V'][3] gathered from vertices f32[V][3] (both nullable together: no positions);
+ * vertex_map u32[V'] and face_map u32[F'] (each nullable), the old index of each new vertex and face.  WDGS_E_CAPACITY, with nothing written, when
+ * capacity_vertices < V' or capacity_faces < F'; WDGS_E_STATE when no select precedes it.  Stream-ordered, no host wait, recordable. */
+int wdgs_mesh_components_compact(wdgs_mesh_components* components, const void* vertices_f32_dev, void* vertices_out_f32_dev, void* faces_out_u32_dev,
+                                 void* vertex_map_u32_dev, void* face_map_u32_dev, uint32_t capacity_vertices, uint32_t capacity_faces);
+
 #ifdef __cplusplus
 }
 #endif

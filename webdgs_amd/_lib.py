@@ -159,6 +159,12 @@ SIGNATURES = {
     "wdgs_mesh_sampler_destroy": (_I, [_P]),
     "wdgs_mesh_sampler_count": (_I, [_P, _P, _U, _P, _U, _F, _U, C.POINTER(C.c_uint64)]),
     "wdgs_mesh_sampler_emit": (_I, [_P, _P, _U, _P, _U, _F, _U, _P, _P, _U]),
+    "wdgs_mesh_components_create": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_mesh_components_destroy": (_I, [_P]),
+    "wdgs_mesh_components_label": (_I, [_P, _P, _U, _U, C.POINTER(_U), C.POINTER(_U)]),
+    "wdgs_mesh_components_get": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "wdgs_mesh_components_select": (_I, [_P, _P, _U, C.POINTER(_U), C.POINTER(_U)]),
+    "wdgs_mesh_components_compact": (_I, [_P, _P, _P, _P, _P, _P, _U, _U]),
     "wdgs_point_index_create": (_I, [_P, _P, C.c_uint64, _F, C.POINTER(_P)]),
     "wdgs_point_index_destroy": (_I, [_P]),
     "wdgs_point_index_reserve_queries": (_I, [_P, _U]),

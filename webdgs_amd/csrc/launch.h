@@ -104,6 +104,20 @@ int launch_point_bounds(wdgs_device* dev, const float* points, u32 M, u32* bound
 // out3: u64 { n_found, n_within, sum_q }, cleared and added to
 int launch_point_distance_stats(wdgs_device* dev, const float* d2, u32 K, float max_distance, float threshold, unsigned long long* out3);
 
+// ---- meshclean.hip.  faces u32[F][3] over V vertices; every array below u32, one word per vertex, face or component
+// parent[V], written: the union-find after all links (not yet flat); invalid_faces: one word, cleared and counted into
+int launch_mesh_hook(wdgs_device* dev, const u32* faces, u32 F, u32 V, u32* parent, u32* invalid_faces);
+// parent[V] becomes every vertex's root; used[V], written: 1 at the root of every valid face
+int launch_mesh_roots(wdgs_device* dev, const u32* faces, u32 F, u32 V, u32* parent, u32* used);
+// number[V]: the exclusive scan of used; vertex_component[V] and face_component[F] written; vertex_counts and triangle_counts u32[C], added to
+int launch_mesh_label(wdgs_device* dev, const u32* faces, u32 F, u32 V, const u32* root, const u32* used, const u32* number, u32* vertex_component, u32* face_component,
+                      u32* vertex_counts, u32* triangle_counts);
+// flags[n] = keep[component[i]] (0 for an element without a component); keep u32[C]
+int launch_mesh_keep_flags(wdgs_device* dev, u32 n, const u32* component, const u32* keep, u32 C, u32* flags);
+// the flags of launch_mesh_keep_flags and their exclusive scans; positions f32[V][3] and positions_out (nullable together), vertex_map, face_map nullable
+int launch_mesh_emit(wdgs_device* dev, const u32* faces, u32 F, u32 V, const u32* vertex_flags, const u32* vertex_offsets, const u32* face_flags, const u32* face_offsets,
+                     const float* positions, float* positions_out, u32* vertex_map, u32* faces_out, u32* face_map);
+
 // ---- loss.hip, dssim.hip. pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
 int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
                      const u32* acc_dirty);

@@ -1035,6 +1035,137 @@ def sampleMesh(device: HipDevice, mesh: dict, density: float, seed: int = 0, asB
                 b.destroy()
 
 
+# ----------------------------------------------------------------------------- mesh connected components (no reference counterpart)
+class MeshComponents:
+    """Connected components of an indexed mesh on the device (``wdgs_mesh_components``): ``label`` cuts the faces into components (a lock-free
+    union-find, one wait), ``select`` takes the components to keep, ``compact`` writes the kept part.  ``meshComponents`` and ``removeSmallComponents``
+    are the one-call forms; include/webdgs.h states the definitions."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        self.numFaces = self.numVertices = self.count = self.invalidFaces = 0
+        h = C.c_void_p()
+        check(device.lib.wdgs_mesh_components_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def label(self, faces: HipBuffer, numFaces: int, numVertices: int) -> int:
+        """Labels ``faces`` u32[numFaces][3] over ``numVertices`` vertices and returns the number of components (waits once)."""
+        if not (0 <= int(numFaces) < 2 ** 32 and 0 <= int(numVertices) < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshComponents.label: bad counts {numFaces}, {numVertices}")
+        if faces is not None and int(numFaces) < 2 ** 31 and faces.size < 12 * int(numFaces):
+            raise ValueError("MeshComponents.label: buffer too small for the faces")
+        n, bad = C.c_uint32(0), C.c_uint32(0)
+        check(self.device.lib.wdgs_mesh_components_label(self.handle, faces.ptr if faces is not None else None, int(numFaces), int(numVertices), C.byref(n), C.byref(bad)))
+        self.numFaces, self.numVertices, self.count, self.invalidFaces = int(numFaces), int(numVertices), int(n.value), int(bad.value)
+        return self.count
+
+    def read(self) -> dict:
+        """The last labelling as numpy: ``dict(count, faceComponent u32[F], vertexComponent u32[V], triangles u32[C], vertices u32[C], invalidFaces)``."""
+        p = [C.c_void_p() for _ in range(4)]
+        check(self.device.lib.wdgs_mesh_components_get(self.handle, *[C.byref(x) for x in p]))
+        sizes = (self.numFaces, self.numVertices, self.count, self.count)
+        arrays = [self.device.view(x.value, 4 * n).read(np.uint32, count=n) if n else np.zeros(0, np.uint32) for x, n in zip(p, sizes)]
+        return dict(count=self.count, faceComponent=arrays[0], vertexComponent=arrays[1], triangles=arrays[2], vertices=arrays[3], invalidFaces=self.invalidFaces)
+
+    def select(self, keep) -> tuple:
+        """``keep``: bool[C].  Returns ``(keptVertices, keptFaces)`` (flags, scans; waits)."""
+        k = np.ascontiguousarray(np.asarray(keep).astype(bool).reshape(-1), np.uint8)
+        nv, nf = C.c_uint32(0), C.c_uint32(0)
+        check(self.device.lib.wdgs_mesh_components_select(self.handle, k.ctypes.data if k.size else None, int(k.size), C.byref(nv), C.byref(nf)))
+        return int(nv.value), int(nf.value)
+
+    def compact(self, vertices: Optional[HipBuffer], verticesOut: Optional[HipBuffer], facesOut: HipBuffer, vertexMap: Optional[HipBuffer] = None,
+                faceMap: Optional[HipBuffer] = None, capacityVertices: Optional[int] = None, capacityFaces: Optional[int] = None) -> None:
+        """Writes the kept part for the last ``select``: ``verticesOut`` f32[V'][3] gathered from ``vertices``, ``facesOut`` u32[F'][3] renumbered,
+        ``vertexMap`` u32[V'], ``faceMap`` u32[F'].  ``CapacityError``, with nothing written, when there is too little room.  Stream-ordered."""
+        cv = min([b.size // s for b, s in ((verticesOut, 12), (vertexMap, 4)) if b is not None] or [2 ** 32 - 1]) if capacityVertices is None else int(capacityVertices)
+        cf = min([b.size // s for b, s in ((facesOut, 12), (faceMap, 4)) if b is not None] or [2 ** 32 - 1]) if capacityFaces is None else int(capacityFaces)
+        for b, s, n in ((verticesOut, 12, cv), (vertexMap, 4, cv), (facesOut, 12, cf), (faceMap, 4, cf)):
+            if b is not None and n * s > b.size:
+                raise ValueError("MeshComponents.compact: the capacity exceeds the buffers")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_components_compact(self.handle, ptr(vertices), ptr(verticesOut), ptr(facesOut), ptr(vertexMap), ptr(faceMap), cv, cf))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_mesh_components_destroy(self.handle)
+        self.handle = None
+
+
+def meshComponents(device: HipDevice, mesh: dict) -> dict:
+    """The connected components of ``mesh`` -- the dict ``extractMesh`` and ``loaders.loadMeshPLY`` return, or ``dict(vertices=HipBuffer, faces=HipBuffer)``
+    on the device: ``dict(count, faceComponent u32[F], vertexComponent u32[V], triangles u32[C], vertices u32[C], invalidFaces)``.  Two vertices are
+    connected when a face names both (shared vertices, not shared edges: the rules differ only at pinch points of a welded mesh; a mesh with duplicated
+    vertices falls apart into its triangles); components are numbered in ascending order of their lowest vertex; ``0xFFFFFFFF`` marks a face that names
+    a vertex ``>= V`` and a vertex that no face names.  A function of the mesh alone, bit for bit (include/webdgs.h states it)."""
+    vbuf, nv, own_v = _as_device(device, mesh["vertices"], np.float32, 3, "meshComponents: vertices")
+    fbuf, nf, own_f = _as_device(device, mesh["faces"], np.uint32, 3, "meshComponents: faces")
+    comp = MeshComponents(device)
+    try:
+        comp.label(fbuf, nf, nv)
+        return comp.read()
+    finally:
+        comp.destroy()
+        for b, own in ((vbuf, own_v), (fbuf, own_f)):
+            if own:
+                b.destroy()
+
+
+def _is_default_selection(keepLargest, minTriangles, minFraction) -> bool:
+    return keepLargest is None and not minTriangles > 0 and not minFraction > 0
+
+
+def selectComponents(triangles, keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0) -> np.ndarray:
+    """Which components to keep, ``bool[C]``, from their sizes: ranked by (triangles descending, component number ascending), a component is kept when it
+    is among the first ``keepLargest`` (``None``: all), has ``triangles >= minTriangles`` and ``triangles >= minFraction * largest`` (the product formed
+    and compared in float64).  Host side."""
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1)
+    keep = np.zeros(t.size, bool)
+    if t.size == 0:
+        return keep
+    if keepLargest is not None and int(keepLargest) < 0:
+        raise ValueError("selectComponents: keepLargest must be None or >= 0")
+    order = np.lexsort((np.arange(t.size), -t.astype(np.int64)))
+    first = order if keepLargest is None else order[: int(keepLargest)]
+    keep[first] = True
+    keep &= t.astype(np.int64) >= int(minTriangles)
+    keep &= t.astype(np.float64) >= np.float64(minFraction) * np.float64(t.max())
+    return keep
+
+
+def removeSmallComponents(device: HipDevice, mesh: dict, keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0) -> dict:
+    """``mesh`` without the components ``selectComponents`` does not keep: ``dict(vertices f32[V',3], faces u32[F',3], vertexMap u32[V'], faceMap u32[F'],
+    components u32[kept])`` and ``colours`` / ``keys`` gathered through ``vertexMap`` when the input has them.  Kept faces stay in their order, kept
+    vertices in ascending original index (a vertex is kept exactly when its component is), faces are rewritten to the new indices; ``components`` holds
+    the kept components' triangle counts in component order.  Keeping everything still drops invalid faces and unreferenced vertices; a second call
+    reproduces the first.  Labelled, selected and compacted on the device (``MeshComponents``); the selection itself is the host's."""
+    vbuf, nv, own_v = _as_device(device, mesh["vertices"], np.float32, 3, "removeSmallComponents: vertices")
+    fbuf, nf, own_f = _as_device(device, mesh["faces"], np.uint32, 3, "removeSmallComponents: faces")
+    comp = MeshComponents(device)
+    outs = []
+    try:
+        comp.label(fbuf, nf, nv)
+        sizes = comp.read()["triangles"]
+        keep = selectComponents(sizes, keepLargest, minTriangles, minFraction)
+        kv, kf = comp.select(keep)
+        outs = [device.createBuffer(s * max(n, 1), "compacted mesh") for s, n in ((12, kv), (12, kf), (4, kv), (4, kf))]
+        comp.compact(vbuf, outs[0], outs[1], outs[2], outs[3], kv, kf)
+        out = dict(vertices=outs[0].read(np.float32, count=3 * kv).reshape(kv, 3), faces=outs[1].read(np.uint32, count=3 * kf).reshape(kf, 3),
+                   vertexMap=outs[2].read(np.uint32, count=kv), faceMap=outs[3].read(np.uint32, count=kf), components=sizes[keep])
+    finally:
+        comp.destroy()
+        for b, own in [(vbuf, own_v), (fbuf, own_f)] + [(b, True) for b in outs]:
+            if own:
+                b.destroy()
+    for name in ("colours", "keys"):
+        if name in mesh:
+            out[name] = None if mesh[name] is None else np.ascontiguousarray(np.asarray(mesh[name])[out["vertexMap"]])
+    return out
+
+
 class PointIndex:
     """A uniform grid over ``points`` ([M,3] float32 as numpy, or a ``HipBuffer``) for exact nearest-point queries under a cutoff (``wdgs_point_index``).
     ``cellSize`` is a speed parameter only -- no result depends on it; ``None``: chosen by the first query (its cutoff, or less for many points), which then

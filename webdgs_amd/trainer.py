@@ -1052,23 +1052,32 @@ class Trainer:
         return ids
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
-                    **volumeOptions) -> dict:
+                    keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **volumeOptions) -> dict:
         """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
-        ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result."""
+        ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result.
+
+        ``keepLargest``, ``minTriangles``, ``minFraction``: with any of them set, the mesh goes through ``ops.removeSmallComponents`` -- the floaters of
+        a fused mesh are small components of their own -- and its dict is returned (``vertexMap``, ``faceMap`` and ``components`` added).  With the
+        defaults the raw level set is returned as before and nothing more is launched."""
         volume = ops.TSDFVolume.fromBounds(self.device, lo, hi, voxelSize, **volumeOptions)
         try:
             self.fuseDepth(volume, viewIds, split, depthKind)
-            return volume.extractMesh(minWeight)
+            mesh = volume.extractMesh(minWeight)
         finally:
             volume.destroy()
+        if ops._is_default_selection(keepLargest, minTriangles, minFraction):
+            return mesh
+        return ops.removeSmallComponents(self.device, mesh, keepLargest, minTriangles, minFraction)
 
     # ------------------------------------------------------------------ mesh accuracy against a reference point set (DESIGN.md section 14; no reference counterpart)
     def evaluateGeometry(self, reference, lo, hi, voxelSize: float, maxDistance: float, threshold: float, density: Optional[float] = None, seed: int = 0,
-                         **extractMeshOptions) -> dict:
+                         keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **extractMeshOptions) -> dict:
         """Scores the current model's geometry against ``reference`` -- an ``[M,3]`` array of surface points, or the path of a PLY that holds them:
         ``extractMesh(lo, hi, voxelSize, **extractMeshOptions)``, ``ops.sampleMesh`` at ``density`` samples per unit area (``None``: ``1 / (voxelSize / 2)^2``,
         a spacing of half a voxel) and ``ops.geometryMetrics(samples, reference, maxDistance, threshold)``.  Returns its dict -- accuracy, completeness,
         chamfer, precision, recall, fscore and the counts -- with ``vertices``, ``faces``, ``samples`` (the mesh's and the sample count) and ``ms``.
+
+        ``keepLargest``, ``minTriangles`` and ``minFraction`` are ``extractMesh``'s: the published numbers are those of a mesh without its floaters.
 
         ``extractMesh``'s isolation (``fuseDepth``'s): the pipeline is drained, no RNG draw, no training pass, no recording dropped, the iteration counter
         untouched.  No alignment is attempted: the reference is taken to be in the scene's frame."""
@@ -1078,7 +1087,7 @@ class Trainer:
             raise ValueError(f"evaluateGeometry: the reference must be [M, 3] points, got {ref.shape}")
         if density is None:
             density = 1.0 / (0.5 * float(voxelSize)) ** 2
-        mesh = self.extractMesh(lo, hi, voxelSize, **extractMeshOptions)
+        mesh = self.extractMesh(lo, hi, voxelSize, keepLargest=keepLargest, minTriangles=minTriangles, minFraction=minFraction, **extractMeshOptions)
         samples = ops.sampleMesh(self.device, mesh, density, seed, asBuffers=True)
         try:
             n = samples["count"]
