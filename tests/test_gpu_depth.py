@@ -47,6 +47,11 @@ def _assert_weight_sum_is_alpha(pipe, got, what):
 def test_depth_images_match_float64(hip_device, name, compat):
     cfg = scene_config(name)
     g, sh, cam = harness.scene(cfg)
+    _assert_depth_images_match_float64(hip_device, cfg, g, sh, cam, name, compat)
+
+
+def _assert_depth_images_match_float64(hip_device, cfg, g, sh, cam, name, compat=False):
+    """The three depth images of one scene under one camera against depth64 fed with the GPU's own forward stages.  Returns the walk's statistics."""
     pipe = harness.HipPipeline(hip_device, cfg, g, sh, cam, compat_caps=compat)
     try:
         got = _depth(pipe)
@@ -70,6 +75,7 @@ def test_depth_images_match_float64(hip_device, name, compat):
         assert np.all(stats["probe_in_box"][(got["median"] != 0)]), f"{name}: a median that is no record's z"
         # weight sum against float64 (the bit-level check above is the sharp one)
         assert np.abs(got["weight_sum"].astype(np.float64) - A)[keep].max() <= 1e-6
+        return stats
     finally:
         pipe.destroy()
 

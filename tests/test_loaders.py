@@ -99,6 +99,16 @@ def test_camera_json_and_uniform_block_match_the_synthetic_builder():
         got = loaders.cameraUniforms(cam)
         assert np.allclose(got, blk, rtol=2e-6, atol=2e-6)
         assert got[66] == got[67], "fx is ignored: focal.x = focal.y (SURVEY Q18)"
+    # ... and under the camera zoo: rolled, steep, behind, inside, far, looking away, close (nine non-zero rotation entries, translations up to 50)
+    import camzoo
+    zcfg = camzoo.ZOO_CFG
+    for name in camzoo.NAMES:
+        view = camzoo.view_matrix(name)
+        js = json.dumps([dict(id=1, img_name=name, width=zcfg.width, height=zcfg.height, fx=77.0, fy=zcfg.fy, position=list(camzoo.poses()[name][0]),
+                              rotation=view[:3, :3].tolist())])
+        got = loaders.cameraUniforms(loaders.loadCameraJson(js.encode())[0])
+        assert got.shape == (68,) and np.allclose(got, camzoo.camera(name), rtol=2e-6, atol=2e-6), name
+        assert np.array_equal(got[0:12].reshape(3, 4)[:, :3], camzoo.camera(name)[0:12].reshape(3, 4)[:, :3]), f"{name}: the rotation is copied, not computed"
     # default fovY = 45 degrees when intrinsics are missing (camera.ts:134)
     d = loaders.cameraUniforms(dict(position=np.zeros(3, np.float32), rotation=np.eye(4, dtype=np.float32).reshape(-1)), 200, 100)
     assert math.isclose(d[67], 0.5 * 100 / math.tan(math.radians(22.5)), rel_tol=1e-6)
