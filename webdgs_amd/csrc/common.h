@@ -132,6 +132,26 @@ __device__ __forceinline__ u32 xcd_contiguous(u32 b, u32 g) {
     return k * q + min(k, r) + j;
 }
 
+// The lanes of the wave, among those set in `among`, whose `digit` agrees with this lane's in its low BITS bits: one ballot per bit (the ranking
+// step of the stable counting passes: sort.hip, project.hip).  Kept on the mask's 32-bit halves, with the lane's bit spread over a word (0 or ~0):
+// a bit then costs a bit-field extract, a compare and an xnor + and per half.  Written on the 64-bit mask as `m &= bit ? bal : ~bal` it compiled to
+// ten vector instructions per bit, and at E = 6 M the ranking rounds are what the scatter kernels' waves spend their issue slots on.
+template <u32 BITS>
+__device__ __forceinline__ unsigned long long match_digit(u32 digit, unsigned long long among) {
+    u32 lo = (u32)among, hi = (u32)(among >> 32);
+#pragma unroll
+    for (u32 b = 0; b < BITS; b++) {
+        const bool bit = (digit & (1u << b)) != 0u;
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(bit);
+        const u32 x = bit ? 0xFFFFFFFFu : 0u;
+        lo &= ~((u32)bal ^ x);
+        hi &= ~((u32)(bal >> 32) ^ x);
+    }
+    return ((unsigned long long)hi << 32) | lo;
+}
+// How many of the lanes set in m lie below this one.
+__device__ __forceinline__ u32 lanes_below(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); }
+
 static inline u32 ceil_div(u32 a, u32 b) { return (a + b - 1u) / b; }
 // Number of bits needed to represent v: the forward pass's tile passes sort bits_for(total_tiles) bits of the key's tile field (api.hip; sort.hip's
 // test hook asks with the same function)

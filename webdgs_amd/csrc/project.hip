@@ -492,7 +492,6 @@ __global__ __launch_bounds__(256) void emit_scatter_kernel(u32 n, const u32* __r
     s_inv[threadIdx.x] = 0xFFFFFFFFu / width + 1u;  // floor(k / width) == umulhi(k, inv) for k * width < 2^32 (k <= 2048 here)
     s_dep[threadIdx.x] = depth16;
     s_gbase[col] = tbase + off_c;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const u32 wg_first = wg * 256u;
     auto column_of = [&](u32 key) { const u32 t = (key >> 16u) - 1u; return t - __umulhi(t, inv_ntx) * ntx; };
     for (u32 c0 = 0u; c0 < total; c0 += ES_CHUNK) {
@@ -546,16 +545,9 @@ __global__ __launch_bounds__(256) void emit_scatter_kernel(u32 n, const u32* __r
                 kk[j] = valid ? (((tile_id + 1u) << 16u) | s_dep[o]) : 0xFFFFFFFFu;
                 vv[j] = wg_first + o;
                 const u32 digit = valid ? cx : 0u;
-                unsigned long long m = __ballot(valid);
-#pragma unroll
-                for (u32 b = 0; b < 8; b++) {
-                    const bool bit = (digit >> b) & 1u;
-                    const unsigned long long bal = __ballot(bit);
-                    m &= bit ? bal : ~bal;
-                }
-                // m = valid lanes of this wave holding the same column
+                const unsigned long long m = match_digit<8>(digit, __ballot(valid));   // valid lanes of this wave holding the same column
                 const u32 pre_c = whist[wave][digit];
-                const u32 below = (u32)__popcll(m & lt_mask);
+                const u32 below = lanes_below(m);
                 rk[j] = pre_c + below;
                 if (valid && below == 0u) whist[wave][digit] = pre_c + (u32)__popcll(m);  // group leader bumps the wave counter
             }

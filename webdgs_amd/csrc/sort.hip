@@ -179,8 +179,8 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u32* _
 
     // Wave w owns keys [base + w*1024, base + (w+1)*1024) in 16 rounds of 64 consecutive keys: the order
     // (wave, round, lane) is the input order, which is what makes the pass stable.
-    u32 k[ITEMS], v[ITEMS], rk[ITEMS];
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    // (ranks -- below 64 * ITEMS -- and later positions in the partition -- below TILE -- are held two to a register: see the staging below)
+    u32 k[ITEMS], v[ITEMS], rk2[ITEMS / 2];
 #pragma unroll
     for (u32 j = 0; j < ITEMS; j++) {
         const u32 i = base + wave * (ITEMS * 64u) + j * 64u + lane;
@@ -193,17 +193,13 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u32* _
         const u32 i = base + wave * (ITEMS * 64u) + j * 64u + lane;
         const bool valid = i < count;
         const u32 digit = valid ? digit_of(k[j]) : 0u;
-        unsigned long long m = __ballot(valid);
-#pragma unroll
-        for (u32 b = 0; b < 8; b++) {
-            const bool bit = (digit >> b) & 1u;
-            const unsigned long long bal = __ballot(bit);
-            m &= bit ? bal : ~bal;
-        }
-        // m = valid lanes of this wave holding the same digit
+        const unsigned long long m = match_digit<8>(digit, __ballot(valid));   // valid lanes of this wave holding the same digit
         const u32 pre = whist[wave][digit];
-        const u32 below = (u32)__popcll(m & lt_mask);
-        rk[j] = pre + below;
+        const u32 below = lanes_below(m);
+        rk2[j / 2u] = (j & 1u) ? (rk2[j / 2u] | ((pre + below) << 16u)) : (pre + below);
+        // (the rank is wanted in its register HERE: left alone, the compiler keeps every round's counter and match mask until the loop is over and adds
+        // and packs them there -- three registers more per round, 98 VGPRs in all instead of 62, whatever the packing saves)
+        asm volatile("" : "+v"(rk2[j / 2u]));
         if (valid && below == 0u) whist[wave][digit] = pre + (u32)__popcll(m);  // group leader bumps the wave counter
         // wave-private LDS words: the next round's read is ordered after this write within the wave
     }
@@ -211,8 +207,13 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u32* _
     // Reorder the partition in LDS so that it leaves in digit runs: position in the partition's sorted order =
     // (digits below) + (same digit in earlier waves) + rank in own wave.  A direct scatter writes each run 4 B at a time from 16
     // different wave-instructions (write amplification 1.9x measured); from LDS consecutive lanes write consecutive addresses.
-    __shared__ u32 s_keys[TILE];
-    __shared__ u32 s_vals[TILE];
+    //
+    // ONE staging array, used twice: the keys are reordered and written out, then the values go through the same words.  What the values'
+    // write-out needs of the keys -- each written element's digit -- stays with the thread that wrote the key, a byte each (dmask <= 255), and
+    // the positions in the partition replace the ranks, two to a register.  With a second array the ITEMS = 16 form took 37 KB of LDS and 98
+    // VGPRs: four workgroups per CU, 1024 on the chip, and c3's 1511 partitions ran as one full round and one half empty.  At 21 KB and 62
+    // VGPRs seven fit (1792 resident): one round.
+    __shared__ u32 s_stage[TILE];
     __shared__ u32 s_gdelta[RADIX];   // global base of digit d minus its start in the partition's sorted order
     __shared__ u32 s_wsum[SORT_THREADS / 64];
     {
@@ -263,25 +264,42 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const u32* _
         const u32 i = base + wave * (ITEMS * 64u) + j * 64u + lane;
         if (i < count) {
             const u32 digit = digit_of(k[j]);
-            const u32 lpos = whist[wave][digit] + rk[j];
-            s_keys[lpos] = k[j];
-            s_vals[lpos] = v[j];
+            const u32 lpos = whist[wave][digit] + ((rk2[j / 2u] >> ((j & 1u) * 16u)) & 0xFFFFu);
+            s_stage[lpos] = k[j];
+            rk2[j / 2u] = (j & 1u) ? ((rk2[j / 2u] & 0xFFFFu) | (lpos << 16u)) : ((rk2[j / 2u] & 0xFFFF0000u) | lpos);
         }
     }
     __syncthreads();
     const u32 n_here = min(TILE, count - base);
-#pragma unroll 4
-    for (u32 e = threadIdx.x; e < n_here; e += SORT_THREADS) {
-        const u32 key = s_keys[e];
-        const u32 pos = s_gdelta[digit_of(key)] + e;
+    u32 dg4[ITEMS / 4];   // the digits of the elements this thread writes out, four to a register
+#pragma unroll
+    for (u32 r = 0; r < ITEMS; r++) {
+        const u32 e = r * SORT_THREADS + threadIdx.x;
+        if ((r & 3u) == 0u) dg4[r / 4u] = 0u;
+        if (e >= n_here) continue;
+        const u32 key = s_stage[e];
+        const u32 digit = digit_of(key);
+        const u32 pos = s_gdelta[digit] + e;
+        dg4[r / 4u] |= digit << ((r & 3u) * 8u);
         keys_out[pos] = key;
-        vals_out[pos] = s_vals[e];
         // In the partition's sorted order the entries of one tile are neighbours (same digit, and the input of this pass is ordered by
         // the tile's low bits), so a tile's first entry here is the one whose predecessor belongs to another tile: about 130 per
         // partition.  The smallest of those positions over all partitions is where the tile starts.
         // (a key whose tile field is 0 or beyond the grid cannot come out of emit; the bound keeps a corrupted list -- entries counted but never
         // written -- from turning into an address 16 GB past the table)
-        if (ranges_mode == 2u && (e == 0u || (s_keys[e - 1u] >> 16u) != (key >> 16u)) && (key >> 16u) - 1u < total_tiles) atomicMin(&ranges[(key >> 16u) - 1u], pos);
+        if (ranges_mode == 2u && (e == 0u || (s_stage[e - 1u] >> 16u) != (key >> 16u)) && (key >> 16u) - 1u < total_tiles) atomicMin(&ranges[(key >> 16u) - 1u], pos);
+    }
+    __syncthreads();   // every key has been read: the values take their places
+#pragma unroll
+    for (u32 j = 0; j < ITEMS; j++) {
+        const u32 i = base + wave * (ITEMS * 64u) + j * 64u + lane;
+        if (i < count) s_stage[(rk2[j / 2u] >> ((j & 1u) * 16u)) & 0xFFFFu] = v[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (u32 r = 0; r < ITEMS; r++) {
+        const u32 e = r * SORT_THREADS + threadIdx.x;
+        if (e < n_here) vals_out[s_gdelta[(dg4[r / 4u] >> ((r & 3u) * 8u)) & 0xFFu] + e] = s_stage[e];
     }
 }
 
@@ -338,7 +356,6 @@ __device__ __forceinline__ void seg_pass_regs(const u32 (&kk)[SEG_ROUNDS], const
     static_assert(BINS <= SEG_BINS && BINS % SEG_THREADS == 0, "digit width");
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const u32 rounds = per_wave / 64u;  // <= SEG_ROUNDS, uniform per workgroup
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
     auto digit_of = [&](u32 key) { return (((key & 0xFFFFu) - sub) >> shift) & (BINS - 1u); };
 #pragma unroll
     for (u32 w = 0; w < SEG_THREADS / 64; w++)
@@ -352,15 +369,9 @@ __device__ __forceinline__ void seg_pass_regs(const u32 (&kk)[SEG_ROUNDS], const
             const u32 i = wave * per_wave + j * 64u + lane;
             const bool valid = i < n;
             const u32 digit = digit_of(kk[j]);
-            unsigned long long m = __ballot(valid);
-#pragma unroll
-            for (u32 b = 0; b < BITS; b++) {
-                const bool bit = (digit >> b) & 1u;
-                const unsigned long long bal = __ballot(bit);
-                m &= bit ? bal : ~bal;
-            }
+            const unsigned long long m = match_digit<BITS>(digit, __ballot(valid));
             const u32 pre = whist[wave][digit];
-            const u32 below = (u32)__popcll(m & lt_mask);
+            const u32 below = lanes_below(m);
             rk[j] = pre + below;
             if (valid && below == 0u) whist[wave][digit] = (seg_hist_t)(pre + (u32)__popcll(m));
         }
@@ -433,7 +444,6 @@ WD_DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" :::
 __device__ void seg_pass_global(const u32* __restrict__ src_k, const u32* __restrict__ src_v, u32* __restrict__ dst_k, u32* __restrict__ dst_v, u32 n,
                                 u32 shift, seg_hist_t (*whist)[SEG_BINS], u32* s_base /*[RADIX]*/, u32* s_wsum) {
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
     s_base[threadIdx.x] = 0u;
     __syncthreads();
     for (u32 i0 = threadIdx.x; i0 < n; i0 += 4u * SEG_THREADS) {   // (four keys per thread and trip, requested together)
@@ -485,14 +495,8 @@ __device__ void seg_pass_global(const u32* __restrict__ src_k, const u32* __rest
         for (u32 j = 0; j < 4u; j++) {
             const bool valid = c0 + j * SEG_THREADS + threadIdx.x < n;
             const u32 digit = (kq[j] >> shift) & (RADIX - 1u);
-            unsigned long long m = __ballot(valid);
-#pragma unroll
-            for (u32 b = 0; b < 8; b++) {
-                const bool bit = (digit >> b) & 1u;
-                const unsigned long long bal = __ballot(bit);
-                m &= bit ? bal : ~bal;
-            }
-            below[j] = (u32)__popcll(m & lt_mask);
+            const unsigned long long m = match_digit<8>(digit, __ballot(valid));
+            below[j] = lanes_below(m);
             group[j] = (valid && below[j] == 0u) ? (u32)__popcll(m) : 0u;
         }
         lds_barrier();   // the counts are cleared
