@@ -409,6 +409,32 @@ def test_k15_loss_gradient_is_the_formula(orc, lam):
     assert np.abs(got[..., :3]).max() <= lam[0] + lam[1] + lam[2] + 1e-6
 
 
+@pytest.mark.parametrize("lam", [(0.8, 0.0, 0.2), (0.5, 0.3, 0.2), (0.0, 0.0, 1.0)], ids=["default", "with-l2", "dssim-only"])
+@pytest.mark.parametrize("w,h", [(7, 5), (65, 43)])
+@pytest.mark.parametrize("kind", ["noise", "anti", "saturated"])
+def test_k15_loss_gradient_is_the_formula_on_crafted_pairs(orc, kind, w, h, lam):
+    """The same comparison, same 2e-6, on the crafted pairs the GPU kernel is compared with the oracle on (tests/lossimages.py): uncorrelated noise,
+    windows of negative covariance (SSIM near -1, the factor 0.5 (1 - SSIM) near 1) and saturated differences that reach the image's edges, at a
+    size smaller than two windows and at one that is no multiple of anything."""
+    import lossimages
+    pred, targ = lossimages.pair(kind, w, h, seed=w * 7919 + h * 31)
+    cfg = orc.training_config(lambda_l1=lam[0], lambda_l2=lam[1], lambda_dssim=lam[2])
+    got = orc.loss_grad(pred, targ, cfg)
+    want, ssim = _loss_gradient_fp64(pred, targ, float(cfg[0]), float(cfg[1]), float(cfg[2]), float(cfg[3]), float(cfg[4]))
+    worst = float(np.abs(got - want).max())
+    print(f"K15 {kind} {w}x{h} {lam}: max |oracle - f64| = {worst:.3e}, SSIM in [{ssim.min():.6f}, {ssim.max():.6f}]")
+    assert got.shape == want.shape and np.all(got[..., 3] == 1.0)
+    assert worst < 2e-6, worst
+    same = pred[..., :3] == targ[..., :3]
+    assert np.all(got[..., :3][same] == 0)                        # sign(0) = 0, and every other term has the factor d = 0
+    assert ssim.min() >= -1 - 1e-9 and ssim.max() <= 1 + 1e-9
+    assert np.abs(got[..., :3]).max() <= lam[0] + lam[1] + lam[2] + 1e-6
+    if kind == "anti":
+        assert ssim.min() < -0.9, ssim.min()                     # the case is there for the negative branch: it must reach it
+    if kind == "saturated":
+        assert same[:, :2].all() and (w <= 2 or not same[:, 2:].any())
+
+
 # ----------------------------------------------------------------------------------------------------------------- (f) K21-K24, K31
 def test_k21_k23_metric_map_in_exact_integer_arithmetic(orc):
     """The per-pixel error is floor(1e6 * sum|d rgb| / 765) -- evaluated here in exact integers -- to within the one unit a float32

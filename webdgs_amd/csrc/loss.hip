@@ -57,6 +57,12 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32*
     if (x >= W || y0 >= H) return;
 
     const bool dssim = cfg.lambda_dssim > 0.0f;
+    // The SSIM quotient's denominator is (mx^2 + my^2 + c1) (vx + vy + c2) with means and variances of values in [0, 1]: at least c1 * c2 and, as its
+    // numerator, at most (2 + c1) (2 + c2) in magnitude when both constants are positive.  The short division (dmath.h) is verified for denominators
+    // in [1e-8, 1e3], so it serves where the constants themselves keep the quotient's operands there (the defaults: c1 * c2 = 9e-8); any other pair
+    // a caller sets -- smaller (a flat window's denominator then leaves the range, down to subnormals and 0), larger or negative -- takes the full
+    // division with its operand scaling and special cases.  Wave-uniform: a kernel argument.
+    const bool short_div = cfg.c1 > 0.0f && cfg.c2 > 0.0f && cfg.c1 * cfg.c2 >= 1e-8f && cfg.c1 <= 10.0f && cfg.c2 <= 10.0f;
     const float n = 25.0f;
     float mx[PPT][3], my[PPT][3], sx2[PPT][3], sy2[PPT][3], sxy[PPT][3];
     if (dssim) {
@@ -85,8 +91,8 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32*
         f2 sx2a[PPT], sx2b[PPT], sy2a[PPT], sy2b[PPT], sxya[PPT], sxyb[PPT], ma[PPT], mb[PPT], na[PPT], nb[PPT];
 #pragma unroll
         for (u32 k = 0; k < PPT; k++) {
-            // (window sums of values in [0, 1] over 25; below, sums of squares over 25 and a quotient whose denominator is at least
-            // c1 * c2 > 0: ordinary operands, so the division without operand scaling and special-case fix-up -- dmath.h)
+            // (window sums of values in [0, 1] over 25 and, below, sums of squares over 25: ordinary operands, so the division without operand
+            // scaling and special-case fix-up -- dmath.h; the SSIM quotient takes it under short_div only)
             mx[k][0] = wd_div_inrange(mxa[k].x, n); mx[k][1] = wd_div_inrange(mxa[k].y, n); mx[k][2] = wd_div_inrange(mxb[k].x, n);
             my[k][0] = wd_div_inrange(mya[k].x, n); my[k][1] = wd_div_inrange(mya[k].y, n); my[k][2] = wd_div_inrange(myb[k].x, n);
             ma[k] = f2{mx[k][0], mx[k][1]}; mb[k] = f2{mx[k][2], 0.f};
@@ -143,9 +149,8 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(u32 W, u32 H, const u32*
                 const float num2 = 2.0f * vxy + cfg.c2;
                 const float den1 = mx[k][c] * mx[k][c] + my[k][c] * my[k][c] + cfg.c1;
                 const float den2 = vx + vy + cfg.c2;
-                // (a caller may set c1 = c2 = 0: then a flat window makes the denominator 0 and the full form's special cases are needed)
                 const float den = den1 * den2;
-                const float ssim = (cfg.c1 > 0.0f && cfg.c2 > 0.0f) ? wd_div_inrange(num1 * num2, den) : wd_div(num1 * num2, den);
+                const float ssim = short_div ? wd_div_inrange(num1 * num2, den) : wd_div(num1 * num2, den);
                 g[c] = ((1.0f - ssim) * 0.5f) * d[c];
             }
         }
