@@ -1,0 +1,553 @@
+"""GPU: the optimizer kernels (csrc/optimizer.hip, adam.h) on crafted state, gradients and counts (tests/adamcases.py), with no rendering pass in
+front of them: Adam + re-pack in its packed-gradient and fp32-sum forms, the owned-slice range form with row publishing, apply_rows, the fp32
+gradient store and accumulate, the fp16 -> fp32 unpack, the load and flush of the compact seven-plane training copy, the deferred SH-DC words and
+the guard.  Every comparison is bit for bit against the oracle (tests/test_adam_cases.py holds the oracle itself to the float64 form on the same
+inputs); the one allowance is that a NaN equals a NaN of any sign and payload, per f32 lane and per fp16 half of a packed word."""
+import numpy as np
+import pytest
+
+from webdgs_amd import _lib, ops
+
+import adamcases as ac
+from harness import assert_bits_equal
+
+pytestmark = pytest.mark.gpu
+
+KEYS = tuple(ac.STATE_WIDTHS)
+FIELD = dict(opt_pos="optPosBuffer", opt_rot="optRotBuffer", opt_scale="optScaleBuffer", opt_opacity="optOpacityBuffer", param_sh="paramSH", state_sh="stateSH")
+SENTINEL = np.uint32(0xA5C3F00D)
+
+
+def _u16(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint16).reshape(a.shape[0], -1)
+
+
+def assert_f32_equal(got, want, what):
+    """Bit for bit; where the oracle has a NaN the kernel must have one (any sign, any payload), and nowhere else."""
+    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
+    assert got.shape == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
+    gn, wn = np.isnan(got), np.isnan(want)
+    apart = np.flatnonzero(gn != wn)
+    assert apart.size == 0, f"{what}: the kernel has {int(gn.sum())} NaN, the oracle {int(wn.sum())}; first difference at flat index {int(apart[0])} (row {int(apart[0]) // got.shape[-1]})"
+    assert_bits_equal(np.where(wn, np.uint32(0), got.view(np.uint32)), np.where(wn, np.uint32(0), want.view(np.uint32)), what)
+
+
+def assert_halves_equal(got, want, what):
+    """The same rule per fp16 half (u16 arrays)."""
+    got, want = np.ascontiguousarray(got, np.uint16), np.ascontiguousarray(want, np.uint16)
+    assert got.shape == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
+    gn, wn = ((got & 0x7C00) == 0x7C00) & ((got & 0x03FF) != 0), ((want & 0x7C00) == 0x7C00) & ((want & 0x03FF) != 0)
+    apart = np.flatnonzero(gn != wn)
+    assert apart.size == 0, f"{what}: the kernel has {int(gn.sum())} NaN halves, the oracle {int(wn.sum())}; first difference at flat index {int(apart[0])} (row {int(apart[0]) // got.shape[-1]})"
+    assert_bits_equal(np.where(wn, np.uint16(0), got), np.where(wn, np.uint16(0), want), what)
+
+
+class Rig:
+    """A point cloud and an optimizer on crafted state, with the host's mirror of what they must hold: `state`, `gauss`, `sh` are advanced by the
+    oracle (`advance`, `apply`) and compared with the device (`check`)."""
+
+    def __init__(self, dev, orc, state, hyper, route="adopt", deferred=False):
+        self.dev, self.orc, self.n = dev, orc, state["opt_pos"].shape[0]
+        n = self.n
+        self.state = ac.copy_state(state)
+        self.gauss, rows = np.zeros((n, 6), np.uint32), ac.sh_rows(n)
+        self.sh = rows.copy()
+        orc.repack(self.state, self.gauss, self.sh)
+        self.sh[:, 1] = (self.sh[:, 1] & 0xFFFF) | (rows[:, 1] & 0xFFFF0000)     # the neighbour of the third trained half keeps its NaN payloads
+        self.pc = ops.createPointCloud(dev, self.gauss, self.sh, 3)
+        self.hyper = np.asarray(hyper, np.float32)
+        if route == "adopt":
+            bufs = {FIELD[k]: dev.bufferFrom(state[k], FIELD[k]) for k in KEYS}
+            self.opt = ops.Optimizer(dev, self.pc, params=ac.hyper_dict(hyper), initialState=dict(buffers=bufs))
+        else:   # a fresh optimizer (unpacked from the cloud), its arrays then rewritten from outside
+            self.opt = ops.Optimizer(dev, self.pc, params=ac.hyper_dict(hyper))
+            b = self.opt.getStateBuffers()
+            for k in KEYS:
+                b[FIELD[k]].write(state[k])
+            self.opt.stateChanged()
+        self.deferred = deferred
+        if deferred:
+            assert self.opt.setDeferredSH(self.pc, True) is not None
+        self.steps = 0
+
+    def destroy(self):
+        self.opt.destroy()
+
+    def buffers(self, packed=None, grad32=None, counts=None):
+        return tuple(None if a is None else self.dev.bufferFrom(a) for a in (packed, grad32, counts))
+
+    def set_hyper(self, hyper):
+        self.hyper = np.asarray(hyper, np.float32)
+        self.opt.setHyperparameters(ac.hyper_dict(hyper))
+
+    def advance(self, counts, packed=None, grad32=None, window=None, hyper=None):
+        """The oracle's step on the mirror: Adam where the count is non-zero and the Gaussian inside `window` = (first, count), the re-pack of every
+        Gaussian inside it; nothing outside it.  Returns the mask of the window."""
+        n, orc = self.n, self.orc
+        inside = np.ones(n, bool) if window is None else ac.in_window(n, *window)
+        c = np.where(inside, counts, 0).astype(np.uint32)
+        st = ac.copy_state(self.state)
+        h = self.hyper if hyper is None else np.asarray(hyper, np.float32)
+        if packed is not None:
+            orc.adam(h, c, np.ascontiguousarray(packed), st)
+        else:
+            orc.adam_f32(h, c, np.ascontiguousarray(grad32), st)
+        g, sh = self.gauss.copy(), self.sh.copy()
+        orc.repack(st, g, sh)
+        sh[:, 1] = (sh[:, 1] & 0xFFFF) | (self.sh[:, 1] & 0xFFFF0000)   # adam.h does not touch that half; the oracle's f16 -> f32 -> f16 may change a NaN payload
+        g[~inside], sh[~inside] = self.gauss[~inside], self.sh[~inside]
+        for k in KEYS:
+            assert np.array_equal(st[k][~inside].view(np.uint32), self.state[k][~inside].view(np.uint32))
+        self.state, self.gauss, self.sh = st, g, sh
+        return inside
+
+    def apply(self, rows, window):
+        """apply_rows on the mirror: outside the skip window the six Gaussian words, SH word 0 and the low half of SH word 1 come from the row."""
+        take = ~ac.in_window(self.n, *window)
+        self.gauss[take] = rows[take, :6]
+        self.sh[take, 0] = rows[take, 6]
+        self.sh[take, 1] = (self.sh[take, 1] & 0xFFFF0000) | (rows[take, 7] & 0xFFFF)
+        return take
+
+    def read_state(self):
+        b = self.opt.getStateBuffers()
+        return {k: b[FIELD[k]].read(np.float32).reshape(self.n, w) for k, w in ac.STATE_WIDTHS.items()}
+
+    def read_cloud(self):
+        """Through raw views of the cloud's memory: no before_read hook brings the SH rows up to date behind the test's back."""
+        g, s = self.pc.gaussian_3d_buffer, self.pc.sh_buffer
+        return (self.dev.view(g.ptr, g.size).read(np.uint32).reshape(self.n, 6), self.dev.view(s.ptr, s.size).read(np.uint32).reshape(self.n, 24))
+
+    def check(self, what, exact=False):
+        if self.deferred:
+            self.opt.flushSH(self.pc)
+        got = self.read_state()
+        for k in KEYS:
+            (assert_bits_equal if exact else assert_f32_equal)(got[k], self.state[k], f"{what}: {k}")
+        g, sh = self.read_cloud()
+        gh, sh_got, sh_want = _u16(g), _u16(sh), _u16(self.sh)
+        if exact:
+            assert_bits_equal(g, self.gauss, f"{what}: Gaussian words")
+            assert_bits_equal(sh, self.sh, f"{what}: SH rows")
+        assert_halves_equal(gh, _u16(self.gauss), f"{what}: Gaussian words")
+        assert_halves_equal(sh_got[:, :3], sh_want[:, :3], f"{what}: SH word 0 and the low half of SH word 1")
+        assert_bits_equal(sh_got[:, 3], sh_want[:, 3], f"{what}: the high half of SH word 1 (the kernels must not touch it)")
+        assert_bits_equal(sh_got[:, 4:], sh_want[:, 4:], f"{what}: SH words 2..23")
+        assert self.opt.getIteration() == self.steps, f"{what}: getIteration() is {self.opt.getIteration()} after {self.steps} steps"
+
+
+def _steps_of(kind):
+    return 3 if kind in ("lanes", "magnitudes") else 1
+
+
+@pytest.mark.parametrize("n", ac.ONE_STEP_SIZES)
+@pytest.mark.parametrize("kind", ac.KINDS)
+def test_packed_step_equals_the_oracle(hip_device, orc, kind, n):
+    """Optimizer.step: state, cloud and iteration against orc.adam + orc.repack, under every hyperparameter set."""
+    for name, h in ac.HYPER.items():
+        case = ac.build(kind, n, hyper=h)
+        rig = Rig(hip_device, orc, case.state, h)
+        try:
+            rig.check(f"{kind} {name} n={n} before any step", exact=True)
+            for s in range(1, _steps_of(kind) + 1):
+                packed, counts = (case.packed, case.counts) if s == 1 else ac.later_gradients(kind, n, s)[::2]
+                bp, _, bc = rig.buffers(packed=packed, counts=counts)
+                rig.opt.step(None, rig.pc, bp, bc)
+                rig.steps += 1
+                rig.advance(counts, packed=packed)
+                rig.check(f"{kind} {name} n={n} step {s}")
+        finally:
+            rig.destroy()
+
+
+@pytest.mark.parametrize("n", ac.ONE_STEP_SIZES)
+@pytest.mark.parametrize("kind", ac.KINDS)
+def test_f32_step_equals_the_oracle(hip_device, orc, kind, n):
+    """Optimizer.stepF32 on the fp32 blocks against orc.adam_f32 + orc.repack."""
+    for name, h in ac.HYPER.items():
+        case = ac.build(kind, n, hyper=h)
+        rig = Rig(hip_device, orc, case.state, h)
+        try:
+            for s in range(1, _steps_of(kind) + 1):
+                g32, counts = (case.grad32, case.counts) if s == 1 else ac.later_gradients(kind, n, s)[1:]
+                _, bg, bc = rig.buffers(grad32=g32, counts=counts)
+                rig.opt.stepF32(None, rig.pc, bg, bc)
+                rig.steps += 1
+                rig.advance(counts, grad32=g32)
+                rig.check(f"f32 {kind} {name} n={n} step {s}")
+        finally:
+            rig.destroy()
+
+
+def test_state_written_from_outside_is_picked_up_by_state_changed(hip_device, orc):
+    """The other route to the same state: a fresh optimizer (unpacked from the cloud), its six arrays rewritten through getStateBuffers(), stateChanged()."""
+    h = ac.HYPER["distinct-lr"]
+    case = ac.build("lanes", ac.N_DEFAULT)
+    rig = Rig(hip_device, orc, case.state, h, route="fresh")
+    try:
+        rig.check("fresh route before any step", exact=True)
+        bp, _, bc = rig.buffers(packed=case.packed, counts=case.counts)
+        rig.opt.step(None, rig.pc, bp, bc)
+        rig.steps += 1
+        rig.advance(case.counts, packed=case.packed)
+        rig.check("fresh route, one step")
+    finally:
+        rig.destroy()
+
+
+def _rows_expected(rig, inside, sentinel_rows):
+    want = sentinel_rows.copy()
+    want[inside, :6] = rig.gauss[inside]
+    want[inside, 6] = rig.sh[inside, 0]
+    want[inside, 7] = rig.sh[inside, 1] & 0xFFFF
+    return want
+
+
+@pytest.mark.parametrize("with_rows", [True, False], ids=["rows", "norows"])
+@pytest.mark.parametrize("first,count", ac.RANGES, ids=[f"{f}-{c}" for f, c in ac.RANGES])
+def test_f32_range_steps_its_slice_and_nothing_else(hip_device, orc, first, count, with_rows, deferred=False):
+    dev, n = hip_device, ac.N_DEFAULT
+    h = ac.HYPER["distinct-lr"]
+    case = ac.build("lanes", n)
+    rig = Rig(dev, orc, case.state, h, deferred=deferred)
+    try:
+        sentinel_rows = np.full((n, 8), SENTINEL, np.uint32)
+        rows = dev.bufferFrom(sentinel_rows) if with_rows else None
+        _, bg, bc = rig.buffers(grad32=case.grad32, counts=case.counts)
+        rig.opt.stepF32Range(None, rig.pc, bg, bc, first, count, rows)
+        rig.steps += 1
+        inside = rig.advance(case.counts, grad32=case.grad32, window=(first, count))
+        assert int(inside.sum()) == count
+        rig.check(f"range ({first}, {count})")
+        if with_rows:
+            got = rows.read(np.uint32).reshape(n, 8)
+            want = _rows_expected(rig, inside, sentinel_rows)
+            assert_halves_equal(_u16(got), _u16(want), f"range ({first}, {count}): rowsOut")
+            assert_bits_equal(got[~inside], sentinel_rows[~inside], f"range ({first}, {count}): rowsOut outside the slice")
+            assert np.all((got[inside, 7] >> 16) == 0)
+        if count:
+            upd = inside & (case.counts != 0)
+            assert np.any(rig.state["opt_pos"][upd] != case.state["opt_pos"][upd]), "the slice was not stepped at all"
+    finally:
+        rig.destroy()
+
+
+def test_f32_range_past_the_end_is_refused_and_changes_nothing(hip_device, orc):
+    dev, n = hip_device, ac.N_DEFAULT
+    case = ac.build("lanes", n)
+    rig = Rig(dev, orc, case.state, ac.HYPER["default"])
+    try:
+        sentinel_rows = np.full((n, 8), SENTINEL, np.uint32)
+        rows = dev.bufferFrom(sentinel_rows)
+        _, bg, bc = rig.buffers(grad32=case.grad32, counts=case.counts)
+        for first, count in [(999, 2), (1000, 1), (0, 1001), (0xFFFFFFFF, 1), (1, 0xFFFFFFFF), (1001, 0)]:
+            with pytest.raises(_lib.WdgsError) as e:
+                rig.opt.stepF32Range(None, rig.pc, bg, bc, first, count, rows)
+            assert e.value.code == _lib.WDGS_E_INVALID, f"({first}, {count}): {e.value}"
+            assert rig.opt.getIteration() == 0
+        rig.check("after refused ranges", exact=True)
+        assert_bits_equal(rows.read(np.uint32).reshape(n, 8), sentinel_rows, "rowsOut after refused ranges")
+        rig.opt.stepF32Range(None, rig.pc, bg, bc, n, 0, rows)      # an empty slice at the very end is a valid one
+        rig.steps += 1
+        rig.check("empty range at n", exact=True)
+    finally:
+        rig.destroy()
+
+
+def test_new_hyperparameters_take_effect_at_the_next_step(hip_device, orc):
+    n = ac.N_DEFAULT
+    h1, h2 = ac.HYPER["default"], ac.HYPER["distinct-lr"].copy()
+    h2[5:8] = (0.5, 0.75, 1e-3)
+    case = ac.build("lanes", n)
+    packed2, _, counts2 = ac.later_gradients("lanes", n, 2)
+    rig = Rig(hip_device, orc, case.state, h1)
+    try:
+        bp, _, bc = rig.buffers(packed=case.packed, counts=case.counts)
+        rig.opt.step(None, rig.pc, bp, bc)
+        rig.steps += 1
+        rig.advance(case.counts, packed=case.packed)
+        rig.check("step 1, first hyperparameters")
+        rig.set_hyper(h2)
+        assert rig.opt.getHyperparameters() == ac.hyper_dict(h2)
+        before = (ac.copy_state(rig.state), rig.gauss.copy(), rig.sh.copy())
+        rig.advance(counts2, packed=packed2, hyper=h1)      # what the old values would give: must differ, or the test proves nothing
+        old = rig.state
+        rig.state, rig.gauss, rig.sh = before
+        bp, _, bc = rig.buffers(packed=packed2, counts=counts2)
+        rig.opt.step(None, rig.pc, bp, bc)
+        rig.steps += 1
+        rig.advance(counts2, packed=packed2)
+        upd = counts2 != 0
+        for k in ("opt_pos", "opt_rot", "opt_scale", "opt_opacity"):
+            assert np.all((old[k][upd] != rig.state[k][upd]).any(1)), f"{k}: the two hyperparameter sets give the same step"
+        rig.check("step 2, second hyperparameters")
+    finally:
+        rig.destroy()
+
+
+@pytest.mark.parametrize("kind", ["lanes", "saturating"])
+def test_deferred_sh_words_flush_to_the_same_rows(hip_device, orc, kind):
+    """setDeferredSH(pc, True): the trained halves go to the compact words, the rows are stale until flushSH, and then equal the immediate form's."""
+    n = ac.N_DEFAULT
+    h = ac.HYPER["distinct-lr"]
+    case = ac.build(kind, n, hyper=h)
+    rig = Rig(hip_device, orc, case.state, h, deferred=True)
+    try:
+        stale_rows = rig.sh.copy()
+        bp, _, bc = rig.buffers(packed=case.packed, counts=case.counts)
+        rig.opt.step(None, rig.pc, bp, bc)
+        rig.steps += 1
+        rig.advance(case.counts, packed=case.packed)
+        assert_bits_equal(rig.read_cloud()[1], stale_rows, f"{kind}: the SH rows before flushSH (deferral leaves them alone)")
+        if kind == "lanes":
+            assert np.any(rig.sh != stale_rows)
+        words = rig.dev.view(rig.pc.dc_words.ptr, 8 * n).read(np.uint32).reshape(n, 2)
+        assert_halves_equal(_u16(words)[:, :3], _u16(rig.sh)[:, :3], f"{kind}: the deferred words")
+        assert np.all((words[:, 1] >> 16) == 0), f"{kind}: the deferred words' unused half"
+        rig.check(f"deferred {kind}")
+        # switched off again, the immediate form goes on from the same rows
+        rig.opt.setDeferredSH(rig.pc, False)
+        rig.deferred = False
+        rig.opt.step(None, rig.pc, bp, bc)
+        rig.steps += 1
+        rig.advance(case.counts, packed=case.packed)
+        rig.check(f"{kind}: immediate step after deferral")
+    finally:
+        rig.destroy()
+
+
+def test_deferred_sh_in_the_range_form(hip_device, orc):
+    test_f32_range_steps_its_slice_and_nothing_else(hip_device, orc, 257, 743, True, deferred=True)
+    test_f32_range_steps_its_slice_and_nothing_else(hip_device, orc, 255, 2, True, deferred=True)
+
+
+@pytest.mark.parametrize("n", ac.ONE_STEP_SIZES)
+def test_unpack_of_a_crafted_cloud(hip_device, orc, n):
+    """A fresh optimizer: parameters are orc.unpack of the cloud, every moment is zero, position w is 1 and scale w is 0."""
+    dev = hip_device
+    g, sh = ac.unpack_cloud(n)
+    pc = ops.createPointCloud(dev, g, sh, 3)
+    opt = ops.Optimizer(dev, pc)
+    try:
+        b = opt.getStateBuffers()
+        got = {k: b[FIELD[k]].read(np.float32).reshape(n, w) for k, w in ac.STATE_WIDTHS.items()}
+        want = orc.unpack(g, sh)
+        for k in KEYS:
+            assert_bits_equal(got[k], want[k], f"unpack n={n}: {k}")
+        for k in ("opt_pos", "opt_rot", "opt_scale"):
+            assert np.all(got[k][:, 4:].view(np.uint32) == 0), f"{k}: moments"
+        assert np.all(got["opt_opacity"][:, 1:].view(np.uint32) == 0) and np.all(got["state_sh"].view(np.uint32) == 0)
+        assert np.all(got["opt_pos"][:, 3] == 1.0) and np.all(got["opt_scale"][:, 3].view(np.uint32) == 0)
+        halves = np.concatenate([_u16(g), _u16(sh)], axis=1)
+        flat = np.concatenate([got["opt_pos"][:, :3], got["opt_opacity"][:, :1], got["opt_rot"][:, :4], got["opt_scale"][:, :3]], axis=1)
+        assert_bits_equal(flat, halves[:, :11].view(np.float16).astype(np.float32), "the 11 Gaussian halves, by numpy's own fp16")
+        assert_bits_equal(got["param_sh"], halves[:, 12:].view(np.float16).astype(np.float32), "the 48 SH halves, by numpy's own fp16")
+        allp = np.concatenate([flat, got["param_sh"]], axis=1)
+        assert np.isinf(allp).any() and np.any(allp == np.float32(2.0 ** -24)) and np.any(np.signbit(allp) & (allp == 0)) and np.any(allp == np.float32(-65504.0))
+    finally:
+        opt.destroy()
+
+
+def test_compact_copy_round_trip(hip_device, orc):
+    """Adopted state comes back bit-identical in all 183 floats per Gaussian before any step (nothing is dirty, nothing is rewritten), and after a
+    step in which no Gaussian is visible (load, step, flush: every trained lane through the seven planes and back)."""
+    n = ac.N_DEFAULT
+    case = ac.build("lanes", n)
+    rig = Rig(hip_device, orc, case.state, ac.HYPER["default"])
+    try:
+        got = rig.read_state()
+        for k in KEYS:
+            assert_bits_equal(got[k], case.state[k], f"adopted and read back: {k}")
+        zero = np.zeros(n, np.uint32)
+        bp, bg, bc = rig.buffers(packed=case.packed, grad32=case.grad32, counts=zero)
+        rig.opt.step(None, rig.pc, bp, bc)
+        rig.opt.stepF32(None, rig.pc, bg, bc)
+        rig.steps += 2
+        rig.check("two steps with no Gaussian visible", exact=True)
+        got = rig.read_state()
+        for k in KEYS:
+            assert_bits_equal(got[k], case.state[k], f"after steps with all counts zero: {k}")
+    finally:
+        rig.destroy()
+
+
+def test_flush_writes_the_fourth_lane_constants_everywhere(hip_device, orc):
+    """The documented deviation of cs_flush (optimizer.hip): the fourth lanes of optPos / optScale come back as 1, 0, 0 / 0, 0, 0 for EVERY Gaussian,
+    where the reference rewrites them only in the Gaussians it updates.  With adopted fourth lanes that are not those constants, kernel and oracle
+    differ on exactly those lanes of the not-updated Gaussians and nowhere else; SH coefficients 3..47 and their moments never change."""
+    n = ac.N_DEFAULT
+    state = ac.lanes_state(n, fourth_lanes=True)
+    packed, _ = ac.lanes_gradients(n)
+    counts = ac.mixed_counts(n)
+    rig = Rig(hip_device, orc, state, ac.HYPER["default"])
+    try:
+        got = rig.read_state()
+        for k in KEYS:
+            assert_bits_equal(got[k], state[k], f"adopted and read back before any step: {k}")
+        bp, _, bc = rig.buffers(packed=packed, counts=counts)
+        rig.opt.step(None, rig.pc, bp, bc)
+        rig.steps += 1
+        rig.advance(counts, packed=packed)
+        got = rig.read_state()
+        for k in KEYS:
+            differs = got[k].view(np.uint32) != rig.state[k].view(np.uint32)
+            expected = np.zeros_like(differs)
+            if k in ("opt_pos", "opt_scale"):
+                expected[np.ix_(counts == 0, [3, 7, 11])] = True
+            assert np.array_equal(differs, expected), f"{k}: kernel and oracle differ on {int(differs.sum())} entries, the fourth lanes of the not-updated Gaussians are {int(expected.sum())}"
+        const_pos, const_scale = np.array([1.0, 0.0, 0.0], np.float32), np.zeros(3, np.float32)
+        assert_bits_equal(got["opt_pos"][:, [3, 7, 11]], np.broadcast_to(const_pos, (n, 3)), "optPos fourth lanes")
+        assert_bits_equal(got["opt_scale"][:, [3, 7, 11]], np.broadcast_to(const_scale, (n, 3)), "optScale fourth lanes")
+        assert_bits_equal(got["param_sh"][:, 3:], state["param_sh"][:, 3:], "SH coefficients 3..47")
+        assert_bits_equal(got["state_sh"][:, 6:], state["state_sh"][:, 6:], "moments of SH coefficients 3..47")
+        for k in KEYS:      # the mirror, given the constants, is what the device holds from here on
+            rig.state[k] = np.where(got[k].view(np.uint32) != rig.state[k].view(np.uint32), got[k], rig.state[k])
+        rig.check("cloud after the step")
+    finally:
+        rig.destroy()
+
+
+@pytest.mark.parametrize("n", ac.ONE_STEP_SIZES)
+def test_gradient_store_and_accumulate(hip_device, orc, n):
+    dev = hip_device
+    views = ac.gradient_views(n)
+    unpacked = [orc.unpack_gradients_f32(p) for p, _ in views]
+    counts = [c for _, c in views]
+    bufs = [(dev.bufferFrom(p), dev.bufferFrom(c)) for p, c in views]
+    acc = dev.bufferFrom(np.full((n, 14), SENTINEL, np.uint32))
+    vis = dev.bufferFrom(np.full(n, SENTINEL, np.uint32))
+    ops.storeGradients(dev, n, bufs[0][0], bufs[0][1], acc, vis)
+    want, wvis = ac.gradient_sums(unpacked[:1], counts[:1])
+    got = acc.read(np.float32).reshape(n, 14)
+    assert_f32_equal(got, want, f"n={n}: store")
+    assert_bits_equal(vis.read(np.uint32), wvis, f"n={n}: visibility after store")
+    hidden = counts[0] == 0
+    assert np.all(got[hidden].view(np.uint32) == 0), "store writes +0.0 where the count is zero"
+    for v in (1, 2):
+        ops.accumulateGradients(dev, n, bufs[v][0], bufs[v][1], acc, vis)
+    want, wvis = ac.gradient_sums(unpacked, counts)
+    assert_f32_equal(acc.read(np.float32).reshape(n, 14), want, f"n={n}: sums of three views")
+    assert_bits_equal(vis.read(np.uint32), wvis, f"n={n}: visibility counts")
+    assert_bits_equal(wvis, sum((c != 0).astype(np.uint32) for c in counts), "the reference's own counts")
+    # accumulate alone, into rows that hold a sentinel: untouched where the count is zero
+    s_acc = np.full((n, 14), np.float32(1234.5), np.float32) + np.arange(14, dtype=np.float32)[None, :]
+    s_vis = np.full(n, 0x5A5A5A5A, np.uint32)
+    acc2, vis2 = dev.bufferFrom(s_acc), dev.bufferFrom(s_vis)
+    ops.accumulateGradients(dev, n, bufs[1][0], bufs[1][1], acc2, vis2)
+    want, wvis = ac.gradient_sums(unpacked[1:2], counts[1:2], acc=s_acc.copy(), visible=s_vis.copy())
+    got, gvis = acc2.read(np.float32).reshape(n, 14), vis2.read(np.uint32)
+    assert_f32_equal(got, want, f"n={n}: accumulate onto sentinel rows")
+    assert_bits_equal(gvis, wvis, f"n={n}: accumulate onto sentinel counts")
+    hidden = counts[1] == 0
+    assert_bits_equal(got[hidden], s_acc[hidden], "rows with a zero count")
+    assert_bits_equal(gvis[hidden], s_vis[hidden], "counts of rows with a zero count")
+
+
+@pytest.mark.parametrize("form", ["ops", "optimizer", "optimizer-deferred"])
+def test_apply_rows_outside_the_skip_window(hip_device, orc, form):
+    dev, n = hip_device, ac.N_DEFAULT
+    case = ac.build("lanes", n)
+    rig = Rig(dev, orc, case.state, ac.HYPER["default"], deferred=(form == "optimizer-deferred"))
+    try:
+        for k, window in enumerate(ac.skip_windows(n)):
+            rows = ac.random_rows(n, seed=40 + k)
+            assert np.all(rows[:, 7] >> 16 != 0)
+            before = rig.gauss.copy()
+            brows = dev.bufferFrom(rows)
+            if form == "ops":
+                ops.applyRepackedRows(dev, n, brows, window[0], window[1], None, rig.pc)
+            else:
+                rig.opt.applyRepackedRows(brows, window[0], window[1], None, rig.pc)
+            take = rig.apply(rows, window)
+            assert np.array_equal(rig.gauss[~take], before[~take])
+            if rig.deferred:    # the compact words themselves, before the flush: word 1 carries the one trained half and nothing of row word 7's high half
+                words = dev.view(rig.pc.dc_words.ptr, 8 * n).read(np.uint32).reshape(n, 2)
+                assert_bits_equal(words[:, 0], rig.sh[:, 0], f"{form}, skip window {window}: deferred word 0")
+                assert_bits_equal(words[:, 1], rig.sh[:, 1] & np.uint32(0xFFFF), f"{form}, skip window {window}: deferred word 1")
+            rig.check(f"{form} apply_rows, skip window {window}", exact=True)
+        taken = [int((~ac.in_window(n, *w)).sum()) for w in ac.skip_windows(n)]
+        assert taken == [n, 0, n - 1, n - 1, n - 2, n - 256, 900, n, n], taken
+    finally:
+        rig.destroy()
+
+
+def test_guard_accumulate(hip_device):
+    dev = hip_device
+    src_words = np.array([0, 1, 0x80000000], np.uint32)
+    src = dev.bufferFrom(src_words)
+    flag = dev.createBuffer(4)
+    for overwrite in (False, True):
+        for start in (0, 1, 6):
+            for k, s in enumerate(src_words):
+                flag.write(np.array([start], np.uint32))
+                ops.guardAccumulate(dev, flag, src, 4 * k, overwrite=overwrite)
+                want = (0 if overwrite else start) | (1 if s != 0 else 0)
+                assert int(flag.read(np.uint32)[0]) == want, f"flag {start}, src {int(s):#x}, overwrite {overwrite}"
+    # folded over three views, as a batched step does it
+    for words, want in (((0, 0, 0), 0), ((0, 0x80000000, 0), 1), ((1, 0, 0), 1), ((0, 0, 7), 1)):
+        src.write(np.array(words, np.uint32))
+        flag.write(np.array([9], np.uint32))
+        for k in range(3):
+            ops.guardAccumulate(dev, flag, src, 4 * k, overwrite=(k == 0))
+        assert int(flag.read(np.uint32)[0]) == want, f"views {words}"
+
+
+def test_a_set_guard_turns_every_form_into_a_no_op(hip_device, orc):
+    """With the guard word non-zero, step, stepF32, stepF32Range with rowsOut and both apply-rows forms leave state, cloud and rowsOut untouched; the
+    fp32 and apply forms report the skipped step at the next host wait, once.  Back at zero, the same calls update as usual."""
+    dev, n = hip_device, ac.N_DEFAULT
+    h = ac.HYPER["distinct-lr"]
+    case = ac.build("lanes", n)
+    rig = Rig(dev, orc, case.state, h)
+    try:
+        sentinel_rows = np.full((n, 8), SENTINEL, np.uint32)
+        rows_out = dev.bufferFrom(sentinel_rows)
+        rows_in_host = ac.random_rows(n, seed=77)
+        rows_in = dev.bufferFrom(rows_in_host)
+        bp, bg, bc = rig.buffers(packed=case.packed, grad32=case.grad32, counts=case.counts)
+        flag = dev.bufferFrom(np.array([0, 0], np.uint32))
+        overflow = dev.bufferFrom(np.array([0x80000000], np.uint32))
+        ops.guardAccumulate(dev, flag, overflow, 0, overwrite=True)
+        assert int(flag.read(np.uint32)[0]) == 1
+        rig.opt.setGuard(flag)
+        dev.synchronize()
+
+        calls = [("step", lambda: rig.opt.step(None, rig.pc, bp, bc), False, True),
+                 ("stepF32", lambda: rig.opt.stepF32(None, rig.pc, bg, bc), True, True),
+                 ("stepF32Range", lambda: rig.opt.stepF32Range(None, rig.pc, bg, bc, 255, 258, rows_out), True, True),
+                 ("ops.applyRepackedRows", lambda: ops.applyRepackedRows(dev, n, rows_in, 256, 256, flag, rig.pc), True, False),
+                 ("Optimizer.applyRepackedRows", lambda: rig.opt.applyRepackedRows(rows_in, 256, 256, flag, rig.pc), True, False)]
+        for name, call, reports, counts_as_step in calls:
+            call()
+            rig.steps += 1 if counts_as_step else 0
+            if reports:     # the report is taken here, before any buffer is read, so that the shared device reaches the next test with nothing pending
+                with pytest.raises(_lib.CapacityError, match="skipped"):
+                    dev.synchronize()
+            dev.synchronize()
+            rig.check(f"guard set: {name}", exact=True)
+            assert_bits_equal(rows_out.read(np.uint32).reshape(n, 8), sentinel_rows, f"guard set: rowsOut after {name}")
+
+        flag.write(np.array([0, 0], np.uint32))
+        for name, call, _, counts_as_step in calls:
+            call()
+            rig.steps += 1 if counts_as_step else 0
+            if name == "step":
+                rig.advance(case.counts, packed=case.packed)
+            elif name == "stepF32":
+                rig.advance(case.counts, grad32=case.grad32)
+            elif name == "stepF32Range":
+                inside = rig.advance(case.counts, grad32=case.grad32, window=(255, 258))
+                got = rows_out.read(np.uint32).reshape(n, 8)
+                assert_halves_equal(_u16(got), _u16(_rows_expected(rig, inside, sentinel_rows)), "guard cleared: rowsOut")
+            else:
+                rig.apply(rows_in_host, (256, 256))
+            dev.synchronize()
+            rig.check(f"guard cleared: {name}", exact=name.endswith("applyRepackedRows"))
+    finally:
+        rig.opt.setGuard(None)
+        try:
+            dev.synchronize()
+        except _lib.CapacityError:      # a failure above left its report behind: taken here, not in the next test
+            pass
+        rig.destroy()
