@@ -100,3 +100,23 @@ def assert_bits_equal(a, b, what):
         item = a.dtype.itemsize
         idx = np.unique(bad // item)
         raise AssertionError(f"{what}: {idx.size} of {a.size} elements differ; first at flat index {idx[0]}: {a.reshape(-1)[idx[0]]!r} vs {b.reshape(-1)[idx[0]]!r}")
+
+
+def assert_f32_equal(got, want, what):
+    """Bit for bit; where the oracle has a NaN the kernel must have one (any sign, any payload), and nowhere else."""
+    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
+    assert got.shape == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
+    gn, wn = np.isnan(got), np.isnan(want)
+    apart = np.flatnonzero(gn != wn)
+    assert apart.size == 0, f"{what}: the kernel has {int(gn.sum())} NaN, the oracle {int(wn.sum())}; first difference at flat index {int(apart[0])} (row {int(apart[0]) // got.shape[-1]})"
+    assert_bits_equal(np.where(wn, np.uint32(0), got.view(np.uint32)), np.where(wn, np.uint32(0), want.view(np.uint32)), what)
+
+
+def assert_halves_equal(got, want, what):
+    """The same rule per fp16 half (u16 arrays)."""
+    got, want = np.ascontiguousarray(got, np.uint16), np.ascontiguousarray(want, np.uint16)
+    assert got.shape == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
+    gn, wn = ((got & 0x7C00) == 0x7C00) & ((got & 0x03FF) != 0), ((want & 0x7C00) == 0x7C00) & ((want & 0x03FF) != 0)
+    apart = np.flatnonzero(gn != wn)
+    assert apart.size == 0, f"{what}: the kernel has {int(gn.sum())} NaN halves, the oracle {int(wn.sum())}; first difference at flat index {int(apart[0])} (row {int(apart[0]) // got.shape[-1]})"
+    assert_bits_equal(np.where(wn, np.uint16(0), got), np.where(wn, np.uint16(0), want), what)

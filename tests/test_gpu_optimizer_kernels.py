@@ -9,7 +9,7 @@ import pytest
 from webdgs_amd import _lib, ops
 
 import adamcases as ac
-from harness import assert_bits_equal
+from harness import assert_bits_equal, assert_f32_equal, assert_halves_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -21,26 +21,6 @@ SENTINEL = np.uint32(0xA5C3F00D)
 def _u16(a):
     a = np.ascontiguousarray(a)
     return a.view(np.uint16).reshape(a.shape[0], -1)
-
-
-def assert_f32_equal(got, want, what):
-    """Bit for bit; where the oracle has a NaN the kernel must have one (any sign, any payload), and nowhere else."""
-    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
-    assert got.shape == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
-    gn, wn = np.isnan(got), np.isnan(want)
-    apart = np.flatnonzero(gn != wn)
-    assert apart.size == 0, f"{what}: the kernel has {int(gn.sum())} NaN, the oracle {int(wn.sum())}; first difference at flat index {int(apart[0])} (row {int(apart[0]) // got.shape[-1]})"
-    assert_bits_equal(np.where(wn, np.uint32(0), got.view(np.uint32)), np.where(wn, np.uint32(0), want.view(np.uint32)), what)
-
-
-def assert_halves_equal(got, want, what):
-    """The same rule per fp16 half (u16 arrays)."""
-    got, want = np.ascontiguousarray(got, np.uint16), np.ascontiguousarray(want, np.uint16)
-    assert got.shape == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
-    gn, wn = ((got & 0x7C00) == 0x7C00) & ((got & 0x03FF) != 0), ((want & 0x7C00) == 0x7C00) & ((want & 0x03FF) != 0)
-    apart = np.flatnonzero(gn != wn)
-    assert apart.size == 0, f"{what}: the kernel has {int(gn.sum())} NaN halves, the oracle {int(wn.sum())}; first difference at flat index {int(apart[0])} (row {int(apart[0]) // got.shape[-1]})"
-    assert_bits_equal(np.where(wn, np.uint16(0), got), np.where(wn, np.uint16(0), want), what)
 
 
 class Rig:

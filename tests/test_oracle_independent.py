@@ -21,6 +21,7 @@ from webdgs_amd import synth
 
 import harness
 import indep64 as ind
+from densifycases import _densify_children_fp64, _rand01  # noqa: F401
 
 
 def _scene(base="c1", n=None, w=None, h=None, sh_deg=None, s0=None, view=None):
@@ -271,35 +272,6 @@ def test_adam_is_the_closed_form_without_bias_correction(orc):
 
 
 # ----------------------------------------------------------------------------------------------------------------- (d) K26-K30
-def _rand01(seed_u32):
-    """f32(hash) * 2^-32 (densify-prune-scatter-gaussians.wgsl:40-43): the u32 -> f32 conversion rounds to 24 bits."""
-    return ind.lowbias32(seed_u32).astype(np.float32).astype(np.float64) / 4294967296.0
-
-
-def _densify_children_fp64(pos, quat, log_sigma, src, dst, action, variant):
-    """Child position and log-scale of output slot `dst` copied from input `src` (float64, vectorised): clone slot 1 is jittered by
-    0.25 sigma (.) U(-1,1)^3, split children sit at +- 0.5 sigma (.) n with n a six-uniform CLT normal and shrink by ln 1.6; offsets are
-    rotated by the (normalised) quaternion (densify-prune-scatter-gaussians.wgsl:79-150)."""
-    src32, dst32 = src.astype(np.uint64), dst.astype(np.uint64)
-    sigma = np.exp(np.clip(log_sigma, -10, 10))
-    R = ind.rotation_from_quaternion(quat / np.sqrt(np.maximum(1e-12, (quat * quat).sum(1, keepdims=True))))
-    out_pos, out_ls = pos.copy(), log_sigma.copy()
-    clone = (action == 1) & (variant == 1)
-    seed = ((src32 * 1664525 + dst32 * 1013904223) & 0xFFFFFFFF).astype(np.uint64)
-    r = np.stack([_rand01(seed ^ c) for c in (0xA2C79, 0x5E2D9, 0x1B873)], 1) * 2.0 - 1.0
-    out_pos[clone] += np.einsum("nij,nj->ni", R, 0.25 * sigma * r)[clone]
-    split = action == 2
-    seed2 = ((src32 * 747796405 + 2891336453) & 0xFFFFFFFF).astype(np.uint64)
-
-    def randn(s):
-        return (sum(_rand01(s ^ c) for c in (0xA2C79, 0x5E2D9, 0x1B873, 0xC0FFE, 0xBADC0, 0xDEADB)) - 3.0) * 1.41421356237
-    d = np.stack([randn(seed2 ^ c) for c in (0x9E3779B9, 0x243F6A88, 0xB7E15162)], 1)
-    sgn = np.where(variant == 1, -1.0, 1.0)[:, None]
-    out_pos[split] += (sgn * np.einsum("nij,nj->ni", R, 0.5 * sigma * d))[split]
-    out_ls[split] = np.clip(log_sigma, -10, 10)[split] - 0.4700036292457356
-    return out_pos, out_ls
-
-
 def test_densify_decisions_capacity_and_children(orc):
     """K26-K30 restated from the rules (densify-prune-decide / -cap / -scatter-*.wgsl), vectorised in float64, against the oracle:
     actions, capped counts, offsets and total exactly; every child's position, log-scale and opacity within one fp16 ulp (working copy) or
