@@ -1,0 +1,251 @@
+'use strict';
+/*
+ * evaluation.js (+ evaluation.d.ts) -- `Evaluator`: everything a Trainer can measure about its model without training it -- held-out evaluation,
+ * normal consistency, TSDF fusion and mesh extraction, geometry metrics, render contribution (webdgs_amd/evaluation.py is the Python host's; none of
+ * it has a counterpart in the reference).  It renders through pass sets of its own (no backward pass), one per image size, built on first use and
+ * following the trainer's cloud, and answers the capacity reports about them itself (CapacityReports.settle).  Trainer keeps the public methods and
+ * delegates to its Evaluator.
+ */
+const hip = require('./webdgs_hip.js');
+const { destroyPassSets } = require('./trainer.js');
+
+/** The evaluation side of one Trainer.  It owns the evaluation views with their camera blocks (and the textures it uploaded itself), the per-size
+ *  evaluation PassSets, the size an overflow has grown their tile-entry lists to and the long-list settings they were built with.
+ *
+ *  The seam -- the only members of the trainer used here:
+ *    - device, pointCloud, iteration;
+ *    - trainCameras, images, cameraBuffers: the training views, for split 'train';
+ *    - newPassSet: carries the live SH-DC words and the trainer's long-list settings;  dcWords, longLists;
+ *    - drain() and growTileEntryCapacity(): a training step still in flight is awaited, its overflow answered as step() would.
+ *  Never the training or metric pass sets, the command buffers, the tickets, the random draws, the optimizer or the densify pass. */
+class Evaluator {
+  constructor(trainer) {
+    this.trainer = trainer; this.device = trainer.device;
+    this.cameras = []; this.images = []; this.cameraBuffers = []; this.ownedTextures = [];
+    this.sets = new Map();
+    this.maxTileEntries = 0;   // tile-entry lists of the evaluation passes (0: what the training passes get)
+    this.tileEntries = 0;      // (what an overflowing evaluation view has made of them)
+    this.longLists = null;
+  }
+  destroy() {
+    this.destroySets();
+    for (const b of this.cameraBuffers.concat(this.ownedTextures)) b.destroy();
+    this.cameraBuffers = []; this.ownedTextures = [];
+  }
+
+  // ---------------------------------------------------------------- views and pass sets
+  /** Views to evaluate on and never to train on (loaders.holdoutSplit gives the every-8th test views of the 3DGS convention).  Same shapes as
+   *  setDataset; the images may have another size than the training images. */
+  setEvaluationViews(cameras, images) {
+    if (cameras.length !== images.length) throw new Error(`setEvaluationViews: ${cameras.length} cameras, ${images.length} images`);
+    for (const b of this.cameraBuffers.concat(this.ownedTextures)) b.destroy();
+    this.ownedTextures = [];
+    const imgs = images.map((im) => {
+      if (im.texture) return im;
+      const tex = this.device.createBuffer({ size: 4 * im.width * im.height, label: 'eval image' });
+      this.device.queue.writeBuffer(tex, 0, im.bitmap);
+      this.ownedTextures.push(tex);
+      return Object.assign({}, im, { texture: tex });
+    });
+    this.cameras = cameras.map((c, i) => (c.camera ? c : Object.assign({}, c, { camera: require('./loaders.js').cameraUniforms(c, imgs[i].width, imgs[i].height) })));
+    this.images = imgs;
+    this.cameraBuffers = this.cameras.map((c) => {
+      const b = this.device.createBuffer({ size: 272, label: 'eval camera uniform' });
+      this.device.queue.writeBuffer(b, 0, c.camera);
+      return b;
+    });
+  }
+  destroySets() { destroyPassSets(this.sets.values()); this.sets = new Map(); }
+  /** The pass set (no backward pass) for one image size, built through the trainer's newPassSet (live SH-DC words, its long-list settings).  Never a guard. */
+  set(w, h, cam) {
+    const key = `${w}x${h}`;
+    if (!this.sets.has(key)) this.sets.set(key, this.trainer.newPassSet(cam, w, h, false, this.tileEntries || this.maxTileEntries || null));
+    return this.sets.get(key);
+  }
+  followCloud() {
+    const t = this.trainer;
+    if (JSON.stringify(this.longLists) !== JSON.stringify(t.longLists)) {
+      this.destroySets();
+      this.longLists = t.longLists ? Object.assign({}, t.longLists) : null;
+    }
+    for (const { forwardPass: fw } of this.sets.values()) {
+      if (fw.pointCloud !== t.pointCloud && !fw.setPointCloud(t.pointCloud)) { this.destroySets(); break; }
+    }
+    for (const s of this.sets.values()) s.forwardPass.setDcSource(t.dcWords);
+  }
+  /** Waits for the evaluation renders; the entries the largest overflowing one needed, or null (other owners' lines are left for them). */
+  overflow() {
+    const { mine } = this.device.capacityReports.settle([...this.sets.values()].map((s) => s.forwardPass.handle), () => this.device.synchronize());
+    return mine.length ? Math.max(...mine.map((o) => o.needed)) : null;
+  }
+  /** { cams, imgs, bufs, ids } of a split, checked: what evaluate, normalConsistency and contributionStats start with. */
+  views(what, viewIds, split) {
+    const t = this.trainer;
+    if (split !== 'eval' && split !== 'train') throw new Error(`${what}: split must be 'eval' or 'train', not ${split}`);
+    if (!t.pointCloud) throw new Error(`${what}: no point cloud`);
+    const [cams, imgs, bufs] = split === 'eval' ? [this.cameras, this.images, this.cameraBuffers] : [t.trainCameras, t.images, t.cameraBuffers];
+    const ids = viewIds === undefined || viewIds === null ? cams.map((_, i) => i) : viewIds.map((v) => Math.floor(v));
+    for (const v of ids) if (!(v >= 0 && v < cams.length)) throw new RangeError(`${what}: view ${v} of ${cams.length} (${split})`);
+    return { cams, imgs, bufs, ids };
+  }
+  /** Drains the trainer's pipeline in front of renders through the evaluation passes (a training step's overflow is met as step() would have met it). */
+  drain() { try { this.trainer.drain(); } catch (e) { if (!this.trainer.growTileEntryCapacity(e)) throw e; } }
+
+  /** The render loop: every view of `ids` through the evaluation pass set of its size, then each(i, v, passSet, width, height); after an overflow the
+   *  lists are grown, restart() is called and ALL views are rendered again. */
+  renderViews(ids, imgs, bufs, each, restart, what) {
+    while (ids.length) {
+      this.followCloud();
+      ids.forEach((v, i) => {
+        const im = imgs[v], w = im.width, h = im.height;
+        const s = this.set(w, h, bufs[v]);
+        s.forwardPass.setCameraBuffer(bufs[v]);
+        s.forwardPass.encode(null);
+        s.rasterizer.encode(null, w, h);
+        each(i, v, s, w, h);
+      });
+      const needed = this.overflow();
+      if (needed === null) break;
+      const now = Math.max(this.tileEntries, ...[...this.sets.values()].map((s) => Number(s.forwardPass.getResources().maxTileEntries)));
+      const next = hip.grownTileEntries(now, needed);
+      if (next <= now) throw new Error(`${what}: a view needs ${needed} tile entries, more than the lists can hold`);
+      console.warn(`evaluation tile-entry lists grown from ${now} to ${next} entries after an overflow; the views are rendered again`);
+      this.tileEntries = next;
+      this.destroySets();
+      if (restart) restart();
+    }
+  }
+
+  // ---------------------------------------------------------------- held-out evaluation
+  /** PSNR and SSIM of the current model on the evaluation views (split 'eval') or on training views (split 'train'): { iteration, views, psnr, ssim,
+   *  sse, mean_psnr, mean_ssim, ms }.  Drains the pipeline, renders every view through passes of its own, writes view i's SSE and SSIM into slot i
+   *  of two device arrays and reads them back once; a view that overflowed its tile-entry lists is rendered again with larger lists.  Training is
+   *  untouched (no random draw, no training pass, no recording dropped).  Per rank, no collective.  Same results as the Python host's. */
+  evaluate(viewIds, split) {
+    const { imgs, bufs, ids } = this.views('evaluate', viewIds, split || 'eval');
+    const t0 = Date.now();
+    this.drain();
+    const n = ids.length, slots = Math.max(1, n);
+    const out = this.device.createBuffer({ size: 16 * slots, label: 'evaluation sse + ssim' });
+    let raw;
+    try {
+      this.renderViews(ids, imgs, bufs, (i, v, s, w, h) => {
+        const pred = s.rasterizer.getOutputTextureView();
+        hip.encodeImageSSE(this.device, pred, imgs[v].texture, w * h, this.device.view(out.ptr + BigInt(8 * i), 8));
+        hip.encodeImageSSIM(this.device, pred, imgs[v].texture, w, h, this.device.view(out.ptr + BigInt(8 * (slots + i)), 8));
+      }, null, 'evaluate');
+      raw = n ? this.device.readBuffer(out, 16 * slots) : new ArrayBuffer(16);
+    } finally { out.destroy(); }
+    const sse = [...new BigUint64Array(raw, 0, n)].map(Number);
+    const ssim = [...new Float64Array(raw, 8 * slots, n)];
+    const psnr = ids.map((v, i) => hip.psnrFromSSE(sse[i], imgs[v].width * imgs[v].height));
+    const mean = (a) => (a.length ? a.reduce((x, y) => x + y, 0) / a.length : NaN);
+    return { iteration: this.trainer.iteration, views: ids, psnr, ssim, sse, mean_psnr: mean(psnr), mean_ssim: mean(ssim), ms: Date.now() - t0 };
+  }
+
+  // ---------------------------------------------------------------- normal consistency (DESIGN.md section 12)
+  /** How well the composited normals of the current model agree with the normals of its own depth map, per view: { iteration, views, value, pixels,
+   *  sum_e, sum_a, mean, ms } -- value[i] the weight-averaged 1 - cos of normalAgreement between encodeNormal's image and depthToNormals of the
+   *  `depthKind` ('median' | 'expected') depth image, mean the same average over all views' pixels.  Rendered through evaluate's passes with its
+   *  isolation; evaluate()'s result is what it was.  Same results as the Python host's. */
+  normalConsistency(viewIds, split, depthKind) {
+    split = split || 'eval'; depthKind = depthKind || 'median';
+    if (depthKind !== 'median' && depthKind !== 'expected') throw new Error(`normalConsistency: depthKind must be 'median' or 'expected', not ${depthKind}`);
+    const { cams, imgs, bufs, ids } = this.views('normalConsistency', viewIds, split);
+    const t0 = Date.now();
+    this.drain();
+    const n = ids.length, slots = Math.max(1, n);
+    const out = this.device.createBuffer({ size: 24 * slots, label: 'normal agreement sums' });
+    const scratch = this.device.createBuffer({ size: 16 * Math.max(1, ...ids.map((v) => imgs[v].width * imgs[v].height)), label: 'depth normals' });
+    let raw;
+    try {
+      this.renderViews(ids, imgs, bufs, (i, v, s, w, h) => {
+        s.rasterizer.encodeDepth(null, [depthKind]);
+        s.rasterizer.encodeNormal(null);
+        hip.depthToNormals(this.device, s.rasterizer.getDepthTextureView(depthKind), w, h, cams[v].camera, scratch);
+        hip.encodeNormalAgreement(this.device, s.rasterizer.getNormalTextureView(), scratch, w, h, this.device.view(out.ptr + BigInt(24 * i), 24));
+      }, null, 'normalConsistency');
+      raw = n ? this.device.readBuffer(out, 24 * slots) : new ArrayBuffer(24);
+    } finally { scratch.destroy(); out.destroy(); }
+    const sums = [...new BigUint64Array(raw, 0, 3 * n)].map(Number);
+    const col = (k) => ids.map((_, i) => sums[3 * i + k]);
+    const sum_e = col(0), sum_a = col(1), pixels = col(2), total = (a) => a.reduce((x, y) => x + y, 0);
+    return { iteration: this.trainer.iteration, views: ids, value: sum_e.map((e, i) => (sum_a[i] ? e / sum_a[i] : NaN)), pixels, sum_e, sum_a,
+      mean: total(sum_a) ? total(sum_e) / total(sum_a) : NaN, ms: Date.now() - t0 };
+  }
+
+  // ---------------------------------------------------------------- TSDF fusion and mesh extraction (DESIGN.md section 13)
+  /** Fuses the current model's depth maps into `volume` (hip.TSDFVolume): for each view in the order given, the forward pass, rasterize,
+   *  encodeDepth([depthKind, 'weight_sum']) and volume.integrate with the weight sum and the rasterizer's output texture as colour (where the volume
+   *  has colour).  Returns the view list.  Rendered through evaluate's passes with its isolation; a view is integrated only once its render is known
+   *  not to have overflowed its tile-entry lists (one wait per view).  Same results as the Python host's. */
+  fuseDepth(volume, viewIds, split, depthKind) {
+    split = split || 'train'; depthKind = depthKind || 'median';
+    if (depthKind !== 'median' && depthKind !== 'expected') throw new Error(`fuseDepth: depthKind must be 'median' or 'expected', not ${depthKind}`);
+    const { imgs, bufs, ids } = this.views('fuseDepth', viewIds, split);
+    this.drain();
+    for (const v of ids) {
+      this.renderViews([v], imgs, bufs, () => {}, null, 'fuseDepth');   // (returns with the view's complete frame in its pass set)
+      const w = imgs[v].width, h = imgs[v].height, rast = this.set(w, h, bufs[v]).rasterizer;
+      rast.encodeDepth(null, [depthKind, 'weight_sum']);
+      volume.integrate(rast.getDepthTextureView(depthKind), bufs[v], w, h, { weightSum: rast.getDepthTextureView('weight_sum'),
+        colour: volume.colour ? rast.getOutputTextureView() : null });
+    }
+    return ids;
+  }
+  /** Scores the current model's geometry against `reference` -- a Float32Array [M*3] of surface points, or the path of a PLY that holds them:
+   *  extractMesh(lo, hi, voxelSize, options), hip.sampleMesh at options.density samples per unit area (default 1 / (voxelSize / 2)^2, a spacing of half a
+   *  voxel; options.seed, default 0) and hip.geometryMetrics(samples, reference, maxDistance, threshold).  Returns its object -- accuracy, completeness,
+   *  chamfer, precision, recall, fscore and the counts -- with vertices, faces, samples (the mesh's and the sample count) and ms.  extractMesh's isolation
+   *  (fuseDepth's) and its keepLargest, minTriangles, minFraction; no alignment is attempted: the reference is taken to be in the scene's frame. */
+  evaluateGeometry(reference, lo, hi, voxelSize, maxDistance, threshold, options) {
+    const o = options || {}, t0 = Date.now();
+    const ref = typeof reference === 'string' ? require('./loaders.js').loadPointsPLY(reference) : reference;
+    const density = o.density === undefined || o.density === null ? 1.0 / (0.5 * voxelSize) ** 2 : o.density;
+    const mesh = this.extractMesh(lo, hi, voxelSize, o);
+    const samples = hip.sampleMesh(this.device, mesh, density, o.seed || 0, { asBuffers: true });
+    let out;
+    try {
+      out = hip.geometryMetrics(this.device, samples.points, ref, maxDistance, threshold, { numPoints: samples.count });
+    } finally { samples.points.destroy(); samples.face.destroy(); }
+    return Object.assign(out, { vertices: mesh.vertices.length / 3, faces: mesh.faces.length / 3, samples: samples.count, ms: Date.now() - t0 });
+  }
+  /** The current model as a triangle mesh of the box [lo, hi]: TSDFVolume.fromBounds, fuseDepth over the views, extractMesh(minWeight); the volume is
+   *  destroyed.  options: { viewIds, split, depthKind, minWeight, truncation, maxWeight, colour, keepLargest, minTriangles, minFraction }.  With one of the
+   *  last three set the mesh goes through hip.removeSmallComponents (the floaters of a fused mesh are small components of their own) and its object is
+   *  returned; otherwise the raw level set, as before, and nothing more is launched.  loaders.saveMeshPLY writes the result. */
+  extractMesh(lo, hi, voxelSize, options) {
+    const o = options || {};
+    const volume = hip.TSDFVolume.fromBounds(this.device, lo, hi, voxelSize, { truncation: o.truncation, maxWeight: o.maxWeight, colour: o.colour });
+    let mesh;
+    try {
+      this.fuseDepth(volume, o.viewIds, o.split, o.depthKind);
+      mesh = volume.extractMesh(o.minWeight);
+    } finally { volume.destroy(); }
+    const unset = (x) => x === undefined || x === null;
+    if (unset(o.keepLargest) && !(o.minTriangles > 0) && !(o.minFraction > 0)) return mesh;
+    return hip.removeSmallComponents(this.device, mesh, { keepLargest: o.keepLargest, minTriangles: o.minTriangles, minFraction: o.minFraction });
+  }
+
+  // ---------------------------------------------------------------- render contribution (DESIGN.md section 11)
+  /** { stats, ids }: the views' contribution records accumulated into one new device buffer (Trainer.pruneByContribution decides on it). */
+  contributionBuffer(viewIds, split, what) {
+    const { imgs, bufs, ids } = this.views(what, viewIds, split);
+    if (ids.reduce((a, v) => a + imgs[v].width * imgs[v].height, 0) >= 2 ** 32) throw new RangeError(`${what}: the views hold 2^32 pixels or more; the per-Gaussian pixel count is 32 bits wide`);
+    this.drain();
+    const stats = hip.createContributionBuffer(this.device, this.trainer.pointCloud.num_points);
+    try {
+      this.renderViews(ids, imgs, bufs, (i, v, s) => s.rasterizer.encodeContribution(null, stats), () => hip.addon.bufferClear(this.device.handle, stats.ptr, stats.size), what);
+    } catch (e) { stats.destroy(); throw e; }
+    return { stats, ids };
+  }
+  /** How much of each Gaussian the views' images hold: { sum_q, weight_sum, max_weight, pixels, views }, one entry per Gaussian, accumulated over
+   *  the views (default: all training views).  Rendered through evaluate's passes with its isolation (drained pipeline, overflow-and-regrow with the
+   *  records cleared and every view walked again, no random draw, no training pass, no recording dropped).  Same results as the Python host's. */
+  contributionStats(viewIds, split) {
+    const { stats, ids } = this.contributionBuffer(viewIds, split || 'train', 'contributionStats');
+    try { return Object.assign(hip.readContribution(stats, this.trainer.pointCloud.num_points), { views: ids }); } finally { stats.destroy(); }
+  }
+}
+
+exports.Evaluator = Evaluator;   // (assigned, not replaced: trainer.js and this module require each other)

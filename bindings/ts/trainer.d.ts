@@ -3,6 +3,7 @@ import { AdamHyperparameters, ContributionRecords, HipBuffer, HipDevice, Optimiz
 import { CameraData } from './loaders';
 import { LoadedImage } from './images';
 import { Exchange } from './parallel';
+import { Evaluator } from './evaluation';
 
 export interface DensifyPruneTrainingConfig {   // trainer.ts:23-40
   schedule: { enabled: boolean; warmupIterations: number; interval: number; stopIterations: number };
@@ -36,11 +37,7 @@ export class Trainer {
   tileEntries(): number;
   /** Doubles the library-sized tile-entry lists after a WDGS_E_CAPACITY report and rebuilds the passes; false when the caller pinned maxTileEntries. */
   growTileEntryCapacity(error: Error): boolean;
-  /** Entries needed by this trainer's passes among those a capacity report names; [] if it names only other owners' passes; null if it names none. */
-  ownOverflow(error: Error): number[] | null;
-  /** true (after one console.warn) for a capacity report about passes this trainer does not own (a Viewer on the same device). */
-  notOurs(error: Error): boolean;
-  /** device.queue.wait / device.synchronize with other owners' capacity reports filtered out. */
+  /** device.queue.wait / device.synchronize through CapacityReports.settle: a report about this trainer's passes is thrown, other owners' lines are left for them. */
   wait(ticket: number): void;
   synchronize(): void;
   /** Records every view's command buffers up front; the number of steps taken depends on the dataset size only. */
@@ -88,8 +85,11 @@ export class Trainer {
   contributionStats(viewIds?: number[] | null, split?: 'eval' | 'train'): ContributionRecords & { views: number[] };
   /** Contribution-based pruning: kept iff every criterion given is met; fraction f prunes the Gaussians below the k-th smallest sum_q, k = floor(f N). */
   pruneByContribution(options: { minMaxWeight?: number; minWeightSum?: number; minPixels?: number; fraction?: number; viewIds?: number[] | null }): { before: number; after: number; pruned: number };
-  /** Tile-entry lists of evaluate's own passes (0: what the training passes get); an overflowing view grows them and is rendered again. */
+  /** Tile-entry lists of the Evaluator's passes (0: what the training passes get); an overflowing view grows them and is rendered again. */
   evalMaxTileEntries: number;
+  /** The evaluation side (evaluation.js): the methods from setEvaluationViews to contributionStats above delegate to it. */
+  readonly evaluator: Evaluator;
+  readonly evalCameras: TrainingView[]; readonly evalImages: TrainingImage[];
   getTrainingConfig(): TrainingConfig; setTrainingConfig(next: Partial<TrainingConfig>): void;
   getOptimizerHyperparameters(): AdamHyperparameters; setOptimizerHyperparameters(next: Partial<AdamHyperparameters>): void;
   setDensifyPruneConfig(next: Partial<DensifyPruneTrainingConfig>): void;

@@ -18,6 +18,10 @@
  * step() resolves once the PREVIOUS step has finished (tickets: queue.mark / queue.wait), so the device never idles across the step
  * boundary; the single-view step runs K17 + Adam + re-pack as ONE kernel (Optimizer.stepWithGeometry).  Results are bit-identical to the
  * one-lane, depth-1, unfused forms (tests/test_gpu_napi.py compares this host with the Python host byte for byte).
+ *
+ * This class is the training step and what it needs.  Everything that measures the model without training it (evaluate, normalConsistency,
+ * fuseDepth, extractMesh, evaluateGeometry, contributionStats) lives in evaluation.js' Evaluator; the methods of those names here delegate to it.
+ * Every host wait goes through CapacityReports.settle (capacity_reports.js), which sorts the device-wide capacity reports by owner.
  */
 const hip = require('./webdgs_hip.js');
 const parallel = require('./parallel.js');
@@ -45,6 +49,8 @@ class PassSet {
 }
 /** Destroys every pass of `sets`, in set order. */
 function destroyPassSets(sets) { for (const s of sets) s.destroy(); }
+module.exports = { PassSet, destroyPassSets };   // (evaluation.js imports these two; the two modules require each other, so they are there before it loads)
+const evaluation = require('./evaluation.js');
 
 class Trainer {
   /** options: random, useCommandBuffers, maxTileEntries, reusePasses, deferredSH, fuseGeometryAdam, keepGradients, pipelineDepth (1..4),
@@ -97,13 +103,8 @@ class Trainer {
     this.lastDensifyPruneIteration = null; this.lastViewportWidth = 1; this.lastViewportHeight = 1; this.pendingPointCloudSwap = null;
     this.trainCameras = []; this.images = []; this.cameraBuffers = [];
     this.commandBuffers = new Map(); this.eagerSteps = 0;
-    // held-out evaluation (setEvaluationViews / evaluate): views never drawn for training, and render passes of evaluate's own, one
-    // PassSet (no backward pass) per image size, built on first use and following the cloud
-    this.evalCameras = []; this.evalImages = []; this.evalCameraBuffers = []; this.evalOwnedTextures = [];
-    this.evalSets = new Map();
-    this.evalMaxTileEntries = 0;   // tile-entry lists of evaluate's passes (0: what the training passes get)
-    this.evalTileEntries = 0;      // (what an overflowing evaluation view has made of them)
-    this.evalLongLists = null;
+    // held-out evaluation and the other measurements of the model: views never drawn for training and render passes of their own (evaluation.js)
+    this.evaluator = new evaluation.Evaluator(this);
   }
 
   densifyOpConfig() {
@@ -128,11 +129,11 @@ class Trainer {
   get metricsRasterizer() { return this.metricSets.length ? this.metricSets[0].rasterizer : null; }
   get metricsPass() { return this.metricSets.length ? this.metricSets[0].backwardPass : null; }
   get metricsTarget() { return this.metricSets.length ? this.metricSets[0].target : null; }
-  /** The training and metric sets: what a step and a densify event run.  (evaluate's sets follow the cloud and answer capacity reports on their own,
-   *  evalFollowCloud / evalOverflow.) */
+  /** The training and metric sets: what a step and a densify event run.  (The Evaluator's sets follow the cloud and answer capacity reports on their
+   *  own, evaluation.js.) */
   allSets() { return this.trainSets.concat(this.metricSets); }
   forwardPasses() { return this.allSets().map((s) => s.forwardPass); }
-  /** Every pass but the optimizer's and evaluate's goes; ensurePipelines and the first use of a metric set build them anew. */
+  /** Every pass but the optimizer's and the Evaluator's goes; ensurePipelines and the first use of a metric set build them anew. */
   destroyPassSets() { destroyPassSets(this.allSets()); this.trainSets = []; this.metricSets = []; }
   applyPointCloudSwap(request) {   // trainer.ts:201-237
     this.drain();
@@ -386,10 +387,10 @@ class Trainer {
 
   growTileEntryCapacity(error) {
     if (this.maxTileEntries !== 0 || this.device.handle === null) return false;
-    const mine = this.ownOverflow(error) || [];   // (a report about other owners' passes only never gets here: wait / synchronize)
+    const { mine } = hip.CapacityReports.split(error, this.ownHandles());   // (a report about other owners' passes only never gets here: settled)
     let now = Math.max(this.grownTileEntries, 1 << 20);
     for (const fw of this.forwardPasses()) now = Math.max(now, fw.getResources().maxTileEntries);
-    const next = Math.min(Math.max(2 * now, mine.length ? Math.floor(Math.max.apply(null, mine) * 1.5) : 0), 0xFFFFF000);
+    const next = hip.grownTileEntries(now, Math.max(0, ...mine.map((o) => o.needed)));
     if (next <= now) return false;
     console.warn(`tile-entry lists grown from ${now} to ${next} entries after an overflow (${error.message}); the step that overflowed was skipped`);
     this.grownTileEntries = next;
@@ -447,31 +448,22 @@ class Trainer {
     if (this.iteration >= this.maxIterations) this.stop();
   }
 
-  /** What THIS trainer's passes needed (entries) among the passes a capacity report names (csrc/api.hip: deferred_checks names every pass that overflowed),
-   *  [] if it names only other owners' passes, null if it names none (a step skipped on every rank). */
-  ownOverflow(error) {
-    const { mine, others } = hip.CapacityReports.split(error, this.forwardPasses().map((fw) => fw.handle));
-    return mine.length || others ? mine.map((o) => o.needed) : null;
+  ownHandles() { return this.forwardPasses().map((fw) => fw.handle); }
+  /** wait() with the capacity reports sorted by owner (CapacityReports.settle).  A report with a line about THIS trainer's passes is thrown -- also one
+   *  that another owner's wait consumed and left for us (a Viewer reading its frame).  Lines about passes this trainer does not own -- a Viewer rendering
+   *  the same cloud on this device: the report is device-wide, whoever waits first gets it -- are left for the passes' owner, who has to enlarge its
+   *  lists; the trainer says so once. */
+  settled(wait) {
+    const s = this.device.capacityReports.settle(this.ownHandles(), wait);
+    if (s.foreign && !this.foreignOverflowWarned) {
+      const left = this.device.capacityReports.pending[this.device.capacityReports.pending.length - 1];   // (what settle has just posted)
+      console.warn(`a forward pass that is not this trainer's overflowed its tile-entry lists (${left.message}); its owner has to enlarge them`);
+      this.foreignOverflowWarned = true;
+    }
+    if (s.mine.length) throw s.error;
   }
-  /** true (after saying so once) for a capacity report about passes this trainer does not own -- a Viewer rendering the same cloud on this device: the
-   *  report is device-wide, whoever waits first gets it, and it is the pass's owner who has to enlarge its lists. */
-  notOurs(error) {
-    if (!(error && error.code === 'WDGS_E_CAPACITY')) return false;
-    const mine = this.ownOverflow(error);
-    if (mine === null || mine.length) return false;
-    this.device.capacityReports.post(error);   // (for the passes' owner: it looks there at its own next wait)
-    if (!this.foreignOverflowWarned) console.warn(`a forward pass that is not this trainer's overflowed its tile-entry lists (${error.message}); its owner has to enlarge them`);
-    this.foreignOverflowWarned = true;
-    return true;
-  }
-  wait(ticket) { try { this.device.queue.wait(ticket); } catch (e) { if (!this.notOurs(e)) throw e; } this.reportsLeftForUs(); }
-  synchronize() { try { this.device.synchronize(); } catch (e) { if (!this.notOurs(e)) throw e; } this.reportsLeftForUs(); }
-  /** A report about THIS trainer's passes that another owner's wait consumed (a Viewer reading its frame): raised here, as if this wait had got it. */
-  reportsLeftForUs() {
-    if (!this.device.capacityReports.pending.length) return;
-    const e = this.device.capacityReports.take(this.forwardPasses().map((fw) => fw.handle));
-    if (e) throw e;
-  }
+  wait(ticket) { this.settled(() => this.device.queue.wait(ticket)); }
+  synchronize() { this.settled(() => this.device.synchronize()); }
 
   /** `await onSubmittedWorkDone()` (trainer.ts:639-645) + the deferred capacity check.  Depth 1: this step's own completion, through the
    *  Promise, as the reference awaits it.  Depth d > 1: a ticket for this step is kept and the step d - 1 submissions ago is awaited. */
@@ -702,225 +694,28 @@ class Trainer {
     this.lastDensifyPruneIteration = this.iteration;
   }
 
-  // ---------------------------------------------------------------- held-out evaluation (no reference counterpart)
-  /** Views to evaluate on and never to train on (loaders.holdoutSplit gives the every-8th test views of the 3DGS convention).  Same shapes as
-   *  setDataset; the images may have another size than the training images. */
-  setEvaluationViews(cameras, images) {
-    if (cameras.length !== images.length) throw new Error(`setEvaluationViews: ${cameras.length} cameras, ${images.length} images`);
-    for (const b of this.evalCameraBuffers.concat(this.evalOwnedTextures)) b.destroy();
-    this.evalOwnedTextures = [];
-    const imgs = images.map((im) => {
-      if (im.texture) return im;
-      const tex = this.device.createBuffer({ size: 4 * im.width * im.height, label: 'eval image' });
-      this.device.queue.writeBuffer(tex, 0, im.bitmap);
-      this.evalOwnedTextures.push(tex);
-      return Object.assign({}, im, { texture: tex });
-    });
-    this.evalCameras = cameras.map((c, i) => (c.camera ? c : Object.assign({}, c, { camera: require('./loaders.js').cameraUniforms(c, imgs[i].width, imgs[i].height) })));
-    this.evalImages = imgs;
-    this.evalCameraBuffers = this.evalCameras.map((c) => {
-      const b = this.device.createBuffer({ size: 272, label: 'eval camera uniform' });
-      this.device.queue.writeBuffer(b, 0, c.camera);
-      return b;
-    });
-  }
-  destroyEvalSets() { destroyPassSets(this.evalSets.values()); this.evalSets = new Map(); }
-  /** evaluate's pass set (no backward pass) for one image size, built through newForwardPass (live SH-DC words, this trainer's long-list settings).  Never a guard. */
-  evalSet(w, h, cam) {
-    const key = `${w}x${h}`;
-    if (!this.evalSets.has(key)) this.evalSets.set(key, this.newPassSet(cam, w, h, false, this.evalTileEntries || this.evalMaxTileEntries || null));
-    return this.evalSets.get(key);
-  }
-  evalFollowCloud() {
-    if (JSON.stringify(this.evalLongLists) !== JSON.stringify(this.longLists)) {
-      this.destroyEvalSets();
-      this.evalLongLists = this.longLists ? Object.assign({}, this.longLists) : null;
-    }
-    for (const { forwardPass: fw } of this.evalSets.values()) {
-      if (fw.pointCloud !== this.pointCloud && !fw.setPointCloud(this.pointCloud)) { this.destroyEvalSets(); break; }
-    }
-    for (const s of this.evalSets.values()) s.forwardPass.setDcSource(this.dcWords);
-  }
-  /** Waits for the evaluation renders; the entries the largest overflowing one needed, or null (Trainer.py _eval_overflow). */
-  evalOverflow() {
-    const own = [...this.evalSets.values()].map((s) => s.forwardPass.handle);
-    let err = null;
-    try {
-      this.device.synchronize();
-      if (this.device.capacityReports.pending.length) err = this.device.capacityReports.take(own);
-    } catch (e) {
-      if (!(e && e.code === 'WDGS_E_CAPACITY')) throw e;
-      err = e;
-    }
-    if (!err) return null;
-    const { mine, others } = hip.CapacityReports.split(err, own);
-    if (others) this.device.capacityReports.post(err);
-    if (!mine.length && !others) throw err;
-    return mine.length ? Math.max(...mine.map((o) => o.needed)) : null;
-  }
-  /** PSNR and SSIM of the current model on the evaluation views (split 'eval') or on training views (split 'train'): { iteration, views, psnr, ssim,
-   *  sse, mean_psnr, mean_ssim, ms }.  Drains the pipeline, renders every view through passes of its own, writes view i's SSE and SSIM into slot i
-   *  of two device arrays and reads them back once; a view that overflowed its tile-entry lists is rendered again with larger lists.  Training is
-   *  untouched (no random draw, no training pass, no recording dropped).  Per rank, no collective.  Same results as the Python host's. */
-  /** { cams, imgs, bufs, ids } of a split, checked: what evaluate, normalConsistency and contributionStats start with. */
-  evalViews(what, viewIds, split) {
-    if (split !== 'eval' && split !== 'train') throw new Error(`${what}: split must be 'eval' or 'train', not ${split}`);
-    if (!this.pointCloud) throw new Error(`${what}: no point cloud`);
-    const [cams, imgs, bufs] = split === 'eval' ? [this.evalCameras, this.evalImages, this.evalCameraBuffers] : [this.trainCameras, this.images, this.cameraBuffers];
-    const ids = viewIds === undefined || viewIds === null ? cams.map((_, i) => i) : viewIds.map((v) => Math.floor(v));
-    for (const v of ids) if (!(v >= 0 && v < cams.length)) throw new RangeError(`${what}: view ${v} of ${cams.length} (${split})`);
-    return { cams, imgs, bufs, ids };
-  }
-  /** Drains the pipeline in front of renders through the evaluation passes (a training step's overflow is met as step() would have met it). */
-  evalDrain() { try { this.drain(); } catch (e) { if (!this.growTileEntryCapacity(e)) throw e; } }
-  evaluate(viewIds, split) {
-    const { imgs, bufs, ids } = this.evalViews('evaluate', viewIds, split || 'eval');
-    const t0 = Date.now();
-    this.evalDrain();
-    const n = ids.length, slots = Math.max(1, n);
-    const out = this.device.createBuffer({ size: 16 * slots, label: 'evaluation sse + ssim' });
-    this.renderEvalViews(ids, imgs, bufs, (i, v, s, w, h) => {
-      const pred = s.rasterizer.getOutputTextureView();
-      hip.encodeImageSSE(this.device, pred, imgs[v].texture, w * h, this.device.view(out.ptr + BigInt(8 * i), 8));
-      hip.encodeImageSSIM(this.device, pred, imgs[v].texture, w, h, this.device.view(out.ptr + BigInt(8 * (slots + i)), 8));
-    }, null, 'evaluate');
-    const raw = n ? this.device.readBuffer(out, 16 * slots) : new ArrayBuffer(16);
-    out.destroy();
-    const sse = [...new BigUint64Array(raw, 0, n)].map(Number);
-    const ssim = [...new Float64Array(raw, 8 * slots, n)];
-    const psnr = ids.map((v, i) => hip.psnrFromSSE(sse[i], imgs[v].width * imgs[v].height));
-    const mean = (a) => (a.length ? a.reduce((x, y) => x + y, 0) / a.length : NaN);
-    return { iteration: this.iteration, views: ids, psnr, ssim, sse, mean_psnr: mean(psnr), mean_ssim: mean(ssim), ms: Date.now() - t0 };
-  }
+  // ---------------------------------------------------------------- evaluation and analysis: all of it is the Evaluator's (evaluation.js)
+  get evalCameras() { return this.evaluator.cameras; }
+  get evalImages() { return this.evaluator.images; }
+  /** Tile-entry lists of the Evaluator's passes (0: what the training passes get). */
+  get evalMaxTileEntries() { return this.evaluator.maxTileEntries; }
+  set evalMaxTileEntries(n) { this.evaluator.maxTileEntries = n; }
+  /** Evaluator.setEvaluationViews: views to evaluate on and never to train on. */
+  setEvaluationViews(cameras, images) { this.evaluator.setEvaluationViews(cameras, images); }
+  /** Evaluator.evaluate: PSNR and SSIM of the current model on the evaluation or the training views; training is untouched. */
+  evaluate(viewIds, split) { return this.evaluator.evaluate(viewIds, split); }
+  /** Evaluator.normalConsistency: agreement of the composited normals with the normals of the model's own depth map. */
+  normalConsistency(viewIds, split, depthKind) { return this.evaluator.normalConsistency(viewIds, split, depthKind); }
+  /** Evaluator.fuseDepth: fuses the current model's depth maps into `volume`. */
+  fuseDepth(volume, viewIds, split, depthKind) { return this.evaluator.fuseDepth(volume, viewIds, split, depthKind); }
+  /** Evaluator.evaluateGeometry: the extracted mesh scored against a reference point set. */
+  evaluateGeometry(reference, lo, hi, voxelSize, maxDistance, threshold, options) { return this.evaluator.evaluateGeometry(reference, lo, hi, voxelSize, maxDistance, threshold, options); }
+  /** Evaluator.extractMesh: the current model as a triangle mesh of the box [lo, hi]. */
+  extractMesh(lo, hi, voxelSize, options) { return this.evaluator.extractMesh(lo, hi, voxelSize, options); }
+  /** Evaluator.contributionStats: how much of each Gaussian the views' images hold. */
+  contributionStats(viewIds, split) { return this.evaluator.contributionStats(viewIds, split); }
 
-  /** evaluate's render loop, shared with contributionStats: every view of `ids` through the evaluation pass set of its size, then
-   *  each(i, v, passSet, width, height); after an overflow the lists are grown, restart() is called and ALL views are rendered again. */
-  renderEvalViews(ids, imgs, bufs, each, restart, what) {
-    while (ids.length) {
-      this.evalFollowCloud();
-      ids.forEach((v, i) => {
-        const im = imgs[v], w = im.width, h = im.height;
-        const s = this.evalSet(w, h, bufs[v]);
-        s.forwardPass.setCameraBuffer(bufs[v]);
-        s.forwardPass.encode(null);
-        s.rasterizer.encode(null, w, h);
-        each(i, v, s, w, h);
-      });
-      const needed = this.evalOverflow();
-      if (needed === null) break;
-      const now = Math.max(this.evalTileEntries, ...[...this.evalSets.values()].map((s) => Number(s.forwardPass.getResources().maxTileEntries)));
-      const next = Math.min(Math.max(2 * now, Math.floor(needed * 1.5)), 0xFFFFF000);
-      if (next <= now) throw new Error(`${what}: a view needs ${needed} tile entries, more than the lists can hold`);
-      console.warn(`evaluation tile-entry lists grown from ${now} to ${next} entries after an overflow; the views are rendered again`);
-      this.evalTileEntries = next;
-      this.destroyEvalSets();
-      if (restart) restart();
-    }
-  }
-
-  // ---------------------------------------------------------------- normal consistency (DESIGN.md section 12; no reference counterpart)
-  /** How well the composited normals of the current model agree with the normals of its own depth map, per view: { iteration, views, value, pixels,
-   *  sum_e, sum_a, mean, ms } -- value[i] the weight-averaged 1 - cos of normalAgreement between encodeNormal's image and depthToNormals of the
-   *  `depthKind` ('median' | 'expected') depth image, mean the same average over all views' pixels.  Rendered through evaluate's passes with its
-   *  isolation; evaluate()'s result is what it was.  Same results as the Python host's. */
-  normalConsistency(viewIds, split, depthKind) {
-    split = split || 'eval'; depthKind = depthKind || 'median';
-    if (depthKind !== 'median' && depthKind !== 'expected') throw new Error(`normalConsistency: depthKind must be 'median' or 'expected', not ${depthKind}`);
-    const { cams, imgs, bufs, ids } = this.evalViews('normalConsistency', viewIds, split);
-    const t0 = Date.now();
-    this.evalDrain();
-    const n = ids.length, slots = Math.max(1, n);
-    const out = this.device.createBuffer({ size: 24 * slots, label: 'normal agreement sums' });
-    const scratch = this.device.createBuffer({ size: 16 * Math.max(1, ...ids.map((v) => imgs[v].width * imgs[v].height)), label: 'depth normals' });
-    let raw;
-    try {
-      this.renderEvalViews(ids, imgs, bufs, (i, v, s, w, h) => {
-        s.rasterizer.encodeDepth(null, [depthKind]);
-        s.rasterizer.encodeNormal(null);
-        hip.depthToNormals(this.device, s.rasterizer.getDepthTextureView(depthKind), w, h, cams[v].camera, scratch);
-        hip.encodeNormalAgreement(this.device, s.rasterizer.getNormalTextureView(), scratch, w, h, this.device.view(out.ptr + BigInt(24 * i), 24));
-      }, null, 'normalConsistency');
-      raw = n ? this.device.readBuffer(out, 24 * slots) : new ArrayBuffer(24);
-    } finally { scratch.destroy(); out.destroy(); }
-    const sums = [...new BigUint64Array(raw, 0, 3 * n)].map(Number);
-    const col = (k) => ids.map((_, i) => sums[3 * i + k]);
-    const sum_e = col(0), sum_a = col(1), pixels = col(2), total = (a) => a.reduce((x, y) => x + y, 0);
-    return { iteration: this.iteration, views: ids, value: sum_e.map((e, i) => (sum_a[i] ? e / sum_a[i] : NaN)), pixels, sum_e, sum_a,
-      mean: total(sum_a) ? total(sum_e) / total(sum_a) : NaN, ms: Date.now() - t0 };
-  }
-
-  // ---------------------------------------------------------------- TSDF fusion and mesh extraction (DESIGN.md section 13; no reference counterpart)
-  /** Fuses the current model's depth maps into `volume` (hip.TSDFVolume): for each view in the order given, the forward pass, rasterize,
-   *  encodeDepth([depthKind, 'weight_sum']) and volume.integrate with the weight sum and the rasterizer's output texture as colour (where the volume
-   *  has colour).  Returns the view list.  Rendered through evaluate's passes with its isolation; a view is integrated only once its render is known
-   *  not to have overflowed its tile-entry lists (one wait per view).  Same results as the Python host's. */
-  fuseDepth(volume, viewIds, split, depthKind) {
-    split = split || 'train'; depthKind = depthKind || 'median';
-    if (depthKind !== 'median' && depthKind !== 'expected') throw new Error(`fuseDepth: depthKind must be 'median' or 'expected', not ${depthKind}`);
-    const { imgs, bufs, ids } = this.evalViews('fuseDepth', viewIds, split);
-    this.evalDrain();
-    for (const v of ids) {
-      this.renderEvalViews([v], imgs, bufs, () => {}, null, 'fuseDepth');   // (returns with the view's complete frame in its pass set)
-      const w = imgs[v].width, h = imgs[v].height, rast = this.evalSet(w, h, bufs[v]).rasterizer;
-      rast.encodeDepth(null, [depthKind, 'weight_sum']);
-      volume.integrate(rast.getDepthTextureView(depthKind), bufs[v], w, h, { weightSum: rast.getDepthTextureView('weight_sum'),
-        colour: volume.colour ? rast.getOutputTextureView() : null });
-    }
-    return ids;
-  }
-  /** Scores the current model's geometry against `reference` -- a Float32Array [M*3] of surface points, or the path of a PLY that holds them:
-   *  extractMesh(lo, hi, voxelSize, options), hip.sampleMesh at options.density samples per unit area (default 1 / (voxelSize / 2)^2, a spacing of half a
-   *  voxel; options.seed, default 0) and hip.geometryMetrics(samples, reference, maxDistance, threshold).  Returns its object -- accuracy, completeness,
-   *  chamfer, precision, recall, fscore and the counts -- with vertices, faces, samples (the mesh's and the sample count) and ms.  extractMesh's isolation
-   *  (fuseDepth's) and its keepLargest, minTriangles, minFraction; no alignment is attempted: the reference is taken to be in the scene's frame. */
-  evaluateGeometry(reference, lo, hi, voxelSize, maxDistance, threshold, options) {
-    const o = options || {}, t0 = Date.now();
-    const ref = typeof reference === 'string' ? require('./loaders.js').loadPointsPLY(reference) : reference;
-    const density = o.density === undefined || o.density === null ? 1.0 / (0.5 * voxelSize) ** 2 : o.density;
-    const mesh = this.extractMesh(lo, hi, voxelSize, o);
-    const samples = hip.sampleMesh(this.device, mesh, density, o.seed || 0, { asBuffers: true });
-    let out;
-    try {
-      out = hip.geometryMetrics(this.device, samples.points, ref, maxDistance, threshold, { numPoints: samples.count });
-    } finally { samples.points.destroy(); samples.face.destroy(); }
-    return Object.assign(out, { vertices: mesh.vertices.length / 3, faces: mesh.faces.length / 3, samples: samples.count, ms: Date.now() - t0 });
-  }
-  /** The current model as a triangle mesh of the box [lo, hi]: TSDFVolume.fromBounds, fuseDepth over the views, extractMesh(minWeight); the volume is
-   *  destroyed.  options: { viewIds, split, depthKind, minWeight, truncation, maxWeight, colour, keepLargest, minTriangles, minFraction }.  With one of the
-   *  last three set the mesh goes through hip.removeSmallComponents (the floaters of a fused mesh are small components of their own) and its object is
-   *  returned; otherwise the raw level set, as before, and nothing more is launched.  loaders.saveMeshPLY writes the result. */
-  extractMesh(lo, hi, voxelSize, options) {
-    const o = options || {};
-    const volume = hip.TSDFVolume.fromBounds(this.device, lo, hi, voxelSize, { truncation: o.truncation, maxWeight: o.maxWeight, colour: o.colour });
-    let mesh;
-    try {
-      this.fuseDepth(volume, o.viewIds, o.split, o.depthKind);
-      mesh = volume.extractMesh(o.minWeight);
-    } finally { volume.destroy(); }
-    const unset = (x) => x === undefined || x === null;
-    if (unset(o.keepLargest) && !(o.minTriangles > 0) && !(o.minFraction > 0)) return mesh;
-    return hip.removeSmallComponents(this.device, mesh, { keepLargest: o.keepLargest, minTriangles: o.minTriangles, minFraction: o.minFraction });
-  }
-
-  // ---------------------------------------------------------------- render contribution and contribution-based pruning (no reference counterpart)
-  /** { stats, ids }: the views' contribution records (DESIGN.md section 11) accumulated into one new device buffer. */
-  contributionBuffer(viewIds, split, what) {
-    const { imgs, bufs, ids } = this.evalViews(what, viewIds, split);
-    if (ids.reduce((a, v) => a + imgs[v].width * imgs[v].height, 0) >= 2 ** 32) throw new RangeError(`${what}: the views hold 2^32 pixels or more; the per-Gaussian pixel count is 32 bits wide`);
-    this.evalDrain();
-    const stats = hip.createContributionBuffer(this.device, this.pointCloud.num_points);
-    try {
-      this.renderEvalViews(ids, imgs, bufs, (i, v, s) => s.rasterizer.encodeContribution(null, stats), () => hip.addon.bufferClear(this.device.handle, stats.ptr, stats.size), what);
-    } catch (e) { stats.destroy(); throw e; }
-    return { stats, ids };
-  }
-  /** How much of each Gaussian the views' images hold: { sum_q, weight_sum, max_weight, pixels, views }, one entry per Gaussian, accumulated over
-   *  the views (default: all training views).  Rendered through evaluate's passes with its isolation (drained pipeline, overflow-and-regrow with the
-   *  records cleared and every view walked again, no random draw, no training pass, no recording dropped).  Same results as the Python host's. */
-  contributionStats(viewIds, split) {
-    const { stats, ids } = this.contributionBuffer(viewIds, split || 'train', 'contributionStats');
-    try { return Object.assign(hip.readContribution(stats, this.pointCloud.num_points), { views: ids }); } finally { stats.destroy(); }
-  }
+  // ---------------------------------------------------------------- contribution-based pruning (no reference counterpart)
   /** Removes the Gaussians the training views need least: kept iff the Gaussian meets every criterion given -- { minMaxWeight, minWeightSum,
    *  minPixels, fraction, viewIds }; with fraction f, sum_q not below the k-th smallest sum_q, k = floor(f N) (at most k go; ties stay).  Survivors,
    *  SH rows and optimizer state are compacted in index order, bit for bit, and the cloud is swapped as after a densify event.  { before, after,
@@ -932,7 +727,7 @@ class Trainer {
     if (!(minMaxWeight >= 0 && minWeightSum >= 0 && minPixels >= 0 && fraction >= 0 && fraction < 1)) throw new RangeError('pruneByContribution: the thresholds must be >= 0 and fraction in [0, 1)');
     if (!(minMaxWeight || minWeightSum || minPixels || fraction)) throw new Error('pruneByContribution: give at least one of minMaxWeight, minWeightSum, minPixels, fraction');
     if (!this.optimizer || !this.densifyPrune) throw new Error('pruneByContribution: no point cloud');
-    const { stats } = this.contributionBuffer(o.viewIds, 'train', 'pruneByContribution');
+    const { stats } = this.evaluator.contributionBuffer(o.viewIds, 'train', 'pruneByContribution');
     try {
       const n = this.pointCloud.num_points, unchanged = { before: n, after: n, pruned: 0 };
       const rule = { minMaxWeight, minWeightSum, minPixels: Math.floor(minPixels), minSumQ: 0n };
@@ -966,10 +761,10 @@ class Trainer {
       try { this.device.synchronize(); } catch (_e) { /* a deferred report about a step of a trainer that is going away */ }
     }
     this.invalidateCommandBuffers();
-    this.destroyPassSets(); this.destroyEvalSets();
+    this.destroyPassSets(); this.evaluator.destroy();
     for (const name of ['optimizer', 'densifyPrune']) { if (this[name]) this[name].destroy(); this[name] = null; }
-    for (const b of this.cameraBuffers.concat(this.evalCameraBuffers, this.evalOwnedTextures)) b.destroy();
-    this.cameraBuffers = []; this.evalCameraBuffers = []; this.evalOwnedTextures = [];
+    for (const b of this.cameraBuffers) b.destroy();
+    this.cameraBuffers = [];
     for (const t of this.ownedTextures || []) t.destroy();
     this.ownedTextures = [];
     for (const name of ['dpGrad', 'dpVisible', 'dpRows', 'dpFlag', 'agreeWord']) { if (this[name]) this[name].destroy(); this[name] = null; }
@@ -979,4 +774,4 @@ class Trainer {
 }
 Trainer.DEFAULT_LANES = 3;
 
-module.exports = { Trainer, cameraBlockFor, mat4Inverse, projectionMatrix, DEFAULT_DENSIFY };
+Object.assign(module.exports, { Trainer, cameraBlockFor, mat4Inverse, projectionMatrix, DEFAULT_DENSIFY });

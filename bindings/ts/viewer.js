@@ -78,18 +78,12 @@ class Viewer {
    *  device are left to them. */
   settleCapacity(rerender) {
     for (let attempt = 0; attempt < 4 && this.forwardPass; attempt++) {   // this viewer's own pass: its word is consumed by its own check
-      try {
-        this.forwardPass.check();
-        const left = this.device.capacityReports.take([this.forwardPass.handle]);   // (consumed by another owner's wait, left for us)
-        if (left) throw left;
-        break;
-      } catch (e) {
-        const mine = e && e.code === 'WDGS_E_CAPACITY' ? hip.CapacityReports.split(e, [this.forwardPass.handle]).mine : [];   // (a report names up to four passes: this viewer's line)
-        if (!mine.length) throw e;
-        this.tileEntries = Math.min(Math.max(2 * mine[0].capacity, Math.floor(mine[0].needed * 1.5)), 0xFFFFF000);
-        this.buildPasses();
-        rerender();
-      }
+      // (a report about this pass that another owner's wait consumed was left in device.capacityReports: settle finds it there)
+      const { mine } = this.device.capacityReports.settle([this.forwardPass.handle], () => this.forwardPass.check());
+      if (!mine.length) break;
+      this.tileEntries = hip.grownTileEntries(mine[0].capacity, mine[0].needed);
+      this.buildPasses();
+      rerender();
     }
   }
   /** The presented image as a Uint8Array of width * height * 4 bytes (synchronises). */

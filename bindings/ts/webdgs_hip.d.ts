@@ -17,19 +17,9 @@ export class HipEncoder {
   finish(): HipCommandBuffer;
   abort(): void;
 }
-/** Capacity reports that reached the wrong owner (a Trainer and a Viewer sharing a device): left here for the owner of the passes they name. */
-export interface Overflow { needed: number; capacity: number; handle: bigint; }
-export class CapacityReports {
-  constructor(keep?: number);
-  pending: Error[];
-  /** One record per pass a capacity report names (csrc/api.hip: deferred_checks, wdgs_tiled_forward_check), in its order; [] for any other error. */
-  static parse(error: Error): Overflow[];
-  /** The records about `ownHandles`' passes, and whether the report also names passes of another owner. */
-  static split(error: Error, ownHandles: Array<bigint | number>): { mine: Overflow[]; others: boolean };
-  static passesNamed(error: Error): bigint[];
-  post(error: Error): void;
-  take(ownHandles: Array<bigint | number>): Error | null;
-}
+// capacity reports and the growth rule of tile-entry lists live in capacity_reports.js (no addon needed) and are re-exported here
+import { CapacityReports } from './capacity_reports';
+export { CapacityReports, Overflow, Settled, grownTileEntries } from './capacity_reports';
 export class HipDevice {
   constructor(ordinal?: number);
   readonly capacityReports: CapacityReports;

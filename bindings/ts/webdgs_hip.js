@@ -60,37 +60,8 @@ class HipEncoder {
   abort() { if (this.open) { this.open = false; addon.encoderAbort(this.device.handle); } }
 }
 
-/** Capacity reports that reached the wrong owner.  The library reports a truncated tile-entry list at the next host wait on the DEVICE, to whoever waits
- *  (csrc/api.hip: deferred_checks consumes every pass's word and names the passes); a Trainer and a Viewer that share a device each handle the reports
- *  that name their own passes -- and leave the others here, where the passes' owner looks at its own next wait. */
-class CapacityReports {
-  constructor(keep) { this.pending = []; this.keep = keep || 16; }
-  /** [{ needed, capacity, handle }] -- one record per pass the report names, in the report's order (handle: a BigInt); [] for any other error.  The one
-   *  reader of report text (webdgs_amd/ops.py has its twin).  It follows two format strings of csrc/api.hip:
-   *    deferred_checks:          "tile entries overflow: " + "%u entries needed, max_tile_entries = %u (forward pass %p)" joined by "; " + " (raise ...)"
-   *    wdgs_tiled_forward_check: "tile entries overflow: %u entries needed, max_tile_entries = %u (forward pass %p)"
-   *  Known limit: the library names at most four passes per report; a fifth that overflowed in the same wait is consumed unnamed. */
-  static parse(error) {
-    const out = [], re = /(\d+) entries needed, max_tile_entries = (\d+) \(forward pass (0x[0-9a-fA-F]+)\)/g, text = String(error && error.message);
-    for (let m = re.exec(text); m; m = re.exec(text)) out.push({ needed: Number(m[1]), capacity: Number(m[2]), handle: BigInt(m[3]) });
-    return out;
-  }
-  /** { mine, others }: the records about `ownHandles`' passes, and whether the report also names passes of another owner. */
-  static split(error, ownHandles) {
-    const own = ownHandles.map((h) => BigInt(h)), named = CapacityReports.parse(error);
-    const mine = named.filter((o) => own.some((h) => h === o.handle));
-    return { mine, others: mine.length < named.length };
-  }
-  static passesNamed(error) { return CapacityReports.parse(error).map((o) => o.handle); }
-  post(error) { this.pending.push(error); if (this.pending.length > this.keep) this.pending.splice(0, this.pending.length - this.keep); }
-  /** The oldest pending report that names one of `ownHandles` (removed), or null. */
-  take(ownHandles) {
-    for (let i = 0; i < this.pending.length; i++) {
-      if (CapacityReports.split(this.pending[i], ownHandles).mine.length) return this.pending.splice(i, 1)[0];
-    }
-    return null;
-  }
-}
+// capacity reports and the growth rule of tile-entry lists: plain JavaScript of its own (loadable without the addon), re-exported below
+const { CapacityReports, grownTileEntries } = require('./capacity_reports.js');
 
 class HipDevice {                        // GPUDevice + GPUQueue
   constructor(ordinal) {
@@ -1003,6 +974,6 @@ const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
 module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
-  geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
+  geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, grownTileEntries, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

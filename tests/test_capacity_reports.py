@@ -1,4 +1,4 @@
-"""CPU: the mailbox for capacity reports that reached the wrong owner (ops.CapacityReports; bindings/ts/webdgs_hip.js mirrors it).  The library reports
+"""CPU: the mailbox for capacity reports that reached the wrong owner (ops.CapacityReports; bindings/ts/capacity_reports.js mirrors it).  The library reports
 a truncated tile-entry list device-wide, to whoever waits first (csrc/api.hip: deferred_checks); a Trainer and a Viewer on one device each keep the
 reports about their own passes and leave the others for the owner (dropped, such a report was lost to the owner)."""
 import json
@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REPORTS_JS = os.path.join(ROOT, "bindings", "ts", "capacity_reports.js")   # (plain JavaScript: loads without the N-API addon)
 
 
 def _report(*passes):
@@ -39,8 +40,8 @@ def test_reports_wait_for_the_owner_of_the_passes_they_name():
 
 def test_the_node_host_keeps_the_same_mailbox():
     node = shutil.which("node")
-    if not node or not os.path.exists(os.path.join(ROOT, "bindings", "napi", "webdgs_napi.node")):
-        pytest.skip("node or the N-API addon is not available")
+    if not node:
+        pytest.skip("node is not available")
     src = """
       const { CapacityReports } = require(process.argv[1]);
       const rep = (n, h) => new Error(`tile entries overflow: ${n} entries needed, max_tile_entries = 1048576 (forward pass 0x${h.toString(16)})`);
@@ -51,14 +52,12 @@ def test_the_node_host_keeps_the_same_mailbox():
       out.push(box.pending.length === 3, /^tile entries overflow: 2 /.test(box.take([0x7000]).message));
       console.log(JSON.stringify(out));
     """
-    r = subprocess.run([node, "-e", src, os.path.join(ROOT, "bindings", "ts", "webdgs_hip.js")], capture_output=True, text=True, timeout=120)
-    if r.returncode != 0 and "libamdhip64" in r.stderr + r.stdout:
-        pytest.skip("the addon needs the HIP runtime to load")
+    r = subprocess.run([node, "-e", src, REPORTS_JS], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
     assert json.loads(r.stdout.strip().splitlines()[-1]) == [True] * 5
 
 
-# ---- the report parser (ops.CapacityReports.parse / split; webdgs_hip.js mirrors it), on exact copies of the library's two message forms (csrc/api.hip)
+# ---- the report parser (ops.CapacityReports.parse / split; capacity_reports.js mirrors it), on exact copies of the library's two message forms (csrc/api.hip)
 def _line(needed, capacity, handle):
     return f"{needed} entries needed, max_tile_entries = {capacity} (forward pass {handle:#x})"   # "%u entries needed, max_tile_entries = %u (forward pass %p)"
 
@@ -105,8 +104,8 @@ def test_split_tells_own_passes_from_other_owners():
 
 def test_the_node_host_parses_and_splits_the_same():
     node = shutil.which("node")
-    if not node or not os.path.exists(os.path.join(ROOT, "bindings", "napi", "webdgs_napi.node")):
-        pytest.skip("node or the N-API addon is not available")
+    if not node:
+        pytest.skip("node is not available")
     src = """
       const { CapacityReports } = require(process.argv[1]);
       const passes = JSON.parse(process.argv[2]).map((p) => ({ needed: p[0], capacity: p[1], handle: BigInt(p[2]) }));
@@ -123,12 +122,140 @@ def test_the_node_host_parses_and_splits_the_same():
       s = CapacityReports.split(deferred([a]), []); out.push(s.mine.length === 0 && s.others === true);
       console.log(JSON.stringify(out));
     """
-    r = subprocess.run([node, "-e", src, os.path.join(ROOT, "bindings", "ts", "webdgs_hip.js"), json.dumps([[n, c, hex(h)] for n, c, h in PASSES]), SKIPPED],
+    r = subprocess.run([node, "-e", src, REPORTS_JS, json.dumps([[n, c, hex(h)] for n, c, h in PASSES]), SKIPPED],
                        capture_output=True, text=True, timeout=120)
-    if r.returncode != 0 and "libamdhip64" in r.stderr + r.stdout:
-        pytest.skip("the addon needs the HIP runtime to load")
     assert r.returncode == 0, r.stderr[-2000:]
     assert json.loads(r.stdout.strip().splitlines()[-1]) == [True] * 10
+
+
+# ---- settle: the one routine every owner of forward passes waits through (ops.CapacityReports.settle; capacity_reports.js mirrors it), with a fake wait
+A, B, C = PASSES[:3]          # a and c are the owner's passes, b is another owner's
+OWN = [A[2], C[2]]
+GROWN = [((1 << 20, (1 << 20) + 1), 2 << 20), ((1 << 20, 4_000_000), 6_000_000), ((0xFFFFF000, 5_000_000_000), 0xFFFFF000), ((3, 3), 6)]
+
+
+def _raises(error):
+    def wait():
+        if error is not None:
+            raise error
+    return wait
+
+
+def _capacity(*passes):
+    from webdgs_amd.ops import CapacityError
+    return CapacityError(-3, "tile entries overflow: " + "; ".join(_line(*p) for p in passes) + " (raise wdgs_tiled_forward_config.max_tile_entries)")
+
+
+def test_settle_returns_nothing_when_nothing_was_reported():
+    from webdgs_amd.ops import CapacityReports, Settled
+    box = CapacityReports()
+    assert box.settle(OWN, _raises(None)) == Settled([], False, None) and box.pending == []
+
+
+def test_settle_keeps_a_report_about_own_passes_whole():
+    from webdgs_amd.ops import CapacityReports, Overflow
+    box, report = CapacityReports(), _capacity(C, A)
+    got = box.settle(OWN, _raises(report))
+    assert got.mine == [Overflow(*C), Overflow(*A)] and got.foreign is False and got.error is report   # (the report's order)
+    assert box.pending == []
+
+
+def test_settle_leaves_a_report_about_others_for_them():
+    from webdgs_amd.ops import CapacityReports, Overflow
+    box = CapacityReports()
+    got = box.settle([A[2]], _raises(_capacity(B, C)))
+    assert got.mine == [] and got.foreign is True and got.error is None
+    assert len(box.pending) == 1 and CapacityReports.parse(box.pending[0]) == [Overflow(*B), Overflow(*C)]
+    assert box.take([A[2]]) is None
+
+
+def test_settle_splits_a_mixed_report_between_its_owners():
+    from webdgs_amd.ops import CapacityReports, Overflow
+    box, report = CapacityReports(), _capacity(A, B, C)
+    got = box.settle(OWN, _raises(report))
+    assert got.mine == [Overflow(*A), Overflow(*C)] and got.foreign is True and got.error is report
+    assert len(box.pending) == 1 and CapacityReports.parse(box.pending[0]) == [Overflow(*B)]
+    assert box.take(OWN) is None
+    left = box.take([B[2]])
+    assert left is not None and CapacityReports.parse(left) == [Overflow(*B)] and box.pending == []
+
+
+def test_settle_sorts_a_pending_report_by_the_same_rule():
+    from webdgs_amd.ops import CapacityReports, Overflow
+    box, report = CapacityReports(), _capacity(B, A)
+    box.post(report)
+    got = box.settle(OWN, _raises(None))
+    assert got.mine == [Overflow(*A)] and got.foreign is True and got.error is report
+    assert [CapacityReports.parse(e) for e in box.pending] == [[Overflow(*B)]]
+    # ... also behind a wait whose own report had no line of ours: both others' lines wait for their owners
+    box = CapacityReports()
+    box.post(report)
+    got = box.settle(OWN, _raises(_capacity(PASSES[3])))
+    assert got.mine == [Overflow(*A)] and got.foreign is True and got.error is report
+    assert [CapacityReports.parse(e) for e in box.pending] == [[Overflow(*PASSES[3])], [Overflow(*B)]]
+
+
+def test_settle_lets_the_skipped_step_and_other_errors_through():
+    from webdgs_amd.ops import CapacityError, CapacityReports, WdgsError
+    box, waiting = CapacityReports(), _capacity(A)
+    box.post(waiting)
+    skipped = CapacityError(-3, SKIPPED[len("[wdgs -3] "):])
+    with pytest.raises(CapacityError) as caught:
+        box.settle(OWN, _raises(skipped))
+    assert caught.value is skipped and box.pending == [waiting], "nobody's report: raised unchanged, the mailbox untouched"
+    other = WdgsError(-1, "wdgs_buffer_create: size must be positive")
+    with pytest.raises(WdgsError) as caught:
+        box.settle(OWN, _raises(other))
+    assert caught.value is other and box.pending == [waiting]
+    with pytest.raises(KeyError):
+        box.settle(OWN, _raises(KeyError("not the library's")))
+
+
+@pytest.mark.parametrize("args,want", GROWN)
+def test_grown_tile_entries(args, want):
+    from webdgs_amd.ops import grownTileEntries
+    assert grownTileEntries(*args) == want
+
+
+def test_the_node_host_settles_and_grows_the_same():
+    node = shutil.which("node")
+    if not node:
+        pytest.skip("node is not available")
+    src = """
+      const { CapacityReports, grownTileEntries } = require(process.argv[1]);
+      const [A, B, C, D] = JSON.parse(process.argv[2]).map((p) => ({ needed: p[0], capacity: p[1], handle: BigInt(p[2]) }));
+      const line = (p) => `${p.needed} entries needed, max_tile_entries = ${p.capacity} (forward pass 0x${p.handle.toString(16)})`;
+      const capacity = (...ps) => Object.assign(new Error('[wdgs -3] tile entries overflow: ' + ps.map(line).join('; ') + ' (raise wdgs_tiled_forward_config.max_tile_entries)'), { code: 'WDGS_E_CAPACITY' });
+      const raises = (e) => () => { if (e) throw e; };
+      const same = (got, want) => got.length === want.length && got.every((o, i) => o.needed === want[i].needed && o.capacity === want[i].capacity && o.handle === want[i].handle);
+      const parsed = (box) => box.pending.map((e) => CapacityReports.parse(e));
+      const thrown = (f) => { try { f(); } catch (e) { return e; } return null; };
+      const own = [A.handle, C.handle], out = {};
+      let box = new CapacityReports(), got = box.settle(own, raises(null));
+      out.nothing = got.mine.length === 0 && got.foreign === false && got.error === null && box.pending.length === 0;
+      let report = capacity(C, A); box = new CapacityReports(); got = box.settle(own, raises(report));
+      out.own = same(got.mine, [C, A]) && got.foreign === false && got.error === report && box.pending.length === 0;
+      box = new CapacityReports(); got = box.settle([A.handle], raises(capacity(B, C)));
+      out.others = got.mine.length === 0 && got.foreign === true && got.error === null && box.pending.length === 1 && same(parsed(box)[0], [B, C]) && box.take([A.handle]) === null;
+      report = capacity(A, B, C); box = new CapacityReports(); got = box.settle(own, raises(report));
+      out.mixed = same(got.mine, [A, C]) && got.foreign === true && got.error === report && box.pending.length === 1 && same(parsed(box)[0], [B]) && box.take(own) === null;
+      const left = box.take([B.handle]);
+      out.mixedLeft = left !== null && left.code === 'WDGS_E_CAPACITY' && same(CapacityReports.parse(left), [B]) && box.pending.length === 0;
+      report = capacity(B, A); box = new CapacityReports(); box.post(report); got = box.settle(own, raises(null));
+      out.pending = same(got.mine, [A]) && got.foreign === true && got.error === report && box.pending.length === 1 && same(parsed(box)[0], [B]);
+      box = new CapacityReports(); box.post(report); got = box.settle(own, raises(capacity(D)));
+      out.pendingBehindOthers = same(got.mine, [A]) && got.error === report && box.pending.length === 2 && same(parsed(box)[0], [D]) && same(parsed(box)[1], [B]);
+      const waiting = capacity(A), skipped = Object.assign(new Error(process.argv[3]), { code: 'WDGS_E_CAPACITY' }), other = Object.assign(new Error('[wdgs -1] wdgs_buffer_create: size must be positive'), { code: 'WDGS_E' });
+      box = new CapacityReports(); box.post(waiting);
+      out.skipped = thrown(() => box.settle(own, raises(skipped))) === skipped && box.pending.length === 1 && box.pending[0] === waiting;
+      out.other = thrown(() => box.settle(own, raises(other))) === other && box.pending.length === 1 && box.pending[0] === waiting;
+      out.grown = JSON.parse(process.argv[4]).map((g) => grownTileEntries(g[0][0], g[0][1]) === g[1]);
+      console.log(JSON.stringify(out));
+    """
+    r = subprocess.run([node, "-e", src, REPORTS_JS, json.dumps([[n, c, hex(h)] for n, c, h in PASSES]), SKIPPED, json.dumps(GROWN)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1]) == dict(nothing=True, own=True, others=True, mixed=True, mixedLeft=True, pending=True, pendingBehindOthers=True,
+                                                                 skipped=True, other=True, grown=[True] * 4)
 
 
 # ---- the pass sets of the trainer (trainer.PassSet), without a device: stub ops that record their destroy()

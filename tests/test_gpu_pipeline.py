@@ -173,6 +173,55 @@ def test_another_owners_overflow_is_not_the_trainers_to_answer(hip_device):
         pc.gaussian_3d_buffer.destroy(); pc.sh_buffer.destroy()
 
 
+def test_a_report_about_two_owners_reaches_both(hip_device):
+    """A Viewer's frame and a Trainer's step overflow before the same wait: the library's one report names both passes.  The Trainer answers its
+    line (grows its lists, once) and the Viewer's line is left in the mailbox as a report of its own (ops.CapacityReports.settle), which the Viewer
+    answers at its next read."""
+    import warnings
+    from webdgs_amd import synth
+    from webdgs_amd.viewer import Viewer
+    dev = hip_device
+    cfg = synth.SceneConfig(2, 6000, 512, 384, 1, 550.0, 0.2, "few-large-splats")
+    g, sh = synth.make_gaussians(cfg)
+    cams = synth.circle_cameras(cfg, 2)
+    images = [dict(texture=dev.bufferFrom(np.zeros((cfg.height, cfg.width, 4), np.uint8)), width=cfg.width, height=cfg.height) for _ in cams]
+    pc = ops.createPointCloud(dev, g, sh, cfg.sh_deg)
+    v = Viewer(dev, cfg.width, cfg.height)
+    v.setCamera(cams[0])
+    v.setPointCloud(pc)
+    v.setRenderMode("gaussian")
+    t = Trainer(dev, seed=9, pipeline_depth=1)
+    t.setDensifyPruneConfig(dict(schedule=dict(enabled=False)))
+    t.setPointCloud(pc)
+    t.setDataset([dict(camera=c, width=cfg.width, height=cfg.height) for c in cams], images)
+    t.start()
+    dev.capacityReports.pending.clear()
+    try:
+        viewer_pass = int(v.getForwardPass().handle.value)
+        trainer_passes = {int(fw.handle.value) for fw in t._forward_passes()}
+        with warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            v.render(None)
+            t.step([0])
+        grown = [str(w.message) for w in seen if issubclass(w.category, RuntimeWarning) and "tile-entry lists grown" in str(w.message)]
+        # the premise: one wait, one report, both owners' passes in it (the warning quotes the report)
+        assert len(grown) == 1, [str(w.message) for w in seen]
+        quoted = ops.CapacityReports.passes_named(grown[0])
+        assert viewer_pass in quoted and quoted & trainer_passes, (grown[0], hex(viewer_pass), [hex(h) for h in trainer_passes])
+        # the viewer's line was left for the viewer, and only that
+        left = [ops.CapacityReports.passes_named(e) for e in dev.capacityReports.pending]
+        assert any(viewer_pass in names and not names & trainer_passes for names in left), left
+        v.readFrame()
+        assert int(v.getForwardPass().getResources()["maxTileEntries"]) > (1 << 20) + 4096, "the viewer enlarged its lists at its own read"
+        assert dev.capacityReports.pending == []
+    finally:
+        dev.capacityReports.pending.clear()
+        t.pointCloud = None  # (the cloud is shared: destroyed below, once)
+        t.destroy()
+        v.destroy()
+        pc.gaussian_3d_buffer.destroy(); pc.sh_buffer.destroy()
+
+
 @pytest.mark.parametrize("depth", [1, 2])
 def test_kernel_times_are_collected_by_ticket_waits(hip_device, depth):
     """bench.py's per-kernel leg: eager steps with an event pair around every launch; the pairs are folded into the totals by the

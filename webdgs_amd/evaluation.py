@@ -1,0 +1,296 @@
+"""``Evaluator`` -- everything a ``Trainer`` can measure about its model without training it: held-out evaluation, normal consistency, TSDF fusion
+and mesh extraction, geometry metrics, render contribution.  None of it has a counterpart in the reference.
+
+It renders through pass sets of its own (no backward pass), one per image size, built on first use and following the trainer's cloud, and answers
+the capacity reports about them itself (``ops.CapacityReports.settle``).  ``Trainer`` keeps the public methods and delegates to its Evaluator; what
+"training is untouched" rests on is the short list of trainer members in the class docstring below.
+"""
+from __future__ import annotations
+
+import time
+import warnings
+from typing import Optional
+
+import numpy as np
+
+from . import loaders, ops
+from .trainer import PassSet, destroy_pass_sets
+
+
+class Evaluator:
+    """The evaluation side of one ``Trainer``.  It owns the evaluation views with their camera blocks, the per-size evaluation ``PassSet``s, the size
+    an overflow has grown their tile-entry lists to and the long-list settings they were built with.
+
+    The seam -- the only members of the trainer used here:
+      * ``device``, ``pointCloud``, ``iteration``;
+      * ``trainCameras``, ``images``, ``_camera_buffers``: the training views, for ``split="train"``;
+      * ``_views``: the camera and image shapes ``setDataset`` accepts;
+      * ``_new_pass_set``: carries the live SH-DC words and the trainer's long-list settings;  ``_dc_words``, ``longLists``;
+      * ``drain()`` and ``_grow_tile_entry_capacity()``: a training step still in flight is awaited, its overflow answered as ``step()`` would.
+    Never the training or metric pass sets, the command-buffer cache, the tickets, the RNG, the optimizer or the densify pass."""
+
+    def __init__(self, trainer):
+        self.trainer = trainer
+        self.device = trainer.device
+        self.cameras: list = []
+        self.images: list = []
+        self._camera_buffers: list = []
+        self._sets: dict = {}
+        self.maxTileEntries = 0       # tile-entry lists of the evaluation passes (0: what the training passes get)
+        self._tile_entries = 0        # (what an overflowing evaluation view has made of them)
+        self._long_lists: Optional[dict] = None
+
+    def destroy(self) -> None:
+        self._destroy_sets()
+        self._camera_buffers = []
+
+    # ------------------------------------------------------------------ views and pass sets
+    def setEvaluationViews(self, cameras: list, images: list) -> None:
+        """Views to evaluate on and never to train on (``loaders.holdoutSplit`` gives the every-8th test views of the 3DGS convention).  Same
+        shapes as ``setDataset``; the images may have another size than the training images."""
+        cameras, images = list(cameras), list(images)
+        if len(cameras) != len(images):
+            raise ValueError(f"setEvaluationViews: {len(cameras)} cameras, {len(images)} images")
+        self.cameras, self.images = self.trainer._views(cameras, images)
+        self._camera_buffers = [self.device.bufferFrom(np.asarray(c["camera"], np.float32)) for c in self.cameras]
+
+    def _destroy_sets(self) -> None:
+        destroy_pass_sets(self._sets.values())
+        self._sets = {}
+
+    def _set(self, width: int, height: int, cameraBuffer) -> PassSet:
+        """The pass set (no backward pass) for one image size: built through the trainer's ``_new_pass_set`` (the live SH-DC words, its long-list
+        settings), with lists of ``_tile_entries`` if an evaluation view has outgrown the training passes' size.  Never a guard."""
+        key = (int(width), int(height))
+        if key not in self._sets:
+            self._sets[key] = self.trainer._new_pass_set(cameraBuffer, key[0], key[1], backward=False, max_tile_entries=self._tile_entries or self.maxTileEntries or None)
+        return self._sets[key]
+
+    def _follow_cloud(self) -> None:
+        """Brings the passes to the trainer's current cloud (a swap after a densify event, another size) and its current long-list settings."""
+        t = self.trainer
+        if self._long_lists != t.longLists:
+            self._destroy_sets()
+            self._long_lists = None if t.longLists is None else dict(t.longLists)
+        for s in list(self._sets.values()):
+            if s.forwardPass.pointCloud is not t.pointCloud and not s.forwardPass.setPointCloud(t.pointCloud):
+                self._destroy_sets()   # (another SH degree: built anew below)
+                break
+        for s in self._sets.values():
+            s.forwardPass.setDcSource(t._dc_words)
+
+    def _overflow(self) -> Optional[int]:
+        """Waits for the evaluation renders; the entries the largest overflowing one needed, or None (other owners' lines are left for them)."""
+        mine = self.device.capacityReports.settle((int(s.forwardPass.handle.value or 0) for s in self._sets.values()), self.device.synchronize).mine
+        return max(o.needed for o in mine) if mine else None
+
+    def _views(self, what: str, viewIds: Optional[list], split: str) -> tuple:
+        """(cameras, images, camera buffers, view ids) of a split, checked: what ``evaluate``, ``normalConsistency`` and ``contributionStats`` start with."""
+        t = self.trainer
+        if split not in ("eval", "train"):
+            raise ValueError(f"{what}: split must be 'eval' or 'train', not {split!r}")
+        if t.pointCloud is None:
+            raise RuntimeError(f"{what}: no point cloud")
+        cams, imgs, bufs = ((self.cameras, self.images, self._camera_buffers) if split == "eval" else
+                            (t.trainCameras, t.images, t._camera_buffers))
+        ids = list(range(len(cams))) if viewIds is None else [int(v) for v in viewIds]
+        for v in ids:
+            if not 0 <= v < len(cams):
+                raise IndexError(f"{what}: view {v} of {len(cams)} ({split})")
+        return cams, imgs, bufs, ids
+
+    def _drain(self) -> None:
+        """Drains the trainer's pipeline in front of renders through the evaluation passes."""
+        try:
+            self.trainer.drain()
+        except ops.CapacityError as e:   # a training step's overflow, as step() would have met it at its next wait
+            if not self.trainer._grow_tile_entry_capacity(e):
+                raise
+
+    def _render_views(self, ids: list, imgs: list, bufs: list, each, restart=None, what: str = "evaluate") -> None:
+        """The render loop: every view of ``ids`` through the evaluation pass set of its size, then ``each(i, v, passSet, width, height)``; after
+        an overflow the lists are grown, ``restart()`` is called and ALL views are rendered again."""
+        while ids:
+            self._follow_cloud()
+            for i, v in enumerate(ids):
+                w, h = int(imgs[v]["width"]), int(imgs[v]["height"])
+                s = self._set(w, h, bufs[v])
+                fw, rast = s.forwardPass, s.rasterizer
+                fw.setCameraBuffer(bufs[v])
+                fw.encode(None)
+                rast.encode(None, w, h)
+                each(i, v, s, w, h)
+            needed = self._overflow()
+            if needed is None:
+                break
+            now = max([int(s.forwardPass.getResources()["maxTileEntries"]) for s in self._sets.values()] + [self._tile_entries])
+            new = ops.grownTileEntries(now, needed)
+            if new <= now:
+                raise RuntimeError(f"{what}: a view needs {needed} tile entries, more than the lists can hold")
+            warnings.warn(f"evaluation tile-entry lists grown from {now} to {new} entries after an overflow; the views are rendered again", RuntimeWarning, stacklevel=4)
+            self._tile_entries = new
+            self._destroy_sets()
+            if restart is not None:
+                restart()
+
+    # ------------------------------------------------------------------ held-out evaluation
+    def evaluate(self, viewIds: Optional[list] = None, split: str = "eval") -> dict:
+        """PSNR and SSIM of the current model on the evaluation views (``split="eval"``, ``setEvaluationViews``) or on training views
+        (``split="train"``): ``dict(iteration, views, psnr=[...], ssim=[...], mean_psnr, mean_ssim, ms)``.  PSNR comes from the exact SSE kernel
+        (``inf`` for identical images); SSIM is ``ops.imageSSIM``'s; the means are means of the per-view values; ``ms`` the call's wall time.
+
+        Drains the pipeline, then renders every view through passes of its own and writes view i's SSE and SSIM into slot i of two device arrays,
+        read back once at the end.  A view whose tile-entry list overflowed is rendered again with larger lists -- never reported from a truncated
+        render.  Training is untouched: no RNG draw, no training pass, no recording dropped; a trainer that evaluates every few steps follows the
+        same trajectory as one that never does.  Per rank with ``world_size > 1`` (no collective)."""
+        cams, imgs, bufs, ids = self._views("evaluate", viewIds, split)
+        t0 = time.perf_counter()
+        self._drain()
+        n = len(ids)
+        out = self.device.createBuffer(16 * max(1, n), "evaluation sse + ssim")
+        sse_at, ssim_at = out.ptr, out.ptr + 8 * max(1, n)
+        try:
+            def measure(i, v, s, w, h):
+                pred = s.rasterizer.getOutputTextureView()
+                ops.encodeImageSSE(self.device, pred, imgs[v]["texture"], w * h, self.device.view(sse_at + 8 * i, 8))
+                ops.encodeImageSSIM(self.device, pred, imgs[v]["texture"], w, h, self.device.view(ssim_at + 8 * i, 8))
+            self._render_views(ids, imgs, bufs, measure, what="evaluate")
+            sse = out.read(np.uint64, count=n) if n else np.zeros(0, np.uint64)
+            ssim = out.read(np.float64, count=n, offset=8 * max(1, n)) if n else np.zeros(0)
+        finally:
+            out.destroy()
+        psnr = [ops.psnrFromSSE(int(sse[i]), int(imgs[v]["width"]) * int(imgs[v]["height"])) for i, v in enumerate(ids)]
+        ssim_l = [float(x) for x in ssim]
+        return dict(iteration=self.trainer.iteration, views=ids, psnr=psnr, ssim=ssim_l, sse=[int(x) for x in sse],
+                    mean_psnr=float(np.mean(psnr)) if n else float("nan"), mean_ssim=float(np.mean(ssim_l)) if n else float("nan"),
+                    ms=(time.perf_counter() - t0) * 1e3)
+
+    # ------------------------------------------------------------------ normal consistency
+    def normalConsistency(self, viewIds: Optional[list] = None, split: str = "eval", depthKind: str = "median") -> dict:
+        """How well the composited normals of the current model agree with the normals of its own depth map, per view: a geometry score that needs no
+        ground truth (a surface scores near 0, a fog near 1).  ``dict(iteration, views, value=[...], pixels=[...], sum_e=[...], sum_a=[...], mean, ms)``:
+        ``value`` is ``ops.normalAgreement``'s weight-averaged ``1 - cos`` between ``encodeNormal``'s image and ``ops.depthToNormals`` of the
+        ``depthKind`` depth image (nan for a view where no pixel counts), ``mean`` the same average over all views' pixels (``sum sum_e / sum sum_a``).
+
+        Rendered through evaluate's passes, with its isolation: the pipeline is drained, a view whose lists overflowed is rendered again, no RNG draw,
+        no training pass, no recording dropped; ``evaluate()``'s result is what it was.  Per rank with ``world_size > 1``."""
+        if depthKind not in ("median", "expected"):
+            raise ValueError(f"normalConsistency: depthKind must be 'median' or 'expected', not {depthKind!r}")
+        cams, imgs, bufs, ids = self._views("normalConsistency", viewIds, split)
+        t0 = time.perf_counter()
+        self._drain()
+        n = len(ids)
+        out = self.device.createBuffer(24 * max(1, n), "normal agreement sums")
+        scratch = self.device.createBuffer(16 * max([1] + [int(imgs[v]["width"]) * int(imgs[v]["height"]) for v in ids]), "depth normals")
+        try:
+            def measure(i, v, s, w, h):
+                s.rasterizer.encodeDepth(None, (depthKind,))
+                s.rasterizer.encodeNormal(None)
+                ops.depthToNormals(self.device, s.rasterizer.getDepthTextureView(depthKind), w, h, cams[v]["camera"], scratch)
+                ops.encodeNormalAgreement(self.device, s.rasterizer.getNormalTextureView(), scratch, w, h, self.device.view(out.ptr + 24 * i, 24))
+            self._render_views(ids, imgs, bufs, measure, what="normalConsistency")
+            sums = (out.read(np.uint64, count=3 * n) if n else np.zeros(0, np.uint64)).reshape(n, 3)
+        finally:
+            scratch.destroy()
+            out.destroy()
+        sum_e, sum_a, pixels = ([int(x) for x in sums[:, k]] for k in range(3))
+        return dict(iteration=self.trainer.iteration, views=ids, value=[(e / a) if a else float("nan") for e, a in zip(sum_e, sum_a)], pixels=pixels,
+                    sum_e=sum_e, sum_a=sum_a, mean=(sum(sum_e) / sum(sum_a)) if sum(sum_a) else float("nan"), ms=(time.perf_counter() - t0) * 1e3)
+
+    # ------------------------------------------------------------------ TSDF fusion and mesh extraction
+    def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
+        """Fuses the current model's depth maps into ``volume``: for each view in the order given, the forward pass, rasterize,
+        ``encodeDepth((depthKind, "weight_sum"))`` and ``volume.integrate`` with the weight sum and the rasterizer's output texture as colour (where the
+        volume has colour).  Returns the view list.
+
+        Rendered through evaluate's passes, with its isolation: the pipeline is drained, no RNG draw, no training pass, no recording dropped, the
+        iteration counter untouched.  A view is integrated only once its render is known not to have overflowed its tile-entry lists (one wait per view):
+        a fusion cannot be taken back, so it never sees a truncated render.  Per rank with ``world_size > 1``."""
+        if depthKind not in ("median", "expected"):
+            raise ValueError(f"fuseDepth: depthKind must be 'median' or 'expected', not {depthKind!r}")
+        cams, imgs, bufs, ids = self._views("fuseDepth", viewIds, split)
+        self._drain()
+        for v in ids:
+            self._render_views([v], imgs, bufs, lambda i, v, s, w, h: None, what="fuseDepth")   # (returns with the view's complete frame in its pass set)
+            w, h = int(imgs[v]["width"]), int(imgs[v]["height"])
+            rast = self._set(w, h, bufs[v]).rasterizer
+            rast.encodeDepth(None, (depthKind, "weight_sum"))
+            volume.integrate(rast.getDepthTextureView(depthKind), bufs[v], w, h, weightSum=rast.getDepthTextureView("weight_sum"),
+                             colour=rast.getOutputTextureView() if volume.colour else None)
+        return ids
+
+    def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
+                    keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **volumeOptions) -> dict:
+        """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
+        ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result.
+
+        ``keepLargest``, ``minTriangles``, ``minFraction``: with any of them set, the mesh goes through ``ops.removeSmallComponents`` -- the floaters of
+        a fused mesh are small components of their own -- and its dict is returned (``vertexMap``, ``faceMap`` and ``components`` added).  With the
+        defaults the raw level set is returned as before and nothing more is launched."""
+        volume = ops.TSDFVolume.fromBounds(self.device, lo, hi, voxelSize, **volumeOptions)
+        try:
+            self.fuseDepth(volume, viewIds, split, depthKind)
+            mesh = volume.extractMesh(minWeight)
+        finally:
+            volume.destroy()
+        if ops._is_default_selection(keepLargest, minTriangles, minFraction):
+            return mesh
+        return ops.removeSmallComponents(self.device, mesh, keepLargest, minTriangles, minFraction)
+
+    # ------------------------------------------------------------------ mesh accuracy against a reference point set
+    def evaluateGeometry(self, reference, lo, hi, voxelSize: float, maxDistance: float, threshold: float, density: Optional[float] = None, seed: int = 0,
+                         keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **extractMeshOptions) -> dict:
+        """Scores the current model's geometry against ``reference`` -- an ``[M,3]`` array of surface points, or the path of a PLY that holds them:
+        ``extractMesh(lo, hi, voxelSize, **extractMeshOptions)``, ``ops.sampleMesh`` at ``density`` samples per unit area (``None``: ``1 / (voxelSize / 2)^2``,
+        a spacing of half a voxel) and ``ops.geometryMetrics(samples, reference, maxDistance, threshold)``.  Returns its dict -- accuracy, completeness,
+        chamfer, precision, recall, fscore and the counts -- with ``vertices``, ``faces``, ``samples`` (the mesh's and the sample count) and ``ms``.
+
+        ``keepLargest``, ``minTriangles`` and ``minFraction`` are ``extractMesh``'s: the published numbers are those of a mesh without its floaters.
+
+        ``extractMesh``'s isolation (``fuseDepth``'s): the pipeline is drained, no RNG draw, no training pass, no recording dropped, the iteration counter
+        untouched.  No alignment is attempted: the reference is taken to be in the scene's frame."""
+        t0 = time.perf_counter()
+        ref = loaders.loadPointsPLY(reference) if isinstance(reference, (str, bytes)) or hasattr(reference, "__fspath__") else np.ascontiguousarray(reference, np.float32)
+        if ref.ndim != 2 or ref.shape[1] != 3:
+            raise ValueError(f"evaluateGeometry: the reference must be [M, 3] points, got {ref.shape}")
+        if density is None:
+            density = 1.0 / (0.5 * float(voxelSize)) ** 2
+        mesh = self.extractMesh(lo, hi, voxelSize, keepLargest=keepLargest, minTriangles=minTriangles, minFraction=minFraction, **extractMeshOptions)
+        samples = ops.sampleMesh(self.device, mesh, density, seed, asBuffers=True)
+        try:
+            n = samples["count"]
+            out = ops.geometryMetrics(self.device, self.device.view(samples["points"].ptr, 12 * n), ref, maxDistance, threshold)
+        finally:
+            samples["points"].destroy()
+            samples["face"].destroy()
+        out.update(vertices=int(mesh["vertices"].shape[0]), faces=int(mesh["faces"].shape[0]), samples=int(n), ms=(time.perf_counter() - t0) * 1e3)
+        return out
+
+    # ------------------------------------------------------------------ render contribution
+    def contributionBuffer(self, viewIds: Optional[list], split: str, what: str) -> tuple:
+        """(buffer, view ids): the views' contribution records accumulated into one new device buffer (``Trainer.pruneByContribution`` decides on it)."""
+        cams, imgs, bufs, ids = self._views(what, viewIds, split)
+        if sum(int(imgs[v]["width"]) * int(imgs[v]["height"]) for v in ids) >= 2 ** 32:
+            raise ValueError(f"{what}: the views hold 2^32 pixels or more; the per-Gaussian pixel count is 32 bits wide")
+        self._drain()
+        stats = ops.createContributionBuffer(self.device, self.trainer.pointCloud.num_points)
+        try:
+            self._render_views(ids, imgs, bufs, lambda i, v, s, w, h: s.rasterizer.encodeContribution(None, stats), restart=stats.clear, what=what)
+        except BaseException:
+            stats.destroy()
+            raise
+        return stats, ids
+
+    def contributionStats(self, viewIds: Optional[list] = None, split: str = "train") -> dict:
+        """How much of each Gaussian the views' images hold: ``dict(sum_q, weight_sum, max_weight, pixels, views)``, one
+        entry per Gaussian, accumulated over the views -- the sum and the maximum of the compositing weights ``alpha (1 - A)`` and the number of
+        (pixel, Gaussian) pairs composited.  Rendered through evaluate's passes, with its isolation: the pipeline is drained, a view whose lists
+        overflowed is rendered again (the records are cleared and every view is walked again), no RNG draw, no training pass, no recording
+        dropped.  Per rank with ``world_size > 1``."""
+        stats, ids = self.contributionBuffer(viewIds, split, "contributionStats")
+        try:
+            out = ops.readContribution(stats, self.trainer.pointCloud.num_points)
+        finally:
+            stats.destroy()
+        out["views"] = ids
+        return out

@@ -173,20 +173,62 @@ class Overflow(NamedTuple):
     handle: int
 
 
+class Settled(NamedTuple):
+    """What ``CapacityReports.settle`` found for one owner: its passes' lines, whether a line was left for another owner, and the report its lines
+    came from (``None`` when there are none)."""
+    mine: list
+    foreign: bool
+    error: Optional[Exception]
+
+
+def grownTileEntries(now: int, needed: int) -> int:
+    """Tile-entry lists after an overflow: twice what they hold, or 1.5 x what the frame needed where that is more; never more than a sort takes."""
+    return min(max(2 * now, int(needed * 1.5)), 0xFFFFF000)
+
+
 class CapacityReports:
     """Capacity reports that reached the wrong owner.  The library reports a truncated tile-entry list at the next host wait on the DEVICE, to whoever
-    waits (csrc/api.hip: deferred_checks consumes every pass's word and names the passes); a Trainer and a Viewer that share a device each handle the
-    reports that name their own passes -- and leave the others HERE, where the passes' owner looks at its own next wait (dropped instead, a
-    report consumed by the wrong owner was lost to the right one)."""
+    waits (csrc/api.hip: deferred_checks consumes every pass's word and names up to four passes).  The owners of forward passes on a device -- a
+    Trainer's training and metric sets, its Evaluator's sets, a Viewer -- all wait through ``settle``, which has the one rule: an owner keeps the lines
+    about its own passes, every other line is left HERE as a report of its own, where the passes' owner finds it at its own next wait (ADVICE r4:
+    dropped instead, a report consumed by the wrong owner was lost to the right one)."""
 
     def __init__(self, keep: int = 16):
         self.pending: list = []
         self.keep = keep
 
+    def settle(self, own_handles, wait) -> Settled:
+        """``wait()``, then the capacity report it raised -- or, if that had no line of ``own_handles``' passes, the oldest pending report that has one --
+        sorted: the owner's lines are returned, the others posted.  A report that names no pass (an optimizer step skipped on every rank: nobody's)
+        and every other error propagate."""
+        own = {int(h) for h in own_handles}
+        mine, foreign, report = [], False, None
+        try:
+            wait()
+        except CapacityError as e:
+            if not self.parse(e):
+                raise
+            report = e
+            mine, foreign = self._keep(report, own)
+        if not mine:
+            report = self.take(own)
+            if report is not None:
+                mine, left = self._keep(report, own)
+                foreign = foreign or left
+        return Settled(mine, foreign, report if mine else None)
+
+    def _keep(self, report, own: set) -> tuple:
+        """``split``; the other owners' lines are posted as one report in deferred_checks' format, so that ``parse`` stays the reader of report text."""
+        mine, others = self.split(report, own)
+        if others:
+            lines = "; ".join(f"{o.needed} entries needed, max_tile_entries = {o.capacity} (forward pass {o.handle:#x})" for o in self.parse(report) if o.handle not in own)
+            self.post(CapacityError(_lib.WDGS_E_CAPACITY, f"tile entries overflow: {lines} (raise wdgs_tiled_forward_config.max_tile_entries)"))
+        return mine, others
+
     @staticmethod
     def parse(error) -> list:
         """One ``Overflow(needed, capacity, handle)`` per pass the report names, in the report's order; ``[]`` for any other error."""
-        # The one reader of report text (bindings/ts/webdgs_hip.js has its twin).  It follows two format strings of csrc/api.hip:
+        # The one reader of report text (bindings/ts/capacity_reports.js has its twin).  It follows two format strings of csrc/api.hip:
         #   deferred_checks:          "tile entries overflow: " + "; ".join("%u entries needed, max_tile_entries = %u (forward pass %p)") + " (raise ...)"
         #   wdgs_tiled_forward_check: "tile entries overflow: %u entries needed, max_tile_entries = %u (forward pass %p)"
         # Known limit: the library names at most four passes per report; a fifth that overflowed in the same wait is consumed unnamed.

@@ -7,6 +7,10 @@ DESIGN.md: the rasterizer's grid always follows the current viewport (fixes SURV
 their own camera (fixes Q12: uploads are stream-ordered here); the point-cloud swap is applied inside the step that
 produced it instead of on the next animation frame.  New: ``world_size > 1`` runs view-sharded data parallelism
 (``webdgs_amd.parallel``).
+
+This class is the training step and what it needs.  Everything that measures the model without training it -- ``evaluate``, ``normalConsistency``,
+``fuseDepth``, ``extractMesh``, ``evaluateGeometry``, ``contributionStats`` -- lives in ``evaluation.Evaluator``; the methods of those names here
+delegate to it.  Every host wait goes through ``ops.CapacityReports.settle``, which sorts the device-wide capacity reports by owner.
 """
 from __future__ import annotations
 
@@ -46,6 +50,9 @@ def destroy_pass_sets(sets) -> None:
     """Destroys every pass of ``sets``, in set order."""
     for s in sets:
         s.destroy()
+
+
+from . import evaluation  # noqa: E402  (it imports PassSet and destroy_pass_sets from here)
 
 
 class Trainer:
@@ -131,15 +138,8 @@ class Trainer:
         self.pendingPointCloudSwap: Optional[dict] = None
         self.trainCameras: list = []   # dicts: camera (float32[68]), width, height
         self.images: list = []         # dicts: texture (HipBuffer rgba8), width, height
-        # held-out evaluation (setEvaluationViews / evaluate): views never drawn for training, and render passes of evaluate's own, one
-        # PassSet (no backward pass) per image size, built on first use and following the cloud
-        self.evalCameras: list = []
-        self.evalImages: list = []
-        self._eval_camera_buffers: list = []
-        self._eval_sets: dict = {}
-        self.evalMaxTileEntries = 0       # tile-entry lists of evaluate's passes (0: what the training passes get)
-        self._eval_tile_entries = 0       # (what an overflowing evaluation view has made of them)
-        self._eval_long_lists: Optional[dict] = None
+        # held-out evaluation and the other measurements of the model: views never drawn for training and render passes of their own (evaluation.py)
+        self.evaluator = evaluation.Evaluator(self)
 
         self.densifyPruneConfig = dict(  # trainer.ts:147-164
             schedule=dict(enabled=True, warmupIterations=500, interval=100, stopIterations=15_000),
@@ -170,15 +170,15 @@ class Trainer:
     metricsTarget = property(lambda self: self._metric_sets[0].target if self._metric_sets else None)
 
     def _all_sets(self) -> list:
-        """The training and metric sets: what a step and a densify event run.  (evaluate's sets follow the cloud and answer capacity reports on their
-        own, ``_eval_follow_cloud`` / ``_eval_overflow``.)"""
+        """The training and metric sets: what a step and a densify event run.  (The Evaluator's sets follow the cloud and answer capacity reports on
+        their own, evaluation.py.)"""
         return self._train_sets + self._metric_sets
 
     def _forward_passes(self) -> list:
         return [s.forwardPass for s in self._all_sets()]
 
     def _destroy_pass_sets(self) -> None:
-        """Every pass but the optimizer's and evaluate's goes; ``ensurePipelines`` and the first use of a metric set build them anew."""
+        """Every pass but the optimizer's and the Evaluator's goes;``ensurePipelines`` and the first use of a metric set build them anew."""
         destroy_pass_sets(self._all_sets())
         self._train_sets, self._metric_sets = [], []
 
@@ -515,9 +515,9 @@ class Trainer:
     def _grow_tile_entry_capacity(self, error) -> bool:
         if self.maxTileEntries != 0 or not self.device.handle:
             return False
-        mine = self._own_overflow(error) or []   # (a report about other owners' passes only never gets here: _wait / _synchronize)
+        mine, _ = ops.CapacityReports.split(error, self._own_handles())   # (a report about other owners' passes only never gets here: _settled)
         now = max([int(fw.getResources()["maxTileEntries"]) for fw in self._forward_passes()] + [self._grown_tile_entries, 1 << 20])
-        new = min(max(2 * now, int(max(mine) * 1.5) if mine else 0), 0xFFFFF000)
+        new = ops.grownTileEntries(now, max([o.needed for o in mine] + [0]))
         if new <= now:
             return False
         warnings.warn(f"tile-entry lists grown from {now} to {new} entries after an overflow ({error}); the step that overflowed was skipped", RuntimeWarning, stacklevel=3)
@@ -775,45 +775,27 @@ class Trainer:
         self.exchange.allreduce_counts(self._agree_word.ptr, 1)
         return int(self._agree_word.read(np.uint32, 1)[0]) != 0
 
-    def _own_overflow(self, error) -> Optional[list]:
-        """What THIS trainer's passes needed (entries) among the passes a capacity report names (csrc/api.hip: deferred_checks names every pass that
-        overflowed), ``[]`` if it names only other owners' passes, ``None`` if it names none (a step skipped on every rank)."""
-        mine, others = ops.CapacityReports.split(error, (int(fw.handle.value or 0) for fw in self._forward_passes()))
-        return [o.needed for o in mine] if mine or others else None
+    def _own_handles(self) -> list:
+        return [int(fw.handle.value or 0) for fw in self._forward_passes()]
 
-    def _not_ours(self, error) -> bool:
-        """True (after saying so once) for a capacity report about passes this trainer does not own -- a Viewer rendering the same cloud on this
-        device: the report is device-wide, whoever waits first gets it, and it is the pass's owner who has to enlarge its lists."""
-        if self._own_overflow(error) != []:
-            return False
-        self.device.capacityReports.post(error)   # (for the passes' owner: it looks there at its own next wait)
-        if not self._foreign_overflow_warned:
-            warnings.warn(f"a forward pass that is not this trainer's overflowed its tile-entry lists ({error}); its owner has to enlarge them", RuntimeWarning, stacklevel=4)
+    def _settled(self, wait) -> None:
+        """``wait()`` with the capacity reports sorted by owner (``ops.CapacityReports.settle``).  A report with a line about THIS trainer's passes is
+        raised -- also one that another owner's wait consumed and left for us (a Viewer reading its frame).  Lines about passes this trainer does not
+        own -- a Viewer rendering the same cloud on this device: the report is device-wide, whoever waits first gets it -- are left for the passes'
+        owner, who has to enlarge its lists; the trainer says so once."""
+        s = self.device.capacityReports.settle(self._own_handles(), wait)
+        if s.foreign and not self._foreign_overflow_warned:
+            left = self.device.capacityReports.pending[-1]   # (what settle has just posted)
+            warnings.warn(f"a forward pass that is not this trainer's overflowed its tile-entry lists ({left}); its owner has to enlarge them", RuntimeWarning, stacklevel=4)
             self._foreign_overflow_warned = True
-        return True
+        if s.mine:
+            raise s.error
 
     def _wait(self, ticket) -> None:
-        try:
-            self.device.queue.wait(ticket)
-        except ops.CapacityError as e:
-            if not self._not_ours(e):
-                raise
-        self._reports_left_for_us()
+        self._settled(lambda: self.device.queue.wait(ticket))
 
     def _synchronize(self) -> None:
-        try:
-            self.device.synchronize()
-        except ops.CapacityError as e:
-            if not self._not_ours(e):
-                raise
-        self._reports_left_for_us()
-
-    def _reports_left_for_us(self) -> None:
-        """A report about THIS trainer's passes that another owner's wait consumed (a Viewer reading its frame): raised here, as if this wait had got it."""
-        if self.device.capacityReports.pending:
-            e = self.device.capacityReports.take(int(fw.handle.value or 0) for fw in self._forward_passes())
-            if e is not None:
-                raise e
+        self._settled(self.device.synchronize)
 
     def _finish_step(self, n_views: int) -> None:
         """``await onSubmittedWorkDone()`` (trainer.ts:639-645) + the deferred capacity check, for the step ``pipeline_depth - 1``
@@ -857,276 +839,54 @@ class Trainer:
                 pass  # (a deferred report about a step of a trainer that is going away)
         self._invalidate_command_buffers()
         self._destroy_pass_sets()
-        self._destroy_eval_sets()
+        self.evaluator.destroy()
         for op in (self.optimizer, self.densifyPrune):
             if op is not None:
                 op.destroy()
         self.optimizer = self.densifyPrune = None
         self._dp_grad = self._dp_visible = self._dp_rows = self._dp_flag = None
         self._camera_buffers = []
-        self._eval_camera_buffers = []
         self.pointCloud = None
         self.isTraining = False
 
-    # ------------------------------------------------------------------ held-out evaluation (no reference counterpart)
+    # ------------------------------------------------------------------ evaluation and analysis: all of it is the Evaluator's (evaluation.py)
+    evalCameras = property(lambda self: self.evaluator.cameras)
+    evalImages = property(lambda self: self.evaluator.images)
+    evalMaxTileEntries = property(lambda self: self.evaluator.maxTileEntries, lambda self, n: setattr(self.evaluator, "maxTileEntries", n),
+                                  doc="tile-entry lists of the Evaluator's passes (0: what the training passes get)")
+
     def setEvaluationViews(self, cameras: list, images: list) -> None:
-        """Views to evaluate on and never to train on (``loaders.holdoutSplit`` gives the every-8th test views of the 3DGS convention).  Same
-        shapes as ``setDataset``; the images may have another size than the training images."""
-        cameras, images = list(cameras), list(images)
-        if len(cameras) != len(images):
-            raise ValueError(f"setEvaluationViews: {len(cameras)} cameras, {len(images)} images")
-        self.evalCameras, self.evalImages = self._views(cameras, images)
-        self._eval_camera_buffers = [self.device.bufferFrom(np.asarray(c["camera"], np.float32)) for c in self.evalCameras]
-
-    def _destroy_eval_sets(self) -> None:
-        destroy_pass_sets(self._eval_sets.values())
-        self._eval_sets = {}
-
-    def _eval_set(self, width: int, height: int, cameraBuffer) -> PassSet:
-        """evaluate's pass set (no backward pass) for one image size: built through ``_new_forward_pass`` (the live SH-DC words, this trainer's
-        long-list settings), with lists of ``_eval_tile_entries`` if an evaluation view has outgrown the training passes' size.  Never a guard."""
-        key = (int(width), int(height))
-        if key not in self._eval_sets:
-            self._eval_sets[key] = self._new_pass_set(cameraBuffer, key[0], key[1], backward=False, max_tile_entries=self._eval_tile_entries or self.evalMaxTileEntries or None)
-        return self._eval_sets[key]
-
-    def _eval_follow_cloud(self) -> None:
-        """Brings evaluate's passes to the current cloud (a swap after a densify event, another size) and the current long-list settings."""
-        if self._eval_long_lists != self.longLists:
-            self._destroy_eval_sets()
-            self._eval_long_lists = None if self.longLists is None else dict(self.longLists)
-        for s in list(self._eval_sets.values()):
-            if s.forwardPass.pointCloud is not self.pointCloud and not s.forwardPass.setPointCloud(self.pointCloud):
-                self._destroy_eval_sets()   # (another SH degree: built anew below)
-                break
-        for s in self._eval_sets.values():
-            s.forwardPass.setDcSource(self._dc_words)
-
-    def _eval_overflow(self) -> Optional[int]:
-        """Waits for the evaluation renders; the entries the largest overflowing one needed, or None.  A report that also names passes of another
-        owner (a Viewer on this device) is left for that owner (ops.CapacityReports)."""
-        own = {int(s.forwardPass.handle.value or 0) for s in self._eval_sets.values()}
-        try:
-            self.device.synchronize()
-            err = self.device.capacityReports.take(own) if self.device.capacityReports.pending else None
-        except ops.CapacityError as e:
-            err = e
-        if err is None:
-            return None
-        mine, others = ops.CapacityReports.split(err, own)
-        if others:
-            self.device.capacityReports.post(err)
-        if not mine and not others:
-            raise err
-        return max(o.needed for o in mine) if mine else None
-
-    def _eval_views(self, what: str, viewIds: Optional[list], split: str) -> tuple:
-        """(cameras, images, camera buffers, view ids) of a split, checked: what ``evaluate``, ``normalConsistency`` and ``contributionStats`` start with."""
-        if split not in ("eval", "train"):
-            raise ValueError(f"{what}: split must be 'eval' or 'train', not {split!r}")
-        if self.pointCloud is None:
-            raise RuntimeError(f"{what}: no point cloud")
-        cams, imgs, bufs = ((self.evalCameras, self.evalImages, self._eval_camera_buffers) if split == "eval" else
-                            (self.trainCameras, self.images, self._camera_buffers))
-        ids = list(range(len(cams))) if viewIds is None else [int(v) for v in viewIds]
-        for v in ids:
-            if not 0 <= v < len(cams):
-                raise IndexError(f"{what}: view {v} of {len(cams)} ({split})")
-        return cams, imgs, bufs, ids
-
-    def _eval_drain(self) -> None:
-        """Drains the pipeline in front of renders through the evaluation passes."""
-        try:
-            self.drain()
-        except ops.CapacityError as e:   # a training step's overflow, as step() would have met it at its next wait
-            if not self._grow_tile_entry_capacity(e):
-                raise
+        """``Evaluator.setEvaluationViews``: views to evaluate on and never to train on."""
+        self.evaluator.setEvaluationViews(cameras, images)
 
     def evaluate(self, viewIds: Optional[list] = None, split: str = "eval") -> dict:
-        """PSNR and SSIM of the current model on the evaluation views (``split="eval"``, ``setEvaluationViews``) or on training views
-        (``split="train"``): ``dict(iteration, views, psnr=[...], ssim=[...], mean_psnr, mean_ssim, ms)``.  PSNR comes from the exact SSE kernel
-        (``inf`` for identical images); SSIM is ``ops.imageSSIM``'s; the means are means of the per-view values; ``ms`` the call's wall time.
+        """``Evaluator.evaluate``: PSNR and SSIM of the current model on the evaluation or the training views; training is untouched."""
+        return self.evaluator.evaluate(viewIds, split)
 
-        Drains the pipeline, then renders every view through passes of its own and writes view i's SSE and SSIM into slot i of two device arrays,
-        read back once at the end.  A view whose tile-entry list overflowed is rendered again with larger lists -- never reported from a truncated
-        render.  Training is untouched: no RNG draw, no training pass, no recording dropped; a trainer that evaluates every few steps follows the
-        same trajectory as one that never does.  Per rank with ``world_size > 1`` (no collective)."""
-        cams, imgs, bufs, ids = self._eval_views("evaluate", viewIds, split)
-        t0 = time.perf_counter()
-        self._eval_drain()
-        n = len(ids)
-        out = self.device.createBuffer(16 * max(1, n), "evaluation sse + ssim")
-        sse_at, ssim_at = out.ptr, out.ptr + 8 * max(1, n)
-
-        def measure(i, v, s, w, h):
-            pred = s.rasterizer.getOutputTextureView()
-            ops.encodeImageSSE(self.device, pred, imgs[v]["texture"], w * h, self.device.view(sse_at + 8 * i, 8))
-            ops.encodeImageSSIM(self.device, pred, imgs[v]["texture"], w, h, self.device.view(ssim_at + 8 * i, 8))
-        self._render_eval_views(ids, imgs, bufs, measure, what="evaluate")
-        sse = out.read(np.uint64, count=n) if n else np.zeros(0, np.uint64)
-        ssim = out.read(np.float64, count=n, offset=8 * max(1, n)) if n else np.zeros(0)
-        psnr = [ops.psnrFromSSE(int(sse[i]), int(imgs[v]["width"]) * int(imgs[v]["height"])) for i, v in enumerate(ids)]
-        ssim_l = [float(x) for x in ssim]
-        return dict(iteration=self.iteration, views=ids, psnr=psnr, ssim=ssim_l, sse=[int(x) for x in sse],
-                    mean_psnr=float(np.mean(psnr)) if n else float("nan"), mean_ssim=float(np.mean(ssim_l)) if n else float("nan"),
-                    ms=(time.perf_counter() - t0) * 1e3)
-
-    def _render_eval_views(self, ids: list, imgs: list, bufs: list, each, restart=None, what: str = "evaluate") -> None:
-        """evaluate's render loop, shared with contributionStats: every view of ``ids`` through the evaluation pass set of its size, then
-        ``each(i, v, passSet, width, height)``; after an overflow the lists are grown, ``restart()`` is called and ALL views are rendered again."""
-        while ids:
-            self._eval_follow_cloud()
-            for i, v in enumerate(ids):
-                w, h = int(imgs[v]["width"]), int(imgs[v]["height"])
-                s = self._eval_set(w, h, bufs[v])
-                fw, rast = s.forwardPass, s.rasterizer
-                fw.setCameraBuffer(bufs[v])
-                fw.encode(None)
-                rast.encode(None, w, h)
-                each(i, v, s, w, h)
-            needed = self._eval_overflow()
-            if needed is None:
-                break
-            now = max([int(s.forwardPass.getResources()["maxTileEntries"]) for s in self._eval_sets.values()] + [self._eval_tile_entries])
-            new = min(max(2 * now, int(needed * 1.5)), 0xFFFFF000)
-            if new <= now:
-                raise RuntimeError(f"{what}: a view needs {needed} tile entries, more than the lists can hold")
-            warnings.warn(f"evaluation tile-entry lists grown from {now} to {new} entries after an overflow; the views are rendered again", RuntimeWarning, stacklevel=3)
-            self._eval_tile_entries = new
-            self._destroy_eval_sets()
-            if restart is not None:
-                restart()
-
-    # ------------------------------------------------------------------ normal consistency (DESIGN.md section 12; no reference counterpart)
     def normalConsistency(self, viewIds: Optional[list] = None, split: str = "eval", depthKind: str = "median") -> dict:
-        """How well the composited normals of the current model agree with the normals of its own depth map, per view: a geometry score that needs no
-        ground truth (a surface scores near 0, a fog near 1).  ``dict(iteration, views, value=[...], pixels=[...], sum_e=[...], sum_a=[...], mean, ms)``:
-        ``value`` is ``ops.normalAgreement``'s weight-averaged ``1 - cos`` between ``encodeNormal``'s image and ``ops.depthToNormals`` of the
-        ``depthKind`` depth image (nan for a view where no pixel counts), ``mean`` the same average over all views' pixels (``sum sum_e / sum sum_a``).
+        """``Evaluator.normalConsistency``: agreement of the composited normals with the normals of the model's own depth map."""
+        return self.evaluator.normalConsistency(viewIds, split, depthKind)
 
-        Rendered through evaluate's passes, with its isolation: the pipeline is drained, a view whose lists overflowed is rendered again, no RNG draw,
-        no training pass, no recording dropped; ``evaluate()``'s result is what it was.  Per rank with ``world_size > 1``."""
-        if depthKind not in ("median", "expected"):
-            raise ValueError(f"normalConsistency: depthKind must be 'median' or 'expected', not {depthKind!r}")
-        cams, imgs, bufs, ids = self._eval_views("normalConsistency", viewIds, split)
-        t0 = time.perf_counter()
-        self._eval_drain()
-        n = len(ids)
-        out = self.device.createBuffer(24 * max(1, n), "normal agreement sums")
-        scratch = self.device.createBuffer(16 * max([1] + [int(imgs[v]["width"]) * int(imgs[v]["height"]) for v in ids]), "depth normals")
-        try:
-            def measure(i, v, s, w, h):
-                s.rasterizer.encodeDepth(None, (depthKind,))
-                s.rasterizer.encodeNormal(None)
-                ops.depthToNormals(self.device, s.rasterizer.getDepthTextureView(depthKind), w, h, cams[v]["camera"], scratch)
-                ops.encodeNormalAgreement(self.device, s.rasterizer.getNormalTextureView(), scratch, w, h, self.device.view(out.ptr + 24 * i, 24))
-            self._render_eval_views(ids, imgs, bufs, measure, what="normalConsistency")
-            sums = (out.read(np.uint64, count=3 * n) if n else np.zeros(0, np.uint64)).reshape(n, 3)
-        finally:
-            scratch.destroy()
-            out.destroy()
-        sum_e, sum_a, pixels = ([int(x) for x in sums[:, k]] for k in range(3))
-        return dict(iteration=self.iteration, views=ids, value=[(e / a) if a else float("nan") for e, a in zip(sum_e, sum_a)], pixels=pixels,
-                    sum_e=sum_e, sum_a=sum_a, mean=(sum(sum_e) / sum(sum_a)) if sum(sum_a) else float("nan"), ms=(time.perf_counter() - t0) * 1e3)
-
-    # ------------------------------------------------------------------ TSDF fusion and mesh extraction (DESIGN.md section 13; no reference counterpart)
     def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
-        """Fuses the current model's depth maps into ``volume``: for each view in the order given, the forward pass, rasterize,
-        ``encodeDepth((depthKind, "weight_sum"))`` and ``volume.integrate`` with the weight sum and the rasterizer's output texture as colour (where the
-        volume has colour).  Returns the view list.
-
-        Rendered through evaluate's passes, with its isolation: the pipeline is drained, no RNG draw, no training pass, no recording dropped, the
-        iteration counter untouched.  A view is integrated only once its render is known not to have overflowed its tile-entry lists (one wait per view):
-        a fusion cannot be taken back, so it never sees a truncated render.  Per rank with ``world_size > 1``."""
-        if depthKind not in ("median", "expected"):
-            raise ValueError(f"fuseDepth: depthKind must be 'median' or 'expected', not {depthKind!r}")
-        cams, imgs, bufs, ids = self._eval_views("fuseDepth", viewIds, split)
-        self._eval_drain()
-        for v in ids:
-            self._render_eval_views([v], imgs, bufs, lambda i, v, s, w, h: None, what="fuseDepth")   # (returns with the view's complete frame in its pass set)
-            w, h = int(imgs[v]["width"]), int(imgs[v]["height"])
-            rast = self._eval_set(w, h, bufs[v]).rasterizer
-            rast.encodeDepth(None, (depthKind, "weight_sum"))
-            volume.integrate(rast.getDepthTextureView(depthKind), bufs[v], w, h, weightSum=rast.getDepthTextureView("weight_sum"),
-                             colour=rast.getOutputTextureView() if volume.colour else None)
-        return ids
+        """``Evaluator.fuseDepth``: fuses the current model's depth maps into ``volume``."""
+        return self.evaluator.fuseDepth(volume, viewIds, split, depthKind)
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
                     keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **volumeOptions) -> dict:
-        """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
-        ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result.
+        """``Evaluator.extractMesh``: the current model as a triangle mesh of the box ``[lo, hi]``."""
+        return self.evaluator.extractMesh(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, **volumeOptions)
 
-        ``keepLargest``, ``minTriangles``, ``minFraction``: with any of them set, the mesh goes through ``ops.removeSmallComponents`` -- the floaters of
-        a fused mesh are small components of their own -- and its dict is returned (``vertexMap``, ``faceMap`` and ``components`` added).  With the
-        defaults the raw level set is returned as before and nothing more is launched."""
-        volume = ops.TSDFVolume.fromBounds(self.device, lo, hi, voxelSize, **volumeOptions)
-        try:
-            self.fuseDepth(volume, viewIds, split, depthKind)
-            mesh = volume.extractMesh(minWeight)
-        finally:
-            volume.destroy()
-        if ops._is_default_selection(keepLargest, minTriangles, minFraction):
-            return mesh
-        return ops.removeSmallComponents(self.device, mesh, keepLargest, minTriangles, minFraction)
-
-    # ------------------------------------------------------------------ mesh accuracy against a reference point set (DESIGN.md section 14; no reference counterpart)
     def evaluateGeometry(self, reference, lo, hi, voxelSize: float, maxDistance: float, threshold: float, density: Optional[float] = None, seed: int = 0,
                          keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **extractMeshOptions) -> dict:
-        """Scores the current model's geometry against ``reference`` -- an ``[M,3]`` array of surface points, or the path of a PLY that holds them:
-        ``extractMesh(lo, hi, voxelSize, **extractMeshOptions)``, ``ops.sampleMesh`` at ``density`` samples per unit area (``None``: ``1 / (voxelSize / 2)^2``,
-        a spacing of half a voxel) and ``ops.geometryMetrics(samples, reference, maxDistance, threshold)``.  Returns its dict -- accuracy, completeness,
-        chamfer, precision, recall, fscore and the counts -- with ``vertices``, ``faces``, ``samples`` (the mesh's and the sample count) and ``ms``.
-
-        ``keepLargest``, ``minTriangles`` and ``minFraction`` are ``extractMesh``'s: the published numbers are those of a mesh without its floaters.
-
-        ``extractMesh``'s isolation (``fuseDepth``'s): the pipeline is drained, no RNG draw, no training pass, no recording dropped, the iteration counter
-        untouched.  No alignment is attempted: the reference is taken to be in the scene's frame."""
-        t0 = time.perf_counter()
-        ref = loaders.loadPointsPLY(reference) if isinstance(reference, (str, bytes)) or hasattr(reference, "__fspath__") else np.ascontiguousarray(reference, np.float32)
-        if ref.ndim != 2 or ref.shape[1] != 3:
-            raise ValueError(f"evaluateGeometry: the reference must be [M, 3] points, got {ref.shape}")
-        if density is None:
-            density = 1.0 / (0.5 * float(voxelSize)) ** 2
-        mesh = self.extractMesh(lo, hi, voxelSize, keepLargest=keepLargest, minTriangles=minTriangles, minFraction=minFraction, **extractMeshOptions)
-        samples = ops.sampleMesh(self.device, mesh, density, seed, asBuffers=True)
-        try:
-            n = samples["count"]
-            out = ops.geometryMetrics(self.device, self.device.view(samples["points"].ptr, 12 * n), ref, maxDistance, threshold)
-        finally:
-            samples["points"].destroy()
-            samples["face"].destroy()
-        out.update(vertices=int(mesh["vertices"].shape[0]), faces=int(mesh["faces"].shape[0]), samples=int(n), ms=(time.perf_counter() - t0) * 1e3)
-        return out
-
-    # ------------------------------------------------------------------ render contribution and contribution-based pruning (no reference counterpart)
-    def _contribution_buffer(self, viewIds: Optional[list], split: str, what: str) -> tuple:
-        """(buffer, view ids): the views' contribution records accumulated into one new device buffer."""
-        cams, imgs, bufs, ids = self._eval_views(what, viewIds, split)
-        if sum(int(imgs[v]["width"]) * int(imgs[v]["height"]) for v in ids) >= 2 ** 32:
-            raise ValueError(f"{what}: the views hold 2^32 pixels or more; the per-Gaussian pixel count is 32 bits wide")
-        self._eval_drain()
-        stats = ops.createContributionBuffer(self.device, self.pointCloud.num_points)
-        try:
-            self._render_eval_views(ids, imgs, bufs, lambda i, v, s, w, h: s.rasterizer.encodeContribution(None, stats), restart=stats.clear, what=what)
-        except BaseException:
-            stats.destroy()
-            raise
-        return stats, ids
+        """``Evaluator.evaluateGeometry``: the extracted mesh scored against a reference point set."""
+        return self.evaluator.evaluateGeometry(reference, lo, hi, voxelSize, maxDistance, threshold, density, seed, keepLargest, minTriangles, minFraction,
+                                               **extractMeshOptions)
 
     def contributionStats(self, viewIds: Optional[list] = None, split: str = "train") -> dict:
-        """How much of each Gaussian the views' images hold: ``dict(sum_q, weight_sum, max_weight, pixels, views)``, one
-        entry per Gaussian, accumulated over the views -- the sum and the maximum of the compositing weights ``alpha (1 - A)`` and the number of
-        (pixel, Gaussian) pairs composited.  Rendered through evaluate's passes, with its isolation: the pipeline is drained, a view whose lists
-        overflowed is rendered again (the records are cleared and every view is walked again), no RNG draw, no training pass, no recording
-        dropped.  Per rank with ``world_size > 1``."""
-        stats, ids = self._contribution_buffer(viewIds, split, "contributionStats")
-        try:
-            out = ops.readContribution(stats, self.pointCloud.num_points)
-        finally:
-            stats.destroy()
-        out["views"] = ids
-        return out
+        """``Evaluator.contributionStats``: how much of each Gaussian the views' images hold."""
+        return self.evaluator.contributionStats(viewIds, split)
 
+    # ------------------------------------------------------------------ contribution-based pruning (no reference counterpart)
     def pruneByContribution(self, minMaxWeight: float = 0.0, minWeightSum: float = 0.0, minPixels: int = 0, fraction: float = 0.0,
                             viewIds: Optional[list] = None) -> dict:
         """Removes the Gaussians the training views (``viewIds``: all) need least: a Gaussian is kept iff it meets every criterion given --
@@ -1143,7 +903,7 @@ class Trainer:
             raise ValueError("pruneByContribution: give at least one of minMaxWeight, minWeightSum, minPixels, fraction")
         if self.optimizer is None or self.densifyPrune is None:
             raise RuntimeError("pruneByContribution: no point cloud")
-        stats, _ = self._contribution_buffer(viewIds, "train", "pruneByContribution")
+        stats, _ = self.evaluator.contributionBuffer(viewIds, "train", "pruneByContribution")
         try:
             n = self.pointCloud.num_points
             unchanged = dict(before=n, after=n, pruned=0)

@@ -15,8 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import loaders
-from ._lib import CapacityError
-from .ops import CapacityReports, HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer, depthToRGBA8, normalToRGBA8
+from .ops import HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer, depthToRGBA8, grownTileEntries, normalToRGBA8
 
 
 def encodePNG(rgba: np.ndarray) -> bytes:
@@ -155,23 +154,16 @@ class Viewer:
         """Waits for this viewer's frame.  If its tile-entry list outran what the library sized for the cloud (the reference would show the truncated
         picture; the library reports it), the viewer's passes are rebuilt around larger lists and ``rerender()`` encodes the frame again.  (A report
         about this viewer's pass may have been consumed by another owner's wait -- a Trainer on the same device: it was left in
-        ``device.capacityReports``, and is answered here.)"""
+        ``device.capacityReports``, and ``settle`` finds it there.)"""
         for _ in range(4):  # this viewer's own pass: its word is consumed by its own check
             if self.forwardPass is None:
                 break
-            try:
-                self.forwardPass.check()
-                left = self.device.capacityReports.take([int(self.forwardPass.handle.value or 0)])   # (consumed by another owner's wait, left for us)
-                if left is not None:
-                    raise left
+            mine = self.device.capacityReports.settle([int(self.forwardPass.handle.value or 0)], self.forwardPass.check).mine
+            if not mine:
                 break
-            except CapacityError as e:
-                mine, _ = CapacityReports.split(e, [int(self.forwardPass.handle.value or 0)])   # (a report names up to four passes: this viewer's line)
-                if not mine:
-                    raise
-                self._tile_entries = min(max(2 * mine[0].capacity, int(mine[0].needed * 1.5)), 0xFFFFF000)
-                self._build_passes()
-                rerender()
+            self._tile_entries = grownTileEntries(mine[0].capacity, mine[0].needed)
+            self._build_passes()
+            rerender()
 
     def readFrame(self) -> np.ndarray:
         """The presented image as ``[H, W, 4]`` uint8 (synchronises; a frame whose tile-entry list outran the passes is rendered again around
