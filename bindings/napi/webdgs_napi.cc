@@ -470,6 +470,37 @@ static napi_value meshComponentsCompact(napi_env env, napi_callback_info info) {
                                                   get_ptr(env, argv[4]), get_ptr(env, argv[5]), get_u32(env, argv[6]), get_u32(env, argv[7])));
     return js_undefined(env);
 }
+// Welding a triangle soup (include/webdgs.h: wdgs_mesh_welder_*; no reference counterpart).  Slot counts travel as doubles: 2^32 and more must reach the library to be refused
+static uint64_t get_slots(napi_env env, napi_value v) { const double n = get_f64(env, v); return (n >= 0 && n < 18446744073709551616.0) ? (uint64_t)n : ~0ull; }
+static napi_value meshWelderCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_mesh_welder* w = nullptr;
+    WDGS_OK_OR_THROW(wdgs_mesh_welder_create((wdgs_device*)get_ptr(env, argv[0]), &w));
+    return make_ptr(env, w);
+}
+static napi_value meshWelderDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_mesh_welder_destroy((wdgs_mesh_welder*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value meshWelderCount(napi_env env, napi_callback_info info) {  // (welder, keysPtr, numSlots) -> numVertices
+    ARGS(3);
+    uint32_t v = 0;
+    WDGS_OK_OR_THROW(wdgs_mesh_welder_count((wdgs_mesh_welder*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_slots(env, argv[2]), &v));
+    return make_u32(env, v);
+}
+static napi_value meshWelderEmit(napi_env env, napi_callback_info info) {
+    // (welder, keysPtr, numSlots, positionsPtr | null, coloursPtr | null, keysOutPtr | null, verticesOutPtr | null, coloursOutPtr | null, facesOutPtr, capacityVertices)
+    ARGS(10);
+    WDGS_OK_OR_THROW(wdgs_mesh_welder_emit((wdgs_mesh_welder*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_slots(env, argv[2]), get_ptr(env, argv[3]),
+                                           get_ptr(env, argv[4]), get_ptr(env, argv[5]), get_ptr(env, argv[6]), get_ptr(env, argv[7]), get_ptr(env, argv[8]),
+                                           get_u32(env, argv[9])));
+    return js_undefined(env);
+}
+static napi_value meshWelderStats(napi_env env, napi_callback_info info) {  // (welder) -> [passesRun, passesSkipped, vertices, slots]
+    ARGS(1);
+    uint32_t r[4] = {0, 0, 0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_welder_stats((const wdgs_mesh_welder*)get_ptr(env, argv[0]), &r[0], &r[1], &r[2], &r[3]));
+    napi_value a; napi_create_array_with_length(env, 4, &a);
+    for (uint32_t i = 0; i < 4; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
+    return a;
+}
 static napi_value pointIndexCreate(napi_env env, napi_callback_info info) {  // (device, pointsPtr, numPoints, cellSize: 0 = chosen by the first query) -> handle
     ARGS(4);
     wdgs_point_index* ix = nullptr;
@@ -1144,6 +1175,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(meshSamplerCreate); EXPORT_FN(meshSamplerDestroy); EXPORT_FN(meshSamplerCount); EXPORT_FN(meshSamplerEmit);
     EXPORT_FN(meshComponentsCreate); EXPORT_FN(meshComponentsDestroy); EXPORT_FN(meshComponentsLabel); EXPORT_FN(meshComponentsGet); EXPORT_FN(meshComponentsSelect);
     EXPORT_FN(meshComponentsCompact);
+    EXPORT_FN(meshWelderCreate); EXPORT_FN(meshWelderDestroy); EXPORT_FN(meshWelderCount); EXPORT_FN(meshWelderEmit); EXPORT_FN(meshWelderStats);
     EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
     EXPORT_FN(pointDistanceStats);
     EXPORT_FN(pointIndexBounds); EXPORT_FN(pointIndexKNearest); EXPORT_FN(pointCloudPositions); EXPORT_FN(pointCloudNeighbourScales);

@@ -213,18 +213,42 @@ class Evaluator {
   /** The current model as a triangle mesh of the box [lo, hi]: TSDFVolume.fromBounds, fuseDepth over the views, extractMesh(minWeight); the volume is
    *  destroyed.  options: { viewIds, split, depthKind, minWeight, truncation, maxWeight, colour, keepLargest, minTriangles, minFraction }.  With one of the
    *  last three set the mesh goes through hip.removeSmallComponents (the floaters of a fused mesh are small components of their own) and its object is
-   *  returned; otherwise the raw level set, as before, and nothing more is launched.  loaders.saveMeshPLY writes the result. */
+   *  returned; otherwise the raw level set, as before, and nothing more is launched.  loaders.saveMeshPLY writes the result.
+   *  options.weld: 'host' (default) or 'device' (DESIGN.md section 17): the triangles are welded where the volume emitted them and, with a component rule,
+   *  labelled, selected and compacted there as well; the compacted mesh is what is read, colours and keys are read at the welded mesh's size and gathered
+   *  through vertexMap.  The same bytes either way. */
   extractMesh(lo, hi, voxelSize, options) {
-    const o = options || {};
+    const o = options || {}, weld = o.weld || 'host';
+    if (weld !== 'host' && weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
+    const unset = (x) => x === undefined || x === null;
+    const everything = unset(o.keepLargest) && !(o.minTriangles > 0) && !(o.minFraction > 0);
+    const rule = { keepLargest: o.keepLargest, minTriangles: o.minTriangles, minFraction: o.minFraction };
     const volume = hip.TSDFVolume.fromBounds(this.device, lo, hi, voxelSize, { truncation: o.truncation, maxWeight: o.maxWeight, colour: o.colour });
-    let mesh;
+    let mesh = null, welded = null;
     try {
       this.fuseDepth(volume, o.viewIds, o.split, o.depthKind);
-      mesh = volume.extractMesh(o.minWeight);
+      if (weld === 'host' || everything) {
+        mesh = volume.extractMesh(o.minWeight, { weld });
+      } else {
+        const tri = volume.extractTriangleBuffers(o.minWeight);
+        try { welded = hip.weldTrianglesDevice(this.device, tri, { asBuffers: true }); } finally { hip.destroyBuffers(tri); }
+      }
     } finally { volume.destroy(); }
-    const unset = (x) => x === undefined || x === null;
-    if (unset(o.keepLargest) && !(o.minTriangles > 0) && !(o.minFraction > 0)) return mesh;
-    return hip.removeSmallComponents(this.device, mesh, { keepLargest: o.keepLargest, minTriangles: o.minTriangles, minFraction: o.minFraction });
+    if (everything) return mesh;
+    if (!welded) return hip.removeSmallComponents(this.device, mesh, rule);
+    try {
+      const out = hip.removeSmallComponents(this.device, { vertices: welded.vertices, faces: welded.faces }, rule);
+      const V = welded.numVertices, bytes = (b, n) => (n ? this.device.readBuffer(b, n) : new ArrayBuffer(0));
+      out.colours = null;
+      if (welded.colours) {
+        const rgba = new Uint8Array(bytes(welded.colours, 4 * V));
+        out.colours = new Uint8Array(3 * out.vertexMap.length);
+        out.vertexMap.forEach((old, i) => { for (let a = 0; a < 3; a++) out.colours[3 * i + a] = rgba[4 * old + a]; });
+      }
+      const keys = new BigUint64Array(bytes(welded.keys, 8 * V));
+      out.keys = BigUint64Array.from(out.vertexMap, (old) => keys[old]);
+      return out;
+    } finally { hip.destroyBuffers(welded); }
   }
 
   // ---------------------------------------------------------------- render contribution (DESIGN.md section 11)

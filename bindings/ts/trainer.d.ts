@@ -71,15 +71,17 @@ export class Trainer {
    *  passes, training untouched.  Returns the view list.  No reference counterpart. */
   fuseDepth(volume: import('./webdgs_hip').TSDFVolume, viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): number[];
   /** TSDFVolume.fromBounds -> fuseDepth -> extractMesh -> destroy: the current model as a triangle mesh of the box [lo, hi]; with keepLargest, minTriangles or
-   *  minFraction set, without the components removeSmallComponents drops.  No reference counterpart. */
+   *  minFraction set, without the components removeSmallComponents drops.  weld: 'host' (default) or 'device' -- welded, and with a component rule cleaned,
+   *  on the device; the same bytes.  No reference counterpart. */
   extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number,
               options?: { viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected'; minWeight?: number; truncation?: number; maxWeight?: number;
-                          colour?: boolean } & import('./webdgs_hip').ComponentSelection): import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh;
+                          colour?: boolean; weld?: 'host' | 'device' } & import('./webdgs_hip').ComponentSelection): import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh;
   /** extractMesh -> sampleMesh -> geometryMetrics against `reference` (points [M*3], or the path of a PLY): the mesh's accuracy, completeness, Chamfer
    *  distance, precision, recall and F-score, with the mesh's vertex, face and sample counts and ms.  Training untouched.  No reference counterpart. */
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,
                    options?: { density?: number | null; seed?: number; viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected';
-                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean } & import('./webdgs_hip').ComponentSelection):
+                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device' } &
+                     import('./webdgs_hip').ComponentSelection):
     import('./webdgs_hip').GeometryMetrics & { vertices: number; faces: number; samples: number; ms: number };
   /** Per-Gaussian render contribution accumulated over the views (default: all training views); no reference counterpart. */
   contributionStats(viewIds?: number[] | null, split?: 'eval' | 'train'): ContributionRecords & { views: number[] };

@@ -247,11 +247,34 @@ export class TSDFVolume {
             options?: { weightSum?: HipBuffer | null; colour?: HipBuffer | null; minWeightSum?: number | null }): void;
   countTriangles(minWeight?: number | null): number;
   extractTriangles(minWeight?: number | null): TSDFTriangles;
-  extractMesh(minWeight?: number | null): TriangleMesh;
+  /** extractTriangles without the read-back: what weldTrianglesDevice takes; the caller destroys the buffers (destroyBuffers). */
+  extractTriangleBuffers(minWeight?: number | null): TSDFTriangleBuffers;
+  /** weld: 'host' (default: weldTriangles) or 'device' (weldTrianglesDevice: the same bytes, slot-sized arrays never cross the bus). */
+  extractMesh(minWeight?: number | null, options?: { weld?: 'host' | 'device' }): TriangleMesh;
   destroy(): void;
 }
 /** extractTriangles' output as an indexed mesh: vertices are the distinct edge keys in ascending order.  No reference counterpart. */
 export function weldTriangles(tri: TSDFTriangles): TriangleMesh;
+/** positions f32[F][3][3], keys u64[F][3], colours rgba8[F][3] on the device. */
+export interface TSDFTriangleBuffers { positions: HipBuffer; keys: HipBuffer; colours: HipBuffer | null; numTriangles: number }
+/** vertices f32[V][3], faces u32[F][3], keys u64[V], colours rgba8[V] on the device, each buffer of exactly that size. */
+export interface WeldedMeshBuffers { vertices: HipBuffer; faces: HipBuffer; colours: HipBuffer | null; keys: HipBuffer; numVertices: number; numFaces: number }
+/** Welds a triangle soup on the device (wdgs_mesh_welder): a stable u64 radix sort of (key, slot) pairs, head flags, a scan, a gather; count, then emit with
+ *  the same keys.  No reference counterpart. */
+export class MeshWelder {
+  constructor(device: HipDevice);
+  readonly numSlots: number; readonly numVertices: number;
+  count(keys: HipBuffer | null, numSlots: number): number;
+  emit(keys: HipBuffer | null, numSlots: number, positions: HipBuffer | null, colours: HipBuffer | null, facesOut: HipBuffer | null, verticesOut?: HipBuffer | null,
+       coloursOut?: HipBuffer | null, keysOut?: HipBuffer | null, capacity?: number | null): void;
+  stats(): { passesRun: number; passesSkipped: number; vertices: number; slots: number };
+  destroy(): void;
+}
+/** weldTriangles on the device, byte for byte; a vertex takes the position and colour of the lowest slot that carries its key.  No reference counterpart. */
+export function weldTrianglesDevice(device: HipDevice, tri: TSDFTriangles | TSDFTriangleBuffers, options?: { asBuffers?: false }): TriangleMesh;
+export function weldTrianglesDevice(device: HipDevice, tri: TSDFTriangles | TSDFTriangleBuffers, options: { asBuffers: true }): WeldedMeshBuffers;
+/** Destroys every HipBuffer among the values of `buffers`. */
+export function destroyBuffers(buffers: object): void;
 /** The index of "no point found" (PointIndex.nearest).  No reference counterpart. */
 export const NO_INDEX: 0xFFFFFFFF;
 export interface MeshSamples { points: Float32Array; face: Uint32Array; count: number }

@@ -555,8 +555,26 @@ class TSDFVolume {
         colours: cols ? new Uint8Array(bytes(cols, 12 * total)) : null, count: total };
     } finally { pos.destroy(); keys.destroy(); if (cols) cols.destroy(); }
   }
-  /** The welded mesh (weldTriangles of extractTriangles). */
-  extractMesh(minWeight) { return weldTriangles(this.extractTriangles(minWeight)); }
+  /** extractTriangles without the read-back: { positions, keys, colours | null, numTriangles }, the three as HipBuffers the caller destroys
+   *  (f32[F][3][3], u64[F][3], rgba8[F][3]): what weldTrianglesDevice takes. */
+  extractTriangleBuffers(minWeight) {
+    const total = this.countTriangles(minWeight), room = Math.max(total, 1);
+    const out = { positions: this.device.createBuffer({ size: 36 * room }), keys: this.device.createBuffer({ size: 24 * room }),
+      colours: this.colour ? this.device.createBuffer({ size: 12 * room }) : null, numTriangles: total };
+    try {
+      addon.tsdfVolumeEmitTriangles(this.handle, out.positions.ptr, out.keys.ptr, out.colours ? out.colours.ptr : null, total);
+    } catch (e) { destroyBuffers(out); throw e; }
+    return out;
+  }
+  /** The welded mesh.  options.weld: 'host' (default: weldTriangles of extractTriangles) or 'device' (the triangles stay on the device and
+   *  weldTrianglesDevice welds them there: the same bytes, and only the V- and F-sized arrays of the result cross the bus). */
+  extractMesh(minWeight, options) {
+    const weld = (options && options.weld) || 'host';
+    if (weld === 'host') return weldTriangles(this.extractTriangles(minWeight));
+    if (weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
+    const tri = this.extractTriangleBuffers(minWeight);
+    try { return weldTrianglesDevice(this.device, tri); } finally { destroyBuffers(tri); }
+  }
   destroy() {
     if (this.destroyed) return;
     this.destroyed = true;
@@ -583,6 +601,89 @@ function weldTriangles(tri) {
     if (colours) for (let a = 0; a < 3; a++) colours[3 * v + a] = tri.colours[4 * i + a];
   });
   return { vertices, faces, colours, keys };
+}
+
+// ---------------------------------------------------------------- welding on the device (include/webdgs.h, DESIGN.md section 17; no reference counterpart)
+/** Destroys every HipBuffer among the values of `buffers` (what extractTriangleBuffers and weldTrianglesDevice hand out). */
+function destroyBuffers(buffers) { Object.values(buffers).forEach((b) => { if (b instanceof HipBuffer) b.destroy(); }); }
+/** A buffer the library owns whose size is exactly `size` bytes, 0 included (asDevice counts whole rows of it). */
+function exactBuffer(device, size) {
+  const b = addon.bufferCreate(device.handle, Math.max(size, 8));
+  return new HipBuffer(device, b.ptr, size, b.handle);
+}
+/** Welds a triangle soup on the device (wdgs_mesh_welder): count sorts the (key, slot) pairs with a stable radix sort, flags the first pair of every
+ *  distinct key and returns their number (one wait); emit writes the indexed mesh.  weldTrianglesDevice is the one-call form. */
+class MeshWelder {
+  constructor(device) { this.device = device; this.destroyed = false; this.numSlots = 0; this.numVertices = 0; this.handle = addon.meshWelderCreate(device.handle); }
+  /** The number of distinct keys among keys u64[numSlots], numSlots three per triangle and below 2^32 (sort, flags, scan; waits once). */
+  count(keys, numSlots) {
+    if (keys && numSlots < 2 ** 32 && keys.size < 8 * numSlots) throw new Error('MeshWelder.count: buffer too small for the keys');
+    this.numVertices = addon.meshWelderCount(this.handle, keys ? keys.ptr : null, numSlots);
+    this.numSlots = numSlots;
+    return this.numVertices;
+  }
+  /** Writes facesOut u32[numSlots], verticesOut f32[V][3] gathered from positions, coloursOut rgba8[V] gathered from colours and keysOut u64[V] for the
+   *  count before it (WDGS_E_STATE otherwise; WDGS_E_CAPACITY, with nothing written, when there is room for fewer than V vertices).  Each pair and
+   *  keysOut nullable.  Stream-ordered: it waits for nothing and records. */
+  emit(keys, numSlots, positions, colours, facesOut, verticesOut, coloursOut, keysOut, capacity) {
+    const outs = [[verticesOut, 12], [coloursOut, 4], [keysOut, 8]].filter(([b]) => b);
+    const cap = capacity === undefined || capacity === null ? Math.min(0xFFFFFFFF, ...outs.map(([b, s]) => Math.floor(b.size / s))) : capacity;
+    for (const [b, s] of outs) if (cap * s > b.size) throw new Error('MeshWelder.emit: the capacity exceeds the buffers');
+    if (numSlots < 2 ** 32 && ((facesOut && facesOut.size < 4 * numSlots) || (positions && positions.size < 12 * numSlots) || (colours && colours.size < 4 * numSlots))) {
+      throw new Error('MeshWelder.emit: buffers too small for the slots');
+    }
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshWelderEmit(this.handle, ptr(keys), numSlots, ptr(positions), ptr(colours), ptr(keysOut), ptr(verticesOut), ptr(coloursOut), ptr(facesOut), cap);
+  }
+  /** The last count: { passesRun, passesSkipped, vertices, slots } -- of the eight radix passes, those whose digit differs somewhere ran. */
+  stats() {
+    const r = addon.meshWelderStats(this.handle);
+    return { passesRun: r[0], passesSkipped: r[1], vertices: r[2], slots: r[3] };
+  }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.meshWelderDestroy(this.handle); this.handle = null; }
+}
+/** weldTriangles on the device, byte for byte: `tri` is extractTriangles' output (uploaded) or extractTriangleBuffers' (left as it is); returns what
+ *  weldTriangles returns.  A vertex takes the position and colour of the lowest slot that carries its key.  options.asBuffers: vertices f32[V][3], faces
+ *  u32[F][3], keys u64[V] and colours rgba8[V] (or null) stay on the device as HipBuffers of exactly those sizes -- what meshComponents,
+ *  removeSmallComponents and sampleMesh take -- with numVertices and numFaces; the caller destroys them (destroyBuffers). */
+function weldTrianglesDevice(device, tri, options) {
+  const own = !(tri.keys instanceof HipBuffer);
+  let src, F;
+  if (own) {
+    if (tri.keys.length % 3 !== 0) throw new Error('weldTrianglesDevice: the keys are not three per triangle');
+    F = tri.keys.length / 3;
+    if (tri.positions.length !== 9 * F || (tri.colours && tri.colours.length !== 12 * F)) throw new Error('weldTrianglesDevice: positions or colours disagree with the keys');
+    const upload = (a) => { const b = device.createBuffer({ size: Math.max(a.byteLength, 8) }); if (a.byteLength) device.queue.writeBuffer(b, 0, a); return b; };
+    src = { keys: upload(tri.keys), positions: upload(tri.positions), colours: tri.colours ? upload(tri.colours) : null };
+  } else {
+    F = tri.numTriangles;
+    src = { keys: tri.keys, positions: tri.positions, colours: tri.colours || null };
+  }
+  const S = 3 * F, welder = new MeshWelder(device);
+  let out = {};
+  try {
+    const V = welder.count(src.keys, S);
+    out = { vertices: exactBuffer(device, 12 * V), faces: exactBuffer(device, 4 * S), colours: src.colours ? exactBuffer(device, 4 * V) : null, keys: exactBuffer(device, 8 * V) };
+    welder.emit(src.keys, S, src.positions, src.colours, out.faces, out.vertices, out.colours, out.keys, V);
+    if (options && options.asBuffers) {
+      device.synchronize();   // (an uploaded soup is released below)
+      const result = Object.assign({}, out, { numVertices: V, numFaces: F });
+      out = {};
+      return result;
+    }
+    const bytes = (b, n) => (n ? device.readBuffer(b, n) : new ArrayBuffer(0));
+    let colours = null;
+    if (out.colours) {
+      const rgba = new Uint8Array(bytes(out.colours, 4 * V));
+      colours = new Uint8Array(3 * V);
+      for (let v = 0; v < V; v++) for (let a = 0; a < 3; a++) colours[3 * v + a] = rgba[4 * v + a];
+    }
+    return { vertices: new Float32Array(bytes(out.vertices, 12 * V)), faces: new Uint32Array(bytes(out.faces, 4 * S)), colours, keys: new BigUint64Array(bytes(out.keys, 8 * V)) };
+  } finally {
+    welder.destroy();
+    destroyBuffers(out);
+    if (own) destroyBuffers(src);
+  }
 }
 
 // ---------------------------------------------------------------- mesh accuracy metrics (include/webdgs.h, DESIGN.md section 14; no reference counterpart)
@@ -973,7 +1074,7 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, MeshWelder, weldTrianglesDevice, destroyBuffers, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
   geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, grownTileEntries, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

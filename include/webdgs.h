@@ -759,6 +759,31 @@ int wdgs_mesh_components_select(wdgs_mesh_components* components, const uint8_t*
 int wdgs_mesh_components_compact(wdgs_mesh_components* components, const void* vertices_f32_dev, void* vertices_out_f32_dev, void* faces_out_u32_dev,
                                  void* vertex_map_u32_dev, void* face_map_u32_dev, uint32_t capacity_vertices, uint32_t capacity_faces);
 
+/* ---------------------------------------------------------------- Welding a triangle soup: a stable u64 key sort, head flags, a scan, a gather
+ *
+ * Input: S = 3 F slots, 0 <= S < 2^32 (anything else: WDGS_E_INVALID), with keys u64[S], positions f32[S][3] and (optional) colours rgba8[S] on the device -- the
+ * layout emit_triangles writes.  Keys are arbitrary u64; 0 and 2^64 - 1 are keys like any other.  Outputs: V, the number of distinct keys; keys_out u64[V], the
+ * distinct keys ascending; vertices f32[V][3] and colours rgba8[V], for every distinct key the bits of the LOWEST slot that carries it (also where equal keys carry
+ * different positions); faces u32[S], for every slot the rank of its key among the distinct keys.  Each is a function of the input alone, bit for bit, whatever the
+ * launch geometry or the order in which threads ran: a stable least-significant-digit radix sort of (key, slot) pairs by 8-bit digits, each pass a histogram, a scan
+ * and a scatter in launches of their own, and no workgroup ever waits for another.  A pass whose digit is the same in every key is skipped.  No reference counterpart. */
+typedef struct wdgs_mesh_welder wdgs_mesh_welder;
+int wdgs_mesh_welder_create(wdgs_device* dev, wdgs_mesh_welder** out);
+int wdgs_mesh_welder_destroy(wdgs_mesh_welder* welder);
+/* Sorts the pairs into arrays the object owns (it grows them as needed: 32 bytes per slot), flags the heads and scans them.  Waits once, to read V, so it cannot be
+ * recorded (WDGS_E_STATE).  WDGS_E_INVALID for num_slots >= 2^32 or no multiple of 3 and for null keys with num_slots != 0.  The keys are read again by emit when
+ * no pass ran and must stay as they are until then. */
+int wdgs_mesh_welder_count(wdgs_mesh_welder* welder, const void* keys_u64_dev, uint64_t num_slots, uint32_t* num_vertices);
+/* Writes the outputs of the last count: faces_out u32[S]; keys_out u64[V] (nullable); vertices_out f32[V][3] gathered from positions (nullable together);
+ * colours_out rgba8[V] gathered from colours (nullable together).  WDGS_E_STATE unless the last count succeeded with these very keys and num_slots;
+ * WDGS_E_CAPACITY when capacity_vertices < V; nothing is written in either case.  Stream-ordered, no host wait, recordable. */
+int wdgs_mesh_welder_emit(wdgs_mesh_welder* welder, const void* keys_u64_dev, uint64_t num_slots, const void* positions_f32_dev, const void* colours_rgba8_dev,
+                          void* keys_out_u64_dev, void* vertices_out_f32_dev, void* colours_out_rgba8_dev, void* faces_out_u32_dev, uint32_t capacity_vertices);
+/* The last count: the radix passes that ran and those skipped (eight in all), V and S; each pointer nullable.  WDGS_E_STATE when no count precedes it.  The
+ * kernels' event times are the device's (wdgs_device_get_kernel_times): weld_key_bits, weld_plan, weld_histogram, weld_scatter, weld_heads, weld_emit and the
+ * scan's three.  No device work. */
+int wdgs_mesh_welder_stats(const wdgs_mesh_welder* welder, uint32_t* passes_run, uint32_t* passes_skipped, uint32_t* num_vertices, uint32_t* num_slots);
+
 #ifdef __cplusplus
 }
 #endif

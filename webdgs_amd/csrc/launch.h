@@ -118,6 +118,23 @@ int launch_mesh_keep_flags(wdgs_device* dev, u32 n, const u32* component, const 
 int launch_mesh_emit(wdgs_device* dev, const u32* faces, u32 F, u32 V, const u32* vertex_flags, const u32* vertex_offsets, const u32* face_flags, const u32* face_offsets,
                      const float* positions, float* positions_out, u32* vertex_map, u32* faces_out, u32* face_map);
 
+// ---- meshweld.hip.  keys u64[S] (the caller's, never written); keys_a, keys_b u64[S] and slots_a, slots_b u32[S]: the pair buffers the sort's passes alternate
+// between; counters: the welder's 28-word block (V and the plan of passes); every kernel of a pass that the plan skips returns at once
+// or_and: u64[2 * weld_table_words(S) / 256], written: the OR and the AND of every tile's keys; counters: the plan, written
+int launch_weld_plan(wdgs_device* dev, const unsigned long long* keys, u32 S, unsigned long long* or_and, u32* counters);
+// the words of the digit-major table (and of its scan) for S slots
+u32 weld_table_words(u32 S);
+// table, offsets: u32[weld_table_words(S)], written by every pass that runs
+int launch_weld_sort(wdgs_device* dev, ScanScratch* scan, const unsigned long long* keys, u32 S, unsigned long long* keys_a, unsigned long long* keys_b, u32* slots_a,
+                     u32* slots_b, const u32* counters, u32* table, u32* offsets);
+// flags u32[S], written: 1 where a sorted pair begins a run of equal keys
+int launch_weld_heads(wdgs_device* dev, const unsigned long long* keys, u32 S, const unsigned long long* keys_a, const unsigned long long* keys_b, const u32* counters,
+                      u32* flags);
+// ids: the exclusive scan of flags; positions f32[S][3] with vertices_out, colours rgba8[S] with colours_out, keys_out: each nullable; faces_out u32[S]
+int launch_weld_emit(wdgs_device* dev, const unsigned long long* keys, u32 S, const unsigned long long* keys_a, const unsigned long long* keys_b, const u32* slots_a,
+                     const u32* slots_b, const u32* counters, const u32* flags, const u32* ids, const float* positions, const u32* colours, unsigned long long* keys_out,
+                     float* vertices_out, u32* colours_out, u32* faces_out);
+
 // ---- loss.hip, dssim.hip. pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
 int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
                      const u32* acc_dirty);

@@ -220,22 +220,47 @@ class Evaluator:
         return ids
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
-                    keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **volumeOptions) -> dict:
+                    keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", **volumeOptions) -> dict:
         """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
         ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result.
 
         ``keepLargest``, ``minTriangles``, ``minFraction``: with any of them set, the mesh goes through ``ops.removeSmallComponents`` -- the floaters of
         a fused mesh are small components of their own -- and its dict is returned (``vertexMap``, ``faceMap`` and ``components`` added).  With the
-        defaults the raw level set is returned as before and nothing more is launched."""
+        defaults the raw level set is returned as before and nothing more is launched.
+
+        ``weld="device"``: the triangles are welded where the volume emitted them (``ops.weldTrianglesDevice``) and, with a
+        component rule, labelled, selected and compacted there as well; the compacted mesh is what is read, and ``colours`` and ``keys`` are read at
+        the welded mesh's size and gathered through ``vertexMap``.  The same bytes as ``weld="host"`` either way."""
+        if weld not in ("host", "device"):
+            raise ValueError(f"extractMesh: weld must be 'host' or 'device', not {weld!r}")
+        everything = ops._is_default_selection(keepLargest, minTriangles, minFraction)
         volume = ops.TSDFVolume.fromBounds(self.device, lo, hi, voxelSize, **volumeOptions)
+        mesh = welded = None
         try:
             self.fuseDepth(volume, viewIds, split, depthKind)
-            mesh = volume.extractMesh(minWeight)
+            if weld == "host" or everything:
+                mesh = volume.extractMesh(minWeight, weld=weld)
+            else:
+                tri = volume.extractTriangleBuffers(minWeight)
+                try:
+                    welded = ops.weldTrianglesDevice(self.device, tri, asBuffers=True)
+                finally:
+                    ops.destroyBuffers(tri)
         finally:
             volume.destroy()
-        if ops._is_default_selection(keepLargest, minTriangles, minFraction):
+        if everything:
             return mesh
-        return ops.removeSmallComponents(self.device, mesh, keepLargest, minTriangles, minFraction)
+        if welded is None:
+            return ops.removeSmallComponents(self.device, mesh, keepLargest, minTriangles, minFraction)
+        try:
+            out = ops.removeSmallComponents(self.device, dict(vertices=welded["vertices"], faces=welded["faces"]), keepLargest, minTriangles, minFraction)
+            V = welded["numVertices"]
+            out["colours"] = None if welded["colours"] is None else np.ascontiguousarray(
+                welded["colours"].read(np.uint8, count=4 * V).reshape(V, 4)[:, :3][out["vertexMap"]])
+            out["keys"] = np.ascontiguousarray(welded["keys"].read(np.uint64, count=V)[out["vertexMap"]])
+            return out
+        finally:
+            ops.destroyBuffers(welded)
 
     # ------------------------------------------------------------------ mesh accuracy against a reference point set (DESIGN.md section 14)
     def evaluateGeometry(self, reference, lo, hi, voxelSize: float, maxDistance: float, threshold: float, density: Optional[float] = None, seed: int = 0,

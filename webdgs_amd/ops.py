@@ -974,10 +974,35 @@ class TSDFVolume:
             if cols is not None:
                 cols.destroy()
 
-    def extractMesh(self, minWeight: float = 1.0) -> dict:
+    def extractTriangleBuffers(self, minWeight: float = 1.0) -> dict:
+        """``extractTriangles`` without the read-back: ``dict(positions, keys, colours | None, numTriangles)``, the three as ``HipBuffer`` the caller
+        destroys (f32[F][3][3], u64[F][3], rgba8[F][3]): what ``weldTrianglesDevice`` takes."""
+        total = self.countTriangles(minWeight)
+        pos = self.device.createBuffer(36 * max(total, 1), "tsdf triangle positions")
+        keys = self.device.createBuffer(24 * max(total, 1), "tsdf triangle keys")
+        cols = self.device.createBuffer(12 * max(total, 1), "tsdf triangle colours") if self.colour else None
+        out = dict(positions=pos, keys=keys, colours=cols, numTriangles=total)
+        try:
+            check(self.device.lib.wdgs_tsdf_volume_emit_triangles(self.handle, pos.ptr, keys.ptr, cols.ptr if cols is not None else None, total))
+        except BaseException:
+            destroyBuffers(out)
+            raise
+        return out
+
+    def extractMesh(self, minWeight: float = 1.0, weld: str = "host") -> dict:
         """The welded mesh: ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None, keys u64[V])``.  Vertices are the triangles' distinct edge
-        keys in ascending order (equal keys carry equal position bits); triangles are kept as emitted, zero-area ones included.  Welded on the host."""
-        return weldTriangles(self.extractTriangles(minWeight))
+        keys in ascending order (equal keys carry equal position bits); triangles are kept as emitted, zero-area ones included.  ``weld="host"``: the
+        triangles are read back and welded by ``weldTriangles``.  ``weld="device"``: they stay on the device and ``weldTrianglesDevice`` welds them
+        there -- the same bytes, and only the V- and F-sized arrays of the result cross the bus."""
+        if weld == "host":
+            return weldTriangles(self.extractTriangles(minWeight))
+        if weld != "device":
+            raise ValueError(f"extractMesh: weld must be 'host' or 'device', not {weld!r}")
+        tri = self.extractTriangleBuffers(minWeight)
+        try:
+            return weldTrianglesDevice(self.device, tri)
+        finally:
+            destroyBuffers(tri)
 
     def destroy(self) -> None:
         if self.destroyed:
@@ -996,6 +1021,114 @@ def weldTriangles(tri: dict) -> dict:
     vertices = np.ascontiguousarray(tri["positions"], np.float32).reshape(-1, 3)[first]
     colours = None if tri.get("colours") is None else np.ascontiguousarray(np.asarray(tri["colours"], np.uint8).reshape(-1, 4)[first, :3])
     return dict(vertices=np.ascontiguousarray(vertices), faces=inverse.reshape(-1, 3).astype(np.uint32), colours=colours, keys=uniq)
+
+
+# ----------------------------------------------------------------------------- welding on the device (no reference counterpart)
+def destroyBuffers(buffers: dict) -> None:
+    """Destroys every ``HipBuffer`` among the values of ``buffers`` (the dicts ``extractTriangleBuffers`` and ``weldTrianglesDevice`` hand out)."""
+    for b in buffers.values():
+        if isinstance(b, HipBuffer):
+            b.destroy()
+
+
+class MeshWelder:
+    """Welds a triangle soup on the device (``wdgs_mesh_welder``): ``count`` sorts the (key, slot) pairs with a stable radix sort, flags the first pair
+    of every distinct key and returns their number (one wait); ``emit`` writes the indexed mesh.  ``weldTrianglesDevice`` is the one-call form;
+    include/webdgs.h states the definition."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        self.numSlots = self.numVertices = 0
+        h = C.c_void_p()
+        check(device.lib.wdgs_mesh_welder_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def count(self, keys: Optional[HipBuffer], numSlots: int) -> int:
+        """The number of distinct keys among ``keys`` u64[numSlots], ``numSlots`` three per triangle and below 2^32 (sort, flags, scan; waits once)."""
+        if not 0 <= int(numSlots) < 2 ** 64:
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshWelder.count: bad slot count {numSlots}")
+        if keys is not None and int(numSlots) < 2 ** 32 and keys.size < 8 * int(numSlots):
+            raise ValueError("MeshWelder.count: buffer too small for the keys")
+        n = C.c_uint32(0)
+        check(self.device.lib.wdgs_mesh_welder_count(self.handle, keys.ptr if keys is not None else None, int(numSlots), C.byref(n)))
+        self.numSlots, self.numVertices = int(numSlots), int(n.value)
+        return self.numVertices
+
+    def emit(self, keys: Optional[HipBuffer], numSlots: int, positions: Optional[HipBuffer], colours: Optional[HipBuffer], facesOut: Optional[HipBuffer],
+             verticesOut: Optional[HipBuffer] = None, coloursOut: Optional[HipBuffer] = None, keysOut: Optional[HipBuffer] = None,
+             capacity: Optional[int] = None) -> None:
+        """Writes ``facesOut`` u32[numSlots], ``verticesOut`` f32[V][3] gathered from ``positions`` f32[numSlots][3], ``coloursOut`` rgba8[V] gathered from
+        ``colours`` rgba8[numSlots] and ``keysOut`` u64[V] for the count before it (``StateError`` otherwise; ``CapacityError``, with nothing written, when
+        there is room for fewer than V vertices).  Stream-ordered: it waits for nothing and records."""
+        outs = ((verticesOut, 12), (coloursOut, 4), (keysOut, 8))
+        cap = min([b.size // s for b, s in outs if b is not None] or [2 ** 32 - 1]) if capacity is None else int(capacity)
+        for b, s in outs:
+            if b is not None and cap * s > b.size:
+                raise ValueError("MeshWelder.emit: the capacity exceeds the buffers")
+        n = int(numSlots)
+        if n < 2 ** 32 and ((facesOut is not None and facesOut.size < 4 * n) or (positions is not None and positions.size < 12 * n)
+                            or (colours is not None and colours.size < 4 * n)):
+            raise ValueError("MeshWelder.emit: buffers too small for the slots")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_welder_emit(self.handle, ptr(keys), n, ptr(positions), ptr(colours), ptr(keysOut), ptr(verticesOut), ptr(coloursOut),
+                                                    ptr(facesOut), cap))
+
+    def stats(self) -> dict:
+        """The last count: ``dict(passesRun, passesSkipped, vertices, slots)`` -- of the eight radix passes, those whose digit differs somewhere ran.  The
+        kernels' event times are ``HipDevice.kernelTimes``' (``weld_*`` and the scan's)."""
+        v = [C.c_uint32(0) for _ in range(4)]
+        check(self.device.lib.wdgs_mesh_welder_stats(self.handle, *[C.byref(x) for x in v]))
+        return dict(passesRun=int(v[0].value), passesSkipped=int(v[1].value), vertices=int(v[2].value), slots=int(v[3].value))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_mesh_welder_destroy(self.handle)
+        self.handle = None
+
+
+def weldTrianglesDevice(device: HipDevice, tri: dict, asBuffers: bool = False) -> dict:
+    """``weldTriangles`` on the device, byte for byte: ``tri`` is ``extractTriangles``'s numpy dict (uploaded) or ``extractTriangleBuffers``'s dict of
+    ``HipBuffer`` plus ``numTriangles`` (left as it is); returns ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None, keys u64[V])``.  A vertex
+    takes the position and colour of the lowest slot that carries its key.  ``asBuffers``: ``vertices`` f32[V][3], ``faces`` u32[F][3], ``keys`` u64[V] and
+    ``colours`` rgba8[V] (or ``None``) stay on the device as ``HipBuffer`` of exactly those sizes -- what ``meshComponents``, ``removeSmallComponents``
+    and ``sampleMesh`` take -- and ``numVertices`` and ``numFaces`` are added; the caller destroys them (``destroyBuffers``)."""
+    own = not isinstance(tri["keys"], HipBuffer)
+    if own:
+        k = np.ascontiguousarray(tri["keys"], np.uint64).reshape(-1)
+        if k.size % 3:
+            raise ValueError("weldTrianglesDevice: the keys are not three per triangle")
+        F = k.size // 3
+        p = np.ascontiguousarray(tri["positions"], np.float32).reshape(-1)
+        c = None if tri.get("colours") is None else np.ascontiguousarray(tri["colours"], np.uint8).reshape(-1)
+        if p.size != 9 * F or (c is not None and c.size != 12 * F):
+            raise ValueError("weldTrianglesDevice: positions or colours disagree with the keys")
+        src = dict(keys=device.bufferFrom(k), positions=device.bufferFrom(p), colours=None if c is None else device.bufferFrom(c))
+    else:
+        F = int(tri["numTriangles"])
+        src = dict(keys=tri["keys"], positions=tri["positions"], colours=tri.get("colours"))
+    S = 3 * F
+    welder = MeshWelder(device)
+    out = {}
+    try:
+        V = welder.count(src["keys"], S)
+        out = dict(vertices=device.createBuffer(12 * V, "welded vertices"), faces=device.createBuffer(4 * S, "welded faces"),
+                   colours=None if src["colours"] is None else device.createBuffer(4 * V, "welded colours"), keys=device.createBuffer(8 * V, "welded keys"))
+        welder.emit(src["keys"], S, src["positions"], src["colours"], out["faces"], out["vertices"], out["colours"], out["keys"], V)
+        if asBuffers:
+            device.synchronize()   # (an uploaded soup is released below)
+            result, out = dict(out, numVertices=V, numFaces=F), {}
+            return result
+        colours = None if out["colours"] is None else np.ascontiguousarray(out["colours"].read(np.uint8, count=4 * V).reshape(V, 4)[:, :3])
+        return dict(vertices=out["vertices"].read(np.float32, count=3 * V).reshape(V, 3), faces=out["faces"].read(np.uint32, count=S).reshape(F, 3),
+                    colours=colours, keys=out["keys"].read(np.uint64, count=V))
+    finally:
+        welder.destroy()
+        destroyBuffers(out)
+        if own:
+            destroyBuffers(src)
 
 
 # ----------------------------------------------------------------------------- mesh accuracy metrics (DESIGN.md section 14; no reference counterpart)
