@@ -420,6 +420,33 @@ int wdgs_debug_eval_math(wdgs_device* dev, uint32_t which, uint32_t count, const
  * ping_pong[final_out_index].  Long tile lists are not built.  WDGS_E_INVALID for a grid the forward pass never asks for. */
 int wdgs_debug_sort_tiles(wdgs_sorter* s, uint32_t route, uint32_t num_tiles_x, uint32_t num_tiles_y, void* ranges_u32_dev);
 
+/* Test hook, not part of the reference's surface: composites one frame with the forward pass's rasterize kernel (K14) on tables the caller
+ * built -- no projection, no sort.  The settings block and the tile grid are made from viewport, render mode, point size and radius cap by the
+ * code a forward pass uses (0 = the default: 128 px cap, 3 px points; a negative cap lifts it).  splats: 6 words per row, num_splats rows
+ * count (an entry whose value is >= num_splats is skipped, as the reference skips it); sorted_keys / sorted_vals: the entries, key =
+ * (tile + 1) << 16 | depth16, in tile order; count: one device u32, the number of entries; ranges: u32[T + 1], the first entry of each of the
+ * T = ceil(w/16) ceil(h/16) tiles, 0xFFFFFFFF for an empty one, ranges[T] = count; max_batches: the compat cap on a tile's list in batches of
+ * 256 entries, 0 = none.  nf_stamp == NULL sends every tile through the kernel's EXACT body (the reference's own forms of min, clamp and
+ * exp); with nf_stamp (u32[T]) a tile takes it where nf_stamp[tile] == *nf_frame and the fast body elsewhere, so stamps that match nowhere
+ * send every tile through the fast body.  Writes the three caller-owned images, W*H elements each: rgba8, final T (f32), n_contrib (u32).
+ * No long-list work is passed: long tile lists need the forward pass's own structures and are tested through it (tests/test_gpu_nan.py).
+ * WDGS_E_INVALID for a null pointer, an empty viewport, or more tiles than the 16-bit tile field of the key holds. */
+typedef struct wdgs_debug_raster_frame {
+    uint32_t viewport_width, viewport_height;
+    float max_splat_radius_px, point_size_px;
+    uint32_t render_mode; /* 1 = gaussian, 0 = point cloud */
+    uint32_t num_splats;
+    uint32_t max_batches;
+    const void* splats;
+    const void* sorted_keys;
+    const void* sorted_vals;
+    const void* count;
+    const void* ranges;
+    const void* nf_stamp; /* nullable */
+    const void* nf_frame; /* nullable when nf_stamp is */
+} wdgs_debug_raster_frame;
+int wdgs_debug_rasterize(wdgs_device* dev, const wdgs_debug_raster_frame* frame, void* rgba8_dev, void* final_t_dev, void* n_contrib_dev);
+
 /* ---------------------------------------------------------------- Optimizer
  * Replaces allocateOptimizerStateBuffers (renderers/optimizer.ts:27-38), `new Optimizer(device, pointCloud, params?,
  * initialState?)` (71-88), .step (295-350), hyperparameter accessors (256-278), .destroy (352). */

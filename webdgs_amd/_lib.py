@@ -90,6 +90,12 @@ class ContributionRule(C.Structure):
     _fields_ = [("min_max_weight", C.c_float), ("min_weight_sum", C.c_float), ("min_pixels", C.c_uint32), ("min_sum_q", C.c_uint64)]
 
 
+class DebugRasterFrame(C.Structure):
+    _fields_ = [("viewport_width", C.c_uint32), ("viewport_height", C.c_uint32), ("max_splat_radius_px", C.c_float), ("point_size_px", C.c_float),
+                ("render_mode", C.c_uint32), ("num_splats", C.c_uint32), ("max_batches", C.c_uint32), ("splats", C.c_void_p), ("sorted_keys", C.c_void_p),
+                ("sorted_vals", C.c_void_p), ("count", C.c_void_p), ("ranges", C.c_void_p), ("nf_stamp", C.c_void_p), ("nf_frame", C.c_void_p)]
+
+
 _P = C.c_void_p
 _U = C.c_uint32
 _I = C.c_int
@@ -133,6 +139,7 @@ SIGNATURES = {
     "wdgs_densify_prune_get_buffers": (_I, [_P, C.POINTER(DensifyPrepared)]),
     "wdgs_debug_eval_math": (_I, [_P, _U, _U, _P, _P]),
     "wdgs_debug_sort_tiles": (_I, [_P, _U, _U, _U, _P]),
+    "wdgs_debug_rasterize": (_I, [_P, C.POINTER(DebugRasterFrame), _P, _P, _P]),
     "wdgs_comm_get_unique_id": (_I, [C.POINTER(C.c_uint8)]),
     "wdgs_comm_create": (_I, [_P, C.POINTER(C.c_uint8), _I, _I, C.POINTER(_P)]),
     "wdgs_comm_destroy": (_I, [_P]),

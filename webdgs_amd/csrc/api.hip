@@ -729,14 +729,25 @@ static int forward_make_sorter(wdgs_tiled_forward* op, u32 capacity) {
     op->sorter.reset(sorter);
     return WDGS_OK;
 }
+// The settings block and the tile grid the forward kernels are handed, from the host's configuration values (0 = the reference's default) and the
+// viewport: what a forward pass builds for itself, and what wdgs_debug_rasterize builds for the frame it is given
+static RenderSettings forward_settings(float gaussian_scale, u32 sh_deg, float point_size_px, u32 render_mode, float max_splat_radius_px) {
+    return RenderSettings{gaussian_scale != 0.f ? gaussian_scale : 1.0f, (float)sh_deg, 0.f, 0.f, point_size_px != 0.f ? point_size_px : 3.0f,
+                          render_mode ? 1.0f : 0.0f, max_splat_radius_px != 0.f ? max_splat_radius_px : 128.0f};
+}
+static void settings_set_viewport(RenderSettings& st, TileInfo& ti, u32 w, u32 h) {
+    st.viewport_x = (float)w;
+    st.viewport_y = (float)h;
+    ti.num_tiles_x = ceil_div(w, 16);
+    ti.num_tiles_y = ceil_div(h, 16);
+    ti.total_tiles = ti.num_tiles_x * ti.num_tiles_y;
+}
+// the sort key keeps tile_id + 1 in 16 bits (tiled-forward.wgsl:121-136)
+static bool viewport_tiles_fit(u32 w, u32 h) { return (uint64_t)ceil_div(w, 16) * ceil_div(h, 16) + 1 <= 0xFFFFu; }
 static void forward_set_viewport(wdgs_tiled_forward* op, u32 w, u32 h) {
     op->cfg.viewport_width = w;
     op->cfg.viewport_height = h;
-    op->settings.viewport_x = (float)w;
-    op->settings.viewport_y = (float)h;
-    op->tile_info.num_tiles_x = ceil_div(w, 16);
-    op->tile_info.num_tiles_y = ceil_div(h, 16);
-    op->tile_info.total_tiles = op->tile_info.num_tiles_x * op->tile_info.num_tiles_y;
+    settings_set_viewport(op->settings, op->tile_info, w, h);
 }
 // The per-tile tables that follow the viewport: the non-finite stamps and, when long lists are on, their marks.  They only grow.
 static int forward_alloc_nf_stamp(wdgs_tiled_forward* op) {
@@ -801,17 +812,14 @@ int wdgs_tiled_forward_create(wdgs_device* d, const wdgs_tiled_forward_config* c
     WDGS_REQUIRE(d && cfg && out, WDGS_E_INVALID, "wdgs_tiled_forward_create: null argument");
     WDGS_REQUIRE(cfg->viewport_width > 0 && cfg->viewport_height > 0, WDGS_E_INVALID, "viewport must be non-empty");
     WDGS_REQUIRE(cfg->sh_deg <= 3, WDGS_E_INVALID, "sh_deg %u > 3", cfg->sh_deg);
-    // the sort key keeps tile_id + 1 in 16 bits (tiled-forward.wgsl:121-136)
     const uint64_t tiles = (uint64_t)ceil_div(cfg->viewport_width, 16) * ceil_div(cfg->viewport_height, 16);
-    WDGS_REQUIRE(tiles + 1 <= 0xFFFFu, WDGS_E_CAPACITY, "%llu tiles do not fit the 16-bit tile field of the sort key", (unsigned long long)tiles);
+    WDGS_REQUIRE(viewport_tiles_fit(cfg->viewport_width, cfg->viewport_height), WDGS_E_CAPACITY, "%llu tiles do not fit the 16-bit tile field of the sort key", (unsigned long long)tiles);
     auto op = std::make_unique<wdgs_tiled_forward>();
     op->dev = d;
     op->cfg = *cfg;
     const u32 n = cfg->num_points;
     const uint64_t cap = forward_tile_entry_cap(*cfg, n);
-    op->settings = RenderSettings{cfg->gaussian_scale != 0.f ? cfg->gaussian_scale : 1.0f, (float)cfg->sh_deg, 0.f, 0.f,
-                                  cfg->point_size_px != 0.f ? cfg->point_size_px : 3.0f, cfg->render_mode ? 1.0f : 0.0f,
-                                  cfg->max_splat_radius_px != 0.f ? cfg->max_splat_radius_px : 128.0f};
+    op->settings = forward_settings(cfg->gaussian_scale, cfg->sh_deg, cfg->point_size_px, cfg->render_mode, cfg->max_splat_radius_px);
     op->tile_info.max_tile_entries = (u32)cap;
     forward_set_viewport(op.get(), cfg->viewport_width, cfg->viewport_height);
     WDGS_TRY(op->stats.alloc(FORWARD_STATS_BYTES / 4, true, d->stream));
@@ -997,7 +1005,7 @@ int wdgs_tiled_forward_is_projected(const wdgs_tiled_forward* op) { return (op &
 
 int wdgs_tiled_forward_set_viewport(wdgs_tiled_forward* op, uint32_t w, uint32_t h) {
     WDGS_REQUIRE(op && w > 0 && h > 0, WDGS_E_INVALID, "wdgs_tiled_forward_set_viewport: invalid argument");
-    WDGS_REQUIRE((uint64_t)ceil_div(w, 16) * ceil_div(h, 16) + 1 <= 0xFFFFu, WDGS_E_CAPACITY, "viewport %ux%u has too many tiles for the 16-bit tile field", w, h);
+    WDGS_REQUIRE(viewport_tiles_fit(w, h), WDGS_E_CAPACITY, "viewport %ux%u has too many tiles for the 16-bit tile field", w, h);
     WDGS_REQUIRE(!op->dev->capturing, WDGS_E_STATE, "wdgs_tiled_forward_set_viewport while recording a command buffer");
     forward_set_viewport(op, w, h);
     const int r = forward_alloc_per_tile(op);
@@ -1142,6 +1150,38 @@ int wdgs_tiled_rasterizer_encode(wdgs_tiled_rasterizer* op, uint32_t width, uint
                               (f->ranges_valid && f->long_lists.hdr && !op->compat_caps) ? &f->long_lists : nullptr));   // (the table this pass's sort built and marked)
     op->encoded = true;
     return WDGS_OK;
+}
+
+// Test hook (include/webdgs.h): launch_rasterize on a CompositedFrame made of the caller's device pointers -- the settings block and the tile grid
+// by the forward pass's own forward_settings / settings_set_viewport, the launch by the call wdgs_tiled_rasterizer_encode makes, without the
+// long-list work.  The walkers of tilewalk.h take the same struct: a hook for them would build its frame here too.
+static int debug_frame(const wdgs_debug_raster_frame* fr, const char* who, CompositedFrame* out) {
+    WDGS_REQUIRE(fr->splats && fr->sorted_keys && fr->sorted_vals && fr->count && fr->ranges, WDGS_E_INVALID, "%s: null table in the frame", who);
+    WDGS_REQUIRE(fr->viewport_width > 0 && fr->viewport_height > 0, WDGS_E_INVALID, "%s: the viewport must be non-empty, not %u x %u", who, fr->viewport_width,
+                 fr->viewport_height);
+    WDGS_REQUIRE(viewport_tiles_fit(fr->viewport_width, fr->viewport_height), WDGS_E_INVALID, "%s: viewport %ux%u has too many tiles for the 16-bit tile field", who,
+                 fr->viewport_width, fr->viewport_height);
+    WDGS_REQUIRE(!fr->nf_stamp || fr->nf_frame, WDGS_E_INVALID, "%s: nf_stamp without the frame word it is compared with", who);
+    CompositedFrame f = {};
+    f.st = forward_settings(0.f, 0u, fr->point_size_px, fr->render_mode, fr->max_splat_radius_px);
+    settings_set_viewport(f.st, f.ti, fr->viewport_width, fr->viewport_height);
+    f.splats = static_cast<const u32*>(fr->splats);
+    f.num_splats = fr->num_splats;
+    f.ranges = static_cast<const u32*>(fr->ranges);
+    f.sorted_keys = static_cast<const u32*>(fr->sorted_keys);
+    f.sorted_vals = static_cast<const u32*>(fr->sorted_vals);
+    f.count_ptr = static_cast<const u32*>(fr->count);
+    f.max_batches = fr->max_batches;
+    f.nf_stamp = static_cast<const u32*>(fr->nf_stamp);
+    f.nf_frame = static_cast<const u32*>(fr->nf_frame);
+    *out = f;
+    return WDGS_OK;
+}
+int wdgs_debug_rasterize(wdgs_device* dev, const wdgs_debug_raster_frame* frame, void* rgba8_dev, void* final_t_dev, void* n_contrib_dev) {
+    WDGS_REQUIRE(dev && frame && rgba8_dev && final_t_dev && n_contrib_dev, WDGS_E_INVALID, "wdgs_debug_rasterize: null argument");
+    CompositedFrame f;
+    WDGS_TRY(debug_frame(frame, "wdgs_debug_rasterize", &f));
+    return launch_rasterize(dev, f, static_cast<u32*>(rgba8_dev), static_cast<float*>(final_t_dev), static_cast<u32*>(n_contrib_dev), nullptr);
 }
 
 // Depth images of the frame the last encode composited (depth.hip; no counterpart in the reference, which renders colour only).  The walk is

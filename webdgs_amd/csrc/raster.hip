@@ -62,7 +62,15 @@ __device__ __attribute__((always_inline)) void rasterize_body(const RenderSettin
         u32 key_c, val_c, key_n, val_n;
         fetch_kv(0u, key_c, val_c);
         fetch_kv(1u, key_n, val_n);
-        bool valid = (key_c >> 16u) == want_key && val_c < num_splats;
+        // listed: the entry is one of this tile's; valid: it also names a Splat.  An entry that does not is skipped WITHOUT being counted, as the
+        // reference skips it (tiled-rasterizer.wgsl:150, 197-201: processed_in_tile counts the staged records only), so n_contrib is the number of
+        // valid entries up to the last contributor.  The forward pass emits none; tests/rastercases.py does.
+        bool listed = (key_c >> 16u) == want_key;
+        bool valid = listed && val_c < num_splats;
+        // All of it is kept out of the walk of a list without such entries, which pays one scalar compare per chunk: the state below changes only
+        // in a chunk that holds one (`holes`).
+        u32 skipped = 0u;                                // (uniform) listed entries that name no Splat, in the chunks before this one
+        u32 empty_from = 0u, empty_last = 0xFFFFFFFFu;   // (uniform) the latest run of chunks without a valid entry: its first and its last chunk
         uint2 w01 = make_uint2(0u, 0u), w23 = w01, w45 = w01;
         if (valid) {
             const uint2* sp = reinterpret_cast<const uint2*>(splats + (size_t)val_c * 6);
@@ -74,9 +82,13 @@ __device__ __attribute__((always_inline)) void rasterize_body(const RenderSettin
         const u32 list_len = ((next_start > start && next_start < total) ? next_start : total) - start;
         bool dead = false;   // (EXACT; uniform) no pixel of the block can still change its sums
         for (u32 chunk = 0;; chunk++) {
-            // entries of a tile are contiguous, so the valid lanes are a prefix of the chunk
-            const unsigned long long vmask = __ballot(valid);
-            if (vmask == 0ull) break;
+            // entries of a tile are contiguous, so the listed lanes are a prefix of the chunk
+            const unsigned long long vmask = __ballot(valid), lmask = __ballot(listed);
+            if (lmask == 0ull) break;
+            const bool holes = vmask != lmask;   // (uniform, rare)
+            // the record's number among the tile's valid entries, from 1
+            u32 number = chunk * 64u + lane + 1u - skipped;
+            if (__builtin_expect(holes, 0)) number = chunk * 64u - skipped + (u32)__popcll(vmask & lt_mask) + 1u;
             if (issue_priority) {
                 // (as a scalar: exec-masked s_setprio would all execute, backward_raster.hip)
                 const u32 done = chunk * 64u, left = (u32)__builtin_amdgcn_readfirstlane((int)((list_len > done) ? list_len - done : 0u));
@@ -112,10 +124,11 @@ __device__ __attribute__((always_inline)) void rasterize_body(const RenderSettin
                 // are powers of two, which commute with every rounding of the products and sums they pass through, so they are applied to
                 // the conic once per record instead of to the power once per (pixel, splat) -- same bits, one multiplication less
                 s_con[slot] = make_float4(-0.5f * wd_unpack_lo(w23.x), -wd_unpack_hi(w23.x), -0.5f * wd_unpack_lo(w23.y), wd_unpack_hi(w45.y));
-                s_col[slot] = make_float4(wd_unpack_lo(w45.x), wd_unpack_hi(w45.x), wd_unpack_lo(w45.y), __uint_as_float(chunk * 64u + lane + 1u));
+                s_col[slot] = make_float4(wd_unpack_lo(w45.x), wd_unpack_hi(w45.x), wd_unpack_lo(w45.y), __uint_as_float(number));
             }
             // issue the next chunk's gather and the (key, index) loads of the chunk after it; they land while this chunk composites
-            valid = (key_n >> 16u) == want_key && val_n < num_splats;
+            listed = (key_n >> 16u) == want_key;
+            valid = listed && val_n < num_splats;
             if (valid) {
                 const uint2* sp = reinterpret_cast<const uint2*>(splats + (size_t)val_n * 6);
                 w01 = sp[0]; w23 = sp[1]; w45 = sp[2];
@@ -195,7 +208,16 @@ __device__ __attribute__((always_inline)) void rasterize_body(const RenderSettin
             // every pixel of this wave saturated -> nothing later can change an output of this wave
             if (GAUSSIAN_MODE && !__any(in_bounds && !(A > 0.99f))) break;
             if (EXACT && GAUSSIAN_MODE) dead = !__any(in_bounds && (A <= 0.99f));   // (false for a saturated and for a NaN sum)
-            if (vmask != ~0ull) break;  // the tile's list ended inside this chunk
+            if (lmask != ~0ull) break;  // the tile's list ended inside this chunk
+            if (__builtin_expect(holes, 0)) {
+                skipped += (u32)__popcll(lmask & ~vmask);
+                // the reference ends its walk at the first batch of 256 entries without a valid one (tiled-rasterizer.wgsl:187-192): four chunks here
+                if (vmask == 0ull) {
+                    if (empty_last + 1u != chunk) empty_from = chunk;
+                    empty_last = chunk;
+                    if ((chunk & 3u) == 3u && chunk - empty_from >= 3u) break;
+                }
+            }
         }
     }
 
