@@ -501,6 +501,42 @@ static napi_value meshWelderStats(napi_env env, napi_callback_info info) {  // (
     for (uint32_t i = 0; i < 4; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
     return a;
 }
+// Simplification by vertex clustering (include/webdgs.h: wdgs_mesh_simplifier_*; no reference counterpart)
+static napi_value meshSimplifierCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_mesh_simplifier* s = nullptr;
+    WDGS_OK_OR_THROW(wdgs_mesh_simplifier_create((wdgs_device*)get_ptr(env, argv[0]), &s));
+    return make_ptr(env, s);
+}
+static napi_value meshSimplifierDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_mesh_simplifier_destroy((wdgs_mesh_simplifier*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value meshSimplifierCount(napi_env env, napi_callback_info info) {
+    // (simplifier, verticesPtr | null, numVertices, facesPtr | null, numFaces, coloursPtr | null, ox, oy, oz, cellSize) -> [vertices, faces]
+    ARGS(10);
+    const float origin[3] = {(float)get_f64(env, argv[6]), (float)get_f64(env, argv[7]), (float)get_f64(env, argv[8])};
+    uint32_t r[2] = {0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_simplifier_count((wdgs_mesh_simplifier*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_ptr(env, argv[3]),
+                                                get_u32(env, argv[4]), get_ptr(env, argv[5]), origin, (float)get_f64(env, argv[9]), &r[0], &r[1]));
+    napi_value a; napi_create_array_with_length(env, 2, &a);
+    for (uint32_t i = 0; i < 2; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
+    return a;
+}
+static napi_value meshSimplifierEmit(napi_env env, napi_callback_info info) {
+    // (simplifier, verticesPtr | null, numVertices, facesPtr | null, numFaces, coloursPtr | null, verticesOutPtr | null, coloursOutPtr | null, keysOutPtr | null,
+    //  facesOutPtr | null, faceMapPtr | null, vertexClusterPtr | null, capacityVertices, capacityFaces)
+    ARGS(14);
+    WDGS_OK_OR_THROW(wdgs_mesh_simplifier_emit((wdgs_mesh_simplifier*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_ptr(env, argv[3]),
+                                               get_u32(env, argv[4]), get_ptr(env, argv[5]), get_ptr(env, argv[6]), get_ptr(env, argv[7]), get_ptr(env, argv[8]),
+                                               get_ptr(env, argv[9]), get_ptr(env, argv[10]), get_ptr(env, argv[11]), get_u32(env, argv[12]), get_u32(env, argv[13])));
+    return js_undefined(env);
+}
+static napi_value meshSimplifierStats(napi_env env, napi_callback_info info) {  // (simplifier) -> [clusters, invalid, outside, collapsed, duplicate, vertices, faces]
+    ARGS(1);
+    uint32_t r[7] = {0, 0, 0, 0, 0, 0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_simplifier_stats((const wdgs_mesh_simplifier*)get_ptr(env, argv[0]), &r[0], &r[1], &r[2], &r[3], &r[4], &r[5], &r[6]));
+    napi_value a; napi_create_array_with_length(env, 7, &a);
+    for (uint32_t i = 0; i < 7; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
+    return a;
+}
 static napi_value pointIndexCreate(napi_env env, napi_callback_info info) {  // (device, pointsPtr, numPoints, cellSize: 0 = chosen by the first query) -> handle
     ARGS(4);
     wdgs_point_index* ix = nullptr;
@@ -1176,6 +1212,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(meshComponentsCreate); EXPORT_FN(meshComponentsDestroy); EXPORT_FN(meshComponentsLabel); EXPORT_FN(meshComponentsGet); EXPORT_FN(meshComponentsSelect);
     EXPORT_FN(meshComponentsCompact);
     EXPORT_FN(meshWelderCreate); EXPORT_FN(meshWelderDestroy); EXPORT_FN(meshWelderCount); EXPORT_FN(meshWelderEmit); EXPORT_FN(meshWelderStats);
+    EXPORT_FN(meshSimplifierCreate); EXPORT_FN(meshSimplifierDestroy); EXPORT_FN(meshSimplifierCount); EXPORT_FN(meshSimplifierEmit); EXPORT_FN(meshSimplifierStats);
     EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
     EXPORT_FN(pointDistanceStats);
     EXPORT_FN(pointIndexBounds); EXPORT_FN(pointIndexKNearest); EXPORT_FN(pointCloudPositions); EXPORT_FN(pointCloudNeighbourScales);

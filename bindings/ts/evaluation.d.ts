@@ -1,13 +1,13 @@
 // Typings of evaluation.js: the evaluation side of a Trainer (no reference counterpart).  The Trainer's methods of the same names delegate here; their
 // typings in trainer.d.ts carry the descriptions.
-import { ComponentSelection, CompactedMesh, ContributionRecords, GeometryMetrics, HipBuffer, TriangleMesh, TSDFVolume } from './webdgs_hip';
+import { ComponentSelection, CompactedMesh, ContributionRecords, GeometryMetrics, HipBuffer, SimplifiedMesh, TriangleMesh, TSDFVolume } from './webdgs_hip';
 import { CameraData } from './loaders';
 import { LoadedImage } from './images';
 import { EvaluationResult, NormalConsistencyResult, Trainer, TrainingImage, TrainingView } from './trainer';
 
 type Split = 'eval' | 'train';
 type DepthKind = 'median' | 'expected';
-type MeshOptions = { viewIds?: number[] | null; split?: Split; depthKind?: DepthKind; minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device' } & ComponentSelection;
+type MeshOptions = { viewIds?: number[] | null; split?: Split; depthKind?: DepthKind; minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null } & ComponentSelection;
 
 export class Evaluator {
   /** Uses of the trainer only: device, pointCloud, iteration, trainCameras, images, cameraBuffers, newPassSet, dcWords, longLists, drain(), growTileEntryCapacity(). */
@@ -20,7 +20,7 @@ export class Evaluator {
   evaluate(viewIds?: number[] | null, split?: Split): EvaluationResult;
   normalConsistency(viewIds?: number[] | null, split?: Split, depthKind?: DepthKind): NormalConsistencyResult;
   fuseDepth(volume: TSDFVolume, viewIds?: number[] | null, split?: Split, depthKind?: DepthKind): number[];
-  extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, options?: MeshOptions): TriangleMesh | CompactedMesh;
+  extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, options?: MeshOptions): TriangleMesh | CompactedMesh | SimplifiedMesh;
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,
                    options?: { density?: number | null; seed?: number } & MeshOptions): GeometryMetrics & { vertices: number; faces: number; samples: number; ms: number };
   contributionStats(viewIds?: number[] | null, split?: Split): ContributionRecords & { views: number[] };

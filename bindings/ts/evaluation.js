@@ -216,13 +216,18 @@ class Evaluator {
    *  returned; otherwise the raw level set, as before, and nothing more is launched.  loaders.saveMeshPLY writes the result.
    *  options.weld: 'host' (default) or 'device' (DESIGN.md section 17): the triangles are welded where the volume emitted them and, with a component rule,
    *  labelled, selected and compacted there as well; the compacted mesh is what is read, colours and keys are read at the welded mesh's size and gathered
-   *  through vertexMap.  The same bytes either way. */
+   *  through vertexMap.  The same bytes either way.
+   *  options.simplify: a cell size (DESIGN.md section 18): the mesh is simplified last -- after welding and component removal, so that floaters are not
+   *  merged into the surface first -- by hip.simplifyMesh on the grid of that cell size from the volume's lo, and its object is returned.  With weld
+   *  'device' positions and faces stay on the device from the volume to the simplified mesh; with a component rule the colours alone are gathered through
+   *  vertexMap on the host.  The same bytes either way; without it, as before, and nothing more is launched. */
   extractMesh(lo, hi, voxelSize, options) {
     const o = options || {}, weld = o.weld || 'host';
     if (weld !== 'host' && weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
     const unset = (x) => x === undefined || x === null;
     const everything = unset(o.keepLargest) && !(o.minTriangles > 0) && !(o.minFraction > 0);
     const rule = { keepLargest: o.keepLargest, minTriangles: o.minTriangles, minFraction: o.minFraction };
+    if (!unset(o.simplify)) return this.extractSimplified(lo, hi, voxelSize, o, weld, everything, rule);
     const volume = hip.TSDFVolume.fromBounds(this.device, lo, hi, voxelSize, { truncation: o.truncation, maxWeight: o.maxWeight, colour: o.colour });
     let mesh = null, welded = null;
     try {
@@ -249,6 +254,32 @@ class Evaluator {
       out.keys = BigUint64Array.from(out.vertexMap, (old) => keys[old]);
       return out;
     } finally { hip.destroyBuffers(welded); }
+  }
+  /** extractMesh with options.simplify set: volume, weld, component removal (when a rule is given), hip.simplifyMesh from the volume's origin. */
+  extractSimplified(lo, hi, voxelSize, o, weld, everything, rule) {
+    const volume = hip.TSDFVolume.fromBounds(this.device, lo, hi, voxelSize, { truncation: o.truncation, maxWeight: o.maxWeight, colour: o.colour });
+    let welded = {}, kept = {};
+    try {
+      this.fuseDepth(volume, o.viewIds, o.split, o.depthKind);
+      const origin = volume.origin;
+      if (everything) return volume.extractMesh(o.minWeight, { weld, simplify: o.simplify });
+      if (weld === 'host') return hip.simplifyMesh(this.device, hip.removeSmallComponents(this.device, volume.extractMesh(o.minWeight), rule), o.simplify, { origin });
+      const tri = volume.extractTriangleBuffers(o.minWeight);
+      try { welded = hip.weldTrianglesDevice(this.device, tri, { asBuffers: true }); } finally { hip.destroyBuffers(tri); }
+      kept = hip.removeSmallComponents(this.device, { vertices: welded.vertices, faces: welded.faces }, Object.assign({ asBuffers: true }, rule));
+      if (welded.colours) {
+        const V = welded.numVertices, nv = kept.numVertices, bytes = (b, n) => (n ? this.device.readBuffer(b, n) : new ArrayBuffer(0));
+        const all = new Uint32Array(bytes(welded.colours, 4 * V)), map = new Uint32Array(bytes(kept.vertexMap, 4 * nv));
+        const gathered = Uint32Array.from(map, (old) => all[old]);
+        kept.colours = this.device.createBuffer({ size: Math.max(gathered.byteLength, 8), label: 'compacted colours' });
+        if (gathered.byteLength) this.device.queue.writeBuffer(kept.colours, 0, gathered);
+      }
+      return hip.simplifyMesh(this.device, kept, o.simplify, { origin });
+    } finally {
+      volume.destroy();
+      hip.destroyBuffers(welded);
+      hip.destroyBuffers(kept);
+    }
   }
 
   // ---------------------------------------------------------------- render contribution (DESIGN.md section 11)

@@ -72,15 +72,17 @@ export class Trainer {
   fuseDepth(volume: import('./webdgs_hip').TSDFVolume, viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): number[];
   /** TSDFVolume.fromBounds -> fuseDepth -> extractMesh -> destroy: the current model as a triangle mesh of the box [lo, hi]; with keepLargest, minTriangles or
    *  minFraction set, without the components removeSmallComponents drops.  weld: 'host' (default) or 'device' -- welded, and with a component rule cleaned,
-   *  on the device; the same bytes.  No reference counterpart. */
+   *  on the device; the same bytes.  simplify: a cell size -- the mesh is simplified last, by vertex clustering on that grid from lo (simplifyMesh), and
+   *  its object is returned.  No reference counterpart. */
   extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number,
               options?: { viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected'; minWeight?: number; truncation?: number; maxWeight?: number;
-                          colour?: boolean; weld?: 'host' | 'device' } & import('./webdgs_hip').ComponentSelection): import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh;
+                          colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null } & import('./webdgs_hip').ComponentSelection):
+    import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh | import('./webdgs_hip').SimplifiedMesh;
   /** extractMesh -> sampleMesh -> geometryMetrics against `reference` (points [M*3], or the path of a PLY): the mesh's accuracy, completeness, Chamfer
    *  distance, precision, recall and F-score, with the mesh's vertex, face and sample counts and ms.  Training untouched.  No reference counterpart. */
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,
                    options?: { density?: number | null; seed?: number; viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected';
-                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device' } &
+                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null } &
                      import('./webdgs_hip').ComponentSelection):
     import('./webdgs_hip').GeometryMetrics & { vertices: number; faces: number; samples: number; ms: number };
   /** Per-Gaussian render contribution accumulated over the views (default: all training views); no reference counterpart. */

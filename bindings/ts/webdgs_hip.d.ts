@@ -250,7 +250,9 @@ export class TSDFVolume {
   /** extractTriangles without the read-back: what weldTrianglesDevice takes; the caller destroys the buffers (destroyBuffers). */
   extractTriangleBuffers(minWeight?: number | null): TSDFTriangleBuffers;
   /** weld: 'host' (default: weldTriangles) or 'device' (weldTrianglesDevice: the same bytes, slot-sized arrays never cross the bus). */
-  extractMesh(minWeight?: number | null, options?: { weld?: 'host' | 'device' }): TriangleMesh;
+  extractMesh(minWeight?: number | null, options?: { weld?: 'host' | 'device'; simplify?: null }): TriangleMesh;
+  /** simplify: a cell size -- the welded mesh goes through simplifyMesh on that grid from the volume's origin (with weld 'device', on the device). */
+  extractMesh(minWeight: number | null | undefined, options: { weld?: 'host' | 'device'; simplify: number }): SimplifiedMesh;
   destroy(): void;
 }
 /** extractTriangles' output as an indexed mesh: vertices are the distinct edge keys in ascending order.  No reference counterpart. */
@@ -275,6 +277,34 @@ export function weldTrianglesDevice(device: HipDevice, tri: TSDFTriangles | TSDF
 export function weldTrianglesDevice(device: HipDevice, tri: TSDFTriangles | TSDFTriangleBuffers, options: { asBuffers: true }): WeldedMeshBuffers;
 /** Destroys every HipBuffer among the values of `buffers`. */
 export function destroyBuffers(buffers: object): void;
+/** The last count of a MeshSimplifier: the occupied cells, the dropped faces by class, V' and F'. */
+export interface SimplifyStats { clusters: number; invalid: number; outside: number; collapsed: number; duplicate: number; vertices: number; faces: number }
+/** A simplified mesh: keys are the vertices' cell keys, faceMap the old face of each new one, vertexCluster the new vertex of each old one (0xFFFFFFFF: none). */
+export interface SimplifiedMesh extends TriangleMesh { faceMap: Uint32Array; vertexCluster: Uint32Array; stats: SimplifyStats }
+/** The same on the device, each buffer of exactly its size: f32[V'][3], u32[F'][3], rgba8[V'], u64[V'], u32[F'], u32[V]. */
+export interface SimplifiedMeshBuffers { vertices: HipBuffer; faces: HipBuffer; colours: HipBuffer | null; keys: HipBuffer; faceMap: HipBuffer; vertexCluster: HipBuffer;
+                                         numVertices: number; numFaces: number; stats: SimplifyStats }
+/** A mesh on the device: f32[V][3], u32[F][3], rgba8[V]; without the counts, whole buffers. */
+export interface MeshBuffers { vertices: HipBuffer; faces: HipBuffer; colours?: HipBuffer | null; numVertices?: number; numFaces?: number }
+/** Simplifies an indexed mesh on the device by vertex clustering (wdgs_mesh_simplifier): cell keys, the weld's stable sort, integer means per cluster, the
+ *  face filter; count, then emit with the same mesh.  No reference counterpart. */
+export class MeshSimplifier {
+  constructor(device: HipDevice);
+  readonly numVertices: number; readonly numFaces: number;
+  count(vertices: HipBuffer | null, numVertices: number, faces: HipBuffer | null, numFaces: number, colours: HipBuffer | null, origin: ArrayLike<number>,
+        cellSize: number): { vertices: number; faces: number };
+  emit(vertices: HipBuffer | null, numVertices: number, faces: HipBuffer | null, numFaces: number, colours: HipBuffer | null, verticesOut: HipBuffer | null,
+       facesOut: HipBuffer | null, coloursOut?: HipBuffer | null, keysOut?: HipBuffer | null, faceMap?: HipBuffer | null, vertexCluster?: HipBuffer | null,
+       capacityVertices?: number | null, capacityFaces?: number | null): void;
+  stats(): SimplifyStats;
+  destroy(): void;
+}
+/** `mesh` simplified by vertex clustering on a grid of cellSize from options.origin (default, typed-array input only: the minimum of the finite vertices);
+ *  a function of its arguments alone, bit for bit.  No reference counterpart. */
+export function simplifyMesh(device: HipDevice, mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null } | MeshBuffers, cellSize: number,
+                             options?: { origin?: ArrayLike<number> | null; asBuffers?: false }): SimplifiedMesh;
+export function simplifyMesh(device: HipDevice, mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null } | MeshBuffers, cellSize: number,
+                             options: { origin?: ArrayLike<number> | null; asBuffers: true }): SimplifiedMeshBuffers;
 /** The index of "no point found" (PointIndex.nearest).  No reference counterpart. */
 export const NO_INDEX: 0xFFFFFFFF;
 export interface MeshSamples { points: Float32Array; face: Uint32Array; count: number }

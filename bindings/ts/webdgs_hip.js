@@ -567,13 +567,24 @@ class TSDFVolume {
     return out;
   }
   /** The welded mesh.  options.weld: 'host' (default: weldTriangles of extractTriangles) or 'device' (the triangles stay on the device and
-   *  weldTrianglesDevice welds them there: the same bytes, and only the V- and F-sized arrays of the result cross the bus). */
+   *  weldTrianglesDevice welds them there: the same bytes, and only the V- and F-sized arrays of the result cross the bus).  options.simplify: a cell
+   *  size (DESIGN.md section 18): the welded mesh goes through simplifyMesh on the grid of that cell size from the volume's origin and its object is
+   *  returned; with weld 'device' the welded mesh stays on the device until it is simplified.  Without it nothing more is launched. */
   extractMesh(minWeight, options) {
     const weld = (options && options.weld) || 'host';
-    if (weld === 'host') return weldTriangles(this.extractTriangles(minWeight));
-    if (weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
+    const simplify = options && options.simplify !== undefined && options.simplify !== null ? options.simplify : null;
+    if (weld !== 'host' && weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
+    if (weld === 'host') {
+      const mesh = weldTriangles(this.extractTriangles(minWeight));
+      return simplify === null ? mesh : simplifyMesh(this.device, mesh, simplify, { origin: this.origin });
+    }
     const tri = this.extractTriangleBuffers(minWeight);
-    try { return weldTrianglesDevice(this.device, tri); } finally { destroyBuffers(tri); }
+    let welded = {};
+    try {
+      if (simplify === null) return weldTrianglesDevice(this.device, tri);
+      welded = weldTrianglesDevice(this.device, tri, { asBuffers: true });
+      return simplifyMesh(this.device, welded, simplify, { origin: this.origin });
+    } finally { destroyBuffers(tri); destroyBuffers(welded); }
   }
   destroy() {
     if (this.destroyed) return;
@@ -681,6 +692,113 @@ function weldTrianglesDevice(device, tri, options) {
     return { vertices: new Float32Array(bytes(out.vertices, 12 * V)), faces: new Uint32Array(bytes(out.faces, 4 * S)), colours, keys: new BigUint64Array(bytes(out.keys, 8 * V)) };
   } finally {
     welder.destroy();
+    destroyBuffers(out);
+    if (own) destroyBuffers(src);
+  }
+}
+
+// ---------------------------------------------------------------- simplification by vertex clustering (include/webdgs.h, DESIGN.md section 18; no reference counterpart)
+/** Simplifies an indexed mesh on the device by vertex clustering (wdgs_mesh_simplifier): count keys every vertex by its cell of the grid (origin, cellSize),
+ *  numbers the clusters, reduces each to one representative, drops the faces that are invalid, outside, collapsed or duplicates and returns
+ *  { vertices: V', faces: F' } (one wait); emit writes the simplified mesh.  simplifyMesh is the one-call form. */
+class MeshSimplifier {
+  constructor(device) { this.device = device; this.destroyed = false; this.numVertices = 0; this.numFaces = 0; this.handle = addon.meshSimplifierCreate(device.handle); }
+  /** { vertices, faces }: V' and F' for vertices f32[numVertices][3], faces u32[numFaces][3] and (nullable) colours rgba8[numVertices]; origin: three numbers. */
+  count(vertices, numVertices, faces, numFaces, colours, origin, cellSize) {
+    if (numVertices < 2 ** 31 && numFaces < 2 ** 31 && ((vertices && vertices.size < 12 * numVertices) || (faces && faces.size < 12 * numFaces) ||
+      (colours && colours.size < 4 * numVertices))) throw new Error('MeshSimplifier.count: buffers too small for the mesh');
+    const ptr = (b) => (b ? b.ptr : null);
+    const r = addon.meshSimplifierCount(this.handle, ptr(vertices), numVertices, ptr(faces), numFaces, ptr(colours), Math.fround(origin[0]), Math.fround(origin[1]),
+      Math.fround(origin[2]), Math.fround(cellSize));
+    this.numVertices = r[0]; this.numFaces = r[1];
+    return { vertices: r[0], faces: r[1] };
+  }
+  /** Writes verticesOut f32[V'][3], facesOut u32[F'][3], coloursOut rgba8[V'] (with colours), keysOut u64[V'], faceMap u32[F'] and vertexCluster
+   *  u32[numVertices] (the last three nullable) for the count before it (WDGS_E_STATE otherwise; WDGS_E_CAPACITY, with nothing written, when there is room
+   *  for fewer than V' vertices or F' faces).  Stream-ordered: it waits for nothing and records. */
+  emit(vertices, numVertices, faces, numFaces, colours, verticesOut, facesOut, coloursOut, keysOut, faceMap, vertexCluster, capacityVertices, capacityFaces) {
+    const room = (pairs) => Math.min(0xFFFFFFFF, ...pairs.filter(([b]) => b).map(([b, s]) => Math.floor(b.size / s)));
+    const vouts = [[verticesOut, 12], [coloursOut, 4], [keysOut, 8]], fouts = [[facesOut, 12], [faceMap, 4]];
+    const cv = capacityVertices === undefined || capacityVertices === null ? room(vouts) : capacityVertices;
+    const cf = capacityFaces === undefined || capacityFaces === null ? room(fouts) : capacityFaces;
+    for (const [b, s] of vouts) if (b && cv * s > b.size) throw new Error('MeshSimplifier.emit: the capacity exceeds the buffers');
+    for (const [b, s] of fouts) if (b && cf * s > b.size) throw new Error('MeshSimplifier.emit: the capacity exceeds the buffers');
+    if (vertexCluster && vertexCluster.size < 4 * numVertices) throw new Error('MeshSimplifier.emit: vertexCluster is too small for the vertices');
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshSimplifierEmit(this.handle, ptr(vertices), numVertices, ptr(faces), numFaces, ptr(colours), ptr(verticesOut), ptr(coloursOut), ptr(keysOut), ptr(facesOut),
+      ptr(faceMap), ptr(vertexCluster), cv, cf);
+  }
+  /** The last count: { clusters, invalid, outside, collapsed, duplicate, vertices, faces } -- the occupied cells, the dropped faces by class, V' and F'. */
+  stats() {
+    const r = addon.meshSimplifierStats(this.handle);
+    return { clusters: r[0], invalid: r[1], outside: r[2], collapsed: r[3], duplicate: r[4], vertices: r[5], faces: r[6] };
+  }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.meshSimplifierDestroy(this.handle); this.handle = null; }
+}
+/** `mesh` simplified by vertex clustering on a grid of cellSize from options.origin: the vertices of one cell become one vertex at the integer mean of their
+ *  sub-cell offsets (colours alike), faces that collapse or repeat a lower face's cluster triple are dropped, unreferenced clusters are left out.  `mesh` is
+ *  what extractMesh / loadMeshPLY return (uploaded; colours Uint8Array[V*3] get an alpha of 255, [V*4] go as they are) or { vertices, faces, colours | null }
+ *  as HipBuffers (f32[V][3], u32[F][3], rgba8[V]) with numVertices / numFaces or whole buffers, as weldTrianglesDevice hands out with asBuffers (left as it
+ *  is).  options.origin: three numbers; without one, the per-axis minimum of the finite vertices (typed-array input only; a device mesh needs one).  Returns
+ *  { vertices, faces, colours | null, keys, faceMap, vertexCluster, stats }; a function of its arguments alone, bit for bit (include/webdgs.h states it).
+ *  options.asBuffers: the six stay on the device as HipBuffers of exactly their sizes (colours rgba8[V']), with numVertices and numFaces. */
+function simplifyMesh(device, mesh, cellSize, options) {
+  const o = options || {}, own = !(mesh.vertices instanceof HipBuffer);
+  let src, V, F, origin = o.origin;
+  if (own) {
+    if (mesh.vertices.length % 3 !== 0 || mesh.faces.length % 3 !== 0) throw new Error('simplifyMesh: vertices and faces are three values per row');
+    V = mesh.vertices.length / 3; F = mesh.faces.length / 3;
+    let rgba = null;
+    if (mesh.colours) {
+      if (mesh.colours.length === 4 * V) rgba = mesh.colours;
+      else if (mesh.colours.length === 3 * V) {
+        rgba = new Uint8Array(4 * V).fill(255);
+        for (let v = 0; v < V; v++) for (let a = 0; a < 3; a++) rgba[4 * v + a] = mesh.colours[3 * v + a];
+      } else throw new Error(`simplifyMesh: ${mesh.colours.length} colour bytes for ${V} vertices`);
+    }
+    if (origin === undefined || origin === null) {
+      origin = [Infinity, Infinity, Infinity];
+      for (let v = 0; v < V; v++) {
+        const p = mesh.vertices.subarray(3 * v, 3 * v + 3);
+        if (Number.isFinite(p[0]) && Number.isFinite(p[1]) && Number.isFinite(p[2])) for (let a = 0; a < 3; a++) origin[a] = Math.min(origin[a], p[a]);
+      }
+      if (!Number.isFinite(origin[0])) origin = [0, 0, 0];
+    }
+    const upload = (a) => { const b = device.createBuffer({ size: Math.max(a.byteLength, 8) }); if (a.byteLength) device.queue.writeBuffer(b, 0, a); return b; };
+    src = { vertices: upload(mesh.vertices instanceof Float32Array ? mesh.vertices : Float32Array.from(mesh.vertices)),
+      faces: upload(mesh.faces instanceof Uint32Array ? mesh.faces : Uint32Array.from(mesh.faces)), colours: rgba ? upload(rgba) : null };
+  } else {
+    if (origin === undefined || origin === null) throw new Error('simplifyMesh: a mesh on the device needs an explicit origin');
+    V = mesh.numVertices === undefined ? Math.floor(mesh.vertices.size / 12) : mesh.numVertices;
+    F = mesh.numFaces === undefined ? Math.floor(mesh.faces.size / 12) : mesh.numFaces;
+    src = { vertices: mesh.vertices, faces: mesh.faces, colours: mesh.colours || null };
+  }
+  const simplifier = new MeshSimplifier(device);
+  let out = {};
+  try {
+    const n = simplifier.count(src.vertices, V, src.faces, F, src.colours, origin, cellSize), nv = n.vertices, nf = n.faces;
+    out = { vertices: exactBuffer(device, 12 * nv), faces: exactBuffer(device, 12 * nf), colours: src.colours ? exactBuffer(device, 4 * nv) : null,
+      keys: exactBuffer(device, 8 * nv), faceMap: exactBuffer(device, 4 * nf), vertexCluster: exactBuffer(device, 4 * V) };
+    simplifier.emit(src.vertices, V, src.faces, F, src.colours, out.vertices, out.faces, out.colours, out.keys, out.faceMap, out.vertexCluster, nv, nf);
+    const stats = simplifier.stats();
+    if (o.asBuffers) {
+      device.synchronize();   // (an uploaded mesh is released below)
+      const result = Object.assign({}, out, { numVertices: nv, numFaces: nf, stats });
+      out = {};
+      return result;
+    }
+    const bytes = (b, k) => (k ? device.readBuffer(b, k) : new ArrayBuffer(0));
+    let colours = null;
+    if (out.colours) {
+      const rgba = new Uint8Array(bytes(out.colours, 4 * nv));
+      colours = new Uint8Array(3 * nv);
+      for (let v = 0; v < nv; v++) for (let a = 0; a < 3; a++) colours[3 * v + a] = rgba[4 * v + a];
+    }
+    return { vertices: new Float32Array(bytes(out.vertices, 12 * nv)), faces: new Uint32Array(bytes(out.faces, 12 * nf)), colours,
+      keys: new BigUint64Array(bytes(out.keys, 8 * nv)), faceMap: new Uint32Array(bytes(out.faceMap, 4 * nf)),
+      vertexCluster: new Uint32Array(bytes(out.vertexCluster, 4 * V)), stats };
+  } finally {
+    simplifier.destroy();
     destroyBuffers(out);
     if (own) destroyBuffers(src);
   }
@@ -818,7 +936,8 @@ function selectComponents(triangles, options) {
 /** `mesh` without the components selectComponents does not keep: { vertices, faces, vertexMap, faceMap, components } and colours / keys gathered through
  *  vertexMap when the input has them.  Kept faces stay in their order, kept vertices in ascending original index, faces are rewritten to the new indices;
  *  components holds the kept components' triangle counts.  Keeping everything still drops invalid faces and unreferenced vertices; a second call
- *  reproduces the first.  options: { keepLargest, minTriangles, minFraction }. */
+ *  reproduces the first.  options: { keepLargest, minTriangles, minFraction, asBuffers }.  asBuffers: vertices, faces, vertexMap and faceMap stay on the
+ *  device as HipBuffers (of at least one element's size) with numVertices and numFaces; colours and keys are not gathered; the caller destroys them. */
 function removeSmallComponents(device, mesh, options) {
   const v = asDevice(device, mesh.vertices, Float32Array, 3, 'removeSmallComponents: vertices');
   const f = asDevice(device, mesh.faces, Uint32Array, 3, 'removeSmallComponents: faces');
@@ -831,6 +950,13 @@ function removeSmallComponents(device, mesh, options) {
     const kept = comp.select(keep);
     for (const n of [12 * kept.vertices, 12 * kept.faces, 4 * kept.vertices, 4 * kept.faces]) outs.push(device.createBuffer({ size: Math.max(n, 4), label: 'compacted mesh' }));
     comp.compact(v.buf, outs[0], outs[1], outs[2], outs[3], kept.vertices, kept.faces);
+    if (options && options.asBuffers) {
+      device.synchronize();   // (an uploaded mesh is released below)
+      const result = { vertices: outs[0], faces: outs[1], vertexMap: outs[2], faceMap: outs[3], numVertices: kept.vertices, numFaces: kept.faces,
+        components: sizes.filter((_, c) => keep[c]) };
+      outs.length = 0;
+      return result;
+    }
     const bytes = (b, n) => (n ? device.readBuffer(b, n) : new ArrayBuffer(0));
     out = { vertices: new Float32Array(bytes(outs[0], 12 * kept.vertices)), faces: new Uint32Array(bytes(outs[1], 12 * kept.faces)),
       vertexMap: new Uint32Array(bytes(outs[2], 4 * kept.vertices)), faceMap: new Uint32Array(bytes(outs[3], 4 * kept.faces)),
@@ -1074,7 +1200,7 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, MeshWelder, weldTrianglesDevice, destroyBuffers, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, MeshWelder, weldTrianglesDevice, destroyBuffers, MeshSimplifier, simplifyMesh, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
   geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, grownTileEntries, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

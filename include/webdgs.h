@@ -811,6 +811,47 @@ int wdgs_mesh_welder_emit(wdgs_mesh_welder* welder, const void* keys_u64_dev, ui
  * scan's three.  No device work. */
 int wdgs_mesh_welder_stats(const wdgs_mesh_welder* welder, uint32_t* passes_run, uint32_t* passes_skipped, uint32_t* num_vertices, uint32_t* num_slots);
 
+/* ---------------------------------------------------------------- Mesh simplification by vertex clustering
+ *
+ * Input: an indexed mesh on the device, vertices f32[V][3], faces u32[F][3], optional colours rgba8[V], 0 <= V, F < 2^31 (WDGS_E_INVALID otherwise).  Parameters:
+ * origin f32[3], finite, and cell_size, an f32 that is finite and > 0 (anything else: WDGS_E_INVALID); inv = 1.0f / cell_size is formed once on the host in f32
+ * and no kernel divides floats.
+ * CELLS.  Per axis t = (p - origin) * inv and c = floorf(t), each operation rounded once.  A vertex is INSIDE when all three t are finite and all three c satisfy
+ * 0 <= c < 2^21; its key is cz 2^42 | cy 2^21 | cx.  An OUTSIDE vertex has the key 2^64 - 1 and belongs to no cluster.  The CLUSTERS are the distinct inside
+ * keys, numbered 0 .. C - 1 in ascending key order.
+ * REPRESENTATIVE, integers only.  Per axis and vertex q = u32((t - c) * 65536.0f) (the subtraction is exact, the conversion truncates); Q the sum of q over the
+ * cluster's n vertices as a u64; Qm = (2 Q + n) / (2 n) in unsigned integer division; the position is origin + (f32(c) + (f32(Qm) + 0.5f) * 2^-16) * cell_size,
+ * each operation rounded once in that order.  Each of the four colour bytes alike: (2 sum + n) / (2 n).  No float is ever summed, so nothing depends on the order
+ * in which threads ran.  Positions are thereby re-quantised to cell_size 2^-16: the result is NOT the identity however small the cell.
+ * FACES.  A face is dropped, and counted in exactly one class, in this order of precedence: INVALID, an index >= V (never read as an address); OUTSIDE, it names
+ * an outside vertex; COLLAPSED, two of its corners fall in one cluster; DUPLICATE, a face of lower index has the same three clusters in the same cyclic order
+ * (rotate each face so that its smallest cluster comes first and compare the triples: (a, b, c) and (a, c, b) are different faces and both stay).  Kept faces stay
+ * in input order with their corners in input order, rewritten to the new vertex numbering.  A cluster is emitted as a vertex exactly when a kept face names it;
+ * emitted vertices are in ascending key order.
+ * OUTPUTS.  V', F'; vertices_out f32[V'][3]; colours_out rgba8[V'] (with colours); keys_out u64[V'], the cell keys; faces_out u32[F'][3]; face_map u32[F'], the
+ * old face of each new one; vertex_cluster u32[V], the new index of each old vertex or 0xFFFFFFFF when it has none; the counts C, invalid, outside, collapsed,
+ * duplicate.  Each is a function of the input alone, bit for bit.  No reference counterpart. */
+typedef struct wdgs_mesh_simplifier wdgs_mesh_simplifier;
+int wdgs_mesh_simplifier_create(wdgs_device* dev, wdgs_mesh_simplifier** out);
+int wdgs_mesh_simplifier_destroy(wdgs_mesh_simplifier* simplifier);
+/* Everything up to the final scans, into arrays the object owns (it grows them as needed: about 130 bytes per vertex and 70 per face): cell keys, three stable
+ * sorts (the weld's: the vertices' keys, then two over the faces), the clusters' integer sums and representatives, the face classes, the flags and their scans.
+ * Waits ONCE, to read C, V', F' and the class counts in one copy (a second time before it, only when its arrays have to grow), so it cannot be recorded
+ * (WDGS_E_STATE).  colours nullable.  The mesh is read again by emit and must stay as it is until then. */
+int wdgs_mesh_simplifier_count(wdgs_mesh_simplifier* simplifier, const void* vertices_f32_dev, uint32_t num_vertices, const void* faces_u32_dev, uint32_t num_faces,
+                               const void* colours_rgba8_dev, const float* origin, float cell_size, uint32_t* vertices_out, uint32_t* faces_out);
+/* Writes the outputs of the last count; colours_out nullable together with colours; keys_out, face_map and vertex_cluster nullable.  WDGS_E_STATE unless the last
+ * count succeeded with these very vertices, faces, colours and counts; WDGS_E_CAPACITY when capacity_vertices < V' or capacity_faces < F'; nothing is written in
+ * either case.  Stream-ordered, no host wait, recordable. */
+int wdgs_mesh_simplifier_emit(wdgs_mesh_simplifier* simplifier, const void* vertices_f32_dev, uint32_t num_vertices, const void* faces_u32_dev, uint32_t num_faces,
+                              const void* colours_rgba8_dev, void* vertices_out_f32_dev, void* colours_out_rgba8_dev, void* keys_out_u64_dev, void* faces_out_u32_dev,
+                              void* face_map_u32_dev, void* vertex_cluster_u32_dev, uint32_t capacity_vertices, uint32_t capacity_faces);
+/* The last count: C, the four classes of dropped faces, V' and F'; each pointer nullable.  WDGS_E_STATE when no count precedes it.  The kernels' event times are
+ * the device's (wdgs_device_get_kernel_times): simplify_cell_keys, simplify_accumulate, simplify_finalize, simplify_face_keys, simplify_fold,
+ * simplify_face_keys2, simplify_mark, simplify_emit_vertices, simplify_emit_faces, and the weld's and the scan's.  No device work. */
+int wdgs_mesh_simplifier_stats(const wdgs_mesh_simplifier* simplifier, uint32_t* clusters, uint32_t* invalid_faces, uint32_t* outside_faces, uint32_t* collapsed_faces,
+                               uint32_t* duplicate_faces, uint32_t* vertices_out, uint32_t* faces_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,11 @@ SIGNATURES = {
     "wdgs_mesh_welder_count": (_I, [_P, _P, C.c_uint64, C.POINTER(_U)]),
     "wdgs_mesh_welder_emit": (_I, [_P, _P, C.c_uint64, _P, _P, _P, _P, _P, _P, _U]),
     "wdgs_mesh_welder_stats": (_I, [_P, C.POINTER(_U), C.POINTER(_U), C.POINTER(_U), C.POINTER(_U)]),
+    "wdgs_mesh_simplifier_create": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_mesh_simplifier_destroy": (_I, [_P]),
+    "wdgs_mesh_simplifier_count": (_I, [_P, _P, _U, _P, _U, _P, C.POINTER(_F), _F, C.POINTER(_U), C.POINTER(_U)]),
+    "wdgs_mesh_simplifier_emit": (_I, [_P, _P, _U, _P, _U, _P, _P, _P, _P, _P, _P, _P, _U, _U]),
+    "wdgs_mesh_simplifier_stats": (_I, [_P] + [C.POINTER(_U)] * 7),
     "wdgs_point_index_create": (_I, [_P, _P, C.c_uint64, _F, C.POINTER(_P)]),
     "wdgs_point_index_destroy": (_I, [_P]),
     "wdgs_point_index_reserve_queries": (_I, [_P, _U]),

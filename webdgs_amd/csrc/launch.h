@@ -135,6 +135,33 @@ int launch_weld_emit(wdgs_device* dev, const unsigned long long* keys, u32 S, co
                      const u32* slots_b, const u32* counters, const u32* flags, const u32* ids, const float* positions, const u32* colours, unsigned long long* keys_out,
                      float* vertices_out, u32* colours_out, u32* faces_out);
 
+// ---- meshsimplify.hip.  vertices f32[V][3], faces u32[F][3], colours rgba8[V] (nullable); origin, inv = 1 / cell_size and cell_size: the grid (webdgs.h)
+// keys u64[V], written: every vertex's cell key, 2^64 - 1 outside the grid
+int launch_simplify_cell_keys(wdgs_device* dev, const float* vertices, u32 V, const float origin[3], float inv, float cell_size, unsigned long long* keys);
+// rank u32[V]: the rank of every vertex's key among the distinct keys; acc u64[V][8], cleared and added to: per rank Qx, Qy, Qz, n and the four colour sums
+int launch_simplify_accumulate(wdgs_device* dev, const float* vertices, const u32* colours, const u32* rank, u32 V, const float origin[3], float inv, float cell_size,
+                               unsigned long long* acc);
+// cluster_keys u64[totals[0]]: the distinct keys; positions f32[V][3] and colours u32[V], written at every rank whose key is a cell's
+int launch_simplify_finalize(wdgs_device* dev, const unsigned long long* cluster_keys, const u32* totals, const unsigned long long* acc, u32 V, const float origin[3],
+                             float inv, float cell_size, bool with_colours, float* positions, u32* colours);
+// the rows of class counts (three words each) launch_simplify_face_keys leaves for F faces
+u32 simplify_partial_rows(u32 F);
+// keys u64[F], lead u32[F], iota u32[F], partial u32[3 rows], written: the first-stage key and smallest cluster of every candidate face, f, the class counts
+int launch_simplify_face_keys(wdgs_device* dev, const u32* faces, u32 F, u32 V, const unsigned long long* vertex_keys, const u32* rank, unsigned long long* keys, u32* lead,
+                              u32* iota, u32* partial);
+// totals[3..5] = the folded class counts, totals[6] = 1 when the last of the totals[0] distinct keys is the outside key
+int launch_simplify_fold(wdgs_device* dev, const u32* partial, u32 rows, const unsigned long long* cluster_keys, u32* totals);
+// keys[f] = lead[f] * 2^32 | rank1[f] for a candidate; a dropped face keeps 2^64 - 1
+int launch_simplify_face_keys2(wdgs_device* dev, const u32* lead, const u32* rank1, u32 F, unsigned long long* keys);
+// rank2 u32[F]: the rank of the second key; head_face: per rank the lowest face that carries it; face_flags u32[F] written, cluster_flags u32[V] cleared and set
+int launch_simplify_mark(wdgs_device* dev, const u32* faces, u32 F, u32 V, const u32* lead, const u32* rank2, const u32* head_face, const u32* rank, u32* face_flags,
+                         u32* cluster_flags);
+// the flags of launch_simplify_mark and their exclusive scans; colours_out (with colours), keys_out, face_map, vertex_cluster nullable
+int launch_simplify_emit(wdgs_device* dev, const u32* faces, u32 F, u32 V, const u32* totals, const u32* cluster_flags, const u32* cluster_offsets,
+                         const unsigned long long* cluster_keys, const float* positions, const u32* colours, const unsigned long long* vertex_keys, const u32* rank,
+                         const u32* face_flags, const u32* face_offsets, float* vertices_out, u32* colours_out, unsigned long long* keys_out, u32* faces_out, u32* face_map,
+                         u32* vertex_cluster);
+
 // ---- loss.hip, dssim.hip. pred, targ: rgba8[W*H]; out: rgba32f[W*H]; acc nullable (no clear), else i32[acc_rows * 12] cleared when *acc_dirty != 0
 int launch_loss_grad(wdgs_device* dev, u32 W, u32 H, const u32* pred, const u32* targ, const wdgs_training_config& cfg, float4* out, int* acc, u32 acc_rows,
                      const u32* acc_dirty);

@@ -220,7 +220,8 @@ class Evaluator:
         return ids
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
-                    keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", **volumeOptions) -> dict:
+                    keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", simplify: Optional[float] = None,
+                    **volumeOptions) -> dict:
         """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
         ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result.
 
@@ -230,9 +231,18 @@ class Evaluator:
 
         ``weld="device"``: the triangles are welded where the volume emitted them (``ops.weldTrianglesDevice``) and, with a
         component rule, labelled, selected and compacted there as well; the compacted mesh is what is read, and ``colours`` and ``keys`` are read at
-        the welded mesh's size and gathered through ``vertexMap``.  The same bytes as ``weld="host"`` either way."""
+        the welded mesh's size and gathered through ``vertexMap``.  The same bytes as ``weld="host"`` either way.
+
+        ``simplify=cellSize``: the mesh is simplified last -- after welding and component removal, so that floaters are not
+        merged into the surface first -- by ``ops.simplifyMesh`` on the grid of that cell size from the volume's ``lo``, and its dict is returned
+        (``vertices``, ``faces``, ``colours``, ``keys``, ``faceMap``, ``vertexCluster``, ``stats``).  With ``weld="device"`` positions and faces stay
+        on the device from the volume to the simplified mesh; with a component rule the colours alone are gathered through ``vertexMap`` on the
+        host, 4 bytes per vertex.  The same bytes as ``weld="host"`` either way.  ``None``: as before, and nothing more is launched."""
         if weld not in ("host", "device"):
             raise ValueError(f"extractMesh: weld must be 'host' or 'device', not {weld!r}")
+        if simplify is not None:
+            return self._extract_simplified(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld, simplify,
+                                            volumeOptions)
         everything = ops._is_default_selection(keepLargest, minTriangles, minFraction)
         volume = ops.TSDFVolume.fromBounds(self.device, lo, hi, voxelSize, **volumeOptions)
         mesh = welded = None
@@ -261,6 +271,37 @@ class Evaluator:
             return out
         finally:
             ops.destroyBuffers(welded)
+
+    def _extract_simplified(self, lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld, simplify,
+                            volumeOptions) -> dict:
+        """``extractMesh`` with ``simplify`` set: volume, weld, component removal (when a rule is given), ``ops.simplifyMesh`` from the volume's origin."""
+        everything = ops._is_default_selection(keepLargest, minTriangles, minFraction)
+        volume = ops.TSDFVolume.fromBounds(self.device, lo, hi, voxelSize, **volumeOptions)
+        welded, kept = {}, {}
+        try:
+            self.fuseDepth(volume, viewIds, split, depthKind)
+            origin = volume.origin
+            if everything:
+                return volume.extractMesh(minWeight, weld=weld, simplify=simplify)
+            if weld == "host":
+                mesh = ops.removeSmallComponents(self.device, volume.extractMesh(minWeight), keepLargest, minTriangles, minFraction)
+                return ops.simplifyMesh(self.device, mesh, simplify, origin)
+            tri = volume.extractTriangleBuffers(minWeight)
+            try:
+                welded = ops.weldTrianglesDevice(self.device, tri, asBuffers=True)
+            finally:
+                ops.destroyBuffers(tri)
+            kept = ops.removeSmallComponents(self.device, dict(vertices=welded["vertices"], faces=welded["faces"]), keepLargest, minTriangles, minFraction,
+                                             asBuffers=True)
+            V, nv = welded["numVertices"], kept["numVertices"]
+            if welded["colours"] is not None:
+                gathered = welded["colours"].read(np.uint32, count=V)[kept["vertexMap"].read(np.uint32, count=nv)]
+                kept["colours"] = self.device.bufferFrom(np.ascontiguousarray(gathered), "compacted colours")
+            return ops.simplifyMesh(self.device, kept, simplify, origin)
+        finally:
+            volume.destroy()
+            ops.destroyBuffers(welded)
+            ops.destroyBuffers(kept)
 
     # ------------------------------------------------------------------ mesh accuracy against a reference point set (DESIGN.md section 14)
     def evaluateGeometry(self, reference, lo, hi, voxelSize: float, maxDistance: float, threshold: float, density: Optional[float] = None, seed: int = 0,

@@ -989,20 +989,30 @@ class TSDFVolume:
             raise
         return out
 
-    def extractMesh(self, minWeight: float = 1.0, weld: str = "host") -> dict:
+    def extractMesh(self, minWeight: float = 1.0, weld: str = "host", simplify: Optional[float] = None) -> dict:
         """The welded mesh: ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None, keys u64[V])``.  Vertices are the triangles' distinct edge
         keys in ascending order (equal keys carry equal position bits); triangles are kept as emitted, zero-area ones included.  ``weld="host"``: the
         triangles are read back and welded by ``weldTriangles``.  ``weld="device"``: they stay on the device and ``weldTrianglesDevice`` welds them
-        there -- the same bytes, and only the V- and F-sized arrays of the result cross the bus."""
-        if weld == "host":
-            return weldTriangles(self.extractTriangles(minWeight))
-        if weld != "device":
+        there -- the same bytes, and only the V- and F-sized arrays of the result cross the bus.
+
+        ``simplify=cellSize``: the welded mesh goes through ``simplifyMesh`` on the grid of that cell size from the volume's
+        origin, and its dict is returned (``faceMap``, ``vertexCluster`` and ``stats`` added); with ``weld="device"`` the welded mesh stays on the
+        device until it is simplified.  ``None``: nothing more is launched."""
+        if weld not in ("host", "device"):
             raise ValueError(f"extractMesh: weld must be 'host' or 'device', not {weld!r}")
+        if weld == "host":
+            mesh = weldTriangles(self.extractTriangles(minWeight))
+            return mesh if simplify is None else simplifyMesh(self.device, mesh, simplify, self.origin)
         tri = self.extractTriangleBuffers(minWeight)
+        welded = {}
         try:
-            return weldTrianglesDevice(self.device, tri)
+            if simplify is None:
+                return weldTrianglesDevice(self.device, tri)
+            welded = weldTrianglesDevice(self.device, tri, asBuffers=True)
+            return simplifyMesh(self.device, welded, simplify, self.origin)
         finally:
             destroyBuffers(tri)
+            destroyBuffers(welded)
 
     def destroy(self) -> None:
         if self.destroyed:
@@ -1126,6 +1136,136 @@ def weldTrianglesDevice(device: HipDevice, tri: dict, asBuffers: bool = False) -
                     colours=colours, keys=out["keys"].read(np.uint64, count=V))
     finally:
         welder.destroy()
+        destroyBuffers(out)
+        if own:
+            destroyBuffers(src)
+
+
+# ----------------------------------------------------------------------------- simplification by vertex clustering (no reference counterpart)
+class MeshSimplifier:
+    """Simplifies an indexed mesh on the device by vertex clustering (``wdgs_mesh_simplifier``): ``count`` keys every vertex by its cell of the grid
+    ``(origin, cellSize)``, numbers the clusters, reduces each to one representative, drops the faces that are invalid, outside, collapsed or
+    duplicates and returns ``(V', F')`` (one wait); ``emit`` writes the simplified mesh.  ``simplifyMesh`` is the one-call form; include/webdgs.h
+    states the definition."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        self.numVertices = self.numFaces = 0
+        h = C.c_void_p()
+        check(device.lib.wdgs_mesh_simplifier_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def count(self, vertices: Optional[HipBuffer], numVertices: int, faces: Optional[HipBuffer], numFaces: int, colours: Optional[HipBuffer], origin,
+              cellSize: float) -> tuple:
+        """``(V', F')`` for ``vertices`` f32[numVertices][3], ``faces`` u32[numFaces][3] and (optional) ``colours`` rgba8[numVertices] (keys, sorts, sums,
+        classes, flags, scans; waits once)."""
+        nv, nf = int(numVertices), int(numFaces)
+        if not (0 <= nv < 2 ** 32 and 0 <= nf < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshSimplifier.count: bad counts {numVertices}, {numFaces}")
+        if nv < 2 ** 31 and nf < 2 ** 31 and ((vertices is not None and vertices.size < 12 * nv) or (faces is not None and faces.size < 12 * nf)
+                                              or (colours is not None and colours.size < 4 * nv)):
+            raise ValueError("MeshSimplifier.count: buffers too small for the mesh")
+        o = (C.c_float * 3)(*[float(x) for x in np.asarray(origin, np.float32).reshape(3)])
+        ptr = lambda b: b.ptr if b is not None else None
+        v, f = C.c_uint32(0), C.c_uint32(0)
+        check(self.device.lib.wdgs_mesh_simplifier_count(self.handle, ptr(vertices), nv, ptr(faces), nf, ptr(colours), o, float(cellSize), C.byref(v), C.byref(f)))
+        self.numVertices, self.numFaces = int(v.value), int(f.value)
+        return self.numVertices, self.numFaces
+
+    def emit(self, vertices: Optional[HipBuffer], numVertices: int, faces: Optional[HipBuffer], numFaces: int, colours: Optional[HipBuffer],
+             verticesOut: Optional[HipBuffer], facesOut: Optional[HipBuffer], coloursOut: Optional[HipBuffer] = None, keysOut: Optional[HipBuffer] = None,
+             faceMap: Optional[HipBuffer] = None, vertexCluster: Optional[HipBuffer] = None, capacityVertices: Optional[int] = None,
+             capacityFaces: Optional[int] = None) -> None:
+        """Writes ``verticesOut`` f32[V'][3], ``facesOut`` u32[F'][3], ``coloursOut`` rgba8[V'], ``keysOut`` u64[V'], ``faceMap`` u32[F'] and
+        ``vertexCluster`` u32[numVertices] for the count before it (``StateError`` otherwise; ``CapacityError``, with nothing written, when there is
+        room for fewer than V' vertices or F' faces).  Stream-ordered: it waits for nothing and records."""
+        vouts, fouts = ((verticesOut, 12), (coloursOut, 4), (keysOut, 8)), ((facesOut, 12), (faceMap, 4))
+        cv = min([b.size // s for b, s in vouts if b is not None] or [2 ** 32 - 1]) if capacityVertices is None else int(capacityVertices)
+        cf = min([b.size // s for b, s in fouts if b is not None] or [2 ** 32 - 1]) if capacityFaces is None else int(capacityFaces)
+        for outs, cap in ((vouts, cv), (fouts, cf)):
+            for b, s in outs:
+                if b is not None and cap * s > b.size:
+                    raise ValueError("MeshSimplifier.emit: the capacity exceeds the buffers")
+        if vertexCluster is not None and vertexCluster.size < 4 * int(numVertices):
+            raise ValueError("MeshSimplifier.emit: vertexCluster is too small for the vertices")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_simplifier_emit(self.handle, ptr(vertices), int(numVertices), ptr(faces), int(numFaces), ptr(colours), ptr(verticesOut),
+                                                        ptr(coloursOut), ptr(keysOut), ptr(facesOut), ptr(faceMap), ptr(vertexCluster), cv, cf))
+
+    def stats(self) -> dict:
+        """The last count: ``dict(clusters, invalid, outside, collapsed, duplicate, vertices, faces)`` -- the occupied cells, the dropped faces by class,
+        V' and F'.  The kernels' event times are ``HipDevice.kernelTimes``' (``simplify_*``, ``weld_*`` and the scan's)."""
+        v = [C.c_uint32(0) for _ in range(7)]
+        check(self.device.lib.wdgs_mesh_simplifier_stats(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("clusters", "invalid", "outside", "collapsed", "duplicate", "vertices", "faces"), (int(x.value) for x in v)))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_mesh_simplifier_destroy(self.handle)
+        self.handle = None
+
+
+def simplifyMesh(device: HipDevice, mesh: dict, cellSize: float, origin=None, asBuffers: bool = False) -> dict:
+    """``mesh`` simplified by vertex clustering on a grid of ``cellSize`` from ``origin``: the vertices of one cell become one vertex at the integer mean
+    of their sub-cell offsets (colours alike), faces that collapse or repeat a lower face's cluster triple are dropped, unreferenced clusters are left
+    out.  ``mesh`` is the dict ``extractMesh`` / ``loaders.loadMeshPLY`` return (uploaded; colours u8[V,3] get an alpha of 255, u8[V,4] go as they are),
+    or a dict of ``HipBuffer``s -- ``vertices`` f32[V][3], ``faces`` u32[F][3], ``colours`` rgba8[V] or ``None``, with ``numVertices`` / ``numFaces``
+    or whole buffers -- as ``weldTrianglesDevice(asBuffers=True)`` hands out (left as it is).  ``origin=None``: the per-axis minimum of the finite
+    vertices (numpy input only; a device mesh needs an origin: ``ValueError``).  Returns ``dict(vertices f32[V',3], faces u32[F',3], colours u8[V',3] |
+    None, keys u64[V'], faceMap u32[F'], vertexCluster u32[V], stats)``; a function of its arguments alone, bit for bit (include/webdgs.h states it).
+    ``asBuffers``: ``vertices``, ``faces``, ``colours`` (rgba8[V']), ``keys``, ``faceMap`` and ``vertexCluster`` stay on the device as ``HipBuffer`` of
+    exactly those sizes -- what ``meshComponents``, ``sampleMesh`` and another ``simplifyMesh`` take -- and ``numVertices`` and ``numFaces`` are added;
+    the caller destroys them (``destroyBuffers``)."""
+    own = not isinstance(mesh["vertices"], HipBuffer)
+    if own:
+        v = np.ascontiguousarray(mesh["vertices"], np.float32)
+        f = np.ascontiguousarray(mesh["faces"], np.uint32)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"simplifyMesh: expected vertices [V, 3] and faces [F, 3], got {v.shape} and {f.shape}")
+        c = None
+        if mesh.get("colours") is not None:
+            c = np.ascontiguousarray(mesh["colours"], np.uint8)
+            if c.ndim != 2 or c.shape[0] != v.shape[0] or c.shape[1] not in (3, 4):
+                raise ValueError(f"simplifyMesh: colours of shape {c.shape} for {v.shape[0]} vertices")
+            if c.shape[1] == 3:
+                c = np.ascontiguousarray(np.concatenate([c, np.full((c.shape[0], 1), 255, np.uint8)], axis=1))
+        if origin is None:
+            finite = v[np.all(np.isfinite(v), axis=1)]
+            origin = finite.min(axis=0) if finite.shape[0] else np.zeros(3, np.float32)
+        V, F = v.shape[0], f.shape[0]
+        src = dict(vertices=device.bufferFrom(v, "simplifyMesh: vertices"), faces=device.bufferFrom(f, "simplifyMesh: faces"),
+                   colours=None if c is None else device.bufferFrom(c, "simplifyMesh: colours"))
+    else:
+        if origin is None:
+            raise ValueError("simplifyMesh: a mesh on the device needs an explicit origin")
+        if not isinstance(mesh["faces"], HipBuffer) or not (mesh.get("colours") is None or isinstance(mesh["colours"], HipBuffer)):
+            raise ValueError("simplifyMesh: vertices on the device need faces and colours on the device")
+        V = int(mesh["numVertices"]) if "numVertices" in mesh else mesh["vertices"].size // 12
+        F = int(mesh["numFaces"]) if "numFaces" in mesh else mesh["faces"].size // 12
+        src = dict(vertices=mesh["vertices"], faces=mesh["faces"], colours=mesh.get("colours"))
+    simplifier = MeshSimplifier(device)
+    out = {}
+    try:
+        nv, nf = simplifier.count(src["vertices"], V, src["faces"], F, src["colours"], origin, cellSize)
+        out = dict(vertices=device.createBuffer(12 * nv, "simplified vertices"), faces=device.createBuffer(12 * nf, "simplified faces"),
+                   colours=None if src["colours"] is None else device.createBuffer(4 * nv, "simplified colours"), keys=device.createBuffer(8 * nv, "simplified keys"),
+                   faceMap=device.createBuffer(4 * nf, "simplified face map"), vertexCluster=device.createBuffer(4 * V, "simplified vertex clusters"))
+        simplifier.emit(src["vertices"], V, src["faces"], F, src["colours"], out["vertices"], out["faces"], out["colours"], out["keys"], out["faceMap"],
+                        out["vertexCluster"], nv, nf)
+        stats = simplifier.stats()
+        if asBuffers:
+            device.synchronize()   # (an uploaded mesh is released below)
+            result, out = dict(out, numVertices=nv, numFaces=nf, stats=stats), {}
+            return result
+        colours = None if out["colours"] is None else np.ascontiguousarray(out["colours"].read(np.uint8, count=4 * nv).reshape(nv, 4)[:, :3])
+        return dict(vertices=out["vertices"].read(np.float32, count=3 * nv).reshape(nv, 3), faces=out["faces"].read(np.uint32, count=3 * nf).reshape(nf, 3),
+                    colours=colours, keys=out["keys"].read(np.uint64, count=nv), faceMap=out["faceMap"].read(np.uint32, count=nf),
+                    vertexCluster=out["vertexCluster"].read(np.uint32, count=V), stats=stats)
+    finally:
+        simplifier.destroy()
         destroyBuffers(out)
         if own:
             destroyBuffers(src)
@@ -1311,12 +1451,15 @@ def selectComponents(triangles, keepLargest: Optional[int] = None, minTriangles:
     return keep
 
 
-def removeSmallComponents(device: HipDevice, mesh: dict, keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0) -> dict:
+def removeSmallComponents(device: HipDevice, mesh: dict, keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0,
+                          asBuffers: bool = False) -> dict:
     """``mesh`` without the components ``selectComponents`` does not keep: ``dict(vertices f32[V',3], faces u32[F',3], vertexMap u32[V'], faceMap u32[F'],
     components u32[kept])`` and ``colours`` / ``keys`` gathered through ``vertexMap`` when the input has them.  Kept faces stay in their order, kept
     vertices in ascending original index (a vertex is kept exactly when its component is), faces are rewritten to the new indices; ``components`` holds
     the kept components' triangle counts in component order.  Keeping everything still drops invalid faces and unreferenced vertices; a second call
-    reproduces the first.  Labelled, selected and compacted on the device (``MeshComponents``); the selection itself is the host's."""
+    reproduces the first.  Labelled, selected and compacted on the device (``MeshComponents``); the selection itself is the host's.
+    ``asBuffers``: ``vertices``, ``faces``, ``vertexMap`` and ``faceMap`` stay on the device as ``HipBuffer`` (of at least one element's size),
+    ``numVertices`` and ``numFaces`` are added, ``colours`` and ``keys`` are not gathered; the caller destroys them (``destroyBuffers``)."""
     vbuf, nv, own_v = _as_device(device, mesh["vertices"], np.float32, 3, "removeSmallComponents: vertices")
     fbuf, nf, own_f = _as_device(device, mesh["faces"], np.uint32, 3, "removeSmallComponents: faces")
     comp = MeshComponents(device)
@@ -1328,6 +1471,10 @@ def removeSmallComponents(device: HipDevice, mesh: dict, keepLargest: Optional[i
         kv, kf = comp.select(keep)
         outs = [device.createBuffer(s * max(n, 1), "compacted mesh") for s, n in ((12, kv), (12, kf), (4, kv), (4, kf))]
         comp.compact(vbuf, outs[0], outs[1], outs[2], outs[3], kv, kf)
+        if asBuffers:
+            device.synchronize()   # (an uploaded mesh is released below)
+            result, outs = dict(vertices=outs[0], faces=outs[1], vertexMap=outs[2], faceMap=outs[3], numVertices=kv, numFaces=kf, components=sizes[keep]), []
+            return result
         out = dict(vertices=outs[0].read(np.float32, count=3 * kv).reshape(kv, 3), faces=outs[1].read(np.uint32, count=3 * kf).reshape(kf, 3),
                    vertexMap=outs[2].read(np.uint32, count=kv), faceMap=outs[3].read(np.uint32, count=kf), components=sizes[keep])
     finally:
