@@ -206,6 +206,38 @@ def test_two_runs_agree_and_one_simplifier_takes_meshes_of_any_size(hip_device):
         simp.destroy()
 
 
+def test_one_simplification_is_three_sorts_launch_for_launch(hip_device):
+    """The launch sequence of one count + emit, pinned: three stable u64 sorts (csrc/keysort.hip) -- the six sort labels three times, the two per-pass
+    ones twenty-four -- every simplify_* kernel once, and the library scan's three kernels 29 times each: three times eight digit tables and head
+    flags, then the cluster and face flags.  The scan_* literals are what the library gave on this mesh before the sort became one object; the others
+    follow from the code."""
+    dev = hip_device
+    m = S.case("random")
+    assert (m["vertices"].shape[0], m["faces"].shape[0]) == (20481, 40000)
+    src = _upload(dev, m)
+    simp = ops.MeshSimplifier(dev)
+    try:
+        outs = _outputs(dev, src["V"], src["F"], src["V"])
+        dev.synchronize()
+        dev.setProfiling(True)
+        dev.kernelTimes(reset=True)
+        _count(simp, src)
+        _emit(simp, src, outs)
+        dev.synchronize()
+        dev.setProfiling(False)
+        times = dev.kernelTimes(reset=True)
+    finally:
+        dev.setProfiling(False)
+        simp.destroy()
+    launches = {k: v[0] for k, v in times.items()}
+    print("launches:", sorted(launches.items()))
+    assert {k: n for k, n in launches.items() if k.startswith("weld_")} == dict(weld_key_bits=3, weld_plan=3, weld_histogram=24, weld_scatter=24, weld_heads=3,
+                                                                                  weld_emit=3), launches
+    simplify = ("cell_keys", "accumulate", "finalize", "face_keys", "fold", "face_keys2", "mark", "emit_vertices", "emit_faces")
+    assert {k: n for k, n in launches.items() if k.startswith("simplify_")} == {f"simplify_{k}": 1 for k in simplify}, launches
+    assert {k: n for k, n in launches.items() if k.startswith("scan_")} == dict(scan_reduce=29, scan_block_sums=29, scan_downsweep=29), launches
+
+
 # ---------------------------------------------------------------- 3. two spheres in a TSDF volume
 def _rgba(mesh):
     return None if mesh["colours"] is None else np.concatenate([mesh["colours"], np.full((mesh["colours"].shape[0], 1), 255, np.uint8)], axis=1)

@@ -1,4 +1,4 @@
-"""GPU: welding a triangle soup on the device (csrc/meshweld.hip).  Every output byte equals ``ops.weldTriangles`` on the same soup: the
+"""GPU: welding a triangle soup on the device (csrc/meshweld.hip over the sort of csrc/keysort.hip).  Every output byte equals ``ops.weldTriangles`` on the same soup: the
 crafted soups of tests/meshweld_ref.py (sizes and edge values, pass skipping, load and duplication, the lowest-slot rule, a digit table of several scan blocks),
 capacity and state errors, recording, repeats and reuse, the two-sphere TSDF volume, and the Trainer surface."""
 import numpy as np
@@ -173,6 +173,41 @@ def test_two_runs_agree_and_one_welder_takes_soups_of_any_size(hip_device):
             _assert_mesh(got, ops.weldTriangles(W.case(name)), f"reused welder: {name}")
     finally:
         welder.destroy()
+
+
+# The launches of one stable u64 sort; histogram and scatter launch for every one of the eight passes, and a pass the plan skips returns at once
+SORT_LAUNCHES = dict(weld_key_bits=1, weld_plan=1, weld_histogram=8, weld_scatter=8, weld_heads=1, weld_emit=1)
+
+
+def test_one_weld_is_one_sort_launch_for_launch(hip_device):
+    """The launch sequence of one count + emit, pinned: the six sort labels once per sort (the two per-pass ones eight times), and the library scan's
+    three kernels nine times each -- eight digit tables and the head flags.  The scan_* literals are what the library gave on this soup before the
+    sort moved into csrc/keysort.hip; the sort's follow from its code."""
+    dev = hip_device
+    tri = W.case("random-u64")
+    assert tri["keys"].size == 20481
+    src = _upload(dev, tri)
+    F = src["numTriangles"]
+    welder = ops.MeshWelder(dev)
+    try:
+        outs = _outputs(dev, 3 * F, F)
+        dev.synchronize()
+        dev.setProfiling(True)
+        dev.kernelTimes(reset=True)
+        welder.count(src["keys"], 3 * F)
+        _emit(welder, src, outs)
+        dev.synchronize()
+        dev.setProfiling(False)
+        times = dev.kernelTimes(reset=True)
+        stats = welder.stats()
+    finally:
+        dev.setProfiling(False)
+        welder.destroy()
+    launches = {k: v[0] for k, v in times.items()}
+    print("launches:", sorted(launches.items()))
+    assert {k: n for k, n in launches.items() if k.startswith("weld_")} == SORT_LAUNCHES, launches
+    assert {k: n for k, n in launches.items() if k.startswith("scan_")} == dict(scan_reduce=9, scan_block_sums=9, scan_downsweep=9), launches
+    assert stats["passesRun"] == 8, stats
 
 
 # ---------------------------------------------------------------- 3. two spheres in a TSDF volume

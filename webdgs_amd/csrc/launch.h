@@ -118,22 +118,47 @@ int launch_mesh_keep_flags(wdgs_device* dev, u32 n, const u32* component, const 
 int launch_mesh_emit(wdgs_device* dev, const u32* faces, u32 F, u32 V, const u32* vertex_flags, const u32* vertex_offsets, const u32* face_flags, const u32* face_offsets,
                      const float* positions, float* positions_out, u32* vertex_map, u32* faces_out, u32* face_map);
 
-// ---- meshweld.hip.  keys u64[S] (the caller's, never written); keys_a, keys_b u64[S] and slots_a, slots_b u32[S]: the pair buffers the sort's passes alternate
-// between; counters: the welder's 28-word block (V and the plan of passes); every kernel of a pass that the plan skips returns at once
-// or_and: u64[2 * weld_table_words(S) / 256], written: the OR and the AND of every tile's keys; counters: the plan, written
-int launch_weld_plan(wdgs_device* dev, const unsigned long long* keys, u32 S, unsigned long long* or_and, u32* counters);
-// the words of the digit-major table (and of its scan) for S slots
-u32 weld_table_words(u32 S);
-// table, offsets: u32[weld_table_words(S)], written by every pass that runs
-int launch_weld_sort(wdgs_device* dev, ScanScratch* scan, const unsigned long long* keys, u32 S, unsigned long long* keys_a, unsigned long long* keys_b, u32* slots_a,
-                     u32* slots_b, const u32* counters, u32* table, u32* offsets);
-// flags u32[S], written: 1 where a sorted pair begins a run of equal keys
-int launch_weld_heads(wdgs_device* dev, const unsigned long long* keys, u32 S, const unsigned long long* keys_a, const unsigned long long* keys_b, const u32* counters,
-                      u32* flags);
-// ids: the exclusive scan of flags; positions f32[S][3] with vertices_out, colours rgba8[S] with colours_out, keys_out: each nullable; faces_out u32[S]
-int launch_weld_emit(wdgs_device* dev, const unsigned long long* keys, u32 S, const unsigned long long* keys_a, const unsigned long long* keys_b, const u32* slots_a,
-                     const u32* slots_b, const u32* counters, const u32* flags, const u32* ids, const float* positions, const u32* colours, unsigned long long* keys_out,
-                     float* vertices_out, u32* colours_out, u32* faces_out);
+// ---- keysort.hip: the stable u64 key sort the welder (meshweld.hip) and the simplifier (meshsimplify.hip) group by; its sizing rule: keysort_sizes.h
+// The counters block, u32 words: the distinct keys, the passes run, the buffer that holds the sorted pairs, a spare, then per pass: run, input buffer, output buffer
+constexpr u32 KS_C_TOTAL = 0, KS_C_PASSES = 1, KS_C_FINAL = 2, KS_C_RUN = 4, KS_C_IN = 12, KS_C_OUT = 20, KS_C_WORDS = 28;
+constexpr u32 KS_PASSES = 8;   // 8-bit digits; every kernel of a pass that the plan skips returns at once
+// The sort's pairs as one kernel argument.  Valid once the sort's launches are enqueued: which buffer holds the sorted order is read from the counters on the device
+struct KeySortView {
+    const unsigned long long* keys0;   // buffer 0: the caller's keys (never written); slot = index
+    unsigned long long* keys[2];       // buffers 1 and 2: the pair buffers the passes alternate between
+    u32* slots[2];
+    const u32* counters;
+    __device__ __forceinline__ const unsigned long long* keys_of(u32 b) const { return b == 0u ? keys0 : keys[b - 1u]; }
+    __device__ __forceinline__ const u32* slots_of(u32 b) const { return b == 0u ? nullptr : slots[b - 1u]; }
+    __device__ __forceinline__ const unsigned long long* sorted_keys() const { return keys_of(counters[KS_C_FINAL]); }
+    __device__ __forceinline__ const u32* sorted_slots() const { return slots_of(counters[KS_C_FINAL]); }   // nullptr: slot = index (no pass ran)
+};
+struct KeySort {
+    DevMem<unsigned long long> keys_a, keys_b;   // [n]
+    DevMem<u32> slots_a, slots_b;                // [n]
+    DevMem<u32> flags, ids;                      // [n]: the head flags of the sorted pairs and their scan
+    DevMem<u32> table, offsets;                  // [256 * workgroups]: a pass's digit-major histogram and its scan
+    DevMem<unsigned long long> or_and;           // [2 * workgroups]: the OR and the AND of every tile's keys
+    DevMem<u32> counters;                        // KS_C_WORDS; the host may read TOTAL and PASSES after a wait
+    ScanScratch scratch;
+    u32 capacity_n = 0, capacity_table = 0, capacity_scan = 0;
+
+    int create(wdgs_device* dev);   // the zeroed counters
+    // Room for sorts of S_a and of S_b slots, grow-only; drains the lanes once before anything grows, waits for nothing otherwise
+    int reserve(wdgs_device* dev, u32 S_a, u32 S_b = 0);
+    // Plan, eight passes, head flags and their scan, whose total -- the number of distinct keys -- goes to total_out (device, nullable).  0 < S <= reserved
+    int sort(wdgs_device* dev, const unsigned long long* keys, u32 S, u32* total_out);
+    // After sort() of the same keys: rank_out[slot] = the rank of the slot's key among the distinct keys; per distinct key, at its rank: keys_out the key, and
+    // gather_u32_out / gather_f32x3_out what the key's LOWEST slot has in gather_u32[S] / gather_f32x3[S][3] (each of the three nullable, a payload with its output)
+    int emit(wdgs_device* dev, const unsigned long long* keys, u32 S, u32* rank_out, unsigned long long* keys_out, const u32* gather_u32, u32* gather_u32_out,
+             const float* gather_f32x3, float* gather_f32x3_out);
+    // sort() then emit()
+    int rank(wdgs_device* dev, const unsigned long long* keys, u32 S, u32* total_out, u32* rank_out, unsigned long long* keys_out, const u32* gather_u32,
+             u32* gather_u32_out, const float* gather_f32x3, float* gather_f32x3_out);
+    KeySortView view(const unsigned long long* keys) const { return KeySortView{keys, {keys_a, keys_b}, {slots_a, slots_b}, counters}; }
+    ScanScratch* scan() { return &scratch; }   // for the owner's further scans of at most the reserved sizes
+    u32* total() const { return counters + KS_C_TOTAL; }
+};
 
 // ---- meshsimplify.hip.  vertices f32[V][3], faces u32[F][3], colours rgba8[V] (nullable); origin, inv = 1 / cell_size and cell_size: the grid (webdgs.h)
 // keys u64[V], written: every vertex's cell key, 2^64 - 1 outside the grid

@@ -1,7 +1,7 @@
 // Mesh simplification by vertex clustering on the device (no counterpart in the reference, which renders colour only).
 //
-// Every vertex falls into a cell of a uniform grid; the distinct cells that hold a vertex are the clusters, numbered in ascending key order by the weld's
-// stable u64 sort (launch_weld_plan / _sort / _heads / _emit with S = V).  A cluster's representative is the integer mean of its vertices' 16-bit sub-cell
+// Every vertex falls into a cell of a uniform grid; the distinct cells that hold a vertex are the clusters, numbered in ascending key order by the library's
+// stable u64 sort (KeySort::rank, keysort.hip, with S = V).  A cluster's representative is the integer mean of its vertices' 16-bit sub-cell
 // offsets, its colour the integer mean of their bytes: only integers are ever summed, so no result depends on the order in which threads ran.  Faces are
 // classified, rotated so that their smallest cluster leads, and the duplicates among them found by two more sorts (S = F): the rank of (b, c) feeds the key
 // (a, rank), and -- the sort being stable -- the head of a run of equal second keys is the lowest face index with that triple.  Kept faces flag their
@@ -9,7 +9,6 @@
 //
 // Section 16's and 17's rule holds: no spin-wait, no inter-workgroup flag, no look-back, no grid barrier, no float atomics.  The only global atomics are
 // ms_accumulate's integer adds onto the clusters' sums, which commute; everything else reads what earlier launches wrote, with plain loads.
-#include <algorithm>
 #include <cmath>
 #include <memory>
 
@@ -29,7 +28,6 @@ constexpr u32 MS_ACC_TILE = MS_THREADS * MS_STEPS;   // 4096 vertices per workgr
 constexpr u32 MS_ACC_WORDS = 8;                 // per cluster, u64: Qx, Qy, Qz, n, and the four colour sums
 constexpr u32 MS_FACE_ROUNDS = 4;               // faces per thread of ms_face_keys: its workgroup leaves one row of class counts per 1024 faces
 constexpr u32 MS_FACE_TILE = MS_THREADS * MS_FACE_ROUNDS;
-constexpr u32 MS_SORT_WORDS = 28;               // the weld's counters block (launch.h)
 // The totals block, u32 words: distinct keys (the outside key included), emitted vertices, kept faces, the three class counts ms_fold leaves, 1 when the
 // last distinct key is the outside key, the two sorts' distinct face keys (unused by the host)
 constexpr u32 MS_T_DISTINCT = 0, MS_T_VERTICES = 1, MS_T_FACES = 2, MS_T_INVALID = 3, MS_T_OUTSIDE = 4, MS_T_COLLAPSED = 5, MS_T_HAS_OUTSIDE = 6, MS_T_SPARE = 7,
@@ -440,12 +438,7 @@ int launch_simplify_emit(wdgs_device* dev, const u32* faces, u32 F, u32 V, const
 // ---------------------------------------------------------------- the C ABI object (include/webdgs.h)
 struct wdgs_mesh_simplifier {
     wdgs_device* dev = nullptr;
-    // the sorts' arrays, [N = max(V, F)] and [table words]: what wdgs_mesh_welder holds, shared by the three sorts in turn
-    DevMem<unsigned long long> keys_a, keys_b;
-    DevMem<u32> slots_a, slots_b, flags, ids, table, offsets;
-    DevMem<unsigned long long> or_and;
-    DevMem<u32> sort_counters;
-    ScanScratch scan;
+    KeySort sort;                                                // reserved for V and for F: the three sorts use it in turn
     // per vertex [V]
     DevMem<unsigned long long> vertex_keys, cluster_keys, acc;   // acc: [8 V]
     DevMem<u32> rank, cluster_colours, cluster_flags, cluster_offsets;
@@ -454,7 +447,7 @@ struct wdgs_mesh_simplifier {
     DevMem<unsigned long long> face_keys;
     DevMem<u32> lead, face_rank, iota, head_face, face_flags, face_offsets, partial;
     DevMem<u32> totals;                                          // MS_T_WORDS
-    u32 capacity_v = 0, capacity_f = 0, capacity_n = 0, capacity_table = 0, capacity_scan = 0;
+    u32 capacity_v = 0, capacity_f = 0;
     bool counted = false;
     const void *vertices = nullptr, *faces = nullptr, *colours = nullptr;
     u32 V = 0, F = 0;
@@ -463,24 +456,10 @@ struct wdgs_mesh_simplifier {
 
 namespace {
 
-// The weld's sort of keys[S], its head flags and their scan; rank_out[slot] = the rank of the slot's key, keys_out (nullable) the distinct keys, gather_out
-// (nullable, with gather) gather[lowest slot] per distinct key; the number of distinct keys goes to *total
-int sort_and_rank(wdgs_mesh_simplifier* s, const unsigned long long* keys, u32 S, u32* total, u32* rank_out, unsigned long long* keys_out, const u32* gather, u32* gather_out) {
-    wdgs_device* d = s->dev;
-    WDGS_TRY(launch_weld_plan(d, keys, S, s->or_and, s->sort_counters));
-    WDGS_TRY(launch_weld_sort(d, &s->scan, keys, S, s->keys_a, s->keys_b, s->slots_a, s->slots_b, s->sort_counters, s->table, s->offsets));
-    WDGS_TRY(launch_weld_heads(d, keys, S, s->keys_a, s->keys_b, s->sort_counters, s->flags));
-    WDGS_TRY(scan_exclusive_u32(d, &s->scan, s->flags, s->ids, S, total));
-    return launch_weld_emit(d, keys, S, s->keys_a, s->keys_b, s->slots_a, s->slots_b, s->sort_counters, s->flags, s->ids, nullptr, gather, keys_out, nullptr, gather_out,
-                            rank_out);
-}
-
+// One wait on a call that grows: whichever of the two drains comes second -- this one or the sort's own -- finds the lanes idle, no launch lying between them
 int simplifier_reserve(wdgs_mesh_simplifier* s, u32 V, u32 F) {
     wdgs_device* d = s->dev;
-    // (the sorts' tile grows with S, so the larger S need not have the larger table)
-    const u32 N = std::max(V, F), table_words = std::max(weld_table_words(V), weld_table_words(F)), scan_words = std::max(N, table_words);
-    if (V <= s->capacity_v && F <= s->capacity_f && N <= s->capacity_n && table_words <= s->capacity_table && scan_words <= s->capacity_scan) return WDGS_OK;
-    WDGS_CHECK_HIP(wdgs_sync_lanes(d));   // (nothing in flight may still read the blocks given back)
+    if (V > s->capacity_v || F > s->capacity_f) WDGS_CHECK_HIP(wdgs_sync_lanes(d));   // (nothing in flight may still read the blocks given back)
     if (V > s->capacity_v) {
         s->capacity_v = 0;
         WDGS_TRY(s->vertex_keys.alloc(V, false, d->stream));
@@ -505,29 +484,7 @@ int simplifier_reserve(wdgs_mesh_simplifier* s, u32 V, u32 F) {
         WDGS_TRY(s->partial.alloc(3 * (size_t)simplify_partial_rows(F), false, d->stream));
         s->capacity_f = F;
     }
-    if (N > s->capacity_n) {
-        s->capacity_n = 0;
-        WDGS_TRY(s->keys_a.alloc(N, false, d->stream));
-        WDGS_TRY(s->keys_b.alloc(N, false, d->stream));
-        WDGS_TRY(s->slots_a.alloc(N, false, d->stream));
-        WDGS_TRY(s->slots_b.alloc(N, false, d->stream));
-        WDGS_TRY(s->flags.alloc(N, false, d->stream));
-        WDGS_TRY(s->ids.alloc(N, false, d->stream));
-        s->capacity_n = N;
-    }
-    if (table_words > s->capacity_table) {
-        s->capacity_table = 0;
-        WDGS_TRY(s->table.alloc(table_words, false, d->stream));
-        WDGS_TRY(s->offsets.alloc(table_words, false, d->stream));
-        WDGS_TRY(s->or_and.alloc(2u * (table_words / 256u), false, d->stream));
-        s->capacity_table = table_words;
-    }
-    if (scan_words > s->capacity_scan) {
-        s->capacity_scan = 0;
-        WDGS_TRY(scan_scratch_create(&s->scan, scan_words));
-        s->capacity_scan = scan_words;
-    }
-    return WDGS_OK;
+    return s->sort.reserve(d, V, F);
 }
 
 }  // namespace
@@ -537,7 +494,7 @@ extern "C" int wdgs_mesh_simplifier_create(wdgs_device* dev, wdgs_mesh_simplifie
     WDGS_REQUIRE(!dev->capturing, WDGS_E_STATE, "wdgs_mesh_simplifier_create while recording a command buffer");
     auto s = std::make_unique<wdgs_mesh_simplifier>();
     s->dev = dev;
-    WDGS_TRY(s->sort_counters.alloc(MS_SORT_WORDS, true, dev->stream));
+    WDGS_TRY(s->sort.create(dev));
     WDGS_TRY(s->totals.alloc(MS_T_WORDS, true, dev->stream));
     *out = s.release();
     return WDGS_OK;
@@ -575,18 +532,18 @@ extern "C" int wdgs_mesh_simplifier_count(wdgs_mesh_simplifier* s, const void* v
         const u32* colours = static_cast<const u32*>(colours_rgba8_dev);
         WDGS_CHECK_HIP(hipMemsetAsync(s->totals, 0, sizeof(u32) * MS_T_WORDS, d->stream));
         WDGS_TRY(launch_simplify_cell_keys(d, vertices, V, origin, inv, cell_size, s->vertex_keys));
-        WDGS_TRY(sort_and_rank(s, s->vertex_keys, V, s->totals + MS_T_DISTINCT, s->rank, s->cluster_keys, nullptr, nullptr));
+        WDGS_TRY(s->sort.rank(d, s->vertex_keys, V, s->totals + MS_T_DISTINCT, s->rank, s->cluster_keys, nullptr, nullptr, nullptr, nullptr));
         WDGS_TRY(launch_simplify_accumulate(d, vertices, colours, s->rank, V, origin, inv, cell_size, s->acc));
         WDGS_TRY(launch_simplify_finalize(d, s->cluster_keys, s->totals, s->acc, V, origin, inv, cell_size, colours != nullptr, s->cluster_positions, s->cluster_colours));
         if (F != 0u) WDGS_TRY(launch_simplify_face_keys(d, faces, F, V, s->vertex_keys, s->rank, s->face_keys, s->lead, s->iota, s->partial));
         WDGS_TRY(launch_simplify_fold(d, s->partial, simplify_partial_rows(F), s->cluster_keys, s->totals));
         if (F != 0u) {
-            WDGS_TRY(sort_and_rank(s, s->face_keys, F, s->totals + MS_T_SPARE, s->face_rank, nullptr, nullptr, nullptr));
+            WDGS_TRY(s->sort.rank(d, s->face_keys, F, s->totals + MS_T_SPARE, s->face_rank, nullptr, nullptr, nullptr, nullptr, nullptr));
             WDGS_TRY(launch_simplify_face_keys2(d, s->lead, s->face_rank, F, s->face_keys));
-            WDGS_TRY(sort_and_rank(s, s->face_keys, F, s->totals + MS_T_SPARE, s->face_rank, nullptr, s->iota, s->head_face));
+            WDGS_TRY(s->sort.rank(d, s->face_keys, F, s->totals + MS_T_SPARE, s->face_rank, nullptr, s->iota, s->head_face, nullptr, nullptr));   // (lowest face per key)
             WDGS_TRY(launch_simplify_mark(d, faces, F, V, s->lead, s->face_rank, s->head_face, s->rank, s->face_flags, s->cluster_flags));
-            WDGS_TRY(scan_exclusive_u32(d, &s->scan, s->cluster_flags, s->cluster_offsets, V, s->totals + MS_T_VERTICES));
-            WDGS_TRY(scan_exclusive_u32(d, &s->scan, s->face_flags, s->face_offsets, F, s->totals + MS_T_FACES));
+            WDGS_TRY(scan_exclusive_u32(d, s->sort.scan(), s->cluster_flags, s->cluster_offsets, V, s->totals + MS_T_VERTICES));
+            WDGS_TRY(scan_exclusive_u32(d, s->sort.scan(), s->face_flags, s->face_offsets, F, s->totals + MS_T_FACES));
         } else {
             WDGS_CHECK_HIP(hipMemsetAsync(s->cluster_flags, 0, sizeof(u32) * (size_t)V, d->stream));
         }
