@@ -537,6 +537,47 @@ static napi_value meshSimplifierStats(napi_env env, napi_callback_info info) {  
     for (uint32_t i = 0; i < 7; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
     return a;
 }
+// Adjacency, Taubin smoothing and vertex normals (include/webdgs.h: wdgs_mesh_adjacency_*; no reference counterpart)
+static napi_value meshAdjacencyCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_mesh_adjacency* a = nullptr;
+    WDGS_OK_OR_THROW(wdgs_mesh_adjacency_create((wdgs_device*)get_ptr(env, argv[0]), &a));
+    return make_ptr(env, a);
+}
+static napi_value meshAdjacencyDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_mesh_adjacency_destroy((wdgs_mesh_adjacency*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value meshAdjacencyCount(napi_env env, napi_callback_info info) {  // (adjacency, facesPtr | null, numFaces, numVertices) -> directed edges
+    ARGS(4);
+    uint32_t e = 0;
+    WDGS_OK_OR_THROW(wdgs_mesh_adjacency_count((wdgs_mesh_adjacency*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]), &e));
+    return make_u32(env, e);
+}
+static napi_value meshAdjacencyEmit(napi_env env, napi_callback_info info) {  // (adjacency, rowStartPtr | null, neighboursPtr | null, boundaryPtr | null, capacityEdges)
+    ARGS(5);
+    WDGS_OK_OR_THROW(wdgs_mesh_adjacency_emit((wdgs_mesh_adjacency*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_ptr(env, argv[3]),
+                                              get_u32(env, argv[4])));
+    return js_undefined(env);
+}
+static napi_value meshAdjacencySmooth(napi_env env, napi_callback_info info) {  // (adjacency, verticesInPtr, verticesOutPtr, numVertices, iterations, lambda, mu, flags)
+    ARGS(8);
+    WDGS_OK_OR_THROW(wdgs_mesh_adjacency_smooth((wdgs_mesh_adjacency*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_u32(env, argv[3]),
+                                                get_u32(env, argv[4]), (float)get_f64(env, argv[5]), (float)get_f64(env, argv[6]), get_u32(env, argv[7])));
+    return js_undefined(env);
+}
+static napi_value meshAdjacencyNormals(napi_env env, napi_callback_info info) {  // (adjacency, verticesPtr, facesPtr, numVertices, numFaces, normalsOutPtr)
+    ARGS(6);
+    WDGS_OK_OR_THROW(wdgs_mesh_adjacency_normals((wdgs_mesh_adjacency*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_u32(env, argv[3]),
+                                                 get_u32(env, argv[4]), get_ptr(env, argv[5])));
+    return js_undefined(env);
+}
+static napi_value meshAdjacencyStats(napi_env env, napi_callback_info info) {
+    // (adjacency) -> [directedEdges, edges, boundaryEdges, nonManifoldEdges, invalidFaces, boundaryVertices, isolatedVertices, maxDegree]
+    ARGS(1);
+    uint32_t r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_adjacency_stats((const wdgs_mesh_adjacency*)get_ptr(env, argv[0]), &r[0], &r[1], &r[2], &r[3], &r[4], &r[5], &r[6], &r[7]));
+    napi_value a; napi_create_array_with_length(env, 8, &a);
+    for (uint32_t i = 0; i < 8; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
+    return a;
+}
 static napi_value pointIndexCreate(napi_env env, napi_callback_info info) {  // (device, pointsPtr, numPoints, cellSize: 0 = chosen by the first query) -> handle
     ARGS(4);
     wdgs_point_index* ix = nullptr;
@@ -1213,6 +1254,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(meshComponentsCompact);
     EXPORT_FN(meshWelderCreate); EXPORT_FN(meshWelderDestroy); EXPORT_FN(meshWelderCount); EXPORT_FN(meshWelderEmit); EXPORT_FN(meshWelderStats);
     EXPORT_FN(meshSimplifierCreate); EXPORT_FN(meshSimplifierDestroy); EXPORT_FN(meshSimplifierCount); EXPORT_FN(meshSimplifierEmit); EXPORT_FN(meshSimplifierStats);
+    EXPORT_FN(meshAdjacencyCreate); EXPORT_FN(meshAdjacencyDestroy); EXPORT_FN(meshAdjacencyCount); EXPORT_FN(meshAdjacencyEmit); EXPORT_FN(meshAdjacencySmooth);
+    EXPORT_FN(meshAdjacencyNormals); EXPORT_FN(meshAdjacencyStats);
     EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
     EXPORT_FN(pointDistanceStats);
     EXPORT_FN(pointIndexBounds); EXPORT_FN(pointIndexKNearest); EXPORT_FN(pointCloudPositions); EXPORT_FN(pointCloudNeighbourScales);

@@ -7,7 +7,7 @@ import { EvaluationResult, NormalConsistencyResult, Trainer, TrainingImage, Trai
 
 type Split = 'eval' | 'train';
 type DepthKind = 'median' | 'expected';
-type MeshOptions = { viewIds?: number[] | null; split?: Split; depthKind?: DepthKind; minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null } & ComponentSelection;
+type MeshOptions = { viewIds?: number[] | null; split?: Split; depthKind?: DepthKind; minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean } & ComponentSelection;
 
 export class Evaluator {
   /** Uses of the trainer only: device, pointCloud, iteration, trainCameras, images, cameraBuffers, newPassSet, dcWords, longLists, drain(), growTileEntryCapacity(). */

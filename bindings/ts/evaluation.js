@@ -220,14 +220,17 @@ class Evaluator {
    *  options.simplify: a cell size (DESIGN.md section 18): the mesh is simplified last -- after welding and component removal, so that floaters are not
    *  merged into the surface first -- by hip.simplifyMesh on the grid of that cell size from the volume's lo, and its object is returned.  With weld
    *  'device' positions and faces stay on the device from the volume to the simplified mesh; with a component rule the colours alone are gathered through
-   *  vertexMap on the host.  The same bytes either way; without it, as before, and nothing more is launched. */
+   *  vertexMap on the host.  The same bytes either way; without it, as before, and nothing more is launched.
+   *  options.smooth: an iteration count, and options.normals (DESIGN.md section 19): hip.smoothMesh with its defaults after welding and component removal and
+   *  BEFORE simplify -- the fine mesh is denoised, then decimated -- with stats added; and normals, hip.vertexNormals of the final mesh.  With weld 'device'
+   *  the positions stay on the device through both.  Without them: as before, no new key and nothing more launched. */
   extractMesh(lo, hi, voxelSize, options) {
     const o = options || {}, weld = o.weld || 'host';
     if (weld !== 'host' && weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
     const unset = (x) => x === undefined || x === null;
     const everything = unset(o.keepLargest) && !(o.minTriangles > 0) && !(o.minFraction > 0);
     const rule = { keepLargest: o.keepLargest, minTriangles: o.minTriangles, minFraction: o.minFraction };
-    if (!unset(o.simplify)) return this.extractSimplified(lo, hi, voxelSize, o, weld, everything, rule);
+    if (!unset(o.simplify) || !unset(o.smooth) || o.normals) return this.extractFinished(lo, hi, voxelSize, o, weld, everything, rule);
     const volume = hip.TSDFVolume.fromBounds(this.device, lo, hi, voxelSize, { truncation: o.truncation, maxWeight: o.maxWeight, colour: o.colour });
     let mesh = null, welded = null;
     try {
@@ -255,26 +258,44 @@ class Evaluator {
       return out;
     } finally { hip.destroyBuffers(welded); }
   }
-  /** extractMesh with options.simplify set: volume, weld, component removal (when a rule is given), hip.simplifyMesh from the volume's origin. */
-  extractSimplified(lo, hi, voxelSize, o, weld, everything, rule) {
+  /** extractMesh with options.simplify, smooth or normals set: volume, weld, component removal (when a rule is given), then hip.finishMesh: smoothing,
+   *  simplification from the volume's origin, normals. */
+  extractFinished(lo, hi, voxelSize, o, weld, everything, rule) {
+    const unset = (x) => x === undefined || x === null;
+    const simplify = unset(o.simplify) ? null : o.simplify, smooth = unset(o.smooth) ? null : o.smooth, normals = !!o.normals;
     const volume = hip.TSDFVolume.fromBounds(this.device, lo, hi, voxelSize, { truncation: o.truncation, maxWeight: o.maxWeight, colour: o.colour });
     let welded = {}, kept = {};
     try {
       this.fuseDepth(volume, o.viewIds, o.split, o.depthKind);
       const origin = volume.origin;
-      if (everything) return volume.extractMesh(o.minWeight, { weld, simplify: o.simplify });
-      if (weld === 'host') return hip.simplifyMesh(this.device, hip.removeSmallComponents(this.device, volume.extractMesh(o.minWeight), rule), o.simplify, { origin });
+      if (everything) return volume.extractMesh(o.minWeight, { weld, simplify, smooth, normals });
+      if (weld === 'host') {
+        return hip.finishMesh(this.device, hip.removeSmallComponents(this.device, volume.extractMesh(o.minWeight), rule), origin, smooth, simplify, normals);
+      }
       const tri = volume.extractTriangleBuffers(o.minWeight);
       try { welded = hip.weldTrianglesDevice(this.device, tri, { asBuffers: true }); } finally { hip.destroyBuffers(tri); }
       kept = hip.removeSmallComponents(this.device, { vertices: welded.vertices, faces: welded.faces }, Object.assign({ asBuffers: true }, rule));
-      if (welded.colours) {
-        const V = welded.numVertices, nv = kept.numVertices, bytes = (b, n) => (n ? this.device.readBuffer(b, n) : new ArrayBuffer(0));
+      const V = welded.numVertices, nv = kept.numVertices, nf = kept.numFaces, bytes = (b, n) => (n ? this.device.readBuffer(b, n) : new ArrayBuffer(0));
+      if (simplify !== null && welded.colours) {
         const all = new Uint32Array(bytes(welded.colours, 4 * V)), map = new Uint32Array(bytes(kept.vertexMap, 4 * nv));
         const gathered = Uint32Array.from(map, (old) => all[old]);
         kept.colours = this.device.createBuffer({ size: Math.max(gathered.byteLength, 8), label: 'compacted colours' });
         if (gathered.byteLength) this.device.queue.writeBuffer(kept.colours, 0, gathered);
       }
-      return hip.simplifyMesh(this.device, kept, o.simplify, { origin });
+      // what removeSmallComponents returns for the typed-array mesh: colours and keys gathered through vertexMap
+      const read = (device, b) => {
+        const out = { vertices: new Float32Array(bytes(b.vertices, 12 * nv)), faces: new Uint32Array(bytes(b.faces, 12 * nf)),
+          vertexMap: new Uint32Array(bytes(b.vertexMap, 4 * nv)), faceMap: new Uint32Array(bytes(b.faceMap, 4 * nf)), components: b.components, colours: null };
+        if (welded.colours) {
+          const rgba = new Uint8Array(bytes(welded.colours, 4 * V));
+          out.colours = new Uint8Array(3 * nv);
+          out.vertexMap.forEach((old, i) => { for (let a = 0; a < 3; a++) out.colours[3 * i + a] = rgba[4 * old + a]; });
+        }
+        const keys = new BigUint64Array(bytes(welded.keys, 8 * V));
+        out.keys = BigUint64Array.from(out.vertexMap, (old) => keys[old]);
+        return out;
+      };
+      return hip.finishMesh(this.device, kept, origin, smooth, simplify, normals, read);
     } finally {
       volume.destroy();
       hip.destroyBuffers(welded);

@@ -27,11 +27,11 @@ export function loadCamera(fileOrFiles: { name?: string; data: Bytes } | { name?
 export function cameraUniforms(cam: Partial<CameraData>, width?: number, height?: number): Float32Array;
 /** Train / test split, every `every`-th view (index % every === 0) to test: [trainCams, trainImgs, testCams, testImgs]. */
 /** A mesh { vertices, faces, colours } as a binary little-endian PLY (x y z float, red green blue uchar if coloured, vertex_indices list uchar uint). */
-export function meshPLYBytes(mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null }): Buffer;
+export function meshPLYBytes(mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null; normals?: Float32Array | null }): Buffer;
 /** Points [N*3] as a binary little-endian PLY (vertex x y z float); loadPointsPLY reads any binary little-endian PLY's vertex positions.  No reference counterpart. */
 export function pointsPLYBytes(points: Float32Array | ArrayLike<number>): Buffer;
 export function savePointsPLY(path: string, points: Float32Array | ArrayLike<number>): void;
 export function loadPointsPLY(path: string): Float32Array;
-export function saveMeshPLY(path: string, mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null }): void;
+export function saveMeshPLY(path: string, mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null; normals?: Float32Array | null }): void;
 export function holdoutSplit<C, I>(cameras: C[], images: I[], every?: number): [C[], I[], C[], I[]];
 export function fromQuat(qx: number, qy: number, qz: number, qw: number): Float32Array;

@@ -310,21 +310,24 @@ function holdoutSplit(cameras, images, every = 8) {
   return [cameras.filter((_, i) => !test(i)), images.filter((_, i) => !test(i)), cameras.filter((_, i) => test(i)), images.filter((_, i) => test(i))];
 }
 
-/** A mesh { vertices: Float32Array[V*3], faces: Uint32Array[F*3], colours: Uint8Array[V*3] | null } (TSDFVolume.extractMesh) as a binary
- *  little-endian PLY: the vertex element x y z float and, with colours, red green blue uchar; the face element vertex_indices as list uchar uint.
- *  The bytes the Python host's loaders.meshPLYBytes writes.  No reference counterpart. */
+/** A mesh { vertices: Float32Array[V*3], faces: Uint32Array[F*3], colours: Uint8Array[V*3] | null, normals?: Float32Array[V*3] }
+ *  (TSDFVolume.extractMesh) as a binary little-endian PLY: the vertex element x y z float, with normals nx ny nz float, and with colours red green blue
+ *  uchar; the face element vertex_indices as list uchar uint.  The bytes the Python host's loaders.meshPLYBytes writes.  No reference counterpart. */
 function meshPLYBytes(mesh) {
-  const V = mesh.vertices.length / 3, F = mesh.faces.length / 3, c = mesh.colours || null;
+  const V = mesh.vertices.length / 3, F = mesh.faces.length / 3, c = mesh.colours || null, n = mesh.normals || null;
   if (c && c.length !== 3 * V) throw new Error(`meshPLYBytes: ${V} vertices, ${c.length / 3} colours`);
+  if (n && n.length !== 3 * V) throw new Error(`meshPLYBytes: ${V} vertices, ${n.length / 3} normals`);
   const header = ['ply', 'format binary_little_endian 1.0', `element vertex ${V}`, 'property float x', 'property float y', 'property float z']
+    .concat(n ? ['property float nx', 'property float ny', 'property float nz'] : [])
     .concat(c ? ['property uchar red', 'property uchar green', 'property uchar blue'] : [])
     .concat([`element face ${F}`, 'property list uchar uint vertex_indices', 'end_header']).join('\n') + '\n';
-  const vs = c ? 15 : 12, head = Buffer.from(header, 'ascii'), out = Buffer.alloc(head.length + vs * V + 13 * F);
+  const co = n ? 24 : 12, vs = co + (c ? 3 : 0), head = Buffer.from(header, 'ascii'), out = Buffer.alloc(head.length + vs * V + 13 * F);
   head.copy(out, 0);
   let o = head.length;
   for (let v = 0; v < V; v++, o += vs) {
     for (let a = 0; a < 3; a++) out.writeFloatLE(mesh.vertices[3 * v + a], o + 4 * a);
-    if (c) for (let a = 0; a < 3; a++) out[o + 12 + a] = c[3 * v + a];
+    if (n) for (let a = 0; a < 3; a++) out.writeFloatLE(n[3 * v + a], o + 12 + 4 * a);
+    if (c) for (let a = 0; a < 3; a++) out[o + co + a] = c[3 * v + a];
   }
   for (let f = 0; f < F; f++, o += 13) {
     out[o] = 3;

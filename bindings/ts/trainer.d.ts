@@ -76,13 +76,13 @@ export class Trainer {
    *  its object is returned.  No reference counterpart. */
   extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number,
               options?: { viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected'; minWeight?: number; truncation?: number; maxWeight?: number;
-                          colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null } & import('./webdgs_hip').ComponentSelection):
+                          colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean } & import('./webdgs_hip').ComponentSelection):
     import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh | import('./webdgs_hip').SimplifiedMesh;
   /** extractMesh -> sampleMesh -> geometryMetrics against `reference` (points [M*3], or the path of a PLY): the mesh's accuracy, completeness, Chamfer
    *  distance, precision, recall and F-score, with the mesh's vertex, face and sample counts and ms.  Training untouched.  No reference counterpart. */
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,
                    options?: { density?: number | null; seed?: number; viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected';
-                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null } &
+                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean } &
                      import('./webdgs_hip').ComponentSelection):
     import('./webdgs_hip').GeometryMetrics & { vertices: number; faces: number; samples: number; ms: number };
   /** Per-Gaussian render contribution accumulated over the views (default: all training views); no reference counterpart. */

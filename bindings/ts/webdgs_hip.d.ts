@@ -253,6 +253,9 @@ export class TSDFVolume {
   extractMesh(minWeight?: number | null, options?: { weld?: 'host' | 'device'; simplify?: null }): TriangleMesh;
   /** simplify: a cell size -- the welded mesh goes through simplifyMesh on that grid from the volume's origin (with weld 'device', on the device). */
   extractMesh(minWeight: number | null | undefined, options: { weld?: 'host' | 'device'; simplify: number }): SimplifiedMesh;
+  /** smooth: an iteration count -- smoothMesh with its defaults, before simplify, with stats added; normals: vertexNormals of the final mesh is added. */
+  extractMesh(minWeight: number | null | undefined, options: { weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean }):
+    TriangleMesh & { stats?: AdjacencyStats | SimplifyStats; normals?: Float32Array; faceMap?: Uint32Array; vertexCluster?: Uint32Array };
   destroy(): void;
 }
 /** extractTriangles' output as an indexed mesh: vertices are the distinct edge keys in ascending order.  No reference counterpart. */
@@ -305,6 +308,38 @@ export function simplifyMesh(device: HipDevice, mesh: { vertices: Float32Array; 
                              options?: { origin?: ArrayLike<number> | null; asBuffers?: false }): SimplifiedMesh;
 export function simplifyMesh(device: HipDevice, mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null } | MeshBuffers, cellSize: number,
                              options: { origin?: ArrayLike<number> | null; asBuffers: true }): SimplifiedMeshBuffers;
+/** The last count of a MeshAdjacency: E and E / 2, the undirected edges that one face (boundary) or three and more (non-manifold) hold, the faces left out,
+ *  the ends of boundary edges, the vertices without a neighbour, the longest row. */
+export interface AdjacencyStats { directedEdges: number; edges: number; boundaryEdges: number; nonManifoldEdges: number; invalidFaces: number; boundaryVertices: number;
+                                  isolatedVertices: number; maxDegree: number }
+export interface SmoothOptions { lambda?: number; mu?: number; pinBoundary?: boolean }
+/** The per-vertex neighbour lists of an indexed mesh on the device (wdgs_mesh_adjacency): one stable u64 sort of the faces' directed half-edge keys; count, then
+ *  emit, smooth (Taubin's lambda | mu steps) and normals (area-weighted) over that count.  No reference counterpart. */
+export class MeshAdjacency {
+  constructor(device: HipDevice);
+  readonly numEdges: number; readonly numVertices: number; readonly numFaces: number;
+  count(faces: HipBuffer | null, numFaces: number, numVertices: number): number;
+  emit(rowStart?: HipBuffer | null, neighbours?: HipBuffer | null, boundary?: HipBuffer | null, capacityEdges?: number | null): void;
+  smooth(verticesIn: HipBuffer | null, verticesOut: HipBuffer | null, numVertices: number, iterations?: number | null, options?: SmoothOptions): void;
+  normals(vertices: HipBuffer | null, faces: HipBuffer | null, numVertices: number, numFaces: number, normalsOut: HipBuffer | null): void;
+  stats(): AdjacencyStats;
+  destroy(): void;
+}
+type MeshArrays = { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null };
+/** rowStart[V + 1], neighbours[E] (ascending within a row) and boundary[V] of the mesh's faces; a function of the faces alone, bit for bit. */
+export function meshAdjacency(device: HipDevice, mesh: MeshArrays | MeshBuffers): { rowStart: Uint32Array; neighbours: Uint32Array; boundary: Uint32Array; stats: AdjacencyStats };
+/** `mesh` after `iterations` (default 10) rounds of Taubin smoothing: its object with new vertices and stats added; bit for bit a function of its arguments. */
+export function smoothMesh<M extends MeshArrays>(device: HipDevice, mesh: M, iterations?: number | null, options?: SmoothOptions & { asBuffers?: false }):
+  M & { stats: AdjacencyStats };
+export function smoothMesh<M extends MeshBuffers>(device: HipDevice, mesh: M, iterations?: number | null, options?: SmoothOptions & { asBuffers?: false }):
+  Omit<M, 'vertices'> & { vertices: Float32Array; stats: AdjacencyStats };
+export function smoothMesh(device: HipDevice, mesh: MeshArrays | MeshBuffers, iterations: number | null | undefined, options: SmoothOptions & { asBuffers: true }):
+  MeshBuffers & { stats: AdjacencyStats; numVertices: number; numFaces: number };
+/** The area-weighted unit normals [V*3] of the mesh; (0, 0, 0) for a vertex without a face of non-zero finite area. */
+export function vertexNormals(device: HipDevice, mesh: MeshArrays | MeshBuffers): Float32Array;
+/** extractMesh's last stages in their order -- smoothMesh, simplifyMesh from `origin`, vertexNormals -- each only when asked for (null, null, false: none). */
+export function finishMesh(device: HipDevice, mesh: MeshArrays | MeshBuffers, origin: ArrayLike<number>, smooth: number | null, simplify: number | null, normals: boolean,
+                           read?: (device: HipDevice, mesh: MeshBuffers) => object): any;
 /** The index of "no point found" (PointIndex.nearest).  No reference counterpart. */
 export const NO_INDEX: 0xFFFFFFFF;
 export interface MeshSamples { points: Float32Array; face: Uint32Array; count: number }

@@ -567,23 +567,30 @@ class TSDFVolume {
     return out;
   }
   /** The welded mesh.  options.weld: 'host' (default: weldTriangles of extractTriangles) or 'device' (the triangles stay on the device and
-   *  weldTrianglesDevice welds them there: the same bytes, and only the V- and F-sized arrays of the result cross the bus).  options.simplify: a cell
-   *  size (DESIGN.md section 18): the welded mesh goes through simplifyMesh on the grid of that cell size from the volume's origin and its object is
-   *  returned; with weld 'device' the welded mesh stays on the device until it is simplified.  Without it nothing more is launched. */
+   *  weldTrianglesDevice welds them there: the same bytes, and only the V- and F-sized arrays of the result cross the bus).  options.smooth: an iteration
+   *  count (DESIGN.md section 19): the welded mesh goes through smoothMesh with its defaults -- before it is simplified -- and stats is added;
+   *  options.normals: normals Float32Array[V*3], vertexNormals of the final mesh, is added; with weld 'device' the positions stay on the device through
+   *  both.  options.simplify: a cell size (DESIGN.md section 18): the welded mesh goes through simplifyMesh on the grid of that cell size from the
+   *  volume's origin and its object is returned; with weld 'device' the welded mesh stays on the device until it is simplified.  Without the three nothing
+   *  more is launched. */
   extractMesh(minWeight, options) {
     const weld = (options && options.weld) || 'host';
     const simplify = options && options.simplify !== undefined && options.simplify !== null ? options.simplify : null;
+    const smooth = options && options.smooth !== undefined && options.smooth !== null ? options.smooth : null;
+    const normals = !!(options && options.normals), plain = smooth === null && !normals;
     if (weld !== 'host' && weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
     if (weld === 'host') {
       const mesh = weldTriangles(this.extractTriangles(minWeight));
-      return simplify === null ? mesh : simplifyMesh(this.device, mesh, simplify, { origin: this.origin });
+      if (plain) return simplify === null ? mesh : simplifyMesh(this.device, mesh, simplify, { origin: this.origin });
+      return finishMesh(this.device, mesh, this.origin, smooth, simplify, normals);
     }
     const tri = this.extractTriangleBuffers(minWeight);
     let welded = {};
     try {
-      if (simplify === null) return weldTrianglesDevice(this.device, tri);
+      if (simplify === null && plain) return weldTrianglesDevice(this.device, tri);
       welded = weldTrianglesDevice(this.device, tri, { asBuffers: true });
-      return simplifyMesh(this.device, welded, simplify, { origin: this.origin });
+      if (plain) return simplifyMesh(this.device, welded, simplify, { origin: this.origin });
+      return finishMesh(this.device, welded, this.origin, smooth, simplify, normals, readWelded);
     } finally { destroyBuffers(tri); destroyBuffers(welded); }
   }
   destroy() {
@@ -621,6 +628,18 @@ function destroyBuffers(buffers) { Object.values(buffers).forEach((b) => { if (b
 function exactBuffer(device, size) {
   const b = addon.bufferCreate(device.handle, Math.max(size, 8));
   return new HipBuffer(device, b.ptr, size, b.handle);
+}
+/** The rgb bytes of `count` rgba8 words of a device buffer. */
+function readRGB(device, buffer, count) {
+  const rgba = new Uint8Array(count ? device.readBuffer(buffer, 4 * count) : new ArrayBuffer(0)), rgb = new Uint8Array(3 * count);
+  for (let v = 0; v < count; v++) for (let a = 0; a < 3; a++) rgb[3 * v + a] = rgba[4 * v + a];
+  return rgb;
+}
+/** The welded mesh weldTrianglesDevice hands out with asBuffers, read back: { vertices, faces, colours: rgb | null, keys }. */
+function readWelded(device, b) {
+  const V = b.numVertices, F = b.numFaces, bytes = (x, n) => (n ? device.readBuffer(x, n) : new ArrayBuffer(0));
+  return { vertices: new Float32Array(bytes(b.vertices, 12 * V)), faces: new Uint32Array(bytes(b.faces, 12 * F)), colours: b.colours ? readRGB(device, b.colours, V) : null,
+    keys: new BigUint64Array(bytes(b.keys, 8 * V)) };
 }
 /** Welds a triangle soup on the device (wdgs_mesh_welder): count sorts the (key, slot) pairs with a stable radix sort, flags the first pair of every
  *  distinct key and returns their number (one wait); emit writes the indexed mesh.  weldTrianglesDevice is the one-call form. */
@@ -682,14 +701,7 @@ function weldTrianglesDevice(device, tri, options) {
       out = {};
       return result;
     }
-    const bytes = (b, n) => (n ? device.readBuffer(b, n) : new ArrayBuffer(0));
-    let colours = null;
-    if (out.colours) {
-      const rgba = new Uint8Array(bytes(out.colours, 4 * V));
-      colours = new Uint8Array(3 * V);
-      for (let v = 0; v < V; v++) for (let a = 0; a < 3; a++) colours[3 * v + a] = rgba[4 * v + a];
-    }
-    return { vertices: new Float32Array(bytes(out.vertices, 12 * V)), faces: new Uint32Array(bytes(out.faces, 4 * S)), colours, keys: new BigUint64Array(bytes(out.keys, 8 * V)) };
+    return readWelded(device, Object.assign({}, out, { numVertices: V, numFaces: F }));
   } finally {
     welder.destroy();
     destroyBuffers(out);
@@ -787,21 +799,203 @@ function simplifyMesh(device, mesh, cellSize, options) {
       out = {};
       return result;
     }
-    const bytes = (b, k) => (k ? device.readBuffer(b, k) : new ArrayBuffer(0));
-    let colours = null;
-    if (out.colours) {
-      const rgba = new Uint8Array(bytes(out.colours, 4 * nv));
-      colours = new Uint8Array(3 * nv);
-      for (let v = 0; v < nv; v++) for (let a = 0; a < 3; a++) colours[3 * v + a] = rgba[4 * v + a];
-    }
-    return { vertices: new Float32Array(bytes(out.vertices, 12 * nv)), faces: new Uint32Array(bytes(out.faces, 12 * nf)), colours,
-      keys: new BigUint64Array(bytes(out.keys, 8 * nv)), faceMap: new Uint32Array(bytes(out.faceMap, 4 * nf)),
-      vertexCluster: new Uint32Array(bytes(out.vertexCluster, 4 * V)), stats };
+    return readSimplified(device, Object.assign({}, out, { numVertices: nv, numFaces: nf, stats }), V);
   } finally {
     simplifier.destroy();
     destroyBuffers(out);
     if (own) destroyBuffers(src);
   }
+}
+
+/** The mesh simplifyMesh hands out with asBuffers for an input of V vertices, read back as simplifyMesh returns it. */
+function readSimplified(device, b, V) {
+  const nv = b.numVertices, nf = b.numFaces, bytes = (x, k) => (k ? device.readBuffer(x, k) : new ArrayBuffer(0));
+  return { vertices: new Float32Array(bytes(b.vertices, 12 * nv)), faces: new Uint32Array(bytes(b.faces, 12 * nf)), colours: b.colours ? readRGB(device, b.colours, nv) : null,
+    keys: new BigUint64Array(bytes(b.keys, 8 * nv)), faceMap: new Uint32Array(bytes(b.faceMap, 4 * nf)), vertexCluster: new Uint32Array(bytes(b.vertexCluster, 4 * V)),
+    stats: b.stats };
+}
+
+// ---------------------------------------------------------------- adjacency, smoothing and vertex normals (include/webdgs.h, DESIGN.md section 19; no reference counterpart)
+const SMOOTH_PIN_BOUNDARY = 1;   // WDGS_SMOOTH_PIN_BOUNDARY
+const ADJACENCY_STATS = ['directedEdges', 'edges', 'boundaryEdges', 'nonManifoldEdges', 'invalidFaces', 'boundaryVertices', 'isolatedVertices', 'maxDegree'];
+/** The per-vertex neighbour lists of an indexed mesh on the device (wdgs_mesh_adjacency) and what stands on them: count sorts the faces' directed half-edge
+ *  keys (the welder's stable u64 sort over 6 F slots), delimits the rows, flags the boundary and returns E (one wait); emit writes rowStart, neighbours and
+ *  boundary; smooth runs Taubin's lambda | mu steps and normals the area-weighted vertex normals over that count, both stream-ordered.  meshAdjacency,
+ *  smoothMesh and vertexNormals are the one-call forms. */
+class MeshAdjacency {
+  constructor(device) {
+    this.device = device; this.destroyed = false; this.numEdges = 0; this.numVertices = 0; this.numFaces = 0;
+    this.handle = addon.meshAdjacencyCreate(device.handle);
+  }
+  /** E, the number of directed edges of faces u32[numFaces][3] over numVertices vertices (waits once).  The faces must stay as they are while normals may
+   *  still be called. */
+  count(faces, numFaces, numVertices) {
+    if (6 * numFaces < 2 ** 32 && faces && faces.size < 12 * numFaces) throw new Error('MeshAdjacency.count: buffer too small for the faces');
+    this.numEdges = addon.meshAdjacencyCount(this.handle, faces ? faces.ptr : null, numFaces, numVertices);
+    this.numVertices = numVertices; this.numFaces = numFaces;
+    return this.numEdges;
+  }
+  /** Writes rowStart u32[V + 1], neighbours u32[E] and boundary u32[V] of the count before it, each nullable (WDGS_E_STATE without a count;
+   *  WDGS_E_CAPACITY, with nothing written, when there is room for fewer than E edges).  Stream-ordered: it waits for nothing and records. */
+  emit(rowStart, neighbours, boundary, capacityEdges) {
+    const cap = capacityEdges === undefined || capacityEdges === null ? (neighbours ? Math.floor(neighbours.size / 4) : 0xFFFFFFFF) : capacityEdges;
+    if (neighbours && 4 * cap > neighbours.size) throw new Error('MeshAdjacency.emit: the capacity exceeds the buffer');
+    if ((rowStart && rowStart.size < 4 * (this.numVertices + 1)) || (boundary && boundary.size < 4 * this.numVertices)) {
+      throw new Error('MeshAdjacency.emit: buffers too small for the vertices');
+    }
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshAdjacencyEmit(this.handle, ptr(rowStart), ptr(neighbours), ptr(boundary), cap);
+  }
+  /** verticesOut f32[V][3] = verticesIn after `iterations` rounds of step(lambda) then step(mu) over the counted adjacency (a weight of exactly 0 skips its
+   *  step; verticesOut may be verticesIn).  options: { lambda = 0.5, mu = -0.53, pinBoundary = true }.  WDGS_E_STATE unless numVertices is the count's.
+   *  Stream-ordered: it waits for nothing, allocates nothing and records. */
+  smooth(verticesIn, verticesOut, numVertices, iterations, options) {
+    const o = options || {}, lambda = o.lambda === undefined ? 0.5 : o.lambda, mu = o.mu === undefined ? -0.53 : o.mu, pin = o.pinBoundary === undefined ? true : o.pinBoundary;
+    for (const b of [verticesIn, verticesOut]) if (b && numVertices === this.numVertices && b.size < 12 * numVertices) throw new Error('MeshAdjacency.smooth: buffer too small for the vertices');
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshAdjacencySmooth(this.handle, ptr(verticesIn), ptr(verticesOut), numVertices, iterations === undefined || iterations === null ? 10 : iterations,
+      Math.fround(lambda), Math.fround(mu), pin ? SMOOTH_PIN_BOUNDARY : 0);
+  }
+  /** normalsOut f32[V][3]: the area-weighted normals of vertices f32[V][3] over the counted faces -- `faces` must be the buffer that was counted, unchanged
+   *  (WDGS_E_STATE otherwise).  Stream-ordered: it waits for nothing and records. */
+  normals(vertices, faces, numVertices, numFaces, normalsOut) {
+    for (const b of [vertices, normalsOut]) if (b && numVertices === this.numVertices && b.size < 12 * numVertices) throw new Error('MeshAdjacency.normals: buffer too small for the vertices');
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshAdjacencyNormals(this.handle, ptr(vertices), ptr(faces), numVertices, numFaces, ptr(normalsOut));
+  }
+  /** The last count: { directedEdges, edges, boundaryEdges, nonManifoldEdges, invalidFaces, boundaryVertices, isolatedVertices, maxDegree }. */
+  stats() {
+    const r = addon.meshAdjacencyStats(this.handle), out = {};
+    ADJACENCY_STATS.forEach((k, i) => { out[k] = r[i]; });
+    return out;
+  }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.meshAdjacencyDestroy(this.handle); this.handle = null; }
+}
+/** { vertices, faces, V, F, own }: the mesh's positions and faces as HipBuffers -- uploaded from typed arrays (own: the caller destroys them) or taken as they
+ *  are from an object of buffers with numVertices / numFaces or whole buffers. */
+function meshOnDevice(device, mesh, what) {
+  if (!(mesh.vertices instanceof HipBuffer)) {
+    if (mesh.vertices.length % 3 !== 0 || mesh.faces.length % 3 !== 0) throw new Error(`${what}: vertices and faces are three values per row`);
+    const upload = (a) => { const b = device.createBuffer({ size: Math.max(a.byteLength, 8) }); if (a.byteLength) device.queue.writeBuffer(b, 0, a); return b; };
+    return { vertices: upload(mesh.vertices instanceof Float32Array ? mesh.vertices : Float32Array.from(mesh.vertices)),
+      faces: upload(mesh.faces instanceof Uint32Array ? mesh.faces : Uint32Array.from(mesh.faces)), V: mesh.vertices.length / 3, F: mesh.faces.length / 3, own: true };
+  }
+  if (!(mesh.faces instanceof HipBuffer)) throw new Error(`${what}: vertices on the device need faces on the device`);
+  return { vertices: mesh.vertices, faces: mesh.faces, V: mesh.numVertices === undefined ? Math.floor(mesh.vertices.size / 12) : mesh.numVertices,
+    F: mesh.numFaces === undefined ? Math.floor(mesh.faces.size / 12) : mesh.numFaces, own: false };
+}
+/** The neighbour lists of `mesh` (typed arrays or device buffers; only the faces and the vertex count matter): { rowStart: Uint32Array[V+1], neighbours:
+ *  Uint32Array[E], boundary: Uint32Array[V], stats } -- vertex v neighbours neighbours[rowStart[v] .. rowStart[v+1]), ascending; boundary is 1 on both ends
+ *  of every edge that one face alone holds.  A function of the faces alone, bit for bit (include/webdgs.h states it). */
+function meshAdjacency(device, mesh) {
+  const src = meshOnDevice(device, mesh, 'meshAdjacency'), adjacency = new MeshAdjacency(device);
+  let out = {};
+  try {
+    const V = src.V, E = adjacency.count(src.faces, src.F, V);
+    out = { rowStart: exactBuffer(device, 4 * (V + 1)), neighbours: exactBuffer(device, 4 * E), boundary: exactBuffer(device, 4 * V) };
+    adjacency.emit(out.rowStart, out.neighbours, out.boundary, E);
+    const bytes = (b, n) => (n ? device.readBuffer(b, n) : new ArrayBuffer(0));
+    return { rowStart: new Uint32Array(bytes(out.rowStart, 4 * (V + 1))), neighbours: new Uint32Array(bytes(out.neighbours, 4 * E)),
+      boundary: new Uint32Array(bytes(out.boundary, 4 * V)), stats: adjacency.stats() };
+  } finally {
+    adjacency.destroy();
+    destroyBuffers(out);
+    if (src.own) { src.vertices.destroy(); src.faces.destroy(); }
+  }
+}
+/** { smoothed, normals, stats } of a mesh on the device through one MeshAdjacency: a new buffer of the positions after `smooth` iterations (null: not
+ *  wanted) and a new buffer of the normals of the smoothed -- else the given -- positions.  The caller destroys both. */
+function smoothAndNormals(device, vertices, faces, V, F, smooth, normals, options) {
+  const adjacency = new MeshAdjacency(device);
+  let out = {};
+  try {
+    adjacency.count(faces, F, V);
+    if (smooth !== null) {
+      out.smoothed = exactBuffer(device, 12 * V);
+      adjacency.smooth(vertices, out.smoothed, V, smooth, options);
+    }
+    if (normals) {
+      out.normals = exactBuffer(device, 12 * V);
+      adjacency.normals(out.smoothed || vertices, faces, V, F, out.normals);
+    }
+    const result = { smoothed: out.smoothed || null, normals: out.normals || null, stats: adjacency.stats() };
+    device.synchronize();   // (the object's arrays are released below)
+    out = {};
+    return result;
+  } finally {
+    adjacency.destroy();
+    destroyBuffers(out);
+  }
+}
+/** `mesh` after `iterations` (default 10) rounds of Taubin's lambda | mu smoothing (mu = 0: plain Laplacian smoothing): every vertex moves towards, then away
+ *  from, the f32 mean of its neighbours, summed in ascending neighbour order; with pinBoundary the ends of boundary edges stay where they are.  options:
+ *  { lambda = 0.5, mu = -0.53, pinBoundary = true, asBuffers }.  `mesh` is what extractMesh / loadMeshPLY return, or an object of HipBuffers as
+ *  weldTrianglesDevice and simplifyMesh hand out with asBuffers (left as it is).  Returns the mesh's object with new vertices, every other entry passed through,
+ *  and stats added; bit for bit a function of its arguments (include/webdgs.h states it).  options.asBuffers: vertices is a new HipBuffer f32[V][3] the
+ *  caller destroys; a typed-array mesh's faces are then handed out as a buffer too, with numVertices and numFaces. */
+function smoothMesh(device, mesh, iterations, options) {
+  const o = options || {}, src = meshOnDevice(device, mesh, 'smoothMesh');
+  let smoothed = null, keepFaces = false;
+  try {
+    const r = smoothAndNormals(device, src.vertices, src.faces, src.V, src.F, iterations === undefined || iterations === null ? 10 : iterations, false, o);
+    smoothed = r.smoothed;
+    if (o.asBuffers) {
+      const result = Object.assign({}, mesh, { vertices: smoothed, stats: r.stats, numVertices: src.V, numFaces: src.F });
+      if (src.own) { result.faces = src.faces; keepFaces = true; }
+      smoothed = null;
+      return result;
+    }
+    return Object.assign({}, mesh, { vertices: new Float32Array(src.V ? device.readBuffer(smoothed, 12 * src.V) : new ArrayBuffer(0)), stats: r.stats });
+  } finally {
+    if (smoothed) smoothed.destroy();
+    if (src.own) { src.vertices.destroy(); if (!keepFaces) src.faces.destroy(); }
+  }
+}
+/** The area-weighted unit normals Float32Array[V*3] of `mesh` (typed arrays or device buffers): per vertex the sum of its faces' cross products in the order
+ *  the half-edge sort fixes, normalised; (0, 0, 0) for a vertex without a face of non-zero finite area. */
+function vertexNormals(device, mesh) {
+  const src = meshOnDevice(device, mesh, 'vertexNormals');
+  let normals = null;
+  try {
+    normals = smoothAndNormals(device, src.vertices, src.faces, src.V, src.F, null, true).normals;
+    return new Float32Array(src.V ? device.readBuffer(normals, 12 * src.V) : new ArrayBuffer(0));
+  } finally {
+    if (normals) normals.destroy();
+    if (src.own) { src.vertices.destroy(); src.faces.destroy(); }
+  }
+}
+/** What extractMesh does to a welded (and compacted) mesh, in its order: smoothMesh(mesh, smooth) when smooth is not null, then simplifyMesh(mesh, simplify,
+ *  origin) when simplify is not null, then normals = vertexNormals(mesh) when asked for; returned as typed arrays.  A typed-array mesh goes through the three
+ *  functions as they are.  A mesh of HipBuffers with numVertices and numFaces stays on the device throughout: its vertices buffer is replaced by the smoothed
+ *  one (the caller still destroys the object), and read(device, mesh) turns it into the object to return when it is not simplified. */
+function finishMesh(device, mesh, origin, smooth, simplify, normals, read) {
+  if (!(mesh.vertices instanceof HipBuffer)) {
+    if (smooth !== null) mesh = smoothMesh(device, mesh, smooth);
+    if (simplify !== null) mesh = simplifyMesh(device, mesh, simplify, { origin });
+    return normals ? Object.assign({}, mesh, { normals: vertexNormals(device, mesh) }) : mesh;
+  }
+  const V = mesh.numVertices, F = mesh.numFaces;
+  const normalsOf = (buf, n) => { try { return new Float32Array(n ? device.readBuffer(buf, 12 * n) : new ArrayBuffer(0)); } finally { buf.destroy(); } };
+  let stats = null, vn = null;
+  if (smooth !== null || (normals && simplify === null)) {
+    const r = smoothAndNormals(device, mesh.vertices, mesh.faces, V, F, smooth, normals && simplify === null);
+    stats = r.stats;
+    if (r.smoothed) { mesh.vertices.destroy(); mesh.vertices = r.smoothed; }
+    if (r.normals) vn = normalsOf(r.normals, V);
+  }
+  if (simplify === null) {
+    const out = read(device, mesh);
+    if (smooth !== null) out.stats = stats;
+    if (normals) out.normals = vn;
+    return out;
+  }
+  if (!normals) return simplifyMesh(device, mesh, simplify, { origin });
+  const simplified = simplifyMesh(device, mesh, simplify, { origin, asBuffers: true });
+  try {
+    const out = readSimplified(device, simplified, V);
+    out.normals = normalsOf(smoothAndNormals(device, simplified.vertices, simplified.faces, simplified.numVertices, simplified.numFaces, null, true).normals, simplified.numVertices);
+    return out;
+  } finally { destroyBuffers(simplified); }
 }
 
 // ---------------------------------------------------------------- mesh accuracy metrics (include/webdgs.h, DESIGN.md section 14; no reference counterpart)
@@ -1200,7 +1394,7 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, MeshWelder, weldTrianglesDevice, destroyBuffers, MeshSimplifier, simplifyMesh, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, MeshWelder, weldTrianglesDevice, destroyBuffers, MeshSimplifier, simplifyMesh, MeshAdjacency, meshAdjacency, smoothMesh, vertexNormals, finishMesh, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
   geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, grownTileEntries, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

@@ -852,6 +852,61 @@ int wdgs_mesh_simplifier_emit(wdgs_mesh_simplifier* simplifier, const void* vert
 int wdgs_mesh_simplifier_stats(const wdgs_mesh_simplifier* simplifier, uint32_t* clusters, uint32_t* invalid_faces, uint32_t* outside_faces, uint32_t* collapsed_faces,
                                uint32_t* duplicate_faces, uint32_t* vertices_out, uint32_t* faces_out);
 
+/* ---------------------------------------------------------------- Mesh adjacency, Taubin smoothing and vertex normals
+ *
+ * Input: an indexed mesh on the device, vertices f32[V][3], faces u32[F][3], 0 <= V < 2^31 and 0 <= 6 F < 2^32 (WDGS_E_INVALID otherwise).
+ * HALF-EDGES.  Face f with corners (c0, c1, c2) is VALID when all three are < V and pairwise different; an index >= V is never used as an address.  A valid face
+ * owns six slots s = 6 f + 2 j + d, j in {0, 1, 2}, d in {0, 1}: the forward slot d = 0 has the key c_j 2^32 | c_(j+1 mod 3), the backward slot d = 1 the key
+ * c_(j+1 mod 3) 2^32 | c_j.  The six slots of an invalid face have the key 2^64 - 1; invalid faces are counted and contribute nothing.
+ * ADJACENCY.  The distinct keys other than 2^64 - 1, ascending, are the directed edges; there are E of them, an even number.  neighbours u32[E] is their low
+ * words; row_start u32[V + 1] delimits each vertex's run, ascending by construction, row_start[V] = E.  The MULTIPLICITY of the directed edge (a, b) is the number
+ * of slots that carry its key, which is the number of valid faces on the undirected edge {a, b}: 1 is a BOUNDARY edge, 3 or more a NON-MANIFOLD one.  boundary
+ * u32[V] is 1 on both ends of every boundary edge and 0 elsewhere.  The statistics: directed_edges = E, edges = E / 2, boundary_edges and non_manifold_edges
+ * (undirected: counted where from < to), invalid_faces, boundary_vertices, isolated_vertices (empty rows), max_degree.  V - edges + (F - invalid_faces) is the
+ * Euler characteristic of a mesh whose every vertex is used.
+ * ONE SMOOTHING STEP step(p, w), all f32, each operation rounded once in the order written.  A vertex is copied bit for bit when it is PINNED (the flag
+ * WDGS_SMOOTH_PIN_BOUNDARY is set and boundary[v] = 1) or has a non-finite coordinate.  Otherwise s = (+0, +0, +0), n = 0; for u over the row of v in ascending
+ * order: skipped when p_u has a non-finite coordinate, else s += p_u per axis and n += 1.  n = 0: copied.  Else m = s / f32(n), d = m - p_v, r = p_v + w d (the
+ * product, then the sum); where r has a non-finite coordinate p_v is copied instead, so the set of finite vertices never changes between steps.
+ * SMOOTHING.  For `iterations` rounds: p <- step(p, lambda), then p <- step(p, mu); a step whose weight is exactly 0 is not run at all (mu = 0 is plain
+ * Laplacian smoothing), iterations = 0 copies the input.  The usual Taubin pair is lambda = 0.5, mu = -0.53.  lambda and mu finite and iterations <=
+ * WDGS_SMOOTH_MAX_ITERATIONS, else WDGS_E_INVALID.  Faces, colours and keys are untouched.
+ * VERTEX NORMALS, area-weighted.  g_f = (p_c1 - p_c0) x (p_c2 - p_c0), each component two products and one subtraction, always from the face's own corner order
+ * (every corner of a face adds the same bits).  For vertex v the slots whose key's high word is v are walked in SORTED SLOT ORDER -- ascending neighbour, then
+ * ascending slot: the sort is stable -- taking the forward slots only, so that each incident valid face appears once, at f = slot / 6; g_f is added per axis
+ * in that order, a g_f with a non-finite component skipped.  q = (sx sx + sy sy) + sz sz; the normal is s / sqrt(q) per axis, and (+0, +0, +0) when no face was
+ * added or q is zero or not finite.
+ * Every output is a function of the input alone, bit for bit, whatever the launch geometry or the order in which threads ran: one stable u64 sort of the 6 F
+ * keys (the welder's), and float sums taken by one thread in an order the sort fixes.  No reference counterpart. */
+#define WDGS_SMOOTH_PIN_BOUNDARY 1u
+#define WDGS_SMOOTH_MAX_ITERATIONS 1024u
+typedef struct wdgs_mesh_adjacency wdgs_mesh_adjacency;
+int wdgs_mesh_adjacency_create(wdgs_device* dev, wdgs_mesh_adjacency** out);
+int wdgs_mesh_adjacency_destroy(wdgs_mesh_adjacency* adjacency);
+/* Keys, the sort, the rows, the flags and the statistics, into arrays the object owns (it grows them as needed: 44 bytes per slot -- 264 per face, the sort's pairs among them -- and 32 per vertex, the
+ * smoothing steps' second position buffer f32[V][3] among them, so that smooth allocates nothing).  Waits ONCE, to read E and the statistics in one copy (a second
+ * time before it, only when its arrays have to grow), so it cannot be recorded (WDGS_E_STATE).  The faces are read again by normals and must stay as they are
+ * until then. */
+int wdgs_mesh_adjacency_count(wdgs_mesh_adjacency* adjacency, const void* faces_u32_dev, uint32_t num_faces, uint32_t num_vertices, uint32_t* directed_edges);
+/* Writes row_start_out u32[V + 1], neighbours_out u32[E] and boundary_out u32[V] of the last count, each nullable.  WDGS_E_STATE when no count precedes it;
+ * WDGS_E_CAPACITY when capacity_edges < E; nothing is written in either case.  Stream-ordered, no host wait, recordable. */
+int wdgs_mesh_adjacency_emit(wdgs_mesh_adjacency* adjacency, void* row_start_out_u32_dev, void* neighbours_out_u32_dev, void* boundary_out_u32_dev,
+                             uint32_t capacity_edges);
+/* vertices_out f32[V][3] = vertices_in smoothed over the last count's adjacency; flags: WDGS_SMOOTH_PIN_BOUNDARY or 0.  vertices_out may be vertices_in; the
+ * result lands in vertices_out whatever the number of steps run.  WDGS_E_STATE unless num_vertices is the last count's V.  Stream-ordered, no host wait, no
+ * allocation, recordable. */
+int wdgs_mesh_adjacency_smooth(wdgs_mesh_adjacency* adjacency, const void* vertices_in_f32_dev, void* vertices_out_f32_dev, uint32_t num_vertices, uint32_t iterations,
+                               float lambda, float mu, uint32_t flags);
+/* normals_out f32[V][3] of vertices f32[V][3] -- any positions: the smoothed ones, say -- over the last count's sorted slots.  faces must be the very faces
+ * that were counted, unchanged: WDGS_E_STATE unless the pointer and both counts are the last count's.  Stream-ordered, no host wait, recordable. */
+int wdgs_mesh_adjacency_normals(wdgs_mesh_adjacency* adjacency, const void* vertices_f32_dev, const void* faces_u32_dev, uint32_t num_vertices, uint32_t num_faces,
+                                void* normals_out_f32_dev);
+/* The last count's statistics; each pointer nullable.  WDGS_E_STATE when no count precedes it.  The kernels' event times are the device's
+ * (wdgs_device_get_kernel_times): adjacency_half_edge_keys, adjacency_fold, adjacency_edges, adjacency_rows, adjacency_emit, adjacency_copy,
+ * adjacency_smooth_step, adjacency_vertex_normals, and the weld's and the scan's.  No device work. */
+int wdgs_mesh_adjacency_stats(const wdgs_mesh_adjacency* adjacency, uint32_t* directed_edges, uint32_t* edges, uint32_t* boundary_edges, uint32_t* non_manifold_edges,
+                              uint32_t* invalid_faces, uint32_t* boundary_vertices, uint32_t* isolated_vertices, uint32_t* max_degree);
+
 #ifdef __cplusplus
 }
 #endif

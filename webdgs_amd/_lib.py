@@ -182,6 +182,13 @@ SIGNATURES = {
     "wdgs_mesh_simplifier_count": (_I, [_P, _P, _U, _P, _U, _P, C.POINTER(_F), _F, C.POINTER(_U), C.POINTER(_U)]),
     "wdgs_mesh_simplifier_emit": (_I, [_P, _P, _U, _P, _U, _P, _P, _P, _P, _P, _P, _P, _U, _U]),
     "wdgs_mesh_simplifier_stats": (_I, [_P] + [C.POINTER(_U)] * 7),
+    "wdgs_mesh_adjacency_create": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_mesh_adjacency_destroy": (_I, [_P]),
+    "wdgs_mesh_adjacency_count": (_I, [_P, _P, _U, _U, C.POINTER(_U)]),
+    "wdgs_mesh_adjacency_emit": (_I, [_P, _P, _P, _P, _U]),
+    "wdgs_mesh_adjacency_smooth": (_I, [_P, _P, _P, _U, _U, _F, _F, _U]),
+    "wdgs_mesh_adjacency_normals": (_I, [_P, _P, _P, _U, _U, _P]),
+    "wdgs_mesh_adjacency_stats": (_I, [_P] + [C.POINTER(_U)] * 8),
     "wdgs_point_index_create": (_I, [_P, _P, C.c_uint64, _F, C.POINTER(_P)]),
     "wdgs_point_index_destroy": (_I, [_P]),
     "wdgs_point_index_reserve_queries": (_I, [_P, _U]),

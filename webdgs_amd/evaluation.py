@@ -221,7 +221,7 @@ class Evaluator:
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
                     keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", simplify: Optional[float] = None,
-                    **volumeOptions) -> dict:
+                    smooth: Optional[int] = None, normals: bool = False, **volumeOptions) -> dict:
         """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
         ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result.
 
@@ -237,12 +237,17 @@ class Evaluator:
         merged into the surface first -- by ``ops.simplifyMesh`` on the grid of that cell size from the volume's ``lo``, and its dict is returned
         (``vertices``, ``faces``, ``colours``, ``keys``, ``faceMap``, ``vertexCluster``, ``stats``).  With ``weld="device"`` positions and faces stay
         on the device from the volume to the simplified mesh; with a component rule the colours alone are gathered through ``vertexMap`` on the
-        host, 4 bytes per vertex.  The same bytes as ``weld="host"`` either way.  ``None``: as before, and nothing more is launched."""
+        host, 4 bytes per vertex.  The same bytes as ``weld="host"`` either way.  ``None``: as before, and nothing more is launched.
+
+        ``smooth=iterations`` and ``normals=True``: ``ops.smoothMesh`` with its defaults after welding and component removal
+        and BEFORE ``simplify`` -- the fine mesh is denoised, then decimated -- with ``stats`` added; and ``normals f32[V,3]``, ``ops.vertexNormals`` of
+        the final mesh.  With ``weld="device"`` the positions stay on the device through both.  ``None`` and ``False``: as before, no new key and
+        nothing more launched."""
         if weld not in ("host", "device"):
             raise ValueError(f"extractMesh: weld must be 'host' or 'device', not {weld!r}")
-        if simplify is not None:
-            return self._extract_simplified(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld, simplify,
-                                            volumeOptions)
+        if simplify is not None or smooth is not None or normals:
+            return self._extract_finished(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld, simplify,
+                                          smooth, normals, volumeOptions)
         everything = ops._is_default_selection(keepLargest, minTriangles, minFraction)
         volume = ops.TSDFVolume.fromBounds(self.device, lo, hi, voxelSize, **volumeOptions)
         mesh = welded = None
@@ -272,9 +277,10 @@ class Evaluator:
         finally:
             ops.destroyBuffers(welded)
 
-    def _extract_simplified(self, lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld, simplify,
-                            volumeOptions) -> dict:
-        """``extractMesh`` with ``simplify`` set: volume, weld, component removal (when a rule is given), ``ops.simplifyMesh`` from the volume's origin."""
+    def _extract_finished(self, lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld, simplify, smooth, normals,
+                          volumeOptions) -> dict:
+        """``extractMesh`` with ``simplify``, ``smooth`` or ``normals`` set: volume, weld, component removal (when a rule is given), then
+        ``ops.finishMesh``: smoothing, simplification from the volume's origin, normals."""
         everything = ops._is_default_selection(keepLargest, minTriangles, minFraction)
         volume = ops.TSDFVolume.fromBounds(self.device, lo, hi, voxelSize, **volumeOptions)
         welded, kept = {}, {}
@@ -282,10 +288,10 @@ class Evaluator:
             self.fuseDepth(volume, viewIds, split, depthKind)
             origin = volume.origin
             if everything:
-                return volume.extractMesh(minWeight, weld=weld, simplify=simplify)
+                return volume.extractMesh(minWeight, weld=weld, simplify=simplify, smooth=smooth, normals=normals)
             if weld == "host":
                 mesh = ops.removeSmallComponents(self.device, volume.extractMesh(minWeight), keepLargest, minTriangles, minFraction)
-                return ops.simplifyMesh(self.device, mesh, simplify, origin)
+                return ops.finishMesh(self.device, mesh, origin, smooth, simplify, normals)
             tri = volume.extractTriangleBuffers(minWeight)
             try:
                 welded = ops.weldTrianglesDevice(self.device, tri, asBuffers=True)
@@ -293,11 +299,20 @@ class Evaluator:
                 ops.destroyBuffers(tri)
             kept = ops.removeSmallComponents(self.device, dict(vertices=welded["vertices"], faces=welded["faces"]), keepLargest, minTriangles, minFraction,
                                              asBuffers=True)
-            V, nv = welded["numVertices"], kept["numVertices"]
-            if welded["colours"] is not None:
+            V, nv, nf = welded["numVertices"], kept["numVertices"], kept["numFaces"]
+            if simplify is not None and welded["colours"] is not None:
                 gathered = welded["colours"].read(np.uint32, count=V)[kept["vertexMap"].read(np.uint32, count=nv)]
                 kept["colours"] = self.device.bufferFrom(np.ascontiguousarray(gathered), "compacted colours")
-            return ops.simplifyMesh(self.device, kept, simplify, origin)
+
+            def read(b) -> dict:   # what removeSmallComponents returns for the numpy mesh: colours and keys gathered through vertexMap
+                out = dict(vertices=b["vertices"].read(np.float32, count=3 * nv).reshape(nv, 3), faces=b["faces"].read(np.uint32, count=3 * nf).reshape(nf, 3),
+                           vertexMap=b["vertexMap"].read(np.uint32, count=nv), faceMap=b["faceMap"].read(np.uint32, count=nf), components=b["components"])
+                out["colours"] = None if welded["colours"] is None else np.ascontiguousarray(
+                    welded["colours"].read(np.uint8, count=4 * V).reshape(V, 4)[:, :3][out["vertexMap"]])
+                out["keys"] = np.ascontiguousarray(welded["keys"].read(np.uint64, count=V)[out["vertexMap"]])
+                return out
+
+            return ops.finishMesh(self.device, kept, origin, smooth, simplify, normals, read)
         finally:
             volume.destroy()
             ops.destroyBuffers(welded)

@@ -318,12 +318,20 @@ def backprojectDepth(depth: np.ndarray, camera) -> np.ndarray:
 # ----------------------------------------------------------------------------- triangle meshes (no reference counterpart)
 def meshPLYBytes(mesh: dict) -> bytes:
     """A mesh ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None)`` (``ops.TSDFVolume.extractMesh``) as a binary little-endian PLY: the
-    vertex element ``x y z`` float and, with colours, ``red green blue`` uchar; the face element ``vertex_indices`` as ``list uchar uint``."""
+    vertex element ``x y z`` float, with ``normals f32[V,3]`` in the mesh ``nx ny nz`` float, and with colours ``red green blue`` uchar; the face element
+    ``vertex_indices`` as ``list uchar uint``."""
     v = np.ascontiguousarray(mesh["vertices"], "<f4").reshape(-1, 3)
     f = np.ascontiguousarray(mesh["faces"], "<u4").reshape(-1, 3)
     c = mesh.get("colours")
+    n = mesh.get("normals")
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y", "property float z"]
+    if n is not None:
+        n = np.ascontiguousarray(n, "<f4").reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise ValueError(f"meshPLYBytes: {v.shape[0]} vertices, {n.shape[0]} normals")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
     if c is not None:
         c = np.ascontiguousarray(c, np.uint8).reshape(-1, 3)
         if c.shape[0] != v.shape[0]:
@@ -333,6 +341,8 @@ def meshPLYBytes(mesh: dict) -> bytes:
     header += [f"element face {f.shape[0]}", "property list uchar uint vertex_indices", "end_header"]
     vert = np.empty(v.shape[0], np.dtype(fields))
     vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if n is not None:
+        vert["nx"], vert["ny"], vert["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if c is not None:
         vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
     face = np.empty(f.shape[0], np.dtype([("n", "u1"), ("i", "<u4", (3,))]))
@@ -348,7 +358,8 @@ def saveMeshPLY(path: str, mesh: dict) -> None:
 
 
 def loadMeshPLY(path: str) -> dict:
-    """Reads a mesh PLY as ``saveMeshPLY`` writes it (triangles only): ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None)``."""
+    """Reads a mesh PLY as ``saveMeshPLY`` writes it (triangles only): ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None)``, and
+    ``normals f32[V,3]`` when the file has ``nx ny nz``."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.find(b"end_header\n")
@@ -367,11 +378,12 @@ def loadMeshPLY(path: str) -> dict:
             props[cur] = []
         elif w[:1] == ["property"]:
             props[cur].append(" ".join(w[1:]))
-    xyz, rgb = ["float x", "float y", "float z"], ["uchar red", "uchar green", "uchar blue"]
-    if list(elements) != ["vertex", "face"] or props["vertex"] not in (xyz, xyz + rgb) or props["face"] != ["list uchar uint vertex_indices"]:
+    xyz, nrm, rgb = ["float x", "float y", "float z"], ["float nx", "float ny", "float nz"], ["uchar red", "uchar green", "uchar blue"]
+    if (list(elements) != ["vertex", "face"] or props["vertex"] not in (xyz, xyz + rgb, xyz + nrm, xyz + nrm + rgb)
+            or props["face"] != ["list uchar uint vertex_indices"]):
         raise ValueError("loadMeshPLY: not a mesh as saveMeshPLY writes it")
-    coloured = props["vertex"] == xyz + rgb
-    vdt = np.dtype([("p", "<f4", (3,))] + ([("c", "u1", (3,))] if coloured else []))
+    coloured, with_normals = props["vertex"][-3:] == rgb, props["vertex"][3:6] == nrm
+    vdt = np.dtype([("p", "<f4", (3,))] + ([("n", "<f4", (3,))] if with_normals else []) + ([("c", "u1", (3,))] if coloured else []))
     fdt = np.dtype([("n", "u1"), ("i", "<u4", (3,))])
     nv, nf = elements["vertex"], elements["face"]
     if len(body) != nv * vdt.itemsize + nf * fdt.itemsize:
@@ -380,8 +392,11 @@ def loadMeshPLY(path: str) -> dict:
     face = np.frombuffer(body, fdt, count=nf, offset=nv * vdt.itemsize)
     if nf and not np.all(face["n"] == 3):
         raise ValueError("loadMeshPLY: only triangles are read")
-    return dict(vertices=np.ascontiguousarray(vert["p"], np.float32), faces=np.ascontiguousarray(face["i"], np.uint32),
-                colours=np.ascontiguousarray(vert["c"]) if coloured else None)
+    out = dict(vertices=np.ascontiguousarray(vert["p"], np.float32), faces=np.ascontiguousarray(face["i"], np.uint32),
+               colours=np.ascontiguousarray(vert["c"]) if coloured else None)
+    if with_normals:
+        out["normals"] = np.ascontiguousarray(vert["n"], np.float32)
+    return out
 
 
 # ----------------------------------------------------------------------------- point sets (no reference counterpart)

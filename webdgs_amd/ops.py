@@ -989,27 +989,36 @@ class TSDFVolume:
             raise
         return out
 
-    def extractMesh(self, minWeight: float = 1.0, weld: str = "host", simplify: Optional[float] = None) -> dict:
+    def extractMesh(self, minWeight: float = 1.0, weld: str = "host", simplify: Optional[float] = None, smooth: Optional[int] = None, normals: bool = False) -> dict:
         """The welded mesh: ``dict(vertices f32[V,3], faces u32[F,3], colours u8[V,3] | None, keys u64[V])``.  Vertices are the triangles' distinct edge
         keys in ascending order (equal keys carry equal position bits); triangles are kept as emitted, zero-area ones included.  ``weld="host"``: the
         triangles are read back and welded by ``weldTriangles``.  ``weld="device"``: they stay on the device and ``weldTrianglesDevice`` welds them
         there -- the same bytes, and only the V- and F-sized arrays of the result cross the bus.
 
+        ``smooth=iterations``: the welded mesh goes through ``smoothMesh`` with its defaults -- before it is simplified: the
+        fine mesh is denoised, then decimated -- and ``stats`` is added.  ``normals=True``: ``normals f32[V,3]``, ``vertexNormals`` of the final mesh,
+        is added.  With ``weld="device"`` the positions stay on the device through both.
+
         ``simplify=cellSize``: the welded mesh goes through ``simplifyMesh`` on the grid of that cell size from the volume's
         origin, and its dict is returned (``faceMap``, ``vertexCluster`` and ``stats`` added); with ``weld="device"`` the welded mesh stays on the
-        device until it is simplified.  ``None``: nothing more is launched."""
+        device until it is simplified.  With ``None``, ``None`` and ``False`` nothing more is launched."""
         if weld not in ("host", "device"):
             raise ValueError(f"extractMesh: weld must be 'host' or 'device', not {weld!r}")
+        plain = smooth is None and not normals
         if weld == "host":
             mesh = weldTriangles(self.extractTriangles(minWeight))
-            return mesh if simplify is None else simplifyMesh(self.device, mesh, simplify, self.origin)
+            if plain:
+                return mesh if simplify is None else simplifyMesh(self.device, mesh, simplify, self.origin)
+            return finishMesh(self.device, mesh, self.origin, smooth, simplify, normals)
         tri = self.extractTriangleBuffers(minWeight)
         welded = {}
         try:
-            if simplify is None:
+            if simplify is None and plain:
                 return weldTrianglesDevice(self.device, tri)
             welded = weldTrianglesDevice(self.device, tri, asBuffers=True)
-            return simplifyMesh(self.device, welded, simplify, self.origin)
+            if plain:
+                return simplifyMesh(self.device, welded, simplify, self.origin)
+            return finishMesh(self.device, welded, self.origin, smooth, simplify, normals, _read_welded)
         finally:
             destroyBuffers(tri)
             destroyBuffers(welded)
@@ -1034,6 +1043,14 @@ def weldTriangles(tri: dict) -> dict:
 
 
 # ----------------------------------------------------------------------------- welding on the device (no reference counterpart)
+def _read_welded(bufs: dict) -> dict:
+    """The welded mesh ``weldTrianglesDevice(asBuffers=True)`` hands out, read back: ``dict(vertices, faces, colours u8[V,3] | None, keys)``."""
+    V, F = bufs["numVertices"], bufs["numFaces"]
+    colours = None if bufs["colours"] is None else np.ascontiguousarray(bufs["colours"].read(np.uint8, count=4 * V).reshape(V, 4)[:, :3])
+    return dict(vertices=bufs["vertices"].read(np.float32, count=3 * V).reshape(V, 3), faces=bufs["faces"].read(np.uint32, count=3 * F).reshape(F, 3),
+                colours=colours, keys=bufs["keys"].read(np.uint64, count=V))
+
+
 def destroyBuffers(buffers: dict) -> None:
     """Destroys every ``HipBuffer`` among the values of ``buffers`` (the dicts ``extractTriangleBuffers`` and ``weldTrianglesDevice`` hand out)."""
     for b in buffers.values():
@@ -1131,9 +1148,7 @@ def weldTrianglesDevice(device: HipDevice, tri: dict, asBuffers: bool = False) -
             device.synchronize()   # (an uploaded soup is released below)
             result, out = dict(out, numVertices=V, numFaces=F), {}
             return result
-        colours = None if out["colours"] is None else np.ascontiguousarray(out["colours"].read(np.uint8, count=4 * V).reshape(V, 4)[:, :3])
-        return dict(vertices=out["vertices"].read(np.float32, count=3 * V).reshape(V, 3), faces=out["faces"].read(np.uint32, count=S).reshape(F, 3),
-                    colours=colours, keys=out["keys"].read(np.uint64, count=V))
+        return _read_welded(dict(out, numVertices=V, numFaces=F))
     finally:
         welder.destroy()
         destroyBuffers(out)
@@ -1208,6 +1223,15 @@ class MeshSimplifier:
         self.handle = None
 
 
+def _read_simplified(bufs: dict, V: int) -> dict:
+    """The mesh ``simplifyMesh(asBuffers=True)`` hands out for an input of ``V`` vertices, read back as ``simplifyMesh`` returns it."""
+    nv, nf = bufs["numVertices"], bufs["numFaces"]
+    colours = None if bufs["colours"] is None else np.ascontiguousarray(bufs["colours"].read(np.uint8, count=4 * nv).reshape(nv, 4)[:, :3])
+    return dict(vertices=bufs["vertices"].read(np.float32, count=3 * nv).reshape(nv, 3), faces=bufs["faces"].read(np.uint32, count=3 * nf).reshape(nf, 3),
+                colours=colours, keys=bufs["keys"].read(np.uint64, count=nv), faceMap=bufs["faceMap"].read(np.uint32, count=nf),
+                vertexCluster=bufs["vertexCluster"].read(np.uint32, count=V), stats=bufs["stats"])
+
+
 def simplifyMesh(device: HipDevice, mesh: dict, cellSize: float, origin=None, asBuffers: bool = False) -> dict:
     """``mesh`` simplified by vertex clustering on a grid of ``cellSize`` from ``origin``: the vertices of one cell become one vertex at the integer mean
     of their sub-cell offsets (colours alike), faces that collapse or repeat a lower face's cluster triple are dropped, unreferenced clusters are left
@@ -1260,15 +1284,251 @@ def simplifyMesh(device: HipDevice, mesh: dict, cellSize: float, origin=None, as
             device.synchronize()   # (an uploaded mesh is released below)
             result, out = dict(out, numVertices=nv, numFaces=nf, stats=stats), {}
             return result
-        colours = None if out["colours"] is None else np.ascontiguousarray(out["colours"].read(np.uint8, count=4 * nv).reshape(nv, 4)[:, :3])
-        return dict(vertices=out["vertices"].read(np.float32, count=3 * nv).reshape(nv, 3), faces=out["faces"].read(np.uint32, count=3 * nf).reshape(nf, 3),
-                    colours=colours, keys=out["keys"].read(np.uint64, count=nv), faceMap=out["faceMap"].read(np.uint32, count=nf),
-                    vertexCluster=out["vertexCluster"].read(np.uint32, count=V), stats=stats)
+        return _read_simplified(dict(out, numVertices=nv, numFaces=nf, stats=stats), V)
     finally:
         simplifier.destroy()
         destroyBuffers(out)
         if own:
             destroyBuffers(src)
+
+
+# ----------------------------------------------------------------------------- adjacency, smoothing and vertex normals (no reference counterpart)
+SMOOTH_PIN_BOUNDARY = 1   # WDGS_SMOOTH_PIN_BOUNDARY
+ADJACENCY_STATS = ("directedEdges", "edges", "boundaryEdges", "nonManifoldEdges", "invalidFaces", "boundaryVertices", "isolatedVertices", "maxDegree")
+
+
+class MeshAdjacency:
+    """The per-vertex neighbour lists of an indexed mesh on the device (``wdgs_mesh_adjacency``) and what stands on them: ``count`` sorts the faces'
+    directed half-edge keys (the welder's stable u64 sort over ``6 F`` slots), delimits the rows, flags the boundary and returns ``E`` (one wait);
+    ``emit`` writes ``rowStart``, ``neighbours`` and ``boundary``; ``smooth`` runs Taubin's lambda | mu steps and ``normals`` the area-weighted vertex
+    normals over that count, both stream-ordered.  ``meshAdjacency``, ``smoothMesh`` and ``vertexNormals`` are the one-call forms; include/webdgs.h
+    states the definition."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        self.numEdges = self.numVertices = self.numFaces = 0
+        h = C.c_void_p()
+        check(device.lib.wdgs_mesh_adjacency_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def count(self, faces: Optional[HipBuffer], numFaces: int, numVertices: int) -> int:
+        """``E``, the number of directed edges of ``faces`` u32[numFaces][3] over ``numVertices`` vertices (keys, sort, rows, flags, statistics; waits
+        once).  The faces must stay as they are while ``normals`` may still be called."""
+        nf, nv = int(numFaces), int(numVertices)
+        if not (0 <= nv < 2 ** 32 and 0 <= nf < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshAdjacency.count: bad counts {numVertices}, {numFaces}")
+        if 6 * nf < 2 ** 32 and faces is not None and faces.size < 12 * nf:
+            raise ValueError("MeshAdjacency.count: buffer too small for the faces")
+        e = C.c_uint32(0)
+        check(self.device.lib.wdgs_mesh_adjacency_count(self.handle, faces.ptr if faces is not None else None, nf, nv, C.byref(e)))
+        self.numEdges, self.numVertices, self.numFaces = int(e.value), nv, nf
+        return self.numEdges
+
+    def emit(self, rowStart: Optional[HipBuffer] = None, neighbours: Optional[HipBuffer] = None, boundary: Optional[HipBuffer] = None,
+             capacityEdges: Optional[int] = None) -> None:
+        """Writes ``rowStart`` u32[V + 1], ``neighbours`` u32[E] and ``boundary`` u32[V] of the count before it, each optional (``StateError`` without a
+        count; ``CapacityError``, with nothing written, when there is room for fewer than E edges).  Stream-ordered: it waits for nothing and records."""
+        cap = (neighbours.size // 4 if neighbours is not None else 2 ** 32 - 1) if capacityEdges is None else int(capacityEdges)
+        if neighbours is not None and 4 * cap > neighbours.size:
+            raise ValueError("MeshAdjacency.emit: the capacity exceeds the buffer")
+        if (rowStart is not None and rowStart.size < 4 * (self.numVertices + 1)) or (boundary is not None and boundary.size < 4 * self.numVertices):
+            raise ValueError("MeshAdjacency.emit: buffers too small for the vertices")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_adjacency_emit(self.handle, ptr(rowStart), ptr(neighbours), ptr(boundary), cap))
+
+    def smooth(self, verticesIn: Optional[HipBuffer], verticesOut: Optional[HipBuffer], numVertices: int, iterations: int = 10, lam: float = 0.5, mu: float = -0.53,
+               pinBoundary: bool = True) -> None:
+        """``verticesOut`` f32[V][3] = ``verticesIn`` after ``iterations`` rounds of ``step(lam)`` then ``step(mu)`` over the counted adjacency (a weight of
+        exactly 0 skips its step; ``verticesOut`` may be ``verticesIn``).  ``StateError`` unless ``numVertices`` is the count's.  Stream-ordered: it
+        waits for nothing, allocates nothing and records."""
+        nv, it = int(numVertices), int(iterations)
+        if not (0 <= nv < 2 ** 32 and 0 <= it < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshAdjacency.smooth: bad counts {numVertices}, {iterations}")
+        for b in (verticesIn, verticesOut):
+            if b is not None and nv == self.numVertices and b.size < 12 * nv:
+                raise ValueError("MeshAdjacency.smooth: buffer too small for the vertices")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_adjacency_smooth(self.handle, ptr(verticesIn), ptr(verticesOut), nv, it, float(lam), float(mu),
+                                                         SMOOTH_PIN_BOUNDARY if pinBoundary else 0))
+
+    def normals(self, vertices: Optional[HipBuffer], faces: Optional[HipBuffer], numVertices: int, numFaces: int, normalsOut: Optional[HipBuffer]) -> None:
+        """``normalsOut`` f32[V][3]: the area-weighted normals of ``vertices`` f32[V][3] over the counted faces -- ``faces`` must be the buffer that was
+        counted, unchanged (``StateError`` otherwise).  Stream-ordered: it waits for nothing and records."""
+        nv = int(numVertices)
+        for b in (vertices, normalsOut):
+            if b is not None and nv == self.numVertices and b.size < 12 * nv:
+                raise ValueError("MeshAdjacency.normals: buffer too small for the vertices")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_adjacency_normals(self.handle, ptr(vertices), ptr(faces), nv, int(numFaces), ptr(normalsOut)))
+
+    def stats(self) -> dict:
+        """The last count: ``dict(directedEdges, edges, boundaryEdges, nonManifoldEdges, invalidFaces, boundaryVertices, isolatedVertices, maxDegree)``.
+        The kernels' event times are ``HipDevice.kernelTimes``' (``adjacency_*``, ``weld_*`` and the scan's)."""
+        v = [C.c_uint32(0) for _ in ADJACENCY_STATS]
+        check(self.device.lib.wdgs_mesh_adjacency_stats(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(ADJACENCY_STATS, (int(x.value) for x in v)))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_mesh_adjacency_destroy(self.handle)
+        self.handle = None
+
+
+def _mesh_on_device(device: HipDevice, mesh: dict, what: str) -> tuple:
+    """``(vertices, faces, V, F, own)``: the mesh's positions and faces as ``HipBuffer`` -- uploaded from numpy (``own``: the caller destroys them) or
+    taken as they are from a dict of buffers with ``numVertices`` / ``numFaces`` or whole buffers."""
+    if not isinstance(mesh["vertices"], HipBuffer):
+        v = np.ascontiguousarray(mesh["vertices"], np.float32)
+        f = np.ascontiguousarray(mesh["faces"], np.uint32)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"{what}: expected vertices [V, 3] and faces [F, 3], got {v.shape} and {f.shape}")
+        return device.bufferFrom(v, f"{what}: vertices"), device.bufferFrom(f, f"{what}: faces"), v.shape[0], f.shape[0], True
+    if not isinstance(mesh["faces"], HipBuffer):
+        raise ValueError(f"{what}: vertices on the device need faces on the device")
+    V = int(mesh["numVertices"]) if "numVertices" in mesh else mesh["vertices"].size // 12
+    F = int(mesh["numFaces"]) if "numFaces" in mesh else mesh["faces"].size // 12
+    return mesh["vertices"], mesh["faces"], V, F, False
+
+
+def meshAdjacency(device: HipDevice, mesh: dict) -> dict:
+    """The neighbour lists of ``mesh`` (numpy, or a dict of ``HipBuffer`` as ``weldTrianglesDevice(asBuffers=True)`` hands out; only ``faces`` and the
+    vertex count matter): ``dict(rowStart u32[V+1], neighbours u32[E], boundary u32[V], stats)`` -- vertex ``v`` neighbours
+    ``neighbours[rowStart[v]:rowStart[v+1]]``, ascending; ``boundary`` is 1 on both ends of every edge that one face alone holds; ``stats`` is
+    ``MeshAdjacency.stats``'s dict.  A function of the faces alone, bit for bit (include/webdgs.h states it)."""
+    vertices, faces, V, F, own = _mesh_on_device(device, mesh, "meshAdjacency")
+    adjacency = MeshAdjacency(device)
+    out = {}
+    try:
+        E = adjacency.count(faces, F, V)
+        out = dict(rowStart=device.createBuffer(4 * (V + 1), "adjacency row starts"), neighbours=device.createBuffer(4 * E, "adjacency neighbours"),
+                   boundary=device.createBuffer(4 * V, "adjacency boundary flags"))
+        adjacency.emit(out["rowStart"], out["neighbours"], out["boundary"], E)
+        return dict(rowStart=out["rowStart"].read(np.uint32, count=V + 1), neighbours=out["neighbours"].read(np.uint32, count=E),
+                    boundary=out["boundary"].read(np.uint32, count=V), stats=adjacency.stats())
+    finally:
+        adjacency.destroy()
+        destroyBuffers(out)
+        if own:
+            vertices.destroy()
+            faces.destroy()
+
+
+def _smooth_and_normals(device: HipDevice, vertices: HipBuffer, faces: HipBuffer, V: int, F: int, smooth, normals: bool, lam: float = 0.5, mu: float = -0.53,
+                        pinBoundary: bool = True) -> tuple:
+    """``(smoothed | None, normals | None, stats)`` of a mesh on the device through one ``MeshAdjacency``: a new buffer of the positions after ``smooth``
+    iterations (``None``: not wanted) and a new buffer of the normals of the smoothed -- else the given -- positions.  The caller destroys both."""
+    adjacency = MeshAdjacency(device)
+    out = {}
+    try:
+        adjacency.count(faces, F, V)
+        if smooth is not None:
+            out["smoothed"] = device.createBuffer(12 * V, "smoothed vertices")
+            adjacency.smooth(vertices, out["smoothed"], V, smooth, lam, mu, pinBoundary)
+        if normals:
+            out["normals"] = device.createBuffer(12 * V, "vertex normals")
+            adjacency.normals(out.get("smoothed", vertices), faces, V, F, out["normals"])
+        stats = adjacency.stats()
+        device.synchronize()   # (the object's arrays are released below)
+        result, out = (out.get("smoothed"), out.get("normals"), stats), {}
+        return result
+    finally:
+        adjacency.destroy()
+        destroyBuffers(out)
+
+
+def smoothMesh(device: HipDevice, mesh: dict, iterations: int = 10, lam: float = 0.5, mu: float = -0.53, pinBoundary: bool = True, asBuffers: bool = False) -> dict:
+    """``mesh`` after ``iterations`` rounds of Taubin's lambda | mu smoothing (``mu = 0``: plain Laplacian smoothing): every vertex moves towards, then
+    away from, the f32 mean of its neighbours, summed in ascending neighbour order; with ``pinBoundary`` the ends of boundary edges stay where they are.
+    ``mesh`` is the dict ``extractMesh`` / ``loaders.loadMeshPLY`` return, or a dict of ``HipBuffer``s as ``weldTrianglesDevice(asBuffers=True)`` and
+    ``simplifyMesh(asBuffers=True)`` hand out (left as it is).  Returns the mesh's dict with new ``vertices``, every other entry passed through, and
+    ``stats`` (``MeshAdjacency.stats``) added; a function of its arguments alone, bit for bit (include/webdgs.h states it).  ``asBuffers``: ``vertices``
+    is a new ``HipBuffer`` f32[V][3] the caller destroys; a numpy mesh's ``faces`` are then handed out as a buffer too, with ``numVertices`` and
+    ``numFaces`` added."""
+    vertices, faces, V, F, own = _mesh_on_device(device, mesh, "smoothMesh")
+    smoothed = None
+    try:
+        smoothed, _, stats = _smooth_and_normals(device, vertices, faces, V, F, iterations, False, lam, mu, pinBoundary)
+        if asBuffers:
+            result = dict(mesh, vertices=smoothed, stats=stats, numVertices=V, numFaces=F)
+            if own:
+                result["faces"], faces = faces, None
+            smoothed = None
+            return result
+        return dict(mesh, vertices=smoothed.read(np.float32, count=3 * V).reshape(V, 3), stats=stats)
+    finally:
+        if smoothed is not None:
+            smoothed.destroy()
+        if own:
+            vertices.destroy()
+            if faces is not None:
+                faces.destroy()
+
+
+def vertexNormals(device: HipDevice, mesh: dict) -> np.ndarray:
+    """The area-weighted unit normals ``f32[V,3]`` of ``mesh`` (numpy or a dict of ``HipBuffer``s): per vertex the sum of its faces' cross products in the
+    order the half-edge sort fixes, normalised; ``(0, 0, 0)`` for a vertex without a face of non-zero finite area.  A function of the mesh alone, bit for
+    bit (include/webdgs.h states it)."""
+    vertices, faces, V, F, own = _mesh_on_device(device, mesh, "vertexNormals")
+    normals = None
+    try:
+        _, normals, _ = _smooth_and_normals(device, vertices, faces, V, F, None, True)
+        return normals.read(np.float32, count=3 * V).reshape(V, 3)
+    finally:
+        if normals is not None:
+            normals.destroy()
+        if own:
+            vertices.destroy()
+            faces.destroy()
+
+
+def finishMesh(device: HipDevice, mesh: dict, origin, smooth: Optional[int], simplify: Optional[float], normals: bool, read=None) -> dict:
+    """What ``extractMesh`` does to a welded (and compacted) mesh, in its order: ``smoothMesh(mesh, smooth)`` when ``smooth`` is not ``None``, then
+    ``simplifyMesh(mesh, simplify, origin)`` when ``simplify`` is not ``None``, then ``normals = vertexNormals(mesh)`` when asked for; returned as numpy.
+    A numpy ``mesh`` goes through the three functions as they are.  A mesh of ``HipBuffer``s with ``numVertices`` and ``numFaces`` stays on the device
+    throughout: its ``vertices`` buffer is replaced by the smoothed one (the caller still destroys the dict), and ``read(mesh)`` turns it into the numpy
+    dict to return when it is not simplified."""
+    if not isinstance(mesh["vertices"], HipBuffer):
+        if smooth is not None:
+            mesh = smoothMesh(device, mesh, smooth)
+        if simplify is not None:
+            mesh = simplifyMesh(device, mesh, simplify, origin)
+        return dict(mesh, normals=vertexNormals(device, mesh)) if normals else mesh
+    V, F = int(mesh["numVertices"]), int(mesh["numFaces"])
+
+    def normals_of(buf) -> np.ndarray:
+        try:
+            return buf.read(np.float32, count=buf.size // 4).reshape(-1, 3)
+        finally:
+            buf.destroy()
+
+    stats = vn = None
+    if smooth is not None or (normals and simplify is None):
+        smoothed, nbuf, stats = _smooth_and_normals(device, mesh["vertices"], mesh["faces"], V, F, smooth, normals and simplify is None)
+        if smoothed is not None:
+            mesh["vertices"].destroy()
+            mesh["vertices"] = smoothed
+        if nbuf is not None:
+            vn = normals_of(nbuf)
+    if simplify is None:
+        out = read(mesh)
+        if smooth is not None:
+            out["stats"] = stats
+        if normals:
+            out["normals"] = vn
+        return out
+    if not normals:
+        return simplifyMesh(device, mesh, simplify, origin)
+    simplified = simplifyMesh(device, mesh, simplify, origin, asBuffers=True)
+    try:
+        out = _read_simplified(simplified, V)
+        _, nbuf, _ = _smooth_and_normals(device, simplified["vertices"], simplified["faces"], simplified["numVertices"], simplified["numFaces"], None, True)
+        out["normals"] = normals_of(nbuf)
+        return out
+    finally:
+        destroyBuffers(simplified)
 
 
 # ----------------------------------------------------------------------------- mesh accuracy metrics (DESIGN.md section 14; no reference counterpart)

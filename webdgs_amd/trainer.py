@@ -873,11 +873,12 @@ class Trainer:
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
                     keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", simplify: Optional[float] = None,
-                    **volumeOptions) -> dict:
-        """``Evaluator.extractMesh``: the current model as a triangle mesh of the box ``[lo, hi]``, welded on the host or (``weld="device"``) on the device
-        and, with ``simplify=cellSize``, simplified by vertex clustering at the end."""
+                    smooth: Optional[int] = None, normals: bool = False, **volumeOptions) -> dict:
+        """``Evaluator.extractMesh``: the current model as a triangle mesh of the box ``[lo, hi]``, welded on the host or (``weld="device"``) on the device;
+        with ``smooth=iterations`` Taubin-smoothed, with ``simplify=cellSize`` then simplified by vertex clustering, with ``normals=True`` given the
+        final mesh's vertex normals."""
         return self.evaluator.extractMesh(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld=weld,
-                                          simplify=simplify, **volumeOptions)
+                                          simplify=simplify, smooth=smooth, normals=normals, **volumeOptions)
 
     def evaluateGeometry(self, reference, lo, hi, voxelSize: float, maxDistance: float, threshold: float, density: Optional[float] = None, seed: int = 0,
                          keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **extractMeshOptions) -> dict:
