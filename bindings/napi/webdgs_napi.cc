@@ -578,6 +578,41 @@ static napi_value meshAdjacencyStats(napi_env env, napi_callback_info info) {
     for (uint32_t i = 0; i < 8; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
     return a;
 }
+// Mesh rasterization and depth agreement (include/webdgs.h: wdgs_mesh_rasterizer_*, wdgs_depth_agreement; no reference counterpart)
+static napi_value meshRasterizerCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_mesh_rasterizer* r = nullptr;
+    WDGS_OK_OR_THROW(wdgs_mesh_rasterizer_create((wdgs_device*)get_ptr(env, argv[0]), &r));
+    return make_ptr(env, r);
+}
+static napi_value meshRasterizerDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_mesh_rasterizer_destroy((wdgs_mesh_rasterizer*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value meshRasterizerEncode(napi_env env, napi_callback_info info) {
+    // (rasterizer, verticesPtr | null, numVertices, facesPtr | null, numFaces, coloursPtr | null, cameraPtr, width, height, near, cull, depthPtr | null, facePtr | null,
+    //  colourPtr | null, normalPtr | null)
+    ARGS(15);
+    WDGS_OK_OR_THROW(wdgs_mesh_rasterizer_encode((wdgs_mesh_rasterizer*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_ptr(env, argv[3]),
+                                                 get_u32(env, argv[4]), get_ptr(env, argv[5]), get_ptr(env, argv[6]), get_u32(env, argv[7]), get_u32(env, argv[8]),
+                                                 (float)get_f64(env, argv[9]), get_u32(env, argv[10]), get_ptr(env, argv[11]), get_ptr(env, argv[12]), get_ptr(env, argv[13]),
+                                                 get_ptr(env, argv[14])));
+    return js_undefined(env);
+}
+static napi_value meshRasterizerStats(napi_env env, napi_callback_info info) {
+    // (rasterizer) -> [invalidFaces, clippedFaces, degenerateFaces, culledFaces, emptyFaces, rasterizedFaces, coveredPixels, viewportMismatch]
+    ARGS(1);
+    uint32_t r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_rasterizer_stats((wdgs_mesh_rasterizer*)get_ptr(env, argv[0]), &r[0], &r[1], &r[2], &r[3], &r[4], &r[5], &r[6], &r[7]));
+    napi_value a; napi_create_array_with_length(env, 8, &a);
+    for (uint32_t i = 0; i < 8; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
+    return a;
+}
+static napi_value depthAgreement(napi_env env, napi_callback_info info) {
+    // (device, aPtr, bPtr, bWeightSumPtr | null, minWeightSum, width, height, maxDifference, threshold, outPtr): u64 {both, onlyA, onlyB, within, sum_q}
+    ARGS(10);
+    WDGS_OK_OR_THROW(wdgs_depth_agreement((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_ptr(env, argv[3]),
+                                          (float)get_f64(env, argv[4]), get_u32(env, argv[5]), get_u32(env, argv[6]), (float)get_f64(env, argv[7]),
+                                          (float)get_f64(env, argv[8]), get_ptr(env, argv[9])));
+    return js_undefined(env);
+}
 static napi_value pointIndexCreate(napi_env env, napi_callback_info info) {  // (device, pointsPtr, numPoints, cellSize: 0 = chosen by the first query) -> handle
     ARGS(4);
     wdgs_point_index* ix = nullptr;
@@ -1256,6 +1291,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(meshSimplifierCreate); EXPORT_FN(meshSimplifierDestroy); EXPORT_FN(meshSimplifierCount); EXPORT_FN(meshSimplifierEmit); EXPORT_FN(meshSimplifierStats);
     EXPORT_FN(meshAdjacencyCreate); EXPORT_FN(meshAdjacencyDestroy); EXPORT_FN(meshAdjacencyCount); EXPORT_FN(meshAdjacencyEmit); EXPORT_FN(meshAdjacencySmooth);
     EXPORT_FN(meshAdjacencyNormals); EXPORT_FN(meshAdjacencyStats);
+    EXPORT_FN(meshRasterizerCreate); EXPORT_FN(meshRasterizerDestroy); EXPORT_FN(meshRasterizerEncode); EXPORT_FN(meshRasterizerStats); EXPORT_FN(depthAgreement);
     EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
     EXPORT_FN(pointDistanceStats);
     EXPORT_FN(pointIndexBounds); EXPORT_FN(pointIndexKNearest); EXPORT_FN(pointCloudPositions); EXPORT_FN(pointCloudNeighbourScales);

@@ -19,6 +19,8 @@ export class Evaluator {
   setEvaluationViews(cameras: (TrainingView | CameraData)[], images: (TrainingImage | LoadedImage)[]): void;
   evaluate(viewIds?: number[] | null, split?: Split): EvaluationResult;
   normalConsistency(viewIds?: number[] | null, split?: Split, depthKind?: DepthKind): NormalConsistencyResult;
+  meshDepthAgreement(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: import('./trainer').MeshDepthAgreementOptions):
+    import('./trainer').MeshDepthAgreementResult;
   fuseDepth(volume: TSDFVolume, viewIds?: number[] | null, split?: Split, depthKind?: DepthKind): number[];
   extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, options?: MeshOptions): TriangleMesh | CompactedMesh | SimplifiedMesh;
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,

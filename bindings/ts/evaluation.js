@@ -174,6 +174,51 @@ class Evaluator {
       mean: total(sum_a) ? total(sum_e) / total(sum_a) : NaN, ms: Date.now() - t0 };
   }
 
+  // ---------------------------------------------------------------- a mesh against the model's own depth maps (DESIGN.md section 20)
+  /** How far `mesh` (hip.rasterizeMesh's: typed arrays or an object of HipBuffers) agrees with the model it came from, view by view, with no reference
+   *  geometry: per view the model's depthKind depth map (b; present where its weight sum is at least minWeightSum) against the mesh rasterized under the same
+   *  camera (a), through hip.encodeDepthAgreement.  options: { viewIds, split = 'eval', depthKind = 'median', maxDifference = 1, threshold = 0.05,
+   *  minWeightSum = 0.5, near, cull }.  Returns { iteration, views, both, onlyA, onlyB, within, sum_q, mean (one entry per view), total, ms }: onlyB pixels are
+   *  where the model sees surface and the mesh has a hole.  Rendered through evaluate's passes with its isolation.  Same results as the Python host's. */
+  meshDepthAgreement(mesh, options) {
+    const o = options || {}, split = o.split || 'eval', depthKind = o.depthKind || 'median';
+    const maxDifference = o.maxDifference === undefined ? 1.0 : o.maxDifference, threshold = o.threshold === undefined ? 0.05 : o.threshold;
+    const minWeightSum = o.minWeightSum === undefined ? 0.5 : o.minWeightSum;
+    if (depthKind !== 'median' && depthKind !== 'expected') throw new Error(`meshDepthAgreement: depthKind must be 'median' or 'expected', not ${depthKind}`);
+    const { imgs, bufs, ids } = this.views('meshDepthAgreement', o.viewIds, split);
+    const t0 = Date.now();
+    this.drain();
+    const dev = this.device, n = ids.length, slots = Math.max(1, n);
+    const src = hip.meshOnDevice(dev, mesh, 'meshDepthAgreement');
+    const out = dev.createBuffer({ size: 40 * slots, label: 'depth agreement sums' });
+    const scratch = dev.createBuffer({ size: 4 * Math.max(1, ...ids.map((v) => imgs[v].width * imgs[v].height)), label: 'mesh depth' });
+    const rasterizer = new hip.MeshRasterizer(dev);
+    let raw;
+    try {
+      if (n) {   // (grown once, to the largest view, in front of the loop)
+        const big = ids.reduce((a, v) => (imgs[v].width * imgs[v].height > imgs[a].width * imgs[a].height ? v : a), ids[0]);
+        rasterizer.encode(src.vertices, src.V, src.faces, src.F, null, bufs[ids[0]], imgs[big].width, imgs[big].height, { near: o.near, cull: o.cull, depth: scratch });
+      }
+      this.renderViews(ids, imgs, bufs, (i, v, s, w, h) => {
+        s.rasterizer.encodeDepth(null, [depthKind, 'weight_sum']);
+        rasterizer.encode(src.vertices, src.V, src.faces, src.F, null, bufs[v], w, h, { near: o.near, cull: o.cull, depth: scratch });
+        hip.encodeDepthAgreement(dev, scratch, s.rasterizer.getDepthTextureView(depthKind), w, h, maxDifference, threshold, dev.view(out.ptr + BigInt(40 * i), 40),
+          { bWeightSum: s.rasterizer.getDepthTextureView('weight_sum'), minWeightSum });
+      }, null, 'meshDepthAgreement');
+      raw = n ? dev.readBuffer(out, 40 * slots) : new ArrayBuffer(40);
+    } finally {
+      rasterizer.destroy(); scratch.destroy(); out.destroy();
+      if (src.own) { src.vertices.destroy(); src.faces.destroy(); }
+    }
+    const sums = [...new BigUint64Array(raw, 0, 5 * n)].map(Number);
+    const per = ids.map((_, i) => hip.depthAgreementResult(sums.slice(5 * i, 5 * i + 5), maxDifference));
+    const result = { iteration: this.trainer.iteration, views: ids };
+    for (const k of ['both', 'onlyA', 'onlyB', 'within', 'sum_q', 'mean']) result[k] = per.map((p) => p[k]);
+    result.total = hip.depthAgreementResult([0, 1, 2, 3, 4].map((k) => ids.reduce((a, _, i) => a + sums[5 * i + k], 0)), maxDifference);
+    result.ms = Date.now() - t0;
+    return result;
+  }
+
   // ---------------------------------------------------------------- TSDF fusion and mesh extraction (DESIGN.md section 13)
   /** Fuses the current model's depth maps into `volume` (hip.TSDFVolume): for each view in the order given, the forward pass, rasterize,
    *  encodeDepth([depthKind, 'weight_sum']) and volume.integrate with the weight sum and the rasterizer's output texture as colour (where the volume

@@ -67,6 +67,9 @@ export class Trainer {
   /** Agreement of the composited normals with the normals of the model's own depth map, per view and weight-averaged over all (1 - cos: a surface
    *  scores near 0); rendered through evaluate's passes, training untouched.  No reference counterpart. */
   normalConsistency(viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): NormalConsistencyResult;
+  /** A mesh rasterized under each view against the model's own depth map of that view: per-view and summed counts of the pixels where both, the mesh alone
+   *  (onlyA) and the model alone (onlyB: a hole in the mesh) have a depth, and the mean absolute difference; training untouched.  No reference counterpart. */
+  meshDepthAgreement(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: MeshDepthAgreementOptions): MeshDepthAgreementResult;
   /** Fuses the current model's depth maps (and the rendered colour) into a TSDFVolume, view by view in the order given; rendered through evaluate's
    *  passes, training untouched.  Returns the view list.  No reference counterpart. */
   fuseDepth(volume: import('./webdgs_hip').TSDFVolume, viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): number[];
@@ -106,6 +109,14 @@ export class Trainer {
 }
 export interface EvaluationResult {
   iteration: number; views: number[]; psnr: number[]; ssim: number[]; sse: number[]; mean_psnr: number; mean_ssim: number; ms: number;
+}
+export interface MeshDepthAgreementOptions {
+  viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected'; maxDifference?: number; threshold?: number; minWeightSum?: number;
+  near?: number; cull?: 'none' | 'back' | 'front';
+}
+export interface MeshDepthAgreementResult {
+  iteration: number; views: number[]; both: number[]; onlyA: number[]; onlyB: number[]; within: number[]; sum_q: number[]; mean: number[];
+  total: import('./webdgs_hip').DepthAgreement; ms: number;
 }
 export interface NormalConsistencyResult {
   iteration: number; views: number[]; value: number[]; pixels: number[]; sum_e: number[]; sum_a: number[]; mean: number; ms: number;

@@ -706,6 +706,8 @@ class Trainer {
   evaluate(viewIds, split) { return this.evaluator.evaluate(viewIds, split); }
   /** Evaluator.normalConsistency: agreement of the composited normals with the normals of the model's own depth map. */
   normalConsistency(viewIds, split, depthKind) { return this.evaluator.normalConsistency(viewIds, split, depthKind); }
+  /** Evaluator.meshDepthAgreement: a mesh rasterized under each view against the model's own depth map of that view. */
+  meshDepthAgreement(mesh, options) { return this.evaluator.meshDepthAgreement(mesh, options); }
   /** Evaluator.fuseDepth: fuses the current model's depth maps into `volume`. */
   fuseDepth(volume, viewIds, split, depthKind) { return this.evaluator.fuseDepth(volume, viewIds, split, depthKind); }
   /** Evaluator.evaluateGeometry: the extracted mesh scored against a reference point set. */

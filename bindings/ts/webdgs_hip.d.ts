@@ -325,7 +325,7 @@ export class MeshAdjacency {
   stats(): AdjacencyStats;
   destroy(): void;
 }
-type MeshArrays = { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null };
+export type MeshArrays = { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null };
 /** rowStart[V + 1], neighbours[E] (ascending within a row) and boundary[V] of the mesh's faces; a function of the faces alone, bit for bit. */
 export function meshAdjacency(device: HipDevice, mesh: MeshArrays | MeshBuffers): { rowStart: Uint32Array; neighbours: Uint32Array; boundary: Uint32Array; stats: AdjacencyStats };
 /** `mesh` after `iterations` (default 10) rounds of Taubin smoothing: its object with new vertices and stats added; bit for bit a function of its arguments. */
@@ -340,6 +340,42 @@ export function vertexNormals(device: HipDevice, mesh: MeshArrays | MeshBuffers)
 /** extractMesh's last stages in their order -- smoothMesh, simplifyMesh from `origin`, vertexNormals -- each only when asked for (null, null, false: none). */
 export function finishMesh(device: HipDevice, mesh: MeshArrays | MeshBuffers, origin: ArrayLike<number>, smooth: number | null, simplify: number | null, normals: boolean,
                            read?: (device: HipDevice, mesh: MeshBuffers) => object): any;
+/** The face classes of a MeshRasterizer's last encode -- every face is in exactly one -- the pixels some face covers, and whether the camera block was of another
+ *  image size (nothing is drawn then). */
+export interface RasterStats { invalidFaces: number; clippedFaces: number; degenerateFaces: number; culledFaces: number; emptyFaces: number; rasterizedFaces: number;
+                               coveredPixels: number; viewportMismatch: number }
+export type CullMode = 'none' | 'back' | 'front';
+export type RasterOutput = 'depth' | 'face' | 'colour' | 'normal';
+export const CULL_MODES: { none: 0; back: 1; front: 2 };
+/** A face whose bounding box exceeds this many pixels on either axis is drawn by the kernel of 8 x 8 blocks (WDGS_MESH_RASTER_LARGE_FACE_PIXELS). */
+export const MESH_RASTER_LARGE_FACE_PIXELS: number;
+/** The default near depth: the depth below which the forward pass drops a Gaussian. */
+export const MESH_RASTER_NEAR: number;
+export const NO_FACE: 0xFFFFFFFF;
+/** A z-buffered triangle rasterizer under the library's camera block (wdgs_mesh_rasterizer): depth f32, face u32, colour rgba8 and normal rgba32f images of an
+ *  indexed mesh on the device, each byte a function of the input alone.  No clipping: a face with a vertex nearer than `near` is dropped.  No reference counterpart. */
+export class MeshRasterizer {
+  constructor(device: HipDevice);
+  encode(vertices: HipBuffer | null, numVertices: number, faces: HipBuffer | null, numFaces: number, colours: HipBuffer | null, camera: HipBuffer, width: number, height: number,
+         options?: { near?: number | null; cull?: CullMode; depth?: HipBuffer | null; face?: HipBuffer | null; colour?: HipBuffer | null; normal?: HipBuffer | null }): void;
+  stats(): RasterStats;
+  destroy(): void;
+}
+export interface MeshImages { depth?: Float32Array; face?: Uint32Array; colour?: Uint8Array; normal?: Float32Array; stats: RasterStats }
+export interface MeshImageBuffers { depth?: HipBuffer; face?: HipBuffer; colour?: HipBuffer; normal?: HipBuffer; stats: RasterStats }
+/** The images of `mesh` under `camera` (the 68-float block); options.outputs defaults to ['depth', 'face']; row-major, width x height. */
+export function rasterizeMesh(device: HipDevice, mesh: MeshArrays | MeshBuffers, camera: Float32Array | HipBuffer, width: number, height: number,
+                              options?: { near?: number | null; cull?: CullMode; outputs?: RasterOutput[]; asBuffers?: false }): MeshImages;
+export function rasterizeMesh(device: HipDevice, mesh: MeshArrays | MeshBuffers, camera: Float32Array | HipBuffer, width: number, height: number,
+                              options: { near?: number | null; cull?: CullMode; outputs?: RasterOutput[]; asBuffers: true }): MeshImageBuffers;
+/** depthAgreement's counts: the pixels where both, a alone, b alone have a depth; those of `both` within the threshold; the quantised sum and the mean of |a - b|. */
+export interface DepthAgreement { both: number; onlyA: number; onlyB: number; within: number; sum_q: number; mean: number }
+export function encodeDepthAgreement(device: HipDevice, a: HipBuffer, b: HipBuffer, width: number, height: number, maxDifference: number, threshold: number, out: HipBuffer,
+                                     options?: { bWeightSum?: HipBuffer | null; minWeightSum?: number }): void;
+export function depthAgreementResult(sums: ArrayLike<number | bigint>, maxDifference: number): DepthAgreement;
+export function depthAgreement(device: HipDevice, a: Float32Array | HipBuffer, b: Float32Array | HipBuffer, width: number, height: number, maxDifference: number,
+                               threshold: number, options?: { bWeightSum?: Float32Array | HipBuffer | null; minWeightSum?: number }): DepthAgreement;
+export function meshOnDevice(device: HipDevice, mesh: MeshArrays | MeshBuffers, what: string): { vertices: HipBuffer; faces: HipBuffer; V: number; F: number; own: boolean };
 /** The index of "no point found" (PointIndex.nearest).  No reference counterpart. */
 export const NO_INDEX: 0xFFFFFFFF;
 export interface MeshSamples { points: Float32Array; face: Uint32Array; count: number }

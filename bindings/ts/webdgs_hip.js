@@ -998,9 +998,130 @@ function finishMesh(device, mesh, origin, smooth, simplify, normals, read) {
   } finally { destroyBuffers(simplified); }
 }
 
+// ---------------------------------------------------------------- mesh rasterization and depth agreement (include/webdgs.h, DESIGN.md section 20; no reference counterpart)
+const CULL_MODES = { none: 0, back: 1, front: 2 };   // WDGS_CULL_NONE, WDGS_CULL_BACK, WDGS_CULL_FRONT
+const MESH_RASTER_LARGE_FACE_PIXELS = 8;             // WDGS_MESH_RASTER_LARGE_FACE_PIXELS
+const MESH_RASTER_MAX_SIZE = 8192;                   // WDGS_MESH_RASTER_MAX_SIZE
+const MESH_RASTER_NEAR = 0.01;   // the depth below which the forward pass drops a Gaussian (csrc/project.hip, project_one: ndc.z < 0 under the cameras' znear of 0.01)
+const NO_FACE = 0xFFFFFFFF;
+const RASTER_STATS = ['invalidFaces', 'clippedFaces', 'degenerateFaces', 'culledFaces', 'emptyFaces', 'rasterizedFaces', 'coveredPixels', 'viewportMismatch'];
+const RASTER_OUTPUTS = { depth: [4, Float32Array], face: [4, Uint32Array], colour: [4, Uint8Array], normal: [16, Float32Array] };   // bytes per pixel, read-back type
+/** A z-buffered triangle rasterizer under the library's camera block (wdgs_mesh_rasterizer): encode draws an indexed mesh on the device into the depth, face,
+ *  colour and normal images asked for, stats reads the face classes and the covered pixels of the last encode.  Every byte is a function of the input alone
+ *  (include/webdgs.h states the definition).  There is no clipping: a face with a vertex nearer than `near` is dropped whole.  rasterizeMesh is the one-call form. */
+class MeshRasterizer {
+  constructor(device) { this.device = device; this.destroyed = false; this.handle = addon.meshRasterizerCreate(device.handle); }
+  /** Draws vertices f32[numVertices][3], faces u32[numFaces][3] (and colours rgba8[numVertices] for a colour image) under `camera` (the 68-float block on the
+   *  device) into options.depth f32, .face u32, .colour rgba8 and .normal rgba32f images of width x height, each optional; options.near (default
+   *  MESH_RASTER_NEAR), options.cull ('none', 'back', 'front').  Stream-ordered: it waits for nothing and records -- except a call that has to grow the object's
+   *  arrays (WDGS_E_STATE while recording; encode once eagerly first). */
+  encode(vertices, numVertices, faces, numFaces, colours, camera, width, height, options) {
+    const o = options || {}, cull = o.cull || 'none', near = o.near === undefined || o.near === null ? MESH_RASTER_NEAR : o.near;
+    if (!(cull in CULL_MODES)) { const e = new Error(`MeshRasterizer.encode: unknown cull mode ${cull} (none, back, front)`); e.code = 'WDGS_E'; throw e; }
+    if (numVertices < 2 ** 31 && 3 * numFaces < 2 ** 32 && ((vertices && vertices.size < 12 * numVertices) || (faces && faces.size < 12 * numFaces) ||
+                                                           (colours && colours.size < 4 * numVertices))) throw new Error('MeshRasterizer.encode: buffers too small for the mesh');
+    if (camera.size < 272) throw new Error('MeshRasterizer.encode: the camera block has 68 floats');
+    if (width >= 1 && width <= MESH_RASTER_MAX_SIZE && height >= 1 && height <= MESH_RASTER_MAX_SIZE) {
+      for (const k of Object.keys(RASTER_OUTPUTS)) if (o[k] && o[k].size < RASTER_OUTPUTS[k][0] * width * height) throw new Error(`MeshRasterizer.encode: the ${k} image is too small for ${width}x${height}`);
+    }
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshRasterizerEncode(this.handle, ptr(vertices), numVertices, ptr(faces), numFaces, ptr(colours), camera.ptr, width, height, Math.fround(near), CULL_MODES[cull],
+      ptr(o.depth), ptr(o.face), ptr(o.colour), ptr(o.normal));
+  }
+  /** The last encode: { invalidFaces, clippedFaces, degenerateFaces, culledFaces, emptyFaces, rasterizedFaces, coveredPixels, viewportMismatch } -- every face
+   *  is in exactly one class.  Waits (WDGS_E_STATE before an encode and while recording). */
+  stats() {
+    const r = addon.meshRasterizerStats(this.handle), out = {};
+    RASTER_STATS.forEach((k, i) => { out[k] = r[i]; });
+    return out;
+  }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.meshRasterizerDestroy(this.handle); this.handle = null; }
+}
+/** The images of `mesh` under `camera` (the 68-float block: a Float32Array or a HipBuffer): { depth: Float32Array[H*W], face: Uint32Array[H*W], colour:
+ *  Uint8Array[H*W*4], normal: Float32Array[H*W*4], stats } with the options.outputs asked for (default ['depth', 'face']).  `mesh` is what extractMesh /
+ *  loadMeshPLY return, or an object of HipBuffers as weldTrianglesDevice and simplifyMesh hand out with asBuffers (left as it is); 'colour' needs its colours.
+ *  A pixel no face covers has depth 0, face NO_FACE, colour and normal all zero.  options: { near = MESH_RASTER_NEAR, cull = 'none', outputs, asBuffers }.
+ *  A function of its arguments alone, bit for bit (include/webdgs.h states it).  options.asBuffers: the images stay on the device as HipBuffers the caller
+ *  destroys. */
+function rasterizeMesh(device, mesh, camera, width, height, options) {
+  const o = options || {}, outputs = o.outputs || ['depth', 'face'];
+  for (const k of outputs) if (!(k in RASTER_OUTPUTS)) throw new Error(`rasterizeMesh: unknown output ${k} (depth, face, colour, normal)`);
+  const src = meshOnDevice(device, mesh, 'rasterizeMesh');
+  const upload = (a) => { const b = device.createBuffer({ size: Math.max(a.byteLength, 8) }); if (a.byteLength) device.queue.writeBuffer(b, 0, a); return b; };
+  let colours = null, ownColours = false, cam = null, ownCam = false, rasterizer = null, out = {};
+  try {
+    if (outputs.includes('colour')) {
+      const c = mesh.colours;
+      if (!c) { const e = new Error('rasterizeMesh: a colour image needs a mesh with colours'); e.code = 'WDGS_E'; throw e; }
+      if (c instanceof HipBuffer) colours = c;
+      else {
+        let rgba = c;
+        if (c.length === 3 * src.V) {
+          rgba = new Uint8Array(4 * src.V).fill(255);
+          for (let v = 0; v < src.V; v++) for (let a = 0; a < 3; a++) rgba[4 * v + a] = c[3 * v + a];
+        } else if (c.length !== 4 * src.V) throw new Error(`rasterizeMesh: ${c.length} colour bytes for ${src.V} vertices`);
+        colours = upload(rgba instanceof Uint8Array ? rgba : Uint8Array.from(rgba)); ownColours = true;
+      }
+    }
+    if (camera instanceof HipBuffer) cam = camera;
+    else {
+      if (camera.length !== 68) throw new Error(`rasterizeMesh: the camera block has 68 floats, got ${camera.length}`);
+      cam = upload(camera instanceof Float32Array ? camera : Float32Array.from(camera)); ownCam = true;
+    }
+    rasterizer = new MeshRasterizer(device);
+    const npix = width >= 1 && width <= MESH_RASTER_MAX_SIZE && height >= 1 && height <= MESH_RASTER_MAX_SIZE ? width * height : 0;
+    for (const k of outputs) out[k] = exactBuffer(device, RASTER_OUTPUTS[k][0] * npix);
+    rasterizer.encode(src.vertices, src.V, src.faces, src.F, colours, cam, width, height, Object.assign({ near: o.near, cull: o.cull }, out));
+    const stats = rasterizer.stats();
+    if (o.asBuffers) { const result = Object.assign({}, out, { stats }); out = {}; return result; }
+    const result = { stats };
+    for (const k of outputs) result[k] = new RASTER_OUTPUTS[k][1](npix ? device.readBuffer(out[k], RASTER_OUTPUTS[k][0] * npix) : new ArrayBuffer(0));
+    return result;
+  } finally {
+    if (rasterizer) rasterizer.destroy();
+    destroyBuffers(out);
+    if (src.own) { src.vertices.destroy(); src.faces.destroy(); }
+    if (ownColours) colours.destroy();
+    if (ownCam) cam.destroy();
+  }
+}
+/** Stream-ordered depthAgreement: the five u64 sums into the first 40 bytes of `out` (no host wait).  options: { bWeightSum, minWeightSum = 0 }. */
+function encodeDepthAgreement(device, a, b, width, height, maxDifference, threshold, out, options) {
+  const o = options || {}, n = width * height;
+  if (a.size < 4 * n || b.size < 4 * n || (o.bWeightSum && o.bWeightSum.size < 4 * n) || out.size < 40) throw new Error(`depthAgreement: buffers too small for ${width}x${height}`);
+  addon.depthAgreement(device.handle, a.ptr, b.ptr, o.bWeightSum ? o.bWeightSum.ptr : null, Math.fround(o.minWeightSum || 0), width, height, Math.fround(maxDifference),
+    Math.fround(threshold), out.ptr);
+}
+/** The five sums as depthAgreement returns them (Numbers, exact below 2^53). */
+function depthAgreementResult(sums, maxDifference) {
+  const [both, onlyA, onlyB, within, sum_q] = sums.map(Number);
+  return { both, onlyA, onlyB, within, sum_q, mean: both ? sum_q * Math.fround(maxDifference) / 2 ** 24 / both : NaN };
+}
+/** How far two f32 depth images (Float32Array or HipBuffer) agree: both, onlyA, onlyB count the pixels where both, `a` alone, `b` alone have a depth (finite
+ *  and > 0; `b` also only where options.bWeightSum >= options.minWeightSum when that image is given); within those of `both` with |a - b| <= threshold; sum_q
+ *  the sum of u32(min(|a - b| / maxDifference, 1) 2^24) and mean = sum_q maxDifference / 2^24 / both (NaN when both is 0).  Exact integer sums.
+ *  0 < threshold <= maxDifference.  Synchronises. */
+function depthAgreement(device, a, b, width, height, maxDifference, threshold, options) {
+  const o = options || {}, n = width * height, owned = [];
+  const onDevice = (x, what) => {
+    if (!x || x instanceof HipBuffer) return x || null;
+    if (x.length !== n) throw new Error(`depthAgreement: ${what} has ${x.length} values for ${width}x${height}`);
+    const d = asDevice(device, x, Float32Array, 1, `depthAgreement: ${what}`);
+    owned.push(d.buf);
+    return d.buf;
+  };
+  const out = device.createBuffer({ size: 40 });
+  try {
+    encodeDepthAgreement(device, onDevice(a, 'a'), onDevice(b, 'b'), width, height, maxDifference, threshold, out,
+      { bWeightSum: onDevice(o.bWeightSum, 'bWeightSum'), minWeightSum: o.minWeightSum });
+    return depthAgreementResult([...new BigUint64Array(device.readBuffer(out, 40))], maxDifference);
+  } finally { out.destroy(); owned.forEach((x) => x.destroy()); }
+}
+
 // ---------------------------------------------------------------- mesh accuracy metrics (include/webdgs.h, DESIGN.md section 14; no reference counterpart)
 const NO_INDEX = 0xFFFFFFFF;
 const KNN_EXCLUDE_SELF = 1;   // WDGS_KNN_EXCLUDE_SELF
+
 /** { buf, rows, owned } of a [rows, width] array given as a typed array (uploaded; owned) or as a HipBuffer (whole rows of it). */
 function asDevice(device, array, Type, width, what) {
   if (array instanceof HipBuffer) return { buf: array, rows: Math.floor(array.size / (Type.BYTES_PER_ELEMENT * width)), owned: false };
@@ -1394,7 +1515,7 @@ class Communicator {
 const MAX_LANES = 4;         // WDGS_MAX_LANES
 const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 
-module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, MeshWelder, weldTrianglesDevice, destroyBuffers, MeshSimplifier, simplifyMesh, MeshAdjacency, meshAdjacency, smoothMesh, vertexNormals, finishMesh, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
+module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, MeshWelder, weldTrianglesDevice, destroyBuffers, MeshSimplifier, simplifyMesh, MeshAdjacency, meshAdjacency, smoothMesh, vertexNormals, finishMesh, CULL_MODES, MESH_RASTER_LARGE_FACE_PIXELS, MESH_RASTER_NEAR, NO_FACE, MeshRasterizer, rasterizeMesh, encodeDepthAgreement, depthAgreementResult, depthAgreement, meshOnDevice, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
   geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, grownTileEntries, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8 };

@@ -907,6 +907,74 @@ int wdgs_mesh_adjacency_normals(wdgs_mesh_adjacency* adjacency, const void* vert
 int wdgs_mesh_adjacency_stats(const wdgs_mesh_adjacency* adjacency, uint32_t* directed_edges, uint32_t* edges, uint32_t* boundary_edges, uint32_t* non_manifold_edges,
                               uint32_t* invalid_faces, uint32_t* boundary_vertices, uint32_t* isolated_vertices, uint32_t* max_degree);
 
+/* ---------------------------------------------------------------- Mesh rasterization: depth, face, colour and normal images of a mesh
+ *
+ * Input: an indexed mesh on the device, vertices f32[V][3] (world space), faces u32[F][3], optional colours rgba8[V] (the welder's and the simplifier's layout:
+ * red in the low byte), the 68-float camera block, width, height, near, cull.  WDGS_E_INVALID, with nothing written: V >= 2^31 or 3 F >= 2^32; width or height
+ * outside 1 .. WDGS_MESH_RASTER_MAX_SIZE; near not positive and finite; an unknown cull; a pointer that is not 4-byte aligned (the normal image: 16).
+ * VERTEX, all f32, each operation rounded once: wdgs_tsdf_volume_integrate's arithmetic, so that a mesh vertex lands where fusion sampled it.  v = view (p, 1),
+ * floats 0 - 15 of the block, column-major, the products summed left to right; z = v.z; sx = (((P00 v.x) / z) / 2 + 0.5) W, sy = ((((-P11) v.y) / z) / 2 + 0.5) H,
+ * P00 = block[32], P11 = block[37], W and H the width and height as floats.  The vertex is USABLE when v is finite, z >= near, sx and sy are finite and
+ * |sx|, |sy| <= 16384.  Its fixed-point position is X = (i32) rint(256 sx), Y = (i32) rint(256 sy), to nearest, ties to even: 8 sub-pixel bits.
+ * FACE.  Each face falls into exactly one class, tested in this order, and each class is counted: INVALID, an index >= V (never used as an address); CLIPPED, a
+ * vertex that is not usable; DEGENERATE, A = 0; CULLED, dropped by cull; EMPTY, no pixel centre of the viewport inside its bounding box; RASTERIZED, the rest.
+ * A = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0) in i64.  THERE IS NO NEAR-PLANE AND NO GUARD-BAND CLIPPING: a face with a vertex nearer than `near`, or further
+ * than 16384 pixels from the origin of the image, is dropped whole.
+ * cull is WDGS_CULL_NONE, WDGS_CULL_BACK (drops A > 0) or WDGS_CULL_FRONT (drops A < 0): FRONT IS A < 0.  Under the library's cameras the view matrix is a rotation
+ * into +x right, +y down, +z forward, P00 > 0 and P11 < 0, so (sx, sy) is (v.x, v.y) / z scaled by positive numbers.  A face wound counter-clockwise seen from
+ * outside has g = (p1 - p0) x (p2 - p0) pointing outwards, and a rotation keeps that; a camera outside the surface sees it when g . v0 < 0; and for a triangle in
+ * front of the camera the sign of the area of its projection (v.x / z, v.y / z) is the sign of g . v0 (the triangle (0,0,1), (1,0,1), (0,1,1) has g = (0,0,1),
+ * g . v0 = 1 and area +1).  So the faces extract_triangles winds outwards show A < 0 to a camera outside.  A camera block with P00 P11 > 0, or a view matrix
+ * that mirrors, swaps the two.
+ * COVERAGE, integers only.  Pixel (i, j) has the centre c = (256 i + 128, 256 j + 128).  s = sign(A); edge k runs from vertex a = k + 1 to b = k + 2 (mod 3);
+ * e_k = s ((Xb - Xa)(c.y - Ya) - (Yb - Ya)(c.x - Xa)) in i64, so e_0 + e_1 + e_2 = |A|.  The pixel is covered when every e_k > 0, or e_k = 0 and the edge OWNS
+ * its line: alpha > 0 or (alpha = 0 and beta > 0), alpha = -s (Yb - Ya), beta = s (Xb - Xa).  Two faces on one edge have opposite (alpha, beta) on it, so a pixel
+ * centre on a shared edge or a shared vertex belongs to exactly one of them.  The bounding box: the pixels with min X <= 256 i + 128 <= max X and the same in y,
+ * clamped to the viewport.
+ * DEPTH, perspective-correct, f32: lambda_k = f32(e_k) / f32(|A|) (the conversions round to nearest even); w_k = 1 / z_k; q = (lambda_0 w_0 + lambda_1 w_1) +
+ * lambda_2 w_2, each lambda_k w_k rounded; zp = 1 / q.  A fragment whose zp is not finite or not > 0 is skipped.
+ * HIDDEN SURFACE.  Every fragment does one unsigned 64-bit atomic min of bits(zp) 2^32 | f into a u64[W H] image cleared to all ones: the nearest depth wins,
+ * equal depths go to the lowest face index, and nothing depends on the order of faces, waves or launches.
+ * OUTPUTS, each nullable and written only when asked for, row-major.  A pixel no fragment reached: depth 0 (the depth maps' "nothing here"), face 0xFFFFFFFF,
+ * colour {0,0,0,0}, normal {0,0,0,0}.  Otherwise depth f32 = zp; face u32 = f; colour rgba8: lambda_k recomputed for that face and pixel, per channel t =
+ * ((lambda_0 w_0) C_0 + (lambda_1 w_1) C_1) + (lambda_2 w_2) C_2 with C_k the vertex's byte as a float, the byte rint(min(max(t zp, 0), 255)), alpha 255 (asking
+ * for it without vertex colours: WDGS_E_INVALID); normal rgba32f: the face's geometric normal in view space, g = (v1 - v0) x (v2 - v0), each component two products
+ * and a subtraction, n = g / sqrt((gx gx + gy gy) + gz gz), negated where (nx v0.x + ny v0.y) + nz v0.z > 0 (wdgs_depth_to_normals' rule), {n, 1} -- or {0,0,0,0}
+ * where n is zero or not finite -- which is the depth-normal image wdgs_normal_agreement and wdgs_normal_to_rgba8 take.
+ * STATISTICS: the six classes, covered_pixels (those some fragment reached) and viewport_mismatch: 1 when floats 64, 65 of the camera block are not width and
+ * height.  The faces are then classified all the same, but none is drawn: every output asked for is written as all-untouched and covered_pixels is 0.
+ * Every output byte is a function of the input alone.  No reference counterpart.
+ *
+ * Faces whose bounding box is larger than WDGS_MESH_RASTER_LARGE_FACE_PIXELS pixels on either axis are drawn by another kernel (one wave per 8 x 8 pixel
+ * block) than the others (one thread per face); the bytes are the same. */
+#define WDGS_CULL_NONE 0u
+#define WDGS_CULL_BACK 1u
+#define WDGS_CULL_FRONT 2u
+#define WDGS_MESH_RASTER_MAX_SIZE 8192u
+#ifndef WDGS_MESH_RASTER_LARGE_FACE_PIXELS   /* (a same-box comparison builds the library with another value: csrc/Makefile, EXTRA) */
+#define WDGS_MESH_RASTER_LARGE_FACE_PIXELS 8u
+#endif
+typedef struct wdgs_mesh_rasterizer wdgs_mesh_rasterizer;
+int wdgs_mesh_rasterizer_create(wdgs_device* dev, wdgs_mesh_rasterizer** out);
+int wdgs_mesh_rasterizer_destroy(wdgs_mesh_rasterizer* rasterizer);
+/* Draws the mesh into arrays the object owns -- 20 bytes per vertex, 8 per face, 8 per pixel, grown as needed and reused -- and resolves them into the outputs
+ * asked for.  Stream-ordered, no host wait, recordable -- except a call that has to grow the arrays: that one waits once and cannot be recorded (WDGS_E_STATE;
+ * encode once eagerly with the largest sizes first).  The kernels' event times are the device's (wdgs_device_get_kernel_times): raster_vertices, raster_faces,
+ * raster_blocks, raster_resolve and the scan's. */
+int wdgs_mesh_rasterizer_encode(wdgs_mesh_rasterizer* rasterizer, const void* vertices_f32_dev, uint32_t num_vertices, const void* faces_u32_dev, uint32_t num_faces,
+                                const void* colours_rgba8_dev, const void* camera_dev, uint32_t width, uint32_t height, float near, uint32_t cull,
+                                void* depth_out_f32_dev, void* face_out_u32_dev, void* colour_out_rgba8_dev, void* normal_out_rgba32f_dev);
+/* The statistics of the last encode, each pointer nullable.  Copies one block back and waits, so it cannot be recorded; WDGS_E_STATE also before any encode. */
+int wdgs_mesh_rasterizer_stats(wdgs_mesh_rasterizer* rasterizer, uint32_t* invalid_faces, uint32_t* clipped_faces, uint32_t* degenerate_faces, uint32_t* culled_faces,
+                               uint32_t* empty_faces, uint32_t* rasterized_faces, uint32_t* covered_pixels, uint32_t* viewport_mismatch);
+/* How far two depth images f32[W H] agree.  A depth is PRESENT when it is finite and > 0; b's, when b_weight_sum (nullable) is given, only where that image's
+ * value is >= min_weight_sum as well.  out u64[5] = { both, only_a, only_b: the pixels where both, a alone, b alone are present;  within: of `both`, those with
+ * d = |a - b| (f32) <= threshold;  sum_q: the sum over `both` of u32(min(d / max_difference, 1) 2^24), truncating }: exact integer sums, so the result does not
+ * depend on the order of anything.  The mean absolute difference, clamped at max_difference, is sum_q max_difference / 2^24 / both.  0 < threshold <=
+ * max_difference, both finite, and the image size as above (WDGS_E_INVALID).  Stream-ordered, no host wait, recordable. */
+int wdgs_depth_agreement(wdgs_device* dev, const void* a_f32_dev, const void* b_f32_dev, const void* b_weight_sum_f32_dev, float min_weight_sum, uint32_t width,
+                         uint32_t height, float max_difference, float threshold, void* out_u64x5_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WDGS_LIB_PATH") or os.path.join(_HERE, "lib", "libwebdgs_hip.so")
 
 WDGS_OK, WDGS_E_INVALID, WDGS_E_HIP, WDGS_E_CAPACITY, WDGS_E_STATE = 0, -1, -2, -3, -4
+# include/webdgs.h, mesh rasterization: a face whose bounding box exceeds this many pixels on either axis takes the kernel of 8 x 8 blocks
+MESH_RASTER_LARGE_FACE_PIXELS = 8   # WDGS_MESH_RASTER_LARGE_FACE_PIXELS
+MESH_RASTER_MAX_SIZE = 8192          # WDGS_MESH_RASTER_MAX_SIZE
 
 
 class WdgsError(RuntimeError):
@@ -189,6 +192,11 @@ SIGNATURES = {
     "wdgs_mesh_adjacency_smooth": (_I, [_P, _P, _P, _U, _U, _F, _F, _U]),
     "wdgs_mesh_adjacency_normals": (_I, [_P, _P, _P, _U, _U, _P]),
     "wdgs_mesh_adjacency_stats": (_I, [_P] + [C.POINTER(_U)] * 8),
+    "wdgs_mesh_rasterizer_create": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_mesh_rasterizer_destroy": (_I, [_P]),
+    "wdgs_mesh_rasterizer_encode": (_I, [_P, _P, _U, _P, _U, _P, _P, _U, _U, _F, _U, _P, _P, _P, _P]),
+    "wdgs_mesh_rasterizer_stats": (_I, [_P] + [C.POINTER(_U)] * 8),
+    "wdgs_depth_agreement": (_I, [_P, _P, _P, _P, _F, _U, _U, _F, _F, _P]),
     "wdgs_point_index_create": (_I, [_P, _P, C.c_uint64, _F, C.POINTER(_P)]),
     "wdgs_point_index_destroy": (_I, [_P]),
     "wdgs_point_index_reserve_queries": (_I, [_P, _U]),

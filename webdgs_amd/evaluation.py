@@ -197,6 +197,57 @@ class Evaluator:
         return dict(iteration=self.trainer.iteration, views=ids, value=[(e / a) if a else float("nan") for e, a in zip(sum_e, sum_a)], pixels=pixels,
                     sum_e=sum_e, sum_a=sum_a, mean=(sum(sum_e) / sum(sum_a)) if sum(sum_a) else float("nan"), ms=(time.perf_counter() - t0) * 1e3)
 
+    # ------------------------------------------------------------------ a mesh against the model's own depth maps
+    def meshDepthAgreement(self, mesh: dict, viewIds: Optional[list] = None, split: str = "eval", depthKind: str = "median", maxDifference: float = 1.0,
+                           threshold: float = 0.05, minWeightSum: float = 0.5, near: float = ops.MESH_RASTER_NEAR, cull: str = "none") -> dict:
+        """How far ``mesh`` (``ops.rasterizeMesh``'s: numpy or a dict of ``HipBuffer``) agrees with the model it came from, view by view, with no reference
+        geometry: per view the model's ``depthKind`` depth map (``b``; present where its weight sum is at least ``minWeightSum``) against the mesh
+        rasterized under the same camera (``a``), through ``ops.encodeDepthAgreement``.  ``dict(iteration, views, both=[...], onlyA=[...], onlyB=[...],
+        within=[...], sum_q=[...], mean=[...], total=dict(both, onlyA, onlyB, within, sum_q, mean), ms)``: ``onlyB`` pixels are where the model sees
+        surface and the mesh has a hole, ``onlyA`` where the mesh has surface the model does not show; ``mean`` is the mean absolute depth difference
+        over ``both``, clamped at ``maxDifference``; ``within`` counts differences of at most ``threshold``.
+
+        Rendered through evaluate's passes, with its isolation: the pipeline is drained, a view whose lists overflowed is rendered again, no RNG draw,
+        no training pass, no recording dropped.  Per rank with ``world_size > 1``."""
+        if depthKind not in ("median", "expected"):
+            raise ValueError(f"meshDepthAgreement: depthKind must be 'median' or 'expected', not {depthKind!r}")
+        cams, imgs, bufs, ids = self._views("meshDepthAgreement", viewIds, split)
+        t0 = time.perf_counter()
+        self._drain()
+        n = len(ids)
+        dev = self.device
+        vertices, faces, V, F, own = ops._mesh_on_device(dev, mesh, "meshDepthAgreement")
+        out = dev.createBuffer(40 * max(1, n), "depth agreement sums")
+        sizes = [(int(imgs[v]["width"]), int(imgs[v]["height"])) for v in ids]
+        scratch = dev.createBuffer(4 * max([1] + [w * h for w, h in sizes]), "mesh depth")
+        rasterizer = ops.MeshRasterizer(dev)
+        try:
+            if sizes:   # (grown once, to the largest view, in front of the loop)
+                w, h = max(sizes, key=lambda s: s[0] * s[1])
+                rasterizer.encode(vertices, V, faces, F, None, bufs[ids[0]], w, h, near, cull, depth=scratch)
+
+            def measure(i, v, s, w, h):
+                s.rasterizer.encodeDepth(None, (depthKind, "weight_sum"))
+                rasterizer.encode(vertices, V, faces, F, None, bufs[v], w, h, near, cull, depth=scratch)
+                ops.encodeDepthAgreement(dev, scratch, s.rasterizer.getDepthTextureView(depthKind), w, h, maxDifference, threshold, dev.view(out.ptr + 40 * i, 40),
+                                         bWeightSum=s.rasterizer.getDepthTextureView("weight_sum"), minWeightSum=minWeightSum)
+            self._render_views(ids, imgs, bufs, measure, what="meshDepthAgreement")
+            sums = (out.read(np.uint64, count=5 * n) if n else np.zeros(0, np.uint64)).reshape(n, 5)
+        finally:
+            rasterizer.destroy()
+            scratch.destroy()
+            out.destroy()
+            if own:
+                vertices.destroy()
+                faces.destroy()
+        per = [ops._depth_agreement_result(row, maxDifference) for row in sums]
+        result = dict(iteration=self.trainer.iteration, views=ids)
+        for k in ("both", "onlyA", "onlyB", "within", "sum_q", "mean"):
+            result[k] = [p[k] for p in per]
+        result["total"] = ops._depth_agreement_result([sum(int(row[k]) for row in sums) for k in range(5)], maxDifference)
+        result["ms"] = (time.perf_counter() - t0) * 1e3
+        return result
+
     # ------------------------------------------------------------------ TSDF fusion and mesh extraction (DESIGN.md section 13)
     def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
         """Fuses the current model's depth maps into ``volume``: for each view in the order given, the forward pass, rasterize,

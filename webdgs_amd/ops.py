@@ -1531,6 +1531,201 @@ def finishMesh(device: HipDevice, mesh: dict, origin, smooth: Optional[int], sim
         destroyBuffers(simplified)
 
 
+# ----------------------------------------------------------------------------- mesh rasterization and depth agreement (no reference counterpart)
+CULL_MODES = {"none": 0, "back": 1, "front": 2}   # WDGS_CULL_NONE, WDGS_CULL_BACK, WDGS_CULL_FRONT
+MESH_RASTER_LARGE_FACE_PIXELS = _lib.MESH_RASTER_LARGE_FACE_PIXELS
+# the depth below which the forward pass drops a Gaussian: csrc/project.hip, project_one, `ndc.z < 0.0f`, which synth.projection_matrix's znear = 0.01 puts there
+MESH_RASTER_NEAR = 0.01
+RASTER_STATS = ("invalidFaces", "clippedFaces", "degenerateFaces", "culledFaces", "emptyFaces", "rasterizedFaces", "coveredPixels", "viewportMismatch")
+RASTER_OUTPUTS = {"depth": (4, np.float32), "face": (4, np.uint32), "colour": (4, np.uint8), "normal": (16, np.float32)}   # bytes per pixel, read-back type
+NO_FACE = 0xFFFFFFFF
+
+
+class MeshRasterizer:
+    """A z-buffered triangle rasterizer under the library's camera block (``wdgs_mesh_rasterizer``): ``encode`` draws an indexed mesh on the device into
+    the depth, face, colour and normal images asked for, ``stats`` reads the face classes and the covered pixels of the last encode.  Every byte is a
+    function of the input alone (include/webdgs.h states the definition; coverage in integers, one 64-bit atomic min per fragment).  There is no
+    clipping: a face with a vertex nearer than ``near`` is dropped whole.  ``rasterizeMesh`` is the one-call form."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        h = C.c_void_p()
+        check(device.lib.wdgs_mesh_rasterizer_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def encode(self, vertices: Optional[HipBuffer], numVertices: int, faces: Optional[HipBuffer], numFaces: int, colours: Optional[HipBuffer], camera: HipBuffer,
+               width: int, height: int, near: float = MESH_RASTER_NEAR, cull: str = "none", depth: Optional[HipBuffer] = None, face: Optional[HipBuffer] = None,
+               colour: Optional[HipBuffer] = None, normal: Optional[HipBuffer] = None) -> None:
+        """Draws ``vertices`` f32[numVertices][3], ``faces`` u32[numFaces][3] (and ``colours`` rgba8[numVertices] for a colour image) under ``camera``
+        (the 68-float block on the device) into ``depth`` f32, ``face`` u32, ``colour`` rgba8 and ``normal`` rgba32f images of ``width`` x ``height``, each
+        optional.  Stream-ordered: it waits for nothing and records -- except a call that has to grow the object's arrays (``StateError`` while
+        recording; encode once eagerly first)."""
+        nv, nf, w, h = int(numVertices), int(numFaces), int(width), int(height)
+        if cull not in CULL_MODES:
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshRasterizer.encode: unknown cull mode {cull!r} (none, back, front)")
+        if not (0 <= nv < 2 ** 32 and 0 <= nf < 2 ** 32 and 0 <= w < 2 ** 32 and 0 <= h < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshRasterizer.encode: bad counts {numVertices}, {numFaces}, {width}x{height}")
+        if nv < 2 ** 31 and 3 * nf < 2 ** 32 and ((vertices is not None and vertices.size < 12 * nv) or (faces is not None and faces.size < 12 * nf)
+                                                 or (colours is not None and colours.size < 4 * nv)):
+            raise ValueError("MeshRasterizer.encode: buffers too small for the mesh")
+        if camera.size < 272:
+            raise ValueError("MeshRasterizer.encode: the camera block has 68 floats")
+        if 1 <= w <= _lib.MESH_RASTER_MAX_SIZE and 1 <= h <= _lib.MESH_RASTER_MAX_SIZE:
+            for name, buf in (("depth", depth), ("face", face), ("colour", colour), ("normal", normal)):
+                if buf is not None and buf.size < RASTER_OUTPUTS[name][0] * w * h:
+                    raise ValueError(f"MeshRasterizer.encode: the {name} image is too small for {w}x{h}")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_rasterizer_encode(self.handle, ptr(vertices), nv, ptr(faces), nf, ptr(colours), camera.ptr, w, h, float(near), CULL_MODES[cull],
+                                                          ptr(depth), ptr(face), ptr(colour), ptr(normal)))
+
+    def stats(self) -> dict:
+        """The last encode: ``dict(invalidFaces, clippedFaces, degenerateFaces, culledFaces, emptyFaces, rasterizedFaces, coveredPixels, viewportMismatch)``
+        -- every face is in exactly one class.  Waits (``StateError`` before an encode and while recording)."""
+        v = [C.c_uint32(0) for _ in RASTER_STATS]
+        check(self.device.lib.wdgs_mesh_rasterizer_stats(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(RASTER_STATS, (int(x.value) for x in v)))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_mesh_rasterizer_destroy(self.handle)
+        self.handle = None
+
+
+def _mesh_colours_on_device(device: HipDevice, mesh: dict, V: int, own: bool, what: str) -> tuple:
+    """``(colours | None, owned)``: the mesh's vertex colours as an rgba8[V] ``HipBuffer`` -- a numpy mesh's u8[V,3] get an alpha of 255, as ``simplifyMesh``
+    uploads them."""
+    c = mesh.get("colours")
+    if c is None:
+        return None, False
+    if isinstance(c, HipBuffer):
+        if own:
+            raise ValueError(f"{what}: colours on the device need vertices on the device")
+        return c, False
+    if not own:
+        raise ValueError(f"{what}: vertices on the device need colours on the device")
+    c = np.ascontiguousarray(c, np.uint8)
+    if c.ndim != 2 or c.shape[0] != V or c.shape[1] not in (3, 4):
+        raise ValueError(f"{what}: colours of shape {c.shape} for {V} vertices")
+    if c.shape[1] == 3:
+        c = np.ascontiguousarray(np.concatenate([c, np.full((V, 1), 255, np.uint8)], axis=1))
+    return device.bufferFrom(c, f"{what}: colours"), True
+
+
+def _camera_on_device(device: HipDevice, camera, what: str) -> tuple:
+    if isinstance(camera, HipBuffer):
+        return camera, False
+    c = np.ascontiguousarray(camera, np.float32).reshape(-1)
+    if c.size != 68:
+        raise ValueError(f"{what}: the camera block has 68 floats, got {c.size}")
+    return device.bufferFrom(c, f"{what}: camera"), True
+
+
+def rasterizeMesh(device: HipDevice, mesh: dict, camera, width: int, height: int, near: float = MESH_RASTER_NEAR, cull: str = "none", outputs=("depth", "face"),
+                  asBuffers: bool = False) -> dict:
+    """The images of ``mesh`` under ``camera`` (the 68-float block, numpy or ``HipBuffer``): ``dict(depth f32[H,W], face u32[H,W], colour u8[H,W,4], normal
+    f32[H,W,4], stats)`` with the ``outputs`` asked for.  ``mesh`` is the dict ``extractMesh`` / ``loaders.loadMeshPLY`` return, or a dict of ``HipBuffer``s
+    as ``weldTrianglesDevice(asBuffers=True)`` and ``simplifyMesh(asBuffers=True)`` hand out (left as it is); ``colour`` needs its ``colours``.  A pixel no
+    face covers has depth 0, face ``NO_FACE``, colour and normal all zero.  ``near`` defaults to the depth below which the forward pass drops a Gaussian, so
+    mesh and model are clipped alike -- by dropping, not by cutting: a face with a vertex nearer than ``near`` is not drawn.  ``cull``: ``"none"``,
+    ``"back"`` or ``"front"``.  A function of its arguments alone, bit for bit (include/webdgs.h states it).  ``asBuffers``: the images stay on the device
+    as ``HipBuffer`` the caller destroys."""
+    outputs = tuple(outputs)
+    for name in outputs:
+        if name not in RASTER_OUTPUTS:
+            raise ValueError(f"rasterizeMesh: unknown output {name!r} (depth, face, colour, normal)")
+    w, h = int(width), int(height)
+    vertices, faces, V, F, own = _mesh_on_device(device, mesh, "rasterizeMesh")
+    colours = cam = None
+    own_colours = own_cam = False
+    rasterizer = None
+    out = {}
+    try:
+        if "colour" in outputs:
+            colours, own_colours = _mesh_colours_on_device(device, mesh, V, own, "rasterizeMesh")
+            if colours is None:
+                raise _lib.WdgsError(_lib.WDGS_E_INVALID, "rasterizeMesh: a colour image needs a mesh with colours")
+        cam, own_cam = _camera_on_device(device, camera, "rasterizeMesh")
+        rasterizer = MeshRasterizer(device)
+        npix = w * h if 1 <= w <= _lib.MESH_RASTER_MAX_SIZE and 1 <= h <= _lib.MESH_RASTER_MAX_SIZE else 0
+        out = {name: device.createBuffer(RASTER_OUTPUTS[name][0] * npix, f"mesh {name} image") for name in outputs}
+        rasterizer.encode(vertices, V, faces, F, colours, cam, w, h, near, cull, **out)
+        stats = rasterizer.stats()
+        if asBuffers:
+            result, out = dict(out, stats=stats), {}
+            return result
+        shapes = {"depth": (h, w), "face": (h, w), "colour": (h, w, 4), "normal": (h, w, 4)}
+        return dict({name: out[name].read(RASTER_OUTPUTS[name][1], count=int(np.prod(shapes[name]))).reshape(shapes[name]) for name in outputs}, stats=stats)
+    finally:
+        if rasterizer is not None:
+            rasterizer.destroy()
+        destroyBuffers(out)
+        if own:
+            vertices.destroy()
+            faces.destroy()
+        if own_colours:
+            colours.destroy()
+        if own_cam:
+            cam.destroy()
+
+
+def faceIndexColours(face) -> np.ndarray:
+    """A face image u32[H,W] as rgba8 ``[H, W, 4]``: a fixed integer hash of the index (a multiply by 2654435761 mod 2^32, xor-folded by 15 bits; the low
+    three bytes, each or-ed with 0x40 so that no face is black), alpha 255; ``NO_FACE`` all zero."""
+    f = np.ascontiguousarray(face, np.uint32)
+    x = (f.astype(np.uint64) * np.uint64(2654435761) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    x ^= x >> np.uint32(15)
+    out = np.stack([(x & np.uint32(0xFF)) | np.uint32(0x40), ((x >> np.uint32(8)) & np.uint32(0xFF)) | np.uint32(0x40),
+                    ((x >> np.uint32(16)) & np.uint32(0xFF)) | np.uint32(0x40), np.full(f.shape, 255, np.uint32)], axis=-1).astype(np.uint8)
+    out[f == np.uint32(NO_FACE)] = 0
+    return out
+
+
+def encodeDepthAgreement(device: HipDevice, a: HipBuffer, b: HipBuffer, width: int, height: int, maxDifference: float, threshold: float, out: HipBuffer,
+                         bWeightSum: Optional[HipBuffer] = None, minWeightSum: float = 0.0) -> None:
+    """Stream-ordered ``depthAgreement``: the five u64 sums into the first 40 bytes of ``out``.  No host wait."""
+    n = int(width) * int(height)
+    if a.size < 4 * n or b.size < 4 * n or (bWeightSum is not None and bWeightSum.size < 4 * n) or out.size < 40:
+        raise ValueError(f"depthAgreement: buffers too small for {width}x{height}")
+    check(device.lib.wdgs_depth_agreement(device.handle, a.ptr, b.ptr, bWeightSum.ptr if bWeightSum is not None else None, float(minWeightSum), int(width), int(height),
+                                          float(maxDifference), float(threshold), out.ptr))
+
+
+def _depth_agreement_result(sums, maxDifference: float) -> dict:
+    both, only_a, only_b, within, sum_q = (int(x) for x in sums)
+    mean = (sum_q * float(np.float32(maxDifference)) / 2.0 ** 24 / both) if both else float("nan")
+    return dict(both=both, onlyA=only_a, onlyB=only_b, within=within, sum_q=sum_q, mean=mean)
+
+
+def depthAgreement(device: HipDevice, a, b, width: int, height: int, maxDifference: float, threshold: float, bWeightSum=None, minWeightSum: float = 0.0) -> dict:
+    """How far two f32 depth images (numpy or ``HipBuffer``) agree: ``both``, ``onlyA``, ``onlyB`` count the pixels where both, ``a`` alone, ``b`` alone
+    have a depth (finite and > 0; ``b`` also only where ``bWeightSum >= minWeightSum`` when that image is given); ``within`` those of ``both`` with
+    ``|a - b| <= threshold``; ``sum_q`` the sum of ``u32(min(|a - b| / maxDifference, 1) 2^24)`` and ``mean = sum_q maxDifference / 2^24 / both`` the mean
+    absolute difference clamped at ``maxDifference`` (nan when ``both`` is 0).  Exact integer sums.  ``0 < threshold <= maxDifference``.  Synchronises."""
+    n = int(width) * int(height)
+    owned = []
+
+    def on_device(x, what):
+        if x is None or isinstance(x, HipBuffer):
+            return x
+        arr = np.ascontiguousarray(x, np.float32).reshape(-1)
+        if arr.size != n:
+            raise ValueError(f"depthAgreement: {what} has {arr.size} values for {width}x{height}")
+        owned.append(device.bufferFrom(arr, f"depthAgreement: {what}"))
+        return owned[-1]
+
+    out = device.createBuffer(40, "depth agreement")
+    try:
+        encodeDepthAgreement(device, on_device(a, "a"), on_device(b, "b"), width, height, maxDifference, threshold, out, on_device(bWeightSum, "bWeightSum"), minWeightSum)
+        return _depth_agreement_result(out.read(np.uint64, count=5), maxDifference)
+    finally:
+        out.destroy()
+        for x in owned:
+            x.destroy()
+
+
 # ----------------------------------------------------------------------------- mesh accuracy metrics (DESIGN.md section 14; no reference counterpart)
 NO_INDEX = 0xFFFFFFFF
 KNN_EXCLUDE_SELF = 1   # WDGS_KNN_EXCLUDE_SELF

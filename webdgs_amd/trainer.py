@@ -867,6 +867,10 @@ class Trainer:
         """``Evaluator.normalConsistency``: agreement of the composited normals with the normals of the model's own depth map."""
         return self.evaluator.normalConsistency(viewIds, split, depthKind)
 
+    def meshDepthAgreement(self, mesh: dict, viewIds: Optional[list] = None, split: str = "eval", depthKind: str = "median", **options) -> dict:
+        """``Evaluator.meshDepthAgreement``: a mesh rasterized under each view against the model's own depth map of that view."""
+        return self.evaluator.meshDepthAgreement(mesh, viewIds, split, depthKind, **options)
+
     def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
         """``Evaluator.fuseDepth``: fuses the current model's depth maps into ``volume``."""
         return self.evaluator.fuseDepth(volume, viewIds, split, depthKind)

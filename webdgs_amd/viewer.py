@@ -15,7 +15,8 @@ from typing import Optional
 import numpy as np
 
 from . import loaders
-from .ops import HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer, depthToRGBA8, grownTileEntries, normalToRGBA8
+from .ops import (MESH_RASTER_NEAR, HipBuffer, HipDevice, HipEncoder, PointCloud, TiledForwardPass, TiledRasterizer, depthToRGBA8, faceIndexColours, grownTileEntries,
+                  normalToRGBA8, rasterizeMesh)
 
 
 def encodePNG(rgba: np.ndarray) -> bytes:
@@ -240,6 +241,44 @@ class Viewer:
             out.destroy()
         with open(path, "wb") as f:
             f.write(encodePNG(rgba))
+
+    # ---- meshes (no reference counterpart)
+    def renderMesh(self, mesh: dict, mode: str = "colour", near: float = MESH_RASTER_NEAR, cull: str = "none", depthRange: Optional[tuple] = None) -> np.ndarray:
+        """``mesh`` (``ops.rasterizeMesh``'s: numpy or a dict of ``HipBuffer``) under the current camera as ``[H, W, 4]`` uint8, alpha 255 where a face
+        shows and the pixel all zero -- black -- where none does, except as the presentation kernels say: ``"colour"``, the interpolated vertex
+        colours; ``"depth"``, ``ops.depthToRGBA8`` between ``depthRange`` (default: the smallest and largest depth of the image); ``"normal"``,
+        ``ops.normalToRGBA8`` of the faces' geometric normals; ``"face"``, a fixed integer hash of the face index.  Needs no point cloud and touches
+        neither the swap-chain image nor the viewer's passes (synchronises)."""
+        if mode not in ("colour", "depth", "normal", "face"):
+            raise ValueError(f"Viewer.renderMesh: mode must be 'colour', 'depth', 'normal' or 'face', not {mode!r}")
+        w, h = self.width, self.height
+        if mode in ("colour", "face"):
+            out = rasterizeMesh(self.device, mesh, self.cameraBuffer, w, h, near, cull, (mode,))
+            return out["colour"] if mode == "colour" else faceIndexColours(out["face"])
+        bufs = rasterizeMesh(self.device, mesh, self.cameraBuffer, w, h, near, cull, (mode,), asBuffers=True)
+        target = self.device.createBuffer(4 * w * h, "mesh presentation")
+        try:
+            if mode == "depth":
+                lo, hi = depthRange if depthRange is not None else (None, None)
+                if lo is None or hi is None:
+                    d = bufs["depth"].read(np.float32, w * h)
+                    seen = d[d > 0]
+                    lo = float(seen.min()) if lo is None and seen.size else (1.0 if lo is None else float(lo))
+                    hi = float(seen.max()) if hi is None and seen.size else (2.0 if hi is None else float(hi))
+                if not hi > lo:   # (one depth only: any range around it)
+                    hi = float(np.nextafter(np.float32(lo), np.float32(np.inf))) * 2.0
+                depthToRGBA8(self.device, bufs["depth"], w, h, lo, hi, target)
+            else:
+                normalToRGBA8(self.device, bufs["normal"], w, h, target)
+            return target.read(np.uint8, 4 * w * h).reshape(h, w, 4)
+        finally:
+            target.destroy()
+            bufs[mode].destroy()
+
+    def saveMeshPNG(self, path: str, mesh: dict, mode: str = "colour", **options) -> None:
+        """``renderMesh(mesh, mode, **options)`` as a PNG."""
+        with open(path, "wb") as f:
+            f.write(encodePNG(self.renderMesh(mesh, mode, **options)))
 
     def savePNG(self, path: str) -> None:
         with open(path, "wb") as f:
