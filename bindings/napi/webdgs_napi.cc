@@ -613,6 +613,71 @@ static napi_value depthAgreement(napi_env env, napi_callback_info info) {
                                           (float)get_f64(env, argv[8]), get_ptr(env, argv[9])));
     return js_undefined(env);
 }
+// Per-face visibility and the face filter (include/webdgs.h: wdgs_face_visibility_*, wdgs_mesh_face_filter_*; no reference counterpart)
+static napi_value faceVisibilityCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_face_visibility* v = nullptr;
+    WDGS_OK_OR_THROW(wdgs_face_visibility_create((wdgs_device*)get_ptr(env, argv[0]), &v));
+    return make_ptr(env, v);
+}
+static napi_value faceVisibilityDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_face_visibility_destroy((wdgs_face_visibility*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value faceVisibilityReset(napi_env env, napi_callback_info info) {  // (visibility, numFaces)
+    ARGS(2);
+    WDGS_OK_OR_THROW(wdgs_face_visibility_reset((wdgs_face_visibility*)get_ptr(env, argv[0]), get_u32(env, argv[1])));
+    return js_undefined(env);
+}
+static napi_value faceVisibilityAccumulate(napi_env env, napi_callback_info info) {
+    // (visibility, faceImagePtr | null, meshDepthPtr | null, modelDepthPtr | null, modelWeightSumPtr | null, minWeightSum, threshold, width, height)
+    ARGS(9);
+    WDGS_OK_OR_THROW(wdgs_face_visibility_accumulate((wdgs_face_visibility*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_ptr(env, argv[3]),
+                                                     get_ptr(env, argv[4]), (float)get_f64(env, argv[5]), (float)get_f64(env, argv[6]), get_u32(env, argv[7]),
+                                                     get_u32(env, argv[8])));
+    return js_undefined(env);
+}
+static napi_value faceVisibilityGet(napi_env env, napi_callback_info info) {  // (visibility) -> countersPtr
+    ARGS(1);
+    void* p = nullptr;
+    WDGS_OK_OR_THROW(wdgs_face_visibility_get((wdgs_face_visibility*)get_ptr(env, argv[0]), &p));
+    return make_ptr(env, p);
+}
+static napi_value faceVisibilityStats(napi_env env, napi_callback_info info) {  // (visibility) -> [views, foreignPixels, countedPixels, agreeingPixels] (doubles: below 2^53)
+    ARGS(1);
+    uint64_t r[4] = {0, 0, 0, 0};
+    WDGS_OK_OR_THROW(wdgs_face_visibility_stats((wdgs_face_visibility*)get_ptr(env, argv[0]), &r[0], &r[1], &r[2], &r[3]));
+    napi_value a; napi_create_array_with_length(env, 4, &a);
+    for (uint32_t i = 0; i < 4; i++) { napi_value x; napi_create_double(env, (double)r[i], &x); napi_set_element(env, a, i, x); }
+    return a;
+}
+static napi_value faceVisibilityFlags(napi_env env, napi_callback_info info) {
+    // (device, countersPtr | null, numFaces, minPixels, minViews, minAgreeing, minAgreeingQ16, keepPtr | null)
+    ARGS(8);
+    WDGS_OK_OR_THROW(wdgs_face_visibility_flags((wdgs_device*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]),
+                                                get_u32(env, argv[4]), get_u32(env, argv[5]), get_u32(env, argv[6]), get_ptr(env, argv[7])));
+    return js_undefined(env);
+}
+static napi_value meshFaceFilterCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_mesh_face_filter* f = nullptr;
+    WDGS_OK_OR_THROW(wdgs_mesh_face_filter_create((wdgs_device*)get_ptr(env, argv[0]), &f));
+    return make_ptr(env, f);
+}
+static napi_value meshFaceFilterDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_mesh_face_filter_destroy((wdgs_mesh_face_filter*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value meshFaceFilterSelect(napi_env env, napi_callback_info info) {  // (filter, facesPtr | null, numFaces, numVertices, keepPtr | null) -> [keptVertices, keptFaces, invalidFaces]
+    ARGS(5);
+    uint32_t r[3] = {0, 0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_face_filter_select((wdgs_mesh_face_filter*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]),
+                                                  get_ptr(env, argv[4]), &r[0], &r[1], &r[2]));
+    napi_value a; napi_create_array_with_length(env, 3, &a);
+    for (uint32_t i = 0; i < 3; i++) napi_set_element(env, a, i, make_u32(env, r[i]));
+    return a;
+}
+static napi_value meshFaceFilterCompact(napi_env env, napi_callback_info info) {
+    // (filter, verticesPtr | null, verticesOutPtr | null, facesOutPtr, vertexMapPtr | null, faceMapPtr | null, capacityVertices, capacityFaces)
+    ARGS(8);
+    WDGS_OK_OR_THROW(wdgs_mesh_face_filter_compact((wdgs_mesh_face_filter*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_ptr(env, argv[3]),
+                                                   get_ptr(env, argv[4]), get_ptr(env, argv[5]), get_u32(env, argv[6]), get_u32(env, argv[7])));
+    return js_undefined(env);
+}
 static napi_value pointIndexCreate(napi_env env, napi_callback_info info) {  // (device, pointsPtr, numPoints, cellSize: 0 = chosen by the first query) -> handle
     ARGS(4);
     wdgs_point_index* ix = nullptr;
@@ -1292,6 +1357,9 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(meshAdjacencyCreate); EXPORT_FN(meshAdjacencyDestroy); EXPORT_FN(meshAdjacencyCount); EXPORT_FN(meshAdjacencyEmit); EXPORT_FN(meshAdjacencySmooth);
     EXPORT_FN(meshAdjacencyNormals); EXPORT_FN(meshAdjacencyStats);
     EXPORT_FN(meshRasterizerCreate); EXPORT_FN(meshRasterizerDestroy); EXPORT_FN(meshRasterizerEncode); EXPORT_FN(meshRasterizerStats); EXPORT_FN(depthAgreement);
+    EXPORT_FN(faceVisibilityCreate); EXPORT_FN(faceVisibilityDestroy); EXPORT_FN(faceVisibilityReset); EXPORT_FN(faceVisibilityAccumulate); EXPORT_FN(faceVisibilityGet);
+    EXPORT_FN(faceVisibilityStats); EXPORT_FN(faceVisibilityFlags);
+    EXPORT_FN(meshFaceFilterCreate); EXPORT_FN(meshFaceFilterDestroy); EXPORT_FN(meshFaceFilterSelect); EXPORT_FN(meshFaceFilterCompact);
     EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
     EXPORT_FN(pointDistanceStats);
     EXPORT_FN(pointIndexBounds); EXPORT_FN(pointIndexKNearest); EXPORT_FN(pointCloudPositions); EXPORT_FN(pointCloudNeighbourScales);

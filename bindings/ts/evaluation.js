@@ -9,6 +9,12 @@
 const hip = require('./webdgs_hip.js');
 const { destroyPassSets } = require('./trainer.js');
 
+/** hip.FaceVisibility's cumulative totals as per-view lists: the counted, agreeing and foreign pixels of each view. */
+function perView(totals) {
+  const per = (key) => totals.map((t, i) => t[key] - (i ? totals[i - 1][key] : 0));
+  return { counted: per('countedPixels'), agreeing: per('agreeingPixels'), foreign: per('foreignPixels') };
+}
+
 /** The evaluation side of one Trainer.  It owns the evaluation views with their camera blocks (and the textures it uploaded itself), the per-size
  *  evaluation PassSets, the size an overflow has grown their tile-entry lists to and the long-list settings they were built with.
  *
@@ -219,6 +225,80 @@ class Evaluator {
     return result;
   }
 
+  // ---------------------------------------------------------------- which faces of a mesh the views see (DESIGN.md section 21)
+  /** { visibility, ids, totals }: a hip.FaceVisibility of the mesh on the device (src: hip.meshOnDevice's) accumulated over the views -- the caller destroys
+   *  it -- and its cumulative totals after each view.  meshDepthAgreement's loop: the rasterizer grown once, one encode and one accumulate per view. */
+  faceVisibilityOver(what, src, o) {
+    const split = o.split || 'train', depthKind = o.depthKind || 'median';
+    const threshold = o.threshold === undefined || o.threshold === null ? 0.05 : o.threshold, minWeightSum = o.minWeightSum === undefined || o.minWeightSum === null ? 0.5 : o.minWeightSum;
+    if (depthKind !== 'median' && depthKind !== 'expected') throw new Error(`${what}: depthKind must be 'median' or 'expected', not ${depthKind}`);
+    const { imgs, bufs, ids } = this.views(what, o.viewIds, split);
+    this.drain();
+    const dev = this.device, npix = Math.max(4, ...ids.map((v) => imgs[v].width * imgs[v].height));
+    const depth = dev.createBuffer({ size: 4 * npix, label: 'mesh depth' }), image = dev.createBuffer({ size: 4 * npix, label: 'mesh face image' });
+    const rasterizer = new hip.MeshRasterizer(dev), visibility = new hip.FaceVisibility(dev), totals = [];
+    try {
+      visibility.reset(src.F);
+      if (ids.length) {   // (grown once, to the largest view, in front of the loop)
+        const big = ids.reduce((a, v) => (imgs[v].width * imgs[v].height > imgs[a].width * imgs[a].height ? v : a), ids[0]);
+        rasterizer.encode(src.vertices, src.V, src.faces, src.F, null, bufs[ids[0]], imgs[big].width, imgs[big].height, { near: o.near, cull: o.cull, depth, face: image });
+      }
+      this.renderViews(ids, imgs, bufs, (i, v, s, w, h) => {
+        s.rasterizer.encodeDepth(null, [depthKind, 'weight_sum']);
+        rasterizer.encode(src.vertices, src.V, src.faces, src.F, null, bufs[v], w, h, { near: o.near, cull: o.cull, depth, face: image });
+        visibility.accumulate(image, w, h, { meshDepth: depth, modelDepth: s.rasterizer.getDepthTextureView(depthKind),
+          modelWeightSum: s.rasterizer.getDepthTextureView('weight_sum'), minWeightSum, threshold });
+        totals.push(visibility.stats());
+      }, () => { visibility.reset(src.F); totals.length = 0; }, what);
+      dev.synchronize();
+    } catch (e) {
+      visibility.destroy();
+      throw e;
+    } finally { rasterizer.destroy(); depth.destroy(); image.destroy(); }
+    return { visibility, ids, totals };
+  }
+  /** Which faces of `mesh` (hip.rasterizeMesh's: typed arrays or an object of HipBuffers) the views see, and where the model agrees with them: per view the
+   *  mesh is rasterized under the view's camera and its face image accumulated (hip.FaceVisibility) beside the mesh's depth and the model's depthKind depth
+   *  map.  options: { viewIds, split = 'train', depthKind = 'median', threshold = 0.05, minWeightSum = 0.5, near, cull }.  Returns { iteration, views,
+   *  counters: Uint32Array[3 F] (pixels, agreeing, views per face), counted, agreeing, foreign (one entry per view), ms }.  hip.selectFaces turns the counters
+   *  into a mask and hip.filterFaces applies it; cullMesh does both on the device.  Rendered through evaluate's passes with its isolation.  Same results as
+   *  the Python host's. */
+  meshVisibility(mesh, options) {
+    const o = options || {}, t0 = Date.now(), src = hip.meshOnDevice(this.device, mesh, 'meshVisibility');
+    let acc = null;
+    try {
+      acc = this.faceVisibilityOver('meshVisibility', src, o);
+      return Object.assign({ iteration: this.trainer.iteration, views: acc.ids, counters: acc.visibility.read() }, perView(acc.totals), { ms: Date.now() - t0 });
+    } finally {
+      if (acc) acc.visibility.destroy();
+      if (src.own) { src.vertices.destroy(); src.faces.destroy(); }
+    }
+  }
+  /** `mesh` without the faces the views do not see: meshVisibility's counters, hip.selectFaces' rule on them and hip.filterFaces, with flags and compaction on
+   *  the device.  options: the rule { minPixels = 1, minViews = 1, minAgreeing = 0, minAgreeingFraction = 0 } and meshVisibility's options.  Returns
+   *  filterFaces' object (colours / keys of a typed-array mesh gathered through vertexMap) with counters, the counters of the input's faces, and views added.
+   *  Same results as the Python host's. */
+  cullMesh(mesh, options) {
+    const o = options || {}, dev = this.device;
+    hip.selectFaces(new Uint32Array(0), o);   // (the rule is checked before anything is rendered)
+    const src = hip.meshOnDevice(dev, mesh, 'cullMesh');
+    let acc = null, keep = null, out;
+    try {
+      acc = this.faceVisibilityOver('cullMesh', src, o);
+      keep = dev.createBuffer({ size: Math.max(src.F, 8), label: 'face keep flags' });
+      acc.visibility.flags(keep, o);
+      out = hip.filterFaces(dev, { vertices: src.vertices, faces: src.faces, numVertices: src.V, numFaces: src.F }, keep);
+      out.counters = acc.visibility.read();
+      out.views = acc.ids;
+    } finally {
+      if (acc) acc.visibility.destroy();
+      if (keep) keep.destroy();
+      if (src.own) { src.vertices.destroy(); src.faces.destroy(); }
+    }
+    hip.gatherVertexAttributes(mesh, out);
+    return out;
+  }
+
   // ---------------------------------------------------------------- TSDF fusion and mesh extraction (DESIGN.md section 13)
   /** Fuses the current model's depth maps into `volume` (hip.TSDFVolume): for each view in the order given, the forward pass, rasterize,
    *  encodeDepth([depthKind, 'weight_sum']) and volume.integrate with the weight sum and the rasterizer's output texture as colour (where the volume
@@ -273,6 +353,11 @@ class Evaluator {
     const o = options || {}, weld = o.weld || 'host';
     if (weld !== 'host' && weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
     const unset = (x) => x === undefined || x === null;
+    if (!unset(o.cull)) {   // (DESIGN.md section 21: after welding and component removal, before smooth, simplify and normals)
+      const mesh = this.extractMesh(lo, hi, voxelSize, Object.assign({}, o, { cull: null, simplify: null, smooth: null, normals: false }));
+      const culled = this.cullMesh(mesh, Object.assign({ viewIds: o.viewIds, split: o.split, depthKind: o.depthKind }, o.cull));
+      return hip.finishMesh(this.device, culled, Float32Array.from(lo), unset(o.smooth) ? null : o.smooth, unset(o.simplify) ? null : o.simplify, !!o.normals);
+    }
     const everything = unset(o.keepLargest) && !(o.minTriangles > 0) && !(o.minFraction > 0);
     const rule = { keepLargest: o.keepLargest, minTriangles: o.minTriangles, minFraction: o.minFraction };
     if (!unset(o.simplify) || !unset(o.smooth) || o.normals) return this.extractFinished(lo, hi, voxelSize, o, weld, everything, rule);

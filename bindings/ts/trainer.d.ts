@@ -70,22 +70,30 @@ export class Trainer {
   /** A mesh rasterized under each view against the model's own depth map of that view: per-view and summed counts of the pixels where both, the mesh alone
    *  (onlyA) and the model alone (onlyB: a hole in the mesh) have a depth, and the mean absolute difference; training untouched.  No reference counterpart. */
   meshDepthAgreement(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: MeshDepthAgreementOptions): MeshDepthAgreementResult;
+  /** Which faces of a mesh the views see: per face the pixels that show it over all views, those of them where the model's depth map agrees with the mesh's
+   *  depth, and the views that show it; per view the pixels counted, agreeing and foreign.  Training untouched.  No reference counterpart. */
+  meshVisibility(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: MeshVisibilityOptions): MeshVisibilityResult;
+  /** The mesh without the faces the views do not see: meshVisibility's counters, selectFaces' rule and filterFaces, flags and compaction on the device; its
+   *  object carries the input's counters and the views.  Training untouched.  No reference counterpart. */
+  cullMesh(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: CullMeshOptions):
+    import('./webdgs_hip').FilteredMesh & { counters: Uint32Array; views: number[] };
   /** Fuses the current model's depth maps (and the rendered colour) into a TSDFVolume, view by view in the order given; rendered through evaluate's
    *  passes, training untouched.  Returns the view list.  No reference counterpart. */
   fuseDepth(volume: import('./webdgs_hip').TSDFVolume, viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): number[];
   /** TSDFVolume.fromBounds -> fuseDepth -> extractMesh -> destroy: the current model as a triangle mesh of the box [lo, hi]; with keepLargest, minTriangles or
    *  minFraction set, without the components removeSmallComponents drops.  weld: 'host' (default) or 'device' -- welded, and with a component rule cleaned,
    *  on the device; the same bytes.  simplify: a cell size -- the mesh is simplified last, by vertex clustering on that grid from lo (simplifyMesh), and
-   *  its object is returned.  No reference counterpart. */
+   *  its object is returned.  cull: cullMesh's options -- the faces no view sees are removed after welding and component removal and before smooth, simplify
+   *  and normals.  No reference counterpart. */
   extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number,
               options?: { viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected'; minWeight?: number; truncation?: number; maxWeight?: number;
-                          colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean } & import('./webdgs_hip').ComponentSelection):
-    import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh | import('./webdgs_hip').SimplifiedMesh;
+                          colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null } & import('./webdgs_hip').ComponentSelection):
+    import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh | import('./webdgs_hip').SimplifiedMesh | import('./webdgs_hip').FilteredMesh;
   /** extractMesh -> sampleMesh -> geometryMetrics against `reference` (points [M*3], or the path of a PLY): the mesh's accuracy, completeness, Chamfer
    *  distance, precision, recall and F-score, with the mesh's vertex, face and sample counts and ms.  Training untouched.  No reference counterpart. */
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,
                    options?: { density?: number | null; seed?: number; viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected';
-                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean } &
+                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null } &
                      import('./webdgs_hip').ComponentSelection):
     import('./webdgs_hip').GeometryMetrics & { vertices: number; faces: number; samples: number; ms: number };
   /** Per-Gaussian render contribution accumulated over the views (default: all training views); no reference counterpart. */
@@ -117,6 +125,14 @@ export interface MeshDepthAgreementOptions {
 export interface MeshDepthAgreementResult {
   iteration: number; views: number[]; both: number[]; onlyA: number[]; onlyB: number[]; within: number[]; sum_q: number[]; mean: number[];
   total: import('./webdgs_hip').DepthAgreement; ms: number;
+}
+export interface MeshVisibilityOptions {
+  viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected'; threshold?: number; minWeightSum?: number; near?: number;
+  cull?: 'none' | 'back' | 'front';
+}
+export type CullMeshOptions = MeshVisibilityOptions & import('./webdgs_hip').FaceRule;
+export interface MeshVisibilityResult {
+  iteration: number; views: number[]; counters: Uint32Array; counted: number[]; agreeing: number[]; foreign: number[]; ms: number;
 }
 export interface NormalConsistencyResult {
   iteration: number; views: number[]; value: number[]; pixels: number[]; sum_e: number[]; sum_a: number[]; mean: number; ms: number;

@@ -708,6 +708,10 @@ class Trainer {
   normalConsistency(viewIds, split, depthKind) { return this.evaluator.normalConsistency(viewIds, split, depthKind); }
   /** Evaluator.meshDepthAgreement: a mesh rasterized under each view against the model's own depth map of that view. */
   meshDepthAgreement(mesh, options) { return this.evaluator.meshDepthAgreement(mesh, options); }
+  /** Evaluator.meshVisibility: per face of a mesh the pixels and views that show it, and the pixels where the model's depth agrees. */
+  meshVisibility(mesh, options) { return this.evaluator.meshVisibility(mesh, options); }
+  /** Evaluator.cullMesh: a mesh without the faces the views do not see (flags and compaction on the device). */
+  cullMesh(mesh, options) { return this.evaluator.cullMesh(mesh, options); }
   /** Evaluator.fuseDepth: fuses the current model's depth maps into `volume`. */
   fuseDepth(volume, viewIds, split, depthKind) { return this.evaluator.fuseDepth(volume, viewIds, split, depthKind); }
   /** Evaluator.evaluateGeometry: the extracted mesh scored against a reference point set. */

@@ -416,6 +416,48 @@ export function selectComponents(triangles: ArrayLike<number>, options?: Compone
 /** The mesh without the components selectComponents does not keep; colours and keys follow vertexMap.  No reference counterpart. */
 export function removeSmallComponents(device: HipDevice, mesh: { vertices: Float32Array | HipBuffer; faces: Uint32Array | HipBuffer; colours?: Uint8Array | null;
                                       keys?: BigUint64Array | null }, options?: ComponentSelection): CompactedMesh;
+/** The rule on per-face counters: pixels >= minPixels (1), views >= minViews (1), agreeing >= minAgreeing (0) and agreeing 65536 >=
+ *  rint(minAgreeingFraction 65536) pixels (0). */
+export interface FaceRule { minPixels?: number; minViews?: number; minAgreeing?: number; minAgreeingFraction?: number }
+export interface FaceVisibilityStats { views: number; foreignPixels: number; countedPixels: number; agreeingPixels: number }
+export interface FilteredMesh { vertices: Float32Array; faces: Uint32Array; vertexMap: Uint32Array; faceMap: Uint32Array; invalidFaces: number;
+                                colours?: Uint8Array | null; keys?: BigUint64Array | null }
+export interface FilteredMeshBuffers { vertices: HipBuffer; faces: HipBuffer; vertexMap: HipBuffer; faceMap: HipBuffer; numVertices: number; numFaces: number;
+                                       invalidFaces: number }
+/** Per-face counters over views (wdgs_face_visibility): u32[F][3] = { pixels, agreeing, views }, integer sums of the rasterizer's face images.  No reference
+ *  counterpart. */
+export class FaceVisibility {
+  constructor(device: HipDevice);
+  readonly numFaces: number;
+  reset(numFaces: number): void;
+  accumulate(faceImage: HipBuffer | null, width: number, height: number, options?: { meshDepth?: HipBuffer | null; modelDepth?: HipBuffer | null;
+             modelWeightSum?: HipBuffer | null; minWeightSum?: number; threshold?: number }): void;
+  buffer(): HipBuffer | null;
+  read(): Uint32Array;
+  flags(keep: HipBuffer | null, rule?: FaceRule): void;
+  stats(): FaceVisibilityStats;
+  destroy(): void;
+}
+/** keep u8[numFaces] from counters u32[numFaces][3], both on the device, by the rule.  Stream-ordered.  No reference counterpart. */
+export function encodeFaceVisibilityFlags(device: HipDevice, counters: HipBuffer | null, numFaces: number, keep: HipBuffer | null, rule?: FaceRule): void;
+/** Which faces to keep (Uint8Array[F] of 0 / 1) from counters Uint32Array[3 F]: the host restatement of FaceVisibility.flags.  No reference counterpart. */
+export function selectFaces(counters: ArrayLike<number>, rule?: FaceRule): Uint8Array;
+/** MeshComponents' compaction for an arbitrary face mask (wdgs_mesh_face_filter): select, compact.  No reference counterpart. */
+export class MeshFaceFilter {
+  constructor(device: HipDevice);
+  select(faces: HipBuffer | null, numFaces: number, numVertices: number, keep: HipBuffer | null): { vertices: number; faces: number; invalidFaces: number };
+  compact(vertices: HipBuffer | null, verticesOut: HipBuffer | null, facesOut: HipBuffer | null, vertexMap?: HipBuffer | null, faceMap?: HipBuffer | null,
+          capacityVertices?: number | null, capacityFaces?: number | null): void;
+  destroy(): void;
+}
+/** The mesh without the faces whose flag is zero and the vertices no kept face names; colours and keys follow vertexMap.  No reference counterpart. */
+export function filterFaces(device: HipDevice, mesh: MeshArrays | MeshBuffers, keep: ArrayLike<number | boolean> | HipBuffer, options?: { asBuffers?: false }): FilteredMesh;
+export function filterFaces(device: HipDevice, mesh: MeshArrays | MeshBuffers, keep: ArrayLike<number | boolean> | HipBuffer, options: { asBuffers: true }): FilteredMeshBuffers;
+/** Which faces of a mesh the cameras see, without a model: every camera's face image rasterized and accumulated.  No reference counterpart. */
+export function faceVisibility(device: HipDevice, mesh: MeshArrays | MeshBuffers, cameras: Array<Float32Array | HipBuffer>, width: number, height: number,
+                               options?: { near?: number; cull?: 'none' | 'back' | 'front' }): { counters: Uint32Array; stats: FaceVisibilityStats };
+/** colours and keys of a typed-array mesh gathered through out.vertexMap into out. */
+export function gatherVertexAttributes(mesh: { colours?: unknown; keys?: unknown }, out: { vertexMap: Uint32Array; colours?: Uint8Array | null; keys?: BigUint64Array | null }): void;
 /** A uniform grid over points for exact nearest-point queries under a cutoff (wdgs_point_index); the cell edge is a speed parameter only.  No reference
  *  counterpart. */
 export class PointIndex {

@@ -1289,6 +1289,170 @@ function removeSmallComponents(device, mesh, options) {
   if (mesh.keys !== undefined) out.keys = mesh.keys ? BigUint64Array.from(out.vertexMap, (old) => mesh.keys[old]) : null;
   return out;
 }
+// ---------------------------------------------------------------- per-face visibility and removal of unseen faces (include/webdgs.h, DESIGN.md section 21)
+const VISIBILITY_STATS = ['views', 'foreignPixels', 'countedPixels', 'agreeingPixels'];
+const invalidArgument = (message) => { const e = new Error(message); e.code = 'WDGS_E'; return e; };
+/** rint(fraction 65536) for a fraction in [0, 1], ties to even: what wdgs_face_visibility_flags compares with. */
+function fractionQ16(fraction, what) {
+  const x = fraction === undefined || fraction === null ? 0 : Number(fraction);
+  if (!(x >= 0 && x <= 1)) throw invalidArgument(`${what}: minAgreeingFraction ${fraction} is not in [0, 1]`);
+  const y = x * 65536, f = Math.floor(y), d = y - f;
+  return d > 0.5 || (d === 0.5 && f % 2 === 1) ? f + 1 : f;
+}
+/** [minPixels, minViews, minAgreeing, q16] of a rule { minPixels = 1, minViews = 1, minAgreeing = 0, minAgreeingFraction = 0 }. */
+function faceRule(rule, what) {
+  const o = rule || {}, pick = (v, d) => (v === undefined || v === null ? d : v);
+  const counts = [pick(o.minPixels, 1), pick(o.minViews, 1), pick(o.minAgreeing, 0)];
+  if (!counts.every((x) => Number.isInteger(x) && x >= 0 && x < 2 ** 32)) throw invalidArgument(`${what}: minPixels, minViews, minAgreeing ${counts} must fit 32 unsigned bits`);
+  return counts.concat([fractionQ16(o.minAgreeingFraction, what)]);
+}
+/** Per-face counters over views (wdgs_face_visibility): reset sizes them for a mesh, accumulate adds one view -- the face image MeshRasterizer.encode wrote
+ *  and, optionally, the mesh's and the model's depth images -- read / buffer hand out u32[F][3] = { pixels, agreeing, views }, flags applies the rule on the
+ *  device and stats reads the totals.  Integer sums: every byte is a function of the inputs.  faceVisibility is the one-call form without a model. */
+class FaceVisibility {
+  constructor(device) { this.device = device; this.destroyed = false; this.numFaces = 0; this.handle = addon.faceVisibilityCreate(device.handle); }
+  /** Sizes and zeroes the counters for numFaces faces; the accumulated views start at 0.  A call that grows the arrays waits once. */
+  reset(numFaces) { addon.faceVisibilityReset(this.handle, numFaces); this.numFaces = numFaces; }
+  /** One view of width x height: faceImage u32, and both or neither of options.meshDepth and options.modelDepth f32 (options.modelWeightSum beside them,
+   *  optional; options.minWeightSum = 0, options.threshold = 0.05).  Stream-ordered, recordable.  WDGS_E_CAPACITY, with nothing written, when one more view
+   *  of this size could carry a pixel count past 32 bits. */
+  accumulate(faceImage, width, height, options) {
+    const o = options || {};
+    if (width >= 1 && width <= MESH_RASTER_MAX_SIZE && height >= 1 && height <= MESH_RASTER_MAX_SIZE) {
+      for (const b of [faceImage, o.meshDepth, o.modelDepth, o.modelWeightSum]) if (b && b.size < 4 * width * height) throw new Error(`FaceVisibility.accumulate: an image is too small for ${width}x${height}`);
+    }
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.faceVisibilityAccumulate(this.handle, ptr(faceImage), ptr(o.meshDepth), ptr(o.modelDepth), ptr(o.modelWeightSum), Math.fround(o.minWeightSum || 0),
+      Math.fround(o.threshold === undefined || o.threshold === null ? 0.05 : o.threshold), width, height);
+  }
+  /** The counters u32[F][3] on the device as of this call (one launch writes them; null for no faces), valid until the next buffer, read, reset or destroy. */
+  buffer() {
+    const p = addon.faceVisibilityGet(this.handle);
+    return this.numFaces ? this.device.view(p, 12 * this.numFaces) : null;
+  }
+  /** The counters as a Uint32Array[3 F]: pixels, agreeing, views per face (waits). */
+  read() { const b = this.buffer(); return new Uint32Array(b ? this.device.readBuffer(b, 12 * this.numFaces) : new ArrayBuffer(0)); }
+  /** keep u8[F] on the device from the current counters, by selectFaces' rule.  Stream-ordered, recordable. */
+  flags(keep, rule) { encodeFaceVisibilityFlags(this.device, this.buffer(), this.numFaces, keep, rule); }
+  /** { views, foreignPixels, countedPixels, agreeingPixels } since the reset (waits). */
+  stats() { const r = addon.faceVisibilityStats(this.handle), out = {}; VISIBILITY_STATS.forEach((k, i) => { out[k] = r[i]; }); return out; }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.faceVisibilityDestroy(this.handle); this.handle = null; }
+}
+/** wdgs_face_visibility_flags: keep u8[numFaces] from counters u32[numFaces][3], both on the device.  Stream-ordered, recordable. */
+function encodeFaceVisibilityFlags(device, counters, numFaces, keep, rule) {
+  const r = faceRule(rule, 'faceVisibilityFlags');
+  if (numFaces < 2 ** 31 && ((counters && counters.size < 12 * numFaces) || (keep && keep.size < numFaces))) throw new Error('faceVisibilityFlags: buffers too small for the faces');
+  addon.faceVisibilityFlags(device.handle, counters ? counters.ptr : null, numFaces, r[0], r[1], r[2], r[3], keep ? keep.ptr : null);
+}
+/** Which faces to keep, a Uint8Array[F] of 0 / 1, from counters Uint32Array[3 F] = { pixels, agreeing, views } per face: pixels >= minPixels, views >= minViews,
+ *  agreeing >= minAgreeing and agreeing 65536 >= rint(minAgreeingFraction 65536) pixels in 64-bit integers.  The host restatement of FaceVisibility.flags. */
+function selectFaces(counters, rule) {
+  const r = faceRule(rule, 'selectFaces'), F = Math.floor(counters.length / 3), keep = new Uint8Array(F), q16 = BigInt(r[3]);
+  for (let f = 0; f < F; f++) {
+    const pixels = counters[3 * f], agreeing = counters[3 * f + 1], views = counters[3 * f + 2];
+    keep[f] = pixels >= r[0] && views >= r[1] && agreeing >= r[2] && BigInt(agreeing) * 65536n >= q16 * BigInt(pixels) ? 1 : 0;
+  }
+  return keep;
+}
+/** MeshComponents' compaction for an arbitrary face mask (wdgs_mesh_face_filter): select takes the faces and a u8 flag per face on the device, compact writes
+ *  the kept part.  filterFaces is the one-call form. */
+class MeshFaceFilter {
+  constructor(device) { this.device = device; this.destroyed = false; this.handle = addon.meshFaceFilterCreate(device.handle); }
+  /** { vertices, faces, invalidFaces }: the numbers kept of faces u32[numFaces][3] over numVertices vertices under keep u8[numFaces], and the faces that name
+   *  no vertex (flags, scans; waits). */
+  select(faces, numFaces, numVertices, keep) {
+    if (numFaces < 2 ** 31 && ((faces && faces.size < 12 * numFaces) || (keep && keep.size < numFaces))) throw new Error('MeshFaceFilter.select: buffers too small for the faces');
+    const r = addon.meshFaceFilterSelect(this.handle, faces ? faces.ptr : null, numFaces, numVertices, keep ? keep.ptr : null);
+    return { vertices: r[0], faces: r[1], invalidFaces: r[2] };
+  }
+  /** MeshComponents.compact's arguments and rules for the last select.  Stream-ordered, recordable. */
+  compact(vertices, verticesOut, facesOut, vertexMap, faceMap, capacityVertices, capacityFaces) {
+    const room = (pairs) => Math.min(0xFFFFFFFF, ...pairs.filter(([b]) => b).map(([b, s]) => Math.floor(b.size / s)));
+    const cv = capacityVertices === undefined || capacityVertices === null ? room([[verticesOut, 12], [vertexMap, 4]]) : capacityVertices;
+    const cf = capacityFaces === undefined || capacityFaces === null ? room([[facesOut, 12], [faceMap, 4]]) : capacityFaces;
+    for (const [b, s, n] of [[verticesOut, 12, cv], [vertexMap, 4, cv], [facesOut, 12, cf], [faceMap, 4, cf]]) {
+      if (b && n * s > b.size) throw new Error('MeshFaceFilter.compact: the capacity exceeds the buffers');
+    }
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshFaceFilterCompact(this.handle, ptr(vertices), ptr(verticesOut), ptr(facesOut), ptr(vertexMap), ptr(faceMap), cv, cf);
+  }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.meshFaceFilterDestroy(this.handle); this.handle = null; }
+}
+/** `mesh` without the faces whose keep flag (an array of F truthy / falsy values, or a u8[F] HipBuffer) is zero, and without the vertices no kept face names:
+ *  { vertices, faces, vertexMap, faceMap, invalidFaces } and colours / keys gathered through vertexMap when the input has them -- removeSmallComponents' shape
+ *  and rules.  `mesh`: typed arrays, or an object of HipBuffers as meshOnDevice takes (left as it is).  options.asBuffers: the four arrays stay on the device
+ *  as HipBuffers (of at least one element's size) with numVertices and numFaces; colours and keys are not gathered; the caller destroys them. */
+function filterFaces(device, mesh, keep, options) {
+  const src = meshOnDevice(device, mesh, 'filterFaces');
+  const outs = [];
+  let kbuf = keep, ownKeep = false, filt = null, out;
+  try {
+    if (!(keep instanceof HipBuffer)) {
+      if (keep.length !== src.F) throw new Error(`filterFaces: ${keep.length} flags for ${src.F} faces`);
+      kbuf = device.createBuffer({ size: Math.max(src.F, 8), label: 'filterFaces: flags' }); ownKeep = true;
+      if (src.F) device.queue.writeBuffer(kbuf, 0, Uint8Array.from(keep, (k) => (k ? 1 : 0)));
+    }
+    filt = new MeshFaceFilter(device);
+    const kept = filt.select(src.faces, src.F, src.V, kbuf);
+    for (const n of [12 * kept.vertices, 12 * kept.faces, 4 * kept.vertices, 4 * kept.faces]) outs.push(device.createBuffer({ size: Math.max(n, 4), label: 'filtered mesh' }));
+    filt.compact(src.vertices, outs[0], outs[1], outs[2], outs[3], kept.vertices, kept.faces);
+    if (options && options.asBuffers) {
+      device.synchronize();   // (an uploaded mesh is released below)
+      const result = { vertices: outs[0], faces: outs[1], vertexMap: outs[2], faceMap: outs[3], numVertices: kept.vertices, numFaces: kept.faces, invalidFaces: kept.invalidFaces };
+      outs.length = 0;
+      return result;
+    }
+    const bytes = (b, n) => (n ? device.readBuffer(b, n) : new ArrayBuffer(0));
+    out = { vertices: new Float32Array(bytes(outs[0], 12 * kept.vertices)), faces: new Uint32Array(bytes(outs[1], 12 * kept.faces)),
+      vertexMap: new Uint32Array(bytes(outs[2], 4 * kept.vertices)), faceMap: new Uint32Array(bytes(outs[3], 4 * kept.faces)), invalidFaces: kept.invalidFaces };
+  } finally {
+    if (filt) filt.destroy();
+    if (src.own) { src.vertices.destroy(); src.faces.destroy(); }
+    if (ownKeep) kbuf.destroy();
+    outs.forEach((b) => b.destroy());
+  }
+  gatherVertexAttributes(mesh, out);
+  return out;
+}
+/** colours (three bytes per vertex) and keys of a typed-array mesh, gathered through out.vertexMap into out. */
+function gatherVertexAttributes(mesh, out) {
+  if (mesh.colours !== undefined && !(mesh.colours instanceof HipBuffer)) {
+    out.colours = mesh.colours ? new Uint8Array(3 * out.vertexMap.length) : null;
+    if (out.colours) out.vertexMap.forEach((old, i) => { for (let a = 0; a < 3; a++) out.colours[3 * i + a] = mesh.colours[3 * old + a]; });
+  }
+  if (mesh.keys !== undefined && !(mesh.keys instanceof HipBuffer)) out.keys = mesh.keys ? BigUint64Array.from(out.vertexMap, (old) => mesh.keys[old]) : null;
+}
+/** Which faces of `mesh` the `cameras` (68-float blocks: Float32Arrays or HipBuffers) see, without a model: every camera's face image is rasterized at
+ *  width x height and accumulated.  { counters: Uint32Array[3 F], stats }; agreeing equals pixels here.  options: { near = MESH_RASTER_NEAR, cull = 'none' }.
+ *  selectFaces and filterFaces take it from there. */
+function faceVisibility(device, mesh, cameras, width, height, options) {
+  const o = options || {}, src = meshOnDevice(device, mesh, 'faceVisibility');
+  let rasterizer = null, visibility = null, image = null;
+  try {
+    rasterizer = new MeshRasterizer(device); visibility = new FaceVisibility(device);
+    visibility.reset(src.F);
+    const npix = width >= 1 && width <= MESH_RASTER_MAX_SIZE && height >= 1 && height <= MESH_RASTER_MAX_SIZE ? width * height : 0;
+    image = device.createBuffer({ size: Math.max(4 * npix, 16), label: 'mesh face image' });
+    for (const camera of cameras) {
+      let cam = camera;
+      if (!(camera instanceof HipBuffer)) {
+        if (camera.length !== 68) throw new Error(`faceVisibility: the camera block has 68 floats, got ${camera.length}`);
+        cam = device.createBuffer({ size: 272 });
+        device.queue.writeBuffer(cam, 0, camera instanceof Float32Array ? camera : Float32Array.from(camera));
+      }
+      try {
+        rasterizer.encode(src.vertices, src.V, src.faces, src.F, null, cam, width, height, { near: o.near, cull: o.cull, face: image });
+        visibility.accumulate(image, width, height);
+      } finally {
+        if (cam !== camera) { device.synchronize(); cam.destroy(); }
+      }
+    }
+    return { counters: visibility.read(), stats: visibility.stats() };
+  } finally {
+    for (const x of [visibility, rasterizer, image]) if (x) x.destroy();
+    if (src.own) { src.vertices.destroy(); src.faces.destroy(); }
+  }
+}
 /** A uniform grid over `points` ([M*3] Float32Array, or a HipBuffer) for exact nearest-point queries under a cutoff (wdgs_point_index).  options:
  *  { cellSize, count }.  cellSize is a speed parameter only -- no result depends on it; without one it is chosen by the first query (its cutoff, or less
  *  for many points), which then finishes the build.  Non-finite points are left out.  The build waits once; queries are stream-ordered. */
@@ -1518,4 +1682,4 @@ const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, MeshWelder, weldTrianglesDevice, destroyBuffers, MeshSimplifier, simplifyMesh, MeshAdjacency, meshAdjacency, smoothMesh, vertexNormals, finishMesh, CULL_MODES, MESH_RASTER_LARGE_FACE_PIXELS, MESH_RASTER_NEAR, NO_FACE, MeshRasterizer, rasterizeMesh, encodeDepthAgreement, depthAgreementResult, depthAgreement, meshOnDevice, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
   geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, grownTileEntries, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
-  DensifyPrunePass, downsampleRGBA8 };
+  DensifyPrunePass, downsampleRGBA8, FaceVisibility, MeshFaceFilter, encodeFaceVisibilityFlags, selectFaces, filterFaces, faceVisibility, gatherVertexAttributes };

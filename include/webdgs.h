@@ -975,6 +975,68 @@ int wdgs_mesh_rasterizer_stats(wdgs_mesh_rasterizer* rasterizer, uint32_t* inval
 int wdgs_depth_agreement(wdgs_device* dev, const void* a_f32_dev, const void* b_f32_dev, const void* b_weight_sum_f32_dev, float min_weight_sum, uint32_t width,
                          uint32_t height, float max_difference, float threshold, void* out_u64x5_dev);
 
+/* ---------------------------------------------------------------- Per-face visibility over views, and removal of unseen faces
+ *
+ * Three parts: an accumulator of the rasterizer's face images into per-face counters, a rule that turns counters into keep flags, and a face filter that
+ * compacts a mesh by any mask.  Integer work throughout; every output byte is a function of the inputs alone.  No reference counterpart.
+ *
+ * THE ACCUMULATOR holds, for a mesh of F faces (0 <= F < 2^31), counters u32[F][3] = { pixels, agreeing, views }, and four totals.  One accumulate call takes
+ * one VIEW: face_image u32[W H] (what wdgs_mesh_rasterizer_encode writes), and either both or neither of mesh_depth f32[W H] (the same encode's depth image)
+ * and model_depth f32[W H], with model_weight_sum f32[W H] nullable beside them.  Only counts matter, so the image is read as one row of W H pixels.  For pixel p,
+ * f = face_image[p]:
+ *   f < F            the pixel is COUNTED: pixels[f] += 1, counted_pixels += 1;
+ *   f = 0xFFFFFFFF   the pixel is EMPTY: nothing;
+ *   any other f      the pixel is FOREIGN: foreign_pixels += 1; f is never used as an address.
+ * A counted pixel AGREES when both depth images are given and wdgs_depth_agreement's presence rule holds for both, in that function's f32 operations:
+ * a = mesh_depth[p] finite and > 0; b = model_depth[p] finite and > 0 and, when the weight sum is given, model_weight_sum[p] >= min_weight_sum; and
+ * |a - b| <= threshold, the subtraction rounded once to f32.  With both depth pointers null every counted pixel agrees.  An agreeing pixel: agreeing[f] += 1,
+ * agreeing_pixels += 1.  views[f] += 1 exactly once per call in which f has at least one counted pixel; the accumulated views += 1 per call.
+ * OVERFLOW IS REFUSED, NOT SATURATED: a call returns WDGS_E_CAPACITY, with nothing written, when (views accumulated so far + 1) W H >= 2^32, in host arithmetic
+ * on the calls made (a recorded call counts once when recorded; stats brings the host's count up to the device's), so that no pixel count can reach 2^32.
+ * WDGS_E_INVALID, with nothing written: W or H outside 1 .. WDGS_MESH_RASTER_MAX_SIZE; threshold not finite and > 0 (also in the null-depth form, which does
+ * not use it); exactly one depth pointer null, or a weight sum without depths; a null face image; an image pointer that is not 16-byte aligned.  The checks
+ * are made in this order, the capacity check before the face image's. */
+typedef struct wdgs_face_visibility wdgs_face_visibility;
+int wdgs_face_visibility_create(wdgs_device* dev, wdgs_face_visibility** out);
+int wdgs_face_visibility_destroy(wdgs_face_visibility* visibility);
+/* Sizes the object's arrays for num_faces faces -- 28 bytes per face, grown as needed and reused -- and zeroes them, the totals and the accumulated views.
+ * Stream-ordered and recordable, except a call that has to grow the arrays: that one waits once and cannot be recorded (WDGS_E_STATE). */
+int wdgs_face_visibility_reset(wdgs_face_visibility* visibility, uint32_t num_faces);
+/* One view, as defined above.  Stream-ordered, no host wait, recordable (a replay is one more view).  WDGS_E_STATE before a reset.  The kernels' event times
+ * are the device's (wdgs_device_get_kernel_times): face_visibility_accumulate, face_visibility_advance. */
+int wdgs_face_visibility_accumulate(wdgs_face_visibility* visibility, const void* face_image_u32_dev, const void* mesh_depth_f32_dev, const void* model_depth_f32_dev,
+                                    const void* model_weight_sum_f32_dev, float min_weight_sum, float threshold, uint32_t width, uint32_t height);
+/* The device pointer to counters u32[F][3] (null for F = 0): the counts of every accumulate enqueued before this call, written by one launch this call
+ * enqueues (the pixel and agreeing counts are kept as the halves of one 64-bit word per face, so that a run of pixels is one add), complete once the stream
+ * has run and valid until the next get, reset or destroy.  Stream-ordered, no host wait, recordable.  WDGS_E_STATE before a reset. */
+int wdgs_face_visibility_get(wdgs_face_visibility* visibility, void** counters_u32_dev);
+/* The totals since the reset, each pointer nullable: the accumulated views, foreign_pixels, counted_pixels, agreeing_pixels.  Copies one block back and waits,
+ * so it cannot be recorded (WDGS_E_STATE, also before a reset). */
+int wdgs_face_visibility_stats(wdgs_face_visibility* visibility, uint64_t* views, uint64_t* foreign_pixels, uint64_t* counted_pixels, uint64_t* agreeing_pixels);
+/* THE RULE.  keep u8[F]: keep[f] = 1 when pixels >= min_pixels and views >= min_views and agreeing >= min_agreeing and
+ * agreeing 65536 >= min_agreeing_q16 pixels (both products in u64), else 0, for counters u32[F][3] anywhere on the device.  min_agreeing_q16 is a fraction of
+ * 65536, at most 65536 (WDGS_E_INVALID; F >= 2^31 likewise); the hosts convert a fraction in [0, 1] with rint(fraction 65536).  A face with pixels = 0 passes the
+ * fourth test and fails the first unless min_pixels = 0.  Stream-ordered, no host wait, recordable. */
+int wdgs_face_visibility_flags(wdgs_device* dev, const void* counters_u32_dev, uint32_t num_faces, uint32_t min_pixels, uint32_t min_views, uint32_t min_agreeing,
+                               uint32_t min_agreeing_q16, void* keep_u8_dev);
+/* THE FILTER: wdgs_mesh_components' compaction for an arbitrary mask.  faces u32[F][3] over V vertices, 0 <= F, V < 2^31 (WDGS_E_INVALID otherwise), keep
+ * u8[F] on the device.  A face is KEPT when its flag is non-zero and its three indices are < V; a vertex is kept exactly when a kept face names it.  A face
+ * with an index >= V is counted in invalid_faces whatever its flag, is never kept and never read as an address. */
+typedef struct wdgs_mesh_face_filter wdgs_mesh_face_filter;
+int wdgs_mesh_face_filter_create(wdgs_device* dev, wdgs_mesh_face_filter** out);
+int wdgs_mesh_face_filter_destroy(wdgs_mesh_face_filter* filter);
+/* Flags faces and vertices into arrays the object owns (8 bytes per face and per vertex, grown as needed), scans both with the library's scan, waits and
+ * returns V', F' and the invalid faces; cannot be recorded (WDGS_E_STATE).  The flags are read here only; the faces are read again by compact and must stay as
+ * they are until then. */
+int wdgs_mesh_face_filter_select(wdgs_mesh_face_filter* filter, const void* faces_u32_dev, uint32_t num_faces, uint32_t num_vertices, const void* keep_u8_dev,
+                                 uint32_t* kept_vertices, uint32_t* kept_faces, uint32_t* invalid_faces);
+/* wdgs_mesh_components_compact's signature and rules for the last select: kept faces in their original order with their indices rewritten, faces_out
+ * u32[F'][3]; kept vertices in ascending original index, vertices_out f32[V'][3] gathered from vertices f32[V][3] (both nullable together); vertex_map u32[V']
+ * and face_map u32[F'] (each nullable).  WDGS_E_CAPACITY, with nothing written, when capacity_vertices < V' or capacity_faces < F'; WDGS_E_STATE when no select
+ * precedes it.  Stream-ordered, no host wait, recordable. */
+int wdgs_mesh_face_filter_compact(wdgs_mesh_face_filter* filter, const void* vertices_f32_dev, void* vertices_out_f32_dev, void* faces_out_u32_dev,
+                                  void* vertex_map_u32_dev, void* face_map_u32_dev, uint32_t capacity_vertices, uint32_t capacity_faces);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,17 @@ SIGNATURES = {
     "wdgs_mesh_rasterizer_encode": (_I, [_P, _P, _U, _P, _U, _P, _P, _U, _U, _F, _U, _P, _P, _P, _P]),
     "wdgs_mesh_rasterizer_stats": (_I, [_P] + [C.POINTER(_U)] * 8),
     "wdgs_depth_agreement": (_I, [_P, _P, _P, _P, _F, _U, _U, _F, _F, _P]),
+    "wdgs_face_visibility_create": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_face_visibility_destroy": (_I, [_P]),
+    "wdgs_face_visibility_reset": (_I, [_P, _U]),
+    "wdgs_face_visibility_accumulate": (_I, [_P, _P, _P, _P, _P, _F, _F, _U, _U]),
+    "wdgs_face_visibility_get": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_face_visibility_stats": (_I, [_P] + [C.POINTER(C.c_uint64)] * 4),
+    "wdgs_face_visibility_flags": (_I, [_P, _P, _U, _U, _U, _U, _U, _P]),
+    "wdgs_mesh_face_filter_create": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_mesh_face_filter_destroy": (_I, [_P]),
+    "wdgs_mesh_face_filter_select": (_I, [_P, _P, _U, _U, _P, C.POINTER(_U), C.POINTER(_U), C.POINTER(_U)]),
+    "wdgs_mesh_face_filter_compact": (_I, [_P, _P, _P, _P, _P, _P, _U, _U]),
     "wdgs_point_index_create": (_I, [_P, _P, C.c_uint64, _F, C.POINTER(_P)]),
     "wdgs_point_index_destroy": (_I, [_P]),
     "wdgs_point_index_reserve_queries": (_I, [_P, _U]),

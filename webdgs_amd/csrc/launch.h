@@ -118,6 +118,18 @@ int launch_mesh_keep_flags(wdgs_device* dev, u32 n, const u32* component, const 
 int launch_mesh_emit(wdgs_device* dev, const u32* faces, u32 F, u32 V, const u32* vertex_flags, const u32* vertex_offsets, const u32* face_flags, const u32* face_offsets,
                      const float* positions, float* positions_out, u32* vertex_map, u32* faces_out, u32* face_map);
 
+// ---- meshvisibility.hip.  face_image u32[npix]; mesh_depth, model_depth (null together) and weight_sum (nullable) f32[npix], all 16-byte aligned
+// pairs u64[F] (pixels | agreeing << 32), stamps u32[F], views u32[F], added to; state u64[4]: the views so far (advanced by one), foreign, counted, agreeing
+int launch_face_visibility_accumulate(wdgs_device* dev, const u32* face_image, const float* mesh_depth, const float* model_depth, const float* weight_sum,
+                                      float min_weight_sum, float threshold, u32 npix, u32 F, unsigned long long* pairs, u32* stamps, u32* views,
+                                      unsigned long long* state);
+// counters u32[F][3] = { pixels, agreeing, views }, written
+int launch_face_visibility_pack(wdgs_device* dev, u32 F, const unsigned long long* pairs, const u32* views, u32* counters);
+// keep u8[F], written: the rule of wdgs_face_visibility_flags
+int launch_face_visibility_flags(wdgs_device* dev, u32 F, const u32* counters, u32 min_pixels, u32 min_views, u32 min_agreeing, u32 min_agreeing_q16, unsigned char* keep);
+// face_flags u32[F] written; vertex_flags u32[V] cleared and set; invalid_faces: one word, cleared and counted into.  launch_mesh_emit writes the kept part
+int launch_face_filter_flags(wdgs_device* dev, const u32* faces, u32 F, u32 V, const unsigned char* keep, u32* face_flags, u32* vertex_flags, u32* invalid_faces);
+
 // ---- keysort.hip: the stable u64 key sort the welder (meshweld.hip) and the simplifier (meshsimplify.hip) group by; its sizing rule: keysort_sizes.h
 // The counters block, u32 words: the distinct keys, the passes run, the buffer that holds the sorted pairs, a spare, then per pass: run, input buffer, output buffer
 constexpr u32 KS_C_TOTAL = 0, KS_C_PASSES = 1, KS_C_FINAL = 2, KS_C_RUN = 4, KS_C_IN = 12, KS_C_OUT = 20, KS_C_WORDS = 28;

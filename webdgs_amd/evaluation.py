@@ -248,6 +248,119 @@ class Evaluator:
         result["ms"] = (time.perf_counter() - t0) * 1e3
         return result
 
+    # ------------------------------------------------------------------ which faces of a mesh the views see
+    def _face_visibility(self, what: str, vertices, faces, V: int, F: int, viewIds, split: str, depthKind: str, threshold: float, minWeightSum: float, near: float,
+                         cull: str) -> tuple:
+        """``(visibility, view ids, totals)``: an ``ops.FaceVisibility`` of the mesh on the device accumulated over the views -- the caller destroys it --
+        and its cumulative totals after each view.  ``meshDepthAgreement``'s loop: the rasterizer grown once, one encode and one accumulate per view."""
+        if depthKind not in ("median", "expected"):
+            raise ValueError(f"{what}: depthKind must be 'median' or 'expected', not {depthKind!r}")
+        cams, imgs, bufs, ids = self._views(what, viewIds, split)
+        self._drain()
+        dev = self.device
+        sizes = [(int(imgs[v]["width"]), int(imgs[v]["height"])) for v in ids]
+        npix = max([1] + [w * h for w, h in sizes])
+        depth, image = dev.createBuffer(4 * npix, "mesh depth"), dev.createBuffer(4 * npix, "mesh face image")
+        rasterizer, visibility = ops.MeshRasterizer(dev), ops.FaceVisibility(dev)
+        totals: list = []
+        try:
+            visibility.reset(F)
+            if sizes:   # (grown once, to the largest view, in front of the loop)
+                w, h = max(sizes, key=lambda s: s[0] * s[1])
+                rasterizer.encode(vertices, V, faces, F, None, bufs[ids[0]], w, h, near, cull, depth=depth, face=image)
+
+            def restart():
+                visibility.reset(F)
+                totals.clear()
+
+            def measure(i, v, s, w, h):
+                s.rasterizer.encodeDepth(None, (depthKind, "weight_sum"))
+                rasterizer.encode(vertices, V, faces, F, None, bufs[v], w, h, near, cull, depth=depth, face=image)
+                visibility.accumulate(image, w, h, depth, s.rasterizer.getDepthTextureView(depthKind), s.rasterizer.getDepthTextureView("weight_sum"), minWeightSum,
+                                      threshold)
+                totals.append(visibility.stats())
+            self._render_views(ids, imgs, bufs, measure, restart=restart, what=what)
+            dev.synchronize()
+        except BaseException:
+            visibility.destroy()
+            raise
+        finally:
+            rasterizer.destroy()
+            depth.destroy()
+            image.destroy()
+        return visibility, ids, totals
+
+    @staticmethod
+    def _per_view(totals: list) -> dict:
+        """The cumulative totals as per-view lists: the counted, agreeing and foreign pixels of each view."""
+        out = {}
+        for name, key in (("counted", "countedPixels"), ("agreeing", "agreeingPixels"), ("foreign", "foreignPixels")):
+            cumulative = [0] + [t[key] for t in totals]
+            out[name] = [b - a for a, b in zip(cumulative, cumulative[1:])]
+        return out
+
+    def meshVisibility(self, mesh: dict, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", threshold: float = 0.05,
+                       minWeightSum: float = 0.5, near: float = ops.MESH_RASTER_NEAR, cull: str = "none") -> dict:
+        """Which faces of ``mesh`` (``ops.rasterizeMesh``'s: numpy or a dict of ``HipBuffer``) the views see, and where the model agrees with them: per
+        view the mesh is rasterized under the view's camera and its face image accumulated (``ops.FaceVisibility``) beside the mesh's depth and the
+        model's ``depthKind`` depth map.  ``dict(iteration, views, counters u32[F,3] = {pixels, agreeing, views}, counted=[...], agreeing=[...],
+        foreign=[...], ms)``: per face the pixels that show it over all views, those of them where the model's depth is present (its weight sum at least
+        ``minWeightSum``) and within ``threshold`` of the mesh's, and the views that show it; per view the pixels counted, agreeing, and foreign (none,
+        for a face image of the same mesh).  ``ops.selectFaces`` turns the counters into a mask and ``ops.filterFaces`` applies it; ``cullMesh`` does
+        both on the device.  Where ``meshDepthAgreement`` says how far a mesh disagrees with the model, this says which faces do.
+
+        Rendered through evaluate's passes, with its isolation: the pipeline is drained, a view whose lists overflowed is rendered again (the counters
+        are reset and every view is accumulated again), no RNG draw, no training pass, no recording dropped.  Per rank with ``world_size > 1``."""
+        t0 = time.perf_counter()
+        vertices, faces, V, F, own = ops._mesh_on_device(self.device, mesh, "meshVisibility")
+        visibility = None
+        try:
+            visibility, ids, totals = self._face_visibility("meshVisibility", vertices, faces, V, F, viewIds, split, depthKind, threshold, minWeightSum, near, cull)
+            counters = visibility.read()
+        finally:
+            if visibility is not None:
+                visibility.destroy()
+            if own:
+                vertices.destroy()
+                faces.destroy()
+        return dict(iteration=self.trainer.iteration, views=ids, counters=counters, **self._per_view(totals), ms=(time.perf_counter() - t0) * 1e3)
+
+    def cullMesh(self, mesh: dict, minPixels: int = 1, minViews: int = 1, minAgreeing: int = 0, minAgreeingFraction: float = 0.0, **visibilityOptions) -> dict:
+        """``mesh`` without the faces the views do not see: ``meshVisibility(mesh, **visibilityOptions)``'s counters, ``ops.selectFaces``' rule on them and
+        ``ops.filterFaces``, with flags and compaction on the device -- the mesh crosses the bus once each way and not between counters and compaction.
+        Returns ``filterFaces``' dict (``vertices``, ``faces``, ``vertexMap``, ``faceMap``, ``invalidFaces``, and ``colours`` / ``keys`` gathered through
+        ``vertexMap`` when a numpy mesh has them) with ``counters u32[F,3]``, the counters of the input's faces, and ``views`` added.  With the defaults
+        a face stays when at least one pixel of one view shows it; ``minAgreeingFraction`` drops faces the model's depth contradicts.  ``meshVisibility``'s
+        isolation."""
+        dev = self.device
+        defaults = dict(viewIds=None, split="train", depthKind="median", threshold=0.05, minWeightSum=0.5, near=ops.MESH_RASTER_NEAR, cull="none")
+        unknown = sorted(set(visibilityOptions) - set(defaults))
+        if unknown:
+            raise TypeError(f"cullMesh: unknown options {unknown} (meshVisibility's: {sorted(defaults)})")
+        opt = dict(defaults, **visibilityOptions)
+        ops.selectFaces(np.zeros((0, 3), np.uint32), minPixels, minViews, minAgreeing, minAgreeingFraction)   # (the rule is checked before anything is rendered)
+        vertices, faces, V, F, own = ops._mesh_on_device(dev, mesh, "cullMesh")
+        visibility = keep = None
+        try:
+            visibility, ids, _ = self._face_visibility("cullMesh", vertices, faces, V, F, opt["viewIds"], opt["split"], opt["depthKind"], opt["threshold"],
+                                                       opt["minWeightSum"], opt["near"], opt["cull"])
+            keep = dev.createBuffer(max(F, 1), "face keep flags")
+            visibility.flags(keep, minPixels, minViews, minAgreeing, minAgreeingFraction)
+            out = ops.filterFaces(dev, dict(vertices=vertices, faces=faces, numVertices=V, numFaces=F), keep)
+            out["counters"] = visibility.read()
+            out["views"] = ids
+        finally:
+            for o in (visibility, keep):
+                if o is not None:
+                    o.destroy()
+            if own:
+                vertices.destroy()
+                faces.destroy()
+        for name in ("colours", "keys"):
+            if name in mesh and not isinstance(mesh[name], ops.HipBuffer):
+                out[name] = None if mesh[name] is None else np.ascontiguousarray(np.asarray(mesh[name])[out["vertexMap"]])
+        return out
+
     # ------------------------------------------------------------------ TSDF fusion and mesh extraction (DESIGN.md section 13)
     def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
         """Fuses the current model's depth maps into ``volume``: for each view in the order given, the forward pass, rasterize,
@@ -272,7 +385,7 @@ class Evaluator:
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
                     keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", simplify: Optional[float] = None,
-                    smooth: Optional[int] = None, normals: bool = False, **volumeOptions) -> dict:
+                    smooth: Optional[int] = None, normals: bool = False, cull: Optional[dict] = None, **volumeOptions) -> dict:
         """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
         ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result.
 
@@ -293,9 +406,19 @@ class Evaluator:
         ``smooth=iterations`` and ``normals=True``: ``ops.smoothMesh`` with its defaults after welding and component removal
         and BEFORE ``simplify`` -- the fine mesh is denoised, then decimated -- with ``stats`` added; and ``normals f32[V,3]``, ``ops.vertexNormals`` of
         the final mesh.  With ``weld="device"`` the positions stay on the device through both.  ``None`` and ``False``: as before, no new key and
-        nothing more launched."""
+        nothing more launched.
+
+        ``cull=dict(...)``: the faces no view sees are removed by ``cullMesh(mesh, **cull)`` -- its rule (``minPixels``,
+        ``minViews``, ``minAgreeing``, ``minAgreeingFraction``) and ``meshVisibility``'s options, with ``viewIds``, ``split`` and ``depthKind`` defaulting
+        to the extraction's own -- after welding and component removal and BEFORE ``smooth``, ``simplify`` and ``normals``, which see the boundary it
+        cuts; ``cullMesh``'s dict is what goes on (``vertexMap`` and ``faceMap`` are its own, into the mesh it was given).  The welded mesh is read and
+        handed to ``cullMesh`` as numpy with either weld, so the bytes are the same.  ``None``: as before, no new key and nothing more launched."""
         if weld not in ("host", "device"):
             raise ValueError(f"extractMesh: weld must be 'host' or 'device', not {weld!r}")
+        if cull is not None:
+            mesh = self.extractMesh(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld=weld, **volumeOptions)
+            culled = self.cullMesh(mesh, **dict(dict(viewIds=viewIds, split=split, depthKind=depthKind), **cull))
+            return ops.finishMesh(self.device, culled, np.asarray(lo, np.float64).reshape(3).astype(np.float32), smooth, simplify, normals)
         if simplify is not None or smooth is not None or normals:
             return self._extract_finished(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld, simplify,
                                           smooth, normals, volumeOptions)

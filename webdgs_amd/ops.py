@@ -1943,6 +1943,231 @@ def removeSmallComponents(device: HipDevice, mesh: dict, keepLargest: Optional[i
     return out
 
 
+# ----------------------------------------------------------------------------- per-face visibility and removal of unseen faces
+VISIBILITY_STATS = ("views", "foreignPixels", "countedPixels", "agreeingPixels")
+
+
+def _fraction_q16(fraction: float, what: str) -> int:
+    """``rint(fraction 65536)`` for a fraction in [0, 1]: what ``wdgs_face_visibility_flags`` compares with."""
+    x = float(fraction)
+    if not 0.0 <= x <= 1.0:
+        raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"{what}: minAgreeingFraction {fraction} is not in [0, 1]")
+    return int(np.rint(np.float64(x) * 65536.0))
+
+
+def _rule_counts(minPixels, minViews, minAgreeing, what: str) -> tuple:
+    rule = (int(minPixels), int(minViews), int(minAgreeing))
+    if not all(0 <= x < 2 ** 32 for x in rule):
+        raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"{what}: minPixels, minViews, minAgreeing {rule} must fit 32 unsigned bits")
+    return rule
+
+
+class FaceVisibility:
+    """Per-face counters over views (``wdgs_face_visibility``): ``reset`` sizes them for a mesh, ``accumulate`` adds one view -- the face image
+    ``MeshRasterizer.encode`` wrote and, optionally, the mesh's and the model's depth images -- ``read`` / ``buffer`` hand out ``u32[F][3]`` =
+    ``{pixels, agreeing, views}``, ``flags`` applies the rule on the device and ``stats`` reads the totals.  Integer sums: every byte is a function of
+    the inputs (include/webdgs.h states the definition).  ``faceVisibility`` is the one-call form without a model."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        self.numFaces = 0
+        h = C.c_void_p()
+        check(device.lib.wdgs_face_visibility_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def reset(self, numFaces: int) -> None:
+        """Sizes and zeroes the counters for ``numFaces`` faces; the accumulated views start at 0.  A call that grows the arrays waits once."""
+        if not 0 <= int(numFaces) < 2 ** 32:
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"FaceVisibility.reset: bad face count {numFaces}")
+        check(self.device.lib.wdgs_face_visibility_reset(self.handle, int(numFaces)))
+        self.numFaces = int(numFaces)
+
+    def accumulate(self, faceImage: Optional[HipBuffer], width: int, height: int, meshDepth: Optional[HipBuffer] = None, modelDepth: Optional[HipBuffer] = None,
+                   modelWeightSum: Optional[HipBuffer] = None, minWeightSum: float = 0.0, threshold: float = 0.05) -> None:
+        """One view of ``width`` x ``height``: ``faceImage`` u32, and both or neither of ``meshDepth`` and ``modelDepth`` f32 (``modelWeightSum`` f32
+        beside them, optional).  A pixel agrees when both depths are present (``depthAgreement``'s rule) and ``|mesh - model| <= threshold``; without
+        depth images every counted pixel agrees.  Stream-ordered, recordable.  ``CapacityError``, with nothing written, when one more view of this
+        size could carry a pixel count past 32 bits."""
+        w, h = int(width), int(height)
+        if not (0 <= w < 2 ** 32 and 0 <= h < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"FaceVisibility.accumulate: bad image size {width}x{height}")
+        if 1 <= w <= _lib.MESH_RASTER_MAX_SIZE and 1 <= h <= _lib.MESH_RASTER_MAX_SIZE:
+            for b in (faceImage, meshDepth, modelDepth, modelWeightSum):
+                if b is not None and b.size < 4 * w * h:
+                    raise ValueError(f"FaceVisibility.accumulate: an image is too small for {w}x{h}")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_face_visibility_accumulate(self.handle, ptr(faceImage), ptr(meshDepth), ptr(modelDepth), ptr(modelWeightSum), float(minWeightSum),
+                                                              float(threshold), w, h))
+
+    def buffer(self) -> Optional[HipBuffer]:
+        """The counters ``u32[F][3]`` on the device as of this call (one launch writes them; ``None`` for no faces), valid until the next ``buffer``,
+        ``read``, ``reset`` or ``destroy``.  Stream-ordered, recordable."""
+        p = C.c_void_p()
+        check(self.device.lib.wdgs_face_visibility_get(self.handle, C.byref(p)))
+        return self.device.view(p.value, 12 * self.numFaces, "face visibility counters") if self.numFaces else None
+
+    def read(self) -> np.ndarray:
+        """The counters as numpy ``u32[F, 3]`` = ``{pixels, agreeing, views}`` (waits)."""
+        b = self.buffer()
+        return b.read(np.uint32, count=3 * self.numFaces).reshape(self.numFaces, 3) if b is not None else np.zeros((0, 3), np.uint32)
+
+    def flags(self, keep: Optional[HipBuffer], minPixels: int = 1, minViews: int = 1, minAgreeing: int = 0, minAgreeingFraction: float = 0.0) -> None:
+        """``keep`` u8[F] on the device from the current counters, by ``selectFaces``' rule.  Stream-ordered, recordable."""
+        encodeFaceVisibilityFlags(self.device, self.buffer(), self.numFaces, keep, minPixels, minViews, minAgreeing, minAgreeingFraction)
+
+    def stats(self) -> dict:
+        """``dict(views, foreignPixels, countedPixels, agreeingPixels)`` since the reset (waits)."""
+        v = [C.c_uint64(0) for _ in VISIBILITY_STATS]
+        check(self.device.lib.wdgs_face_visibility_stats(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(VISIBILITY_STATS, (int(x.value) for x in v)))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_face_visibility_destroy(self.handle)
+        self.handle = None
+
+
+def encodeFaceVisibilityFlags(device: HipDevice, counters: Optional[HipBuffer], numFaces: int, keep: Optional[HipBuffer], minPixels: int = 1, minViews: int = 1,
+                              minAgreeing: int = 0, minAgreeingFraction: float = 0.0) -> None:
+    """``wdgs_face_visibility_flags``: ``keep`` u8[numFaces] from ``counters`` u32[numFaces][3], both on the device.  Stream-ordered, recordable."""
+    n = int(numFaces)
+    if not 0 <= n < 2 ** 32:
+        raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"faceVisibilityFlags: bad face count {numFaces}")
+    rule = _rule_counts(minPixels, minViews, minAgreeing, "faceVisibilityFlags")
+    q16 = _fraction_q16(minAgreeingFraction, "faceVisibilityFlags")
+    if n < 2 ** 31 and ((counters is not None and counters.size < 12 * n) or (keep is not None and keep.size < n)):
+        raise ValueError("faceVisibilityFlags: buffers too small for the faces")
+    ptr = lambda b: b.ptr if b is not None else None
+    check(device.lib.wdgs_face_visibility_flags(device.handle, ptr(counters), n, *rule, q16, ptr(keep)))
+
+
+def selectFaces(counters, minPixels: int = 1, minViews: int = 1, minAgreeing: int = 0, minAgreeingFraction: float = 0.0) -> np.ndarray:
+    """Which faces to keep, ``bool[F]``, from ``counters`` u32[F, 3] = ``{pixels, agreeing, views}``: ``pixels >= minPixels``, ``views >= minViews``,
+    ``agreeing >= minAgreeing`` and ``agreeing 65536 >= rint(minAgreeingFraction 65536) pixels`` in 64-bit integers.  The host restatement of
+    ``FaceVisibility.flags``, bit for bit."""
+    c = np.ascontiguousarray(counters, np.uint32).reshape(-1, 3).astype(np.uint64)
+    rule = _rule_counts(minPixels, minViews, minAgreeing, "selectFaces")
+    q16 = np.uint64(_fraction_q16(minAgreeingFraction, "selectFaces"))
+    return ((c[:, 0] >= np.uint64(rule[0])) & (c[:, 2] >= np.uint64(rule[1])) & (c[:, 1] >= np.uint64(rule[2]))
+            & (c[:, 1] * np.uint64(65536) >= q16 * c[:, 0]))
+
+
+class MeshFaceFilter:
+    """``MeshComponents``' compaction for an arbitrary face mask (``wdgs_mesh_face_filter``): ``select`` takes the faces and a u8 flag per face on the
+    device, ``compact`` writes the kept part.  ``filterFaces`` is the one-call form."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        h = C.c_void_p()
+        check(device.lib.wdgs_mesh_face_filter_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def select(self, faces: Optional[HipBuffer], numFaces: int, numVertices: int, keep: Optional[HipBuffer]) -> tuple:
+        """``(keptVertices, keptFaces, invalidFaces)`` for ``faces`` u32[numFaces][3] over ``numVertices`` vertices under ``keep`` u8[numFaces]: a face
+        is kept when its flag is non-zero and its indices are vertices, a vertex exactly when a kept face names it (flags, scans; waits)."""
+        nf, nv = int(numFaces), int(numVertices)
+        if not (0 <= nf < 2 ** 32 and 0 <= nv < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshFaceFilter.select: bad counts {numFaces}, {numVertices}")
+        if nf < 2 ** 31 and ((faces is not None and faces.size < 12 * nf) or (keep is not None and keep.size < nf)):
+            raise ValueError("MeshFaceFilter.select: buffers too small for the faces")
+        ptr = lambda b: b.ptr if b is not None else None
+        kv, kf, bad = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(self.device.lib.wdgs_mesh_face_filter_select(self.handle, ptr(faces), nf, nv, ptr(keep), C.byref(kv), C.byref(kf), C.byref(bad)))
+        return int(kv.value), int(kf.value), int(bad.value)
+
+    def compact(self, vertices: Optional[HipBuffer], verticesOut: Optional[HipBuffer], facesOut: Optional[HipBuffer], vertexMap: Optional[HipBuffer] = None,
+                faceMap: Optional[HipBuffer] = None, capacityVertices: Optional[int] = None, capacityFaces: Optional[int] = None) -> None:
+        """``MeshComponents.compact``'s arguments and rules for the last ``select``.  Stream-ordered, recordable."""
+        cv = min([b.size // s for b, s in ((verticesOut, 12), (vertexMap, 4)) if b is not None] or [2 ** 32 - 1]) if capacityVertices is None else int(capacityVertices)
+        cf = min([b.size // s for b, s in ((facesOut, 12), (faceMap, 4)) if b is not None] or [2 ** 32 - 1]) if capacityFaces is None else int(capacityFaces)
+        for b, s, n in ((verticesOut, 12, cv), (vertexMap, 4, cv), (facesOut, 12, cf), (faceMap, 4, cf)):
+            if b is not None and n * s > b.size:
+                raise ValueError("MeshFaceFilter.compact: the capacity exceeds the buffers")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_face_filter_compact(self.handle, ptr(vertices), ptr(verticesOut), ptr(facesOut), ptr(vertexMap), ptr(faceMap), cv, cf))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_mesh_face_filter_destroy(self.handle)
+        self.handle = None
+
+
+def filterFaces(device: HipDevice, mesh: dict, keep, asBuffers: bool = False) -> dict:
+    """``mesh`` without the faces whose ``keep`` flag (``bool[F]`` / ``u8[F]`` numpy, or a u8[F] ``HipBuffer``) is zero, and without the vertices no kept
+    face names: ``dict(vertices f32[V',3], faces u32[F',3], vertexMap u32[V'], faceMap u32[F'], invalidFaces)`` and ``colours`` / ``keys`` gathered
+    through ``vertexMap`` when the input has them -- ``removeSmallComponents``' shape and rules (kept faces in their order, kept vertices in ascending
+    original index; a face that names no vertex is never kept).  ``mesh``: numpy, or a dict of ``HipBuffer`` as ``_mesh_on_device`` takes (left as it
+    is).  ``asBuffers``: the four arrays stay on the device as ``HipBuffer`` (of at least one element's size), ``numVertices`` and ``numFaces`` are
+    added, ``colours`` and ``keys`` are not gathered; the caller destroys them (``destroyBuffers``)."""
+    vbuf, fbuf, nv, nf, own = _mesh_on_device(device, mesh, "filterFaces")
+    kbuf, own_k = keep, False
+    filt = None
+    outs = []
+    try:
+        if not isinstance(keep, HipBuffer):
+            k = np.ascontiguousarray(np.asarray(keep).astype(bool).reshape(-1), np.uint8)
+            if k.size != nf:
+                raise ValueError(f"filterFaces: {k.size} flags for {nf} faces")
+            kbuf, own_k = device.bufferFrom(k, "filterFaces: flags"), True
+        filt = MeshFaceFilter(device)
+        kv, kf, bad = filt.select(fbuf, nf, nv, kbuf)
+        outs = [device.createBuffer(s * max(n, 1), "filtered mesh") for s, n in ((12, kv), (12, kf), (4, kv), (4, kf))]
+        filt.compact(vbuf, outs[0], outs[1], outs[2], outs[3], kv, kf)
+        if asBuffers:
+            device.synchronize()   # (an uploaded mesh is released below)
+            result, outs = dict(vertices=outs[0], faces=outs[1], vertexMap=outs[2], faceMap=outs[3], numVertices=kv, numFaces=kf, invalidFaces=bad), []
+            return result
+        out = dict(vertices=outs[0].read(np.float32, count=3 * kv).reshape(kv, 3), faces=outs[1].read(np.uint32, count=3 * kf).reshape(kf, 3),
+                   vertexMap=outs[2].read(np.uint32, count=kv), faceMap=outs[3].read(np.uint32, count=kf), invalidFaces=bad)
+    finally:
+        if filt is not None:
+            filt.destroy()
+        for b, o in [(vbuf, own), (fbuf, own), (kbuf, own_k)] + [(b, True) for b in outs]:
+            if o:
+                b.destroy()
+    for name in ("colours", "keys"):
+        if name in mesh and not isinstance(mesh[name], HipBuffer):
+            out[name] = None if mesh[name] is None else np.ascontiguousarray(np.asarray(mesh[name])[out["vertexMap"]])
+    return out
+
+
+def faceVisibility(device: HipDevice, mesh: dict, cameras, width: int, height: int, near: float = MESH_RASTER_NEAR, cull: str = "none") -> dict:
+    """Which faces of ``mesh`` the ``cameras`` (68-float blocks, numpy or ``HipBuffer``) see, without a model: every camera's face image is rasterized at
+    ``width`` x ``height`` and accumulated.  ``dict(counters u32[F,3] = {pixels, agreeing, views}, stats)`` -- ``agreeing`` equals ``pixels`` here, and
+    ``stats`` is ``FaceVisibility.stats``'s dict.  ``selectFaces`` and ``filterFaces`` take it from there."""
+    w, h = int(width), int(height)
+    vertices, faces, V, F, own = _mesh_on_device(device, mesh, "faceVisibility")
+    rasterizer = visibility = image = None
+    try:
+        rasterizer, visibility = MeshRasterizer(device), FaceVisibility(device)
+        visibility.reset(F)
+        npix = w * h if 1 <= w <= _lib.MESH_RASTER_MAX_SIZE and 1 <= h <= _lib.MESH_RASTER_MAX_SIZE else 0
+        image = device.createBuffer(4 * max(npix, 1), "mesh face image")
+        for camera in cameras:
+            cam, own_cam = _camera_on_device(device, camera, "faceVisibility")
+            try:
+                rasterizer.encode(vertices, V, faces, F, None, cam, w, h, near, cull, face=image)
+                visibility.accumulate(image, w, h)
+            finally:
+                if own_cam:
+                    device.synchronize()
+                    cam.destroy()
+        return dict(counters=visibility.read(), stats=visibility.stats())
+    finally:
+        for o in (visibility, rasterizer, image):
+            if o is not None:
+                o.destroy()
+        if own:
+            vertices.destroy()
+            faces.destroy()
+
+
 class PointIndex:
     """A uniform grid over ``points`` ([M,3] float32 as numpy, or a ``HipBuffer``) for exact nearest-point queries under a cutoff (``wdgs_point_index``).
     ``cellSize`` is a speed parameter only -- no result depends on it; ``None``: chosen by the first query (its cutoff, or less for many points), which then

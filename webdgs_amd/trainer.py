@@ -871,18 +871,27 @@ class Trainer:
         """``Evaluator.meshDepthAgreement``: a mesh rasterized under each view against the model's own depth map of that view."""
         return self.evaluator.meshDepthAgreement(mesh, viewIds, split, depthKind, **options)
 
+    def meshVisibility(self, mesh: dict, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", **options) -> dict:
+        """``Evaluator.meshVisibility``: per face of a mesh the pixels and views that show it, and the pixels where the model's depth agrees."""
+        return self.evaluator.meshVisibility(mesh, viewIds, split, depthKind, **options)
+
+    def cullMesh(self, mesh: dict, minPixels: int = 1, minViews: int = 1, minAgreeing: int = 0, minAgreeingFraction: float = 0.0, **visibilityOptions) -> dict:
+        """``Evaluator.cullMesh``: a mesh without the faces the views do not see (``meshVisibility``, ``ops.selectFaces``' rule and ``ops.filterFaces``,
+        flags and compaction on the device)."""
+        return self.evaluator.cullMesh(mesh, minPixels, minViews, minAgreeing, minAgreeingFraction, **visibilityOptions)
+
     def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
         """``Evaluator.fuseDepth``: fuses the current model's depth maps into ``volume``."""
         return self.evaluator.fuseDepth(volume, viewIds, split, depthKind)
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
                     keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", simplify: Optional[float] = None,
-                    smooth: Optional[int] = None, normals: bool = False, **volumeOptions) -> dict:
+                    smooth: Optional[int] = None, normals: bool = False, cull: Optional[dict] = None, **volumeOptions) -> dict:
         """``Evaluator.extractMesh``: the current model as a triangle mesh of the box ``[lo, hi]``, welded on the host or (``weld="device"``) on the device;
-        with ``smooth=iterations`` Taubin-smoothed, with ``simplify=cellSize`` then simplified by vertex clustering, with ``normals=True`` given the
-        final mesh's vertex normals."""
+        with ``cull=dict(...)`` without the faces no view sees (``cullMesh``'s rule and options), with ``smooth=iterations`` Taubin-smoothed, with
+        ``simplify=cellSize`` then simplified by vertex clustering, with ``normals=True`` given the final mesh's vertex normals."""
         return self.evaluator.extractMesh(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld=weld,
-                                          simplify=simplify, smooth=smooth, normals=normals, **volumeOptions)
+                                          simplify=simplify, smooth=smooth, normals=normals, cull=cull, **volumeOptions)
 
     def evaluateGeometry(self, reference, lo, hi, voxelSize: float, maxDistance: float, threshold: float, density: Optional[float] = None, seed: int = 0,
                          keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **extractMeshOptions) -> dict:
