@@ -678,6 +678,58 @@ static napi_value meshFaceFilterCompact(napi_env env, napi_callback_info info) {
                                                    get_ptr(env, argv[4]), get_ptr(env, argv[5]), get_u32(env, argv[6]), get_u32(env, argv[7])));
     return js_undefined(env);
 }
+// Vertex colours baked from photographs (include/webdgs.h: wdgs_mesh_colour_baker_*; no reference counterpart)
+static napi_value meshColourBakerCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_mesh_colour_baker* b = nullptr;
+    WDGS_OK_OR_THROW(wdgs_mesh_colour_baker_create((wdgs_device*)get_ptr(env, argv[0]), &b));
+    return make_ptr(env, b);
+}
+static napi_value meshColourBakerDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_mesh_colour_baker_destroy((wdgs_mesh_colour_baker*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value meshColourBakerReset(napi_env env, napi_callback_info info) {  // (baker, numVertices)
+    ARGS(2);
+    WDGS_OK_OR_THROW(wdgs_mesh_colour_baker_reset((wdgs_mesh_colour_baker*)get_ptr(env, argv[0]), get_u32(env, argv[1])));
+    return js_undefined(env);
+}
+static napi_value meshColourBakerAccumulate(napi_env env, napi_callback_info info) {
+    // (baker, verticesPtr | null, normalsPtr | null, numVertices, cameraPtr, imagePtr, meshDepthPtr | null, width, height, near, depthTolerance, minCos)
+    ARGS(12);
+    WDGS_OK_OR_THROW(wdgs_mesh_colour_baker_accumulate((wdgs_mesh_colour_baker*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_u32(env, argv[3]),
+                                                       get_ptr(env, argv[4]), get_ptr(env, argv[5]), get_ptr(env, argv[6]), get_u32(env, argv[7]), get_u32(env, argv[8]),
+                                                       (float)get_f64(env, argv[9]), (float)get_f64(env, argv[10]), (float)get_f64(env, argv[11])));
+    return js_undefined(env);
+}
+static napi_value meshColourBakerResolve(napi_env env, napi_callback_info info) {
+    // (baker, coloursOutPtr | null, fallbackPtr | null, bakedOutPtr | null, numVertices, minViews, minWeight: a number or a BigInt below 2^64)
+    ARGS(7);
+    napi_valuetype t; napi_typeof(env, argv[6], &t);
+    uint64_t min_weight = 0; bool lossless = true;
+    if (t == napi_bigint) napi_get_value_bigint_uint64(env, argv[6], &min_weight, &lossless);
+    else min_weight = get_slots(env, argv[6]);
+    WDGS_OK_OR_THROW(wdgs_mesh_colour_baker_resolve((wdgs_mesh_colour_baker*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_ptr(env, argv[2]), get_ptr(env, argv[3]),
+                                                    get_u32(env, argv[4]), get_u32(env, argv[5]), min_weight));
+    return js_undefined(env);
+}
+static napi_value meshColourBakerRead(napi_env env, napi_callback_info info) {  // (baker, numVertices) -> [sums: ArrayBuffer(32 V), views: ArrayBuffer(4 V)]
+    ARGS(2);
+    const size_t V = get_u32(env, argv[1]);
+    void *sums = nullptr, *views = nullptr; napi_value ab[2];
+    NAPI_OK(napi_create_arraybuffer(env, 32 * V, &sums, &ab[0]));
+    NAPI_OK(napi_create_arraybuffer(env, 4 * V, &views, &ab[1]));
+    WDGS_OK_OR_THROW(wdgs_mesh_colour_baker_read((wdgs_mesh_colour_baker*)get_ptr(env, argv[0]), (uint64_t*)sums, (uint32_t*)views));
+    napi_value a; napi_create_array_with_length(env, 2, &a);
+    for (uint32_t i = 0; i < 2; i++) napi_set_element(env, a, i, ab[i]);
+    return a;
+}
+static napi_value meshColourBakerStats(napi_env env, napi_callback_info info) {
+    // (baker) -> [usable, inImage, visible, accumulated, viewportMismatch, bakedVertices] (doubles: below 2^53)
+    ARGS(1);
+    uint64_t r[6] = {0, 0, 0, 0, 0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_colour_baker_stats((wdgs_mesh_colour_baker*)get_ptr(env, argv[0]), &r[0], &r[1], &r[2], &r[3], &r[4], &r[5]));
+    napi_value a; napi_create_array_with_length(env, 6, &a);
+    for (uint32_t i = 0; i < 6; i++) { napi_value x; napi_create_double(env, (double)r[i], &x); napi_set_element(env, a, i, x); }
+    return a;
+}
 static napi_value pointIndexCreate(napi_env env, napi_callback_info info) {  // (device, pointsPtr, numPoints, cellSize: 0 = chosen by the first query) -> handle
     ARGS(4);
     wdgs_point_index* ix = nullptr;
@@ -1360,6 +1412,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(faceVisibilityCreate); EXPORT_FN(faceVisibilityDestroy); EXPORT_FN(faceVisibilityReset); EXPORT_FN(faceVisibilityAccumulate); EXPORT_FN(faceVisibilityGet);
     EXPORT_FN(faceVisibilityStats); EXPORT_FN(faceVisibilityFlags);
     EXPORT_FN(meshFaceFilterCreate); EXPORT_FN(meshFaceFilterDestroy); EXPORT_FN(meshFaceFilterSelect); EXPORT_FN(meshFaceFilterCompact);
+    EXPORT_FN(meshColourBakerCreate); EXPORT_FN(meshColourBakerDestroy); EXPORT_FN(meshColourBakerReset); EXPORT_FN(meshColourBakerAccumulate);
+    EXPORT_FN(meshColourBakerResolve); EXPORT_FN(meshColourBakerRead); EXPORT_FN(meshColourBakerStats);
     EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
     EXPORT_FN(pointDistanceStats);
     EXPORT_FN(pointIndexBounds); EXPORT_FN(pointIndexKNearest); EXPORT_FN(pointCloudPositions); EXPORT_FN(pointCloudNeighbourScales);

@@ -7,7 +7,7 @@ import { EvaluationResult, NormalConsistencyResult, Trainer, TrainingImage, Trai
 
 type Split = 'eval' | 'train';
 type DepthKind = 'median' | 'expected';
-type MeshOptions = { viewIds?: number[] | null; split?: Split; depthKind?: DepthKind; minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: import('./trainer').CullMeshOptions | null } & ComponentSelection;
+type MeshOptions = { viewIds?: number[] | null; split?: Split; depthKind?: DepthKind; minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: import('./trainer').CullMeshOptions | null; bake?: boolean | import('./trainer').BakeMeshOptions | null } & ComponentSelection;
 
 export class Evaluator {
   /** Uses of the trainer only: device, pointCloud, iteration, trainCameras, images, cameraBuffers, newPassSet, dcWords, longLists, drain(), growTileEntryCapacity(). */
@@ -25,8 +25,10 @@ export class Evaluator {
     import('./trainer').MeshVisibilityResult;
   cullMesh(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: import('./trainer').CullMeshOptions):
     import('./webdgs_hip').FilteredMesh & { counters: Uint32Array; views: number[] };
+  bakeMeshColours(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: import('./trainer').BakeMeshOptions):
+    import('./webdgs_hip').BakedMesh & { views: number[] };
   fuseDepth(volume: TSDFVolume, viewIds?: number[] | null, split?: Split, depthKind?: DepthKind): number[];
-  extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, options?: MeshOptions): TriangleMesh | CompactedMesh | SimplifiedMesh | import('./webdgs_hip').FilteredMesh;
+  extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, options?: MeshOptions): TriangleMesh | CompactedMesh | SimplifiedMesh | import('./webdgs_hip').FilteredMesh | import('./webdgs_hip').BakedMesh;
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,
                    options?: { density?: number | null; seed?: number } & MeshOptions): GeometryMetrics & { vertices: number; faces: number; samples: number; ms: number };
   contributionStats(viewIds?: number[] | null, split?: Split): ContributionRecords & { views: number[] };

@@ -299,6 +299,18 @@ class Evaluator {
     return out;
   }
 
+  // ---------------------------------------------------------------- vertex colours from the photographs (DESIGN.md section 22)
+  /** `mesh` (hip.bakeVertexColours': typed arrays or an object of HipBuffers) with its vertex colours taken from the split's photographs -- the device copies
+   *  the trainer holds -- under the split's cameras: hip.bakeVertexColours with its options and { viewIds, split = 'train' }, and its result with views
+   *  added.  The views may differ in size.  Nothing is rendered through the model: the pipeline is drained and that is all.  Same results as the Python
+   *  host's. */
+  bakeMeshColours(mesh, options) {
+    const o = options || {}, { imgs, bufs, ids } = this.views('bakeMeshColours', o.viewIds, o.split || 'train');
+    this.drain();
+    const views = ids.map((v) => ({ camera: bufs[v], image: imgs[v].texture, width: imgs[v].width, height: imgs[v].height }));
+    return Object.assign(hip.bakeMeshFromViews(this.device, mesh, views, o, 'bakeMeshColours'), { views: ids });
+  }
+
   // ---------------------------------------------------------------- TSDF fusion and mesh extraction (DESIGN.md section 13)
   /** Fuses the current model's depth maps into `volume` (hip.TSDFVolume): for each view in the order given, the forward pass, rasterize,
    *  encodeDepth([depthKind, 'weight_sum']) and volume.integrate with the weight sum and the rasterizer's output texture as colour (where the volume
@@ -353,6 +365,13 @@ class Evaluator {
     const o = options || {}, weld = o.weld || 'host';
     if (weld !== 'host' && weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
     const unset = (x) => x === undefined || x === null;
+    if (!unset(o.bake) && o.bake !== false) {   // (DESIGN.md section 22: last, on the final mesh; its normals are the weights even when none are asked for)
+      const mesh = this.extractMesh(lo, hi, voxelSize, Object.assign({}, o, { bake: null }));
+      const out = this.bakeMeshColours(mesh, Object.assign({ viewIds: o.viewIds, split: o.split }, o.bake === true ? {} : o.bake));
+      out.bakeStats = out.stats;
+      if (mesh.stats !== undefined) out.stats = mesh.stats; else delete out.stats;
+      return out;
+    }
     if (!unset(o.cull)) {   // (DESIGN.md section 21: after welding and component removal, before smooth, simplify and normals)
       const mesh = this.extractMesh(lo, hi, voxelSize, Object.assign({}, o, { cull: null, simplify: null, smooth: null, normals: false }));
       const culled = this.cullMesh(mesh, Object.assign({ viewIds: o.viewIds, split: o.split, depthKind: o.depthKind }, o.cull));

@@ -77,6 +77,9 @@ export class Trainer {
    *  object carries the input's counters and the views.  Training untouched.  No reference counterpart. */
   cullMesh(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: CullMeshOptions):
     import('./webdgs_hip').FilteredMesh & { counters: Uint32Array; views: number[] };
+  /** The mesh with its vertex colours taken from the split's photographs under the split's cameras (bakeVertexColours over the trainer's own device copies):
+   *  colours, baked and stats replaced or added, and the views.  Training untouched.  No reference counterpart. */
+  bakeMeshColours(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: BakeMeshOptions): import('./webdgs_hip').BakedMesh & { views: number[] };
   /** Fuses the current model's depth maps (and the rendered colour) into a TSDFVolume, view by view in the order given; rendered through evaluate's
    *  passes, training untouched.  Returns the view list.  No reference counterpart. */
   fuseDepth(volume: import('./webdgs_hip').TSDFVolume, viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): number[];
@@ -84,16 +87,16 @@ export class Trainer {
    *  minFraction set, without the components removeSmallComponents drops.  weld: 'host' (default) or 'device' -- welded, and with a component rule cleaned,
    *  on the device; the same bytes.  simplify: a cell size -- the mesh is simplified last, by vertex clustering on that grid from lo (simplifyMesh), and
    *  its object is returned.  cull: cullMesh's options -- the faces no view sees are removed after welding and component removal and before smooth, simplify
-   *  and normals.  No reference counterpart. */
+   *  and normals.  bake: true or bakeMeshColours' options -- the final mesh's colours are taken from the photographs, last.  No reference counterpart. */
   extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number,
               options?: { viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected'; minWeight?: number; truncation?: number; maxWeight?: number;
-                          colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null } & import('./webdgs_hip').ComponentSelection):
-    import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh | import('./webdgs_hip').SimplifiedMesh | import('./webdgs_hip').FilteredMesh;
+                          colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null; bake?: boolean | BakeMeshOptions | null } & import('./webdgs_hip').ComponentSelection):
+    import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh | import('./webdgs_hip').SimplifiedMesh | import('./webdgs_hip').FilteredMesh | import('./webdgs_hip').BakedMesh;
   /** extractMesh -> sampleMesh -> geometryMetrics against `reference` (points [M*3], or the path of a PLY): the mesh's accuracy, completeness, Chamfer
    *  distance, precision, recall and F-score, with the mesh's vertex, face and sample counts and ms.  Training untouched.  No reference counterpart. */
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,
                    options?: { density?: number | null; seed?: number; viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected';
-                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null } &
+                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null; bake?: boolean | BakeMeshOptions | null } &
                      import('./webdgs_hip').ComponentSelection):
     import('./webdgs_hip').GeometryMetrics & { vertices: number; faces: number; samples: number; ms: number };
   /** Per-Gaussian render contribution accumulated over the views (default: all training views); no reference counterpart. */
@@ -131,6 +134,7 @@ export interface MeshVisibilityOptions {
   cull?: 'none' | 'back' | 'front';
 }
 export type CullMeshOptions = MeshVisibilityOptions & import('./webdgs_hip').FaceRule;
+export type BakeMeshOptions = { viewIds?: number[] | null; split?: 'eval' | 'train' } & import('./webdgs_hip').BakeOptions;
 export interface MeshVisibilityResult {
   iteration: number; views: number[]; counters: Uint32Array; counted: number[]; agreeing: number[]; foreign: number[]; ms: number;
 }

@@ -712,6 +712,8 @@ class Trainer {
   meshVisibility(mesh, options) { return this.evaluator.meshVisibility(mesh, options); }
   /** Evaluator.cullMesh: a mesh without the faces the views do not see (flags and compaction on the device). */
   cullMesh(mesh, options) { return this.evaluator.cullMesh(mesh, options); }
+  /** Evaluator.bakeMeshColours: a mesh with its vertex colours taken from the split's photographs under the split's cameras. */
+  bakeMeshColours(mesh, options) { return this.evaluator.bakeMeshColours(mesh, options); }
   /** Evaluator.fuseDepth: fuses the current model's depth maps into `volume`. */
   fuseDepth(volume, viewIds, split, depthKind) { return this.evaluator.fuseDepth(volume, viewIds, split, depthKind); }
   /** Evaluator.evaluateGeometry: the extracted mesh scored against a reference point set. */

@@ -456,6 +456,33 @@ export function filterFaces(device: HipDevice, mesh: MeshArrays | MeshBuffers, k
 /** Which faces of a mesh the cameras see, without a model: every camera's face image rasterized and accumulated.  No reference counterpart. */
 export function faceVisibility(device: HipDevice, mesh: MeshArrays | MeshBuffers, cameras: Array<Float32Array | HipBuffer>, width: number, height: number,
                                options?: { near?: number; cull?: 'none' | 'back' | 'front' }): { counters: Uint32Array; stats: FaceVisibilityStats };
+export interface BakeStats { usable: number; inImage: number; visible: number; accumulated: number; viewportMismatch: number; bakedVertices: number }
+/** bakeVertexColours' options: normals (true: the mesh's normals, or vertexNormals' when it carries none, weigh the views; false: every view weighs the
+ *  same), depthTolerance (0.05), minCos (0.1: a caller's knob, not a tuned number), minViews (1), minWeight (1), near, occlusion (true), asBuffers. */
+export interface BakeOptions { normals?: boolean; depthTolerance?: number; minCos?: number; minViews?: number; minWeight?: number | bigint; near?: number;
+                               occlusion?: boolean; asBuffers?: boolean }
+export interface BakeView { camera: HipBuffer; image: HipBuffer; width: number; height: number }
+/** Per-vertex colour sums over views (wdgs_mesh_colour_baker): u64[V][4] = { R, G, B, Wt } and u32[V] views, integer sums of bilinear samples of the
+ *  photographs weighted by the cosine to the camera.  No reference counterpart. */
+export class MeshColourBaker {
+  constructor(device: HipDevice);
+  readonly numVertices: number;
+  reset(numVertices: number): void;
+  accumulate(vertices: HipBuffer | null, numVertices: number, camera: HipBuffer | null, image: HipBuffer | null, width: number, height: number,
+             options?: { normals?: HipBuffer | null; meshDepth?: HipBuffer | null; near?: number; depthTolerance?: number; minCos?: number }): void;
+  resolve(coloursOut: HipBuffer | null, numVertices: number, options?: { fallback?: HipBuffer | null; bakedOut?: HipBuffer | null; minViews?: number;
+          minWeight?: number | bigint }): void;
+  read(): { sums: BigUint64Array; views: Uint32Array };
+  stats(): BakeStats;
+  destroy(): void;
+}
+/** The mesh with colours: Uint8Array[3 V] taken from the photographs, baked: Uint8Array[V] and stats; with asBuffers colours rgba8[V] and baked u8[V] stay on
+ *  the device.  No reference counterpart. */
+export function bakeVertexColours(device: HipDevice, mesh: MeshArrays | MeshBuffers, cameras: Array<Float32Array | HipBuffer>, images: Array<Uint8Array | HipBuffer>,
+                                  width: number, height: number, options?: BakeOptions): BakedMesh;
+/** bakeVertexColours for views on the device, which may differ in size. */
+export function bakeMeshFromViews(device: HipDevice, mesh: MeshArrays | MeshBuffers, views: BakeView[], options?: BakeOptions, what?: string): BakedMesh;
+export type BakedMesh = { [key: string]: unknown; colours: Uint8Array | HipBuffer; baked: Uint8Array | HipBuffer; stats: BakeStats };
 /** colours and keys of a typed-array mesh gathered through out.vertexMap into out. */
 export function gatherVertexAttributes(mesh: { colours?: unknown; keys?: unknown }, out: { vertexMap: Uint32Array; colours?: Uint8Array | null; keys?: BigUint64Array | null }): void;
 /** A uniform grid over points for exact nearest-point queries under a cutoff (wdgs_point_index); the cell edge is a speed parameter only.  No reference

@@ -1453,6 +1453,132 @@ function faceVisibility(device, mesh, cameras, width, height, options) {
     if (src.own) { src.vertices.destroy(); src.faces.destroy(); }
   }
 }
+// ---------------------------------------------------------------- vertex colours baked from photographs (include/webdgs.h, DESIGN.md section 22)
+const BAKE_STATS = ['usable', 'inImage', 'visible', 'accumulated', 'viewportMismatch', 'bakedVertices'];
+/** Per-vertex colour sums over views (wdgs_mesh_colour_baker): reset sizes them for a mesh, accumulate adds one view -- a photograph, its camera block and,
+ *  optionally, the vertex normals (the weights) and the depth image MeshRasterizer.encode wrote for this mesh and camera (the occlusion test) -- resolve turns
+ *  the sums into rgba8 vertex colours, read hands out the sums and stats the totals.  Integer sums: the state does not depend on the order of the views and
+ *  every byte is a function of the inputs.  bakeVertexColours is the one-call form. */
+class MeshColourBaker {
+  constructor(device) { this.device = device; this.destroyed = false; this.numVertices = 0; this.handle = addon.meshColourBakerCreate(device.handle); }
+  /** Sizes and zeroes the state for numVertices vertices.  A call that grows the arrays waits once; it cannot be recorded. */
+  reset(numVertices) { addon.meshColourBakerReset(this.handle, numVertices); this.numVertices = numVertices; }
+  /** One view of width x height: vertices f32[numVertices][3], the 68-float camera block, image rgba8; options: { normals, meshDepth (HipBuffers or null),
+   *  near = MESH_RASTER_NEAR, depthTolerance = 0.05, minCos = 0.1 }.  Stream-ordered, recordable. */
+  accumulate(vertices, numVertices, camera, image, width, height, options) {
+    const o = options || {}, pick = (v, d) => (v === undefined || v === null ? d : v);
+    if (numVertices < 2 ** 31 && [vertices, o.normals].some((b) => b && b.size < 12 * numVertices)) throw new Error('MeshColourBaker.accumulate: buffers too small for the vertices');
+    if (camera && camera.size < 272) throw new Error('MeshColourBaker.accumulate: the camera block has 68 floats');
+    if (width >= 1 && width <= MESH_RASTER_MAX_SIZE && height >= 1 && height <= MESH_RASTER_MAX_SIZE) {
+      for (const b of [image, o.meshDepth]) if (b && b.size < 4 * width * height) throw new Error(`MeshColourBaker.accumulate: an image is too small for ${width}x${height}`);
+    }
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshColourBakerAccumulate(this.handle, ptr(vertices), ptr(o.normals), numVertices, ptr(camera), ptr(image), ptr(o.meshDepth), width, height,
+      Math.fround(pick(o.near, MESH_RASTER_NEAR)), Math.fround(pick(o.depthTolerance, 0.05)), Math.fround(pick(o.minCos, 0.1)));
+  }
+  /** coloursOut rgba8[numVertices] from the current sums; options: { fallback (may be coloursOut itself), bakedOut u8[numVertices], minViews = 1,
+   *  minWeight = 1 (a number or a BigInt) }.  Stream-ordered, recordable. */
+  resolve(coloursOut, numVertices, options) {
+    const o = options || {}, pick = (v, d) => (v === undefined || v === null ? d : v), minViews = pick(o.minViews, 1), minWeight = pick(o.minWeight, 1);
+    if (!(Number.isInteger(minViews) && minViews >= 0 && minViews < 2 ** 32) || !(typeof minWeight === 'bigint' ? minWeight >= 0n && minWeight < 2n ** 64n : Number.isInteger(minWeight) && minWeight >= 0)) {
+      const e = new Error(`MeshColourBaker.resolve: bad thresholds ${minViews}, ${minWeight}`); e.code = 'WDGS_E'; throw e;
+    }
+    if (numVertices < 2 ** 31 && ([coloursOut, o.fallback].some((b) => b && b.size < 4 * numVertices) || (o.bakedOut && o.bakedOut.size < numVertices))) throw new Error('MeshColourBaker.resolve: buffers too small for the vertices');
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshColourBakerResolve(this.handle, ptr(coloursOut), ptr(o.fallback), ptr(o.bakedOut), numVertices, minViews, minWeight);
+  }
+  /** { sums: BigUint64Array[4 V] (R, G, B, Wt per vertex), views: Uint32Array[V] } (waits). */
+  read() { const r = addon.meshColourBakerRead(this.handle, this.numVertices); return { sums: new BigUint64Array(r[0]), views: new Uint32Array(r[1]) }; }
+  /** { usable, inImage, visible, accumulated, viewportMismatch, bakedVertices }: the vertices that passed each step summed over the views since the reset, the
+   *  calls whose camera block was of another image size, and the baked vertices of the last resolve (waits). */
+  stats() { const r = addon.meshColourBakerStats(this.handle), out = {}; BAKE_STATS.forEach((k, i) => { out[k] = r[i]; }); return out; }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.meshColourBakerDestroy(this.handle); this.handle = null; }
+}
+/** bakeVertexColours for views that are on the device already: `views` is an array of { camera, image, width, height } with HipBuffers, which may differ in
+ *  size (Evaluator.bakeMeshColours hands in the trainer's own cameras and photographs).  options: bakeVertexColours'. */
+function bakeMeshFromViews(device, mesh, views, options, what) {
+  const o = options || {}, pick = (v, d) => (v === undefined || v === null ? d : v), name = what || 'bakeVertexColours';
+  const occlusion = pick(o.occlusion, true), src = meshOnDevice(device, mesh, name), V = src.V, owned = src.own ? [src.vertices, src.faces] : [];
+  const upload = (a) => { const b = device.createBuffer({ size: Math.max(a.byteLength, 8) }); if (a.byteLength) device.queue.writeBuffer(b, 0, a); owned.push(b); return b; };
+  let baker = null, rasterizer = null, depth = null, out = {};
+  try {
+    let fallback = null, normals = null;
+    const c = mesh.colours;
+    if (c instanceof HipBuffer) fallback = c;
+    else if (c) {
+      let rgba = c;
+      if (c.length === 3 * V) {
+        rgba = new Uint8Array(4 * V).fill(255);
+        for (let v = 0; v < V; v++) for (let a = 0; a < 3; a++) rgba[4 * v + a] = c[3 * v + a];
+      } else if (c.length !== 4 * V) throw new Error(`${name}: ${c.length} colour bytes for ${V} vertices`);
+      fallback = upload(rgba instanceof Uint8Array ? rgba : Uint8Array.from(rgba));
+    }
+    if (pick(o.normals, true)) {
+      const n = mesh.normals;
+      if (n instanceof HipBuffer) normals = n;
+      else if (n) {
+        if (n.length !== 3 * V) throw new Error(`${name}: ${n.length} normal components for ${V} vertices`);
+        normals = upload(n instanceof Float32Array ? n : Float32Array.from(n));
+      } else { normals = smoothAndNormals(device, src.vertices, src.faces, V, src.F, null, true).normals; owned.push(normals); }
+    }
+    const legal = views.filter((w) => w.width >= 1 && w.width <= MESH_RASTER_MAX_SIZE && w.height >= 1 && w.height <= MESH_RASTER_MAX_SIZE);
+    baker = new MeshColourBaker(device);
+    baker.reset(V);
+    if (occlusion && legal.length) {   // (the rasterizer is grown once, to the largest view, in front of the loop)
+      const big = legal.reduce((a, w) => (w.width * w.height > a.width * a.height ? w : a), legal[0]);
+      depth = device.createBuffer({ size: Math.max(4 * big.width * big.height, 16), label: 'mesh depth' });
+      rasterizer = new MeshRasterizer(device);
+      rasterizer.encode(src.vertices, V, src.faces, src.F, null, big.camera, big.width, big.height, { near: o.near, depth });
+    }
+    for (const w of views) {
+      if (rasterizer && legal.includes(w)) rasterizer.encode(src.vertices, V, src.faces, src.F, null, w.camera, w.width, w.height, { near: o.near, depth });
+      baker.accumulate(src.vertices, V, w.camera, w.image, w.width, w.height, { normals, meshDepth: occlusion ? depth : null, near: o.near, depthTolerance: o.depthTolerance, minCos: o.minCos });
+    }
+    out = { colours: device.createBuffer({ size: Math.max(4 * V, 8), label: 'baked colours' }), baked: device.createBuffer({ size: Math.max(V, 8), label: 'baked mask' }) };
+    baker.resolve(out.colours, V, { fallback, bakedOut: out.baked, minViews: o.minViews, minWeight: o.minWeight });
+    const stats = baker.stats();   // (waits: the objects released below are idle)
+    if (o.asBuffers) { const result = Object.assign({}, mesh, out, { stats }); out = {}; return result; }
+    const rgba = new Uint8Array(V ? device.readBuffer(out.colours, 4 * V) : new ArrayBuffer(0)), colours = new Uint8Array(3 * V);
+    for (let v = 0; v < V; v++) for (let a = 0; a < 3; a++) colours[3 * v + a] = rgba[4 * v + a];
+    return Object.assign({}, mesh, { colours, baked: new Uint8Array(V ? device.readBuffer(out.baked, V) : new ArrayBuffer(0)), stats });
+  } finally {
+    for (const x of [baker, rasterizer, depth]) if (x) x.destroy();
+    destroyBuffers(out);
+    device.synchronize();
+    owned.forEach((b) => b.destroy());
+  }
+}
+/** `mesh` with its vertex colours taken from photographs, without a model: per camera (68-float blocks: Float32Arrays or HipBuffers) and its image (rgba8
+ *  Uint8Array[height * width * 4], or a HipBuffer) the mesh's depth image is rasterized (options.occlusion) and every vertex that projects into the photograph,
+ *  is not hidden (all four depth texels round it within depthTolerance of its own depth) and faces the camera adds the bilinear sample there, weighted by the
+ *  cosine between its normal and the direction to the camera.  A vertex at least minViews views coloured, with a weight sum of at least minWeight (256 per
+ *  view that looks straight at it), gets the weighted mean; any other keeps the mesh's own colour (zeros without colours).  options: { normals = true (the
+ *  mesh's, or vertexNormals' when it carries none; false: every view weighs the same), depthTolerance = 0.05, minCos = 0.1 (a caller's knob, not a tuned
+ *  number), minViews = 1, minWeight = 1, near = MESH_RASTER_NEAR, occlusion = true, asBuffers }.  Returns the mesh's object with colours: Uint8Array[3 V]
+ *  replaced and baked: Uint8Array[V] and stats added; asBuffers: colours rgba8[V] and baked u8[V] stay on the device.  Same results as the Python host's. */
+function bakeVertexColours(device, mesh, cameras, images, width, height, options) {
+  if (cameras.length !== images.length) throw new Error(`bakeVertexColours: ${cameras.length} cameras for ${images.length} images`);
+  const owned = [];
+  const upload = (a) => { const b = device.createBuffer({ size: Math.max(a.byteLength, 8) }); if (a.byteLength) device.queue.writeBuffer(b, 0, a); owned.push(b); return b; };
+  try {
+    const views = cameras.map((camera, k) => {
+      let cam = camera, image = images[k];
+      if (!(camera instanceof HipBuffer)) {
+        if (camera.length !== 68) throw new Error(`bakeVertexColours: the camera block has 68 floats, got ${camera.length}`);
+        cam = upload(camera instanceof Float32Array ? camera : Float32Array.from(camera));
+      }
+      if (!(image instanceof HipBuffer)) {
+        if (image.length !== 4 * width * height) throw new Error(`bakeVertexColours: an image of ${image.length} bytes for ${width}x${height} rgba8`);
+        image = upload(image instanceof Uint8Array ? image : Uint8Array.from(image));
+      }
+      return { camera: cam, image, width, height };
+    });
+    return bakeMeshFromViews(device, mesh, views, options);
+  } finally {
+    device.synchronize();
+    owned.forEach((b) => b.destroy());
+  }
+}
 /** A uniform grid over `points` ([M*3] Float32Array, or a HipBuffer) for exact nearest-point queries under a cutoff (wdgs_point_index).  options:
  *  { cellSize, count }.  cellSize is a speed parameter only -- no result depends on it; without one it is chosen by the first query (its cutoff, or less
  *  for many points), which then finishes the build.  Non-finite points are left out.  The build waits once; queries are stream-ordered. */
@@ -1682,4 +1808,5 @@ const MAX_BATCH_VIEWS = 16;  // WDGS_MAX_BATCH_VIEWS
 module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, MeshWelder, weldTrianglesDevice, destroyBuffers, MeshSimplifier, simplifyMesh, MeshAdjacency, meshAdjacency, smoothMesh, vertexNormals, finishMesh, CULL_MODES, MESH_RASTER_LARGE_FACE_PIXELS, MESH_RASTER_NEAR, NO_FACE, MeshRasterizer, rasterizeMesh, encodeDepthAgreement, depthAgreementResult, depthAgreement, meshOnDevice, NO_INDEX, KNN_EXCLUDE_SELF, MeshSampler, sampleMesh, MeshComponents, meshComponents, selectComponents, removeSmallComponents, PointIndex, initScalesFromNeighbours, encodePointDistanceStats, pointDistanceStats,
   geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, grownTileEntries, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
-  DensifyPrunePass, downsampleRGBA8, FaceVisibility, MeshFaceFilter, encodeFaceVisibilityFlags, selectFaces, filterFaces, faceVisibility, gatherVertexAttributes };
+  DensifyPrunePass, downsampleRGBA8, FaceVisibility, MeshFaceFilter, encodeFaceVisibilityFlags, selectFaces, filterFaces, faceVisibility, gatherVertexAttributes,
+  MeshColourBaker, bakeMeshFromViews, bakeVertexColours };

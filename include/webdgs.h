@@ -1037,6 +1037,60 @@ int wdgs_mesh_face_filter_select(wdgs_mesh_face_filter* filter, const void* face
 int wdgs_mesh_face_filter_compact(wdgs_mesh_face_filter* filter, const void* vertices_f32_dev, void* vertices_out_f32_dev, void* faces_out_u32_dev,
                                   void* vertex_map_u32_dev, void* face_map_u32_dev, uint32_t capacity_vertices, uint32_t capacity_faces);
 
+/* ---------------------------------------------------------------- Vertex colours baked from photographs
+ *
+ * An accumulator of views into per-vertex integer sums, and a resolve that turns the sums into rgba8 vertex colours.  Integer sums throughout, so the state
+ * does not depend on the order of the views and every output byte is a function of the inputs alone.  No reference counterpart.
+ *
+ * STATE, for a mesh of V vertices (0 <= V < 2^31): sums u64[V][4] = { R, G, B, Wt }, one 32-byte row per vertex; views u32[V]; and six u64 totals.
+ * One accumulate call takes one VIEW: vertices f32[V][3] (world space), normals f32[V][3] (nullable), the 68-float camera block, image rgba8[W H] (red in the
+ * low byte, row-major; its alpha is ignored), mesh_depth f32[W H] (nullable: the depth image wdgs_mesh_rasterizer_encode wrote for this mesh and camera),
+ * W, H, near, depth_tolerance, min_cos.  If floats 64 and 65 of the camera block are not W and H the call adds 1 to viewport_mismatch and nothing else.
+ * Otherwise, for vertex p:
+ *   1. POSITION.  The rasterizer's VERTEX rule above, verbatim: v, z, sx, sy, usable, X = (i32) rint(256 sx), Y = (i32) rint(256 sy).  A vertex that is not
+ *      usable stops here; a usable one counts in `usable`.
+ *   2. IN THE IMAGE.  X' = X - 128, Y' = Y - 128 (positions relative to the centre of texel (0, 0)); 0 <= X' <= 256 (W - 1) and 0 <= Y' <= 256 (H - 1), else the
+ *      vertex stops; it counts in `in_image`.  i0 = X' >> 8, a = X' & 255, i1 = min(i0 + 1, W - 1); j0, b, j1 likewise from Y'.  No texel outside the image is read.
+ *   3. OCCLUSION, only with mesh_depth.  Each of the four texels (i0 | i1, j0 | j1) must hold d finite and > 0 with |z - d| <= depth_tolerance, the subtraction
+ *      rounded once to f32; all four, else the vertex stops: a vertex on a silhouette is skipped in that view.  A vertex that passes, and every vertex in the
+ *      image when there is no depth image, counts in `visible`.
+ *   4. WEIGHT.  Without normals Q = 256.  With normals n, all f32, each operation rounded once, no contraction, divide and square root correctly rounded:
+ *      nv_i = (view[i] n.x + view[4 + i] n.y) + view[8 + i] n.z for i = 0, 1, 2;  dot = (nv.x v.x + nv.y v.y) + nv.z v.z;  nn = (nv.x nv.x + nv.y nv.y) + nv.z nv.z
+ *      and vv likewise from v;  c = (-dot) / sqrt(nn vv).  The vertex stops when c is not finite or c < min_cos.  Q = (u32) rint(256 (c > 1 ? 1 : c)), to
+ *      nearest, ties to even; the vertex stops when Q = 0.  A vertex that passes counts in `accumulated`.
+ *   5. SAMPLE, integers only.  With T00, T10, T01, T11 the bytes of one channel at (i0, j0), (i1, j0), (i0, j1), (i1, j1):
+ *      S = (256 - a)(256 - b) T00 + a (256 - b) T10 + (256 - a) b T01 + a b T11;  s = (S + 128) >> 8, at most 65280.
+ *   6. ADD.  R += Q s_red, G += Q s_green, B += Q s_blue, Wt += Q, views = min(views + 1, 2^32 - 1).  One view adds less than 2^24 to a sum: no sum can
+ *      overflow within 2^40 views.  The row is read and written by the one thread that owns the vertex, with plain loads and stores.
+ * TOTALS, cumulative since the reset: usable, in_image, visible, accumulated, viewport_mismatch (calls); and baked_vertices of the last resolve.
+ * RESOLVE.  A vertex is BAKED when views >= max(min_views, 1) and Wt >= max(min_weight, 1).  A baked vertex's colour: per channel the byte
+ * min(255, (R + 128 Wt) / (256 Wt)), the division in u64, truncating; alpha 255.  Any other vertex gets fallback[p], or {0,0,0,0} without a fallback.
+ * baked_out u8[V] (nullable) is 1 for a baked vertex and 0 for any other.
+ * REFUSALS, with nothing written, tested in this order.  WDGS_E_STATE: accumulate, resolve, read or stats before a reset; num_vertices other than the reset's;
+ * reset, read or stats while recording.  WDGS_E_INVALID: V >= 2^31; W or H outside 1 .. WDGS_MESH_RASTER_MAX_SIZE; near not positive and finite;
+ * depth_tolerance not finite or < 0; min_cos outside [0, 1] or NaN; a null camera, image, vertices (V > 0) or colours output (V > 0); a pointer that is not
+ * 4-byte aligned. */
+typedef struct wdgs_mesh_colour_baker wdgs_mesh_colour_baker;
+int wdgs_mesh_colour_baker_create(wdgs_device* dev, wdgs_mesh_colour_baker** out);
+int wdgs_mesh_colour_baker_destroy(wdgs_mesh_colour_baker* baker);
+/* Sizes the state for num_vertices vertices -- 36 bytes per vertex, grown as needed and reused -- and zeroes it and the totals.  A call that grows the arrays
+ * waits once.  Cannot be recorded (WDGS_E_STATE). */
+int wdgs_mesh_colour_baker_reset(wdgs_mesh_colour_baker* baker, uint32_t num_vertices);
+/* One view, as defined above.  Stream-ordered, no host wait, no allocation, recordable (a replay is one more view).  The kernel's event time is the device's
+ * (wdgs_device_get_kernel_times): mesh_bake_accumulate. */
+int wdgs_mesh_colour_baker_accumulate(wdgs_mesh_colour_baker* baker, const void* vertices_f32_dev, const void* normals_f32_dev, uint32_t num_vertices,
+                                      const void* camera_dev, const void* image_rgba8_dev, const void* mesh_depth_f32_dev, uint32_t width, uint32_t height, float near,
+                                      float depth_tolerance, float min_cos);
+/* colours_out rgba8[V] from the state as of this call; fallback rgba8[V] nullable and allowed to be colours_out itself; baked_out u8[V] nullable.
+ * Stream-ordered, no host wait, recordable.  Kernel: mesh_bake_resolve. */
+int wdgs_mesh_colour_baker_resolve(wdgs_mesh_colour_baker* baker, void* colours_out_rgba8_dev, const void* fallback_rgba8_dev, void* baked_out_u8_dev,
+                                   uint32_t num_vertices, uint32_t min_views, uint64_t min_weight);
+/* Copies the state to host memory, each pointer nullable: sums_out u64[V][4], views_out u32[V].  Waits, so it cannot be recorded. */
+int wdgs_mesh_colour_baker_read(wdgs_mesh_colour_baker* baker, uint64_t* sums_out, uint32_t* views_out);
+/* The totals, each pointer nullable.  Copies one block back and waits, so it cannot be recorded. */
+int wdgs_mesh_colour_baker_stats(wdgs_mesh_colour_baker* baker, uint64_t* usable, uint64_t* in_image, uint64_t* visible, uint64_t* accumulated,
+                                 uint64_t* viewport_mismatch, uint64_t* baked_vertices);
+
 #ifdef __cplusplus
 }
 #endif

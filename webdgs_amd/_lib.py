@@ -208,7 +208,14 @@ SIGNATURES = {
     "wdgs_mesh_face_filter_destroy": (_I, [_P]),
     "wdgs_mesh_face_filter_select": (_I, [_P, _P, _U, _U, _P, C.POINTER(_U), C.POINTER(_U), C.POINTER(_U)]),
     "wdgs_mesh_face_filter_compact": (_I, [_P, _P, _P, _P, _P, _P, _U, _U]),
-    "wdgs_point_index_create": (_I, [_P, _P, C.c_uint64, _F, C.POINTER(_P)]),
+    "wdgs_mesh_colour_baker_create": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_mesh_colour_baker_destroy": (_I, [_P]),
+    "wdgs_mesh_colour_baker_reset": (_I, [_P, _U]),
+    "wdgs_mesh_colour_baker_accumulate": (_I, [_P, _P, _P, _U, _P, _P, _P, _U, _U, _F, _F, _F]),
+    "wdgs_mesh_colour_baker_resolve": (_I, [_P, _P, _P, _P, _U, _U, C.c_uint64]),
+    "wdgs_mesh_colour_baker_read": (_I, [_P, _P, _P]),
+    "wdgs_mesh_colour_baker_stats": (_I, [_P] + [C.POINTER(C.c_uint64)] * 6),
+    "wdgs_point_index_create":(_I, [_P, _P, C.c_uint64, _F, C.POINTER(_P)]),
     "wdgs_point_index_destroy": (_I, [_P]),
     "wdgs_point_index_reserve_queries": (_I, [_P, _U]),
     "wdgs_point_index_info": (_I, [_P, C.POINTER(_F), C.POINTER(_U), C.POINTER(_U)]),

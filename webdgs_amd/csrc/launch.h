@@ -130,6 +130,14 @@ int launch_face_visibility_flags(wdgs_device* dev, u32 F, const u32* counters, u
 // face_flags u32[F] written; vertex_flags u32[V] cleared and set; invalid_faces: one word, cleared and counted into.  launch_mesh_emit writes the kept part
 int launch_face_filter_flags(wdgs_device* dev, const u32* faces, u32 F, u32 V, const unsigned char* keep, u32* face_flags, u32* vertex_flags, u32* invalid_faces);
 
+// ---- meshbake.hip.  vertices, normals (nullable) f32[V][3]; image rgba8[W H]; mesh_depth (nullable) f32[W H]; sums u64[V][4] = { R, G, B, Wt } in 32-byte
+// aligned rows and views u32[V], added to; totals: the object's block of partial sums (meshbake.hip lays it out), added to
+int launch_mesh_bake_accumulate(wdgs_device* dev, const float* vertices, const float* normals, u32 V, const float* camera, const u32* image, const float* mesh_depth,
+                                u32 W, u32 H, float near, float depth_tolerance, float min_cos, unsigned long long* sums, u32* views, unsigned long long* totals);
+// colours_out rgba8[V] written (fallback, nullable, may be the same array); baked_out u8[V] nullable; the baked vertices are counted into totals' second half, cleared first
+int launch_mesh_bake_resolve(wdgs_device* dev, u32 V, const unsigned long long* sums, const u32* views, u32 min_views, unsigned long long min_weight, const u32* fallback,
+                             u32* colours_out, unsigned char* baked_out, unsigned long long* totals);
+
 // ---- keysort.hip: the stable u64 key sort the welder (meshweld.hip) and the simplifier (meshsimplify.hip) group by; its sizing rule: keysort_sizes.h
 // The counters block, u32 words: the distinct keys, the passes run, the buffer that holds the sorted pairs, a spare, then per pass: run, input buffer, output buffer
 constexpr u32 KS_C_TOTAL = 0, KS_C_PASSES = 1, KS_C_FINAL = 2, KS_C_RUN = 4, KS_C_IN = 12, KS_C_OUT = 20, KS_C_WORDS = 28;

@@ -361,6 +361,26 @@ class Evaluator:
                 out[name] = None if mesh[name] is None else np.ascontiguousarray(np.asarray(mesh[name])[out["vertexMap"]])
         return out
 
+    # ------------------------------------------------------------------ vertex colours from the photographs
+    def bakeMeshColours(self, mesh: dict, viewIds: Optional[list] = None, split: str = "train", **options) -> dict:
+        """``mesh`` (``ops.bakeVertexColours``': numpy or a dict of ``HipBuffer``) with its vertex colours taken from the split's photographs -- the device
+        copies the trainer holds, ``images[v]["texture"]`` -- under the split's cameras: ``ops.bakeVertexColours`` with its ``options`` (``normals``,
+        ``depthTolerance``, ``minCos``, ``minViews``, ``minWeight``, ``near``, ``occlusion``, ``asBuffers``) and its result, with ``views`` added.  The views
+        may differ in size.  Where a mesh's colours so far are the model's rendered colours averaged into voxels, these are the photographs' own.
+
+        Nothing is rendered through the model: the pipeline is drained and that is all -- no RNG draw, no training pass, no recording dropped, the
+        iteration counter untouched.  Per rank with ``world_size > 1``."""
+        known = ("normals", "depthTolerance", "minCos", "minViews", "minWeight", "near", "occlusion", "asBuffers")
+        unknown = sorted(set(options) - set(known))
+        if unknown:
+            raise TypeError(f"bakeMeshColours: unknown options {unknown} (bakeVertexColours': {sorted(known)})")
+        cams, imgs, bufs, ids = self._views("bakeMeshColours", viewIds, split)
+        self._drain()
+        views = [(bufs[v], imgs[v]["texture"], int(imgs[v]["width"]), int(imgs[v]["height"])) for v in ids]
+        out = ops.bakeMeshFromViews(self.device, mesh, views, what="bakeMeshColours", **options)
+        out["views"] = ids
+        return out
+
     # ------------------------------------------------------------------ TSDF fusion and mesh extraction (DESIGN.md section 13)
     def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
         """Fuses the current model's depth maps into ``volume``: for each view in the order given, the forward pass, rasterize,
@@ -385,7 +405,7 @@ class Evaluator:
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
                     keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", simplify: Optional[float] = None,
-                    smooth: Optional[int] = None, normals: bool = False, cull: Optional[dict] = None, **volumeOptions) -> dict:
+                    smooth: Optional[int] = None, normals: bool = False, cull: Optional[dict] = None, bake=None, **volumeOptions) -> dict:
         """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
         ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result.
 
@@ -412,9 +432,22 @@ class Evaluator:
         ``minViews``, ``minAgreeing``, ``minAgreeingFraction``) and ``meshVisibility``'s options, with ``viewIds``, ``split`` and ``depthKind`` defaulting
         to the extraction's own -- after welding and component removal and BEFORE ``smooth``, ``simplify`` and ``normals``, which see the boundary it
         cuts; ``cullMesh``'s dict is what goes on (``vertexMap`` and ``faceMap`` are its own, into the mesh it was given).  The welded mesh is read and
-        handed to ``cullMesh`` as numpy with either weld, so the bytes are the same.  ``None``: as before, no new key and nothing more launched."""
+        handed to ``cullMesh`` as numpy with either weld, so the bytes are the same.  ``None``: as before, no new key and nothing more launched.
+
+        ``bake=True`` or ``bake=dict(...)``: the final mesh -- after ``simplify`` -- gets its vertex colours from the photographs by
+        ``bakeMeshColours(mesh, **bake)``, with ``viewIds`` and ``split`` defaulting to the extraction's own; ``colours`` is replaced and ``baked``,
+        ``bakeStats`` (the baker's totals; ``stats`` stays the smoother's or the simplifier's) and ``views`` are added.  The weights are the final mesh's vertex normals, computed
+        for that even when ``normals=False`` (no ``normals`` key is added then).  ``None``: as before, no new key and nothing more launched."""
         if weld not in ("host", "device"):
             raise ValueError(f"extractMesh: weld must be 'host' or 'device', not {weld!r}")
+        if bake is not None and bake is not False:
+            mesh = self.extractMesh(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld=weld, simplify=simplify,
+                                    smooth=smooth, normals=normals, cull=cull, **volumeOptions)
+            out = self.bakeMeshColours(mesh, **dict(dict(viewIds=viewIds, split=split), **({} if bake is True else bake)))
+            out["bakeStats"] = out.pop("stats")
+            if "stats" in mesh:
+                out["stats"] = mesh["stats"]
+            return out
         if cull is not None:
             mesh = self.extractMesh(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld=weld, **volumeOptions)
             culled = self.cullMesh(mesh, **dict(dict(viewIds=viewIds, split=split, depthKind=depthKind), **cull))

@@ -2168,6 +2168,199 @@ def faceVisibility(device: HipDevice, mesh: dict, cameras, width: int, height: i
             faces.destroy()
 
 
+# ----------------------------------------------------------------------------- vertex colours baked from photographs
+BAKE_STATS = ("usable", "inImage", "visible", "accumulated", "viewportMismatch", "bakedVertices")
+
+
+class MeshColourBaker:
+    """Per-vertex colour sums over views (``wdgs_mesh_colour_baker``): ``reset`` sizes them for a mesh, ``accumulate`` adds one view -- a photograph, its
+    camera block and, optionally, the vertex normals (the weights) and the depth image ``MeshRasterizer.encode`` wrote for this mesh and camera (the
+    occlusion test) -- ``resolve`` turns the sums into rgba8 vertex colours, ``read`` hands out the sums and ``stats`` the totals.  Integer sums: the
+    state does not depend on the order of the views and every byte is a function of the inputs (include/webdgs.h states the definition).
+    ``bakeVertexColours`` is the one-call form."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        self.numVertices = 0
+        h = C.c_void_p()
+        check(device.lib.wdgs_mesh_colour_baker_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def reset(self, numVertices: int) -> None:
+        """Sizes and zeroes the state for ``numVertices`` vertices.  A call that grows the arrays waits once; it cannot be recorded."""
+        if not 0 <= int(numVertices) < 2 ** 32:
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshColourBaker.reset: bad vertex count {numVertices}")
+        check(self.device.lib.wdgs_mesh_colour_baker_reset(self.handle, int(numVertices)))
+        self.numVertices = int(numVertices)
+
+    def accumulate(self, vertices: Optional[HipBuffer], numVertices: int, camera: HipBuffer, image: Optional[HipBuffer], width: int, height: int,
+                   normals: Optional[HipBuffer] = None, meshDepth: Optional[HipBuffer] = None, near: float = MESH_RASTER_NEAR, depthTolerance: float = 0.05,
+                   minCos: float = 0.1) -> None:
+        """One view of ``width`` x ``height``: ``vertices`` f32[numVertices][3], the 68-float ``camera`` block, ``image`` rgba8, and optionally ``normals``
+        f32[numVertices][3] and ``meshDepth`` f32.  A vertex is coloured by this view when it projects into the image, all four depth texels round it
+        are within ``depthTolerance`` of its own depth, and the cosine between its normal and the direction to the camera is at least ``minCos``; the
+        view's weight is that cosine.  Stream-ordered, recordable."""
+        nv, w, h = int(numVertices), int(width), int(height)
+        if not (0 <= nv < 2 ** 32 and 0 <= w < 2 ** 32 and 0 <= h < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshColourBaker.accumulate: bad counts {numVertices}, {width}x{height}")
+        if nv < 2 ** 31 and any(b is not None and b.size < 12 * nv for b in (vertices, normals)):
+            raise ValueError("MeshColourBaker.accumulate: buffers too small for the vertices")
+        if camera is not None and camera.size < 272:
+            raise ValueError("MeshColourBaker.accumulate: the camera block has 68 floats")
+        if 1 <= w <= _lib.MESH_RASTER_MAX_SIZE and 1 <= h <= _lib.MESH_RASTER_MAX_SIZE:
+            for b in (image, meshDepth):
+                if b is not None and b.size < 4 * w * h:
+                    raise ValueError(f"MeshColourBaker.accumulate: an image is too small for {w}x{h}")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_colour_baker_accumulate(self.handle, ptr(vertices), ptr(normals), nv, ptr(camera), ptr(image), ptr(meshDepth), w, h, float(near),
+                                                                float(depthTolerance), float(minCos)))
+
+    def resolve(self, coloursOut: Optional[HipBuffer], numVertices: int, fallback: Optional[HipBuffer] = None, bakedOut: Optional[HipBuffer] = None,
+                minViews: int = 1, minWeight: int = 1) -> None:
+        """``coloursOut`` rgba8[numVertices] from the current sums: a vertex at least ``minViews`` views coloured with a weight sum of at least
+        ``minWeight`` (a view adds at most 256) gets its weighted mean, alpha 255; any other ``fallback``'s colour (which may be ``coloursOut``
+        itself), or zeros.  ``bakedOut`` u8[numVertices]: which.  Stream-ordered, recordable."""
+        nv = int(numVertices)
+        if not (0 <= nv < 2 ** 32 and 0 <= int(minViews) < 2 ** 32 and 0 <= int(minWeight) < 2 ** 64):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshColourBaker.resolve: bad counts {numVertices}, {minViews}, {minWeight}")
+        if nv < 2 ** 31 and (any(b is not None and b.size < 4 * nv for b in (coloursOut, fallback)) or (bakedOut is not None and bakedOut.size < nv)):
+            raise ValueError("MeshColourBaker.resolve: buffers too small for the vertices")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_colour_baker_resolve(self.handle, ptr(coloursOut), ptr(fallback), ptr(bakedOut), nv, int(minViews), int(minWeight)))
+
+    def read(self) -> tuple:
+        """``(sums u64[V, 4] = {R, G, B, Wt}, views u32[V])`` as numpy (waits)."""
+        sums, views = np.zeros((self.numVertices, 4), np.uint64), np.zeros(self.numVertices, np.uint32)
+        check(self.device.lib.wdgs_mesh_colour_baker_read(self.handle, sums.ctypes.data, views.ctypes.data))
+        return sums, views
+
+    def stats(self) -> dict:
+        """``dict(usable, inImage, visible, accumulated, viewportMismatch, bakedVertices)``: the vertices that passed each step summed over the views
+        since the reset, the calls whose camera block was of another image size, and the baked vertices of the last resolve (waits)."""
+        v = [C.c_uint64(0) for _ in BAKE_STATS]
+        check(self.device.lib.wdgs_mesh_colour_baker_stats(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(BAKE_STATS, (int(x.value) for x in v)))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_mesh_colour_baker_destroy(self.handle)
+        self.handle = None
+
+
+def _bake_views(device: HipDevice, vertices: HipBuffer, faces: HipBuffer, V: int, F: int, normals: Optional[HipBuffer], fallback: Optional[HipBuffer], views: list,
+                depthTolerance: float, minCos: float, minViews: int, minWeight: int, near: float, occlusion: bool) -> tuple:
+    """``(colours, baked, stats)``: new rgba8[V] and u8[V] buffers -- the caller destroys them -- of a mesh on the device baked from ``views``, a list of
+    ``(camera, image, width, height)`` on the device.  The rasterizer is grown once, to the largest view, before the loop; per view one encode (with
+    ``occlusion``) and one accumulate; then one resolve."""
+    sizes = [(int(w), int(h)) for _, _, w, h in views]
+    legal = [(w, h) for w, h in sizes if 1 <= w <= _lib.MESH_RASTER_MAX_SIZE and 1 <= h <= _lib.MESH_RASTER_MAX_SIZE]
+    baker = rasterizer = depth = None
+    out = {}
+    try:
+        baker = MeshColourBaker(device)
+        baker.reset(V)
+        if occlusion and legal:
+            w, h = max(legal, key=lambda s: s[0] * s[1])
+            depth = device.createBuffer(4 * w * h, "mesh depth")
+            rasterizer = MeshRasterizer(device)
+            rasterizer.encode(vertices, V, faces, F, None, views[sizes.index((w, h))][0], w, h, near, "none", depth=depth)
+        for (camera, image, _, _), (w, h) in zip(views, sizes):
+            if rasterizer is not None and (w, h) in legal:
+                rasterizer.encode(vertices, V, faces, F, None, camera, w, h, near, "none", depth=depth)
+            baker.accumulate(vertices, V, camera, image, w, h, normals, depth if occlusion else None, near, depthTolerance, minCos)
+        out = dict(colours=device.createBuffer(4 * max(V, 1), "baked colours"), baked=device.createBuffer(max(V, 1), "baked mask"))
+        baker.resolve(out["colours"], V, fallback, out["baked"], minViews, minWeight)
+        stats = baker.stats()   # (waits: the objects released below are idle)
+        result, out = (out["colours"], out["baked"], stats), {}
+        return result
+    finally:
+        for o in (baker, rasterizer, depth):
+            if o is not None:
+                o.destroy()
+        destroyBuffers(out)
+
+
+def bakeMeshFromViews(device: HipDevice, mesh: dict, views: list, normals: bool = True, depthTolerance: float = 0.05, minCos: float = 0.1, minViews: int = 1,
+                      minWeight: int = 1, near: float = MESH_RASTER_NEAR, occlusion: bool = True, asBuffers: bool = False, what: str = "bakeVertexColours") -> dict:
+    """``bakeVertexColours`` for views that are on the device already: ``views`` is a list of ``(camera, image, width, height)`` with ``HipBuffer``s, which
+    may differ in size (``Evaluator.bakeMeshColours`` hands in the trainer's own cameras and photographs)."""
+    vertices, faces, V, F, own = _mesh_on_device(device, mesh, what)
+    owned = [vertices, faces] if own else []
+    try:
+        fallback, own_fallback = _mesh_colours_on_device(device, mesh, V, own, what)
+        if own_fallback:
+            owned.append(fallback)
+        nbuf = None
+        if normals:
+            n = mesh.get("normals")
+            if isinstance(n, HipBuffer):
+                nbuf = n
+            elif n is not None:
+                n = np.ascontiguousarray(n, np.float32)
+                if n.shape != (V, 3):
+                    raise ValueError(f"{what}: normals of shape {n.shape} for {V} vertices")
+                nbuf = device.bufferFrom(n, f"{what}: normals")
+                owned.append(nbuf)
+            else:
+                _, nbuf, _ = _smooth_and_normals(device, vertices, faces, V, F, None, True)
+                owned.append(nbuf)
+        colours, baked, stats = _bake_views(device, vertices, faces, V, F, nbuf, fallback, views, depthTolerance, minCos, minViews, minWeight, near, occlusion)
+        if asBuffers:
+            return dict(mesh, colours=colours, baked=baked, stats=stats)
+        try:
+            rgba = colours.read(np.uint8, count=4 * V).reshape(V, 4)
+            return dict(mesh, colours=np.ascontiguousarray(rgba[:, :3]), baked=baked.read(np.uint8, count=V).astype(bool), stats=stats)
+        finally:
+            colours.destroy()
+            baked.destroy()
+    finally:
+        device.synchronize()
+        for b in owned:
+            b.destroy()
+
+
+def bakeVertexColours(device: HipDevice, mesh: dict, cameras, images, width: int, height: int, normals: bool = True, depthTolerance: float = 0.05, minCos: float = 0.1,
+                      minViews: int = 1, minWeight: int = 1, near: float = MESH_RASTER_NEAR, occlusion: bool = True, asBuffers: bool = False) -> dict:
+    """``mesh`` with its vertex colours taken from photographs, without a model: per ``camera`` (68-float blocks, numpy or ``HipBuffer``) and its ``image``
+    (rgba8 ``[height, width, 4]`` numpy, or a ``HipBuffer``) the mesh's depth image is rasterized (``occlusion``) and every vertex that projects into the
+    photograph, is not hidden (all four depth texels round it within ``depthTolerance`` of its own depth) and faces the camera adds the bilinear sample
+    there, weighted by the cosine between its normal and the direction to the camera.  A vertex at least ``minViews`` views coloured, with a weight sum
+    of at least ``minWeight`` (256 per view that looks straight at it), gets the weighted mean; any other keeps the mesh's own colour (zeros for a mesh
+    without colours).
+
+    ``mesh``: numpy, or a dict of ``HipBuffer`` as ``_mesh_on_device`` takes (left as it is).  ``normals=True``: the weights use the mesh's ``normals``,
+    computed by ``vertexNormals``' kernels when it carries none; ``False``: every view weighs the same and back-facing views are not excluded.
+    ``minCos`` = 0.1 is a caller's knob, not a tuned number: it only keeps grazing views, whose samples are smeared along the surface, out of the mean.
+    Returns the mesh dict with ``colours`` u8[V, 3] replaced -- what ``loaders.saveMeshPLY`` writes -- and ``baked`` bool[V] and ``stats``
+    (``MeshColourBaker.stats``) added; ``asBuffers``: ``colours`` rgba8[V] (alpha 255 where baked) and ``baked`` u8[V] stay on the device as ``HipBuffer``
+    the caller destroys.  A function of its arguments alone, bit for bit."""
+    cameras, images = list(cameras), list(images)
+    if len(cameras) != len(images):
+        raise ValueError(f"bakeVertexColours: {len(cameras)} cameras for {len(images)} images")
+    w, h = int(width), int(height)
+    owned, views = [], []
+    try:
+        for camera, image in zip(cameras, images):
+            cam, own_cam = _camera_on_device(device, camera, "bakeVertexColours")
+            if own_cam:
+                owned.append(cam)
+            if not isinstance(image, HipBuffer):
+                a = np.ascontiguousarray(image, np.uint8)
+                if a.size != 4 * w * h:
+                    raise ValueError(f"bakeVertexColours: an image of shape {a.shape} for {w}x{h} rgba8")
+                image = device.bufferFrom(a, "bakeVertexColours: image")
+                owned.append(image)
+            views.append((cam, image, w, h))
+        return bakeMeshFromViews(device, mesh, views, normals, depthTolerance, minCos, minViews, minWeight, near, occlusion, asBuffers)
+    finally:
+        device.synchronize()
+        for b in owned:
+            b.destroy()
+
+
 class PointIndex:
     """A uniform grid over ``points`` ([M,3] float32 as numpy, or a ``HipBuffer``) for exact nearest-point queries under a cutoff (``wdgs_point_index``).
     ``cellSize`` is a speed parameter only -- no result depends on it; ``None``: chosen by the first query (its cutoff, or less for many points), which then
