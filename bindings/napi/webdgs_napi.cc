@@ -730,6 +730,55 @@ static napi_value meshColourBakerStats(napi_env env, napi_callback_info info) {
     for (uint32_t i = 0; i < 6; i++) { napi_value x; napi_create_double(env, (double)r[i], &x); napi_set_element(env, a, i, x); }
     return a;
 }
+// A texture atlas baked from photographs (include/webdgs.h: wdgs_mesh_texture_baker_*; no reference counterpart)
+static napi_value meshTextureBakerCreate(napi_env env, napi_callback_info info) {  // (device) -> handle
+    ARGS(1);
+    wdgs_mesh_texture_baker* b = nullptr;
+    WDGS_OK_OR_THROW(wdgs_mesh_texture_baker_create((wdgs_device*)get_ptr(env, argv[0]), &b));
+    return make_ptr(env, b);
+}
+static napi_value meshTextureBakerDestroy(napi_env env, napi_callback_info info) { ARGS(1); wdgs_mesh_texture_baker_destroy((wdgs_mesh_texture_baker*)get_ptr(env, argv[0])); return js_undefined(env); }
+static napi_value meshTextureBakerReset(napi_env env, napi_callback_info info) {  // (baker, numFaces, cell, accumulates) -> [width, height, cellsPerRow]
+    ARGS(4);
+    wdgs_mesh_texture_baker* b = (wdgs_mesh_texture_baker*)get_ptr(env, argv[0]);
+    WDGS_OK_OR_THROW(wdgs_mesh_texture_baker_reset(b, get_u32(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3])));
+    uint32_t r[3] = {0, 0, 0};
+    WDGS_OK_OR_THROW(wdgs_mesh_texture_baker_layout(b, &r[0], &r[1], &r[2]));
+    napi_value a; napi_create_array_with_length(env, 3, &a);
+    for (uint32_t i = 0; i < 3; i++) { napi_value x; napi_create_uint32(env, r[i], &x); napi_set_element(env, a, i, x); }
+    return a;
+}
+static napi_value meshTextureBakerAccumulate(napi_env env, napi_callback_info info) {
+    // (baker, verticesPtr | null, numVertices, facesPtr | null, numFaces, cameraPtr, imagePtr, meshDepthPtr | null, width, height, near, depthTolerance, minCos, twoSided)
+    ARGS(14);
+    WDGS_OK_OR_THROW(wdgs_mesh_texture_baker_accumulate((wdgs_mesh_texture_baker*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_ptr(env, argv[3]),
+                                                        get_u32(env, argv[4]), get_ptr(env, argv[5]), get_ptr(env, argv[6]), get_ptr(env, argv[7]), get_u32(env, argv[8]),
+                                                        get_u32(env, argv[9]), (float)get_f64(env, argv[10]), (float)get_f64(env, argv[11]), (float)get_f64(env, argv[12]),
+                                                        get_u32(env, argv[13])));
+    return js_undefined(env);
+}
+static napi_value meshTextureBakerResolve(napi_env env, napi_callback_info info) {
+    // (baker, facesPtr | null, numFaces, numVertices, coloursPtr | null, textureOutPtr | null, stateOutPtr | null, minWeight, fill)
+    ARGS(9);
+    WDGS_OK_OR_THROW(wdgs_mesh_texture_baker_resolve((wdgs_mesh_texture_baker*)get_ptr(env, argv[0]), get_ptr(env, argv[1]), get_u32(env, argv[2]), get_u32(env, argv[3]),
+                                                     get_ptr(env, argv[4]), get_ptr(env, argv[5]), get_ptr(env, argv[6]), get_u32(env, argv[7]), get_u32(env, argv[8])));
+    return js_undefined(env);
+}
+static napi_value meshTextureBakerRead(napi_env env, napi_callback_info info) {  // (baker, rows) -> ArrayBuffer(16 rows)
+    ARGS(2);
+    void* rows = nullptr; napi_value ab;
+    NAPI_OK(napi_create_arraybuffer(env, 16 * (size_t)get_u32(env, argv[1]), &rows, &ab));
+    WDGS_OK_OR_THROW(wdgs_mesh_texture_baker_read((wdgs_mesh_texture_baker*)get_ptr(env, argv[0]), (uint32_t*)rows));
+    return ab;
+}
+static napi_value meshTextureBakerStats(napi_env env, napi_callback_info info) {  // (baker) -> the eleven totals (doubles: below 2^53)
+    ARGS(1);
+    uint64_t r[11] = {0};
+    WDGS_OK_OR_THROW(wdgs_mesh_texture_baker_stats((wdgs_mesh_texture_baker*)get_ptr(env, argv[0]), r));
+    napi_value a; napi_create_array_with_length(env, 11, &a);
+    for (uint32_t i = 0; i < 11; i++) { napi_value x; napi_create_double(env, (double)r[i], &x); napi_set_element(env, a, i, x); }
+    return a;
+}
 static napi_value pointIndexCreate(napi_env env, napi_callback_info info) {  // (device, pointsPtr, numPoints, cellSize: 0 = chosen by the first query) -> handle
     ARGS(4);
     wdgs_point_index* ix = nullptr;
@@ -1414,6 +1463,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT_FN(meshFaceFilterCreate); EXPORT_FN(meshFaceFilterDestroy); EXPORT_FN(meshFaceFilterSelect); EXPORT_FN(meshFaceFilterCompact);
     EXPORT_FN(meshColourBakerCreate); EXPORT_FN(meshColourBakerDestroy); EXPORT_FN(meshColourBakerReset); EXPORT_FN(meshColourBakerAccumulate);
     EXPORT_FN(meshColourBakerResolve); EXPORT_FN(meshColourBakerRead); EXPORT_FN(meshColourBakerStats);
+    EXPORT_FN(meshTextureBakerCreate); EXPORT_FN(meshTextureBakerDestroy); EXPORT_FN(meshTextureBakerReset); EXPORT_FN(meshTextureBakerAccumulate);
+    EXPORT_FN(meshTextureBakerResolve); EXPORT_FN(meshTextureBakerRead); EXPORT_FN(meshTextureBakerStats);
     EXPORT_FN(pointIndexCreate); EXPORT_FN(pointIndexDestroy); EXPORT_FN(pointIndexReserveQueries); EXPORT_FN(pointIndexInfo); EXPORT_FN(pointIndexNearest);
     EXPORT_FN(pointDistanceStats);
     EXPORT_FN(pointIndexBounds); EXPORT_FN(pointIndexKNearest); EXPORT_FN(pointCloudPositions); EXPORT_FN(pointCloudNeighbourScales);

@@ -7,7 +7,7 @@ import { EvaluationResult, NormalConsistencyResult, Trainer, TrainingImage, Trai
 
 type Split = 'eval' | 'train';
 type DepthKind = 'median' | 'expected';
-type MeshOptions = { viewIds?: number[] | null; split?: Split; depthKind?: DepthKind; minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: import('./trainer').CullMeshOptions | null; bake?: boolean | import('./trainer').BakeMeshOptions | null } & ComponentSelection;
+type MeshOptions = { viewIds?: number[] | null; split?: Split; depthKind?: DepthKind; minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: import('./trainer').CullMeshOptions | null; bake?: boolean | import('./trainer').BakeMeshOptions | null; texture?: boolean | import('./trainer').TextureMeshOptions | null } & ComponentSelection;
 
 export class Evaluator {
   /** Uses of the trainer only: device, pointCloud, iteration, trainCameras, images, cameraBuffers, newPassSet, dcWords, longLists, drain(), growTileEntryCapacity(). */
@@ -27,6 +27,8 @@ export class Evaluator {
     import('./webdgs_hip').FilteredMesh & { counters: Uint32Array; views: number[] };
   bakeMeshColours(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: import('./trainer').BakeMeshOptions):
     import('./webdgs_hip').BakedMesh & { views: number[] };
+  bakeMeshTexture(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: import('./trainer').TextureMeshOptions):
+    import('./webdgs_hip').TexturedMesh & { views: number[] };
   fuseDepth(volume: TSDFVolume, viewIds?: number[] | null, split?: Split, depthKind?: DepthKind): number[];
   extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, options?: MeshOptions): TriangleMesh | CompactedMesh | SimplifiedMesh | import('./webdgs_hip').FilteredMesh | import('./webdgs_hip').BakedMesh;
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,

@@ -311,6 +311,17 @@ class Evaluator {
     return Object.assign(hip.bakeMeshFromViews(this.device, mesh, views, o, 'bakeMeshColours'), { views: ids });
   }
 
+  // ---------------------------------------------------------------- a texture atlas from the photographs (DESIGN.md section 23)
+  /** `mesh` with a texture atlas taken from the split's photographs under the split's cameras: hip.bakeTexture over the device copies the trainer holds, with
+   *  its options and { viewIds, split = 'train' }, and its result with views added.  Nothing is rendered through the model: the pipeline is drained and that
+   *  is all.  Same results as the Python host's. */
+  bakeMeshTexture(mesh, options) {
+    const o = options || {}, { imgs, bufs, ids } = this.views('bakeMeshTexture', o.viewIds, o.split || 'train');
+    this.drain();
+    const views = ids.map((v) => ({ camera: bufs[v], image: imgs[v].texture, width: imgs[v].width, height: imgs[v].height }));
+    return Object.assign(hip.bakeTextureFromViews(this.device, mesh, views, o, 'bakeMeshTexture'), { views: ids });
+  }
+
   // ---------------------------------------------------------------- TSDF fusion and mesh extraction (DESIGN.md section 13)
   /** Fuses the current model's depth maps into `volume` (hip.TSDFVolume): for each view in the order given, the forward pass, rasterize,
    *  encodeDepth([depthKind, 'weight_sum']) and volume.integrate with the weight sum and the rasterizer's output texture as colour (where the volume
@@ -365,6 +376,10 @@ class Evaluator {
     const o = options || {}, weld = o.weld || 'host';
     if (weld !== 'host' && weld !== 'device') throw new Error(`extractMesh: weld must be 'host' or 'device', not ${weld}`);
     const unset = (x) => x === undefined || x === null;
+    if (!unset(o.texture) && o.texture !== false) {   // (DESIGN.md section 23: last of all, after bake)
+      const mesh = this.extractMesh(lo, hi, voxelSize, Object.assign({}, o, { texture: null }));
+      return this.bakeMeshTexture(mesh, Object.assign({ viewIds: o.viewIds, split: o.split }, o.texture === true ? {} : o.texture));
+    }
     if (!unset(o.bake) && o.bake !== false) {   // (DESIGN.md section 22: last, on the final mesh; its normals are the weights even when none are asked for)
       const mesh = this.extractMesh(lo, hi, voxelSize, Object.assign({}, o, { bake: null }));
       const out = this.bakeMeshColours(mesh, Object.assign({ viewIds: o.viewIds, split: o.split }, o.bake === true ? {} : o.bake));

@@ -33,5 +33,13 @@ export function pointsPLYBytes(points: Float32Array | ArrayLike<number>): Buffer
 export function savePointsPLY(path: string, points: Float32Array | ArrayLike<number>): void;
 export function loadPointsPLY(path: string): Float32Array;
 export function saveMeshPLY(path: string, mesh: { vertices: Float32Array; faces: Uint32Array; colours?: Uint8Array | null; normals?: Float32Array | null }): void;
+/** A textured mesh (hip.bakeTexture's object) as name.obj, name.mtl and name.png: the bytes the Python host's saveMeshOBJ writes.  No reference counterpart. */
+export interface TexturedMeshArrays { vertices: Float32Array; faces: Uint32Array; uv: Float32Array; texture: Uint8Array; textureWidth: number; textureHeight: number;
+                                      normals?: Float32Array | null }
+export function saveMeshOBJ(path: string, mesh: TexturedMeshArrays): void;
+/** Reads exactly what saveMeshOBJ writes. */
+export function loadMeshOBJ(path: string): TexturedMeshArrays;
+/** C's "%.9g" of a number, ties to even on its exact value. */
+export function formatG9(x: number): string;
 export function holdoutSplit<C, I>(cameras: C[], images: I[], every?: number): [C[], I[], C[], I[]];
 export function fromQuat(qx: number, qy: number, qz: number, qw: number): Float32Array;

@@ -337,6 +337,79 @@ function meshPLYBytes(mesh) {
 }
 function saveMeshPLY(path, mesh) { require('fs').writeFileSync(path, meshPLYBytes(mesh)); }
 
+/** C's "%.9g" of a number, to nearest with ties to even on its exact value (toExponential(100) gives the exact digits of any float32): what the Python host's
+ *  saveMeshOBJ writes, and what a float32 needs to be read back exactly. */
+function formatG9(x) {
+  if (Number.isNaN(x)) return 'nan';
+  if (!Number.isFinite(x)) return x < 0 ? '-inf' : 'inf';
+  const sign = x < 0 || Object.is(x, -0) ? '-' : '';
+  if (x === 0) return sign + '0';
+  const [mant, ex] = Math.abs(x).toExponential(100).split('e');
+  let digits = mant.replace('.', ''), e = parseInt(ex, 10);
+  const rest = digits.slice(9), half = '5' + '0'.repeat(rest.length - 1);
+  let head = digits.slice(0, 9);
+  if (rest > half || (rest === half && (head.charCodeAt(8) - 48) % 2 === 1)) {
+    head = (BigInt(head) + 1n).toString();
+    if (head.length === 10) { head = head.slice(0, 9); e += 1; }
+  }
+  const strip = (t) => (t.includes('.') ? t.replace(/0+$/, '').replace(/\.$/, '') : t);
+  if (e < -4 || e >= 9) return sign + strip(head[0] + '.' + head.slice(1)) + 'e' + (e < 0 ? '-' : '+') + String(Math.abs(e)).padStart(2, '0');
+  if (e >= 0) return sign + strip(head.slice(0, e + 1) + '.' + head.slice(e + 1));
+  return sign + strip('0.' + '0'.repeat(-e - 1) + head);
+}
+/** A textured mesh -- hip.bakeTexture's object: vertices Float32Array[V*3], faces Uint32Array[F*3], uv Float32Array[F*6], texture Uint8Array[Ht*Wt*4] with
+ *  textureWidth and textureHeight, and optionally normals Float32Array[V*3] -- as name.obj (`path`), name.mtl and name.png beside it: one v (and vn) per
+ *  vertex, one vt per face corner, f a/ta b/tb c/tc (a/ta/a with normals) under one usemtl; the PNG through images.encodePNG.  The bytes the Python host's
+ *  loaders.saveMeshOBJ writes; loadMeshOBJ reads all of it back exactly.  No reference counterpart. */
+function saveMeshOBJ(path, mesh) {
+  const fs = require('fs'), { encodePNG } = require('./images.js');
+  if (!path.endsWith('.obj')) throw new Error(`saveMeshOBJ: '${path}' does not end in .obj`);
+  const v = mesh.vertices, f = mesh.faces, uv = mesh.uv, n = mesh.normals || null, V = v.length / 3, F = f.length / 3, W = mesh.textureWidth, H = mesh.textureHeight;
+  if (uv.length !== 6 * F || mesh.texture.length !== 4 * W * H) throw new Error(`saveMeshOBJ: ${uv.length} texture coordinates and a texture of ${mesh.texture.length} bytes for ${F} faces and ${W}x${H}`);
+  if (n && n.length !== 3 * V) throw new Error(`saveMeshOBJ: ${V} vertices, ${n.length / 3} normals`);
+  for (let k = 0; k < f.length; k++) if (f[k] >= V) throw new Error('saveMeshOBJ: a face names a vertex the mesh does not have');
+  const stem = path.slice(0, -4), name = stem.replace(/\\/g, '/').split('/').pop(), lines = [`mtllib ${name}.mtl`];
+  for (let k = 0; k < V; k++) lines.push(`v ${formatG9(v[3 * k])} ${formatG9(v[3 * k + 1])} ${formatG9(v[3 * k + 2])}`);
+  if (n) for (let k = 0; k < V; k++) lines.push(`vn ${formatG9(n[3 * k])} ${formatG9(n[3 * k + 1])} ${formatG9(n[3 * k + 2])}`);
+  for (let k = 0; k < 3 * F; k++) lines.push(`vt ${formatG9(uv[2 * k])} ${formatG9(uv[2 * k + 1])}`);
+  lines.push('usemtl baked');
+  for (let k = 0; k < F; k++) {
+    const corner = (c) => { const a = f[3 * k + c] + 1, t = 3 * k + c + 1; return n ? `${a}/${t}/${a}` : `${a}/${t}`; };
+    lines.push(`f ${corner(0)} ${corner(1)} ${corner(2)}`);
+  }
+  fs.writeFileSync(path, lines.join('\n') + '\n', 'ascii');
+  fs.writeFileSync(stem + '.mtl', `newmtl baked\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd ${name}.png\n`, 'ascii');
+  fs.writeFileSync(stem + '.png', encodePNG(mesh.texture, W, H));
+}
+/** Reads an OBJ as saveMeshOBJ writes it, with the PNG its MTL names: { vertices, faces, uv, texture, textureWidth, textureHeight } and normals when the file
+ *  has vn. */
+function loadMeshOBJ(path) {
+  const fs = require('fs'), { decodePNG } = require('./images.js');
+  const v = [], vn = [], vt = [], faces = [], corners = [];
+  let mtl = null;
+  for (const ln of fs.readFileSync(path, 'ascii').split('\n')) {
+    const w = ln.split(/\s+/).filter((x) => x.length);
+    if (!w.length) continue;
+    if (w[0] === 'v') v.push(+w[1], +w[2], +w[3]);
+    else if (w[0] === 'vn') vn.push(+w[1], +w[2], +w[3]);
+    else if (w[0] === 'vt') vt.push(+w[1], +w[2]);
+    else if (w[0] === 'f') {
+      if (w.length !== 4) throw new Error('loadMeshOBJ: only triangles are read');
+      for (const c of w.slice(1)) { const p = c.split('/'); faces.push(parseInt(p[0], 10) - 1); corners.push(parseInt(p[1], 10) - 1); }
+    } else if (w[0] === 'mtllib') mtl = w[1];
+  }
+  if (mtl === null) throw new Error('loadMeshOBJ: not a mesh as saveMeshOBJ writes it (no mtllib)');
+  const slash = path.replace(/\\/g, '/').lastIndexOf('/'), folder = slash >= 0 ? path.slice(0, slash + 1) : '';
+  let image = null;
+  for (const ln of fs.readFileSync(folder + mtl, 'ascii').split('\n')) { const w = ln.split(/\s+/).filter((x) => x.length); if (w[0] === 'map_Kd') image = w[1]; }
+  if (image === null) throw new Error('loadMeshOBJ: the material names no texture');
+  const png = decodePNG(fs.readFileSync(folder + image)), all = Float32Array.from(vt), uv = new Float32Array(2 * corners.length);
+  corners.forEach((c, k) => { uv[2 * k] = all[2 * c]; uv[2 * k + 1] = all[2 * c + 1]; });
+  const out = { vertices: Float32Array.from(v), faces: Uint32Array.from(faces), uv, texture: png.data, textureWidth: png.width, textureHeight: png.height };
+  if (vn.length) out.normals = Float32Array.from(vn);
+  return out;
+}
+
 // ---------------------------------------------------------------- point sets (no reference counterpart)
 const PLY_SCALAR = { char: 1, int8: 1, uchar: 1, uint8: 1, short: 2, int16: 2, ushort: 2, uint16: 2, int: 4, int32: 4, uint: 4, uint32: 4, float: 4, float32: 4, double: 8, float64: 8 };
 /** Points (Float32Array [N*3]) as a binary little-endian PLY with the one element `vertex` of x y z float. */
@@ -380,5 +453,5 @@ function loadPointsPLY(path) {
   return out;
 }
 
-module.exports = { pointsPLYBytes, savePointsPLY, loadPointsPLY, meshPLYBytes, saveMeshPLY, holdoutSplit, C0, f16Bits, f16ToNumber, decodeHeader, readRawVertex, nShCoeffs, loadPly, loadColmapBin, loadPointCloud, exportPly, loadCameraJson, loadColmapImagesBin,
+module.exports = { pointsPLYBytes, savePointsPLY, loadPointsPLY, meshPLYBytes, saveMeshPLY, formatG9, saveMeshOBJ, loadMeshOBJ, holdoutSplit, C0, f16Bits, f16ToNumber, decodeHeader, readRawVertex, nShCoeffs, loadPly, loadColmapBin, loadPointCloud, exportPly, loadCameraJson, loadColmapImagesBin,
   loadColmapCamerasBin, mergeColmap, loadCamera, cameraUniforms, fromQuat };

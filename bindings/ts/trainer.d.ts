@@ -80,6 +80,9 @@ export class Trainer {
   /** The mesh with its vertex colours taken from the split's photographs under the split's cameras (bakeVertexColours over the trainer's own device copies):
    *  colours, baked and stats replaced or added, and the views.  Training untouched.  No reference counterpart. */
   bakeMeshColours(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: BakeMeshOptions): import('./webdgs_hip').BakedMesh & { views: number[] };
+  /** The mesh with a texture atlas taken from the split's photographs under the split's cameras (bakeTexture over the trainer's own device copies): texture,
+   *  uv, texelState, textureStats and the atlas's sizes added, and the views.  Training untouched.  No reference counterpart. */
+  bakeMeshTexture(mesh: import('./webdgs_hip').MeshArrays | import('./webdgs_hip').MeshBuffers, options?: TextureMeshOptions): import('./webdgs_hip').TexturedMesh & { views: number[] };
   /** Fuses the current model's depth maps (and the rendered colour) into a TSDFVolume, view by view in the order given; rendered through evaluate's
    *  passes, training untouched.  Returns the view list.  No reference counterpart. */
   fuseDepth(volume: import('./webdgs_hip').TSDFVolume, viewIds?: number[] | null, split?: 'eval' | 'train', depthKind?: 'median' | 'expected'): number[];
@@ -90,13 +93,13 @@ export class Trainer {
    *  and normals.  bake: true or bakeMeshColours' options -- the final mesh's colours are taken from the photographs, last.  No reference counterpart. */
   extractMesh(lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number,
               options?: { viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected'; minWeight?: number; truncation?: number; maxWeight?: number;
-                          colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null; bake?: boolean | BakeMeshOptions | null } & import('./webdgs_hip').ComponentSelection):
+                          colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null; bake?: boolean | BakeMeshOptions | null; texture?: boolean | TextureMeshOptions | null } & import('./webdgs_hip').ComponentSelection):
     import('./webdgs_hip').TriangleMesh | import('./webdgs_hip').CompactedMesh | import('./webdgs_hip').SimplifiedMesh | import('./webdgs_hip').FilteredMesh | import('./webdgs_hip').BakedMesh;
   /** extractMesh -> sampleMesh -> geometryMetrics against `reference` (points [M*3], or the path of a PLY): the mesh's accuracy, completeness, Chamfer
    *  distance, precision, recall and F-score, with the mesh's vertex, face and sample counts and ms.  Training untouched.  No reference counterpart. */
   evaluateGeometry(reference: Float32Array | string, lo: ArrayLike<number>, hi: ArrayLike<number>, voxelSize: number, maxDistance: number, threshold: number,
                    options?: { density?: number | null; seed?: number; viewIds?: number[] | null; split?: 'eval' | 'train'; depthKind?: 'median' | 'expected';
-                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null; bake?: boolean | BakeMeshOptions | null } &
+                               minWeight?: number; truncation?: number; maxWeight?: number; colour?: boolean; weld?: 'host' | 'device'; simplify?: number | null; smooth?: number | null; normals?: boolean; cull?: CullMeshOptions | null; bake?: boolean | BakeMeshOptions | null; texture?: boolean | TextureMeshOptions | null } &
                      import('./webdgs_hip').ComponentSelection):
     import('./webdgs_hip').GeometryMetrics & { vertices: number; faces: number; samples: number; ms: number };
   /** Per-Gaussian render contribution accumulated over the views (default: all training views); no reference counterpart. */
@@ -135,6 +138,7 @@ export interface MeshVisibilityOptions {
 }
 export type CullMeshOptions = MeshVisibilityOptions & import('./webdgs_hip').FaceRule;
 export type BakeMeshOptions = { viewIds?: number[] | null; split?: 'eval' | 'train' } & import('./webdgs_hip').BakeOptions;
+export type TextureMeshOptions = { viewIds?: number[] | null; split?: 'eval' | 'train' } & import('./webdgs_hip').TextureOptions;
 export interface MeshVisibilityResult {
   iteration: number; views: number[]; counters: Uint32Array; counted: number[]; agreeing: number[]; foreign: number[]; ms: number;
 }

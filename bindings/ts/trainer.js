@@ -714,6 +714,8 @@ class Trainer {
   cullMesh(mesh, options) { return this.evaluator.cullMesh(mesh, options); }
   /** Evaluator.bakeMeshColours: a mesh with its vertex colours taken from the split's photographs under the split's cameras. */
   bakeMeshColours(mesh, options) { return this.evaluator.bakeMeshColours(mesh, options); }
+  /** Evaluator.bakeMeshTexture: a mesh with a texture atlas taken from the split's photographs under the split's cameras. */
+  bakeMeshTexture(mesh, options) { return this.evaluator.bakeMeshTexture(mesh, options); }
   /** Evaluator.fuseDepth: fuses the current model's depth maps into `volume`. */
   fuseDepth(volume, viewIds, split, depthKind) { return this.evaluator.fuseDepth(volume, viewIds, split, depthKind); }
   /** Evaluator.evaluateGeometry: the extracted mesh scored against a reference point set. */

@@ -483,6 +483,41 @@ export function bakeVertexColours(device: HipDevice, mesh: MeshArrays | MeshBuff
 /** bakeVertexColours for views on the device, which may differ in size. */
 export function bakeMeshFromViews(device: HipDevice, mesh: MeshArrays | MeshBuffers, views: BakeView[], options?: BakeOptions, what?: string): BakedMesh;
 export type BakedMesh = { [key: string]: unknown; colours: Uint8Array | HipBuffer; baked: Uint8Array | HipBuffer; stats: BakeStats };
+export interface TextureStats { invalidFaces: number; facingAwayFaces: number; offImageFaces: number; usable: number; inImage: number; visible: number; accumulated: number;
+                                viewportMismatch: number; bakedTexels: number; filledTexels: number; fallbackTexels: number }
+/** bakeTexture's options: cell (8: the edge of the square cell two faces share, 4, 8, 16 or 32 texels), depthTolerance (0.05), minCos (0.1), minWeight (1),
+ *  near, occlusion (true), twoSided (false), fill (true: an unseen texel next to seen ones of its face takes their mean), asBuffers. */
+export interface TextureOptions { cell?: number; depthTolerance?: number; minCos?: number; minWeight?: number; near?: number; occlusion?: boolean; twoSided?: boolean;
+                                  fill?: boolean; asBuffers?: boolean }
+export interface TextureLayout { width: number; height: number; cellsPerRow: number }
+/** The atlas of numFaces faces in cells of `cell` texels and its per-corner texture coordinates uv: Float32Array[F * 6] (OBJ convention).  Arithmetic alone. */
+export function textureLayout(numFaces: number, cell?: number): TextureLayout & { uv: Float32Array };
+/** Per-texel colour sums of a mesh's texture atlas over views (wdgs_mesh_texture_baker): u32[cells cell cell][4] = { R, G, B, Wsum }, cell-major.  No reference
+ *  counterpart. */
+export class MeshTextureBaker {
+  constructor(device: HipDevice);
+  readonly numFaces: number;
+  readonly cell: number;
+  readonly width: number;
+  readonly height: number;
+  readonly cellsPerRow: number;
+  reset(numFaces: number, cell?: number, accumulates?: number): TextureLayout;
+  accumulate(vertices: HipBuffer | null, numVertices: number, faces: HipBuffer | null, numFaces: number, camera: HipBuffer | null, image: HipBuffer | null, width: number,
+             height: number, options?: { meshDepth?: HipBuffer | null; near?: number; depthTolerance?: number; minCos?: number; twoSided?: boolean }): void;
+  resolve(faces: HipBuffer | null, numFaces: number, numVertices: number, textureOut: HipBuffer | null,
+          options?: { colours?: HipBuffer | null; stateOut?: HipBuffer | null; minWeight?: number; fill?: boolean }): void;
+  read(): Uint32Array;
+  stats(): TextureStats;
+  destroy(): void;
+}
+/** The mesh with texture: Uint8Array[Ht Wt 4], uv: Float32Array[F * 6], texelState: Uint8Array[Ht Wt], textureWidth, textureHeight, textureCell and textureStats;
+ *  with asBuffers texture and texelState stay on the device.  No reference counterpart. */
+export function bakeTexture(device: HipDevice, mesh: MeshArrays | MeshBuffers, cameras: Array<Float32Array | HipBuffer>, images: Array<Uint8Array | HipBuffer>,
+                            width: number, height: number, options?: TextureOptions): TexturedMesh;
+/** bakeTexture for views on the device, which may differ in size. */
+export function bakeTextureFromViews(device: HipDevice, mesh: MeshArrays | MeshBuffers, views: BakeView[], options?: TextureOptions, what?: string): TexturedMesh;
+export type TexturedMesh = { [key: string]: unknown; texture: Uint8Array | HipBuffer; uv: Float32Array; texelState: Uint8Array | HipBuffer; textureWidth: number;
+                             textureHeight: number; textureCell: number; textureStats: TextureStats };
 /** colours and keys of a typed-array mesh gathered through out.vertexMap into out. */
 export function gatherVertexAttributes(mesh: { colours?: unknown; keys?: unknown }, out: { vertexMap: Uint32Array; colours?: Uint8Array | null; keys?: BigUint64Array | null }): void;
 /** A uniform grid over points for exact nearest-point queries under a cutoff (wdgs_point_index); the cell edge is a speed parameter only.  No reference

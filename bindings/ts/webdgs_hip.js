@@ -1579,6 +1579,153 @@ function bakeVertexColours(device, mesh, cameras, images, width, height, options
     owned.forEach((b) => b.destroy());
   }
 }
+// ---------------------------------------------------------------- a texture atlas baked from photographs (include/webdgs.h, DESIGN.md section 23)
+const TEXTURE_STATS = ['invalidFaces', 'facingAwayFaces', 'offImageFaces', 'usable', 'inImage', 'visible', 'accumulated', 'viewportMismatch', 'bakedTexels',
+  'filledTexels', 'fallbackTexels'];
+const MESH_TEXTURE_MAX_SIZE = 16384;
+/** The atlas of numFaces faces in square cells of `cell` texels (4, 8, 16 or 32; default 8), two faces per cell: { width, height, cellsPerRow,
+ *  uv: Float32Array[F * 3 * 2] } with the per-corner texture coordinates in the OBJ convention -- u = (x + 0.5) / width, v = 1 - (y + 0.5) / height for the
+ *  atlas texel (x, y) a corner sits on, computed in doubles and rounded once.  Arithmetic alone; the same bytes as the Python host's. */
+function textureLayout(numFaces, cell) {
+  const F = numFaces, c = cell === undefined || cell === null ? 8 : cell;
+  if (!(Number.isInteger(F) && F >= 0 && F < 2 ** 31)) throw new Error(`textureLayout: ${numFaces} faces (0 to 2^31 - 1)`);
+  if (![4, 8, 16, 32].includes(c)) throw new Error(`textureLayout: a cell of ${cell} texels (4, 8, 16 or 32)`);
+  const cells = Math.floor((F + 1) / 2);
+  let perRow = Math.floor(Math.sqrt(cells));
+  while (perRow * perRow < cells) perRow++;
+  while (perRow > 0 && (perRow - 1) * (perRow - 1) >= cells) perRow--;
+  const rows = perRow ? Math.ceil(cells / perRow) : 0, width = perRow * c, height = rows * c, m = c - 3;
+  if (width > MESH_TEXTURE_MAX_SIZE) throw new Error(`textureLayout: ${F} faces in cells of ${c} texels need an atlas ${width} texels wide (at most ${MESH_TEXTURE_MAX_SIZE})`);
+  const uv = new Float32Array(6 * F), corner = [[0, 0], [m, 0], [0, m]];
+  for (let f = 0; f < F; f++) {
+    const k = Math.floor(f / 2), odd = f % 2;
+    for (let n = 0; n < 3; n++) {
+      const i = odd ? c - 1 - corner[n][0] : corner[n][0], j = odd ? c - 1 - corner[n][1] : corner[n][1];
+      uv[6 * f + 2 * n] = ((k % perRow) * c + i + 0.5) / width;
+      uv[6 * f + 2 * n + 1] = 1.0 - (Math.floor(k / perRow) * c + j + 0.5) / height;
+    }
+  }
+  return { width, height, cellsPerRow: perRow, uv };
+}
+/** Per-texel colour sums of a mesh's texture atlas over views (wdgs_mesh_texture_baker): reset lays the atlas out for a face count and a cell size and zeroes
+ *  the sums, accumulate adds one view, resolve turns the sums into an rgba8 texture, read hands out the sums and stats the totals.  Integer sums: the state does
+ *  not depend on the order of the views and every byte is a function of the inputs.  bakeTexture is the one-call form. */
+class MeshTextureBaker {
+  constructor(device) {
+    this.device = device; this.destroyed = false; this.numFaces = this.cell = this.width = this.height = this.cellsPerRow = 0;
+    this.handle = addon.meshTextureBakerCreate(device.handle);
+  }
+  /** Lays the atlas out and zeroes the state; returns { width, height, cellsPerRow }.  A call that grows the array waits once; it cannot be recorded.
+   *  accumulates: where the count of views starts, for the test of the refusal of the 65536th. */
+  reset(numFaces, cell, accumulates) {
+    const c = cell === undefined || cell === null ? 8 : cell, r = addon.meshTextureBakerReset(this.handle, numFaces, c, accumulates || 0);
+    this.numFaces = numFaces; this.cell = c; [this.width, this.height, this.cellsPerRow] = r;
+    return { width: r[0], height: r[1], cellsPerRow: r[2] };
+  }
+  /** One view of width x height; options: { meshDepth (a HipBuffer or null), near = MESH_RASTER_NEAR, depthTolerance = 0.05, minCos = 0.1, twoSided = false }.
+   *  Stream-ordered, recordable. */
+  accumulate(vertices, numVertices, faces, numFaces, camera, image, width, height, options) {
+    const o = options || {}, pick = (v, d) => (v === undefined || v === null ? d : v);
+    if ((numVertices < 2 ** 31 && vertices && vertices.size < 12 * numVertices) || (numFaces < 2 ** 31 && faces && faces.size < 12 * numFaces)) throw new Error('MeshTextureBaker.accumulate: buffers too small for the mesh');
+    if (camera && camera.size < 272) throw new Error('MeshTextureBaker.accumulate: the camera block has 68 floats');
+    if (width >= 1 && width <= MESH_RASTER_MAX_SIZE && height >= 1 && height <= MESH_RASTER_MAX_SIZE) {
+      for (const b of [image, o.meshDepth]) if (b && b.size < 4 * width * height) throw new Error(`MeshTextureBaker.accumulate: an image is too small for ${width}x${height}`);
+    }
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshTextureBakerAccumulate(this.handle, ptr(vertices), numVertices, ptr(faces), numFaces, ptr(camera), ptr(image), ptr(o.meshDepth), width, height,
+      Math.fround(pick(o.near, MESH_RASTER_NEAR)), Math.fround(pick(o.depthTolerance, 0.05)), Math.fround(pick(o.minCos, 0.1)), o.twoSided ? 1 : 0);
+  }
+  /** textureOut rgba8[height][width] from the current sums; options: { colours rgba8[numVertices], stateOut u8[height][width], minWeight = 1, fill = true }.
+   *  Stream-ordered, recordable. */
+  resolve(faces, numFaces, numVertices, textureOut, options) {
+    const o = options || {}, pick = (v, d) => (v === undefined || v === null ? d : v), minWeight = pick(o.minWeight, 1), n = this.width * this.height;
+    if (!(Number.isInteger(minWeight) && minWeight >= 0 && minWeight < 2 ** 32)) { const e = new Error(`MeshTextureBaker.resolve: bad threshold ${minWeight}`); e.code = 'WDGS_E'; throw e; }
+    if ((textureOut && textureOut.size < 4 * n) || (o.stateOut && o.stateOut.size < n)) throw new Error(`MeshTextureBaker.resolve: an output is too small for ${this.width}x${this.height}`);
+    if ((numFaces < 2 ** 31 && faces && faces.size < 12 * numFaces) || (numVertices < 2 ** 31 && o.colours && o.colours.size < 4 * numVertices)) throw new Error('MeshTextureBaker.resolve: buffers too small for the mesh');
+    const ptr = (b) => (b ? b.ptr : null);
+    addon.meshTextureBakerResolve(this.handle, ptr(faces), numFaces, numVertices, ptr(o.colours), ptr(textureOut), ptr(o.stateOut), minWeight, pick(o.fill, true) ? 1 : 0);
+  }
+  /** Uint32Array[4 * cells * cell * cell]: R, G, B, Wsum per texel, cell-major (waits). */
+  read() { return new Uint32Array(addon.meshTextureBakerRead(this.handle, Math.floor((this.numFaces + 1) / 2) * this.cell * this.cell)); }
+  /** The eleven totals by name (waits). */
+  stats() { const r = addon.meshTextureBakerStats(this.handle), out = {}; TEXTURE_STATS.forEach((k, i) => { out[k] = r[i]; }); return out; }
+  destroy() { if (this.destroyed) return; this.destroyed = true; addon.meshTextureBakerDestroy(this.handle); this.handle = null; }
+}
+/** bakeTexture for views that are on the device already: `views` is an array of { camera, image, width, height } with HipBuffers, which may differ in size.
+ *  options: bakeTexture's. */
+function bakeTextureFromViews(device, mesh, views, options, what) {
+  const o = options || {}, pick = (v, d) => (v === undefined || v === null ? d : v), name = what || 'bakeTexture';
+  const occlusion = pick(o.occlusion, true), cell = pick(o.cell, 8), src = meshOnDevice(device, mesh, name), V = src.V, F = src.F, owned = src.own ? [src.vertices, src.faces] : [];
+  const upload = (a) => { const b = device.createBuffer({ size: Math.max(a.byteLength, 8) }); if (a.byteLength) device.queue.writeBuffer(b, 0, a); owned.push(b); return b; };
+  let baker = null, rasterizer = null, depth = null, out = {};
+  try {
+    let colours = null;
+    const c = mesh.colours;
+    if (c instanceof HipBuffer) colours = c;
+    else if (c) {
+      let rgba = c;
+      if (c.length === 3 * V) {
+        rgba = new Uint8Array(4 * V).fill(255);
+        for (let v = 0; v < V; v++) for (let a = 0; a < 3; a++) rgba[4 * v + a] = c[3 * v + a];
+      } else if (c.length !== 4 * V) throw new Error(`${name}: ${c.length} colour bytes for ${V} vertices`);
+      colours = upload(rgba instanceof Uint8Array ? rgba : Uint8Array.from(rgba));
+    }
+    const layout = textureLayout(F, cell), n = layout.width * layout.height;
+    const legal = views.filter((w) => w.width >= 1 && w.width <= MESH_RASTER_MAX_SIZE && w.height >= 1 && w.height <= MESH_RASTER_MAX_SIZE);
+    baker = new MeshTextureBaker(device);
+    baker.reset(F, cell);
+    if (occlusion && legal.length) {   // (the rasterizer is grown once, to the largest view, in front of the loop)
+      const big = legal.reduce((a, w) => (w.width * w.height > a.width * a.height ? w : a), legal[0]);
+      depth = device.createBuffer({ size: Math.max(4 * big.width * big.height, 16), label: 'mesh depth' });
+      rasterizer = new MeshRasterizer(device);
+      rasterizer.encode(src.vertices, V, src.faces, F, null, big.camera, big.width, big.height, { near: o.near, depth });
+    }
+    for (const w of views) {
+      if (rasterizer && legal.includes(w)) rasterizer.encode(src.vertices, V, src.faces, F, null, w.camera, w.width, w.height, { near: o.near, depth });
+      baker.accumulate(src.vertices, V, src.faces, F, w.camera, w.image, w.width, w.height, { meshDepth: occlusion ? depth : null, near: o.near, depthTolerance: o.depthTolerance,
+        minCos: o.minCos, twoSided: o.twoSided });
+    }
+    out = { texture: device.createBuffer({ size: Math.max(4 * n, 8), label: 'baked texture' }), texelState: device.createBuffer({ size: Math.max(n, 8), label: 'texel state' }) };
+    baker.resolve(src.faces, F, V, out.texture, { colours, stateOut: out.texelState, minWeight: o.minWeight, fill: o.fill });
+    const textureStats = baker.stats();   // (waits: the objects released below are idle)
+    const extra = { uv: layout.uv, textureWidth: layout.width, textureHeight: layout.height, textureCell: cell, textureStats };
+    if (o.asBuffers) { const result = Object.assign({}, mesh, out, extra); out = {}; return result; }
+    return Object.assign({}, mesh, { texture: new Uint8Array(n ? device.readBuffer(out.texture, 4 * n) : new ArrayBuffer(0)),
+      texelState: new Uint8Array(n ? device.readBuffer(out.texelState, n) : new ArrayBuffer(0)) }, extra);
+  } finally {
+    for (const x of [baker, rasterizer, depth]) if (x) x.destroy();
+    destroyBuffers(out);
+    device.synchronize();
+    owned.forEach((b) => b.destroy());
+  }
+}
+/** `mesh` with a texture atlas taken from photographs, without a model (the Python host's ops.bakeTexture).  options: { cell = 8, depthTolerance = 0.05,
+ *  minCos = 0.1, minWeight = 1, near = MESH_RASTER_NEAR, occlusion = true, twoSided = false, fill = true, asBuffers }.  Returns the mesh's object with
+ *  texture: Uint8Array[Ht * Wt * 4] (row 0 at the top), uv: Float32Array[F * 6], texelState: Uint8Array[Ht * Wt] (1 baked, 2 filled, 0 otherwise),
+ *  textureWidth, textureHeight, textureCell and textureStats added; asBuffers: texture and texelState stay on the device.  Same results as the Python host's. */
+function bakeTexture(device, mesh, cameras, images, width, height, options) {
+  if (cameras.length !== images.length) throw new Error(`bakeTexture: ${cameras.length} cameras for ${images.length} images`);
+  const owned = [];
+  const upload = (a) => { const b = device.createBuffer({ size: Math.max(a.byteLength, 8) }); if (a.byteLength) device.queue.writeBuffer(b, 0, a); owned.push(b); return b; };
+  try {
+    const views = cameras.map((camera, k) => {
+      let cam = camera, image = images[k];
+      if (!(camera instanceof HipBuffer)) {
+        if (camera.length !== 68) throw new Error(`bakeTexture: the camera block has 68 floats, got ${camera.length}`);
+        cam = upload(camera instanceof Float32Array ? camera : Float32Array.from(camera));
+      }
+      if (!(image instanceof HipBuffer)) {
+        if (image.length !== 4 * width * height) throw new Error(`bakeTexture: an image of ${image.length} bytes for ${width}x${height} rgba8`);
+        image = upload(image instanceof Uint8Array ? image : Uint8Array.from(image));
+      }
+      return { camera: cam, image, width, height };
+    });
+    return bakeTextureFromViews(device, mesh, views, options);
+  } finally {
+    device.synchronize();
+    owned.forEach((b) => b.destroy());
+  }
+}
 /** A uniform grid over `points` ([M*3] Float32Array, or a HipBuffer) for exact nearest-point queries under a cutoff (wdgs_point_index).  options:
  *  { cellSize, count }.  cellSize is a speed parameter only -- no result depends on it; without one it is chosen by the first query (its cutoff, or less
  *  for many points), which then finishes the build.  Non-finite points are left out.  The build waits once; queries are stream-ordered. */
@@ -1809,4 +1956,4 @@ module.exports = { addon, DEPTH_KINDS, depthToRGBA8, TSDFVolume, weldTriangles, 
   geometryMetrics, NO_NORMAL, depthToNormals, encodeNormalAgreement, normalAgreement, normalToRGBA8, CONTRIBUTION_RECORD_BYTES, createContributionBuffer, readContribution, MAX_LANES, MAX_BATCH_VIEWS, projectViews, geometryViews, imageSSE, imagePSNR, imageSSIM, encodeImageSSE, encodeImageSSIM, psnrFromSSE, Communicator, HipBuffer, HipCommandBuffer, HipEncoder, HipDevice, CapacityReports, grownTileEntries, allocatePointCloudLike, PrefixScanner, get_prefix_scanner, DynamicSortStuff,
   get_dynamic_sorter, TiledForwardPass, TiledRasterizer, TiledBackwardPass, DEFAULT_ADAM_HYPERPARAMETERS, allocateOptimizerStateBuffers, Optimizer,
   DensifyPrunePass, downsampleRGBA8, FaceVisibility, MeshFaceFilter, encodeFaceVisibilityFlags, selectFaces, filterFaces, faceVisibility, gatherVertexAttributes,
-  MeshColourBaker, bakeMeshFromViews, bakeVertexColours };
+  MeshColourBaker, bakeMeshFromViews, bakeVertexColours, MeshTextureBaker, textureLayout, bakeTextureFromViews, bakeTexture };

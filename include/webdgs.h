@@ -1091,6 +1091,84 @@ int wdgs_mesh_colour_baker_read(wdgs_mesh_colour_baker* baker, uint64_t* sums_ou
 int wdgs_mesh_colour_baker_stats(wdgs_mesh_colour_baker* baker, uint64_t* usable, uint64_t* in_image, uint64_t* visible, uint64_t* accumulated,
                                  uint64_t* viewport_mismatch, uint64_t* baked_vertices);
 
+/* ---------------------------------------------------------------- A texture atlas baked from photographs
+ *
+ * An atlas laid out by arithmetic alone, an accumulator of views into per-texel integer sums, and a resolve that turns the sums into an rgba8 texture.
+ * Integer sums throughout, so the state does not depend on the order of the views and every output byte is a function of the inputs alone.  No reference
+ * counterpart.
+ *
+ * THE ATLAS, for a mesh of F faces (0 <= F < 2^31) and a cell edge of C texels (4, 8, 16 or 32), m = C - 3.  cells = ceil(F / 2); cell k holds faces 2k and
+ * 2k + 1; cells_per_row = the least r with r r >= cells; rows = ceil(cells / cells_per_row) (0 for no cells); the atlas is Wt = cells_per_row C by Ht = rows C
+ * texels, row 0 at the top, cell k at column k mod cells_per_row and row k / cells_per_row of cells.  Wt <= WDGS_MESH_TEXTURE_MAX_SIZE.
+ * In a cell's own texel indices (i, j), i rightwards and j downwards: the EVEN face owns the texels with i + j <= C - 2, the ODD face those with i + j >= C,
+ * nobody those with i + j = C - 1.  A texel of a face that does not exist (2k + 1 = F) is owned by nobody.  (i', j') = (i, j) for the even face and
+ * (C - 1 - i, C - 1 - j) for the odd one: the face's corners v0, v1, v2 sit at the centres of the texels (i', j') = (0, 0), (m, 0), (0, m), and the corner's
+ * texture coordinates, for the atlas texel (x, y) it sits on, are u = (x + 0.5) / Wt, v = 1 - (y + 0.5) / Ht (the hosts compute them).  A bilinear lookup
+ * anywhere inside the triangle of those three points touches only texels the face owns.
+ * STATE: rows u32[cells C C][4] = { R, G, B, Wsum }, one 16-byte row per texel in CELL-major order -- the texel (i, j) of cell k is row k C C + j C + i --
+ * eleven u64 totals, and the number of accumulates since the reset.  Rows of texels nobody owns stay zero and are never read or written.
+ * One accumulate call takes one VIEW: vertices f32[V][3] (world space), faces u32[F][3], the 68-float camera block, image rgba8[W H] (red in the low byte,
+ * row-major; its alpha is ignored), mesh_depth f32[W H] (nullable: the depth image wdgs_mesh_rasterizer_encode wrote for this mesh and camera), W, H, near,
+ * depth_tolerance, min_cos, two_sided.  If floats 64 and 65 of the camera block are not W and H the call adds 1 to viewport_mismatch and nothing else (it
+ * still counts as an accumulate).  Otherwise, all f32, each operation rounded once, no contraction, divide and square root correctly rounded:
+ *   1. THE FACE.  Per corner k with index a_k: P_k = the rasterizer's VERTEX rule's v (x, y) and z of vertex a_k.  The corner is GOOD when a_k < V, the three
+ *      components are finite and z >= near.  A face with a corner that is not good is INVALID (a face that crosses the near plane is: nothing is clipped).
+ *      n = (P1 - P0) x (P2 - P0), each component two products and a subtraction; nn = (n.x n.x + n.y n.y) + n.z n.z.  Q(p), for a point p:
+ *      dot = (n.x p.x + n.y p.y) + n.z p.z;  pp = (p.x p.x + p.y p.y) + p.z p.z;  c = (-dot) / sqrt(nn pp), |c| with two_sided;  Q = 0 when c is not finite or
+ *      c < min_cos, else (u32) rint(256 (c > 1 ? 1 : c)), to nearest, ties to even.  A zero-area face has Q = 0 everywhere.  A face that is not invalid is
+ *      FACING AWAY when Q(P_k) = 0 at all three corners.  With the VERTEX rule's sx, sy of a corner, a face that is neither is OFF THE IMAGE when all three
+ *      corners have sx < 0, or all three sx > W, or all three sy < 0, or all three sy > H.  Each face counts in at most one of invalid_faces,
+ *      facing_away_faces, off_image_faces, and its texels stop here; the texels of any other face go on.
+ *   2. THE TEXEL'S POINT, for every texel the face owns -- those outside the triangle included, on the face's plane extended:  u = i' / m, v = j' / m,
+ *      w = (1 - u) - v;  p = (w P0 + u P1) + v P2 per component;  sx = (((P00 p.x) / p.z) 0.5 + 0.5) W and sy = ((((-P11) p.y) / p.z) 0.5 + 0.5) H as the VERTEX rule
+ *      has them.  The texel is USABLE when p is finite, p.z >= near, sx and sy are finite and |sx|, |sy| <= 16384; else it stops.  X = (i32) rint(256 sx),
+ *      Y likewise.  Then step 2 of the vertex colours above, verbatim: X', Y', the in-image test (`in_image`), i0, a, i1, j0, b, j1.
+ *   3. OCCLUSION, only with mesh_depth: step 3 of the vertex colours, with p.z for z.  A texel that passes, and every texel in the image when there is no depth
+ *      image, counts in `visible`.
+ *   4. WEIGHT.  Q = Q(p); the texel stops when Q = 0, else counts in `accumulated`.
+ *   5. SAMPLE, integers only: S of step 5 of the vertex colours per channel, and s = (S + 32768) >> 16, a byte.
+ *   6. ADD.  R += Q s_red, G += Q s_green, B += Q s_blue, Wsum += Q.  One view adds at most 256 x 255 to a sum, so no sum can overflow within 65793 views;
+ *      the accumulate that would be the 65536th since the reset is refused.  The row is read and written by the one thread that owns the texel, with one
+ *      16-byte load and one 16-byte store; a texel that stopped never touches its row.
+ * RESOLVE writes every texel of texture rgba8[Ht][Wt] and of state u8[Ht][Wt] (nullable).  A texel nobody owns gets 0x00000000 and state 0.  An owned texel
+ * with Wsum >= max(min_weight, 1) is BAKED: per channel min((R + Wsum / 2) / Wsum, 255), integer divisions, alpha 255, state 1.  With fill != 0 an owned texel
+ * that is not baked and has a baked texel among its up-to-eight neighbours in the same cell that the same face owns is FILLED: per channel (sum + n / 2) / n
+ * over those n neighbours' baked bytes, alpha 255, state 2.  Any other owned texel takes the FALLBACK, alpha 255, state 0:  i'' = min(i', m),
+ * j'' = min(j', m - i''), k'' = m - i'' - j'';  per channel (k'' c0 + i'' c1 + j'' c2 + m / 2) / m with c_k the byte of vertex a_k in colours rgba8[V]
+ * (nullable), 0 without colours or where a_k >= V.
+ * TOTALS: invalid_faces, facing_away_faces, off_image_faces, usable, in_image, visible, accumulated, cumulative over the views since the reset;
+ * viewport_mismatch (calls); and baked, filled, fallback texels of the last resolve.
+ * REFUSALS, with nothing written, tested in this order.  WDGS_E_INVALID at reset: F >= 2^31; C not 4, 8, 16 or 32; Wt above WDGS_MESH_TEXTURE_MAX_SIZE;
+ * a starting count above 65535.  WDGS_E_STATE: layout, accumulate, resolve, read or stats before a reset; num_faces other than the reset's; the 65536th
+ * accumulate; reset, read or stats while recording.  WDGS_E_INVALID: V >= 2^31; W or H outside 1 .. WDGS_MESH_RASTER_MAX_SIZE; near not positive and finite;
+ * depth_tolerance not finite or < 0; min_cos outside [0, 1] or NaN; a null camera, image, faces (F > 0), vertices (F, V > 0) or texture output (F > 0); a
+ * pointer that is not 4-byte aligned. */
+#define WDGS_MESH_TEXTURE_MAX_SIZE 16384u
+typedef struct wdgs_mesh_texture_baker wdgs_mesh_texture_baker;
+int wdgs_mesh_texture_baker_create(wdgs_device* dev, wdgs_mesh_texture_baker** out);
+int wdgs_mesh_texture_baker_destroy(wdgs_mesh_texture_baker* baker);
+/* Sizes the state for num_faces faces in cells of `cell` texels -- 16 bytes per texel of a used cell, grown as needed and reused -- and zeroes it and the
+ * totals.  `accumulates` is where the count of accumulates starts: 0, except in a test of the refusal of the 65536th.  A call that grows the array waits once.
+ * Cannot be recorded (WDGS_E_STATE). */
+int wdgs_mesh_texture_baker_reset(wdgs_mesh_texture_baker* baker, uint32_t num_faces, uint32_t cell, uint32_t accumulates);
+/* Wt, Ht and cells_per_row of the last reset, each pointer nullable.  No device work. */
+int wdgs_mesh_texture_baker_layout(wdgs_mesh_texture_baker* baker, uint32_t* width, uint32_t* height, uint32_t* cells_per_row);
+/* One view, as defined above.  Stream-ordered, no host wait, no allocation, recordable (a recorded call counts once, when recorded; a replay is one more
+ * view).  The count of accumulates is host arithmetic on the calls made, so REPLAYS ESCAPE THE OVERFLOW GUARD: a command buffer that holds an accumulate and is
+ * submitted some 65 000 times without a reset can wrap the u32 sums silently; whoever replays one that often counts the views themselves.  The kernel's event
+ * time is the device's (wdgs_device_get_kernel_times): mesh_texture_accumulate. */
+int wdgs_mesh_texture_baker_accumulate(wdgs_mesh_texture_baker* baker, const void* vertices_f32_dev, uint32_t num_vertices, const void* faces_u32_dev,
+                                       uint32_t num_faces, const void* camera_dev, const void* image_rgba8_dev, const void* mesh_depth_f32_dev, uint32_t width,
+                                       uint32_t height, float near, float depth_tolerance, float min_cos, uint32_t two_sided);
+/* texture_out rgba8[Ht Wt] and state_out u8[Ht Wt] (nullable) from the state as of this call; colours rgba8[V] nullable.  Stream-ordered, no host wait,
+ * recordable.  Kernel: mesh_texture_resolve. */
+int wdgs_mesh_texture_baker_resolve(wdgs_mesh_texture_baker* baker, const void* faces_u32_dev, uint32_t num_faces, uint32_t num_vertices,
+                                    const void* colours_rgba8_dev, void* texture_out_rgba8_dev, void* state_out_u8_dev, uint32_t min_weight, uint32_t fill);
+/* Copies the state to host memory: rows_out u32[cells C C][4] (nullable).  Waits, so it cannot be recorded. */
+int wdgs_mesh_texture_baker_read(wdgs_mesh_texture_baker* baker, uint32_t* rows_out);
+/* The eleven totals, in the order of TOTALS above, into totals_out u64[11].  Copies one block back and waits, so it cannot be recorded. */
+int wdgs_mesh_texture_baker_stats(wdgs_mesh_texture_baker* baker, uint64_t* totals_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ WDGS_OK, WDGS_E_INVALID, WDGS_E_HIP, WDGS_E_CAPACITY, WDGS_E_STATE = 0, -1, -2, 
 # include/webdgs.h, mesh rasterization: a face whose bounding box exceeds this many pixels on either axis takes the kernel of 8 x 8 blocks
 MESH_RASTER_LARGE_FACE_PIXELS = 8   # WDGS_MESH_RASTER_LARGE_FACE_PIXELS
 MESH_RASTER_MAX_SIZE = 8192          # WDGS_MESH_RASTER_MAX_SIZE
+MESH_TEXTURE_MAX_SIZE = 16384        # WDGS_MESH_TEXTURE_MAX_SIZE
 
 
 class WdgsError(RuntimeError):
@@ -215,6 +216,14 @@ SIGNATURES = {
     "wdgs_mesh_colour_baker_resolve": (_I, [_P, _P, _P, _P, _U, _U, C.c_uint64]),
     "wdgs_mesh_colour_baker_read": (_I, [_P, _P, _P]),
     "wdgs_mesh_colour_baker_stats": (_I, [_P] + [C.POINTER(C.c_uint64)] * 6),
+    "wdgs_mesh_texture_baker_create": (_I, [_P, C.POINTER(_P)]),
+    "wdgs_mesh_texture_baker_destroy": (_I, [_P]),
+    "wdgs_mesh_texture_baker_reset": (_I, [_P, _U, _U, _U]),
+    "wdgs_mesh_texture_baker_layout": (_I, [_P, C.POINTER(_U), C.POINTER(_U), C.POINTER(_U)]),
+    "wdgs_mesh_texture_baker_accumulate": (_I, [_P, _P, _U, _P, _U, _P, _P, _P, _U, _U, _F, _F, _F, _U]),
+    "wdgs_mesh_texture_baker_resolve": (_I, [_P, _P, _U, _U, _P, _P, _P, _U, _U]),
+    "wdgs_mesh_texture_baker_read": (_I, [_P, _P]),
+    "wdgs_mesh_texture_baker_stats": (_I, [_P, C.POINTER(C.c_uint64)]),
     "wdgs_point_index_create":(_I, [_P, _P, C.c_uint64, _F, C.POINTER(_P)]),
     "wdgs_point_index_destroy": (_I, [_P]),
     "wdgs_point_index_reserve_queries": (_I, [_P, _U]),

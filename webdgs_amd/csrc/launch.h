@@ -138,6 +138,16 @@ int launch_mesh_bake_accumulate(wdgs_device* dev, const float* vertices, const f
 int launch_mesh_bake_resolve(wdgs_device* dev, u32 V, const unsigned long long* sums, const u32* views, u32 min_views, unsigned long long min_weight, const u32* fallback,
                              u32* colours_out, unsigned char* baked_out, unsigned long long* totals);
 
+// ---- meshtexture.hip.  cell: 4, 8, 16 or 32; vertices f32[V][3], faces u32[F][3]; image rgba8[W H]; mesh_depth (nullable) f32[W H]; rows
+// u32[ceil(F / 2) cell cell][4] = { R, G, B, Wsum }, cell-major, added to; totals: the object's block of partial sums (meshtexture.hip lays it out), added to
+int launch_mesh_texture_accumulate(wdgs_device* dev, u32 cell, const float* vertices, u32 V, const u32* faces, u32 F, const float* camera, const u32* image,
+                                   const float* mesh_depth, u32 W, u32 H, float near, float depth_tolerance, float min_cos, u32 two_sided, u32* rows,
+                                   unsigned long long* totals);
+// texture_out rgba8 and state_out u8 (nullable) of cells_per_row cell by atlas_rows cell texels, every one written; colours rgba8[V] nullable; the baked, filled
+// and fallback texels are counted into totals' second half, cleared first
+int launch_mesh_texture_resolve(wdgs_device* dev, u32 cell, const u32* rows, const u32* faces, u32 F, u32 V, const u32* colours, u32 cells_per_row, u32 atlas_rows,
+                                u32 min_weight, u32 fill, u32* texture_out, unsigned char* state_out, unsigned long long* totals);
+
 // ---- keysort.hip: the stable u64 key sort the welder (meshweld.hip) and the simplifier (meshsimplify.hip) group by; its sizing rule: keysort_sizes.h
 // The counters block, u32 words: the distinct keys, the passes run, the buffer that holds the sorted pairs, a spare, then per pass: run, input buffer, output buffer
 constexpr u32 KS_C_TOTAL = 0, KS_C_PASSES = 1, KS_C_FINAL = 2, KS_C_RUN = 4, KS_C_IN = 12, KS_C_OUT = 20, KS_C_WORDS = 28;

@@ -381,6 +381,25 @@ class Evaluator:
         out["views"] = ids
         return out
 
+    # ------------------------------------------------------------------ a texture atlas from the photographs
+    def bakeMeshTexture(self, mesh: dict, viewIds: Optional[list] = None, split: str = "train", **options) -> dict:
+        """``mesh`` with a texture atlas taken from the split's photographs under the split's cameras: ``ops.bakeTexture`` over the device copies the
+        trainer holds, with its ``options`` (``cell``, ``depthTolerance``, ``minCos``, ``minWeight``, ``near``, ``occlusion``, ``twoSided``, ``fill``,
+        ``asBuffers``) and its result -- ``texture``, ``uv``, ``texelState``, ``textureStats`` and the atlas's sizes added to the mesh dict -- with ``views``
+        added.  The views may differ in size.  ``loaders.saveMeshOBJ`` writes the result.
+
+        Nothing is rendered through the model, as with ``bakeMeshColours``: the pipeline is drained and that is all."""
+        known = ("cell", "depthTolerance", "minCos", "minWeight", "near", "occlusion", "twoSided", "fill", "asBuffers")
+        unknown = sorted(set(options) - set(known))
+        if unknown:
+            raise TypeError(f"bakeMeshTexture: unknown options {unknown} (bakeTexture's: {sorted(known)})")
+        cams, imgs, bufs, ids = self._views("bakeMeshTexture", viewIds, split)
+        self._drain()
+        views = [(bufs[v], imgs[v]["texture"], int(imgs[v]["width"]), int(imgs[v]["height"])) for v in ids]
+        out = ops.bakeTextureFromViews(self.device, mesh, views, what="bakeMeshTexture", **options)
+        out["views"] = ids
+        return out
+
     # ------------------------------------------------------------------ TSDF fusion and mesh extraction (DESIGN.md section 13)
     def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
         """Fuses the current model's depth maps into ``volume``: for each view in the order given, the forward pass, rasterize,
@@ -405,7 +424,7 @@ class Evaluator:
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
                     keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", simplify: Optional[float] = None,
-                    smooth: Optional[int] = None, normals: bool = False, cull: Optional[dict] = None, bake=None, **volumeOptions) -> dict:
+                    smooth: Optional[int] = None, normals: bool = False, cull: Optional[dict] = None, bake=None, texture=None, **volumeOptions) -> dict:
         """The current model as a triangle mesh of the box ``[lo, hi]``: ``ops.TSDFVolume.fromBounds(lo, hi, voxelSize, **volumeOptions)``,
         ``fuseDepth`` over the views, ``extractMesh(minWeight)``; the volume is destroyed.  ``loaders.saveMeshPLY`` writes the result.
 
@@ -437,9 +456,18 @@ class Evaluator:
         ``bake=True`` or ``bake=dict(...)``: the final mesh -- after ``simplify`` -- gets its vertex colours from the photographs by
         ``bakeMeshColours(mesh, **bake)``, with ``viewIds`` and ``split`` defaulting to the extraction's own; ``colours`` is replaced and ``baked``,
         ``bakeStats`` (the baker's totals; ``stats`` stays the smoother's or the simplifier's) and ``views`` are added.  The weights are the final mesh's vertex normals, computed
-        for that even when ``normals=False`` (no ``normals`` key is added then).  ``None``: as before, no new key and nothing more launched."""
+        for that even when ``normals=False`` (no ``normals`` key is added then).  ``None``: as before, no new key and nothing more launched.
+
+        ``texture=True`` or ``texture=dict(...)``: last of all -- after ``bake`` -- the mesh gets a texture atlas from the photographs
+        by ``bakeMeshTexture(mesh, **texture)``, with ``viewIds`` and ``split`` defaulting to the extraction's own; ``texture``, ``uv``, ``texelState``,
+        ``textureStats``, ``textureWidth``, ``textureHeight``, ``textureCell`` and ``views`` are added and no other key changes.  ``None``: as before, no new
+        key and nothing more launched."""
         if weld not in ("host", "device"):
             raise ValueError(f"extractMesh: weld must be 'host' or 'device', not {weld!r}")
+        if texture is not None and texture is not False:
+            mesh = self.extractMesh(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld=weld, simplify=simplify,
+                                    smooth=smooth, normals=normals, cull=cull, bake=bake, **volumeOptions)
+            return self.bakeMeshTexture(mesh, **dict(dict(viewIds=viewIds, split=split), **({} if texture is True else texture)))
         if bake is not None and bake is not False:
             mesh = self.extractMesh(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld=weld, simplify=simplify,
                                     smooth=smooth, normals=normals, cull=cull, **volumeOptions)

@@ -399,6 +399,91 @@ def loadMeshPLY(path: str) -> dict:
     return out
 
 
+def saveMeshOBJ(path: str, mesh: dict) -> None:
+    """A textured mesh -- ``ops.bakeTexture``'s dict: ``vertices f32[V,3]``, ``faces u32[F,3]``, ``uv f32[F,3,2]``, ``texture u8[Ht,Wt,4]`` and optionally
+    ``normals f32[V,3]`` -- as ``name.obj`` (``path``), ``name.mtl`` and ``name.png`` beside it: one ``v`` (and ``vn``) per vertex, one ``vt`` per face
+    corner, ``f a/ta b/tb c/tc`` (``a/ta/a`` with normals) under one ``usemtl``; the PNG through ``viewer.encodePNG``.  Floats are written with nine
+    significant digits, which is what a float32 needs: ``loadMeshOBJ`` reads all of it back exactly."""
+    from .viewer import encodePNG
+    if not path.endswith(".obj"):
+        raise ValueError(f"saveMeshOBJ: {path!r} does not end in .obj")
+    v = np.ascontiguousarray(mesh["vertices"], np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(mesh["faces"], np.uint32).reshape(-1, 3)
+    uv = np.ascontiguousarray(mesh["uv"], np.float32)
+    texture = np.ascontiguousarray(mesh["texture"], np.uint8)
+    n = mesh.get("normals")
+    if uv.shape != (f.shape[0], 3, 2) or texture.ndim != 3 or texture.shape[2] != 4:
+        raise ValueError(f"saveMeshOBJ: uv of shape {uv.shape} and a texture of shape {texture.shape} for {f.shape[0]} faces")
+    if f.size and int(f.max()) >= v.shape[0]:
+        raise ValueError("saveMeshOBJ: a face names a vertex the mesh does not have")
+    stem = path[:-4]
+    name = stem.replace("\\", "/").rsplit("/", 1)[-1]
+    lines = [f"mtllib {name}.mtl"]
+    lines += ["v %.9g %.9g %.9g" % tuple(map(float, p)) for p in v]
+    if n is not None:
+        n = np.ascontiguousarray(n, np.float32).reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise ValueError(f"saveMeshOBJ: {v.shape[0]} vertices, {n.shape[0]} normals")
+        lines += ["vn %.9g %.9g %.9g" % tuple(map(float, p)) for p in n]
+    lines += ["vt %.9g %.9g" % tuple(map(float, t)) for t in uv.reshape(-1, 2)]
+    lines.append("usemtl baked")
+    corner = "%d/%d/%d" if n is not None else "%d/%d"
+    for k, face in enumerate(f):
+        lines.append("f " + " ".join(corner % ((int(a) + 1, 3 * k + c + 1, int(a) + 1) if n is not None else (int(a) + 1, 3 * k + c + 1)) for c, a in enumerate(face)))
+    with open(path, "w", encoding="ascii", newline="\n") as fh:
+        fh.write("\n".join(lines) + "\n")
+    with open(stem + ".mtl", "w", encoding="ascii", newline="\n") as fh:
+        fh.write(f"newmtl baked\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+    with open(stem + ".png", "wb") as fh:
+        fh.write(encodePNG(texture))
+
+
+def loadMeshOBJ(path: str) -> dict:
+    """Reads an OBJ as ``saveMeshOBJ`` writes it, with the PNG its MTL names: ``dict(vertices f32[V,3], faces u32[F,3], uv f32[F,3,2], texture u8[Ht,Wt,4])``
+    and ``normals f32[V,3]`` when the file has ``vn``."""
+    from .images import decodePNG
+    with open(path, "r", encoding="ascii") as fh:
+        lines = fh.read().split("\n")
+    v, vn, vt, faces, corners, mtl = [], [], [], [], [], None
+    for ln in lines:
+        w = ln.split()
+        if not w:
+            continue
+        if w[0] == "v":
+            v.append([float(x) for x in w[1:4]])
+        elif w[0] == "vn":
+            vn.append([float(x) for x in w[1:4]])
+        elif w[0] == "vt":
+            vt.append([float(x) for x in w[1:3]])
+        elif w[0] == "f":
+            if len(w) != 4:
+                raise ValueError("loadMeshOBJ: only triangles are read")
+            parts = [c.split("/") for c in w[1:]]
+            faces.append([int(p[0]) - 1 for p in parts])
+            corners.append([int(p[1]) - 1 for p in parts])
+        elif w[0] == "mtllib":
+            mtl = w[1]
+    if mtl is None:
+        raise ValueError("loadMeshOBJ: not a mesh as saveMeshOBJ writes it (no mtllib)")
+    folder = path.replace("\\", "/").rsplit("/", 1)[0] + "/" if "/" in path.replace("\\", "/") else ""
+    image = None
+    with open(folder + mtl, "r", encoding="ascii") as fh:
+        for ln in fh.read().split("\n"):
+            w = ln.split()
+            if w[:1] == ["map_Kd"]:
+                image = w[1]
+    if image is None:
+        raise ValueError("loadMeshOBJ: the material names no texture")
+    with open(folder + image, "rb") as fh:
+        texture = decodePNG(fh.read())
+    uv_all = np.array(vt, np.float32).reshape(-1, 2)
+    out = dict(vertices=np.array(v, np.float32).reshape(-1, 3), faces=np.array(faces, np.uint32).reshape(-1, 3),
+               uv=np.ascontiguousarray(uv_all[np.array(corners, np.int64).reshape(-1, 3)]) if faces else np.zeros((0, 3, 2), np.float32), texture=texture)
+    if vn:
+        out["normals"] = np.array(vn, np.float32).reshape(-1, 3)
+    return out
+
+
 # ----------------------------------------------------------------------------- point sets (no reference counterpart)
 _PLY_SCALAR = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2", "int": "<i4", "int32": "<i4",
                "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}

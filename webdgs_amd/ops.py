@@ -2361,6 +2361,216 @@ def bakeVertexColours(device: HipDevice, mesh: dict, cameras, images, width: int
             b.destroy()
 
 
+# ----------------------------------------------------------------------------- a texture atlas baked from photographs
+TEXTURE_STATS = ("invalidFaces", "facingAwayFaces", "offImageFaces", "usable", "inImage", "visible", "accumulated", "viewportMismatch", "bakedTexels",
+                 "filledTexels", "fallbackTexels")
+TEXTURE_CELLS = (4, 8, 16, 32)
+
+
+def textureLayout(numFaces: int, cell: int = 8) -> dict:
+    """The atlas of ``numFaces`` faces in square cells of ``cell`` texels, two faces per cell (include/webdgs.h states it): ``dict(width, height, cellsPerRow,
+    uv f32[F, 3, 2])`` with the per-corner texture coordinates in the OBJ convention -- ``u = (x + 0.5) / width``, ``v = 1 - (y + 0.5) / height`` for the
+    atlas texel ``(x, y)`` a corner sits on, computed in doubles and rounded once.  Arithmetic in ``(numFaces, cell)`` alone; no device work."""
+    F, c = int(numFaces), int(cell)
+    if not 0 <= F < 2 ** 31:
+        raise ValueError(f"textureLayout: {numFaces} faces (0 to 2^31 - 1)")
+    if c not in TEXTURE_CELLS:
+        raise ValueError(f"textureLayout: a cell of {cell} texels (4, 8, 16 or 32)")
+    cells = (F + 1) // 2
+    per_row = math.isqrt(cells)
+    if per_row * per_row < cells:
+        per_row += 1
+    rows = -(-cells // per_row) if per_row else 0
+    width, height = per_row * c, rows * c
+    if width > _lib.MESH_TEXTURE_MAX_SIZE:
+        raise ValueError(f"textureLayout: {F} faces in cells of {c} texels need an atlas {width} texels wide (at most {_lib.MESH_TEXTURE_MAX_SIZE})")
+    m = c - 3
+    f = np.arange(F, dtype=np.int64)
+    k, odd = f // 2, (f % 2)[:, None, None]
+    corner = np.array([[0, 0], [m, 0], [0, m]], np.int64)[None]          # (i', j') of v0, v1, v2
+    local = np.where(odd == 1, c - 1 - corner, corner)                    # (i, j) in the cell: the odd face's chart is turned by 180 degrees
+    x = ((k % max(per_row, 1)) * c)[:, None] + local[:, :, 0]
+    y = ((k // max(per_row, 1)) * c)[:, None] + local[:, :, 1]
+    uv = np.stack([(x + 0.5) / max(width, 1), 1.0 - (y + 0.5) / max(height, 1)], axis=2).astype(np.float32)
+    return dict(width=width, height=height, cellsPerRow=per_row, uv=uv)
+
+
+class MeshTextureBaker:
+    """Per-texel colour sums of a mesh's texture atlas over views (``wdgs_mesh_texture_baker``): ``reset`` lays the atlas out for a face count and a cell
+    size and zeroes the sums, ``accumulate`` adds one view -- a photograph, its camera block and, optionally, the depth image ``MeshRasterizer.encode`` wrote
+    for this mesh and camera (the occlusion test) -- ``resolve`` turns the sums into an rgba8 texture, ``read`` hands out the sums and ``stats`` the totals.
+    Integer sums: the state does not depend on the order of the views and every byte is a function of the inputs (include/webdgs.h states the
+    definition).  ``bakeTexture`` is the one-call form."""
+
+    def __init__(self, device: HipDevice):
+        self.device = device
+        self.destroyed = False
+        self.numFaces = self.cell = self.width = self.height = self.cellsPerRow = 0
+        h = C.c_void_p()
+        check(device.lib.wdgs_mesh_texture_baker_create(device.handle, C.byref(h)))
+        self.handle = h
+
+    def reset(self, numFaces: int, cell: int = 8, _accumulates: int = 0) -> dict:
+        """Lays the atlas out and zeroes the state; returns ``layout()``.  A call that grows the array waits once; it cannot be recorded.  ``_accumulates``
+        is where the count of views starts, for the test of the refusal of the 65536th."""
+        if not (0 <= int(numFaces) < 2 ** 32 and 0 <= int(cell) < 2 ** 32 and 0 <= int(_accumulates) < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshTextureBaker.reset: bad counts {numFaces}, {cell}, {_accumulates}")
+        check(self.device.lib.wdgs_mesh_texture_baker_reset(self.handle, int(numFaces), int(cell), int(_accumulates)))
+        self.numFaces, self.cell = int(numFaces), int(cell)
+        return self.layout()
+
+    def layout(self) -> dict:
+        """``dict(width, height, cellsPerRow)`` of the last reset (``textureLayout`` gives the same, and the texture coordinates)."""
+        w, h, r = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(self.device.lib.wdgs_mesh_texture_baker_layout(self.handle, C.byref(w), C.byref(h), C.byref(r)))
+        self.width, self.height, self.cellsPerRow = int(w.value), int(h.value), int(r.value)
+        return dict(width=self.width, height=self.height, cellsPerRow=self.cellsPerRow)
+
+    def accumulate(self, vertices: Optional[HipBuffer], numVertices: int, faces: Optional[HipBuffer], numFaces: int, camera: HipBuffer, image: Optional[HipBuffer],
+                   width: int, height: int, meshDepth: Optional[HipBuffer] = None, near: float = MESH_RASTER_NEAR, depthTolerance: float = 0.05, minCos: float = 0.1,
+                   twoSided: bool = False) -> None:
+        """One view of ``width`` x ``height``.  A texel is coloured by this view when its point on the face projects into the image, all four depth texels
+        round it are within ``depthTolerance`` of its own depth, and the cosine between the face's normal and the direction to the camera is at least
+        ``minCos``; the view's weight is that cosine.  Stream-ordered, recordable."""
+        nv, nf, w, h = int(numVertices), int(numFaces), int(width), int(height)
+        if not (0 <= nv < 2 ** 32 and 0 <= nf < 2 ** 32 and 0 <= w < 2 ** 32 and 0 <= h < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshTextureBaker.accumulate: bad counts {numVertices}, {numFaces}, {width}x{height}")
+        if (nv < 2 ** 31 and vertices is not None and vertices.size < 12 * nv) or (nf < 2 ** 31 and faces is not None and faces.size < 12 * nf):
+            raise ValueError("MeshTextureBaker.accumulate: buffers too small for the mesh")
+        if camera is not None and camera.size < 272:
+            raise ValueError("MeshTextureBaker.accumulate: the camera block has 68 floats")
+        if 1 <= w <= _lib.MESH_RASTER_MAX_SIZE and 1 <= h <= _lib.MESH_RASTER_MAX_SIZE:
+            for b in (image, meshDepth):
+                if b is not None and b.size < 4 * w * h:
+                    raise ValueError(f"MeshTextureBaker.accumulate: an image is too small for {w}x{h}")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_texture_baker_accumulate(self.handle, ptr(vertices), nv, ptr(faces), nf, ptr(camera), ptr(image), ptr(meshDepth), w, h, float(near),
+                                                                 float(depthTolerance), float(minCos), 1 if twoSided else 0))
+
+    def resolve(self, faces: Optional[HipBuffer], numFaces: int, numVertices: int, textureOut: Optional[HipBuffer], colours: Optional[HipBuffer] = None,
+                stateOut: Optional[HipBuffer] = None, minWeight: int = 1, fill: bool = True) -> None:
+        """``textureOut`` rgba8[height][width] from the current sums: a texel with a weight sum of at least ``minWeight`` (a view adds at most 256) gets its
+        weighted mean; with ``fill`` any other texel next to such texels of its own face gets their mean; the rest the mesh's vertex ``colours``
+        rgba8[numVertices] (zeros without) interpolated over the face.  ``stateOut`` u8[height][width]: 1 baked, 2 filled, 0 otherwise.  Stream-ordered,
+        recordable."""
+        nf, nv = int(numFaces), int(numVertices)
+        if not (0 <= nf < 2 ** 32 and 0 <= nv < 2 ** 32 and 0 <= int(minWeight) < 2 ** 32):
+            raise _lib.WdgsError(_lib.WDGS_E_INVALID, f"MeshTextureBaker.resolve: bad counts {numFaces}, {numVertices}, {minWeight}")
+        n = self.width * self.height
+        if (textureOut is not None and textureOut.size < 4 * n) or (stateOut is not None and stateOut.size < n):
+            raise ValueError(f"MeshTextureBaker.resolve: an output is too small for {self.width}x{self.height}")
+        if (nf < 2 ** 31 and faces is not None and faces.size < 12 * nf) or (nv < 2 ** 31 and colours is not None and colours.size < 4 * nv):
+            raise ValueError("MeshTextureBaker.resolve: buffers too small for the mesh")
+        ptr = lambda b: b.ptr if b is not None else None
+        check(self.device.lib.wdgs_mesh_texture_baker_resolve(self.handle, ptr(faces), nf, nv, ptr(colours), ptr(textureOut), ptr(stateOut), int(minWeight), 1 if fill else 0))
+
+    def read(self) -> np.ndarray:
+        """The sums ``u32[cells * cell * cell, 4] = {R, G, B, Wsum}``, cell-major: texel ``(i, j)`` of cell ``k`` is row ``k cell^2 + j cell + i`` (waits)."""
+        rows = np.zeros((((self.numFaces + 1) // 2) * self.cell * self.cell, 4), np.uint32)
+        check(self.device.lib.wdgs_mesh_texture_baker_read(self.handle, rows.ctypes.data))
+        return rows
+
+    def stats(self) -> dict:
+        """``TEXTURE_STATS``: the faces each face-level test stopped and the texels that passed each step, summed over the views since the reset; the calls
+        whose camera block was of another image size; the baked, filled and fallback texels of the last resolve (waits)."""
+        v = (C.c_uint64 * len(TEXTURE_STATS))()
+        check(self.device.lib.wdgs_mesh_texture_baker_stats(self.handle, v))
+        return dict(zip(TEXTURE_STATS, (int(x) for x in v)))
+
+    def destroy(self) -> None:
+        if self.destroyed:
+            return
+        self.destroyed = True
+        self.device.lib.wdgs_mesh_texture_baker_destroy(self.handle)
+        self.handle = None
+
+
+def bakeTextureFromViews(device: HipDevice, mesh: dict, views: list, cell: int = 8, depthTolerance: float = 0.05, minCos: float = 0.1, minWeight: int = 1,
+                         near: float = MESH_RASTER_NEAR, occlusion: bool = True, twoSided: bool = False, fill: bool = True, asBuffers: bool = False,
+                         what: str = "bakeTexture") -> dict:
+    """``bakeTexture`` for views that are on the device already: ``views`` is a list of ``(camera, image, width, height)`` with ``HipBuffer``s, which may
+    differ in size.  As ``bakeMeshFromViews`` does, the rasterizer is grown once, to the largest view, before the loop; per view one encode (with
+    ``occlusion``) and one accumulate; then one resolve."""
+    vertices, faces, V, F, own = _mesh_on_device(device, mesh, what)
+    owned = [vertices, faces] if own else []
+    baker = rasterizer = depth = None
+    out = {}
+    try:
+        colours, own_colours = _mesh_colours_on_device(device, mesh, V, own, what)
+        if own_colours:
+            owned.append(colours)
+        layout = textureLayout(F, cell)
+        sizes = [(int(w), int(h)) for _, _, w, h in views]
+        legal = [(w, h) for w, h in sizes if 1 <= w <= _lib.MESH_RASTER_MAX_SIZE and 1 <= h <= _lib.MESH_RASTER_MAX_SIZE]
+        baker = MeshTextureBaker(device)
+        baker.reset(F, cell)
+        if occlusion and legal:
+            w, h = max(legal, key=lambda s: s[0] * s[1])
+            depth = device.createBuffer(4 * w * h, "mesh depth")
+            rasterizer = MeshRasterizer(device)
+            rasterizer.encode(vertices, V, faces, F, None, views[sizes.index((w, h))][0], w, h, near, "none", depth=depth)
+        for (camera, image, _, _), (w, h) in zip(views, sizes):
+            if rasterizer is not None and (w, h) in legal:
+                rasterizer.encode(vertices, V, faces, F, None, camera, w, h, near, "none", depth=depth)
+            baker.accumulate(vertices, V, faces, F, camera, image, w, h, depth if occlusion else None, near, depthTolerance, minCos, twoSided)
+        Wt, Ht = layout["width"], layout["height"]
+        out = dict(texture=device.createBuffer(4 * max(Wt * Ht, 1), "baked texture"), texelState=device.createBuffer(max(Wt * Ht, 1), "texel state"))
+        baker.resolve(faces, F, V, out["texture"], colours, out["texelState"], minWeight, fill)
+        stats = baker.stats()   # (waits: the objects released below are idle)
+        extra = dict(uv=layout["uv"], textureWidth=Wt, textureHeight=Ht, textureCell=int(cell), textureStats=stats)
+        if asBuffers:
+            result, out = dict(mesh, **out, **extra), {}
+            return result
+        return dict(mesh, texture=out["texture"].read(np.uint8, count=4 * Wt * Ht).reshape(Ht, Wt, 4),
+                    texelState=out["texelState"].read(np.uint8, count=Wt * Ht).reshape(Ht, Wt), **extra)
+    finally:
+        device.synchronize()
+        for o in (baker, rasterizer, depth):
+            if o is not None:
+                o.destroy()
+        destroyBuffers(out)
+        for b in owned:
+            b.destroy()
+
+
+def bakeTexture(device: HipDevice, mesh: dict, cameras, images, width: int, height: int, cell: int = 8, depthTolerance: float = 0.05, minCos: float = 0.1,
+                minWeight: int = 1, near: float = MESH_RASTER_NEAR, occlusion: bool = True, twoSided: bool = False, fill: bool = True, asBuffers: bool = False) -> dict:
+    """``mesh`` with a texture atlas taken from photographs, without a model.  Every face gets its own small chart -- two faces share a square cell of
+    ``cell`` texels (4, 8, 16 or 32), ``textureLayout`` -- so the detail the photographs hold between two vertices survives ``simplifyMesh``.  Per ``camera``
+    (68-float blocks, numpy or ``HipBuffer``) and its ``image`` (rgba8 ``[height, width, 4]`` numpy, or a ``HipBuffer``) the mesh's depth image is
+    rasterized (``occlusion``) and every texel whose point on its face projects into the photograph, is not hidden and faces the camera (``twoSided``:
+    either way) adds the bilinear sample there, weighted by the cosine between the face's normal and the direction to the camera.  A texel with a weight
+    sum of at least ``minWeight`` (256 per view that looks straight at it) gets the weighted mean; with ``fill`` an unseen texel next to seen ones of its
+    face gets their mean; any other the mesh's vertex colours interpolated (zeros for a mesh without colours).
+
+    Returns the mesh dict with ``texture`` u8[Ht, Wt, 4] (row 0 at the top; texels no face owns are zero), ``uv`` f32[F, 3, 2] per face corner (the OBJ
+    convention: ``loaders.saveMeshOBJ`` writes both), ``texelState`` u8[Ht, Wt] (1 baked, 2 filled, 0 otherwise), ``textureWidth``, ``textureHeight``,
+    ``textureCell`` and ``textureStats`` (``MeshTextureBaker.stats``) added; ``asBuffers``: ``texture`` and ``texelState`` stay on the device as
+    ``HipBuffer`` the caller destroys.  A function of its arguments alone, bit for bit."""
+    cameras, images = list(cameras), list(images)
+    if len(cameras) != len(images):
+        raise ValueError(f"bakeTexture: {len(cameras)} cameras for {len(images)} images")
+    w, h = int(width), int(height)
+    owned, views = [], []
+    try:
+        for camera, image in zip(cameras, images):
+            cam, own_cam = _camera_on_device(device, camera, "bakeTexture")
+            if own_cam:
+                owned.append(cam)
+            if not isinstance(image, HipBuffer):
+                a = np.ascontiguousarray(image, np.uint8)
+                if a.size != 4 * w * h:
+                    raise ValueError(f"bakeTexture: an image of shape {a.shape} for {w}x{h} rgba8")
+                image = device.bufferFrom(a, "bakeTexture: image")
+                owned.append(image)
+            views.append((cam, image, w, h))
+        return bakeTextureFromViews(device, mesh, views, cell, depthTolerance, minCos, minWeight, near, occlusion, twoSided, fill, asBuffers)
+    finally:
+        device.synchronize()
+        for b in owned:
+            b.destroy()
+
+
 class PointIndex:
     """A uniform grid over ``points`` ([M,3] float32 as numpy, or a ``HipBuffer``) for exact nearest-point queries under a cutoff (``wdgs_point_index``).
     ``cellSize`` is a speed parameter only -- no result depends on it; ``None``: chosen by the first query (its cutoff, or less for many points), which then

@@ -884,19 +884,24 @@ class Trainer:
         """``Evaluator.bakeMeshColours``: a mesh with its vertex colours taken from the split's photographs under the split's cameras."""
         return self.evaluator.bakeMeshColours(mesh, viewIds, split, **options)
 
+    def bakeMeshTexture(self, mesh: dict, viewIds: Optional[list] = None, split: str = "train", **options) -> dict:
+        """``Evaluator.bakeMeshTexture``: a mesh with a texture atlas taken from the split's photographs under the split's cameras."""
+        return self.evaluator.bakeMeshTexture(mesh, viewIds, split, **options)
+
     def fuseDepth(self, volume: ops.TSDFVolume, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median") -> list:
         """``Evaluator.fuseDepth``: fuses the current model's depth maps into ``volume``."""
         return self.evaluator.fuseDepth(volume, viewIds, split, depthKind)
 
     def extractMesh(self, lo, hi, voxelSize: float, viewIds: Optional[list] = None, split: str = "train", depthKind: str = "median", minWeight: float = 1.0,
                     keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, weld: str = "host", simplify: Optional[float] = None,
-                    smooth: Optional[int] = None, normals: bool = False, cull: Optional[dict] = None, bake=None, **volumeOptions) -> dict:
+                    smooth: Optional[int] = None, normals: bool = False, cull: Optional[dict] = None, bake=None, texture=None, **volumeOptions) -> dict:
         """``Evaluator.extractMesh``: the current model as a triangle mesh of the box ``[lo, hi]``, welded on the host or (``weld="device"``) on the device;
         with ``cull=dict(...)`` without the faces no view sees (``cullMesh``'s rule and options), with ``smooth=iterations`` Taubin-smoothed, with
         ``simplify=cellSize`` then simplified by vertex clustering, with ``normals=True`` given the final mesh's vertex normals, with ``bake=True`` or
-        ``bake=dict(...)`` coloured from the photographs (``bakeMeshColours``' options)."""
+        ``bake=dict(...)`` coloured from the photographs (``bakeMeshColours``' options), with ``texture=True`` or ``texture=dict(...)`` given a texture
+        atlas from them (``bakeMeshTexture``'s options)."""
         return self.evaluator.extractMesh(lo, hi, voxelSize, viewIds, split, depthKind, minWeight, keepLargest, minTriangles, minFraction, weld=weld,
-                                          simplify=simplify, smooth=smooth, normals=normals, cull=cull, bake=bake, **volumeOptions)
+                                          simplify=simplify, smooth=smooth, normals=normals, cull=cull, bake=bake, texture=texture, **volumeOptions)
 
     def evaluateGeometry(self, reference, lo, hi, voxelSize: float, maxDistance: float, threshold: float, density: Optional[float] = None, seed: int = 0,
                          keepLargest: Optional[int] = None, minTriangles: int = 0, minFraction: float = 0.0, **extractMeshOptions) -> dict:
